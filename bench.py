@@ -97,9 +97,24 @@ def parse_args():
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: every rank joins the process group (gloo when no GPU is visible) and rank 0 "
                          "prints which ranks it saw; no compute (what tests/test_bench_launch.py drives on CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run everything reported beside the headline: per-kernel table and roofline (with "
+                         "calibration and the rocprofv3 traffic runs), full-size verification, the other output mode, variants, "
+                         "end-to-end scopes, IndexOn at 1e8, the CPU baseline, and for N > 1 the other exchange modes and the one-GPU "
+                         "reference run.  The --no-* switches above pick among them.  Without --full a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (joined row count, the chain's stream rows and "
+                         "build rows per index, each index's perm) as float64 DIR/<name>.npy; arrays longer than 2^20 at a fixed "
+                         "seeded sample of their subscripts.  One rank, default mode (not --stream, not CPH_BENCH_FORCE_DIST)")
     args = ap.parse_args()
     if args.rows is None:
         args.rows = 1_000_000_000 if args.stream else 100_000_000
+    if not args.full:
+        # a plain run measures the headline and nothing else: every block reported beside it belongs to --full
+        for k in ("no_alternatives", "no_n1", "no_cpu_baseline", "no_index_1e8", "no_verify", "no_positions", "no_e2e", "no_variants",
+                  "no_traffic", "no_calibration"):
+            setattr(args, k, True)
     return args
 
 
@@ -177,7 +192,7 @@ def measure_traffic(kernel_prefix, args):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="cph_pmc_", dir="/tmp")
         cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "pmc", "--",
-               sys.executable, str(ROOT / "bench.py"), "--steps", "2", "--warmup", "1", "--rows", str(args.rows),
+               sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--rows", str(args.rows),
                "--customers", str(args.customers), "--products", str(args.products), "--no-cpu-baseline",
                "--no-index-1e8", "--no-verify", "--no-e2e", "--no-traffic", "--no-positions", "--no-variants", "--extras", os.devnull] + (["--row-ids"] if args.row_ids else [])
         try:
@@ -336,7 +351,8 @@ def compact_line(out, extras_path):
         line["host"] = out["host"]
     if out.get("extras_error"):
         line["extras_error"] = str(out["extras_error"])[:200]
-    line["extras"] = extras_path
+    if extras_path is not None:
+        line["extras"] = extras_path
     # the budget is a hard limit: optional blocks go, in this order, until the line fits
     for drop in ("kernels_avg_ms", "e2e", "host", "csv_parse", "to_csv", "index_plus_join_1e8", "multi_gpu", "index_on_1e8"):
         if len(json.dumps(line)) <= LINE_BUDGET:
@@ -350,6 +366,8 @@ def compact_line(out, extras_path):
 def emit(out, args):
     """Write the full record beside the repo (gpurun_out/bench_extras.json unless --extras says otherwise), then print the ONE
     compact line — last thing on stdout."""
+    if not (args.full or args.extras):   # a plain run keeps nothing beside its line
+        return print_line(out, None)
     path = Path(args.extras) if args.extras else ROOT / "gpurun_out" / "bench_extras.json"
     shown = str(path)
     try:
@@ -361,9 +379,54 @@ def emit(out, args):
             pass
     except OSError as ex:
         shown = f"not written: {type(ex).__name__}: {ex}"[:120]
+    print_line(out, shown)
+
+
+def print_line(out, extras_shown):
     flush_c_stdio()
     sys.stdout.flush()
-    print(json.dumps(_finite(compact_line(out, shown)), allow_nan=False), flush=True)
+    print(json.dumps(_finite(compact_line(out, extras_shown)), allow_nan=False), flush=True)
+
+
+DUMP_SAMPLE, DUMP_SEED = 1 << 20, 20240613
+
+
+def dump_outputs(dirpath, ch, indexes, dev):
+    """--dump-outputs: what the last timed step handed its caller — the chain result (row count, stream row and build row of every
+    index per joined row: sorted positions, or original row ids with --row-ids) and the two indexes (perm: original row at each
+    sorted position) — as float64 DIR/<name>.npy (every value is an integer below 2^53).  An array longer than DUMP_SAMPLE is
+    written at DUMP_SAMPLE subscripts drawn once from a fixed seed and sorted, the same for equal lengths: 8 MB per array, 33 MB
+    at the bench's size."""
+    import numpy as np
+    import torch
+
+    from csvplus_amd.engine import device_view
+
+    def subscripts(n):
+        if n <= DUMP_SAMPLE:
+            return np.arange(n, dtype=np.int64)
+        return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+    def sampled(ptr, n, typestr, owner):
+        sub = subscripts(n)
+        v = device_view(ptr, n, typestr, owner, dev)[torch.from_numpy(sub).to(dev)].cpu().numpy()
+        return (v.view(np.uint32) if typestr == "<i4" else v).astype(np.float64)
+
+    n = ch.nrows
+    p = ch.device_ptrs()
+    arrays = {"joined_rows": np.array([n], dtype=np.float64)}
+    if ch.identity:   # (stream_row is NULL: result row m is stream row probe_base + m)
+        arrays["stream_row"] = (ch.probe_base + subscripts(n)).astype(np.float64)
+    else:
+        arrays["stream_row"] = sampled(p["stream_row"], n, "<i8", ch)
+    for name, ix, q in zip(("customers", "products"), indexes, p["build_row"]):
+        arrays[f"{name}_build_row"] = sampled(q, n, "<i4", ch)
+        arrays[f"{name}_perm"] = sampled(ix.perm_device_ptr(), ix.nrows, "<i4", ix)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
 
 
 def stream_mode(args, eng, dev, rank, world, share_gpu):
@@ -466,6 +529,10 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         fatal("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        fatal("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.stream or os.environ.get("CPH_BENCH_FORCE_DIST") == "1"):
+        fatal("--dump-outputs writes the one-rank default step's results: not with --gpus > 1, --stream or CPH_BENCH_FORCE_DIST=1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))       # plain command: start the ranks ourselves
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -559,8 +626,9 @@ def main():
     shard_rows = [shard_range(args.rows, r, world)[1] - shard_range(args.rows, r, world)[0] for r in range(world)]
     xstats = []                     # cph_dist_join_stats of every step (N > 1)
 
-    def step():
-        # both build sides as one batch (cph_index_build_many): their host round trips are shared
+    def step(keep=None):
+        # both build sides as one batch (cph_index_build_many): their host round trips are shared.  keep (--dump-outputs, last
+        # timed step, one rank): the chain result and the indexes are handed over instead of released
         ia, ib = eng.index_on_many([[d_cust], [d_prod]], unique=True)
         # the chained join straight through the binding (cph_join_chain, results left in HBM): the timed loop holds
         # no torch views of the result — it needs the row count only.  stream_row is NULL when every order joined
@@ -595,6 +663,9 @@ def main():
             n = ch.nrows
         if not step_info:
             step_info["info"] = (ia.info(), ib.info())
+        if keep is not None:
+            keep.extend((ch, ia, ib))
+            return n, step_info["info"]
         ch.release()
         ia.close()
         ib.close()
@@ -607,37 +678,45 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # Per-kernel timing costs stream time (two HIP events = ~10 us per launch, ~25 launches per step), so the timed
-    # region times ONLY its dominant kernel (cph_ctx_profile_only); which one that is, and the per-kernel breakdown
-    # reported in `kernels`, come from fully profiled steps OUTSIDE the timed region.
-    eng.ctx.profile(True)
-    eng.ctx.profile_read(reset=True)
-    step()
-    pick = eng.ctx.profile_read(reset=True)
-    # (among the kernels whose byte model moves at least a megabyte per step: at toy sizes a sampling or bookkeeping kernel can be the
-    # longest launch of a step by timing noise alone, and a roofline over its few kilobytes rounds to 0 — tests/test_bench_launch.py ran
-    # into that once in ten runs.  At the benchmark's size every kernel of the step is far above the bar.)
-    # (k_chain_dense's bytes are modelled by bench.py itself — chain_bytes() below — not by the library's launch record)
-    modelled = {k: v for k, v in pick.items() if v.get("algo_bytes", 0) >= 1e6 or k == "k_chain_dense"}
-    dom_name = max(modelled.items(), key=lambda kv: kv[1]["total_ms"])[0] if modelled else "k_chain_dense"
-    eng.ctx.profile_only(dom_name)
+    if args.full:
+        # Per-kernel timing costs stream time (two HIP events = ~10 us per launch, ~25 launches per step), so the timed
+        # region times ONLY its dominant kernel (cph_ctx_profile_only); which one that is, and the per-kernel breakdown
+        # reported in `kernels`, come from fully profiled steps OUTSIDE the timed region.
+        eng.ctx.profile(True)
+        eng.ctx.profile_read(reset=True)
+        step()
+        pick = eng.ctx.profile_read(reset=True)
+        # (among the kernels whose byte model moves at least a megabyte per step: at toy sizes a sampling or bookkeeping kernel can be the
+        # longest launch of a step by timing noise alone, and a roofline over its few kilobytes rounds to 0 — tests/test_bench_launch.py ran
+        # into that once in ten runs.  At the benchmark's size every kernel of the step is far above the bar.)
+        # (k_chain_dense's bytes are modelled by bench.py itself — chain_bytes() below — not by the library's launch record)
+        modelled = {k: v for k, v in pick.items() if v.get("algo_bytes", 0) >= 1e6 or k == "k_chain_dense"}
+        dom_name = max(modelled.items(), key=lambda kv: kv[1]["total_ms"])[0] if modelled else "k_chain_dense"
+        eng.ctx.profile_only(dom_name)
     sync_all()
     del xstats[:]
+    last = [] if args.dump_outputs else None
     t0 = time.perf_counter()
     joined = 0
-    for _ in range(args.steps):
-        n, info = step()
+    for i in range(args.steps):
+        n, info = step(last if i == args.steps - 1 else None)
         joined = n
     sync_all()
     dt = time.perf_counter() - t0
     xtimed = list(xstats)
-    prof_timed = eng.ctx.profile_read(reset=True)
-    breakdown_steps = 3
-    eng.ctx.profile(True)
-    for _ in range(breakdown_steps):
-        step()
-    prof = eng.ctx.profile_read(reset=True)
-    eng.ctx.profile(False)
+    if last is not None:
+        dump_outputs(args.dump_outputs, last[0], last[1:], dev)
+        for x in last:
+            x.close()
+        del last[:]
+    if args.full:
+        prof_timed = eng.ctx.profile_read(reset=True)
+        breakdown_steps = 3
+        eng.ctx.profile(True)
+        for _ in range(breakdown_steps):
+            step()
+        prof = eng.ctx.profile_read(reset=True)
+        eng.ctx.profile(False)
     per_rank_ms = [dt / args.steps * 1e3]
     if world > 1:
         cdev = "cpu" if share_gpu else dev
@@ -716,12 +795,6 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = total_joined / (dt / args.steps)
 
-    # ---- per-kernel roofline (HIP events recorded by the library on the ctx stream) -------------
-    # algorithmic bytes the library cannot know (value bytes of the input columns) are added here;
-    # the model is documented in DESIGN.md §"Algorithmic bytes".
-    ia_info, ib_info = info
-    K = breakdown_steps   # the `kernels` table comes from the fully profiled steps behind the timed region
-    total_joined_local = joined if world == 1 or args.exchange == "none" else nloc
     # ---- N > 1: where the step went (rank 0's view), and what one GPU needs for the WHOLE stream ----------------
     multi = None
     if world > 1 or force_dist:
@@ -772,128 +845,135 @@ def main():
                                    note="customers table: every rank builds (A) vs rank 0 builds + cph_dist_index_broadcast (B), "
                                         "critical path per rank; 3e10 rows/s build rate; link rate " +
                                         (f"{link} GB/s measured in this run (measured_exchange_rate)" if link else "50 GB/s ASSUMED (one rank: nothing to measure)"))
-    off_c, off_p = cust_id.nbytes_offsets(), prod_id.nbytes_offsets()   # 0 for fixed-width columns
-    off_o = ords["cust_id"].nbytes_offsets() + ords["prod_id"].nbytes_offsets()
-    cust_bytes, prod_bytes = cust_id.nbytes_values(), prod_id.nbytes_values()
-    # Byte models of the fused chain pass, per launch.  Streams: both keys' bytes + offsets in, two
-    # 4-byte results out per joined row (the stream row is implicit).  Lookups:
-    #   original row ids   contract model: one 4-byte table entry per stream row and step (2 * 4 * rows);
-    #                      compulsory ("hbm"): each 4-byte-per-code row table read once
-    #   sorted positions   the rank tables are 8 bytes per 32 codes (2.5 MB + 40 KB here: L2 / LDS resident) and are charged
-    #                      ONCE, in both models — and not at all for an index that fills its code space (states == rows:
-    #                      the position of a key is its code, the kernel looks nothing up).  Round 3 still charged
-    #                      2 * 4 * rows here, 0.8 GB that never left the L2.
-    stream_bytes = host_bytes["cust_id"] + host_bytes["prod_id"] + off_o
-    out_bytes = 8 * total_joined_local
+    if args.full:
+        # ---- per-kernel roofline (HIP events recorded by the library on the ctx stream) -------------
+        # algorithmic bytes the library cannot know (value bytes of the input columns) are added here;
+        # the model is documented in DESIGN.md §"Algorithmic bytes".
+        ia_info, ib_info = info
+        K = breakdown_steps   # the `kernels` table comes from the fully profiled steps behind the timed region
+        total_joined_local = joined if world == 1 or args.exchange == "none" else nloc
+        off_c, off_p = cust_id.nbytes_offsets(), prod_id.nbytes_offsets()   # 0 for fixed-width columns
+        off_o = ords["cust_id"].nbytes_offsets() + ords["prod_id"].nbytes_offsets()
+        cust_bytes, prod_bytes = cust_id.nbytes_values(), prod_id.nbytes_values()
+        # Byte models of the fused chain pass, per launch.  Streams: both keys' bytes + offsets in, two
+        # 4-byte results out per joined row (the stream row is implicit).  Lookups:
+        #   original row ids   contract model: one 4-byte table entry per stream row and step (2 * 4 * rows);
+        #                      compulsory ("hbm"): each 4-byte-per-code row table read once
+        #   sorted positions   the rank tables are 8 bytes per 32 codes (2.5 MB + 40 KB here: L2 / LDS resident) and are charged
+        #                      ONCE, in both models — and not at all for an index that fills its code space (states == rows:
+        #                      the position of a key is its code, the kernel looks nothing up).  Round 3 still charged
+        #                      2 * 4 * rows here, 0.8 GB that never left the L2.
+        stream_bytes = host_bytes["cust_id"] + host_bytes["prod_id"] + off_o
+        out_bytes = 8 * total_joined_local
 
-    def rank_table_bytes(info, rows):
-        # (both indexes are UniqueIndexOn results: no duplicate keys)
-        return 0.0 if info["table_entries"] == rows else 0.25 * info["table_entries"]
+        def rank_table_bytes(info, rows):
+            # (both indexes are UniqueIndexOn results: no duplicate keys)
+            return 0.0 if info["table_entries"] == rows else 0.25 * info["table_entries"]
 
-    def chain_bytes(positions):
-        if positions:
-            t = rank_table_bytes(ia_info, args.customers) + rank_table_bytes(ib_info, args.products)
-            return stream_bytes + t + out_bytes, stream_bytes + t + out_bytes
-        return (stream_bytes + 2 * 4 * nloc + out_bytes,
-                stream_bytes + 4 * (ia_info["table_entries"] + ib_info["table_entries"]) + out_bytes)
+        def chain_bytes(positions):
+            if positions:
+                t = rank_table_bytes(ia_info, args.customers) + rank_table_bytes(ib_info, args.products)
+                return stream_bytes + t + out_bytes, stream_bytes + t + out_bytes
+            return (stream_bytes + 2 * 4 * nloc + out_bytes,
+                    stream_bytes + 4 * (ia_info["table_entries"] + ib_info["table_entries"]) + out_bytes)
 
-    algo_chain, hbm_chain = chain_bytes(POS)
-    # (round 5) one k_encode_build launch per step = the products table only: the customers' keys are coded inside the first
-    # partition level of their direct sort, whose library-side byte count already holds the 8 bytes of key per row
-    cust_fused = prof.get("k_encode_build", {}).get("launches", 0) <= K and "k_win_partition" in prof
-    extra = {
-        "k_col_stats": K * (cust_bytes + off_c + prod_bytes + off_p),
-        "k_encode_build": K * ((0 if cust_fused else cust_bytes + off_c + ia_info["key_bytes"] * args.customers)
-                               + (prod_bytes + off_p + ib_info["key_bytes"] * args.products)),
-        "k_chain_dense": K * algo_chain,
-    }
-    # compulsory bytes (SURVEY.md §8d "useful"): every input read once, each table read once (not one entry per
-    # probe), every output written once
-    useful = {"k_chain_dense": K * hbm_chain}
-    kernels = {}
-    for name, st in prof.items():
-        b = st["algo_bytes"] + extra.get(name, 0.0)
-        kernels[name] = {"launches": st["launches"], "total_ms": round(st["total_ms"], 4),
-                         "avg_ms": round(st["total_ms"] / max(1, st["launches"]), 5),
-                         "algo_GB": round(b / 1e9, 4),
-                         "GBps": round(b / 1e9 / (st["total_ms"] / 1e3), 1) if st["total_ms"] > 0 else None}
-    # the dominant kernel: its launches INSIDE the timed region (the only ones timed there)
-    if dom_name in kernels and dom_name in prof_timed and prof_timed[dom_name]["launches"]:
-        st = prof_timed[dom_name]
-        per_launch_bytes = kernels[dom_name]["algo_GB"] * 1e9 / max(1, kernels[dom_name]["launches"])
-        kernels[dom_name] = {"launches": st["launches"], "total_ms": round(st["total_ms"], 4),
-                             "avg_ms": round(st["total_ms"] / st["launches"], 5),
-                             "algo_GB": round(per_launch_bytes * st["launches"] / 1e9, 4),
-                             "GBps": round(per_launch_bytes * st["launches"] / 1e9 / (st["total_ms"] / 1e3), 1),
-                             "timed_region": True}
-    dom = (dom_name, kernels[dom_name]) if dom_name in kernels else (None, None)
-    roofline = None
-    if dom[0]:
-        a = dom[1]["GBps"] or 0.0
-        roofline = {"bound": "hbm", "kernel": dom[0], "achieved": a, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": round(a / HBM_PEAK_GBPS, 4), "traffic": None,
-                    "avg_launch_ms": dom[1]["avg_ms"], "launches": dom[1]["launches"],
-                    "algorithmic_bytes_per_launch": round(dom[1]["algo_GB"] * 1e9 / dom[1]["launches"])}
-        if dom[0] in useful and dom[1]["total_ms"] > 0:
-            # `useful` was summed over the K breakdown steps; a step of the N > 1 path launches the kernel once per sub-chunk
-            ub = useful[dom[0]] / K / max(1.0, dom[1]["launches"] / args.steps if dom[1].get("timed_region") else dom[1]["launches"] / K)
-            roofline["useful_bytes_per_launch"] = round(ub)
-            roofline["useful"] = round(ub / 1e9 / (dom[1]["avg_ms"] / 1e3) / HBM_PEAK_GBPS, 4)
-            roofline["frac_hbm"] = roofline["useful"]
-            roofline["frac_note"] = ("frac: the contract's byte model of the timed output mode (bytes_model); frac_hbm: compulsory bytes "
-                                     "only (inputs and lookup tables read once, outputs written once).  Reporting positions the two "
-                                     "coincide: the rank tables are charged once")
-            roofline["bytes_model"] = {"streams_in": round(stream_bytes), "results_out": round(out_bytes),
-                                       "lookups": round(algo_chain - stream_bytes - out_bytes),
-                                       "lookups_compulsory": round(hbm_chain - stream_bytes - out_bytes)}
-        # the whole step (every kernel + host gaps) against the same peak
-        step_bytes = sum(v["algo_GB"] * 1e9 / (args.steps if v.get("timed_region") else K) for v in kernels.values())
-        roofline["step_algorithmic_bytes"] = round(step_bytes)
-        roofline["step_frac"] = round(step_bytes / 1e9 / (ms_per_step / 1e3) / HBM_PEAK_GBPS, 4)
-        # The ceiling of THIS box for the kernel's dominant access pattern, measured now: the chained join makes one
-        # random 4-byte lookup per stream row into the customers row table (4 bytes per code: too big for any L2) and
-        # one into the small products table; a plain gather out[i] = table[idx[i]] of as many lookups into a table of
-        # the same size — no keys to decode, 4 B index in, 4 B value out — is the floor of the customers step alone
-        # (cph_calibrate; the kernel also streams ~25 B of key bytes per row and does the second lookup).
-        if world == 1 and not args.no_calibration and roofline["kernel"] == "k_chain_dense":
-            tb = max(4 * ia_info["table_entries"], 1 << 20)
-            g_ms = eng.ctx.calibrate("gather", tb, nloc, 5)
-            c_bytes = 1 << 30
-            c_ms = eng.ctx.calibrate("copy", c_bytes, 0, 5)
-            calib = {"table_bytes": tb, "lookups": nloc, "ms": round(g_ms, 4), "Glookups_per_s": round(nloc / g_ms / 1e6, 1),
-                     "what": "plain 4-byte gather, same number of lookups, table of the customers ROW table's size, measured in this "
-                             "run (cph_calibrate): the floor of the customers step of k_chain_dense when it reports original row ids"}
-            if not POS:
-                calib["kernel_over_ceiling"] = round(dom[1]["avg_ms"] / g_ms, 3)
-                roofline["gather_ceiling_ms"] = round(g_ms, 4)
-            roofline["gather_ceiling"] = calib
-            roofline["copy_TBps"] = round(2 * c_bytes / (c_ms / 1e3) / 1e12, 3)
-            roofline["copy_note"] = "streaming copy of 1 GiB, read + written bytes per second, measured in this run"
-        roofline["output_mode"] = "sorted positions" if POS else "original row ids"
-    # HBM-side traffic of the dominant kernel: PMC counters cannot be collected inside this process, so
-    # two child runs of this script under `rocprofv3 --pmc` (one counter each) measure them NOW, on this box.
-    # gfx950 correction (MI355X_MICROARCH.md §HBM): FETCH_SIZE tallies a 128-byte request of a wide coalesced
-    # stream as 64 bytes; profiles/r02_pmc_calibration.txt (tools/microbench/pmc_calib.hip) measures the factor
-    # for this kernel's access classes — streamed 4/8-byte-per-lane reads are under-counted 2x, random 4-byte
-    # gathers and WRITE_SIZE are exact — so corrected = FETCH + (streamed input bytes that reached HBM once) + WRITE.
-    if roofline and world == 1 and not args.no_traffic:
-        vals, note = measure_traffic(roofline["kernel"], args)
-        if vals:
-            streamed_in = (host_bytes["cust_id"] + host_bytes["prod_id"] + off_o) if roofline["kernel"] == "k_chain_dense" else 0
-            raw = vals["FETCH_SIZE"] + vals["WRITE_SIZE"]
-            roofline["traffic"] = round(raw + streamed_in / 2)
-            roofline["traffic_raw"] = {"FETCH_SIZE": round(vals["FETCH_SIZE"]), "WRITE_SIZE": round(vals["WRITE_SIZE"])}
-            roofline["traffic_note"] = ("bytes per launch; FETCH_SIZE + WRITE_SIZE from two rocprofv3 --pmc child runs of "
-                                        "this command, + half of the streamed input bytes (gfx950 counts a coalesced "
-                                        "stream's 128-byte requests as 64: profiles/r02_pmc_calibration.txt)")
-        else:
-            roofline["traffic_note"] = f"not measured: {note}"
-    build_names = ("k_col_stats", "k_encode_build", "k_radix_hist_u32", "k_radix_hist_u64", "k_radix_scatter_u32",
-                   "k_radix_scatter_u64", "exclusive_scan_u32", "k_first_dup", "k_build_table", "k_gather_u64", "k_split_count",
-                   "k_direct_scatter", "k_direct_finish", "k_win_partition", "k_win_place", "k_cs_hist", "k_cs_scan", "k_cs_partition", "k_cs_window")
-    build_ms = sum(kernels[k]["total_ms"] for k in build_names if k in kernels)
-    build_gb = sum(kernels[k]["algo_GB"] for k in build_names if k in kernels)
-    kernel_ms_per_step = sum(v["total_ms"] / (args.steps if v.get("timed_region") else K) for v in kernels.values())
+        algo_chain, hbm_chain = chain_bytes(POS)
+        # (round 5) one k_encode_build launch per step = the products table only: the customers' keys are coded inside the first
+        # partition level of their direct sort, whose library-side byte count already holds the 8 bytes of key per row
+        cust_fused = prof.get("k_encode_build", {}).get("launches", 0) <= K and "k_win_partition" in prof
+        extra = {
+            "k_col_stats": K * (cust_bytes + off_c + prod_bytes + off_p),
+            "k_encode_build": K * ((0 if cust_fused else cust_bytes + off_c + ia_info["key_bytes"] * args.customers)
+                                   + (prod_bytes + off_p + ib_info["key_bytes"] * args.products)),
+            "k_chain_dense": K * algo_chain,
+        }
+        # compulsory bytes (SURVEY.md §8d "useful"): every input read once, each table read once (not one entry per
+        # probe), every output written once
+        useful = {"k_chain_dense": K * hbm_chain}
+        kernels = {}
+        for name, st in prof.items():
+            b = st["algo_bytes"] + extra.get(name, 0.0)
+            kernels[name] = {"launches": st["launches"], "total_ms": round(st["total_ms"], 4),
+                             "avg_ms": round(st["total_ms"] / max(1, st["launches"]), 5),
+                             "algo_GB": round(b / 1e9, 4),
+                             "GBps": round(b / 1e9 / (st["total_ms"] / 1e3), 1) if st["total_ms"] > 0 else None}
+        # the dominant kernel: its launches INSIDE the timed region (the only ones timed there)
+        if dom_name in kernels and dom_name in prof_timed and prof_timed[dom_name]["launches"]:
+            st = prof_timed[dom_name]
+            per_launch_bytes = kernels[dom_name]["algo_GB"] * 1e9 / max(1, kernels[dom_name]["launches"])
+            kernels[dom_name] = {"launches": st["launches"], "total_ms": round(st["total_ms"], 4),
+                                 "avg_ms": round(st["total_ms"] / st["launches"], 5),
+                                 "algo_GB": round(per_launch_bytes * st["launches"] / 1e9, 4),
+                                 "GBps": round(per_launch_bytes * st["launches"] / 1e9 / (st["total_ms"] / 1e3), 1),
+                                 "timed_region": True}
+        dom = (dom_name, kernels[dom_name]) if dom_name in kernels else (None, None)
+        roofline = None
+        if dom[0]:
+            a = dom[1]["GBps"] or 0.0
+            roofline = {"bound": "hbm", "kernel": dom[0], "achieved": a, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": round(a / HBM_PEAK_GBPS, 4), "traffic": None,
+                        "avg_launch_ms": dom[1]["avg_ms"], "launches": dom[1]["launches"],
+                        "algorithmic_bytes_per_launch": round(dom[1]["algo_GB"] * 1e9 / dom[1]["launches"])}
+            if dom[0] in useful and dom[1]["total_ms"] > 0:
+                # `useful` was summed over the K breakdown steps; a step of the N > 1 path launches the kernel once per sub-chunk
+                ub = useful[dom[0]] / K / max(1.0, dom[1]["launches"] / args.steps if dom[1].get("timed_region") else dom[1]["launches"] / K)
+                roofline["useful_bytes_per_launch"] = round(ub)
+                roofline["useful"] = round(ub / 1e9 / (dom[1]["avg_ms"] / 1e3) / HBM_PEAK_GBPS, 4)
+                roofline["frac_hbm"] = roofline["useful"]
+                roofline["frac_note"] = ("frac: the contract's byte model of the timed output mode (bytes_model); frac_hbm: compulsory bytes "
+                                         "only (inputs and lookup tables read once, outputs written once).  Reporting positions the two "
+                                         "coincide: the rank tables are charged once")
+                roofline["bytes_model"] = {"streams_in": round(stream_bytes), "results_out": round(out_bytes),
+                                           "lookups": round(algo_chain - stream_bytes - out_bytes),
+                                           "lookups_compulsory": round(hbm_chain - stream_bytes - out_bytes)}
+            # the whole step (every kernel + host gaps) against the same peak
+            step_bytes = sum(v["algo_GB"] * 1e9 / (args.steps if v.get("timed_region") else K) for v in kernels.values())
+            roofline["step_algorithmic_bytes"] = round(step_bytes)
+            roofline["step_frac"] = round(step_bytes / 1e9 / (ms_per_step / 1e3) / HBM_PEAK_GBPS, 4)
+            # The ceiling of THIS box for the kernel's dominant access pattern, measured now: the chained join makes one
+            # random 4-byte lookup per stream row into the customers row table (4 bytes per code: too big for any L2) and
+            # one into the small products table; a plain gather out[i] = table[idx[i]] of as many lookups into a table of
+            # the same size — no keys to decode, 4 B index in, 4 B value out — is the floor of the customers step alone
+            # (cph_calibrate; the kernel also streams ~25 B of key bytes per row and does the second lookup).
+            if world == 1 and not args.no_calibration and roofline["kernel"] == "k_chain_dense":
+                tb = max(4 * ia_info["table_entries"], 1 << 20)
+                g_ms = eng.ctx.calibrate("gather", tb, nloc, 5)
+                c_bytes = 1 << 30
+                c_ms = eng.ctx.calibrate("copy", c_bytes, 0, 5)
+                calib = {"table_bytes": tb, "lookups": nloc, "ms": round(g_ms, 4), "Glookups_per_s": round(nloc / g_ms / 1e6, 1),
+                         "what": "plain 4-byte gather, same number of lookups, table of the customers ROW table's size, measured in this "
+                                 "run (cph_calibrate): the floor of the customers step of k_chain_dense when it reports original row ids"}
+                if not POS:
+                    calib["kernel_over_ceiling"] = round(dom[1]["avg_ms"] / g_ms, 3)
+                    roofline["gather_ceiling_ms"] = round(g_ms, 4)
+                roofline["gather_ceiling"] = calib
+                roofline["copy_TBps"] = round(2 * c_bytes / (c_ms / 1e3) / 1e12, 3)
+                roofline["copy_note"] = "streaming copy of 1 GiB, read + written bytes per second, measured in this run"
+            roofline["output_mode"] = "sorted positions" if POS else "original row ids"
+        # HBM-side traffic of the dominant kernel: PMC counters cannot be collected inside this process, so
+        # two child runs of this script under `rocprofv3 --pmc` (one counter each) measure them NOW, on this box.
+        # gfx950 correction: FETCH_SIZE tallies a 128-byte request of a wide coalesced
+        # stream as 64 bytes; profiles/r02_pmc_calibration.txt (tools/microbench/pmc_calib.hip) measures the factor
+        # for this kernel's access classes — streamed 4/8-byte-per-lane reads are under-counted 2x, random 4-byte
+        # gathers and WRITE_SIZE are exact — so corrected = FETCH + (streamed input bytes that reached HBM once) + WRITE.
+        if roofline and world == 1 and not args.no_traffic:
+            vals, note = measure_traffic(roofline["kernel"], args)
+            if vals:
+                streamed_in = (host_bytes["cust_id"] + host_bytes["prod_id"] + off_o) if roofline["kernel"] == "k_chain_dense" else 0
+                raw = vals["FETCH_SIZE"] + vals["WRITE_SIZE"]
+                roofline["traffic"] = round(raw + streamed_in / 2)
+                roofline["traffic_raw"] = {"FETCH_SIZE": round(vals["FETCH_SIZE"]), "WRITE_SIZE": round(vals["WRITE_SIZE"])}
+                roofline["traffic_note"] = ("bytes per launch; FETCH_SIZE + WRITE_SIZE from two rocprofv3 --pmc child runs of "
+                                            "this command, + half of the streamed input bytes (gfx950 counts a coalesced "
+                                            "stream's 128-byte requests as 64: profiles/r02_pmc_calibration.txt)")
+            else:
+                roofline["traffic_note"] = f"not measured: {note}"
+        build_names = ("k_col_stats", "k_encode_build", "k_radix_hist_u32", "k_radix_hist_u64", "k_radix_scatter_u32",
+                       "k_radix_scatter_u64", "exclusive_scan_u32", "k_first_dup", "k_build_table", "k_gather_u64", "k_split_count",
+                       "k_direct_scatter", "k_direct_finish", "k_win_partition", "k_win_place", "k_cs_hist", "k_cs_scan", "k_cs_partition", "k_cs_window")
+        build_ms = sum(kernels[k]["total_ms"] for k in build_names if k in kernels)
+        build_gb = sum(kernels[k]["algo_GB"] for k in build_names if k in kernels)
+        kernel_ms_per_step = sum(v["total_ms"] / (args.steps if v.get("timed_region") else K) for v in kernels.values())
 
     out = {
         "metric": "joined rows/sec (IndexOn build + chained Join, 1e8-row 3-col orders)",
@@ -915,14 +995,14 @@ def main():
         "compute_ms": (round(ms_per_step - (multi["exposed_exchange_ms"] or 0.0), 4) if multi else round(ms_per_step, 4)),
         "efficiency_vs_n1": multi["efficiency_vs_n1"] if multi else None,
         "multi_gpu": multi,
-        "index_build": {"GBps_algorithmic": round(build_gb / (build_ms / 1e3), 1) if build_ms else None,
-                        "kernel_ms_per_step": round(build_ms / K, 4),
-                        "customers": ia_info, "products": ib_info},
-        "kernel_ms_per_step": round(kernel_ms_per_step, 4),
-        "kernels": kernels,
-        "kernels_note": f"per-kernel times from {K} fully profiled steps run behind the timed region (two HIP events per launch "
-                        f"slow a step by ~10 %); {dom_name} is the one kernel timed inside the timed region itself",
-        "roofline": roofline,
+        **({"index_build": {"GBps_algorithmic": round(build_gb / (build_ms / 1e3), 1) if build_ms else None,
+                            "kernel_ms_per_step": round(build_ms / K, 4),
+                            "customers": ia_info, "products": ib_info},
+            "kernel_ms_per_step": round(kernel_ms_per_step, 4),
+            "kernels": kernels,
+            "kernels_note": f"per-kernel times from {K} fully profiled steps run behind the timed region (two HIP events per launch "
+                            f"slow a step by ~10 %); {dom_name} is the one kernel timed inside the timed region itself",
+            "roofline": roofline} if args.full else {}),
         "host": {"nproc": os.cpu_count(), "cgroup_cpu_max": _cgroup_cpu_max(), "gpu": torch.cuda.get_device_name(dev), "datagen_s": round(gen_s, 1)},
     }
 

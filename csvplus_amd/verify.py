@@ -10,7 +10,7 @@ reference's results from the INPUT columns with plain numpy / torch indexing —
     key equals the stream row's key (csvplus.go:553-567): key bytes of `build_row[r]` == key bytes
     of stream row r.
 
-bench.py runs them after its timed loop (on the 1e8-row outputs it has just timed) and the full-size
+bench.py --full runs them after its timed loop (on the 1e8-row outputs it has just timed) and the full-size
 GPU tests use them too.
 """
 from __future__ import annotations

@@ -85,6 +85,20 @@ def test_more_ranks_than_gpus_is_refused_clearly():
     assert f"needs 2 visible GPUs, this machine shows {have}" in r.stderr and "Traceback" not in r.stderr
 
 
+def test_full_flag_is_accepted_and_dump_outputs_needs_one_rank(tmp_path):
+    """--full (the measurements beside the headline) parses and reaches the self-launched ranks; --dump-outputs writes the one-rank
+    step's results and says so, before any rank starts, when asked for more."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--launch-check", "--full"], env=_env(), capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _json_line(r.stdout)["ranks_seen"] == [0, 1]
+    for extra in (["--gpus", "2"], ["--gpus", "1", "--stream"]):
+        r = subprocess.run([sys.executable, BENCH, *extra, "--dump-outputs", str(tmp_path / "out")], env=_env(), capture_output=True,
+                           text=True, timeout=120)
+        assert r.returncode == 2 and "--dump-outputs" in r.stderr and "Traceback" not in r.stderr, (extra, r.stderr[-2000:])
+        assert not (tmp_path / "out").exists()
+
+
 def test_compact_line_of_the_kept_full_records_fits_the_budget():
     """bench.compact_line on the full records kept under profiles/ (round 5's 22 KB line among them): under the budget, strict JSON,
     `roofline` and `cpu_baseline` with the contract's keys."""
@@ -119,7 +133,7 @@ def test_compact_line_of_the_kept_full_records_fits_the_budget():
     assert len(line) < b.LINE_BUDGET and json.loads(line)["roofline"]["frac"] > 0 and "cpu_baseline" in json.loads(line)
 
 
-SMALL = ["--rows", "300000", "--customers", "20000", "--products", "700", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+SMALL = ["--full", "--rows", "300000", "--customers", "20000", "--products", "700", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
          "--no-index-1e8", "--no-e2e", "--no-traffic"]
 
 
@@ -157,8 +171,8 @@ def test_the_stdout_line_is_small_and_last(tmp_path):
     fields + compact `roofline` / `cpu_baseline` + bare numbers, under 6000 bytes, strict JSON, the LAST line of stdout — with
     every optional block switched on (variants, IndexOn at full test size, the end-to-end scopes, the CPU baseline)."""
     extras = tmp_path / "full.json"
-    cmd = [sys.executable, BENCH, "--gpus", "1", "--rows", "300000", "--customers", "20000", "--products", "700", "--steps", "2", "--warmup", "1",
-           "--no-traffic", "--cpu-sample-rows", "50000", "--verify-sample", "5000", "--extras", str(extras)]
+    cmd = [sys.executable, BENCH, "--gpus", "1", "--full", "--rows", "300000", "--customers", "20000", "--products", "700", "--steps", "2",
+           "--warmup", "1", "--no-traffic", "--cpu-sample-rows", "50000", "--verify-sample", "5000", "--extras", str(extras)]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -246,10 +260,46 @@ def test_one_rank_run_of_the_multi_gpu_path_at_bench_size():
     """The N > 1 step (communicator, cph_dist_join_chain, match totals over the exchange stream) with ONE rank at the bench's own size must
     cost little more than the plain step: round 5 measured 1.09 ms against 0.76 ms (8 sub-chunks of a shard that has nobody to send to);
     the library now sizes its sub-chunks by the shard (dist.hip) — efficiency_vs_n1 = n1 step / this step >= 0.88."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-index-1e8", "--no-e2e",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-index-1e8", "--no-e2e",
                         "--no-traffic", "--no-verify", "--no-variants", "--no-positions", "--no-calibration"],
                        env=_env(CPH_BENCH_FORCE_DIST="1"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["joined_rows_per_step"] == 100_000_000 and d["config"]["rccl_nranks"] == 1 and d["multi_gpu"]["chunks"] == 1
     assert d["efficiency_vs_n1"] >= 0.88, (d["efficiency_vs_n1"], d["ms_per_step"], d["multi_gpu"])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full a run sets up, warms up, times --steps steps and prints the line: no full record, no per-kernel table, no checks
+    beside it.  --dump-outputs writes what the last timed step computed; at this size nothing is sampled, and it is what the oracle
+    computes on the bench's tables (bench.py: synthetic tables): both perms, the stream rows, and perm[build position] = the oracle's
+    build row of every joined row."""
+    import numpy as np
+
+    from csvplus_amd import datagen as dg
+    from oracle import orc
+
+    rows, ncust, nprod = 300000, 20000, 700
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--rows", str(rows), "--customers", str(ncust), "--products", str(nprod),
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d), d
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["joined_rows_per_step"] == rows
+    assert abs(d["value"] - rows / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+    assert not {"roofline", "cpu_baseline", "verified", "extras", "kernel_ms_per_step"} & set(d), d
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(got) == {"joined_rows", "stream_row", "customers_build_row", "customers_perm", "products_build_row", "products_perm"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["joined_rows"].tolist() == [rows]
+    np.testing.assert_array_equal(got["stream_row"], np.arange(rows))
+    ords = dg.orders(rows, ncust, nprod)
+    for name, col, key in (("customers", dg.column(dg.SEQ_PERM, ncust, ncust, encoding=dg.FIXED8, seed=dg.SEED + 1), ords["cust_id"]),
+                           ("products", dg.column(dg.SEQ_PERM, nprod, nprod, encoding=dg.ITOA, seed=dg.SEED + 2), ords["prod_id"])):
+        o = orc.OracleIndex([col])
+        np.testing.assert_array_equal(got[f"{name}_perm"], o.perm)
+        j = o.join([key])
+        assert j["nmatches"] == rows
+        np.testing.assert_array_equal(got[f"{name}_perm"][got[f"{name}_build_row"].astype(np.int64)], j["build_row"])

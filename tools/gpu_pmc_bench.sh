@@ -3,7 +3,7 @@
 export TMPDIR=/tmp; ROOTDIR=$(pwd); OUT=$ROOTDIR/gpurun_out/pmc_bench; mkdir -p $OUT
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD \
-  --output-format csv -d $OUT -o b -- python $ROOTDIR/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-index-1e8 --no-e2e --no-traffic --no-positions --no-verify --no-calibration $BENCH_EXTRA > $OUT/run.log 2>&1
+  --output-format csv -d $OUT -o b -- python $ROOTDIR/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-index-1e8 --no-e2e --no-traffic --no-positions --no-verify --no-calibration $BENCH_EXTRA > $OUT/run.log 2>&1
 echo "rc=$?" >> $OUT/run.log
 cd $ROOTDIR
 python - <<'PY'

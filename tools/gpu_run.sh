@@ -1,7 +1,7 @@
 #!/bin/bash
 # One entry point for everything run on the GPU box:  gpurun -- 'bash tools/gpu_run.sh <recipe> [args]'
 # (rounds 1-5 kept one gpu_r*.sh per call — 60 files; they are in the git history).  Output: gpurun_out/<recipe>/.
-#   driver [tag]        smoke() + the driver's own command line (bench.py --gpus 1 --steps 20 --warmup 5): line + full record kept
+#   driver [tag]        smoke() + the driver's command line with --full (bench.py --gpus 1 --steps 20 --warmup 5 --full): line + full record kept
 #   profile <tag>       rocprofv3 passes over the TIMED STEP ONLY (--no-variants: one instantiation per kernel row) -> gpurun_out/prof_<tag>
 #   profile-variant <tag> <variant>   the same over one variant's step (--variants <variant>, timed step's own passes excluded by launch order)
 #   suite               the whole GPU test suite
@@ -19,7 +19,7 @@ driver)
   TAG=${1:-r06}
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
   T0=$(date +%s)
-  timeout 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --extras $OUT/${TAG}_bench_full.json > $OUT/bench.out 2> $OUT/bench.err
+  timeout 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --extras $OUT/${TAG}_bench_full.json > $OUT/bench.out 2> $OUT/bench.err
   echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"; tail -3 $OUT/bench.err
   tail -1 $OUT/bench.out > $OUT/${TAG}_bench_line.json
   wc -c $OUT/${TAG}_bench_line.json
@@ -49,7 +49,7 @@ fuzz)
   timeout $((S*3+100)) python tools/fuzz_builds.py $S 603 2>&1 | grep -v amdgpu.ids | tee $OUT/fuzz_builds.txt | tail -3
   ;;
 bench)
-  timeout 1500 python3 bench.py --extras $OUT/bench_full.json "$@" > $OUT/bench.out 2> $OUT/bench.err
+  timeout 1500 python3 bench.py --full --extras $OUT/bench_full.json "$@" > $OUT/bench.out 2> $OUT/bench.err
   echo "bench rc=$?"; tail -3 $OUT/bench.err; tail -1 $OUT/bench.out | tee $OUT/bench_line.json | head -c 7000; echo
   ;;
 py)
