@@ -6,8 +6,8 @@ the SoA column staging and the multi-GPU sharding.  There is no CPU fallback.
 
 Modules: `engine` (one GPU: index_on / join / chained_join on torch device memory), `dist` (probe-row sharding +
 allgatherv over RCCL), `streaming` (host -> device pipeline of join chunks), `ingest` (CSV text -> columns),
-`materialize` (gather through row ids, ToCsv), `dedup` (ResolveDuplicates over the device index),
-`pipeline` (CSV -> indices -> chained join -> CSV, all in HBM), `datagen` (deterministic synthetic tables).
+`materialize` (gather through row ids, ToCsv, ToJSON), `dedup` (ResolveDuplicates over the device index),
+`pipeline` (CSV -> indices -> chained join -> CSV or JSON, all in HBM), `datagen` (deterministic synthetic tables).
 """
 from . import _native as native  # noqa: F401
 from ._native import CphError, NativeLibraryMissing, Context, DeviceIndex, Matches, Chain, join_chain  # noqa: F401

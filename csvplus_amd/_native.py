@@ -249,6 +249,9 @@ PROTOTYPES = [
      [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_int32, C.c_uint64, C.POINTER(cph_strval), C.c_int32,
       C.POINTER(C.POINTER(cph_bytes))]),
     ("cph_bytes_release", None, [C.POINTER(cph_bytes)]),
+    ("cph_json_write_rows", C.c_int32,
+     [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.POINTER(cph_strval), C.c_int32, C.c_uint64, C.c_int32,
+      C.POINTER(C.POINTER(cph_bytes))]),
     ("cph_csv_parse", C.c_int32,
      [_P, _P, C.c_uint64, C.c_int32, C.POINTER(cph_csv_options), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_csv_table))]),

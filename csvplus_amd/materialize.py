@@ -1,5 +1,6 @@
 """The step after the path: gathering columns through the joined row ids and writing the
-canonical CSV (cph_gather_rows / cph_csv_write; mergeRows csvplus.go:571-583, ToCsv :379-406)."""
+canonical CSV or JSON (cph_gather_rows / cph_csv_write / cph_json_write_rows; mergeRows csvplus.go:571-583,
+ToCsv :379-406, ToJSON :446-480)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -117,26 +118,13 @@ class DeviceBytes:
             pass
 
 
-def csv_write(ctx: N.Context, cols, header=None, out_mem: int = N.CPH_MEM_HOST, row_ids=None, nrows=None):
-    """ToCsv: header (list of names or None) + rows of `cols`, Go csv.Writer format.
-    row_ids (optional, one entry per column): None = the column's own rows, else the rows of that column feeding
-    the output (numpy uint32/uint64 for host columns, (device_ptr, bits, count[, base]) for device columns) —
-    Join(...).ToCsv(...) fused: mergeRows happens inside the writer (cph_csv_write_rows).
-    Returns bytes (out_mem HOST) or a DeviceBytes handle (DEVICE)."""
+def _rowsel(cols, row_ids, nrows, keep):
+    """cph_strcol array, cph_rowsel array (None without row_ids) and the row count of a writer call (csv_write / json_write)."""
     arr = (N.cph_strcol * len(cols))()
-    keep = []
     for i, c in enumerate(cols):
         sc, k = c.as_c()
         arr[i] = sc
         keep.append(k)
-    hv = None
-    if header is not None:
-        hv = (N.cph_strval * len(cols))()
-        for i, h in enumerate(header):
-            b = np.frombuffer(h.encode() if isinstance(h, str) else bytes(h), dtype=np.uint8)
-            keep.append(b)
-            hv[i].data = b.ctypes.data if len(b) else None
-            hv[i].len = len(b)
     sel = None
     n = cols[0].nrows if nrows is None else int(nrows)
     if row_ids is not None:
@@ -156,10 +144,51 @@ def csv_write(ctx: N.Context, cols, header=None, out_mem: int = N.CPH_MEM_HOST, 
                 sel[i].base = int(ids[3]) if len(ids) > 3 else 0
             if nrows is None:
                 n = cnt
-    out = C.POINTER(N.cph_bytes)()
-    ctx._check(ctx.lib.cph_csv_write_rows(ctx.handle, arr, sel, len(cols), n, hv, out_mem, C.byref(out)))
+    return arr, sel, n
+
+
+def _strvals(names, size, keep):
+    hv = (N.cph_strval * size)()
+    for i, h in enumerate(names):
+        b = np.frombuffer(h.encode() if isinstance(h, str) else bytes(h), dtype=np.uint8)
+        keep.append(b)
+        hv[i].data = b.ctypes.data if len(b) else None
+        hv[i].len = len(b)
+    return hv
+
+
+def _take_bytes(ctx, out, out_mem):
     if out_mem == N.CPH_MEM_DEVICE:
         return DeviceBytes(ctx, out)
     res = N._ptr_array(out.contents.data, int(out.contents.size), np.uint8).tobytes()
     ctx.lib.cph_bytes_release(out)
     return res
+
+
+def csv_write(ctx: N.Context, cols, header=None, out_mem: int = N.CPH_MEM_HOST, row_ids=None, nrows=None):
+    """ToCsv: header (list of names or None) + rows of `cols`, Go csv.Writer format.
+    row_ids (optional, one entry per column): None = the column's own rows, else the rows of that column feeding
+    the output (numpy uint32/uint64 for host columns, (device_ptr, bits, count[, base]) for device columns) —
+    Join(...).ToCsv(...) fused: mergeRows happens inside the writer (cph_csv_write_rows).
+    Returns bytes (out_mem HOST) or a DeviceBytes handle (DEVICE)."""
+    keep = []
+    arr, sel, n = _rowsel(cols, row_ids, nrows, keep)
+    hv = _strvals(header, len(cols), keep) if header is not None else None
+    out = C.POINTER(N.cph_bytes)()
+    ctx._check(ctx.lib.cph_csv_write_rows(ctx.handle, arr, sel, len(cols), n, hv, out_mem, C.byref(out)))
+    return _take_bytes(ctx, out, out_mem)
+
+
+def json_write(ctx: N.Context, cols, names, out_mem: int = N.CPH_MEM_HOST, row_ids=None, nrows=None):
+    """ToJSON (csvplus.go:446-480): the rows of `cols` as a JSON array of objects keyed by `names` (str or bytes, one per
+    column, all different), written as the reference's json.Encoder does — keys in byte order, '\\n' after every object,
+    no HTML escaping (cph_json_write_rows).  row_ids and nrows as in csv_write.
+    Returns bytes (out_mem HOST) or a DeviceBytes handle (DEVICE)."""
+    if len(names) != len(cols):
+        raise ValueError(f"json_write: {len(cols)} columns but {len(names)} names")
+    keep = []
+    arr, sel, n = _rowsel(cols, row_ids, nrows, keep)
+    hv = _strvals(names, len(cols), keep)
+    out = C.POINTER(N.cph_bytes)()
+    ctx._check(ctx.lib.cph_json_write_rows(ctx.handle, arr, sel, hv, len(cols), n, out_mem, C.byref(out)))
+    return _take_bytes(ctx, out, out_mem)

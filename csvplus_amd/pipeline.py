@@ -5,10 +5,12 @@
 
 CSV bytes -> columns (cph_csv_parse) -> indices (cph_index_build) -> fused chained join (cph_join_chain) ->
 output columns (cph_gather_rows: mergeRows, csvplus.go:571-583, column by column) -> CSV bytes
-(cph_csv_write: ToCsv, :379-406).  Nothing leaves HBM between the first and the last step.
+(cph_csv_write: ToCsv, :379-406; or JSON bytes, cph_json_write_rows: ToJSON, :446-480).  Nothing leaves HBM between
+the first and the last step.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import time
 
@@ -60,6 +62,34 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
             ctx.synchronize()
             timings[name] = timings.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
 
+    with _joined(ctx, stream, steps, out_columns, lap, positions) as (cols, ids, n, bufs):
+        t0 = time.perf_counter()
+        from .materialize import csv_write
+        if fused:
+            # mergeRows inside the writer: fields are read through the row-id tuples, nothing is materialised
+            text = csv_write(ctx, cols, [name for name, _, _ in out_columns], out_mem=out_mem, row_ids=ids, nrows=n)
+            lap("to_csv_ms", t0)
+        else:
+            gcols = []
+            for c, i in zip(cols, ids):
+                if i is None and c.nrows == n:
+                    gcols.append(c)
+                    continue
+                cb = gather_rows(ctx, c, i, out_mem=N.CPH_MEM_DEVICE)
+                bufs.append(cb)
+                gcols.append(cb.as_device_strcol())
+            lap("gather_ms", t0)
+            t0 = time.perf_counter()
+            text = csv_write(ctx, gcols, [name for name, _, _ in out_columns], out_mem=out_mem)
+            lap("to_csv_ms", t0)
+        return text
+
+
+@contextlib.contextmanager
+def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions):
+    """Index, chain and output columns of a Join(...) over `steps`: yields (cols, ids, n, bufs) — per output column the column
+    to read and its row ids for the writers (csv_write / json_write row_ids), the joined row count, and a list whose
+    ColBufs are released on exit (with the indexes and the chain)."""
     if positions is None:
         payload = {}
         for _, tab, col in out_columns:
@@ -92,8 +122,6 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
         ptrs = ch.device_ptrs()
         n = ch.nrows
         lap("join_ms", t0)
-        t0 = time.perf_counter()
-        from .materialize import csv_write
         cols, ids = [], []
         for _, tab, col in out_columns:
             cols.append(tab[col] if tab is stream or not positions else sorted_cols[(tabs.index(tab), col)])
@@ -103,24 +131,7 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
                 ids.append((ptrs["build_row"][tabs.index(tab)], 32, n))
         if n == 0:
             cols, ids = [c.head(0) for c in cols], [None] * len(cols)
-        if fused:
-            # mergeRows inside the writer: fields are read through the row-id tuples, nothing is materialised
-            text = csv_write(ctx, cols, [name for name, _, _ in out_columns], out_mem=out_mem, row_ids=ids, nrows=n)
-            lap("to_csv_ms", t0)
-        else:
-            gcols = []
-            for c, i in zip(cols, ids):
-                if i is None and c.nrows == n:
-                    gcols.append(c)
-                    continue
-                cb = gather_rows(ctx, c, i, out_mem=N.CPH_MEM_DEVICE)
-                bufs.append(cb)
-                gcols.append(cb.as_device_strcol())
-            lap("gather_ms", t0)
-            t0 = time.perf_counter()
-            text = csv_write(ctx, gcols, [name for name, _, _ in out_columns], out_mem=out_mem)
-            lap("to_csv_ms", t0)
-        return text
+        yield cols, ids, n, bufs
     finally:
         for cb in bufs:
             cb.release()
@@ -128,3 +139,31 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
             ch.release()
         for ix in indices:
             ix.close()
+
+
+def join_to_json(ctx: N.Context, stream: Table, steps, out_columns=None, timings: dict | None = None, out_mem: int = N.CPH_MEM_HOST,
+                 positions: bool | None = None):
+    """Join(...).ToJSON() (csvplus.go:446-480) over the steps of join_to_csv, written by cph_json_write_rows with mergeRows
+    folded into the writer.  out_columns: [(output name, table, column)] as in join_to_csv, the names all different; None
+    (default): what the reference's joined rows hold — every column of the stream and of every index table, a name present
+    in several of them taken from the first of stream, steps[0], steps[1], ... (nested mergeRows, :559-560, :571-583).
+    Returns the JSON text: bytes, or a DeviceBytes handle for out_mem DEVICE."""
+    if out_columns is None:
+        out_columns, seen = [], set()
+        for tab in [stream] + [t for t, _, _ in steps]:
+            for name in tab.cols:
+                if name not in seen:
+                    seen.add(name)
+                    out_columns.append((name, tab, name))
+
+    def lap(name, t0):
+        if timings is not None:
+            ctx.synchronize()
+            timings[name] = timings.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
+
+    with _joined(ctx, stream, steps, out_columns, lap, positions) as (cols, ids, n, _):
+        t0 = time.perf_counter()
+        from .materialize import json_write
+        text = json_write(ctx, cols, [name for name, _, _ in out_columns], out_mem=out_mem, row_ids=ids, nrows=n)
+        lap("to_json_ms", t0)
+        return text

@@ -674,6 +674,29 @@ CPH_API int32_t cph_csv_write_rows(cph_ctx* ctx, const cph_strcol* cols, const c
                                    const cph_strval* header, int32_t out_mem, cph_bytes** out);
 CPH_API void    cph_bytes_release(cph_bytes* b);
 
+/*
+ * ToJSON (csvplus.go:446-480) over the same rows as cph_csv_write_rows: cols and sel mean exactly what they mean there
+ * (per-column uint32 / uint64 row ids with a base; sel == NULL or sel[c].ids == NULL: the identity, and then cols[c].nrows
+ * must equal nrows; host or device columns), names[c] is the key of column c.  The text is what the reference writes:
+ * '[', then every row as json.Encoder.Encode(row) writes it with SetIndent("", "") and SetEscapeHTML(false) — a compact
+ * object followed by '\n' — with ',' in front of every row but the first, then ']'.  n rows:
+ *     [{"k1":"v1","k2":"v2"}\n,{"k1":"v1","k2":"v2"}\n]        (no spaces; nrows == 0 gives exactly "[]")
+ * A Row is a map[string]string, so the keys of every object are sorted by byte order (the function sorts the columns by
+ * name itself; the order the caller lists them in does not matter).  Keys and values are escaped as Go >= 1.22
+ * encoding/json does with escapeHTML false:
+ *   - 0x20..0x7F other than '"' and the backslash are copied (DEL, '<', '>', '&' included); those two get a backslash in front;
+ *   - 0x08 0x0C 0x0A 0x0D 0x09 -> \b \f \n \r \t (Go before 1.22 wrote \u0008 and \u000c); other bytes < 0x20 -> \u00XX,
+ *     lowercase hex;
+ *   - bytes >= 0x80 are decoded as utf8.DecodeRuneInString does: a valid sequence is copied unchanged (a literal U+FFFD
+ *     too), U+2028 / U+2029 become \u2028 / \u2029, an invalid or truncated sequence (overlong forms, surrogates, leads
+ *     C0 C1 F5..FF, stray continuation bytes) becomes \ufffd and decoding resumes ONE byte later.
+ * CPH_ERR_INVALID: names == NULL, ncols outside 1..16, two equal names (a map holds each key once: the caller resolves
+ * mergeRows collisions, :578-580), row-id bits other than 32 / 64, an identity column whose row count is not nrows.
+ * The result (out_mem HOST or DEVICE) is released with cph_bytes_release; its size is exact.
+ */
+CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, const cph_strval* names,
+                                    int32_t ncols, uint64_t nrows, int32_t out_mem, cph_bytes** out);
+
 /* ---- CSV ingest: bytes -> SoA string columns (csvplus.go:1080-1146) ----------- */
 /*
  * Replaces the parse loop of Reader.Iterate (csv.NewReader + one map per line,
