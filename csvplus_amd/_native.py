@@ -147,6 +147,25 @@ class cph_rowsel(C.Structure):
     _fields_ = [("ids", C.c_void_p), ("bits", C.c_int32), ("reserved_", C.c_int32), ("base", C.c_uint64)]
 
 
+CPH_PRED_LIKE, CPH_PRED_NOT, CPH_PRED_ALL, CPH_PRED_ANY = 1, 2, 3, 4
+CPH_PRED_MAX_OPS, CPH_PRED_MAX_LIKE, CPH_PRED_MAX_STACK = 64, 32, 32
+CPH_FILTER_WHERE, CPH_FILTER_TAKE_WHILE, CPH_FILTER_DROP_WHILE = 0, 1, 2
+CPH_NO_LIMIT = 0xFFFFFFFFFFFFFFFF
+
+
+class cph_pred_op(C.Structure):
+    _fields_ = [("op", C.c_int32), ("arg", C.c_int32), ("value", cph_strval)]
+
+
+class cph_filter_opts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("out_bits", C.c_int32), ("first_row", C.c_uint64), ("skip", C.c_uint64),
+                ("limit", C.c_uint64)]
+
+
+class cph_rowlist(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("first", C.c_uint64), ("ids", C.c_void_p), ("bits", C.c_int32), ("mem", C.c_int32)]
+
+
 class cph_groups(C.Structure):
     _fields_ = [("ngroups", C.c_uint64), ("lower", C.c_void_p), ("upper", C.c_void_p)]
 
@@ -252,6 +271,12 @@ PROTOTYPES = [
     ("cph_json_write_rows", C.c_int32,
      [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.POINTER(cph_strval), C.c_int32, C.c_uint64, C.c_int32,
       C.POINTER(C.POINTER(cph_bytes))]),
+    ("cph_filter_rows", C.c_int32,
+     [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_int32, C.c_uint64, C.POINTER(cph_pred_op), C.c_int32,
+      C.POINTER(cph_filter_opts), C.c_int32, C.POINTER(C.POINTER(cph_rowlist))]),
+    ("cph_rowlist_release", None, [C.POINTER(cph_rowlist)]),
+    ("cph_rowsel_take", C.c_int32,
+     [_P, C.POINTER(cph_rowsel), C.c_int32, C.POINTER(cph_rowlist), C.c_int32, C.POINTER(C.POINTER(cph_rowlist))]),
     ("cph_csv_parse", C.c_int32,
      [_P, _P, C.c_uint64, C.c_int32, C.POINTER(cph_csv_options), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_csv_table))]),

@@ -1,0 +1,562 @@
+// filter.hip — Filter / TakeWhile / DropWhile / Top / Drop with the reference's named predicates (csvplus.go:276-374,
+// :1243-1293): the one stage that PRODUCES a list of row numbers from the data; every other stage consumes one.
+//
+//   cph_filter_rows   a postfix program of Like / Not / All / Any over the columns of a call -> an ascending row list
+//   cph_rowsel_take   out[i] = sel.ids[list[i]] - sel.base: a Join's per-column row ids narrowed to the rows a Filter kept
+//
+// The predicate's strings are read ONCE:
+//   k_pred_eval   rows on lanes (row = tile + 64 k + lane, 4 rows per lane in flight).  Every LIKE term over a real column
+//                 (at most 32) becomes one bit of a per-row mask; the boolean program then runs over that mask on a bit
+//                 stack — it is wave-uniform, only the data differs per lane.  __ballot is 64 bits wide on gfx950: a
+//                 wave's ballot IS the bitmap word of its 64 rows.  A tile's 32 words go through LDS and leave as one
+//                 coalesced store by 32 lanes, whose popcounts add up to the tile's count.
+//   exclusive scan of the tile counts (radix_sort.hip); its total is the result size — the call's host wait.
+//   k_pred_emit   per tile: bitmap words -> rank inside the tile by popcount + mbcnt -> out[rank - skip] = first_row + row
+//                 for the ranks in [skip, skip + limit).  No atomics in either kernel of the WHERE mode.
+// The two WHILE modes only need the first failing row: the same evaluation without the bitmap, one 64-bit atomicMin per
+// wave that saw a failure (none when the value it read at the tile's start is already smaller; tiles behind that value
+// are not read at all).  Their answer is a range: nothing is materialised.
+#include <algorithm>
+#include <cstring>
+#include <new>
+
+#include "materialize_device.hpp"
+
+namespace cph {
+
+constexpr int kFiltRows  = 8;                          // rows per lane and tile
+constexpr int kFiltPhase = 4;                          // ... of which this many are in flight at once
+constexpr int kFiltTile  = kMatThreads * kFiltRows;    // 2048 rows = 32 bitmap words
+constexpr int kFiltWords = kFiltTile / 64;
+constexpr int kFiltWaveWords = kFiltWords / (kMatThreads / kWave);   // 8 words per wave
+constexpr int kLitLds    = 4096;                       // literal bytes kept in LDS; more than that stay in global memory
+
+enum : uint32_t { kTermBytes = 0, kTermFix8 = 1 };
+constexpr uint8_t kTermNever = 0xFF;                   // a LIKE decided on the host: no such column, or a fixed width other than the literal's
+
+// One LIKE over a real column.  A literal of at most 8 bytes is lit8 (zero padded); a longer one lies in the literal
+// block at word lit_off, zero padded to whole 8-byte words.
+struct PredTerm {
+    uint64_t lit8;
+    uint32_t lit_off, len;
+    int32_t  col;
+    uint32_t kind;   // kTermFix8: a fixed-width column of 8 bytes on an 8-byte aligned base — one aligned load and one compare
+};
+struct PredProg {    // travels in the kernel arguments (~0.9 KB): a wave reads it with scalar loads
+    PredTerm term[CPH_PRED_MAX_LIKE];
+    uint8_t  op[CPH_PRED_MAX_OPS];
+    uint8_t  arg[CPH_PRED_MAX_OPS];   // LIKE: its term (kTermNever: false); ALL / ANY: the operand count
+    int32_t  nops, nterms;
+    const uint64_t* lits;
+    uint32_t lit_words, lits_in_lds;
+};
+
+// value bytes [0, len) == the literal; len is the literal's length too
+__device__ __forceinline__ bool like_bytes(const DevCol& col, uint64_t begin, const PredTerm& t, const uint64_t* glits,
+                                           const CPH_LDS uint64_t* slits, bool in_lds) {
+    const uint64_t len = t.len;
+    for (uint64_t j = 0; 8 * j < len; j++) {
+        const uint64_t chunk = load_value_chunk(col.data, begin, len, (int)j);
+        const uint64_t nb = len - 8 * j;
+        const uint64_t valid = nb >= 8 ? ~0ull : ((1ull << (8 * nb)) - 1);
+        const uint64_t lit = len <= 8 ? t.lit8 : in_lds ? slits[t.lit_off + j] : glits[t.lit_off + j];
+        if ((chunk ^ lit) & valid) return false;
+    }
+    return true;
+}
+
+// BITMAP: bitmap[tile * 32 + w] bit b = the predicate holds for row tile * 2048 + 64 w + b of the call (rows >= n: 0),
+//         counts[tile] = the tile's set bits.
+// else:   *first_fail = min(*first_fail, the first row where it does not hold); the host presets it to n.
+template <bool BITMAP>
+__global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds ids, PredProg prog, uint64_t first_row, uint64_t n,
+                                                          uint64_t* __restrict__ bitmap, uint32_t* __restrict__ counts,
+                                                          unsigned long long* first_fail) {
+    __shared__ uint64_t s_lits[kLitLds / 8];
+    __shared__ uint64_t s_words[kFiltWords];
+    const CPH_LDS uint64_t* slits = (const CPH_LDS uint64_t*)s_lits;
+    const bool in_lds = prog.lits_in_lds != 0;
+    if (in_lds) {
+        for (uint32_t q = threadIdx.x; q < prog.lit_words; q += kMatThreads) s_lits[q] = prog.lits[q];
+        __syncthreads();
+    }
+    const int lane = lane_id(), wave = wave_id();
+    const uint64_t ntiles = (n + kFiltTile - 1) / kFiltTile;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * kFiltTile;
+        unsigned long long seen = 0;
+        if constexpr (!BITMAP) {
+            seen = __hip_atomic_load(first_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t0 >= seen) continue;   // an earlier row has failed already: nothing here can be the first
+        }
+        uint64_t myword = 0;
+        unsigned long long fail = ~0ull;
+#pragma unroll
+        for (int ph = 0; ph < kFiltRows / kFiltPhase; ph++) {
+            uint64_t pos[kFiltPhase];   // position in the selection (rows past the end look at the last row; their result is dropped)
+            uint32_t mask[kFiltPhase];
+#pragma unroll
+            for (int k = 0; k < kFiltPhase; k++) {
+                const uint64_t i = t0 + (uint64_t)((wave * kFiltWaveWords + ph * kFiltPhase + k) * 64 + lane);
+                pos[k] = first_row + (i < n ? i : n - 1);
+                mask[k] = 0;
+            }
+            for (int t = 0; t < prog.nterms; t++) {   // uniform
+                const PredTerm& tm = prog.term[t];
+                const DevCol& col = cols.c[tm.col];
+                const RowIds& rid = ids.ids[tm.col];
+                if (tm.kind == kTermFix8) {
+                    uint64_t v[kFiltPhase];
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) v[k] = reinterpret_cast<const uint64_t*>(col.data)[source_row(rid, pos[k])];
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) mask[k] |= (uint32_t)(v[k] == tm.lit8) << t;
+                } else {
+                    uint64_t b[kFiltPhase], l[kFiltPhase];
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) value_span(col, source_row(rid, pos[k]), &b[k], &l[k]);
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++)
+                        mask[k] |= (uint32_t)(l[k] == tm.len && like_bytes(col, b[k], tm, prog.lits, slits, in_lds)) << t;
+                }
+            }
+            // the program over the term bits: a stack of at most 32 booleans, bit 0 = its top
+            uint64_t st[kFiltPhase];
+#pragma unroll
+            for (int k = 0; k < kFiltPhase; k++) st[k] = 0;
+            for (int q = 0; q < prog.nops; q++) {     // uniform
+                const uint32_t op = prog.op[q], a = prog.arg[q];
+                if (op == CPH_PRED_LIKE) {
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) st[k] = (st[k] << 1) | (a == kTermNever ? 0u : (mask[k] >> a) & 1u);
+                } else if (op == CPH_PRED_NOT) {
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) st[k] ^= 1ull;
+                } else {
+                    const uint64_t m = (1ull << a) - 1;   // a <= 32
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {
+                        const uint64_t r = op == CPH_PRED_ALL ? (uint64_t)((st[k] & m) == m) : (uint64_t)((st[k] & m) != 0);
+                        st[k] = ((st[k] >> a) << 1) | r;
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kFiltPhase; k++) {
+                const int w = ph * kFiltPhase + k;
+                const uint64_t i = t0 + (uint64_t)((wave * kFiltWaveWords + w) * 64 + lane);
+                const bool holds = (st[k] & 1ull) != 0;
+                if constexpr (BITMAP) {
+                    const uint64_t word = __ballot(i < n && holds);
+                    if (lane == w) myword = word;
+                } else {
+                    const uint64_t bad = __ballot(i < n && !holds);
+                    const unsigned long long at = t0 + (uint64_t)((wave * kFiltWaveWords + w) * 64) + (uint64_t)__builtin_ctzll(bad | (1ull << 63));
+                    if (bad && at < fail) fail = at;
+                }
+            }
+        }
+        if constexpr (BITMAP) {
+            if (lane < kFiltWaveWords) s_words[wave * kFiltWaveWords + lane] = myword;
+            __syncthreads();
+            if (wave == 0) {   // one lane per word: a 256-byte store
+                const uint64_t word = lane < kFiltWords ? s_words[lane] : 0;
+                if (lane < kFiltWords) bitmap[tile * kFiltWords + lane] = word;
+                const uint32_t c = wave_sum((uint32_t)__popcll(word));
+                if (lane == 0) counts[tile] = c;
+            }
+            __syncthreads();
+        } else {
+            if (lane == 0 && fail < seen) atomicMin(first_fail, fail);
+        }
+    }
+}
+
+// offs[tile] = kept rows in front of the tile (offs[ntiles] = all of them); rank r of the filter's result goes to
+// out[r - skip] for skip <= r < end
+template <class T>
+__global__ __launch_bounds__(kMatThreads) void k_pred_emit(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ offs,
+                                                          uint64_t ntiles, uint64_t first_row, uint64_t skip, uint64_t end,
+                                                          T* __restrict__ out) {
+    const int lane = lane_id(), wave = wave_id();
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t o0 = offs[tile], o1 = offs[tile + 1];
+        if (o0 == o1 || o1 <= skip || o0 >= end) continue;   // uniform
+        const uint64_t word = lane < kFiltWords ? bitmap[tile * kFiltWords + lane] : 0;
+        const uint32_t pc = (uint32_t)__popcll(word);
+        const uint32_t before = wave_inclusive_sum(pc) - pc;
+#pragma unroll
+        for (int k = 0; k < kFiltWaveWords; k++) {
+            const int w = wave * kFiltWaveWords + k;
+            const uint32_t lo = __shfl((uint32_t)word, w, kWave), hi = __shfl((uint32_t)(word >> 32), w, kWave);
+            const uint32_t pre = __shfl(before, w, kWave);
+            const uint64_t bits = (uint64_t)lo | ((uint64_t)hi << 32);
+            if ((bits >> lane) & 1ull) {
+                const uint64_t rank = o0 + pre + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+                if (rank >= skip && rank < end) out[rank - skip] = (T)(first_row + tile * kFiltTile + (uint64_t)(w * 64 + lane));
+            }
+        }
+    }
+}
+
+// out[i] = sel[list[i]] - sel.base, as wide as sel (list.ptr == NULL: list[i] = list.base + i, see the caller)
+__global__ __launch_bounds__(kMatThreads) void k_rowsel_take(RowIds sel, RowIds list, uint64_t list_first, uint64_t n, void* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kMatThreads + threadIdx.x; i < n; i += stride) {
+        const uint64_t li = list.ptr ? source_row(list, i) : list_first + i;
+        const uint64_t v = source_row(sel, li);
+        if (sel.bits == 32) reinterpret_cast<uint32_t*>(out)[i] = (uint32_t)v;
+        else reinterpret_cast<uint64_t*>(out)[i] = v;
+    }
+}
+
+}  // namespace cph
+
+using namespace cph;
+
+// the library-owned row list behind cph_rowlist
+struct cph_rowlist_impl {
+    cph_rowlist pub;   // first
+    cph_ctx* ctx = nullptr;
+    cph::DevBuf d_ids;
+    void* h_block = nullptr;
+};
+
+namespace {
+
+// r->pub.ids / mem from the device array `dev` of n row numbers (the call's last synchronisation)
+Status deliver_ids(cph_ctx* ctx, cph_rowlist_impl* r, DevBuf&& dev, uint64_t n, int32_t bits, int32_t out_mem) {
+    r->pub.nrows = n;
+    r->pub.first = 0;
+    r->pub.bits = bits;
+    r->pub.mem = out_mem;
+    if (out_mem == CPH_MEM_DEVICE) {
+        r->d_ids = std::move(dev);
+        r->pub.ids = r->d_ids.get();
+        CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    } else {
+        const size_t b = (size_t)n * (size_t)(bits / 8);
+        CPH_HIP_TRY(hipHostMalloc(&r->h_block, b + 16, hipHostMallocDefault));
+        CPH_HIP_TRY(hipMemcpyAsync(r->h_block, dev.get(), b, hipMemcpyDeviceToHost, ctx->stream));
+        CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        r->pub.ids = r->h_block;
+        dev.reset();
+    }
+    return {};
+}
+
+void set_range(cph_rowlist_impl* r, uint64_t first, uint64_t n, int32_t bits, int32_t out_mem) {
+    r->pub.nrows = n;
+    r->pub.first = first;
+    r->pub.ids = nullptr;
+    r->pub.bits = bits;
+    r->pub.mem = out_mem;
+}
+
+// the program's shape: every rule of the header's comment that does not need the columns
+Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
+    if (nops < 1 || nops > CPH_PRED_MAX_OPS) return {CPH_ERR_INVALID, "cph_filter_rows: a program has 1..64 ops"};
+    int depth = 0, likes = 0;
+    for (int q = 0; q < nops; q++) {
+        const cph_pred_op& o = prog[q];
+        switch (o.op) {
+            case CPH_PRED_LIKE:
+                if (o.arg < -1 || o.arg >= ncols) return {CPH_ERR_INVALID, "cph_filter_rows: LIKE column outside -1..ncols-1"};
+                if (!o.value.data && o.value.len) return {CPH_ERR_INVALID, "cph_filter_rows: a LIKE value with bytes but no data pointer"};
+                if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE terms"};
+                depth++;
+                break;
+            case CPH_PRED_NOT:
+                if (depth < 1) return {CPH_ERR_INVALID, "cph_filter_rows: stack underflow (NOT on an empty stack)"};
+                break;
+            case CPH_PRED_ALL:
+            case CPH_PRED_ANY:
+                if (o.arg < 0 || o.arg > depth) return {CPH_ERR_INVALID, "cph_filter_rows: stack underflow (ALL / ANY pops more than there is)"};
+                depth += 1 - o.arg;
+                break;
+            default:
+                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4)"};
+        }
+        if (depth > CPH_PRED_MAX_STACK) return {CPH_ERR_INVALID, "cph_filter_rows: stack deeper than 32"};
+    }
+    if (depth != 1) return {CPH_ERR_INVALID, "cph_filter_rows: the program must leave exactly one value"};
+    return {};
+}
+
+unsigned filter_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
+
+}  // namespace
+
+extern "C" {
+
+CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
+                                const cph_pred_op* prog, int32_t nops, const cph_filter_opts* opts, int32_t out_mem,
+                                cph_rowlist** out) {
+    if (!ctx || !out) return CPH_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_with(ctx, {CPH_ERR_HIP, "hipSetDevice failed"});
+    *out = nullptr;
+    if (!prog || !opts) return fail_with(ctx, {CPH_ERR_INVALID, "cph_filter_rows: prog and opts must not be NULL"});
+    if (ncols < 0 || ncols > CPH_MAX_KEY_COLS) return fail_with(ctx, {CPH_ERR_INVALID, "cph_filter_rows: 0..16 columns"});
+    if (ncols && !cols) return fail_with(ctx, {CPH_ERR_INVALID, "cph_filter_rows: cols must not be NULL"});
+    if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
+    if (opts->mode != CPH_FILTER_WHERE && opts->mode != CPH_FILTER_TAKE_WHILE && opts->mode != CPH_FILTER_DROP_WHILE)
+        return fail_with(ctx, {CPH_ERR_INVALID, "cph_filter_rows: unknown mode"});
+    if (opts->out_bits != 32 && opts->out_bits != 64) return fail_with(ctx, {CPH_ERR_INVALID, "cph_filter_rows: out_bits must be 32 or 64"});
+    {
+        Status s = check_program(prog, nops, ncols);
+        if (!s.ok()) return fail_with(ctx, s);
+    }
+    const uint64_t n = nrows, first_row = opts->first_row;
+    if (first_row + n < n) return fail_with(ctx, {CPH_ERR_TOO_MANY_ROWS, "cph_filter_rows: first_row + nrows overflows"});
+    if (n > 0xFFFFFFFFull) return fail_with(ctx, {CPH_ERR_TOO_MANY_ROWS, "cph_filter_rows: more than 2^32-1 rows in one call"});
+    if (opts->out_bits == 32 && first_row + n > 0xFFFFFFFFull)
+        return fail_with(ctx, {CPH_ERR_TOO_MANY_ROWS, "cph_filter_rows: first_row + nrows > 2^32-1 needs out_bits 64"});
+    for (int c = 0; c < ncols; c++) {
+        Status s = validate_cols(cols + c, 1);
+        if (!s.ok()) return fail_with(ctx, s);
+        const bool ident = !sel || !sel[c].ids;
+        if (ident && n && cols[c].nrows < first_row + n)
+            return fail_with(ctx, {CPH_ERR_INVALID, "cph_filter_rows: a column without row ids must have first_row + nrows rows"});
+        if (!ident && sel[c].bits != 32 && sel[c].bits != 64) return fail_with(ctx, {CPH_ERR_INVALID, "row id bits must be 32 or 64"});
+    }
+    auto* r = new (std::nothrow) cph_rowlist_impl();
+    if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
+    r->ctx = ctx;
+    const int32_t bits = opts->out_bits;
+    auto run = [&]() -> Status {
+        if (n == 0) {
+            set_range(r, first_row, 0, bits, out_mem);
+            return {};
+        }
+        std::vector<DevBuf> staged;
+        ColsArg arg{};
+        ColIds ids{};
+        for (int c = 0; c < ncols; c++) {
+            CPH_TRY(stage_cols(ctx, cols + c, 1, &staged, &arg.c[c]));
+            if (sel && sel[c].ids) {
+                ids.ids[c].bits = sel[c].bits;
+                ids.ids[c].base = sel[c].base;
+                const size_t w = (size_t)(sel[c].bits / 8);
+                if (cols[c].mem == CPH_MEM_HOST) {   // the ids live where the column lives; only entries [first_row, first_row + n) are read
+                    staged.emplace_back();
+                    CPH_TRY(staged.back().alloc(&ctx->pool, n * w));
+                    CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), static_cast<const uint8_t*>(sel[c].ids) + first_row * w, n * w,
+                                               hipMemcpyHostToDevice, ctx->stream));
+                    ids.ids[c].ptr = reinterpret_cast<const void*>((uintptr_t)staged.back().get() - (uintptr_t)(first_row * w));
+                } else {
+                    ids.ids[c].ptr = sel[c].ids;
+                }
+            }
+        }
+        // the program: LIKE terms over real columns get a bit each, the others are decided here
+        PredProg pp{};
+        std::vector<uint64_t> lits;
+        double col_bytes = 0;
+        uint32_t seen_cols = 0;
+        for (int q = 0; q < nops; q++) {
+            pp.op[q] = (uint8_t)prog[q].op;
+            pp.arg[q] = (uint8_t)prog[q].arg;
+            if (prog[q].op != CPH_PRED_LIKE) continue;
+            const int c = prog[q].arg;
+            const uint64_t len = prog[q].value.len;
+            if (c < 0 || len > 0xFFFFFFFFull || (arg.c[c].fixed_width && arg.c[c].fixed_width != len)) {
+                pp.arg[q] = kTermNever;
+                continue;
+            }
+            PredTerm& t = pp.term[pp.nterms];
+            pp.arg[q] = (uint8_t)pp.nterms++;
+            t.col = c;
+            t.len = (uint32_t)len;
+            t.kind = arg.c[c].fixed_width == 8 && ((uintptr_t)arg.c[c].data & 7u) == 0 ? kTermFix8 : kTermBytes;
+            if (len <= 8) {
+                if (len) memcpy(&t.lit8, prog[q].value.data, (size_t)len);
+            } else {
+                t.lit_off = (uint32_t)lits.size();
+                lits.resize(lits.size() + (size_t)((len + 7) / 8), 0);
+                memcpy(lits.data() + t.lit_off, prog[q].value.data, (size_t)len);
+            }
+            if (!((seen_cols >> c) & 1u)) {   // byte model: a column's offsets and bytes count once
+                seen_cols |= 1u << c;
+                col_bytes += arg.c[c].fixed_width ? (double)arg.c[c].fixed_width * (double)n
+                                                  : ((double)(arg.c[c].offset_bits / 8) + (double)len) * (double)n;
+                if (ids.ids[c].ptr) col_bytes += (double)(ids.ids[c].bits / 8) * (double)n;
+            }
+        }
+        pp.nops = nops;
+        DevBuf litbuf;
+        if (!lits.empty()) {
+            if (lits.size() > 0xFFFFFFFFull / 8) return {CPH_ERR_INVALID, "cph_filter_rows: literals beyond 4 GiB"};
+            const size_t lb = lits.size() * sizeof(uint64_t);
+            CPH_TRY(litbuf.alloc(&ctx->pool, lb));
+            void* slot = nullptr;
+            CPH_TRY(pinned_upload(ctx, lb, &slot));
+            memcpy(slot, lits.data(), lb);
+            CPH_HIP_TRY(hipMemcpyAsync(litbuf.get(), slot, lb, hipMemcpyHostToDevice, ctx->stream));
+            pp.lits = litbuf.as<uint64_t>();
+            pp.lit_words = (uint32_t)lits.size();
+            pp.lits_in_lds = lb <= (size_t)kLitLds;
+        }
+        const uint64_t ntiles = (n + kFiltTile - 1) / kFiltTile;
+        CPH_TRY(ensure_pinned_scratch(ctx, sizeof(uint64_t)));
+        if (opts->mode != CPH_FILTER_WHERE) {
+            DevBuf ff;
+            CPH_TRY(ff.alloc(&ctx->pool, sizeof(uint64_t)));
+            void* slot = nullptr;
+            CPH_TRY(pinned_upload(ctx, sizeof(uint64_t), &slot));
+            memcpy(slot, &n, sizeof n);
+            CPH_HIP_TRY(hipMemcpyAsync(ff.get(), slot, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+            {
+                ProfScope ps(ctx, "k_pred_eval", col_bytes);
+                hipLaunchKernelGGL(k_pred_eval<false>, dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
+                                   (uint64_t*)nullptr, (uint32_t*)nullptr, ff.as<unsigned long long>());
+            }
+            CPH_HIP_TRY(hipGetLastError());
+            uint64_t stop = 0;   // rows in front of the first failing one
+            CPH_TRY(read_device_value(ctx, ff.as<uint64_t>(), &stop));
+            // TakeWhile: [0, stop); DropWhile: [stop, n) — then .Drop(skip).Top(limit)
+            uint64_t lo = opts->mode == CPH_FILTER_TAKE_WHILE ? 0 : stop, hi = opts->mode == CPH_FILTER_TAKE_WHILE ? stop : n;
+            lo = hi - lo > opts->skip ? lo + opts->skip : hi;
+            if (hi - lo > opts->limit) hi = lo + opts->limit;
+            set_range(r, first_row + lo, hi - lo, bits, out_mem);
+            return {};
+        }
+        DevBuf bitmap, counts;
+        CPH_TRY(bitmap.alloc(&ctx->pool, ntiles * kFiltWords * sizeof(uint64_t)));
+        CPH_TRY(counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
+        {
+            ProfScope ps(ctx, "k_pred_eval", col_bytes + (double)n / 8.0 + 4.0 * (double)ntiles);
+            hipLaunchKernelGGL(k_pred_eval<true>, dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
+                               bitmap.as<uint64_t>(), counts.as<uint32_t>(), (unsigned long long*)nullptr);
+        }
+        CPH_HIP_TRY(hipGetLastError());
+        CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));
+        uint32_t total = 0;
+        CPH_TRY(read_device_value(ctx, counts.as<uint32_t>() + ntiles, &total));   // the call's host wait
+        uint64_t kept = total > opts->skip ? total - opts->skip : 0;
+        if (kept > opts->limit) kept = opts->limit;
+        if (kept == 0) {
+            set_range(r, first_row, 0, bits, out_mem);
+            return {};
+        }
+        DevBuf outb;
+        CPH_TRY(outb.alloc(&ctx->pool, kept * (size_t)(bits / 8)));
+        {
+            ProfScope ps(ctx, "k_pred_emit", (double)n / 8.0 + 4.0 * (double)ntiles + (double)kept * (double)(bits / 8));
+            if (bits == 32)
+                hipLaunchKernelGGL(k_pred_emit<uint32_t>, dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap.as<uint64_t>(),
+                                   counts.as<uint32_t>(), ntiles, first_row, opts->skip, opts->skip + kept, outb.as<uint32_t>());
+            else
+                hipLaunchKernelGGL(k_pred_emit<uint64_t>, dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap.as<uint64_t>(),
+                                   counts.as<uint32_t>(), ntiles, first_row, opts->skip, opts->skip + kept, outb.as<uint64_t>());
+        }
+        CPH_HIP_TRY(hipGetLastError());
+        return deliver_ids(ctx, r, std::move(outb), kept, bits, out_mem);
+    };
+    Status s = run();
+    if (!s.ok()) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (r->h_block) (void)hipHostFree(r->h_block);
+        delete r;
+        return fail_with(ctx, s);
+    }
+    *out = &r->pub;
+    return CPH_OK;
+}
+
+CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel_mem, const cph_rowlist* list, int32_t out_mem,
+                                cph_rowlist** out) {
+    if (!ctx || !out) return CPH_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_with(ctx, {CPH_ERR_HIP, "hipSetDevice failed"});
+    *out = nullptr;
+    if (!list) return fail_with(ctx, {CPH_ERR_INVALID, "cph_rowsel_take: list must not be NULL"});
+    if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
+    const bool ident = !sel || !sel->ids;
+    if (!ident && sel_mem != CPH_MEM_HOST && sel_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad sel_mem"});
+    if (!ident && sel->bits != 32 && sel->bits != 64) return fail_with(ctx, {CPH_ERR_INVALID, "row id bits must be 32 or 64"});
+    if (list->ids && list->bits != 32 && list->bits != 64) return fail_with(ctx, {CPH_ERR_INVALID, "cph_rowsel_take: list bits must be 32 or 64"});
+    if (list->ids && list->mem != CPH_MEM_HOST && list->mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "cph_rowsel_take: bad list mem"});
+    auto* r = new (std::nothrow) cph_rowlist_impl();
+    if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
+    r->ctx = ctx;
+    const uint64_t n = list->nrows;
+    auto run = [&]() -> Status {
+        if (n == 0 || (ident && !list->ids)) {   // nothing to gather: an empty list, or a range through the identity
+            set_range(r, n ? list->first : 0, n, list->bits == 64 ? 64 : 32, out_mem);
+            return {};
+        }
+        // the list on the device
+        RowIds lst;
+        DevBuf lbuf;
+        const size_t lw = (size_t)(list->bits / 8);
+        if (list->ids) {
+            lst.bits = list->bits;
+            if (list->mem == CPH_MEM_HOST) {
+                CPH_TRY(lbuf.alloc(&ctx->pool, n * lw));
+                CPH_HIP_TRY(hipMemcpyAsync(lbuf.get(), list->ids, n * lw, hipMemcpyHostToDevice, ctx->stream));
+                lst.ptr = lbuf.get();
+            } else {
+                lst.ptr = list->ids;
+            }
+        }
+        if (ident) {   // a copy of the list in out_mem
+            DevBuf copy;
+            if (list->mem == CPH_MEM_HOST) {
+                copy = std::move(lbuf);
+            } else {
+                CPH_TRY(copy.alloc(&ctx->pool, n * lw));
+                CPH_HIP_TRY(hipMemcpyAsync(copy.get(), list->ids, n * lw, hipMemcpyDeviceToDevice, ctx->stream));
+            }
+            return deliver_ids(ctx, r, std::move(copy), n, list->bits, out_mem);
+        }
+        RowIds s;
+        s.bits = sel->bits;
+        s.base = sel->base;
+        s.ptr = sel->ids;
+        DevBuf sbuf;
+        if (sel_mem == CPH_MEM_HOST) {   // entries 0 .. the list's last (= largest) row number travel to the device
+            uint64_t last = 0;
+            if (!list->ids) {
+                last = list->first + n - 1;
+            } else if (list->mem == CPH_MEM_HOST) {
+                last = list->bits == 32 ? (uint64_t) static_cast<const uint32_t*>(list->ids)[n - 1] : static_cast<const uint64_t*>(list->ids)[n - 1];
+            } else if (list->bits == 32) {
+                uint32_t v = 0;
+                CPH_TRY(read_device_value(ctx, static_cast<const uint32_t*>(list->ids) + (n - 1), &v));
+                last = v;
+            } else {
+                CPH_TRY(read_device_value(ctx, static_cast<const uint64_t*>(list->ids) + (n - 1), &last));
+            }
+            const size_t sb = (size_t)(last + 1) * (size_t)(sel->bits / 8);
+            CPH_TRY(sbuf.alloc(&ctx->pool, sb));
+            CPH_HIP_TRY(hipMemcpyAsync(sbuf.get(), sel->ids, sb, hipMemcpyHostToDevice, ctx->stream));
+            s.ptr = sbuf.get();
+        }
+        DevBuf outb;
+        CPH_TRY(outb.alloc(&ctx->pool, n * (size_t)(sel->bits / 8)));
+        {
+            ProfScope ps(ctx, "k_rowsel_take", (double)n * (double)(lst.ptr ? lw : 0) + 2.0 * (double)n * (double)(sel->bits / 8));
+            hipLaunchKernelGGL(k_rowsel_take, dim3(grid_rows(n)), dim3(kMatThreads), 0, ctx->stream, s, lst, list->first, n, outb.get());
+        }
+        CPH_HIP_TRY(hipGetLastError());
+        return deliver_ids(ctx, r, std::move(outb), n, sel->bits, out_mem);
+    };
+    Status s = run();
+    if (!s.ok()) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (r->h_block) (void)hipHostFree(r->h_block);
+        delete r;
+        return fail_with(ctx, s);
+    }
+    *out = &r->pub;
+    return CPH_OK;
+}
+
+CPH_API void cph_rowlist_release(cph_rowlist* pub) {
+    if (!pub) return;
+    auto* r = reinterpret_cast<cph_rowlist_impl*>(pub);
+    if (r->ctx) (void)hipSetDevice(r->ctx->device);
+    if (r->h_block) (void)hipHostFree(r->h_block);
+    delete r;
+}
+
+}  // extern "C"

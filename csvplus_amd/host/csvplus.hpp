@@ -11,6 +11,9 @@
 //   TakeRows / Take                    :218,:252 csvplus::TakeRows / Take
 //   DataSource.IndexOn / UniqueIndexOn :529,:535 DataSource::IndexOn / UniqueIndexOn
 //   DataSource.Join / Except           :545,:588 DataSource::Join / Except
+//   DataSource.Filter / TakeWhile / DropWhile / Top / Drop :276-374  DataSource::Filter / TakeWhile / DropWhile (over a
+//                                                declarative csvplus::Pred, evaluated on the GPU) / Top / Drop
+//   Like / All / Any / Not           :1243-1293  csvplus::Like / All / Any / Not (plain data, also callable on a Row)
 //   Index.Iterate / Find / SubIndex    :618-641  Index::Iterate / Find / SubIndex
 //   Index.ResolveDuplicates            :643-653  Index::ResolveDuplicates (groups found on the GPU)
 //   Index.WriteTo / LoadIndex          :655-705  Index::WriteTo / LoadIndex (own binary format, not gob)
@@ -135,6 +138,75 @@ inline Row mergeRows(const Row& left, const Row& right) {
     return r;
 }
 
+// ---- the named predicates (:1243-1293) as DATA ---------------------------------------------------------------------------
+// A Go closure cannot run on a GPU; Like / All / Any / Not are declarative and can: DataSource::Filter / TakeWhile / DropWhile
+// compile a Pred to the postfix program of cph_filter_rows.  A Pred is also callable on a Row (the reference's semantics on
+// the host), so it fits wherever a std::function<bool(const Row&)> is wanted.
+class Pred {
+public:
+    enum Kind { kLike, kNot, kAll, kAny };
+    bool operator()(const Row& row) const {
+        switch (kind_) {
+            case kLike:
+                for (const auto& kv : match_) {                                             // :1285-1289
+                    auto it = row.find(kv.first);
+                    if (it == row.end() || it->second != kv.second) return false;
+                }
+                return true;
+            case kNot: return !kids_[0](row);
+            case kAll:
+                for (const auto& k : kids_)
+                    if (!k(row)) return false;
+                return true;
+            default:
+                for (const auto& k : kids_)
+                    if (k(row)) return true;
+                return false;
+        }
+    }
+    Kind kind() const { return kind_; }
+    const Row& match() const { return match_; }
+    const std::vector<Pred>& operands() const { return kids_; }
+
+private:
+    friend Pred Like(Row match);
+    friend Pred Not(Pred p);
+    friend Pred All(std::vector<Pred> preds);
+    friend Pred Any(std::vector<Pred> preds);
+    Kind kind_ = kAll;
+    Row match_;
+    std::vector<Pred> kids_;
+};
+inline Pred Like(Row match) {
+    if (match.empty()) throw Panic("empty match row in Like() predicate");                // :1280-1282
+    Pred p;
+    p.kind_ = Pred::kLike;
+    p.match_ = std::move(match);
+    return p;
+}
+inline Pred Not(Pred q) {
+    Pred p;
+    p.kind_ = Pred::kNot;
+    p.kids_.push_back(std::move(q));
+    return p;
+}
+inline Pred All(std::vector<Pred> preds = {}) {
+    Pred p;
+    p.kind_ = Pred::kAll;
+    p.kids_ = std::move(preds);
+    return p;
+}
+inline Pred Any(std::vector<Pred> preds = {}) {
+    Pred p;
+    p.kind_ = Pred::kAny;
+    p.kids_ = std::move(preds);
+    return p;
+}
+template <class... P>
+inline Pred All(const Pred& first, const P&... more) { return All(std::vector<Pred>{first, more...}); }
+template <class... P>
+inline Pred Any(const Pred& first, const P&... more) { return Any(std::vector<Pred>{first, more...}); }
+
 using RowFunc = std::function<Error(Row)>;
 
 // ---- GPU context shared by the process (the Go API has no context argument) -------------------------
@@ -223,6 +295,48 @@ struct DeviceIndex {   // owns a cph_index
 inline bool allColumnsUnique(const std::vector<std::string>& columns) {
     std::set<std::string> s(columns.begin(), columns.end());
     return s.size() == columns.size();
+}
+
+// A Pred as the postfix program of cph_filter_rows over its own column list.  A row that LACKS a named column must make that
+// Like false (:1286 `!found`), and presence differs row by row, so it cannot be the program's column -1: the staging
+// carries it instead — such a row gets the column's `absent` value, which is one byte longer than the longest literal any
+// Like compares that column with and therefore equals none of them (equality is on the whole value, length first).
+struct PredProgram {
+    std::vector<std::string> columns;   // distinct names, in order of first use
+    std::vector<std::string> absent;    // per column
+    std::vector<cph_pred_op> ops;       // literal pointers point into `pred`
+    std::shared_ptr<const Pred> pred;
+    void emit(const Pred& p) {
+        switch (p.kind()) {
+            case Pred::kLike:
+                for (const auto& kv : p.match()) {
+                    size_t c = (size_t)(std::find(columns.begin(), columns.end(), kv.first) - columns.begin());
+                    if (c == columns.size()) {
+                        columns.push_back(kv.first);
+                        absent.emplace_back();
+                    }
+                    if (absent[c].size() <= kv.second.size()) absent[c].assign(kv.second.size() + 1, '\0');
+                    cph_pred_op op{CPH_PRED_LIKE, (int32_t)c, {reinterpret_cast<const uint8_t*>(kv.second.data()), kv.second.size()}};
+                    ops.push_back(op);
+                }
+                if (p.match().size() > 1) ops.push_back(cph_pred_op{CPH_PRED_ALL, (int32_t)p.match().size(), {nullptr, 0}});
+                break;
+            case Pred::kNot:
+                emit(p.operands()[0]);
+                ops.push_back(cph_pred_op{CPH_PRED_NOT, 0, {nullptr, 0}});
+                break;
+            default:
+                for (const auto& k : p.operands()) emit(k);
+                ops.push_back(cph_pred_op{p.kind() == Pred::kAll ? CPH_PRED_ALL : CPH_PRED_ANY, (int32_t)p.operands().size(), {nullptr, 0}});
+        }
+    }
+};
+inline std::shared_ptr<const PredProgram> compilePred(const Pred& p) {
+    auto prog = std::make_shared<PredProgram>();
+    prog->pred = std::make_shared<const Pred>(p);
+    prog->emit(*prog->pred);
+    if (prog->columns.size() > (size_t)CPH_MAX_KEY_COLS) throw Panic("predicate over more than 16 columns");
+    return prog;
 }
 
 }  // namespace detail
@@ -405,6 +519,39 @@ public:
         });
     }
 
+    // Filter (:276-286), TakeWhile (:346-358), DropWhile (:362-374) over a declarative predicate: the predicate's columns of a
+    // batch of rows (Gpu::join_batch_rows, read ahead as Join does) are staged and evaluated by ONE cph_filter_rows call; the
+    // rows come out in the source's order.  (A predicate that is a closure stays a host affair: `pred(row)` works for a Pred too.)
+    DataSource Filter(const Pred& pred) const { return filterSource(fn_, detail::compilePred(pred), CPH_FILTER_WHERE); }
+    DataSource TakeWhile(const Pred& pred) const { return filterSource(fn_, detail::compilePred(pred), CPH_FILTER_TAKE_WHILE); }
+    DataSource DropWhile(const Pred& pred) const { return filterSource(fn_, detail::compilePred(pred), CPH_FILTER_DROP_WHILE); }
+    // Top (:313-325) / Drop (:329-342): counters, no data involved
+    DataSource Top(uint64_t n) const {
+        Fn src = fn_;
+        return DataSource([src, n](const RowFunc& fn) {
+            uint64_t counter = n;
+            return src([&](Row row) -> Error {
+                if (counter == 0) return io_EOF;
+                counter--;
+                return fn(std::move(row));
+            });
+        });
+    }
+    DataSource Drop(uint64_t n) const {
+        Fn src = fn_;
+        return DataSource([src, n](const RowFunc& fn) {
+            uint64_t counter = n;
+            return src([&](Row row) -> Error {
+                if (counter == 0) return fn(std::move(row));
+                counter--;
+                return Error();
+            });
+        });
+    }
+
+    // cph_filter_rows calls made so far (tests: one per batch)
+    static uint64_t filter_calls() { return filter_calls_counter(); }
+
     // ToRows (:481-490)
     std::pair<std::vector<Row>, Error> ToRows() const {
         std::vector<Row> rows;
@@ -505,6 +652,77 @@ private:
         cph_matches_release(m);
         batch->clear();
         return err;
+    }
+
+    // One batch through cph_filter_rows (mode WHERE: the rows kept; the WHILE modes: a range).  Emits the kept rows to `fn`;
+    // *first / *count describe the answer (WHERE: count only).
+    static Error filterBatch(cph_ctx* ctx, const detail::PredProgram& prog, int32_t mode, std::vector<Row>* batch, const RowFunc& fn,
+                             uint64_t* first, uint64_t* count) {
+        const size_t n = batch->size(), nc = prog.columns.size();
+        *first = 0;
+        *count = 0;
+        if (n == 0) return Error();
+        std::vector<std::vector<const std::string*>> vals(nc);
+        for (size_t c = 0; c < nc; c++) {
+            vals[c].resize(n);
+            for (size_t i = 0; i < n; i++) {
+                auto it = (*batch)[i].find(prog.columns[c]);
+                vals[c][i] = it == (*batch)[i].end() ? &prog.absent[c] : &it->second;   // see detail::PredProgram
+            }
+        }
+        cph_rowlist* rl = nullptr;
+        int32_t rc;
+        {
+            detail::StagedColumns st(ctx, nc);
+            st.stage(vals, n);
+            cph_filter_opts o{mode, 32, 0, 0, UINT64_MAX};
+            rc = cph_filter_rows(ctx, nc ? st.cols() : nullptr, nullptr, (int32_t)nc, n, prog.ops.data(), (int32_t)prog.ops.size(), &o,
+                                 CPH_MEM_HOST, &rl);
+        }
+        if (rc != CPH_OK) {
+            batch->clear();
+            return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+        }
+        filter_calls_counter()++;
+        const uint32_t* ids = static_cast<const uint32_t*>(rl->ids);
+        Error err;
+        for (uint64_t k = 0; k < rl->nrows && !err; k++) err = fn(std::move((*batch)[ids ? ids[k] : rl->first + k]));
+        *first = rl->first;
+        *count = rl->nrows;
+        cph_rowlist_release(rl);
+        batch->clear();
+        return err;
+    }
+    static uint64_t& filter_calls_counter() {
+        static uint64_t n = 0;
+        return n;
+    }
+
+    static DataSource filterSource(Fn src, std::shared_ptr<const detail::PredProgram> prog, int32_t mode) {
+        return DataSource([src, prog, mode](const RowFunc& fn) -> Error {
+            cph_ctx* ctx = Gpu::Default().ctx();
+            const size_t batch_rows = std::max<size_t>(1, Gpu::Default().join_batch_rows);
+            std::vector<Row> batch;
+            batch.reserve(batch_rows);
+            bool yield = false;   // DropWhile: a row has failed, everything passes from here on (:366-368)
+            auto flush = [&]() -> Error {
+                const uint64_t n = batch.size();
+                uint64_t first = 0, count = 0;
+                Error e = filterBatch(ctx, *prog, mode, &batch, fn, &first, &count);
+                if (e) return e;
+                if (mode == CPH_FILTER_TAKE_WHILE && count < n) return io_EOF;   // the predicate failed: the iteration stops (:350-352)
+                if (mode == CPH_FILTER_DROP_WHILE && count) yield = true;
+                return Error();
+            };
+            Error err = src([&](Row row) -> Error {
+                if (yield) return fn(std::move(row));
+                batch.push_back(std::move(row));
+                return batch.size() >= batch_rows ? flush() : Error();
+            });
+            if (err) return err;
+            err = flush();
+            return err.is_eof() ? Error() : err;   // as the source would have mapped it (:238-239)
+        });
     }
 
     // Reads `src` in batches of Gpu::join_batch_rows rows that carry `columns` (SelectValues, :556 / :599: a row without one

@@ -132,6 +132,9 @@ def _rowsel(cols, row_ids, nrows, keep):
         for i, ids in enumerate(row_ids):
             if ids is None:
                 continue
+            if isinstance(ids, tuple) and isinstance(ids[0], np.ndarray):   # (host ids, base)
+                sel[i].base = int(ids[1])
+                ids = ids[0]
             if isinstance(ids, np.ndarray):
                 if ids.dtype != np.uint64:
                     ids = ids.astype(np.uint32)
@@ -192,3 +195,144 @@ def json_write(ctx: N.Context, cols, names, out_mem: int = N.CPH_MEM_HOST, row_i
     out = C.POINTER(N.cph_bytes)()
     ctx._check(ctx.lib.cph_json_write_rows(ctx.handle, arr, sel, hv, len(cols), n, out_mem, C.byref(out)))
     return _take_bytes(ctx, out, out_mem)
+
+
+# ---- Filter / TakeWhile / DropWhile / Top / Drop (cph_filter_rows, cph_rowsel_take) -----------------------------------
+
+_MODES = {"where": N.CPH_FILTER_WHERE, "take_while": N.CPH_FILTER_TAKE_WHILE, "drop_while": N.CPH_FILTER_DROP_WHILE}
+
+
+class RowList:
+    """cph_rowlist: an ascending list of row numbers (valid until release()).  A range (the WHILE modes, or an empty
+    result) has no array behind it: `ids_ptr` is 0 and the rows are first, first + 1, ..."""
+
+    def __init__(self, ctx, ptr):
+        self.ctx, self.ptr = ctx, ptr
+        c = ptr.contents
+        self.nrows, self.first, self.bits, self.mem = int(c.nrows), int(c.first), int(c.bits), int(c.mem)
+        self.ids_ptr = int(c.ids or 0)
+        self.is_range = self.ids_ptr == 0
+        ctx._children.add(self)
+
+    def __len__(self):
+        return self.nrows
+
+    def to_numpy(self) -> np.ndarray:
+        """The row numbers on the host (a copy): only for lists in host memory and ranges."""
+        dt = np.uint32 if self.bits == 32 else np.uint64
+        if self.is_range:
+            return (np.arange(self.nrows, dtype=np.uint64) + np.uint64(self.first)).astype(dt)
+        assert self.mem == N.CPH_MEM_HOST, "a device row list has no host view: consume it on the device"
+        return N._ptr_array(self.ids_ptr, self.nrows, dt).copy()
+
+    def as_row_ids(self):
+        """(device_ptr, bits, count): the tuple csv_write / json_write / gather_rows take as row ids of a device column."""
+        assert self.mem == N.CPH_MEM_DEVICE and not self.is_range, "a range has no array: use first / nrows"
+        return (self.ids_ptr, self.bits, self.nrows)
+
+    def release(self):
+        if self.ptr:
+            self.ctx.lib.cph_rowlist_release(self.ptr)
+            self.ptr = None
+
+    close = release
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _pred_program(ops, keep):
+    arr = (N.cph_pred_op * max(len(ops), 1))()
+    for i, (op, arg, value) in enumerate(ops):
+        arr[i].op, arr[i].arg = int(op), int(arg)
+        if value is not None:
+            b = np.frombuffer(bytes(value), dtype=np.uint8)
+            keep.append(b)
+            arr[i].value.data = b.ctypes.data if len(b) else None
+            arr[i].value.len = len(b)
+    return arr
+
+
+def filter_rows(ctx: N.Context, cols_by_name, pred, row_ids=None, nrows=None, mode: str = "where", first_row: int = 0,
+                skip: int = 0, limit=None, out_bits=None, out_mem: int = N.CPH_MEM_HOST, as_handle: bool = False):
+    """Filter(pred) / TakeWhile / DropWhile with Drop and Top on either side, evaluated on the device (cph_filter_rows).
+
+    cols_by_name: {column name: StrCol} — the row the predicate sees; a name the predicate uses and the mapping lacks
+    makes its Like false (csvplus.go:1286).  row_ids: {name: ids} (numpy uint32 / uint64, or (numpy ids, base), for host
+    columns; (device_ptr, bits, count[, base]) for device columns) for columns read through row ids, e.g. a Join's; nrows = the rows of the
+    selection to look at, counted from first_row (default: all behind first_row).  mode: "where", "take_while",
+    "drop_while"; skip / limit: Drop / Top behind the filter.  out_bits defaults to 32 when the rows fit.
+
+    Returns the row numbers (positions in the selection) as a numpy array (out_mem HOST) or a RowList handle (DEVICE, or
+    as_handle=True)."""
+    from . import predicates as P
+
+    names, ops = P.compile(pred, list(cols_by_name))
+    cols = [cols_by_name[nm] for nm in names]
+    ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
+    keep = []
+    if cols:
+        arr, sel, total = _rowsel(cols, ids, None, keep)
+    else:
+        arr, sel, total = None, None, 0
+        if nrows is None and cols_by_name:
+            total = min(c.nrows for c in cols_by_name.values())
+    n = max(total - first_row, 0) if nrows is None else int(nrows)
+    if out_bits is None:
+        out_bits = 32 if first_row + n <= 0xFFFFFFFF else 64
+    opts = N.cph_filter_opts(_MODES[mode], int(out_bits), int(first_row), int(skip), N.CPH_NO_LIMIT if limit is None else int(limit))
+    prog = _pred_program(ops, keep)
+    out = C.POINTER(N.cph_rowlist)()
+    ctx._check(ctx.lib.cph_filter_rows(ctx.handle, arr, sel, len(cols), n, prog, len(ops), C.byref(opts), out_mem, C.byref(out)))
+    del keep
+    return _take_rowlist(ctx, out, out_mem, as_handle)
+
+
+def _take_rowlist(ctx, out, out_mem, as_handle):
+    rl = RowList(ctx, out)
+    if out_mem == N.CPH_MEM_DEVICE or as_handle:
+        return rl
+    res = rl.to_numpy()
+    rl.release()
+    return res
+
+
+def take_rows(ctx: N.Context, row_ids, rows, out_mem: int = N.CPH_MEM_HOST, as_handle: bool = False):
+    """out[i] = row_ids[rows[i]] - base (cph_rowsel_take): the row ids of a Join narrowed to the rows a Filter kept.
+    row_ids: numpy uint32 / uint64 or (numpy ids, base) (host), (device_ptr, bits, count[, base]) (device), or None
+    (identity: a copy of `rows`).  rows: a RowList, or a numpy uint32 / uint64 array.  Returns numpy (HOST) or a RowList (DEVICE / as_handle)."""
+    keep = []
+    sel, sel_mem = None, N.CPH_MEM_HOST
+    if row_ids is not None:
+        sel = N.cph_rowsel()
+        if isinstance(row_ids, tuple) and isinstance(row_ids[0], np.ndarray):
+            sel.base = int(row_ids[1])
+            row_ids = row_ids[0]
+        if isinstance(row_ids, np.ndarray):
+            if row_ids.dtype != np.uint64:
+                row_ids = row_ids.astype(np.uint32)
+            row_ids = np.ascontiguousarray(row_ids)
+            keep.append(row_ids)
+            sel.ids, sel.bits = row_ids.ctypes.data if len(row_ids) else None, row_ids.dtype.itemsize * 8
+        else:
+            sel.ids, sel.bits = int(row_ids[0]) or None, int(row_ids[1])
+            sel.base = int(row_ids[3]) if len(row_ids) > 3 else 0
+            sel_mem = N.CPH_MEM_DEVICE
+    if isinstance(rows, RowList):
+        lst = rows.ptr
+    else:
+        a = np.asarray(rows)
+        if a.dtype != np.uint64:
+            a = a.astype(np.uint32)
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        rl = N.cph_rowlist(len(a), 0, a.ctypes.data if len(a) else None, a.dtype.itemsize * 8, N.CPH_MEM_HOST)
+        keep.append(rl)
+        lst = C.pointer(rl)
+    out = C.POINTER(N.cph_rowlist)()
+    ctx._check(ctx.lib.cph_rowsel_take(ctx.handle, C.byref(sel) if sel is not None else None, sel_mem, lst, out_mem, C.byref(out)))
+    del keep
+    return _take_rowlist(ctx, out, out_mem, as_handle)

@@ -6,7 +6,8 @@
 CSV bytes -> columns (cph_csv_parse) -> indices (cph_index_build) -> fused chained join (cph_join_chain) ->
 output columns (cph_gather_rows: mergeRows, csvplus.go:571-583, column by column) -> CSV bytes
 (cph_csv_write: ToCsv, :379-406; or JSON bytes, cph_json_write_rows: ToJSON, :446-480).  Nothing leaves HBM between
-the first and the last step.
+the first and the last step — also not with a Filter(pred).Drop(skip).Top(limit) between the Join and the writer
+(`where`, `skip`, `limit`: cph_filter_rows over the joined rows, cph_rowsel_take on every column's row ids).
 """
 from __future__ import annotations
 
@@ -44,7 +45,7 @@ def read_table(ctx: N.Context, text: bytes, select=None, **kw) -> Table:
 
 
 def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict | None = None, out_mem: int = N.CPH_MEM_HOST,
-                fused: bool = True, positions: bool | None = None):
+                fused: bool = True, positions: bool | None = None, where=None, skip: int = 0, limit=None):
     """steps: [(index_table, index_key_column, stream_key_column), ...] — each index must be unique on its key
     (UniqueIndexOn; a duplicate raises like the reference's error :751).  out_columns: [(output name, table,
     column)] where table is `stream` or one of the index tables; the caller resolves name collisions the way
@@ -56,13 +57,16 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
     (default): whichever is cheaper by the measured costs (profiles/r04_pipeline.txt) — putting a payload column in index
     order costs ~0.3 ms per 1e7 table rows, reporting positions saves ~1.0 ms per 1e8 stream rows, so a one-shot pipeline
     whose stream is only a few times longer than its build tables keeps row ids.
+    where / skip / limit: Join(...).Filter(where).Drop(skip).Top(limit) in front of the writer — `where` is a predicate of
+    csvplus_amd.predicates (Like, All, Any, Not) over the JOINED row: a name is looked up in the stream first, then in
+    steps[0]'s table, steps[1]'s, ... (mergeRows: the stream's value wins); a name none of them has makes its Like false.
     Returns the CSV text (header + joined rows, stream order): bytes, or a DeviceBytes handle for out_mem DEVICE."""
     def lap(name, t0):
         if timings is not None:
             ctx.synchronize()
             timings[name] = timings.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
 
-    with _joined(ctx, stream, steps, out_columns, lap, positions) as (cols, ids, n, bufs):
+    with _joined(ctx, stream, steps, out_columns, lap, positions, where, skip, limit) as (cols, ids, n, bufs):
         t0 = time.perf_counter()
         from .materialize import csv_write
         if fused:
@@ -86,13 +90,25 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
 
 
 @contextlib.contextmanager
-def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions):
+def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions, where=None, skip=0, limit=None):
     """Index, chain and output columns of a Join(...) over `steps`: yields (cols, ids, n, bufs) — per output column the column
     to read and its row ids for the writers (csv_write / json_write row_ids), the joined row count, and a list whose
-    ColBufs are released on exit (with the indexes and the chain)."""
+    ColBufs are released on exit (with the indexes and the chain).  where / skip / limit: see join_to_csv; the rows the
+    filter keeps replace the joined rows (every column's row ids narrowed on the device)."""
+    filtered = where is not None or skip or limit is not None
+    pred_columns = []   # (name, table, name) of the columns the predicate reads, resolved like mergeRows does
+    if filtered:
+        from . import predicates as P
+        if where is None:
+            where = P.All()   # Drop / Top alone: every row holds
+        merged = {}
+        for tab in [stream] + [t for t, _, _ in steps]:
+            for name in tab.cols:
+                merged.setdefault(name, tab)
+        pred_columns = [(name, merged[name], name) for name in P.compile(where, list(merged))[0]]
     if positions is None:
         payload = {}
-        for _, tab, col in out_columns:
+        for _, tab, col in list(out_columns) + pred_columns:
             if tab is not stream:
                 payload[(id(tab), col)] = tab.nrows
         positions = 1.0e-8 * stream.nrows > 3.0e-8 * sum(payload.values())
@@ -110,7 +126,7 @@ def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions):
         sorted_cols = {}   # (table number, column) -> that column in index order
         if positions:
             from .materialize import permute_col
-            for _, tab, col in out_columns:
+            for _, tab, col in list(out_columns) + pred_columns:
                 if tab is not stream and (tabs.index(tab), col) not in sorted_cols:
                     cb = permute_col(ctx, indices[tabs.index(tab)], tab[col])
                     bufs.append(cb)
@@ -122,13 +138,38 @@ def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions):
         ptrs = ch.device_ptrs()
         n = ch.nrows
         lap("join_ms", t0)
-        cols, ids = [], []
-        for _, tab, col in out_columns:
-            cols.append(tab[col] if tab is stream or not positions else sorted_cols[(tabs.index(tab), col)])
-            if tab is stream:
-                ids.append(None if ch.identity or n == 0 else (ptrs["stream_row"], 64, n))
-            else:
-                ids.append((ptrs["build_row"][tabs.index(tab)], 32, n))
+        def resolve(columns):
+            cols, ids = [], []
+            for _, tab, col in columns:
+                cols.append(tab[col] if tab is stream or not positions else sorted_cols[(tabs.index(tab), col)])
+                if tab is stream:
+                    ids.append(None if ch.identity or n == 0 else (ptrs["stream_row"], 64, n))
+                else:
+                    ids.append((ptrs["build_row"][tabs.index(tab)], 32, n))
+            return cols, ids
+
+        cols, ids = resolve(out_columns)
+        if filtered and n:
+            t0 = time.perf_counter()
+            from .materialize import filter_rows, take_rows
+            pcols, pids = resolve(pred_columns)
+            names = [name for name, _, _ in pred_columns]
+            kept = filter_rows(ctx, dict(zip(names, pcols)), where, row_ids=dict(zip(names, pids)), nrows=n, skip=skip, limit=limit,
+                               out_mem=N.CPH_MEM_DEVICE)
+            bufs.append(kept)
+            narrowed = {}   # the columns of one table share their row ids: one gather per distinct array
+            for k, i in enumerate(ids):
+                if len(kept) == 0:
+                    break
+                if i is None:
+                    ids[k] = kept.as_row_ids()
+                    continue
+                if i not in narrowed:
+                    narrowed[i] = take_rows(ctx, i, kept, out_mem=N.CPH_MEM_DEVICE)
+                    bufs.append(narrowed[i])
+                ids[k] = narrowed[i].as_row_ids()
+            n = len(kept)
+            lap("filter_ms", t0)
         if n == 0:
             cols, ids = [c.head(0) for c in cols], [None] * len(cols)
         yield cols, ids, n, bufs
@@ -142,11 +183,12 @@ def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions):
 
 
 def join_to_json(ctx: N.Context, stream: Table, steps, out_columns=None, timings: dict | None = None, out_mem: int = N.CPH_MEM_HOST,
-                 positions: bool | None = None):
+                 positions: bool | None = None, where=None, skip: int = 0, limit=None):
     """Join(...).ToJSON() (csvplus.go:446-480) over the steps of join_to_csv, written by cph_json_write_rows with mergeRows
     folded into the writer.  out_columns: [(output name, table, column)] as in join_to_csv, the names all different; None
     (default): what the reference's joined rows hold — every column of the stream and of every index table, a name present
     in several of them taken from the first of stream, steps[0], steps[1], ... (nested mergeRows, :559-560, :571-583).
+    where / skip / limit: Filter(where).Drop(skip).Top(limit) in front of the writer, as in join_to_csv.
     Returns the JSON text: bytes, or a DeviceBytes handle for out_mem DEVICE."""
     if out_columns is None:
         out_columns, seen = [], set()
@@ -161,9 +203,35 @@ def join_to_json(ctx: N.Context, stream: Table, steps, out_columns=None, timings
             ctx.synchronize()
             timings[name] = timings.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
 
-    with _joined(ctx, stream, steps, out_columns, lap, positions) as (cols, ids, n, _):
+    with _joined(ctx, stream, steps, out_columns, lap, positions, where, skip, limit) as (cols, ids, n, _):
         t0 = time.perf_counter()
         from .materialize import json_write
         text = json_write(ctx, cols, [name for name, _, _ in out_columns], out_mem=out_mem, row_ids=ids, nrows=n)
         lap("to_json_ms", t0)
         return text
+
+
+def filter_to_csv(ctx: N.Context, table: Table, pred, out_columns, mode: str = "where", first_row: int = 0, nrows=None,
+                  skip: int = 0, limit=None, out_mem: int = N.CPH_MEM_HOST):
+    """The reference's headline shape, FromFile(...).Filter(Like(...)).ToCsv(...), on the device: the rows of ONE table
+    where `pred` holds (mode "where"; "take_while" / "drop_while" for TakeWhile / DropWhile; first_row / nrows: Drop / Top
+    in front of the filter, skip / limit: behind it), written as CSV.  out_columns: column names, or (output name, column)
+    pairs.  Returns the CSV text: bytes, or a DeviceBytes handle for out_mem DEVICE."""
+    from . import predicates as P
+    from .materialize import csv_write, filter_rows
+
+    pairs = [(c, c) if isinstance(c, str) else tuple(c) for c in out_columns]
+    kept = filter_rows(ctx, table.cols, pred, nrows=nrows, mode=mode, first_row=first_row, skip=skip, limit=limit,
+                       out_mem=N.CPH_MEM_DEVICE)
+    try:
+        if kept.is_range and len(kept) and kept.first:   # a WHILE mode's answer that does not start at row 0: as an array
+            rng = filter_rows(ctx, table.cols, P.All(), nrows=len(kept), first_row=kept.first, out_mem=N.CPH_MEM_DEVICE)
+            kept.release()
+            kept = rng
+        cols = [table[c] for _, c in pairs]
+        header = [name for name, _ in pairs]
+        if kept.is_range:   # rows 0 .. len - 1 (or none)
+            return csv_write(ctx, [c.head(len(kept)) for c in cols], header, out_mem=out_mem)
+        return csv_write(ctx, cols, header, out_mem=out_mem, row_ids=[kept.as_row_ids()] * len(cols), nrows=len(kept))
+    finally:
+        kept.release()

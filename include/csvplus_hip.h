@@ -697,6 +697,85 @@ CPH_API void    cph_bytes_release(cph_bytes* b);
 CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, const cph_strval* names,
                                     int32_t ncols, uint64_t nrows, int32_t out_mem, cph_bytes** out);
 
+/* ---- Filter / TakeWhile / DropWhile / Top / Drop with the named predicates (csvplus.go:276-374, :1243-1293) ---- */
+/*
+ * The reference's declarative predicates — Like (:1277-1293), All (:1243-1253), Any (:1258-1268), Not (:1271-1275) — as a
+ * small POSTFIX PROGRAM over the columns of a call, so that any nesting of the four is one flat host array.  Every op
+ * works on a stack of booleans, evaluated per row:
+ *   CPH_PRED_LIKE  push (value of column `arg` of this row == value); arg = -1: the row has no such column, push false
+ *                  (:1286 `!found`).  Equality is bytewise on the whole value: same length, same bytes, any byte value
+ *                  (NUL included); the empty literal equals the empty value.
+ *   CPH_PRED_NOT   pop a, push !a
+ *   CPH_PRED_ALL   pop `arg` operands, push their AND; arg == 0 pushes true
+ *   CPH_PRED_ANY   pop `arg` operands, push their OR;  arg == 0 pushes false
+ * Like(Row{"a": x, "b": y}) is  LIKE a x, LIKE b y, ALL 2.  A program must leave exactly one value.  Limits (checked):
+ * at most CPH_PRED_MAX_OPS ops, at most CPH_PRED_MAX_LIKE LIKE ops, a stack of at most CPH_PRED_MAX_STACK values; the
+ * literal of a LIKE may have any length.
+ */
+enum { CPH_PRED_LIKE = 1, CPH_PRED_NOT = 2, CPH_PRED_ALL = 3, CPH_PRED_ANY = 4 };
+#define CPH_PRED_MAX_OPS   64
+#define CPH_PRED_MAX_LIKE  32
+#define CPH_PRED_MAX_STACK 32
+typedef struct {
+    int32_t    op;      /* CPH_PRED_* */
+    int32_t    arg;     /* LIKE: column (index into cols) or -1; ALL / ANY: operand count; NOT: ignored */
+    cph_strval value;   /* LIKE only; host memory */
+} cph_pred_op;
+
+enum { CPH_FILTER_WHERE = 0, CPH_FILTER_TAKE_WHILE = 1, CPH_FILTER_DROP_WHILE = 2 };
+typedef struct {
+    int32_t  mode;       /* CPH_FILTER_WHERE       Filter(pred):    the rows where pred holds (:276-286)
+                            CPH_FILTER_TAKE_WHILE  TakeWhile(pred): the rows before the first row where it fails (:346-358)
+                            CPH_FILTER_DROP_WHILE  DropWhile(pred): that row and all rows after it (:362-374)            */
+    int32_t  out_bits;   /* 32 or 64: width of the row numbers written                                                */
+    uint64_t first_row;  /* the call looks at rows [first_row, first_row + nrows) of the selection:
+                            src.Drop(first_row).Top(nrows) IN FRONT of the filter (:313-342)                          */
+    uint64_t skip;       /* .Drop(skip) BEHIND the filter                                                             */
+    uint64_t limit;      /* .Top(limit) behind that; UINT64_MAX = no limit                                            */
+} cph_filter_opts;
+
+/* An ascending list of row numbers; library-owned until cph_rowlist_release. */
+typedef struct {
+    uint64_t    nrows;
+    uint64_t    first;   /* ids == NULL: the list is the range first, first + 1, ... (the two WHILE modes always answer
+                            this way: nothing is materialised)                                                        */
+    const void* ids;     /* `bits`-wide row numbers in `mem`, ascending = the reference's emission order              */
+    int32_t     bits, mem;
+} cph_rowlist;
+
+/*
+ * cols / sel / nrows mean exactly what they mean for cph_csv_write_rows and cph_json_write_rows (host or device columns,
+ * fixed-width or 32 / 64-bit offsets, per-column uint32 / uint64 row ids with a base, living where the column lives), so
+ * a predicate can be evaluated over JOINED rows without materialising them.  The only difference: the call looks at the
+ * selection's rows [first_row, first_row + nrows), so an identity column needs at least first_row + nrows rows (rather
+ * than exactly nrows) and a row-id array at least that many entries.  ncols may be 0 (and cols NULL) for a program
+ * without LIKE terms over real columns.  The row numbers written are POSITIONS IN THAT SELECTION (they include first_row),
+ * i.e. directly usable as cph_rowsel.ids / row_ids / row_sel of every consumer whose columns are identity columns.
+ * The predicate's strings are read once (one evaluation kernel per call); WHERE keeps a bitmap of one bit per row between
+ * its two kernels.  The result is complete when the call returns (the other calls' rule).
+ *
+ * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / prog / opts / out, cols NULL with ncols > 0, nops outside
+ * 1..CPH_PRED_MAX_OPS, an op outside 1..4, a LIKE column outside -1..ncols-1, a LIKE value with a length but no pointer,
+ * a negative or too large ALL / ANY count (stack underflow), a NOT on an empty stack, a program that does not leave
+ * exactly one value, the limits above, out_bits or row-id bits other than 32 / 64, an unknown mode or out_mem, a short
+ * identity column.  CPH_ERR_TOO_MANY_ROWS when out_bits == 32 and first_row + nrows > 2^32 - 1, and when nrows alone is
+ * (the count of kept rows is a 32-bit number).  nrows == 0 is legal and yields an empty list.
+ */
+CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
+                                const cph_pred_op* prog, int32_t nops, const cph_filter_opts* opts, int32_t out_mem,
+                                cph_rowlist** out);
+CPH_API void    cph_rowlist_release(cph_rowlist* list);
+
+/*
+ * The companion for consumers whose columns are NOT identity columns: out[i] = sel->ids[list[i]] - sel->base — a plain
+ * gather, as wide as sel->ids, base 0 — which is how the per-column row ids of a Join are narrowed to the rows a Filter
+ * kept.  sel == NULL or sel->ids == NULL (the identity) returns a copy of the list (a range stays a range).  sel->ids
+ * live in sel_mem and must have more entries than the list's largest row number; a list in the other memory space is
+ * copied across first.  The result lives in out_mem.
+ */
+CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel_mem, const cph_rowlist* list, int32_t out_mem,
+                                cph_rowlist** out);
+
 /* ---- CSV ingest: bytes -> SoA string columns (csvplus.go:1080-1146) ----------- */
 /*
  * Replaces the parse loop of Reader.Iterate (csv.NewReader + one map per line,
