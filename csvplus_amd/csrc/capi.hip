@@ -458,6 +458,63 @@ Status stage_cols(cph_ctx* ctx, const cph_strcol* cols, int32_t ncols, std::vect
     return {};
 }
 
+Status check_row_sources(const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t first_row, uint64_t nrows, bool exact) {
+    for (int c = 0; c < ncols; c++) {
+        CPH_TRY(validate_cols(cols + c, 1));
+        const bool ident = !sel || !sel[c].ids;
+        if (ident && nrows && (exact ? cols[c].nrows != nrows : cols[c].nrows < first_row + nrows))
+            return {CPH_ERR_INVALID, exact ? "a column without row ids must have nrows rows"
+                                           : "a column without row ids must have at least first_row + nrows rows"};
+        if (!ident && sel[c].bits != 32 && sel[c].bits != 64) return {CPH_ERR_INVALID, "row id bits must be 32 or 64"};
+    }
+    return {};
+}
+
+Status stage_row_sources(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, const int* order, int32_t ncols, uint64_t first_row,
+                         uint64_t n, std::vector<DevBuf>* staged, ColsArg* arg, ColIds* ids) {
+    for (int k = 0; k < ncols; k++) {
+        const int c = order ? order[k] : k;
+        CPH_TRY(stage_cols(ctx, cols + c, 1, staged, &arg->c[k]));
+        if (!sel || !sel[c].ids || !n) continue;
+        RowIds& r = ids->ids[k];
+        r.bits = sel[c].bits;
+        r.base = sel[c].base;
+        r.ptr = sel[c].ids;
+        if (cols[c].mem == CPH_MEM_HOST) {   // the ids live where the column lives
+            const size_t w = (size_t)(sel[c].bits / 8);
+            staged->emplace_back();
+            CPH_TRY(staged->back().alloc(&ctx->pool, n * w));
+            CPH_HIP_TRY(hipMemcpyAsync(staged->back().get(), static_cast<const uint8_t*>(sel[c].ids) + first_row * w, n * w,
+                                       hipMemcpyHostToDevice, ctx->stream));
+            r.ptr = reinterpret_cast<const void*>((uintptr_t)staged->back().get() - (uintptr_t)(first_row * w));
+        }
+    }
+    return {};
+}
+
+Status deliver(cph_ctx* ctx, ResultOwner* owner, const ResultPart* parts, int nparts, int32_t out_mem) {
+    auto show = [](const ResultPart& p, const void* v) { memcpy(p.pub, &v, sizeof v); };
+    auto padded = [](const ResultPart& p) { return (p.bytes + 15) & ~(size_t)15; };
+    uint8_t* h = nullptr;
+    if (out_mem == CPH_MEM_HOST) {
+        size_t need = 16;
+        for (int i = 0; i < nparts; i++) need += padded(parts[i]);
+        CPH_HIP_TRY(hipHostMalloc(&owner->h_block, need, hipHostMallocDefault));
+        h = static_cast<uint8_t*>(owner->h_block);
+    }
+    for (int i = 0; i < nparts; i++) {
+        const ResultPart& p = parts[i];
+        const void* src = p.src ? p.src : p.dev->get();
+        if (h && p.bytes) CPH_HIP_TRY(hipMemcpyAsync(h, src, p.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        show(p, h ? h : src);
+        if (h) h += padded(p);
+    }
+    CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (h)
+        for (int i = 0; i < nparts; i++) parts[i].dev->reset();
+    return {};
+}
+
 static int32_t fail(cph_ctx* ctx, const Status& s) {
     if (ctx) ctx->err = s.msg;
     return s.code;

@@ -6,11 +6,6 @@
 
 namespace cph {
 
-// Kernel-argument bundle: the key columns of one table.
-struct ColsArg {
-    DevCol c[kMaxKeyCols];
-};
-
 // Offset of the first byte `d` in the value [begin, begin + len) of `data`, len when it holds none.  Generic and
 // unhurried (a loop over the value's 8-byte chunks): the virtual columns of a split codec on the probe side; the build
 // kernels of keycodec.hip find the delimiter in registers.

@@ -538,6 +538,25 @@ struct DevCol {
     uint16_t split = 0;
     uint16_t part = 0;
 };
+// Kernel-argument bundle: the key columns of one table.
+struct ColsArg {
+    DevCol c[kMaxKeyCols];
+};
+// Which row of a column feeds output row i (source_row, materialize_device.hpp).
+struct RowIds {
+    const void* ptr = nullptr;   // null: identity
+    int32_t bits = 32;
+    uint64_t base = 0;
+    // CSV writer, gathered columns: the length pass leaves (begin | length << 32) of the value it looked up per OUTPUT row
+    // here, and the copy pass reads that stream instead of fetching row id + offsets again (one random sector less per row)
+    uint64_t* stash = nullptr;
+};
+// Per column: which row of the column feeds output row i (NULL ids: row i itself).  This is mergeRows
+// (csvplus.go:571-583) folded into the writer: the joined row's fields are read straight from the tables
+// through the row-id tuples of the join.
+struct ColIds {
+    RowIds ids[kMaxKeyCols];
+};
 // The key columns as the codec sees them: `real` = the table's (or the stream's) leading nreal key columns; a split
 // codec gets its split column twice (prefix part, suffix part).  Returns the number of virtual columns written to out
 // (room for kMaxKeyCols).
@@ -809,11 +828,62 @@ Status pinned_upload(cph_ctx* ctx, size_t bytes, void** out);   // staging slot 
 Status validate_cols(const cph_strcol* cols, int32_t ncols);
 // Makes columns device resident (host columns are copied into pool blocks kept alive by `storage`).
 Status stage_cols(cph_ctx* ctx, const cph_strcol* cols, int32_t ncols, std::vector<DevBuf>* storage, DevCol* out);
+// Row sources = columns read through optional row ids (cph_rowsel): what the gather, the writers and Filter take.
+// Per column: validate_cols | a column without ids has nrows rows (exact) or at least first_row + nrows | id bits 32 / 64.
+Status check_row_sources(const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t first_row, uint64_t nrows, bool exact);
+// arg->c[k] / ids->ids[k] = column order[k] (order == nullptr: k) on the device.  Ids of a host column are uploaded — only
+// entries [first_row, first_row + n), the pointer biased so that entry i is still found at index i; n == 0: no ids are touched.
+Status stage_row_sources(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, const int* order, int32_t ncols, uint64_t first_row,
+                         uint64_t n, std::vector<DevBuf>* staged, ColsArg* arg, ColIds* ids);
 
 // Records the error text on the ctx and returns the status code (every extern "C" entry point ends through this).
 inline int32_t fail_with(cph_ctx* ctx, const Status& s) {
     if (ctx) ctx->err = s.msg;
     return s.code;
+}
+
+// ---- library-owned results (cph_colbuf, cph_bytes, cph_rowlist, cph_groups, cph_csv_table) ------------------------
+// What every result object holds right behind its public struct `pub`: the ctx it was made on and, for a result in host
+// memory, the one page-locked block its public pointers point into.
+struct ResultOwner {
+    cph_ctx* ctx = nullptr;
+    void* h_block = nullptr;
+    ResultOwner() = default;
+    ResultOwner(const ResultOwner&) = delete;
+    ResultOwner& operator=(const ResultOwner&) = delete;
+    ~ResultOwner() {
+        if (h_block) (void)hipHostFree(h_block);
+    }
+};
+struct ResultPart {
+    DevBuf* dev;                 // the device block that holds the part
+    size_t bytes;
+    void* pub;                   // address of the public pointer (an object pointer of any type) that shows the part
+    const void* src = nullptr;   // the part's first byte where that is not dev's (several parts in one block)
+};
+// Hands the parts over and waits for the stream (the call's last synchronisation).  CPH_MEM_DEVICE: the public pointers show
+// the device blocks.  CPH_MEM_HOST: one page-locked block (every part on a 16-byte boundary), the non-empty parts copied
+// into it, the device blocks given back.
+Status deliver(cph_ctx* ctx, ResultOwner* owner, const ResultPart* parts, int nparts, int32_t out_mem);
+
+// The end of an entry point that filled the result object `r` (struct { Pub pub; ResultOwner own; ... }): hands it out, or
+// on failure waits for the kernels that may still write its blocks, frees it and records the error.
+template <class Impl, class Pub>
+int32_t finish_call(cph_ctx* ctx, Impl* r, const Status& s, Pub** out) {
+    if (!s.ok()) {
+        (void)hipStreamSynchronize(ctx->stream);
+        delete r;
+        return fail_with(ctx, s);
+    }
+    *out = &r->pub;
+    return CPH_OK;
+}
+template <class Impl, class Pub>
+void release_result(Pub* pub) {
+    if (!pub) return;
+    auto* r = reinterpret_cast<Impl*>(pub);
+    if (r->own.ctx) (void)hipSetDevice(r->own.ctx->device);
+    delete r;
 }
 
 // One value device -> host through the ctx's pinned scratch; synchronises the stream.

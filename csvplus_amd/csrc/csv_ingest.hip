@@ -1112,9 +1112,8 @@ using namespace cph;
 
 struct cph_csv_table_impl {
     cph_csv_table pub;   // first
-    cph_ctx* ctx = nullptr;
+    ResultOwner own;
     DevBuf d_data[CPH_MAX_KEY_COLS], d_offs;
-    void* h_block = nullptr;
 };
 
 // The fast path's host side: count pass, one scan, copy pass — tried FIRST (it needs neither the quote parity nor the separator
@@ -1229,7 +1228,7 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
         if (col_index[c] < 0) return fail_with(ctx, {CPH_ERR_INVALID, "negative field index"});
     auto* t = new (std::nothrow) cph_csv_table_impl();
     if (!t) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
-    t->ctx = ctx;
+    t->own.ctx = ctx;
     auto run = [&]() -> Status {
         CsvOpts o{opt->comma, opt->comment, opt->trim_leading_space ? 1 : 0};
         CsvCols cc{};
@@ -1435,63 +1434,23 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
         }   // (!fast_done)
         t->pub.nrecords = nout;
         t->pub.ncols = ncols;
-        // publish
-        if (out_mem == CPH_MEM_DEVICE) {
-            for (int c = 0; c < ncols; c++) {
-                cph_strcol& sc = t->pub.cols[c];
-                sc.data = t->d_data[c].as<uint8_t>();
-                sc.offsets = col_offs(c);
-                sc.nrows = nout;
-                sc.offset_bits = off32 ? 32 : 64;
-                sc.mem = CPH_MEM_DEVICE;
-                sc.fixed_width = 0;
-            }
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        } else {
-            const size_t ocol = (((nout + 1) * osz) + 15) & ~(size_t)15;
-            size_t need = (size_t)ncols * ocol;
-            for (int c = 0; c < ncols; c++) need += (totals[(size_t)c] + 15) & ~(size_t)15;
-            CPH_HIP_TRY(hipHostMalloc(&t->h_block, need + 16, hipHostMallocDefault));
-            uint8_t* h = static_cast<uint8_t*>(t->h_block);
-            for (int c = 0; c < ncols; c++)
-                CPH_HIP_TRY(hipMemcpyAsync(h + (size_t)c * ocol, col_offs(c), (nout + 1) * osz, hipMemcpyDeviceToHost, ctx->stream));
-            size_t pos = (size_t)ncols * ocol;
-            for (int c = 0; c < ncols; c++) {
-                cph_strcol& sc = t->pub.cols[c];
-                sc.offsets = h + (size_t)c * ocol;
-                sc.data = h + pos;
-                if (totals[(size_t)c])
-                    CPH_HIP_TRY(hipMemcpyAsync(h + pos, t->d_data[c].get(), totals[(size_t)c], hipMemcpyDeviceToHost, ctx->stream));
-                pos += (totals[(size_t)c] + 15) & ~(size_t)15;
-                sc.nrows = nout;
-                sc.offset_bits = off32 ? 32 : 64;
-                sc.mem = CPH_MEM_HOST;
-                sc.fixed_width = 0;
-                t->d_data[c].reset();
-            }
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-            t->d_offs.reset();
+        // publish: every column's offsets (all inside d_offs) in front of every column's bytes
+        ResultPart parts[2 * CPH_MAX_KEY_COLS];
+        for (int c = 0; c < ncols; c++) {
+            cph_strcol& sc = t->pub.cols[c];
+            sc.nrows = nout;
+            sc.offset_bits = off32 ? 32 : 64;
+            sc.mem = out_mem;
+            sc.fixed_width = 0;
+            parts[c] = {&t->d_offs, (size_t)(nout + 1) * osz, &sc.offsets, col_offs(c)};
+            parts[ncols + c] = {&t->d_data[c], (size_t)totals[(size_t)c], &sc.data};
         }
-        return {};
+        return deliver(ctx, &t->own, parts, 2 * ncols, out_mem);
     };
-    Status s = run();
-    if (!s.ok()) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (t->h_block) (void)hipHostFree(t->h_block);
-        delete t;
-        return fail_with(ctx, s);
-    }
-    *out = &t->pub;
-    return CPH_OK;
+    return finish_call(ctx, t, run(), out);
 }
 
-CPH_API void cph_csv_table_release(cph_csv_table* pub) {
-    if (!pub) return;
-    auto* t = reinterpret_cast<cph_csv_table_impl*>(pub);
-    if (t->ctx) (void)hipSetDevice(t->ctx->device);
-    if (t->h_block) (void)hipHostFree(t->h_block);
-    delete t;
-}
+CPH_API void cph_csv_table_release(cph_csv_table* pub) { release_result<cph_csv_table_impl>(pub); }
 
 }  // extern "C"
 

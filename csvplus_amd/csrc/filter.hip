@@ -217,9 +217,8 @@ using namespace cph;
 // the library-owned row list behind cph_rowlist
 struct cph_rowlist_impl {
     cph_rowlist pub;   // first
-    cph_ctx* ctx = nullptr;
+    cph::ResultOwner own;
     cph::DevBuf d_ids;
-    void* h_block = nullptr;
 };
 
 namespace {
@@ -230,19 +229,9 @@ Status deliver_ids(cph_ctx* ctx, cph_rowlist_impl* r, DevBuf&& dev, uint64_t n, 
     r->pub.first = 0;
     r->pub.bits = bits;
     r->pub.mem = out_mem;
-    if (out_mem == CPH_MEM_DEVICE) {
-        r->d_ids = std::move(dev);
-        r->pub.ids = r->d_ids.get();
-        CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    } else {
-        const size_t b = (size_t)n * (size_t)(bits / 8);
-        CPH_HIP_TRY(hipHostMalloc(&r->h_block, b + 16, hipHostMallocDefault));
-        CPH_HIP_TRY(hipMemcpyAsync(r->h_block, dev.get(), b, hipMemcpyDeviceToHost, ctx->stream));
-        CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        r->pub.ids = r->h_block;
-        dev.reset();
-    }
-    return {};
+    r->d_ids = std::move(dev);
+    const ResultPart part{&r->d_ids, (size_t)n * (size_t)(bits / 8), &r->pub.ids};
+    return deliver(ctx, &r->own, &part, 1, out_mem);
 }
 
 void set_range(cph_rowlist_impl* r, uint64_t first, uint64_t n, int32_t bits, int32_t out_mem) {
@@ -311,17 +300,13 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
     if (n > 0xFFFFFFFFull) return fail_with(ctx, {CPH_ERR_TOO_MANY_ROWS, "cph_filter_rows: more than 2^32-1 rows in one call"});
     if (opts->out_bits == 32 && first_row + n > 0xFFFFFFFFull)
         return fail_with(ctx, {CPH_ERR_TOO_MANY_ROWS, "cph_filter_rows: first_row + nrows > 2^32-1 needs out_bits 64"});
-    for (int c = 0; c < ncols; c++) {
-        Status s = validate_cols(cols + c, 1);
+    {
+        Status s = check_row_sources(cols, sel, ncols, first_row, n, false);
         if (!s.ok()) return fail_with(ctx, s);
-        const bool ident = !sel || !sel[c].ids;
-        if (ident && n && cols[c].nrows < first_row + n)
-            return fail_with(ctx, {CPH_ERR_INVALID, "cph_filter_rows: a column without row ids must have first_row + nrows rows"});
-        if (!ident && sel[c].bits != 32 && sel[c].bits != 64) return fail_with(ctx, {CPH_ERR_INVALID, "row id bits must be 32 or 64"});
     }
     auto* r = new (std::nothrow) cph_rowlist_impl();
     if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
-    r->ctx = ctx;
+    r->own.ctx = ctx;
     const int32_t bits = opts->out_bits;
     auto run = [&]() -> Status {
         if (n == 0) {
@@ -331,23 +316,7 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         std::vector<DevBuf> staged;
         ColsArg arg{};
         ColIds ids{};
-        for (int c = 0; c < ncols; c++) {
-            CPH_TRY(stage_cols(ctx, cols + c, 1, &staged, &arg.c[c]));
-            if (sel && sel[c].ids) {
-                ids.ids[c].bits = sel[c].bits;
-                ids.ids[c].base = sel[c].base;
-                const size_t w = (size_t)(sel[c].bits / 8);
-                if (cols[c].mem == CPH_MEM_HOST) {   // the ids live where the column lives; only entries [first_row, first_row + n) are read
-                    staged.emplace_back();
-                    CPH_TRY(staged.back().alloc(&ctx->pool, n * w));
-                    CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), static_cast<const uint8_t*>(sel[c].ids) + first_row * w, n * w,
-                                               hipMemcpyHostToDevice, ctx->stream));
-                    ids.ids[c].ptr = reinterpret_cast<const void*>((uintptr_t)staged.back().get() - (uintptr_t)(first_row * w));
-                } else {
-                    ids.ids[c].ptr = sel[c].ids;
-                }
-            }
-        }
+        CPH_TRY(stage_row_sources(ctx, cols, sel, nullptr, ncols, first_row, n, &staged, &arg, &ids));
         // the program: LIKE terms over real columns get a bit each, the others are decided here
         PredProg pp{};
         std::vector<uint64_t> lits;
@@ -452,15 +421,7 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         CPH_HIP_TRY(hipGetLastError());
         return deliver_ids(ctx, r, std::move(outb), kept, bits, out_mem);
     };
-    Status s = run();
-    if (!s.ok()) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (r->h_block) (void)hipHostFree(r->h_block);
-        delete r;
-        return fail_with(ctx, s);
-    }
-    *out = &r->pub;
-    return CPH_OK;
+    return finish_call(ctx, r, run(), out);
 }
 
 CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel_mem, const cph_rowlist* list, int32_t out_mem,
@@ -477,7 +438,7 @@ CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel
     if (list->ids && list->mem != CPH_MEM_HOST && list->mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "cph_rowsel_take: bad list mem"});
     auto* r = new (std::nothrow) cph_rowlist_impl();
     if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
-    r->ctx = ctx;
+    r->own.ctx = ctx;
     const uint64_t n = list->nrows;
     auto run = [&]() -> Status {
         if (n == 0 || (ident && !list->ids)) {   // nothing to gather: an empty list, or a range through the identity
@@ -540,23 +501,9 @@ CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel
         CPH_HIP_TRY(hipGetLastError());
         return deliver_ids(ctx, r, std::move(outb), n, sel->bits, out_mem);
     };
-    Status s = run();
-    if (!s.ok()) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (r->h_block) (void)hipHostFree(r->h_block);
-        delete r;
-        return fail_with(ctx, s);
-    }
-    *out = &r->pub;
-    return CPH_OK;
+    return finish_call(ctx, r, run(), out);
 }
 
-CPH_API void cph_rowlist_release(cph_rowlist* pub) {
-    if (!pub) return;
-    auto* r = reinterpret_cast<cph_rowlist_impl*>(pub);
-    if (r->ctx) (void)hipSetDevice(r->ctx->device);
-    if (r->h_block) (void)hipHostFree(r->h_block);
-    delete r;
-}
+CPH_API void cph_rowlist_release(cph_rowlist* pub) { release_result<cph_rowlist_impl>(pub); }
 
 }  // extern "C"

@@ -454,7 +454,7 @@ using namespace cph;
 
 struct cph_groups_impl {
     cph_groups pub;   // first
-    void* h_block = nullptr;
+    ResultOwner own;
 };
 
 namespace {
@@ -472,6 +472,7 @@ CPH_API int32_t cph_index_dup_groups(cph_ctx* ctx, const cph_index* ix, cph_grou
     if (hipSetDevice(ctx->device) != hipSuccess) return fail_with(ctx, {CPH_ERR_HIP, "hipSetDevice failed"});
     auto* g = new (std::nothrow) cph_groups_impl();
     if (!g) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
+    g->own.ctx = ctx;
     auto run = [&]() -> Status {
         const uint64_t n = ix->nrows;
         uint64_t ng = 0;
@@ -509,34 +510,13 @@ CPH_API int32_t cph_index_dup_groups(cph_ctx* ctx, const cph_index* ix, cph_grou
             }
         }
         g->pub.ngroups = ng;
-        CPH_HIP_TRY(hipHostMalloc(&g->h_block, (2 * ng + 2) * sizeof(uint64_t), hipHostMallocDefault));
-        uint64_t* h = static_cast<uint64_t*>(g->h_block);
-        if (ng) {
-            CPH_HIP_TRY(hipMemcpyAsync(h, lo.get(), ng * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-            CPH_HIP_TRY(hipMemcpyAsync(h + ng, hi.get(), ng * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        g->pub.lower = h;
-        g->pub.upper = h + ng;
-        return {};
+        const ResultPart parts[2] = {{&lo, (size_t)ng * sizeof(uint64_t), &g->pub.lower}, {&hi, (size_t)ng * sizeof(uint64_t), &g->pub.upper}};
+        return deliver(ctx, &g->own, parts, 2, CPH_MEM_HOST);   // groups always go to the host (dedup's resolve callback runs there)
     };
-    Status s = run();
-    if (!s.ok()) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (g->h_block) (void)hipHostFree(g->h_block);
-        delete g;
-        return fail_with(ctx, s);
-    }
-    *out = &g->pub;
-    return CPH_OK;
+    return finish_call(ctx, g, run(), out);
 }
 
-CPH_API void cph_groups_release(cph_groups* pub) {
-    if (!pub) return;
-    auto* g = reinterpret_cast<cph_groups_impl*>(pub);
-    if (g->h_block) (void)hipHostFree(g->h_block);
-    delete g;
-}
+CPH_API void cph_groups_release(cph_groups* pub) { release_result<cph_groups_impl>(pub); }
 
 CPH_API int32_t cph_index_select(cph_ctx* ctx, const cph_index* ix, const uint64_t* positions, uint64_t n, cph_index** out) {
     if (!ctx || !ix || !out || (n && !positions)) return CPH_ERR_INVALID;

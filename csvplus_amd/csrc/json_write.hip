@@ -335,14 +335,12 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
     if (!names) return fail_with(ctx, {CPH_ERR_INVALID, "cph_json_write_rows: names must not be NULL"});
     if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
     if (ncols < 1 || ncols > CPH_MAX_KEY_COLS) return fail_with(ctx, {CPH_ERR_INVALID, "1..16 columns"});
-    for (int c = 0; c < ncols; c++) {
-        Status s = validate_cols(cols + c, 1);
+    {
+        Status s = check_row_sources(cols, sel, ncols, 0, nrows, true);
         if (!s.ok()) return fail_with(ctx, s);
-        const bool ident = !sel || !sel[c].ids;
-        if (ident && nrows && cols[c].nrows != nrows) return fail_with(ctx, {CPH_ERR_INVALID, "a column without row ids must have nrows rows"});
-        if (!ident && sel[c].bits != 32 && sel[c].bits != 64) return fail_with(ctx, {CPH_ERR_INVALID, "row id bits must be 32 or 64"});
-        if (!names[c].data && names[c].len) return fail_with(ctx, {CPH_ERR_INVALID, "a name with bytes but no data pointer"});
     }
+    for (int c = 0; c < ncols; c++)
+        if (!names[c].data && names[c].len) return fail_with(ctx, {CPH_ERR_INVALID, "a name with bytes but no data pointer"});
     // map keys in byte order (sort.Strings in encoding/json's map encoder); a map holds each key once
     std::vector<std::string> key(ncols);
     for (int c = 0; c < ncols; c++) key[c].assign(reinterpret_cast<const char*>(names[c].data), (size_t)names[c].len);
@@ -359,7 +357,7 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
     const uint64_t n = nrows;
     auto* r = new (std::nothrow) cph_bytes_impl();
     if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
-    r->ctx = ctx;
+    r->own.ctx = ctx;
     auto run = [&]() -> Status {
         std::string frags;
         JsonKeys keys{};
@@ -375,23 +373,7 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
         std::vector<DevBuf> staged;
         ColsArg arg{};
         ColIds ids{};
-        for (int k = 0; k < ncols; k++) {
-            const int c = order[k];
-            CPH_TRY(stage_cols(ctx, cols + c, 1, &staged, &arg.c[k]));
-            if (sel && sel[c].ids && n) {
-                ids.ids[k].bits = sel[c].bits;
-                ids.ids[k].base = sel[c].base;
-                if (cols[c].mem == CPH_MEM_HOST) {   // the ids live where the column lives
-                    const size_t b = n * (size_t)(sel[c].bits / 8);
-                    staged.emplace_back();
-                    CPH_TRY(staged.back().alloc(&ctx->pool, b));
-                    CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), sel[c].ids, b, hipMemcpyHostToDevice, ctx->stream));
-                    ids.ids[k].ptr = staged.back().get();
-                } else {
-                    ids.ids[k].ptr = sel[c].ids;
-                }
-            }
-        }
+        CPH_TRY(stage_row_sources(ctx, cols, sel, order.data(), ncols, 0, n, &staged, &arg, &ids));
         uint64_t total = 0;
         if (n) {
             DevBuf kbuf, offs, eflags;
@@ -424,30 +406,12 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
             memcpy(slot, "[]", 2);
             CPH_HIP_TRY(hipMemcpyAsync(r->d_data.get(), slot, 2, hipMemcpyHostToDevice, ctx->stream));
         }
-        const uint64_t size = total + 2;
-        r->pub.size = size;
+        r->pub.size = total + 2;
         r->pub.mem = out_mem;
-        if (out_mem == CPH_MEM_DEVICE) {
-            r->pub.data = r->d_data.as<uint8_t>();
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        } else {
-            CPH_HIP_TRY(hipHostMalloc(&r->h_block, size + 16, hipHostMallocDefault));
-            CPH_HIP_TRY(hipMemcpyAsync(r->h_block, r->d_data.get(), size, hipMemcpyDeviceToHost, ctx->stream));
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-            r->pub.data = static_cast<const uint8_t*>(r->h_block);
-            r->d_data.reset();
-        }
-        return {};
+        const ResultPart part{&r->d_data, (size_t)total + 2, &r->pub.data};
+        return deliver(ctx, &r->own, &part, 1, out_mem);
     };
-    Status s = run();
-    if (!s.ok()) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (r->h_block) (void)hipHostFree(r->h_block);
-        delete r;
-        return fail_with(ctx, s);
-    }
-    *out = &r->pub;
-    return CPH_OK;
+    return finish_call(ctx, r, run(), out);
 }
 
 }  // extern "C"

@@ -890,34 +890,11 @@ using namespace cph;
 
 struct cph_colbuf_impl {
     cph_colbuf pub;   // first
-    cph_ctx* ctx = nullptr;
+    ResultOwner own;
     DevBuf d_data, d_offs;
-    void* h_block = nullptr;
 };
 
 extern "C" {
-
-CPH_API int32_t cph_gather_rows(cph_ctx* ctx, const cph_strcol* col, const void* row_ids, int32_t id_bits, uint64_t id_base,
-                                uint64_t nrows, int32_t out_mem, cph_colbuf** out);
-
-// mergeRows for a caller that works with sorted positions: the payload column in index order (csvplus.go:736: the rows of
-// an Index ARE sorted), gathered once through the index's permutation
-CPH_API int32_t cph_index_permute(cph_ctx* ctx, cph_index* index, const cph_strcol* col, int32_t out_mem, cph_colbuf** out) {
-    if (!ctx || !index || !col || !out) return CPH_ERR_INVALID;
-    *out = nullptr;
-    if (col->nrows < index->table_rows)
-        return fail_with(ctx, {CPH_ERR_INVALID, "cph_index_permute: the column has fewer rows than the table the index was built over"});
-    const uint32_t* perm = nullptr;
-    uint64_t n = 0;
-    const int32_t rc = cph_index_perm(index, col->mem == CPH_MEM_DEVICE ? CPH_MEM_DEVICE : CPH_MEM_HOST, &perm, &n);
-    if (rc != CPH_OK) {
-        if (index->ctx && index->ctx != ctx) ctx->err = index->ctx->err;
-        return rc;
-    }
-    static const uint32_t no_rows = 0;   // an empty index: an empty column (row_ids == NULL would mean "copy the column"; never read)
-    if (n == 0) perm = &no_rows;
-    return cph_gather_rows(ctx, col, perm, 32, 0, n, out_mem, out);
-}
 
 CPH_API int32_t cph_gather_rows(cph_ctx* ctx, const cph_strcol* col, const void* row_ids, int32_t id_bits, uint64_t id_base,
                                 uint64_t nrows, int32_t out_mem, cph_colbuf** out) {
@@ -931,25 +908,18 @@ CPH_API int32_t cph_gather_rows(cph_ctx* ctx, const cph_strcol* col, const void*
     const uint64_t n = row_ids ? nrows : col->nrows;
     auto* r = new (std::nothrow) cph_colbuf_impl();
     if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
-    r->ctx = ctx;
+    r->own.ctx = ctx;
     auto run = [&]() -> Status {
+        cph_rowsel sel{};
+        sel.ids = row_ids;
+        sel.bits = id_bits;
+        sel.base = id_base;
         std::vector<DevBuf> staged;
-        DevCol d;
-        CPH_TRY(stage_cols(ctx, col, 1, &staged, &d));
-        RowIds ids;
-        ids.bits = id_bits;
-        ids.base = id_base;
-        DevBuf idbuf;
-        if (row_ids && n) {
-            if (col->mem == CPH_MEM_HOST) {   // ids live where the column lives
-                const size_t b = n * (size_t)(id_bits / 8);
-                CPH_TRY(idbuf.alloc(&ctx->pool, b));
-                CPH_HIP_TRY(hipMemcpyAsync(idbuf.get(), row_ids, b, hipMemcpyHostToDevice, ctx->stream));
-                ids.ptr = idbuf.get();
-            } else {
-                ids.ptr = row_ids;
-            }
-        }
+        ColsArg arg{};
+        ColIds cids{};
+        CPH_TRY(stage_row_sources(ctx, col, &sel, nullptr, 1, 0, n, &staged, &arg, &cids));
+        const DevCol& d = arg.c[0];
+        RowIds& ids = cids.ids[0];
         CPH_TRY(r->d_offs.alloc(&ctx->pool, (n + 1) * sizeof(uint64_t)));
         uint64_t* offs = r->d_offs.as<uint64_t>();
         uint64_t total = 0;
@@ -982,40 +952,32 @@ CPH_API int32_t cph_gather_rows(cph_ctx* ctx, const cph_strcol* col, const void*
         r->pub.col.offset_bits = 64;
         r->pub.col.mem = out_mem;
         r->pub.col.fixed_width = 0;
-        if (out_mem == CPH_MEM_DEVICE) {
-            r->pub.col.data = r->d_data.as<uint8_t>();
-            r->pub.col.offsets = offs;
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        } else {
-            const size_t ob = (n + 1) * sizeof(uint64_t);
-            CPH_HIP_TRY(hipHostMalloc(&r->h_block, ob + total + 16, hipHostMallocDefault));
-            uint8_t* h = static_cast<uint8_t*>(r->h_block);
-            CPH_HIP_TRY(hipMemcpyAsync(h, offs, ob, hipMemcpyDeviceToHost, ctx->stream));
-            if (total) CPH_HIP_TRY(hipMemcpyAsync(h + ob, r->d_data.get(), total, hipMemcpyDeviceToHost, ctx->stream));
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-            r->pub.col.offsets = h;
-            r->pub.col.data = h + ob;
-            r->d_data.reset();
-            r->d_offs.reset();
-        }
-        return {};
+        const ResultPart parts[2] = {{&r->d_offs, (size_t)(n + 1) * sizeof(uint64_t), &r->pub.col.offsets},
+                                     {&r->d_data, (size_t)total, &r->pub.col.data}};
+        return deliver(ctx, &r->own, parts, 2, out_mem);
     };
-    s = run();
-    if (!s.ok()) {
-        if (r->h_block) (void)hipHostFree(r->h_block);
-        delete r;
-        return fail_with(ctx, s);
-    }
-    *out = &r->pub;
-    return CPH_OK;
+    return finish_call(ctx, r, run(), out);
 }
 
-CPH_API void cph_colbuf_release(cph_colbuf* pub) {
-    if (!pub) return;
-    auto* r = reinterpret_cast<cph_colbuf_impl*>(pub);
-    if (r->ctx) (void)hipSetDevice(r->ctx->device);
-    if (r->h_block) (void)hipHostFree(r->h_block);
-    delete r;
+CPH_API void cph_colbuf_release(cph_colbuf* pub) { release_result<cph_colbuf_impl>(pub); }
+
+// mergeRows for a caller that works with sorted positions: the payload column in index order (csvplus.go:736: the rows of
+// an Index ARE sorted), gathered once through the index's permutation
+CPH_API int32_t cph_index_permute(cph_ctx* ctx, cph_index* index, const cph_strcol* col, int32_t out_mem, cph_colbuf** out) {
+    if (!ctx || !index || !col || !out) return CPH_ERR_INVALID;
+    *out = nullptr;
+    if (col->nrows < index->table_rows)
+        return fail_with(ctx, {CPH_ERR_INVALID, "cph_index_permute: the column has fewer rows than the table the index was built over"});
+    const uint32_t* perm = nullptr;
+    uint64_t n = 0;
+    const int32_t rc = cph_index_perm(index, col->mem == CPH_MEM_DEVICE ? CPH_MEM_DEVICE : CPH_MEM_HOST, &perm, &n);
+    if (rc != CPH_OK) {
+        if (index->ctx && index->ctx != ctx) ctx->err = index->ctx->err;
+        return rc;
+    }
+    static const uint32_t no_rows = 0;   // an empty index: an empty column (row_ids == NULL would mean "copy the column"; never read)
+    if (n == 0) perm = &no_rows;
+    return cph_gather_rows(ctx, col, perm, 32, 0, n, out_mem, out);
 }
 
 CPH_API int32_t cph_csv_write_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
@@ -1025,17 +987,14 @@ CPH_API int32_t cph_csv_write_rows(cph_ctx* ctx, const cph_strcol* cols, const c
     *out = nullptr;
     if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
     if (ncols < 1 || ncols > CPH_MAX_KEY_COLS) return fail_with(ctx, {CPH_ERR_INVALID, "1..16 columns"});
-    for (int c = 0; c < ncols; c++) {
-        Status s = validate_cols(cols + c, 1);
+    {
+        Status s = check_row_sources(cols, sel, ncols, 0, nrows, true);
         if (!s.ok()) return fail_with(ctx, s);
-        const bool ident = !sel || !sel[c].ids;
-        if (ident && nrows && cols[c].nrows != nrows) return fail_with(ctx, {CPH_ERR_INVALID, "a column without row ids must have nrows rows"});
-        if (!ident && sel[c].bits != 32 && sel[c].bits != 64) return fail_with(ctx, {CPH_ERR_INVALID, "row id bits must be 32 or 64"});
     }
     const uint64_t n = nrows;
     auto* r = new (std::nothrow) cph_bytes_impl();
     if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
-    r->ctx = ctx;
+    r->own.ctx = ctx;
     auto run = [&]() -> Status {
         std::string head;
         if (header) {
@@ -1048,22 +1007,7 @@ CPH_API int32_t cph_csv_write_rows(cph_ctx* ctx, const cph_strcol* cols, const c
         std::vector<DevBuf> staged;
         ColsArg arg{};
         ColIds ids{};
-        for (int c = 0; c < ncols; c++) {
-            CPH_TRY(stage_cols(ctx, cols + c, 1, &staged, &arg.c[c]));
-            if (sel && sel[c].ids && n) {
-                ids.ids[c].bits = sel[c].bits;
-                ids.ids[c].base = sel[c].base;
-                if (cols[c].mem == CPH_MEM_HOST) {   // the ids live where the column lives
-                    const size_t b = n * (size_t)(sel[c].bits / 8);
-                    staged.emplace_back();
-                    CPH_TRY(staged.back().alloc(&ctx->pool, b));
-                    CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), sel[c].ids, b, hipMemcpyHostToDevice, ctx->stream));
-                    ids.ids[c].ptr = staged.back().get();
-                } else {
-                    ids.ids[c].ptr = sel[c].ids;
-                }
-            }
-        }
+        CPH_TRY(stage_row_sources(ctx, cols, sel, nullptr, ncols, 0, n, &staged, &arg, &ids));
         uint64_t total = 0;
         bool one_pass = false;   // (round 6) one pass over the joined rows; whatever it does not take goes through the two passes below
         if (ctx->csv_onepass && n >= (ctx->csv_onepass > 1 ? 1u : 4096u))
@@ -1121,27 +1065,10 @@ CPH_API int32_t cph_csv_write_rows(cph_ctx* ctx, const cph_strcol* cols, const c
         }
         r->pub.size = size;
         r->pub.mem = out_mem;
-        if (out_mem == CPH_MEM_DEVICE) {
-            r->pub.data = r->d_data.as<uint8_t>();
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        } else {
-            CPH_HIP_TRY(hipHostMalloc(&r->h_block, size + 16, hipHostMallocDefault));
-            if (size) CPH_HIP_TRY(hipMemcpyAsync(r->h_block, r->d_data.get(), size, hipMemcpyDeviceToHost, ctx->stream));
-            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-            r->pub.data = static_cast<const uint8_t*>(r->h_block);
-            r->d_data.reset();
-        }
-        return {};
+        const ResultPart part{&r->d_data, (size_t)size, &r->pub.data};
+        return deliver(ctx, &r->own, &part, 1, out_mem);
     };
-    Status s = run();
-    if (!s.ok()) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (r->h_block) (void)hipHostFree(r->h_block);
-        delete r;
-        return fail_with(ctx, s);
-    }
-    *out = &r->pub;
-    return CPH_OK;
+    return finish_call(ctx, r, run(), out);
 }
 
 CPH_API int32_t cph_csv_write(cph_ctx* ctx, const cph_strcol* cols, int32_t ncols, const cph_strval* header, int32_t out_mem,
@@ -1150,13 +1077,7 @@ CPH_API int32_t cph_csv_write(cph_ctx* ctx, const cph_strcol* cols, int32_t ncol
     return cph_csv_write_rows(ctx, cols, nullptr, ncols, cols[0].nrows, header, out_mem, out);
 }
 
-CPH_API void cph_bytes_release(cph_bytes* pub) {
-    if (!pub) return;
-    auto* r = reinterpret_cast<cph_bytes_impl*>(pub);
-    if (r->ctx) (void)hipSetDevice(r->ctx->device);
-    if (r->h_block) (void)hipHostFree(r->h_block);
-    delete r;
-}
+CPH_API void cph_bytes_release(cph_bytes* pub) { release_result<cph_bytes_impl>(pub); }
 
 }  // extern "C"
 

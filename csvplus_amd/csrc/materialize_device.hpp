@@ -1,5 +1,7 @@
-// materialize_device.hpp — the device pieces the writers share (materialize.hip: gather and ToCsv; json_write.hip: ToJSON):
-// row ids per column, the byte sinks, the LDS stage, the record loader, the column-count dispatch and the length scan.
+// materialize_device.hpp — the device pieces the writers share (materialize.hip: gather and ToCsv; json_write.hip: ToJSON;
+// filter.hip: Filter): the row-id lookup, the byte sinks, the LDS stage, the record loader, the column-count dispatch and the
+// length scan.  Their host side is shared too and lives in cph_internal.hpp / capi.hip: RowIds / ColIds, check_row_sources and
+// stage_row_sources (columns + row ids onto the device), deliver / finish_call / release_result (the result handed out).
 #pragma once
 
 #include "lds_stage.hpp"
@@ -9,14 +11,6 @@ namespace cph {
 constexpr int kMatThreads = 256;
 constexpr int kMatStage   = 16 * 1024;   // LDS bytes for one tile's output (small: more workgroups per CU hide the barriers)
 
-struct RowIds {
-    const void* ptr = nullptr;   // null: identity
-    int32_t bits = 32;
-    uint64_t base = 0;
-    // CSV writer, gathered columns: the length pass leaves (begin | length << 32) of the value it looked up per OUTPUT row
-    // here, and the copy pass reads that stream instead of fetching row id + offsets again (one random sector less per row)
-    uint64_t* stash = nullptr;
-};
 __device__ __forceinline__ uint64_t source_row(const RowIds& ids, uint64_t i) {
     if (!ids.ptr) return i;
     return (ids.bits == 32 ? (uint64_t) reinterpret_cast<const uint32_t*>(ids.ptr)[i]
@@ -97,13 +91,6 @@ __device__ __forceinline__ uint64_t eq_mask8(uint64_t w, uint64_t pat) {
     return ~(((x & k) + k) | x | k);
 }
 
-// Per column: which row of the column feeds output row i (NULL ids: row i itself).  This is mergeRows
-// (csvplus.go:571-583) folded into the writer: the joined row's fields are read straight from the tables
-// through the row-id tuples of the join.
-struct ColIds {
-    RowIds ids[kMaxKeyCols];
-};
-
 // One record's fields: row ids, then offsets, then the first chunk of every value — three rounds of independent
 // loads instead of a dependent chain per column.  NC > 0: compile-time column count (arrays stay in registers);
 // NC == 0: any count up to kMaxKeyCols, one column at a time.
@@ -155,11 +142,7 @@ static unsigned grid_rows(uint64_t n) {
 // lens[n] -> offs[n+1] in place (offs[n] = total), total also read back
 static Status scan_lengths(cph_ctx* ctx, uint64_t* lens, uint64_t n, uint64_t* total) {
     CPH_TRY(exclusive_scan_u64(ctx, lens, n, lens + n));
-    CPH_TRY(ensure_pinned_scratch(ctx, sizeof(uint64_t)));
-    CPH_HIP_TRY(hipMemcpyAsync(ctx->pinned_scratch, lens + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *total = *reinterpret_cast<const uint64_t*>(ctx->pinned_scratch);
-    return {};
+    return read_device_value(ctx, lens + n, total);
 }
 
 }  // namespace cph
@@ -167,7 +150,6 @@ static Status scan_lengths(cph_ctx* ctx, uint64_t* lens, uint64_t n, uint64_t* t
 // the library-owned byte buffer behind cph_bytes (cph_bytes_release frees whichever writer made it)
 struct cph_bytes_impl {
     cph_bytes pub;    // first
-    cph_ctx* ctx = nullptr;
+    cph::ResultOwner own;
     cph::DevBuf d_data;
-    void* h_block = nullptr;
 };
