@@ -7,13 +7,13 @@ the SoA column staging and the multi-GPU sharding.  There is no CPU fallback.
 Modules: `engine` (one GPU: index_on / join / chained_join on torch device memory), `dist` (probe-row sharding +
 allgatherv over RCCL), `streaming` (host -> device pipeline of join chunks), `ingest` (CSV text -> columns),
 `materialize` (gather through row ids, ToCsv, ToJSON, Filter / TakeWhile / DropWhile over `predicates`: Like, All, Any,
-Not as plain data), `dedup` (ResolveDuplicates over the device index),
+Not, IntCmp, FloatCmp as plain data; ValueAsInt / ValueAsFloat64 for a whole column: to_int / to_float), `dedup` (ResolveDuplicates over the device index),
 `pipeline` (CSV -> indices -> chained join -> CSV or JSON, all in HBM), `datagen` (deterministic synthetic tables).
 """
 from . import _native as native  # noqa: F401
 from ._native import CphError, NativeLibraryMissing, Context, DeviceIndex, Matches, Chain, join_chain  # noqa: F401
 from .columns import StrCol  # noqa: F401
-from .predicates import Like, All, Any, Not  # noqa: F401
+from .predicates import Like, All, Any, Not, IntCmp, FloatCmp  # noqa: F401
 
 __all__ = ["native", "CphError", "NativeLibraryMissing", "Context", "DeviceIndex", "Matches", "Chain", "join_chain", "StrCol",
-           "Like", "All", "Any", "Not"]
+           "Like", "All", "Any", "Not", "IntCmp", "FloatCmp"]

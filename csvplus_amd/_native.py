@@ -148,6 +148,8 @@ class cph_rowsel(C.Structure):
 
 
 CPH_PRED_LIKE, CPH_PRED_NOT, CPH_PRED_ALL, CPH_PRED_ANY = 1, 2, 3, 4
+CPH_PRED_INT_LT, CPH_PRED_INT_LE, CPH_PRED_INT_EQ, CPH_PRED_INT_NE, CPH_PRED_INT_GE, CPH_PRED_INT_GT = 16, 17, 18, 19, 20, 21
+CPH_PRED_FLT_LT, CPH_PRED_FLT_LE, CPH_PRED_FLT_EQ, CPH_PRED_FLT_NE, CPH_PRED_FLT_GE, CPH_PRED_FLT_GT = 24, 25, 26, 27, 28, 29
 CPH_PRED_MAX_OPS, CPH_PRED_MAX_LIKE, CPH_PRED_MAX_STACK = 64, 32, 32
 CPH_FILTER_WHERE, CPH_FILTER_TAKE_WHILE, CPH_FILTER_DROP_WHILE = 0, 1, 2
 CPH_NO_LIMIT = 0xFFFFFFFFFFFFFFFF
@@ -164,6 +166,17 @@ class cph_filter_opts(C.Structure):
 
 class cph_rowlist(C.Structure):
     _fields_ = [("nrows", C.c_uint64), ("first", C.c_uint64), ("ids", C.c_void_p), ("bits", C.c_int32), ("mem", C.c_int32)]
+
+
+CPH_NUM_INT64, CPH_NUM_FLOAT64 = 1, 2
+CPH_NUM_OK, CPH_NUM_ERR_SYNTAX, CPH_NUM_ERR_RANGE, CPH_NUM_ERR_UNSUPPORTED = 0, 1, 2, 3
+CPH_NO_ROW = 0xFFFFFFFFFFFFFFFF
+
+
+class cph_numcol(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("values", C.c_void_p), ("status", C.c_void_p), ("kind", C.c_int32), ("mem", C.c_int32),
+                ("nerrors", C.c_uint64), ("first_error_row", C.c_uint64), ("first_error_kind", C.c_int32), ("reserved_", C.c_int32),
+                ("host_rows", C.c_uint64)]
 
 
 class cph_groups(C.Structure):
@@ -277,6 +290,9 @@ PROTOTYPES = [
     ("cph_rowlist_release", None, [C.POINTER(cph_rowlist)]),
     ("cph_rowsel_take", C.c_int32,
      [_P, C.POINTER(cph_rowsel), C.c_int32, C.POINTER(cph_rowlist), C.c_int32, C.POINTER(C.POINTER(cph_rowlist))]),
+    ("cph_col_to_number", C.c_int32,
+     [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.POINTER(cph_numcol))]),
+    ("cph_numcol_release", None, [C.POINTER(cph_numcol)]),
     ("cph_csv_parse", C.c_int32,
      [_P, _P, C.c_uint64, C.c_int32, C.POINTER(cph_csv_options), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_csv_table))]),

@@ -920,4 +920,17 @@ private:
     double bytes_ = 0;
 };
 
+// numparse.hip: rows [first_row, first_row + n) of a device-resident column, read through `ids`, as int64 / float64
+// (CPH_NUM_INT64 / CPH_NUM_FLOAT64): values[i] (8 bytes) and status[i] (CPH_NUM_*) for row first_row + i, both on the
+// device and complete — the float rows the device defers are finished on the host and patched in — when the call returns
+// (it waits for the stream).  n == 0 allocates nothing.
+struct NumColStats {
+    uint64_t nerrors = 0;
+    uint64_t first_error = UINT64_MAX;   // relative to first_row; UINT64_MAX: no error
+    int32_t first_kind = 0;
+    uint64_t host_rows = 0;              // rows finished on the host
+};
+Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t first_row, uint64_t n, int32_t kind, DevBuf* values,
+                    DevBuf* status, NumColStats* st);
+
 }  // namespace cph

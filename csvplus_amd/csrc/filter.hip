@@ -16,11 +16,20 @@
 // The two WHILE modes only need the first failing row: the same evaluation without the bitmap, one 64-bit atomicMin per
 // wave that saw a failure (none when the value it read at the tile's start is already smaller; tiles behind that value
 // are not read at all).  Their answer is a range: nothing is materialised.
+//
+// Numeric compare terms (CPH_PRED_INT_* / CPH_PRED_FLT_*) are term bits like a LIKE, so the boolean program does not know
+// them apart:
+//   int64    converted in k_pred_eval itself (numparse_device.hpp: parse_int64) from the same 16-byte head a LIKE would
+//            compare; the device decides every integer, so nothing else is needed.
+//   float64  the term's column is converted FIRST through the path of cph_col_to_number (numparse.hip: convert_rows, once
+//            per column and call, deferred rows finished on the host and patched in) and k_pred_eval compares the
+//            resulting doubles — so a WHERE or WHILE answer never depends on where a value was converted.
+// A program without numeric terms launches the NUM = false instantiations: the kernels it always launched.
 #include <algorithm>
 #include <cstring>
 #include <new>
 
-#include "materialize_device.hpp"
+#include "numparse_device.hpp"
 
 namespace cph {
 
@@ -31,7 +40,9 @@ constexpr int kFiltWords = kFiltTile / 64;
 constexpr int kFiltWaveWords = kFiltWords / (kMatThreads / kWave);   // 8 words per wave
 constexpr int kLitLds    = 4096;                       // literal bytes kept in LDS; more than that stay in global memory
 
-enum : uint32_t { kTermBytes = 0, kTermFix8 = 1 };
+enum : uint32_t { kTermBytes = 0, kTermFix8 = 1, kTermInt = 2, kTermF64 = 3 };   // low byte of PredTerm::kind
+// bits 8..11 of a numeric term's kind: which outcomes of (value ? literal) make the relation hold
+enum : uint32_t { kCmpLess = 1, kCmpEqual = 2, kCmpGreater = 4, kCmpUnordered = 8 };
 constexpr uint8_t kTermNever = 0xFF;                   // a LIKE decided on the host: no such column, or a fixed width other than the literal's
 
 // One LIKE over a real column.  A literal of at most 8 bytes is lit8 (zero padded); a longer one lies in the literal
@@ -41,6 +52,9 @@ struct PredTerm {
     uint32_t lit_off, len;
     int32_t  col;
     uint32_t kind;   // kTermFix8: a fixed-width column of 8 bytes on an 8-byte aligned base — one aligned load and one compare
+                     // kTermInt / kTermF64: lit8 = the literal's bits, the relation in bits 8..11
+    const double*  fval;   // kTermF64: the converted column, entry i = row first_row + i of the selection ...
+    const uint8_t* fstat;  // ... and its CPH_NUM_* status bytes
 };
 struct PredProg {    // travels in the kernel arguments (~0.9 KB): a wave reads it with scalar loads
     PredTerm term[CPH_PRED_MAX_LIKE];
@@ -68,7 +82,7 @@ __device__ __forceinline__ bool like_bytes(const DevCol& col, uint64_t begin, co
 // BITMAP: bitmap[tile * 32 + w] bit b = the predicate holds for row tile * 2048 + 64 w + b of the call (rows >= n: 0),
 //         counts[tile] = the tile's set bits.
 // else:   *first_fail = min(*first_fail, the first row where it does not hold); the host presets it to n.
-template <bool BITMAP>
+template <bool BITMAP, bool NUM>
 __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds ids, PredProg prog, uint64_t first_row, uint64_t n,
                                                           uint64_t* __restrict__ bitmap, uint32_t* __restrict__ counts,
                                                           unsigned long long* first_fail) {
@@ -111,6 +125,36 @@ __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds 
                     for (int k = 0; k < kFiltPhase; k++) v[k] = reinterpret_cast<const uint64_t*>(col.data)[source_row(rid, pos[k])];
 #pragma unroll
                     for (int k = 0; k < kFiltPhase; k++) mask[k] |= (uint32_t)(v[k] == tm.lit8) << t;
+                } else if (NUM && (tm.kind & 0xFFu) == kTermInt) {
+                    const uint32_t rel = tm.kind >> 8;
+                    const int64_t lit = (int64_t)tm.lit8;
+                    uint64_t b[kFiltPhase], l[kFiltPhase], c0[kFiltPhase], c1[kFiltPhase];
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) value_span(col, source_row(rid, pos[k]), &b[k], &l[k]);
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) load_head16(col, b[k], l[k], &c0[k], &c1[k]);
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {
+                        int64_t v;
+                        const uint32_t st = parse_int64(col, b[k], l[k], c0[k], c1[k], &v);
+                        const uint32_t cls = v < lit ? kCmpLess : v == lit ? kCmpEqual : kCmpGreater;
+                        mask[k] |= (uint32_t)(st == CPH_NUM_OK && (rel & cls) != 0) << t;   // a row that does not convert: false
+                    }
+                } else if (NUM && (tm.kind & 0xFFu) == kTermF64) {
+                    const uint32_t rel = tm.kind >> 8;
+                    const double lit = __longlong_as_double((long long)tm.lit8);
+                    double v[kFiltPhase];
+                    uint32_t st[kFiltPhase];
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {
+                        v[k] = tm.fval[pos[k] - first_row];
+                        st[k] = tm.fstat[pos[k] - first_row];
+                    }
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {
+                        const uint32_t cls = v[k] < lit ? kCmpLess : v[k] == lit ? kCmpEqual : v[k] > lit ? kCmpGreater : kCmpUnordered;
+                        mask[k] |= (uint32_t)(st[k] == CPH_NUM_OK && (rel & cls) != 0) << t;
+                    }
                 } else {
                     uint64_t b[kFiltPhase], l[kFiltPhase];
 #pragma unroll
@@ -252,7 +296,15 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
             case CPH_PRED_LIKE:
                 if (o.arg < -1 || o.arg >= ncols) return {CPH_ERR_INVALID, "cph_filter_rows: LIKE column outside -1..ncols-1"};
                 if (!o.value.data && o.value.len) return {CPH_ERR_INVALID, "cph_filter_rows: a LIKE value with bytes but no data pointer"};
-                if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE terms"};
+                if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE and numeric terms"};
+                depth++;
+                break;
+            case CPH_PRED_INT_LT: case CPH_PRED_INT_LE: case CPH_PRED_INT_EQ: case CPH_PRED_INT_NE: case CPH_PRED_INT_GE: case CPH_PRED_INT_GT:
+            case CPH_PRED_FLT_LT: case CPH_PRED_FLT_LE: case CPH_PRED_FLT_EQ: case CPH_PRED_FLT_NE: case CPH_PRED_FLT_GE: case CPH_PRED_FLT_GT:
+                if (o.arg < -1 || o.arg >= ncols) return {CPH_ERR_INVALID, "cph_filter_rows: numeric compare column outside -1..ncols-1"};
+                if (!o.value.data || o.value.len != 8)
+                    return {CPH_ERR_INVALID, "cph_filter_rows: a numeric literal is exactly 8 bytes (an int64_t or a double) behind a non-NULL pointer"};
+                if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE and numeric terms"};
                 depth++;
                 break;
             case CPH_PRED_NOT:
@@ -264,13 +316,25 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
                 depth += 1 - o.arg;
                 break;
             default:
-                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4)"};
+                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4, 16..21, 24..29)"};
         }
         if (depth > CPH_PRED_MAX_STACK) return {CPH_ERR_INVALID, "cph_filter_rows: stack deeper than 32"};
     }
     if (depth != 1) return {CPH_ERR_INVALID, "cph_filter_rows: the program must leave exactly one value"};
     return {};
 }
+
+bool is_int_cmp(int32_t op) { return op >= CPH_PRED_INT_LT && op <= CPH_PRED_INT_GT; }
+bool is_flt_cmp(int32_t op) { return op >= CPH_PRED_FLT_LT && op <= CPH_PRED_FLT_GT; }
+// LT LE EQ NE GE GT -> the outcomes under which the relation holds (IEEE: unordered satisfies NE alone)
+uint32_t rel_outcomes(int32_t rel) {
+    static const uint32_t m[6] = {kCmpLess, kCmpLess | kCmpEqual, kCmpEqual, kCmpLess | kCmpGreater | kCmpUnordered, kCmpEqual | kCmpGreater, kCmpGreater};
+    return m[rel];
+}
+struct FloatCol {   // a column converted for this call's float terms
+    int col;
+    DevBuf values, status;
+};
 
 unsigned filter_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
 
@@ -322,9 +386,46 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         std::vector<uint64_t> lits;
         double col_bytes = 0;
         uint32_t seen_cols = 0;
+        bool numeric = false;
+        std::vector<FloatCol> fcols;
+        fcols.reserve((size_t)ncols);
         for (int q = 0; q < nops; q++) {
             pp.op[q] = (uint8_t)prog[q].op;
             pp.arg[q] = (uint8_t)prog[q].arg;
+            if (is_int_cmp(prog[q].op) || is_flt_cmp(prog[q].op)) {   // a term bit like a LIKE: the kernel's program sees a LIKE
+                const int c = prog[q].arg;
+                pp.op[q] = (uint8_t)CPH_PRED_LIKE;
+                if (c < 0) {
+                    pp.arg[q] = kTermNever;
+                    continue;
+                }
+                numeric = true;
+                const bool flt = is_flt_cmp(prog[q].op);
+                PredTerm& t = pp.term[pp.nterms];
+                pp.arg[q] = (uint8_t)pp.nterms++;
+                t.col = c;
+                memcpy(&t.lit8, prog[q].value.data, 8);
+                t.kind = (flt ? kTermF64 : kTermInt) | (rel_outcomes(prog[q].op - (flt ? CPH_PRED_FLT_LT : CPH_PRED_INT_LT)) << 8);
+                if (flt) {
+                    size_t f = 0;
+                    while (f < fcols.size() && fcols[f].col != c) f++;
+                    if (f == fcols.size()) {
+                        fcols.emplace_back();
+                        fcols[f].col = c;
+                        NumColStats st;
+                        CPH_TRY(convert_rows(ctx, arg.c[c], ids.ids[c], first_row, n, CPH_NUM_FLOAT64, &fcols[f].values, &fcols[f].status, &st));
+                        col_bytes += 9.0 * (double)n;   // the converted column read back (its conversion is timed on its own)
+                    }
+                    t.fval = fcols[f].values.as<double>();
+                    t.fstat = fcols[f].status.as<uint8_t>();
+                } else if (!((seen_cols >> c) & 1u)) {   // offsets (or nothing) + the value's head, once per column
+                    seen_cols |= 1u << c;
+                    col_bytes += arg.c[c].fixed_width ? (double)arg.c[c].fixed_width * (double)n
+                                                      : ((double)(arg.c[c].offset_bits / 8) + 8.0) * (double)n;
+                    if (ids.ids[c].ptr) col_bytes += (double)(ids.ids[c].bits / 8) * (double)n;
+                }
+                continue;
+            }
             if (prog[q].op != CPH_PRED_LIKE) continue;
             const int c = prog[q].arg;
             const uint64_t len = prog[q].value.len;
@@ -376,8 +477,12 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
             CPH_HIP_TRY(hipMemcpyAsync(ff.get(), slot, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
             {
                 ProfScope ps(ctx, "k_pred_eval", col_bytes);
-                hipLaunchKernelGGL(k_pred_eval<false>, dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
-                                   (uint64_t*)nullptr, (uint32_t*)nullptr, ff.as<unsigned long long>());
+                if (numeric)
+                    hipLaunchKernelGGL((k_pred_eval<false, true>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
+                                       (uint64_t*)nullptr, (uint32_t*)nullptr, ff.as<unsigned long long>());
+                else
+                    hipLaunchKernelGGL((k_pred_eval<false, false>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
+                                       (uint64_t*)nullptr, (uint32_t*)nullptr, ff.as<unsigned long long>());
             }
             CPH_HIP_TRY(hipGetLastError());
             uint64_t stop = 0;   // rows in front of the first failing one
@@ -394,8 +499,12 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         CPH_TRY(counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
         {
             ProfScope ps(ctx, "k_pred_eval", col_bytes + (double)n / 8.0 + 4.0 * (double)ntiles);
-            hipLaunchKernelGGL(k_pred_eval<true>, dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
-                               bitmap.as<uint64_t>(), counts.as<uint32_t>(), (unsigned long long*)nullptr);
+            if (numeric)
+                hipLaunchKernelGGL((k_pred_eval<true, true>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
+                                   bitmap.as<uint64_t>(), counts.as<uint32_t>(), (unsigned long long*)nullptr);
+            else
+                hipLaunchKernelGGL((k_pred_eval<true, false>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
+                                   bitmap.as<uint64_t>(), counts.as<uint32_t>(), (unsigned long long*)nullptr);
         }
         CPH_HIP_TRY(hipGetLastError());
         CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));

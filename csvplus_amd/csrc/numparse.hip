@@ -1,0 +1,314 @@
+// numparse.hip — Row.ValueAsInt / Row.ValueAsFloat64 (csvplus.go:165-205) for a whole column: strings -> int64 / float64
+// with Go's strconv semantics, plus the error report the reference's callers act on (which row failed first, and how).
+//
+//   cph_col_to_number   one column read through an optional row selection -> values, one status byte per row, the
+//                       number of errors, the first error row and its kind
+//   convert_rows        the same for a caller inside the library (filter.hip: float compare terms)
+//
+//   k_num_parse    rows on lanes (row = tile + 64 k + lane, 8 rows per lane and tile, 4 in flight, the geometry of
+//                  k_pred_eval): span -> the value's first 16 bytes with two branch-free loads -> the SWAR conversion of
+//                  numparse_device.hpp.  Values and status bytes leave as coalesced stores.  A wave that saw an error
+//                  adds its count and sends ONE 64-bit atomicMin of (row << 2 | kind), so the first error row and its
+//                  kind arrive together; a wave that deferred float rows adds their count.
+//   The device decides every row's syntax and every value Clinger's exact cases cover.  The float rows it DEFERS (19+
+//   significant digits, a mantissa >= 2^53, exponents outside the exact range) are rare:
+//   k_num_collect  (only when there are any) gathers position, span and the first bytes of each deferred row into 128-byte
+//                  slots; the host converts those with a correctly rounded routine and
+//   k_num_patch    writes the values and status bytes back.
+#include <algorithm>
+#include <cerrno>
+#include <charconv>
+#include <clocale>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+
+#include <locale.h>
+
+#include "numparse_device.hpp"
+
+namespace cph {
+
+constexpr int kNumRows  = 8;                          // rows per lane and tile
+constexpr int kNumPhase = 4;                          // ... of which this many are in flight at once
+constexpr int kNumTile  = kMatThreads * kNumRows;     // 2048 rows
+constexpr int kNumWaveRows = kNumRows;                // 64-row groups per wave and tile
+constexpr uint32_t kSlotBytes = 104;                  // value bytes a deferred row's slot holds
+
+struct NumCounters {   // zeroed / preset by the host in front of k_num_parse
+    unsigned long long nerrors, first_error, ndeferred, collected;
+};
+struct NumSlot {       // one deferred row on its way to the host
+    uint64_t pos, begin, len;
+    uint8_t bytes[kSlotBytes];
+};
+static_assert(sizeof(NumSlot) == 128, "NumSlot is 128 bytes");
+struct NumPatch {
+    uint64_t pos, bits;
+    uint32_t status, pad_;
+};
+
+template <bool FLT>
+__global__ __launch_bounds__(kMatThreads) void k_num_parse(DevCol col, RowIds rid, uint64_t first_row, uint64_t n,
+                                                          uint64_t* __restrict__ values, uint8_t* __restrict__ status, NumCounters* cnt) {
+    const int lane = lane_id(), wave = wave_id();
+    const uint64_t ntiles = (n + kNumTile - 1) / kNumTile;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * kNumTile;
+        unsigned long long first = ~0ull;   // wave-uniform: (row << 2 | kind) of the wave's first error in this tile
+        uint32_t nerr = 0, ndef = 0;        // wave-uniform
+#pragma unroll
+        for (int ph = 0; ph < kNumRows / kNumPhase; ph++) {
+            uint64_t b[kNumPhase], l[kNumPhase], c0[kNumPhase], c1[kNumPhase];
+            bool live[kNumPhase];
+#pragma unroll
+            for (int k = 0; k < kNumPhase; k++) {
+                const uint64_t i = t0 + (uint64_t)((wave * kNumWaveRows + ph * kNumPhase + k) * 64 + lane);
+                live[k] = i < n;   // rows past the end look at the last row; their result is dropped
+                value_span(col, source_row(rid, first_row + (live[k] ? i : n - 1)), &b[k], &l[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < kNumPhase; k++) load_head16(col, b[k], l[k], &c0[k], &c1[k]);
+#pragma unroll
+            for (int k = 0; k < kNumPhase; k++) {
+                const uint64_t g0 = t0 + (uint64_t)((wave * kNumWaveRows + ph * kNumPhase + k) * 64);
+                uint64_t bits;
+                uint32_t st;
+                if constexpr (FLT) {
+                    double v;
+                    st = parse_float64(col, b[k], l[k], c0[k], c1[k], &v);
+                    bits = (uint64_t)__double_as_longlong(v);
+                } else {
+                    int64_t v;
+                    st = parse_int64(col, b[k], l[k], c0[k], c1[k], &v);
+                    bits = (uint64_t)v;
+                }
+                if (live[k]) {
+                    values[g0 + lane] = bits;
+                    status[g0 + lane] = (uint8_t)st;
+                }
+                const uint64_t bad = __ballot(live[k] && st != CPH_NUM_OK && st != kNumDeferred);
+                if (bad) {   // uniform
+                    const int fl = __builtin_ctzll(bad);
+                    const unsigned long long key = ((unsigned long long)(g0 + (uint64_t)fl) << 2) | (unsigned long long)__shfl(st, fl, kWave);
+                    if (key < first) first = key;
+                    nerr += (uint32_t)__popcll(bad);
+                }
+                if constexpr (FLT) ndef += (uint32_t)__popcll(__ballot(live[k] && st == kNumDeferred));
+            }
+        }
+        if (lane == 0) {
+            if (nerr) {
+                atomicAdd(&cnt->nerrors, (unsigned long long)nerr);
+                atomicMin(&cnt->first_error, first);
+            }
+            if (ndef) atomicAdd(&cnt->ndeferred, (unsigned long long)ndef);
+        }
+    }
+}
+
+// slots[q] = row, span and first bytes of the q-th deferred row (in no particular order)
+__global__ __launch_bounds__(kMatThreads) void k_num_collect(DevCol col, RowIds rid, uint64_t first_row, uint64_t n,
+                                                            const uint8_t* __restrict__ status, NumCounters* cnt, NumSlot* __restrict__ slots,
+                                                            uint64_t nslots) {
+    const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kMatThreads + threadIdx.x; i < n; i += stride) {
+        if (status[i] != kNumDeferred) continue;
+        const uint64_t q = atomicAdd(&cnt->collected, 1ull);
+        if (q >= nslots) continue;   // cannot happen: nslots is the count k_num_parse left
+        uint64_t b, l;
+        value_span(col, source_row(rid, first_row + i), &b, &l);
+        NumSlot& s = slots[q];
+        s.pos = i;
+        s.begin = b;
+        s.len = l;
+        const uint64_t take = l < kSlotBytes ? l : kSlotBytes;
+        for (uint64_t j = 0; 8 * j < take; j++) {
+            const uint64_t chunk = load_value_chunk(col.data, b, l, (int)j);
+            memcpy(s.bytes + 8 * j, &chunk, 8);   // kSlotBytes is a multiple of 8: a whole chunk always fits
+        }
+    }
+}
+
+__global__ __launch_bounds__(kMatThreads) void k_num_patch(const NumPatch* __restrict__ patch, uint64_t np, uint64_t* __restrict__ values,
+                                                          uint8_t* __restrict__ status) {
+    const uint64_t i = (uint64_t)blockIdx.x * kMatThreads + threadIdx.x;
+    if (i >= np) return;
+    values[patch[i].pos] = patch[i].bits;
+    status[patch[i].pos] = (uint8_t)patch[i].status;
+}
+
+namespace {
+
+unsigned num_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
+
+// One syntactically valid decimal value the device deferred: correctly rounded, locale independent.  A finite result
+// is never an error (underflow to 0 or a denormal included, as in Go); +-HUGE_VAL is a range error with value +-Inf.
+uint32_t host_parse_float(const char* s, size_t len, double* out) {
+    bool neg = false;
+    size_t i = 0;
+    if (len && (s[0] == '+' || s[0] == '-')) {
+        neg = s[0] == '-';
+        i = 1;
+    }
+    double v = 0.0;
+    bool done = false;
+#if defined(__cpp_lib_to_chars) && __cpp_lib_to_chars >= 201611L
+    {
+        const std::from_chars_result r = std::from_chars(s + i, s + len, v, std::chars_format::general);
+        done = r.ec == std::errc() && r.ptr == s + len;   // out of range: from_chars does not say which way
+    }
+#endif
+    if (!done) {
+        static locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+        const std::string z(s + i, len - i);
+        v = c_locale ? strtod_l(z.c_str(), nullptr, c_locale) : strtod(z.c_str(), nullptr);
+    }
+    if (neg) v = -v;
+    *out = v;
+    return std::isinf(v) ? CPH_NUM_ERR_RANGE : CPH_NUM_OK;
+}
+
+}  // namespace
+
+Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t first_row, uint64_t n, int32_t kind, DevBuf* values,
+                    DevBuf* status, NumColStats* st) {
+    *st = NumColStats{};
+    if (n == 0) return {};
+    const bool flt = kind == CPH_NUM_FLOAT64;
+    CPH_TRY(values->alloc(&ctx->pool, (size_t)n * 8));
+    CPH_TRY(status->alloc(&ctx->pool, (size_t)n));
+    DevBuf cnt;
+    CPH_TRY(cnt.alloc(&ctx->pool, sizeof(NumCounters)));
+    {
+        void* slot = nullptr;
+        CPH_TRY(pinned_upload(ctx, sizeof(NumCounters), &slot));
+        const NumCounters zero{0ull, ~0ull, 0ull, 0ull};
+        memcpy(slot, &zero, sizeof zero);
+        CPH_HIP_TRY(hipMemcpyAsync(cnt.get(), slot, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const uint64_t ntiles = (n + kNumTile - 1) / kNumTile;
+    {
+        // byte model: offsets (or nothing for a fixed width) + row ids + ~8 value bytes in, 9 bytes out per row
+        const double in_row = (col.fixed_width ? (double)col.fixed_width : (double)(col.offset_bits / 8) + 8.0) + (ids.ptr ? (double)(ids.bits / 8) : 0.0);
+        ProfScope ps(ctx, flt ? "k_num_parse_f64" : "k_num_parse_i64", (in_row + 9.0) * (double)n);
+        if (flt)
+            hipLaunchKernelGGL(k_num_parse<true>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>());
+        else
+            hipLaunchKernelGGL(k_num_parse<false>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>());
+    }
+    CPH_HIP_TRY(hipGetLastError());
+    NumCounters got{};
+    CPH_TRY(read_device_value(ctx, cnt.as<NumCounters>(), &got));   // the call's host wait
+    st->nerrors = got.nerrors;
+    if (got.nerrors) {
+        st->first_error = got.first_error >> 2;
+        st->first_kind = (int32_t)(got.first_error & 3ull);
+    }
+    st->host_rows = got.ndeferred;
+    if (!got.ndeferred) return {};
+
+    // the deferred rows: their bytes come back, the host converts them, the results are patched in
+    const uint64_t nd = got.ndeferred;
+    DevBuf slots;
+    CPH_TRY(slots.alloc(&ctx->pool, (size_t)nd * sizeof(NumSlot)));
+    hipLaunchKernelGGL(k_num_collect, dim3(grid_rows(n)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n, status->as<uint8_t>(),
+                       cnt.as<NumCounters>(), slots.as<NumSlot>(), nd);
+    CPH_HIP_TRY(hipGetLastError());
+    std::vector<NumSlot> hs((size_t)nd);
+    CPH_HIP_TRY(hipMemcpyAsync(hs.data(), slots.get(), (size_t)nd * sizeof(NumSlot), hipMemcpyDeviceToHost, ctx->stream));
+    CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::vector<NumPatch> hp((size_t)nd);
+    std::string longv;
+    for (uint64_t q = 0; q < nd; q++) {
+        const NumSlot& s = hs[(size_t)q];
+        const char* bytes = reinterpret_cast<const char*>(s.bytes);
+        if (s.len > kSlotBytes) {   // a value longer than a slot: straight from the column
+            longv.resize((size_t)s.len);
+            CPH_HIP_TRY(hipMemcpyAsync(&longv[0], col.data + s.begin, (size_t)s.len, hipMemcpyDeviceToHost, ctx->stream));
+            CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
+            bytes = longv.data();
+        }
+        double v = 0.0;
+        const uint32_t k = host_parse_float(bytes, (size_t)s.len, &v);
+        NumPatch& p = hp[(size_t)q];
+        p.pos = s.pos;
+        memcpy(&p.bits, &v, 8);
+        p.status = k;
+        p.pad_ = 0;
+        if (k != CPH_NUM_OK) {
+            st->nerrors++;
+            if (s.pos < st->first_error) {
+                st->first_error = s.pos;
+                st->first_kind = (int32_t)k;
+            }
+        }
+    }
+    DevBuf patch;
+    CPH_TRY(patch.alloc(&ctx->pool, (size_t)nd * sizeof(NumPatch)));
+    CPH_HIP_TRY(hipMemcpyAsync(patch.get(), hp.data(), (size_t)nd * sizeof(NumPatch), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_num_patch, dim3((unsigned)((nd + kMatThreads - 1) / kMatThreads)), dim3(kMatThreads), 0, ctx->stream,
+                       patch.as<NumPatch>(), nd, values->as<uint64_t>(), status->as<uint8_t>());
+    CPH_HIP_TRY(hipGetLastError());
+    CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));   // hp and the patch block stay alive until the kernel has read them
+    return {};
+}
+
+}  // namespace cph
+
+using namespace cph;
+
+// the library-owned result behind cph_numcol
+struct cph_numcol_impl {
+    cph_numcol pub;   // first
+    cph::ResultOwner own;
+    cph::DevBuf d_values, d_status;
+};
+
+extern "C" {
+
+CPH_API int32_t cph_col_to_number(cph_ctx* ctx, const cph_strcol* col, const cph_rowsel* sel, uint64_t nrows, int32_t kind,
+                                  int32_t out_mem, cph_numcol** out) {
+    if (!ctx || !out) return CPH_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_with(ctx, {CPH_ERR_HIP, "hipSetDevice failed"});
+    *out = nullptr;
+    if (!col) return fail_with(ctx, {CPH_ERR_INVALID, "cph_col_to_number: col must not be NULL"});
+    if (kind != CPH_NUM_INT64 && kind != CPH_NUM_FLOAT64)
+        return fail_with(ctx, {CPH_ERR_INVALID, "cph_col_to_number: kind must be CPH_NUM_INT64 or CPH_NUM_FLOAT64"});
+    if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
+    {
+        Status s = check_row_sources(col, sel, 1, 0, nrows, true);
+        if (!s.ok()) return fail_with(ctx, s);
+    }
+    auto* r = new (std::nothrow) cph_numcol_impl();
+    if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
+    r->own.ctx = ctx;
+    r->pub.nrows = nrows;
+    r->pub.kind = kind;
+    r->pub.mem = out_mem;
+    r->pub.first_error_row = UINT64_MAX;
+    auto run = [&]() -> Status {
+        if (nrows == 0) return {};
+        std::vector<DevBuf> staged;
+        ColsArg arg{};
+        ColIds ids{};
+        CPH_TRY(stage_row_sources(ctx, col, sel, nullptr, 1, 0, nrows, &staged, &arg, &ids));
+        NumColStats st;
+        CPH_TRY(convert_rows(ctx, arg.c[0], ids.ids[0], 0, nrows, kind, &r->d_values, &r->d_status, &st));
+        r->pub.nerrors = st.nerrors;
+        r->pub.first_error_row = st.first_error;
+        r->pub.first_error_kind = st.first_kind;
+        r->pub.host_rows = st.host_rows;
+        const ResultPart parts[2] = {{&r->d_values, (size_t)nrows * 8, &r->pub.values}, {&r->d_status, (size_t)nrows, &r->pub.status}};
+        return deliver(ctx, &r->own, parts, 2, out_mem);
+    };
+    return finish_call(ctx, r, run(), out);
+}
+
+CPH_API void cph_numcol_release(cph_numcol* pub) { release_result<cph_numcol_impl>(pub); }
+
+}  // extern "C"

@@ -14,6 +14,10 @@
 //   DataSource.Filter / TakeWhile / DropWhile / Top / Drop :276-374  DataSource::Filter / TakeWhile / DropWhile (over a
 //                                                declarative csvplus::Pred, evaluated on the GPU) / Top / Drop
 //   Like / All / Any / Not           :1243-1293  csvplus::Like / All / Any / Not (plain data, also callable on a Row)
+//   Row.ValueAsInt / ValueAsFloat64  :165-205    csvplus::ValueAsInt / ValueAsFloat64 (one row, on the host);
+//                                                DataSource::ColumnAsInt / ColumnAsFloat64 (a whole column, on the GPU);
+//                                                csvplus::IntCmp / FloatCmp: `v, err := row.ValueAsInt(c); err == nil && v REL k`
+//                                                as a predicate that composes with Like / All / Any / Not
 //   Index.Iterate / Find / SubIndex    :618-641  Index::Iterate / Find / SubIndex
 //   Index.ResolveDuplicates            :643-653  Index::ResolveDuplicates (groups found on the GPU)
 //   Index.WriteTo / LoadIndex          :655-705  Index::WriteTo / LoadIndex (own binary format, not gob)
@@ -42,6 +46,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -54,6 +59,8 @@
 #include <string>
 #include <utility>
 #include <vector>
+
+#include <locale.h>
 
 #include "csvplus_hip.h"
 
@@ -142,11 +149,86 @@ inline Row mergeRows(const Row& left, const Row& right) {
 // A Go closure cannot run on a GPU; Like / All / Any / Not are declarative and can: DataSource::Filter / TakeWhile / DropWhile
 // compile a Pred to the postfix program of cph_filter_rows.  A Pred is also callable on a Row (the reference's semantics on
 // the host), so it fits wherever a std::function<bool(const Row&)> is wanted.
+enum Rel { LT = 0, LE = 1, EQ = 2, NE = 3, GE = 4, GT = 5 };   // the order of CPH_PRED_INT_LT.. / CPH_PRED_FLT_LT..
+
+// Row.ValueAsInt (:165-183) / Row.ValueAsFloat64 (:187-205) on the host: strconv.Atoi / strconv.ParseFloat as the header's
+// cph_col_to_number comment restates them.  Returns CPH_NUM_*; *out = what Go returns beside the error.
+inline int32_t Atoi(const std::string& s, int64_t* out) {
+    *out = 0;
+    size_t i = 0;
+    const bool neg = !s.empty() && s[0] == '-';
+    if (!s.empty() && (s[0] == '+' || s[0] == '-')) i = 1;
+    if (i == s.size()) return CPH_NUM_ERR_SYNTAX;
+    uint64_t n = 0;
+    for (; i < s.size(); i++) {
+        const unsigned d = (unsigned char)s[i] - (unsigned)'0';
+        if (d > 9) return CPH_NUM_ERR_SYNTAX;
+        const uint64_t n10 = n * 10u, n1 = n10 + d;
+        if (n > UINT64_MAX / 10u || n1 < n10) {
+            *out = neg ? INT64_MIN : INT64_MAX;
+            return CPH_NUM_ERR_RANGE;
+        }
+        n = n1;
+    }
+    if (neg ? n > (1ull << 63) : n >= (1ull << 63)) {
+        *out = neg ? INT64_MIN : INT64_MAX;
+        return CPH_NUM_ERR_RANGE;
+    }
+    *out = neg ? (int64_t)(0ull - n) : (int64_t)n;
+    return CPH_NUM_OK;
+}
+inline int32_t ParseFloat(const std::string& s, double* out) {
+    *out = 0.0;
+    if (s.empty()) return CPH_NUM_ERR_SYNTAX;
+    size_t i = (s[0] == '+' || s[0] == '-') ? 1 : 0;
+    const bool neg = s[0] == '-';
+    if (s.find('_') != std::string::npos || (s.size() - i >= 2 && s[i] == '0' && (s[i + 1] | 0x20) == 'x')) return CPH_NUM_ERR_UNSUPPORTED;
+    std::string low = s.substr(i);
+    for (char& c : low)
+        if (c >= 'A' && c <= 'Z') c = (char)(c | 0x20);
+    if (low == "inf" || low == "infinity") {
+        *out = neg ? -HUGE_VAL : HUGE_VAL;
+        return CPH_NUM_OK;
+    }
+    if (i == 0 && low == "nan") {
+        *out = std::nan("");
+        return CPH_NUM_OK;
+    }
+    size_t j = i, digits = 0;
+    while (j < s.size() && s[j] >= '0' && s[j] <= '9') j++, digits++;
+    if (j < s.size() && s[j] == '.') {
+        j++;
+        while (j < s.size() && s[j] >= '0' && s[j] <= '9') j++, digits++;
+    }
+    if (!digits) return CPH_NUM_ERR_SYNTAX;
+    if (j < s.size() && (s[j] | 0x20) == 'e') {
+        j++;
+        if (j < s.size() && (s[j] == '+' || s[j] == '-')) j++;
+        if (j >= s.size() || s[j] < '0' || s[j] > '9') return CPH_NUM_ERR_SYNTAX;
+        while (j < s.size() && s[j] >= '0' && s[j] <= '9') j++;
+    }
+    if (j != s.size()) return CPH_NUM_ERR_SYNTAX;
+    static locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+    *out = c_locale ? strtod_l(s.c_str(), nullptr, c_locale) : strtod(s.c_str(), nullptr);   // correctly rounded (glibc)
+    return std::isinf(*out) ? CPH_NUM_ERR_RANGE : CPH_NUM_OK;
+}
+
 class Pred {
 public:
-    enum Kind { kLike, kNot, kAll, kAny };
+    enum Kind { kLike, kNot, kAll, kAny, kIntCmp, kFloatCmp };
     bool operator()(const Row& row) const {
         switch (kind_) {
+            case kIntCmp:
+            case kFloatCmp: {   // a row without the column, or whose value does not convert, is false under every relation
+                auto it = row.find(column_);
+                if (it == row.end()) return false;
+                if (kind_ == kIntCmp) {
+                    int64_t v;
+                    return Atoi(it->second, &v) == CPH_NUM_OK && holds(v, ilit_);
+                }
+                double v;
+                return ParseFloat(it->second, &v) == CPH_NUM_OK && holds(v, flit_);
+            }
             case kLike:
                 for (const auto& kv : match_) {                                             // :1285-1289
                     auto it = row.find(kv.first);
@@ -167,8 +249,28 @@ public:
     Kind kind() const { return kind_; }
     const Row& match() const { return match_; }
     const std::vector<Pred>& operands() const { return kids_; }
+    const std::string& column() const { return column_; }
+    Rel rel() const { return rel_; }
+    const void* literal() const { return kind_ == kIntCmp ? (const void*)&ilit_ : (const void*)&flit_; }   // 8 bytes
 
 private:
+    template <class T>
+    bool holds(T v, T k) const {
+        switch (rel_) {
+            case LT: return v < k;
+            case LE: return v <= k;
+            case EQ: return v == k;
+            case NE: return v != k;
+            case GE: return v >= k;
+            default: return v > k;
+        }
+    }
+    friend Pred IntCmp(std::string column, Rel rel, int64_t k);
+    friend Pred FloatCmp(std::string column, Rel rel, double x);
+    std::string column_;
+    Rel rel_ = EQ;
+    int64_t ilit_ = 0;
+    double flit_ = 0.0;
     friend Pred Like(Row match);
     friend Pred Not(Pred p);
     friend Pred All(std::vector<Pred> preds);
@@ -182,6 +284,22 @@ inline Pred Like(Row match) {
     Pred p;
     p.kind_ = Pred::kLike;
     p.match_ = std::move(match);
+    return p;
+}
+inline Pred IntCmp(std::string column, Rel rel, int64_t k) {
+    Pred p;
+    p.kind_ = Pred::kIntCmp;
+    p.column_ = std::move(column);
+    p.rel_ = rel;
+    p.ilit_ = k;
+    return p;
+}
+inline Pred FloatCmp(std::string column, Rel rel, double x) {
+    Pred p;
+    p.kind_ = Pred::kFloatCmp;
+    p.column_ = std::move(column);
+    p.rel_ = rel;
+    p.flit_ = x;
     return p;
 }
 inline Pred Not(Pred q) {
@@ -300,7 +418,8 @@ inline bool allColumnsUnique(const std::vector<std::string>& columns) {
 // A Pred as the postfix program of cph_filter_rows over its own column list.  A row that LACKS a named column must make that
 // Like false (:1286 `!found`), and presence differs row by row, so it cannot be the program's column -1: the staging
 // carries it instead — such a row gets the column's `absent` value, which is one byte longer than the longest literal any
-// Like compares that column with and therefore equals none of them (equality is on the whole value, length first).
+// Like compares that column with and therefore equals none of them (equality is on the whole value, length first) — and, being
+// NUL bytes, converts to no number either, which is what IntCmp / FloatCmp need of it.
 struct PredProgram {
     std::vector<std::string> columns;   // distinct names, in order of first use
     std::vector<std::string> absent;    // per column
@@ -321,6 +440,18 @@ struct PredProgram {
                 }
                 if (p.match().size() > 1) ops.push_back(cph_pred_op{CPH_PRED_ALL, (int32_t)p.match().size(), {nullptr, 0}});
                 break;
+            case Pred::kIntCmp:
+            case Pred::kFloatCmp: {
+                size_t c = (size_t)(std::find(columns.begin(), columns.end(), p.column()) - columns.begin());
+                if (c == columns.size()) {
+                    columns.push_back(p.column());
+                    absent.emplace_back();
+                }
+                if (absent[c].empty()) absent[c].assign(1, '\0');   // a NUL converts to no number
+                const int32_t base = p.kind() == Pred::kIntCmp ? (int32_t)CPH_PRED_INT_LT : (int32_t)CPH_PRED_FLT_LT;
+                ops.push_back(cph_pred_op{base + (int32_t)p.rel(), (int32_t)c, {static_cast<const uint8_t*>(p.literal()), 8}});
+                break;
+            }
             case Pred::kNot:
                 emit(p.operands()[0]);
                 ops.push_back(cph_pred_op{CPH_PRED_NOT, 0, {nullptr, 0}});
@@ -549,6 +680,21 @@ public:
         });
     }
 
+    // Row.ValueAsInt (:165-183) / Row.ValueAsFloat64 (:187-205) for every row of the source: the column is staged once and
+    // converted by ONE cph_col_to_number call.  As the reference's iteration stops at the first row whose conversion fails,
+    // the first such row throws Error::DataSourceError(row number, counted from 0) with the reference's message (:176 / :198);
+    // a row without the column throws its `missing column` error (:170 / :192).
+    std::vector<int64_t> ColumnAsInt(const std::string& name) const {
+        std::vector<int64_t> out;
+        columnAsNumber(name, CPH_NUM_INT64, &out);
+        return out;
+    }
+    std::vector<double> ColumnAsFloat64(const std::string& name) const {
+        std::vector<double> out;
+        columnAsNumber(name, CPH_NUM_FLOAT64, &out);
+        return out;
+    }
+
     // cph_filter_rows calls made so far (tests: one per batch)
     static uint64_t filter_calls() { return filter_calls_counter(); }
 
@@ -561,6 +707,48 @@ public:
 
 private:
     Fn fn_;
+    template <class T>
+    void columnAsNumber(const std::string& name, int32_t kind, std::vector<T>* out) const {
+        std::vector<std::string> values;
+        uint64_t missing = UINT64_MAX;
+        Error err = fn_([&](Row row) -> Error {
+            auto it = row.find(name);
+            if (it == row.end()) {
+                missing = values.size();
+                return io_EOF;
+            }
+            values.push_back(std::move(it->second));
+            return Error();
+        });
+        if (err && !err.is_eof()) throw err;
+        const size_t n = values.size();
+        cph_ctx* ctx = Gpu::Default().ctx();
+        std::vector<std::vector<const std::string*>> vals(1);
+        vals[0].resize(n);
+        for (size_t i = 0; i < n; i++) vals[0][i] = &values[i];
+        cph_numcol* nc = nullptr;
+        int32_t rc;
+        {
+            detail::StagedColumns st(ctx, 1);
+            st.stage(vals, n);
+            rc = cph_col_to_number(ctx, st.cols(), nullptr, n, kind, CPH_MEM_HOST, &nc);
+        }
+        if (rc != CPH_OK) throw Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+        if (nc->nerrors) {
+            const uint64_t row = nc->first_error_row;
+            const char* what = nc->first_error_kind == CPH_NUM_ERR_SYNTAX  ? "invalid syntax"
+                               : nc->first_error_kind == CPH_NUM_ERR_RANGE ? "value out of range"
+                                                                           : "not decided by this library (digit separators, hexadecimal floats)";
+            const std::string msg = "column " + quote(name) + ": cannot convert " + quote(values[(size_t)row]) + " to " +
+                                    (kind == CPH_NUM_INT64 ? "integer" : "float") + ": " + what;
+            cph_numcol_release(nc);
+            throw Error::DataSourceError(row, Error(msg));
+        }
+        out->resize(n);
+        if (n) std::memcpy(out->data(), nc->values, n * sizeof(T));
+        cph_numcol_release(nc);
+        if (missing != UINT64_MAX) throw Error::DataSourceError(missing, Error("missing column " + quote(name)));
+    }
     struct ChainStepSpec {
         std::shared_ptr<Index> index;
         std::vector<std::string> columns;

@@ -1,6 +1,7 @@
 """The step after the path: gathering columns through the joined row ids and writing the
 canonical CSV or JSON (cph_gather_rows / cph_csv_write / cph_json_write_rows; mergeRows csvplus.go:571-583,
-ToCsv :379-406, ToJSON :446-480)."""
+ToCsv :379-406, ToJSON :446-480), filtering rows (cph_filter_rows) and converting a column to numbers
+(cph_col_to_number; ValueAsInt / ValueAsFloat64 :165-205)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -336,3 +337,69 @@ def take_rows(ctx: N.Context, row_ids, rows, out_mem: int = N.CPH_MEM_HOST, as_h
     ctx._check(ctx.lib.cph_rowsel_take(ctx.handle, C.byref(sel) if sel is not None else None, sel_mem, lst, out_mem, C.byref(out)))
     del keep
     return _take_rowlist(ctx, out, out_mem, as_handle)
+
+
+# ---- ValueAsInt / ValueAsFloat64 for a whole column (cph_col_to_number) -------------------------------------------------
+
+class NumCol:
+    """cph_numcol: a column as int64 / float64 (valid until release()).  `values` and `status` are numpy arrays (copies)
+    for a host result and (device_ptr, count) pairs for a device result; status holds CPH_NUM_* per row, and at an error
+    row `values` holds what Go returns beside the error.  first_error_row is None when nerrors == 0."""
+
+    def __init__(self, ctx, ptr):
+        self.ctx, self.ptr = ctx, ptr
+        c = ptr.contents
+        self.nrows, self.kind, self.mem = int(c.nrows), int(c.kind), int(c.mem)
+        self.nerrors, self.host_rows = int(c.nerrors), int(c.host_rows)
+        self.first_error_row = None if int(c.first_error_row) == N.CPH_NO_ROW else int(c.first_error_row)
+        self.first_error_kind = int(c.first_error_kind)
+        dt = np.int64 if self.kind == N.CPH_NUM_INT64 else np.float64
+        if self.mem == N.CPH_MEM_HOST:
+            self.values = N._ptr_array(c.values, self.nrows, dt).copy() if self.nrows else np.zeros(0, dt)
+            self.status = N._ptr_array(c.status, self.nrows, np.uint8).copy() if self.nrows else np.zeros(0, np.uint8)
+        else:
+            self.values = (int(c.values or 0), self.nrows)
+            self.status = (int(c.status or 0), self.nrows)
+        ctx._children.add(self)
+
+    def __len__(self):
+        return self.nrows
+
+    def release(self):
+        if self.ptr:
+            self.ctx.lib.cph_numcol_release(self.ptr)
+            self.ptr = None
+
+    close = release
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _to_number(ctx, col, row_ids, nrows, kind, out_mem):
+    keep = []
+    arr, sel, n = _rowsel([col], None if row_ids is None else [row_ids], nrows, keep)
+    out = C.POINTER(N.cph_numcol)()
+    ctx._check(ctx.lib.cph_col_to_number(ctx.handle, arr, sel, n, kind, out_mem, C.byref(out)))
+    del keep
+    res = NumCol(ctx, out)
+    if out_mem == N.CPH_MEM_HOST:
+        res.release()   # the arrays are copies
+    return res
+
+
+def to_int(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, out_mem: int = N.CPH_MEM_HOST):
+    """Row.ValueAsInt (csvplus.go:165-183) for every row of `col`: strconv.Atoi on the device.  row_ids / nrows as in
+    csv_write (numpy uint32 / uint64 or (numpy ids, base) for a host column, (device_ptr, bits, count[, base]) for a
+    device column).  A conversion error is data: see NumCol (nerrors, first_error_row, first_error_kind, status) and
+    predicates.conversion_error for the reference's message."""
+    return _to_number(ctx, col, row_ids, nrows, N.CPH_NUM_INT64, out_mem)
+
+
+def to_float(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, out_mem: int = N.CPH_MEM_HOST):
+    """Row.ValueAsFloat64 (csvplus.go:187-205): strconv.ParseFloat(s, 64), correctly rounded.  `host_rows` of the result
+    counts the rows the device deferred to the library's host side (19+ significant digits, extreme exponents)."""
+    return _to_number(ctx, col, row_ids, nrows, N.CPH_NUM_FLOAT64, out_mem)

@@ -1,14 +1,25 @@
-"""The reference's named predicates as plain data (csvplus.go:1243-1293): Like, All, Any, Not.
+"""The reference's named predicates as plain data (csvplus.go:1243-1293): Like, All, Any, Not — and the numeric
+conditions its users write as closures over Row.ValueAsInt / ValueAsFloat64 (csvplus.go:165-205, csvplus_test.go:272-281):
+IntCmp, FloatCmp.
 
-A Go closure cannot run on a GPU; these four are declarative and can.  `compile` flattens any nesting of them into the
+A Go closure cannot run on a GPU; these are declarative and can.  `compile` flattens any nesting of them into the
 postfix program cph_filter_rows takes (include/csvplus_hip.h), `matches` evaluates a predicate on one row held as a dict —
-the reference's semantics restated on the host, for callers and as the cross-check of the compiler.  Nothing here touches
-the GPU.
+the reference's semantics restated on the host, for callers and as the cross-check of the compiler.  `atoi` and
+`parse_float` restate strconv.Atoi / strconv.ParseFloat as the header's cph_col_to_number comment does.  Nothing here
+touches the GPU.
 """
 from __future__ import annotations
 
+import math
+import re
+import struct
+
 LIKE, NOT, ALL, ANY = 1, 2, 3, 4   # CPH_PRED_*
+INT_LT, FLT_LT = 16, 24            # CPH_PRED_INT_LT / CPH_PRED_FLT_LT; + the relation's index in RELS
+RELS = ("<", "<=", "==", "!=", ">=", ">")
 MAX_OPS, MAX_LIKE, MAX_STACK = 64, 32, 32
+NUM_OK, NUM_ERR_SYNTAX, NUM_ERR_RANGE, NUM_ERR_UNSUPPORTED = 0, 1, 2, 3   # CPH_NUM_*
+INT64_MAX, INT64_MIN = (1 << 63) - 1, -(1 << 63)
 
 
 def _bytes(v) -> bytes:
@@ -67,11 +78,167 @@ class Not(Pred):
         return f"Not({self.pred!r})"
 
 
+class _NumCmp(Pred):
+    def __init__(self, column, rel, literal):
+        if rel not in RELS:
+            raise ValueError(f"unknown relation {rel!r}: one of {' '.join(RELS)}")
+        self.column, self.rel, self.literal = str(column), rel, literal
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.column!r}, {self.rel!r}, {self.literal!r})"
+
+
+class IntCmp(_NumCmp):
+    """IntCmp("born", ">", 1970): `v, err := row.ValueAsInt(column); return err == nil && v REL k`.  A row whose value
+    does not convert (or that lacks the column) is false under every relation, "!=" included."""
+
+    def __init__(self, column, rel, k):
+        k = int(k)
+        if not INT64_MIN <= k <= INT64_MAX:
+            raise ValueError("IntCmp: the literal is not an int64")
+        super().__init__(column, rel, k)
+
+
+class FloatCmp(_NumCmp):
+    """FloatCmp("price", "<=", 9.99): the same over ValueAsFloat64.  Comparisons are IEEE: with a NaN on either side
+    only "!=" holds."""
+
+    def __init__(self, column, rel, x):
+        super().__init__(column, rel, float(x))
+
+
 def _operands(preds):
     for p in preds:
         if not isinstance(p, Pred):
-            raise TypeError(f"not a predicate: {p!r} (closures cannot run on the device; use Like / All / Any / Not)")
+            raise TypeError(f"not a predicate: {p!r} (closures cannot run on the device; use Like / All / Any / Not / IntCmp / FloatCmp)")
     return list(preds)
+
+
+# ---- strconv on the host -----------------------------------------------------------------------------------------------
+
+def atoi(value) -> tuple:
+    """strconv.Atoi on a 64-bit int: (value, NUM_*).  Decided left to right: a byte that is no digit is a syntax error
+    (value 0) unless the unsigned accumulator has overflowed 2^64 in front of it, which is a range error at that byte
+    (INT64_MAX, or INT64_MIN after '-')."""
+    b = _bytes(value)
+    neg = b[:1] == b"-"
+    digits = b[1:] if b[:1] in (b"+", b"-") else b
+    if not digits:
+        return 0, NUM_ERR_SYNTAX
+    n = 0
+    for c in digits:
+        if not 0x30 <= c <= 0x39:
+            return 0, NUM_ERR_SYNTAX
+        n = n * 10 + (c - 0x30)
+        if n >= 1 << 64:
+            return (INT64_MIN if neg else INT64_MAX), NUM_ERR_RANGE
+    if neg:
+        return (-n, NUM_OK) if n <= 1 << 63 else (INT64_MIN, NUM_ERR_RANGE)
+    return (n, NUM_OK) if n < 1 << 63 else (INT64_MAX, NUM_ERR_RANGE)
+
+
+_DECIMAL = re.compile(rb"[+-]?(?:[0-9]+(?:\.[0-9]*)?|\.[0-9]+)(?:[eE][+-]?[0-9]+)?", re.ASCII)
+_INF = re.compile(rb"[+-]?(?:inf|infinity)", re.ASCII | re.IGNORECASE)
+_DEC_PARTS = re.compile(rb"[+-]?([0-9]*)\.?([0-9]*)(?:[eE]([+-]?[0-9]+))?", re.ASCII)
+
+
+def parse_float(value) -> tuple:
+    """strconv.ParseFloat(s, 64): (value, NUM_*).  The grammar is checked BEFORE float() sees the text (Python would
+    accept spaces, underscores and a signed nan).  A value with '_' or a 0x / 0X prefix is NUM_ERR_UNSUPPORTED (Go may
+    accept it; this library does not decide); a magnitude beyond the largest double is a range error with +-Inf."""
+    b = _bytes(value)
+    rest = b[1:] if b[:1] in (b"+", b"-") else b
+    if not b:
+        return 0.0, NUM_ERR_SYNTAX
+    if b"_" in b or rest[:2].lower() == b"0x":
+        return 0.0, NUM_ERR_UNSUPPORTED
+    if _INF.fullmatch(b):
+        return (-math.inf if b[:1] == b"-" else math.inf), NUM_OK
+    if b.lower() == b"nan":
+        return math.nan, NUM_OK
+    if not _DECIMAL.fullmatch(b):
+        return 0.0, NUM_ERR_SYNTAX
+    v = float(b.decode("ascii"))   # correctly rounded; overflow gives inf, underflow 0 or a denormal
+    return v, (NUM_ERR_RANGE if math.isinf(v) else NUM_OK)
+
+
+def float_is_deferred(value) -> bool:
+    """True when the device does not decide this (valid, decimal) value itself and the library's host side finishes it:
+    a mantissa — the first 19 significant digits — that is truncated or >= 2^53, or a decimal exponent outside Clinger's
+    exact cases (-22..37; above 0 only while the mantissa, times 10^(e-22) when e > 22, stays <= 1e15).  This is what cph_numcol.host_rows counts."""
+    b = _bytes(value)
+    if b"_" in b or not _DECIMAL.fullmatch(b):
+        return False
+    ip, fp, ex = _DEC_PARTS.fullmatch(b).groups()
+    digs = (ip + fp).lstrip(b"0")
+    dp = len(ip) - (len(ip + fp) - len(digs))
+    if not digs:
+        return False
+    trunc = any(c != 0x30 for c in digs[19:])
+    digs = digs[:19]
+    mant = int(digs)
+    e = 0
+    if ex is not None:
+        e = min(int(ex.lstrip(b"+-") or b"0"), 99999) * (-1 if ex[:1] == b"-" else 1)
+    exp = dp - len(digs) + e
+    if trunc or mant >= 1 << 53:
+        return True
+    if exp == 0 or -22 <= exp < 0:
+        return False
+    if 0 < exp <= 37:
+        return float(mant) * (10.0 ** (exp - 22) if exp > 22 else 1.0) > 1e15
+    return True
+
+
+def _go_quote(b: bytes) -> str:
+    r"""%q of a string: printable ASCII stays, '"' and the backslash get a backslash, the controls Go names become
+    \a \b \f \n \r \t \v, other control bytes and invalid UTF-8 become \xNN.  unicode.IsPrint is NOT modelled: every
+    validly encoded rune >= U+0080 is copied."""
+    out = []
+    i = 0
+    named = {7: "\\a", 8: "\\b", 12: "\\f", 10: "\\n", 13: "\\r", 9: "\\t", 11: "\\v"}
+    while i < len(b):
+        c = b[i]
+        if c < 0x80:
+            if c == 0x22 or c == 0x5C:
+                out.append("\\" + chr(c))
+            elif c in named:
+                out.append(named[c])
+            elif c < 0x20 or c == 0x7F:
+                out.append("\\x%02x" % c)
+            else:
+                out.append(chr(c))
+            i += 1
+            continue
+        for k in (2, 3, 4):
+            try:
+                out.append(b[i:i + k].decode("utf-8"))
+                i += k
+                break
+            except UnicodeDecodeError:
+                continue
+        else:
+            out.append("\\x%02x" % c)
+            i += 1
+    return '"' + "".join(out) + '"'
+
+
+def conversion_error(column, value, kind, as_float=False) -> str:
+    """The reference's error text (csvplus.go:176, :198):
+    `column "<name>": cannot convert "<value>" to integer: invalid syntax` (or `to float`, or `value out of range`);
+    column and value are quoted as Go's %q does, see _go_quote."""
+    what = {NUM_ERR_SYNTAX: "invalid syntax", NUM_ERR_RANGE: "value out of range",
+            NUM_ERR_UNSUPPORTED: "not decided by this library (digit separators, hexadecimal floats)"}[kind]
+    return f"column {_go_quote(_bytes(column))}: cannot convert {_go_quote(_bytes(value))} to {'float' if as_float else 'integer'}: {what}"
+
+
+def _cmp(rel, a, b) -> bool:
+    return {"<": a < b, "<=": a <= b, "==": a == b, "!=": a != b, ">=": a >= b, ">": a > b}[rel]
+
+
+def _num_holds(is_float, rel, value, literal) -> bool:
+    v, kind = parse_float(value) if is_float else atoi(value)
+    return kind == NUM_OK and _cmp(rel, v, literal)
 
 
 def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of record uses)
@@ -93,6 +260,16 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
                 ops.append((LIKE, used.index(name), value))
             if len(p.items) > 1:
                 ops.append((ALL, len(p.items), None))
+        elif isinstance(p, _NumCmp):
+            flt = isinstance(p, FloatCmp)
+            op = (FLT_LT if flt else INT_LT) + RELS.index(p.rel)
+            lit = struct.pack("<d" if flt else "<q", p.literal)
+            if p.column not in known:
+                ops.append((op, -1, lit))
+            else:
+                if p.column not in used:
+                    used.append(p.column)
+                ops.append((op, used.index(p.column), lit))
         elif isinstance(p, Not):
             emit(p.pred)
             ops.append((NOT, 0, None))
@@ -106,7 +283,7 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
     emit(pred)
     depth = likes = 0
     for op, arg, _ in ops:
-        if op == LIKE:
+        if op == LIKE or op >= INT_LT:
             depth += 1
             likes += 1
         elif op in (ALL, ANY):
@@ -116,7 +293,7 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
     if len(ops) > MAX_OPS:
         raise ValueError(f"predicate compiles to {len(ops)} ops, more than {MAX_OPS}")
     if likes > MAX_LIKE:
-        raise ValueError(f"predicate has {likes} Like terms, more than {MAX_LIKE}")
+        raise ValueError(f"predicate has {likes} Like and numeric terms, more than {MAX_LIKE}")
     return used, ops
 
 
@@ -130,6 +307,11 @@ def matches(pred: Pred, row) -> bool:
             if v is None or _bytes(v) != value:
                 return False
         return True
+    if isinstance(pred, _NumCmp):
+        v = row.get(pred.column)
+        if v is None:
+            v = row.get(pred.column.encode("utf-8"))
+        return v is not None and _num_holds(isinstance(pred, FloatCmp), pred.rel, v, pred.literal)
     if isinstance(pred, Not):
         return not matches(pred.pred, row)
     if isinstance(pred, All):
@@ -145,6 +327,10 @@ def run_ops(ops, values) -> bool:
     for op, arg, value in ops:
         if op == LIKE:
             st.append(arg >= 0 and _bytes(values[arg]) == value)
+        elif op >= INT_LT:
+            flt = op >= FLT_LT
+            (lit,) = struct.unpack("<d" if flt else "<q", value)
+            st.append(arg >= 0 and _num_holds(flt, RELS[op - (FLT_LT if flt else INT_LT)], values[arg], lit))
         elif op == NOT:
             st.append(not st.pop())
         else:

@@ -711,15 +711,27 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
  * Like(Row{"a": x, "b": y}) is  LIKE a x, LIKE b y, ALL 2.  A program must leave exactly one value.  Limits (checked):
  * at most CPH_PRED_MAX_OPS ops, at most CPH_PRED_MAX_LIKE LIKE ops, a stack of at most CPH_PRED_MAX_STACK values; the
  * literal of a LIKE may have any length.
+ *
+ * Numeric compare terms — the reference's `year, _ := row.ValueAsInt("born"); return year > 1970` (csvplus_test.go:272-281)
+ * as data:
+ *   CPH_PRED_INT_LT .. CPH_PRED_INT_GT (16..21, in the order LT LE EQ NE GE GT)   push (int64 of column `arg`)   REL literal
+ *   CPH_PRED_FLT_LT .. CPH_PRED_FLT_GT (24..29, same order)                       push (float64 of column `arg`) REL literal
+ * `value` points at exactly 8 host bytes: the int64_t or the double literal.  The column's value is converted as
+ * cph_col_to_number converts it; a row that does NOT convert (syntax, range, unsupported) pushes FALSE under every
+ * relation, NE included — what the reference's closure does with the error — and arg = -1 (no such column) pushes false.
+ * Float relations are IEEE: with a NaN on either side only NE holds.  A numeric term counts against CPH_PRED_MAX_LIKE
+ * like a LIKE term (LIKE plus numeric terms <= 32).  Ops 0, 5..15, 22, 23 and 30.. are invalid.
  */
 enum { CPH_PRED_LIKE = 1, CPH_PRED_NOT = 2, CPH_PRED_ALL = 3, CPH_PRED_ANY = 4 };
+enum { CPH_PRED_INT_LT = 16, CPH_PRED_INT_LE = 17, CPH_PRED_INT_EQ = 18, CPH_PRED_INT_NE = 19, CPH_PRED_INT_GE = 20, CPH_PRED_INT_GT = 21 };
+enum { CPH_PRED_FLT_LT = 24, CPH_PRED_FLT_LE = 25, CPH_PRED_FLT_EQ = 26, CPH_PRED_FLT_NE = 27, CPH_PRED_FLT_GE = 28, CPH_PRED_FLT_GT = 29 };
 #define CPH_PRED_MAX_OPS   64
 #define CPH_PRED_MAX_LIKE  32
 #define CPH_PRED_MAX_STACK 32
 typedef struct {
     int32_t    op;      /* CPH_PRED_* */
-    int32_t    arg;     /* LIKE: column (index into cols) or -1; ALL / ANY: operand count; NOT: ignored */
-    cph_strval value;   /* LIKE only; host memory */
+    int32_t    arg;     /* LIKE / INT_* / FLT_*: column (index into cols) or -1; ALL / ANY: operand count; NOT: ignored */
+    cph_strval value;   /* LIKE: the literal's bytes; INT_* / FLT_*: 8 bytes, an int64_t / a double; host memory */
 } cph_pred_op;
 
 enum { CPH_FILTER_WHERE = 0, CPH_FILTER_TAKE_WHILE = 1, CPH_FILTER_DROP_WHILE = 2 };
@@ -755,7 +767,8 @@ typedef struct {
  * its two kernels.  The result is complete when the call returns (the other calls' rule).
  *
  * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / prog / opts / out, cols NULL with ncols > 0, nops outside
- * 1..CPH_PRED_MAX_OPS, an op outside 1..4, a LIKE column outside -1..ncols-1, a LIKE value with a length but no pointer,
+ * 1..CPH_PRED_MAX_OPS, an unknown op, a LIKE / numeric column outside -1..ncols-1, a LIKE value with a length but no pointer,
+ * a numeric literal that is not exactly 8 bytes behind a non-NULL pointer,
  * a negative or too large ALL / ANY count (stack underflow), a NOT on an empty stack, a program that does not leave
  * exactly one value, the limits above, out_bits or row-id bits other than 32 / 64, an unknown mode or out_mem, a short
  * identity column.  CPH_ERR_TOO_MANY_ROWS when out_bits == 32 and first_row + nrows > 2^32 - 1, and when nrows alone is
@@ -775,6 +788,49 @@ CPH_API void    cph_rowlist_release(cph_rowlist* list);
  */
 CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel_mem, const cph_rowlist* list, int32_t out_mem,
                                 cph_rowlist** out);
+
+/* ---- Row.ValueAsInt / Row.ValueAsFloat64 for a whole column (csvplus.go:165-205) ---- */
+/*
+ * One string column, read through an optional row selection, as int64 or float64 with the semantics of Go's strconv
+ * (restated here from its published behaviour; the reference tree pins only the two error strings, csvplus_test.go:911-958).
+ *
+ * CPH_NUM_INT64 = strconv.Atoi on a 64-bit int, decided left to right: "", "+", "-" are syntax errors; one optional
+ * '+' / '-', then one or more '0'..'9' (any number of leading zeros; "-0" is 0) is the value; any other byte met BEFORE
+ * the unsigned accumulator overflows 2^64 is a syntax error (value 0); the overflow itself is a range error AT THAT BYTE
+ * (later bytes are not looked at: "99999999999999999999x" is a range error, "9223372036854775808x" a syntax error);
+ * a fully parsed magnitude >= 2^63 without '-', or > 2^63 with it, is a range error.  Range errors carry INT64_MAX, or
+ * INT64_MIN after '-'.
+ *
+ * CPH_NUM_FLOAT64 = strconv.ParseFloat(s, 64): [+-]?inf, [+-]?infinity and nan (no sign), ASCII case-insensitive; else
+ * [+-]? ( D+ [ . D* ] | . D+ ) ( [eE] [+-]? D+ )?; everything else is a syntax error (value 0).  The result is the
+ * correctly rounded double (a zero mantissa gives +-0; underflow to 0 or a denormal is no error); a magnitude beyond the
+ * largest double is a range error with value +-Inf.  A value that contains '_' or starts 0x / 0X after the sign gets
+ * CPH_NUM_ERR_UNSUPPORTED and value 0: Go may accept it (digit separators, hexadecimal floats), this library does not
+ * decide — a stated limit, never a silent wrong answer.  The device converts every value whose mantissa (the first 19
+ * significant digits, none dropped but zeros) is below 2^53 and whose decimal exponent lies in -22..37 (Clinger's exact
+ * cases: one IEEE operation); the other valid rows are finished on the library's host side, and `host_rows` counts them.
+ *
+ * A conversion error is DATA: the call returns CPH_OK and the struct says what failed.  col / sel / nrows mean what they
+ * mean for cph_csv_write_rows with one column (host or device, fixed-width or 32 / 64-bit offsets, optional row ids with
+ * a base: a Join's output converts without being materialised).  CPH_ERR_INVALID (with a message): NULL ctx / col / out,
+ * an unknown kind or out_mem, row-id bits other than 32 / 64, an identity column whose row count is not nrows.
+ * nrows == 0 is legal (values and status are NULL).
+ */
+enum { CPH_NUM_INT64 = 1, CPH_NUM_FLOAT64 = 2 };
+enum { CPH_NUM_OK = 0, CPH_NUM_ERR_SYNTAX = 1, CPH_NUM_ERR_RANGE = 2, CPH_NUM_ERR_UNSUPPORTED = 3 };
+typedef struct {
+    uint64_t       nrows;
+    const void*    values;          /* int64_t[nrows] or double[nrows], in `mem`; what Go returns beside the error at error rows */
+    const uint8_t* status;          /* CPH_NUM_* per row, in `mem` */
+    int32_t        kind, mem;
+    uint64_t       nerrors;
+    uint64_t       first_error_row; /* position in the selection; UINT64_MAX when nerrors == 0 */
+    int32_t        first_error_kind, reserved_;
+    uint64_t       host_rows;       /* float only: rows finished on the host */
+} cph_numcol;
+CPH_API int32_t cph_col_to_number(cph_ctx* ctx, const cph_strcol* col, const cph_rowsel* sel, uint64_t nrows, int32_t kind,
+                                  int32_t out_mem, cph_numcol** out);
+CPH_API void    cph_numcol_release(cph_numcol* col);
 
 /* ---- CSV ingest: bytes -> SoA string columns (csvplus.go:1080-1146) ----------- */
 /*

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""cph_col_to_number and the numeric compare predicates at scale, device-resident columns with 32-bit offsets:
+
+    to_int               over `rows` values of 1-7 decimal digits
+    to_float             over `rows` price-like values ("%d.%02d", integer part < 100 000)
+    filter_rows(IntCmp)  WHERE v > median over the integer column
+    filter_rows(Like)    WHERE v == one of its values over the same column — the yardstick: it reads the same bytes
+                         through the same evaluation kernel (it runs without this feature too: measure it at the parent
+                         commit for the comparison; `like` alone as the third argument skips the rest)
+
+Per case: warm-up, then REPS synchronised calls with the profiler off (wall time per call), and a second pass with
+cph_ctx_profile on for the kernel times.  Next to it cph_calibrate kind 0, this box's streaming-copy rate.
+
+    python tools/microbench/numparse.py [rows=1e8] [reps=20] [like]
+"""
+import sys
+import time
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from csvplus_amd import Context, StrCol, _native as N  # noqa: E402
+from csvplus_amd.materialize import filter_rows  # noqa: E402
+from csvplus_amd.predicates import Like  # noqa: E402
+
+M = int(float(sys.argv[1])) if len(sys.argv) > 1 else 100_000_000
+REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+LIKE_ONLY = len(sys.argv) > 3 and sys.argv[3] == "like"
+ctx = Context(0)
+
+
+def sync():
+    ctx.synchronize()
+    torch.cuda.synchronize()
+
+
+def timed(fn, reps):
+    fn()   # warm-up
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    sync()
+    return (time.perf_counter() - t0) / reps
+
+
+def decimal_column(v, frac=None):
+    """The decimal text of the non-negative integers v (and, with frac, of "v.ff") as a StrCol, built with numpy."""
+    nd = np.ones(len(v), dtype=np.int64)
+    for k in range(1, 10):
+        nd += v >= 10 ** k
+    lens = nd + (3 if frac is not None else 0)
+    offs = np.zeros(len(v) + 1, dtype=np.uint64)
+    np.cumsum(lens, out=offs[1:])
+    data = np.empty(int(offs[-1]), dtype=np.uint8)
+    end = offs[1:].astype(np.int64)
+    if frac is not None:
+        data[end - 1] = 0x30 + frac % 10
+        data[end - 2] = 0x30 + frac // 10
+        data[end - 3] = 0x2E
+        end = end - 3
+    w = v.copy()
+    for k in range(int(nd.max())):
+        live = nd > k
+        data[end[live] - 1 - k] = 0x30 + w[live] % 10
+        w //= 10
+    return StrCol(data, offs.astype(np.uint32), len(v), 32)
+
+
+def profiled(fn):
+    ctx.profile(True)
+    ctx.profile_read(reset=True)
+    for _ in range(3):
+        fn()
+    st = ctx.profile_read(reset=True)
+    ctx.profile(False)
+    return ", ".join(f"{k}={v['total_ms'] / 3:.3f} ms" for k, v in st.items())
+
+
+copy_bytes = 1 << 30
+copy_ms = ctx.calibrate("copy", copy_bytes, reps=10)
+copy_rate = 2 * copy_bytes / (copy_ms * 1e-3)
+print(f"rows {M}, reps {REPS}; streaming copy (cph_calibrate kind 0): {copy_rate / 1e9:.0f} GB/s", flush=True)
+
+rng = np.random.default_rng(1)
+digits = rng.integers(1, 8, M)
+ints = (rng.random(M) * 10.0 ** digits).astype(np.int64)
+hint = decimal_column(ints)
+dint = hint.to_device()
+in_bytes = hint.nbytes_values() + hint.nbytes_offsets()
+cols = {"v": dint}
+like = Like(v=hint.value(0))
+
+
+def report(label, wall, bytes_moved, extra):
+    print(f"{label:22s}: call {wall * 1e3:8.3f} ms  {bytes_moved / wall / 1e9:7.1f} GB/s by the model ({100 * bytes_moved / wall / copy_rate:4.1f} % of copy) | {extra}",
+          flush=True)
+
+
+f = lambda: filter_rows(ctx, cols, like, out_mem=N.CPH_MEM_DEVICE).release()   # noqa: E731
+rl = filter_rows(ctx, cols, like, out_mem=N.CPH_MEM_DEVICE)
+kept = len(rl)
+rl.release()
+report("filter_rows(Like)", timed(f, REPS), in_bytes + 2 * M / 8 + 4 * kept, f"kept {kept} | " + profiled(f))
+if not LIKE_ONLY:
+    from csvplus_amd.materialize import to_float, to_int
+    from csvplus_amd.predicates import IntCmp
+
+    pred = IntCmp("v", ">", int(np.median(ints)))
+    f = lambda: filter_rows(ctx, cols, pred, out_mem=N.CPH_MEM_DEVICE).release()   # noqa: E731
+    rl = filter_rows(ctx, cols, pred, out_mem=N.CPH_MEM_DEVICE)
+    kept = len(rl)
+    rl.release()
+    assert kept == int((ints > int(np.median(ints))).sum())
+    report("filter_rows(IntCmp)", timed(f, REPS), in_bytes + 2 * M / 8 + 4 * kept, f"kept {kept} | " + profiled(f))
+    f = lambda: to_int(ctx, dint, out_mem=N.CPH_MEM_DEVICE).release()   # noqa: E731
+    r = to_int(ctx, dint, out_mem=N.CPH_MEM_DEVICE)
+    assert r.nerrors == 0
+    r.release()
+    report("to_int", timed(f, REPS), in_bytes + 9 * M, profiled(f))
+    del dint, cols
+    torch.cuda.empty_cache()
+    hflt = decimal_column(rng.integers(0, 100000, M), rng.integers(0, 100, M))
+    dflt = hflt.to_device()
+    f = lambda: to_float(ctx, dflt, out_mem=N.CPH_MEM_DEVICE).release()   # noqa: E731
+    r = to_float(ctx, dflt, out_mem=N.CPH_MEM_DEVICE)
+    assert r.nerrors == 0
+    host_rows = r.host_rows
+    r.release()
+    report("to_float", timed(f, REPS), hflt.nbytes_values() + hflt.nbytes_offsets() + 9 * M, f"host_rows {host_rows} | " + profiled(f))
+ctx.close()
