@@ -7,7 +7,8 @@ the SoA column staging and the multi-GPU sharding.  There is no CPU fallback.
 Modules: `engine` (one GPU: index_on / join / chained_join on torch device memory), `dist` (probe-row sharding +
 allgatherv over RCCL), `streaming` (host -> device pipeline of join chunks), `ingest` (CSV text -> columns),
 `materialize` (gather through row ids, ToCsv, ToJSON, Filter / TakeWhile / DropWhile over `predicates`: Like, All, Any,
-Not, IntCmp, FloatCmp as plain data; ValueAsInt / ValueAsFloat64 for a whole column: to_int / to_float), `dedup` (ResolveDuplicates over the device index),
+Not, IntCmp, FloatCmp as plain data; ValueAsInt / ValueAsFloat64 for a whole column: to_int / to_float), `dedup` (ResolveDuplicates over the device index: a callback over the groups, or a named rule — First, Last, DropAll,
+MinBy, MaxBy — resolved on the device: resolve_duplicates_device),
 `pipeline` (CSV -> indices -> chained join -> CSV or JSON, all in HBM), `datagen` (deterministic synthetic tables).
 """
 from . import _native as native  # noqa: F401

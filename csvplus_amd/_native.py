@@ -183,6 +183,21 @@ class cph_groups(C.Structure):
     _fields_ = [("ngroups", C.c_uint64), ("lower", C.c_void_p), ("upper", C.c_void_p)]
 
 
+CPH_RESOLVE_FIRST, CPH_RESOLVE_LAST, CPH_RESOLVE_DROP, CPH_RESOLVE_MIN, CPH_RESOLVE_MAX = 1, 2, 3, 4, 5
+CPH_ORDER_BYTES = 3   # beside CPH_NUM_INT64 / CPH_NUM_FLOAT64
+
+
+class cph_resolve_opts(C.Structure):
+    _fields_ = [("rule", C.c_int32), ("order_kind", C.c_int32), ("keep_last_row", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class cph_resolved(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("positions", C.c_void_p), ("mem", C.c_int32), ("reserved_", C.c_int32),
+                ("ngroups", C.c_uint64), ("group_rows", C.c_uint64), ("nerrors", C.c_uint64),
+                ("first_error_position", C.c_uint64), ("first_error_row", C.c_uint64),
+                ("first_error_kind", C.c_int32), ("reserved2_", C.c_int32), ("host_rows", C.c_uint64)]
+
+
 CPH_DIST_ID_BYTES = 128
 CPH_MAX_GATHER = 8
 
@@ -300,6 +315,9 @@ PROTOTYPES = [
     ("cph_index_dup_groups", C.c_int32, [_P, _P, C.POINTER(C.POINTER(cph_groups))]),
     ("cph_groups_release", None, [C.POINTER(cph_groups)]),
     ("cph_index_select", C.c_int32, [_P, _P, _P, C.c_uint64, C.POINTER(_P)]),
+    ("cph_index_resolve", C.c_int32,
+     [_P, _P, C.POINTER(cph_resolve_opts), C.POINTER(cph_strcol), C.c_int32, C.POINTER(_P), C.POINTER(C.POINTER(cph_resolved))]),
+    ("cph_resolved_release", None, [C.POINTER(cph_resolved)]),
     ("cph_index_save", C.c_int32, [_P, _P, C.c_char_p]),
     ("cph_index_load", C.c_int32, [_P, C.c_char_p, C.POINTER(_P)]),
     ("cph_index_find", C.c_int32,

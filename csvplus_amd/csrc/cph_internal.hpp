@@ -751,6 +751,8 @@ bool index_desc_size(const uint8_t* p, size_t n, size_t* need);     // size of t
 bool index_desc_parse(const uint8_t* p, size_t n, cph_index* ix);
 Status index_adopt_payload(cph_ctx* ctx, cph_index* ix);            // validate the device arrays, finish the index
 size_t index_code_bytes(const cph_index* ix);                       // bytes of sorted codes per row
+// nx (fresh) = index over the n strictly ascending, already checked sorted positions d_pos (device memory) of ix
+Status index_select_device(cph_ctx* ctx, const cph_index* ix, const uint64_t* d_pos, uint64_t n, cph_index* nx);
 
 // chain.hip
 struct ChainStep {
@@ -788,6 +790,7 @@ void warm_chain();
 void warm_materialize();
 void warm_csv_ingest();
 void warm_index_ops();
+void warm_resolve();
 void warm_small_build();
 void warm_window_sort();
 // host_encode.hip: IndexOn over one short key column in host memory through host-formed codes; *taken = false: not applicable

@@ -152,6 +152,44 @@ static size_t code_bytes(const cph_index* ix) {
 }
 
 
+// The device half of cph_index_select, shared with cph_index_resolve (resolve.hip): nx = a new index over the n strictly
+// ascending sorted positions d_pos (DEVICE memory, already checked) of ix — windows, gathered perm and codes, unique scan and
+// table decision.  nx is a fresh cph_index.
+Status index_select_device(cph_ctx* ctx, const cph_index* ix, const uint64_t* d_pos, uint64_t n, cph_index* nx) {
+    nx->ctx = ctx;
+    nx->nrows = n;
+    nx->nkeycols = ix->nkeycols;
+    nx->table_rows = ix->table_rows;
+    nx->codec = ix->codec;
+    nx->sort_passes = 0;
+    for (const auto& w : ix->windows) {   // a long-key index keeps its windows (their device blocks are re-uploaded)
+        nx->windows.emplace_back();
+        cph_key_window& nw = nx->windows.back();
+        nw.codec = w.codec;
+        nw.nseg = w.nseg;
+        memcpy(nw.seg_col, w.seg_col, sizeof nw.seg_col);
+        memcpy(nw.seg_skip, w.seg_skip, sizeof nw.seg_skip);
+        memcpy(nw.seg_take, w.seg_take, sizeof nw.seg_take);
+        nw.word_base = w.word_base;
+        CPH_TRY(codec_upload(ctx, nw.codec, &nw.codec_dev));
+    }
+    CPH_TRY(nx->perm.alloc(&ctx->pool, n * sizeof(uint32_t)));
+    CPH_TRY(nx->sorted_codes.alloc(&ctx->pool, n * code_bytes(ix)));
+    if (n) {
+        const unsigned grid = grid_for_items(n);
+        ProfScope ps(ctx, "k_select", (double)n * (8.0 + 2.0 * (4.0 + (double)code_bytes(ix))));
+        hipLaunchKernelGGL(k_select_u32, dim3(grid), dim3(256), 0, ctx->stream, ix->perm.as<uint32_t>(), d_pos, n, nx->perm.as<uint32_t>());
+        if (ix->codec.key32)
+            hipLaunchKernelGGL(k_select_u32, dim3(grid), dim3(256), 0, ctx->stream, ix->sorted_codes.as<uint32_t>(), d_pos, n, nx->sorted_codes.as<uint32_t>());
+        else
+            for (int w = 0; w < ix->total_words(); w++)
+                hipLaunchKernelGGL(k_select_u64, dim3(grid), dim3(256), 0, ctx->stream, ix->sorted_codes.as<uint64_t>() + (uint64_t)w * ix->nrows,
+                                   d_pos, n, nx->sorted_codes.as<uint64_t>() + (uint64_t)w * n);
+        CPH_HIP_TRY(hipGetLastError());
+    }
+    return finish_index(ctx, nx);
+}
+
 // ---- index descriptor: everything of an index except its two device arrays -----------------------------------
 // (little endian).  Shared by the file format (cph_index_save/_load) and by the broadcast of a built index to the
 // other ranks (dist.hip): both move descriptor, sorted codes, perm.
@@ -526,47 +564,16 @@ CPH_API int32_t cph_index_select(cph_ctx* ctx, const cph_index* ix, const uint64
     auto* nx = new (std::nothrow) cph_index();
     if (!nx) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
     auto run = [&]() -> Status {
-        nx->ctx = ctx;
-        nx->nrows = n;
-        nx->nkeycols = ix->nkeycols;
-        nx->table_rows = ix->table_rows;
-        nx->codec = ix->codec;
-        nx->sort_passes = 0;
-        for (const auto& w : ix->windows) {   // a long-key index keeps its windows (their device blocks are re-uploaded)
-            nx->windows.emplace_back();
-            cph_key_window& nw = nx->windows.back();
-            nw.codec = w.codec;
-            nw.nseg = w.nseg;
-            memcpy(nw.seg_col, w.seg_col, sizeof nw.seg_col);
-            memcpy(nw.seg_skip, w.seg_skip, sizeof nw.seg_skip);
-            memcpy(nw.seg_take, w.seg_take, sizeof nw.seg_take);
-            nw.word_base = w.word_base;
-            CPH_TRY(codec_upload(ctx, nw.codec, &nw.codec_dev));
-        }
         DevBuf pos, bad;
         CPH_TRY(pos.alloc(&ctx->pool, n * sizeof(uint64_t)));
         CPH_TRY(bad.alloc(&ctx->pool, sizeof(uint32_t)));
         CPH_HIP_TRY(hipMemsetAsync(bad.get(), 0, sizeof(uint32_t), ctx->stream));
         if (n) CPH_HIP_TRY(hipMemcpyAsync(pos.get(), positions, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        const unsigned grid = grid_for_items(n);
-        hipLaunchKernelGGL(k_select_check, dim3(grid), dim3(256), 0, ctx->stream, pos.as<uint64_t>(), n, ix->nrows, bad.as<uint32_t>());
+        hipLaunchKernelGGL(k_select_check, dim3(grid_for_items(n)), dim3(256), 0, ctx->stream, pos.as<uint64_t>(), n, ix->nrows, bad.as<uint32_t>());
         uint32_t isbad = 0;
         CPH_TRY(read_device_value(ctx, bad.as<uint32_t>(), &isbad));
         if (isbad) return {CPH_ERR_INVALID, "positions must be strictly ascending sorted positions of the index"};
-        CPH_TRY(nx->perm.alloc(&ctx->pool, n * sizeof(uint32_t)));
-        CPH_TRY(nx->sorted_codes.alloc(&ctx->pool, n * code_bytes(ix)));
-        if (n) {
-            ProfScope ps(ctx, "k_select", (double)n * (8.0 + 2.0 * (4.0 + (double)code_bytes(ix))));
-            hipLaunchKernelGGL(k_select_u32, dim3(grid), dim3(256), 0, ctx->stream, ix->perm.as<uint32_t>(), pos.as<uint64_t>(), n, nx->perm.as<uint32_t>());
-            if (ix->codec.key32)
-                hipLaunchKernelGGL(k_select_u32, dim3(grid), dim3(256), 0, ctx->stream, ix->sorted_codes.as<uint32_t>(), pos.as<uint64_t>(), n, nx->sorted_codes.as<uint32_t>());
-            else
-                for (int w = 0; w < ix->total_words(); w++)
-                    hipLaunchKernelGGL(k_select_u64, dim3(grid), dim3(256), 0, ctx->stream, ix->sorted_codes.as<uint64_t>() + (uint64_t)w * ix->nrows,
-                                       pos.as<uint64_t>(), n, nx->sorted_codes.as<uint64_t>() + (uint64_t)w * n);
-            CPH_HIP_TRY(hipGetLastError());
-        }
-        return finish_index(ctx, nx);
+        return index_select_device(ctx, ix, pos.as<uint64_t>(), n, nx);
     };
     Status s = run();
     if (!s.ok()) {

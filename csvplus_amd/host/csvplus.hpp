@@ -475,6 +475,25 @@ inline std::shared_ptr<const PredProgram> compilePred(const Pred& p) {
 class DataSource;
 
 // ---- Index (:612-641) ------------------------------------------------------------------------------
+// ---- named resolvers for Index::ResolveDuplicates, as DATA ---------------------------------------------------------------
+// The resolvers people write are a handful of fixed rules; like the named predicates they are declarative, so the device can
+// run them (cph_index_resolve): keep the first / last row of a pack, drop the pack, keep the row whose column is smallest /
+// largest as an integer, a float or a string.  Ties go to the first row of the pack; a NaN loses to every number.
+struct Resolver {
+    int32_t rule = 0;         // CPH_RESOLVE_*
+    int32_t order_kind = 0;   // CPH_NUM_INT64 / CPH_NUM_FLOAT64 / CPH_ORDER_BYTES (MIN / MAX only)
+    std::string column;       // the order column (MIN / MAX only)
+};
+inline Resolver KeepFirst() { return {CPH_RESOLVE_FIRST, 0, {}}; }
+inline Resolver KeepLast() { return {CPH_RESOLVE_LAST, 0, {}}; }
+inline Resolver DropDuplicates() { return {CPH_RESOLVE_DROP, 0, {}}; }
+inline Resolver KeepMinInt(std::string col) { return {CPH_RESOLVE_MIN, CPH_NUM_INT64, std::move(col)}; }
+inline Resolver KeepMaxInt(std::string col) { return {CPH_RESOLVE_MAX, CPH_NUM_INT64, std::move(col)}; }
+inline Resolver KeepMinFloat(std::string col) { return {CPH_RESOLVE_MIN, CPH_NUM_FLOAT64, std::move(col)}; }
+inline Resolver KeepMaxFloat(std::string col) { return {CPH_RESOLVE_MAX, CPH_NUM_FLOAT64, std::move(col)}; }
+inline Resolver KeepMin(std::string col) { return {CPH_RESOLVE_MIN, CPH_ORDER_BYTES, std::move(col)}; }
+inline Resolver KeepMax(std::string col) { return {CPH_RESOLVE_MAX, CPH_ORDER_BYTES, std::move(col)}; }
+
 class Index {
 public:
     // Iterate (:618-620): rows sorted on the index columns, each handed out as a copy (:230)
@@ -489,6 +508,13 @@ public:
     // error (returned to the caller).  Compaction follows dedup (:810-867) to the letter.
     using ResolveFunc = std::function<std::pair<Row, Error>(const std::vector<Row>&)>;
     Error ResolveDuplicates(const ResolveFunc& resolve);
+    // The same with a named resolver (KeepFirst, KeepMaxInt("id"), ...): choice, compaction and tail rule run on the device,
+    // nothing crosses to the host per pack.  An order value inside a pack that does not convert returns the error a Go
+    // resolver handing back row.ValueAsInt's error would produce (:176 / :198) and leaves the rows as they were.  When some
+    // row lacks the order column the same rule runs through the callback overload: a missing column inside a pack is the
+    // reference's `missing column` error (:170), one outside a pack is never looked at.
+    Error ResolveDuplicates(const Resolver& resolver);
+    static ResolveFunc resolver_func(const Resolver& resolver);   // the rule as a callback
     // WriteTo (:655-680) / LoadIndex (:682-705).  The reference gob-encodes columns + rows; this file is a
     // length-prefixed little-endian dump of the same two values and is NOT readable by the Go library.
     Error WriteTo(const std::string& fileName) const;
@@ -1159,6 +1185,94 @@ inline Error Index::ResolveDuplicates(const ResolveFunc& resolve) {
     }
     impl_rows.resize(dest);                                                         // :862-864
     invalidate_device();   // the device twin is rebuilt from the surviving rows on next use
+    return Error();
+}
+
+// The named rule as the callback a Go program would write (rows of the pack in index order).
+inline Index::ResolveFunc Index::resolver_func(const Resolver& rs) {
+    return [rs](const std::vector<Row>& pack) -> std::pair<Row, Error> {
+        if (rs.rule == CPH_RESOLVE_FIRST) return {pack.front(), Error()};
+        if (rs.rule == CPH_RESOLVE_LAST) return {pack.back(), Error()};
+        if (rs.rule == CPH_RESOLVE_DROP) return {Row(), Error()};
+        const bool want_min = rs.rule == CPH_RESOLVE_MIN;
+        size_t best = SIZE_MAX;
+        int64_t bi = 0;
+        double bf = 0;
+        for (size_t i = 0; i < pack.size(); i++) {
+            auto it = pack[i].find(rs.column);
+            if (it == pack[i].end()) return {Row(), Error("missing column " + quote(rs.column))};   // :170 / :192
+            const std::string& v = it->second;
+            if (rs.order_kind == CPH_ORDER_BYTES) {
+                const int c = best == SIZE_MAX ? 0 : v.compare(pack[best].at(rs.column));   // char_traits<char>: unsigned bytes
+                if (best == SIZE_MAX || (want_min ? c < 0 : c > 0)) best = i;
+                continue;
+            }
+            int64_t vi = 0;
+            double vf = 0;
+            const int32_t k = rs.order_kind == CPH_NUM_INT64 ? Atoi(v, &vi) : ParseFloat(v, &vf);
+            if (k != CPH_NUM_OK) {
+                const char* what = k == CPH_NUM_ERR_SYNTAX ? "invalid syntax" : k == CPH_NUM_ERR_RANGE ? "value out of range"
+                                                           : "not decided by this library (digit separators, hexadecimal floats)";
+                return {Row(), Error("column " + quote(rs.column) + ": cannot convert " + quote(v) + " to " +
+                                     (rs.order_kind == CPH_NUM_INT64 ? "integer" : "float") + ": " + what)};
+            }
+            if (rs.order_kind == CPH_NUM_INT64) {
+                if (best == SIZE_MAX || (want_min ? vi < bi : vi > bi)) best = i, bi = vi;
+            } else if (vf == vf) {   // a NaN never wins
+                if (best == SIZE_MAX || (want_min ? vf < bf : vf > bf)) best = i, bf = vf;
+            }
+        }
+        return {pack[best == SIZE_MAX ? 0 : best], Error()};   // nothing but NaNs: the first row
+    };
+}
+
+inline Error Index::ResolveDuplicates(const Resolver& rs) {
+    const bool ordered = rs.rule == CPH_RESOLVE_MIN || rs.rule == CPH_RESOLVE_MAX;
+    if (ordered && column_presence(rs.column) != kAll) return ResolveDuplicates(resolver_func(rs));
+    cph_ctx* ctx = Gpu::Default().ctx();
+    const cph_resolve_opts opts{rs.rule, rs.order_kind, 0 /* the reference's tail rule */, 0};
+    // The order column goes in the row order of the twin's BUILD TABLE: row perm[p] = the value of impl_rows[p].  A twin rebuilt
+    // over impl_rows has perm = identity and takes the staged side column; the twin IndexOn leaves behind was built over the
+    // unsorted source rows, so the values are put where its perm looks for them.
+    const cph_strcol* col = nullptr;
+    std::unique_ptr<detail::StagedColumns> scattered;
+    if (ordered) {
+        const uint32_t* perm = nullptr;
+        uint64_t pn = 0;
+        if (cph_index_perm(device().h, CPH_MEM_HOST, &perm, &pn) != CPH_OK || pn != impl_rows.size())
+            throw std::runtime_error(std::string("csvplus: ") + cph_last_error(ctx));
+        bool identity = true;
+        for (uint64_t p = 0; p < pn && identity; p++) identity = perm[p] == p;
+        if (identity) {
+            col = side_column(ctx, rs.column);
+        } else {
+            std::vector<std::vector<const std::string*>> vals(1);
+            vals[0].resize(impl_rows.size());
+            for (uint64_t p = 0; p < pn; p++) vals[0][perm[p]] = &impl_rows[(size_t)p].at(rs.column);
+            scattered = std::make_unique<detail::StagedColumns>(ctx, 1);
+            scattered->stage(vals, impl_rows.size());
+            col = scattered->cols();
+        }
+    }
+    cph_resolved* res = nullptr;
+    if (cph_index_resolve(ctx, device().h, &opts, col, CPH_MEM_HOST, nullptr, &res) != CPH_OK)
+        throw std::runtime_error(std::string("csvplus: ") + cph_last_error(ctx));
+    struct Release { cph_resolved* r; ~Release() { cph_resolved_release(r); } } rel{res};
+    if (res->nerrors) {
+        const std::string& v = impl_rows[(size_t)res->first_error_position].at(rs.column);   // sorted position = subscript of impl_rows
+        const char* what = res->first_error_kind == CPH_NUM_ERR_SYNTAX  ? "invalid syntax"
+                           : res->first_error_kind == CPH_NUM_ERR_RANGE ? "value out of range"
+                                                                        : "not decided by this library (digit separators, hexadecimal floats)";
+        return Error("column " + quote(rs.column) + ": cannot convert " + quote(v) + " to " +
+                     (rs.order_kind == CPH_NUM_INT64 ? "integer" : "float") + ": " + what);
+    }
+    if (res->ngroups == 0) return Error();                                          // :821-823
+    for (uint64_t i = 0; i < res->nrows; i++) {   // positions ascend: position[i] >= i, so a slot is read before it is overwritten
+        const size_t p = (size_t)res->positions[i];
+        if (p != (size_t)i) impl_rows[(size_t)i] = std::move(impl_rows[p]);
+    }
+    impl_rows.resize((size_t)res->nrows);                                           // :862-864
+    invalidate_device();
     return Error();
 }
 

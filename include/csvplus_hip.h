@@ -919,6 +919,52 @@ CPH_API void    cph_groups_release(cph_groups* g);
 CPH_API int32_t cph_index_select(cph_ctx* ctx, const cph_index* index, const uint64_t* positions, uint64_t n,
                                  cph_index** out);
 
+/*
+ * Index.ResolveDuplicates with a NAMED rule instead of a callback: the choice per group, the compaction of dedup
+ * (csvplus.go:810-867) and the new index, all on the device — nothing crosses to the host per group or per row.
+ *
+ * The choice for a group [lo, hi) (a maximal run of >= 2 equal keys, as cph_index_dup_groups reports them):
+ *   CPH_RESOLVE_FIRST  lo           CPH_RESOLVE_LAST  hi-1          CPH_RESOLVE_DROP  no row (the reference's empty row)
+ *   CPH_RESOLVE_MIN / CPH_RESOLVE_MAX   the position whose ORDER VALUE is smallest / largest; ties go to the lowest position
+ *     (the index order is stable, so "first" and "lowest position" mean: first in the input).
+ * The order value of sorted position p is row perm[p] of `order_col`, a column of the BUILD TABLE in its original row order
+ * (host or device, any cph_strcol layout, nrows >= the table's rows).  It is required for MIN / MAX and ignored — may be
+ * NULL — for the other rules.  order_kind says how it is compared:
+ *   CPH_NUM_INT64 / CPH_NUM_FLOAT64   converted exactly as cph_col_to_number converts it.  Floats: -0 equals +0 (a pair of them
+ *                                     is a tie); a NaN loses to every number under MIN and under MAX alike, and a group of
+ *                                     nothing but NaNs keeps lo.
+ *   CPH_ORDER_BYTES                   the index's own comparison (csvplus.go:794-806, strings.Compare): unsigned bytewise, a
+ *                                     proper prefix is smaller.
+ * Survivors: every row outside a group, and every group's chosen row — with the reference's TAIL RULE: when ngroups > 0,
+ * keep_last_row == 0 and the final sorted row n-1 is not inside a group, that row is dropped ([A,A,B] -> [A]; dedup copies
+ * rows[lower-1] only while lower < len(rows), :851-859).  ngroups == 0 changes nothing.
+ *
+ * A group row whose order value does not convert is DATA, as in cph_col_to_number: the call returns CPH_OK with nerrors > 0,
+ * nrows = 0, positions = NULL and *out_index = NULL; first_error_position is the lowest such sorted position,
+ * first_error_row = perm[that], first_error_kind its CPH_NUM_ERR_*.  Rows OUTSIDE groups are never looked at for errors: the
+ * reference's callback never sees them.
+ *
+ * *out_index (when out_index != NULL) = the compacted index, what cph_index_select builds over `positions`.
+ * CPH_ERR_INVALID (with a message): NULL ctx / index / opts / out, an unknown rule, order kind or out_mem, MIN / MAX
+ * without a column or with one shorter than the build table.  Indexes of 0 and 1 rows are legal.
+ */
+enum { CPH_RESOLVE_FIRST = 1, CPH_RESOLVE_LAST = 2, CPH_RESOLVE_DROP = 3, CPH_RESOLVE_MIN = 4, CPH_RESOLVE_MAX = 5 };
+enum { CPH_ORDER_BYTES = 3 };            /* beside CPH_NUM_INT64 = 1, CPH_NUM_FLOAT64 = 2 */
+typedef struct { int32_t rule, order_kind, keep_last_row, reserved_; } cph_resolve_opts;
+typedef struct {
+    uint64_t        nrows;               /* surviving rows */
+    const uint64_t* positions;           /* their sorted positions in the INPUT index, ascending, in `mem` */
+    int32_t         mem, reserved_;
+    uint64_t        ngroups, group_rows; /* runs of >= 2 equal keys, and the rows inside them */
+    uint64_t        nerrors;             /* rows INSIDE groups whose order value did not convert */
+    uint64_t        first_error_position, first_error_row;   /* lowest such sorted position, perm[that]; UINT64_MAX */
+    int32_t         first_error_kind, reserved2_;            /* CPH_NUM_ERR_* */
+    uint64_t        host_rows;           /* float order: values finished on the host */
+} cph_resolved;
+CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* index, const cph_resolve_opts* opts, const cph_strcol* order_col,
+                                  int32_t out_mem, cph_index** out_index /* may be NULL */, cph_resolved** out);
+CPH_API void    cph_resolved_release(cph_resolved* r);
+
 /* Index.WriteTo / LoadIndex (csvplus.go:655-705) for the device index: a flat
  * little-endian file with the key codec, sorted codes and perm.  NOT a gob
  * stream and without row payload: the row table stays with the caller (the
