@@ -179,6 +179,14 @@ class cph_numcol(C.Structure):
                 ("host_rows", C.c_uint64)]
 
 
+CPH_MAP_LITERAL, CPH_MAP_COLUMN, CPH_MAP_INT64 = 1, 2, 3
+CPH_MAP_MAX_PIECES = 16
+
+
+class cph_map_piece(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("arg", C.c_int32), ("value", cph_strval), ("ints", C.c_void_p)]
+
+
 class cph_groups(C.Structure):
     _fields_ = [("ngroups", C.c_uint64), ("lower", C.c_void_p), ("upper", C.c_void_p)]
 
@@ -308,6 +316,9 @@ PROTOTYPES = [
     ("cph_col_to_number", C.c_int32,
      [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.POINTER(cph_numcol))]),
     ("cph_numcol_release", None, [C.POINTER(cph_numcol)]),
+    ("cph_map_format", C.c_int32,
+     [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_int32, C.c_uint64, C.POINTER(cph_map_piece), C.c_int32, C.c_int32,
+      C.POINTER(C.POINTER(cph_colbuf))]),
     ("cph_csv_parse", C.c_int32,
      [_P, _P, C.c_uint64, C.c_int32, C.POINTER(cph_csv_options), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_csv_table))]),

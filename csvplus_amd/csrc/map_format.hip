@@ -1,0 +1,295 @@
+// map_format.hip — Map (csvplus.go:290-296) with a ROW TEMPLATE instead of a closure: one computed string column.
+//
+//   cph_map_format  value i of the new column = the template's pieces in order: literal bytes, the value of a column in
+//                   row i (read through that column's row ids, as the writers read a joined row), an int64 written as
+//                   strconv.FormatInt(v, 10).  Bytes are copied verbatim; nothing is escaped.
+//
+// The pipeline of the gather and of the two-pass CSV writer (materialize.hip): k_map_lens (bytes per row: offsets only, the
+// literals' total, digit counts by compares) -> exclusive scan, whose nrows + 1 entries ARE the result column's offsets ->
+// k_map_copy (a tile's rows assembled in the LDS stage 8 value bytes at a time, streamed out with 16-byte stores; a tile
+// beyond the stage writes its rows to global memory itself).  Two passes, no look-back and no waiting between workgroups.
+// The literals are packed into one small device block that every row reads 8 bytes at a time.
+#include <new>
+#include <string>
+
+#include "materialize_device.hpp"
+
+namespace cph {
+
+struct MapPiece {
+    int32_t kind;          // CPH_MAP_*
+    int32_t col;           // COLUMN: the column
+    uint32_t off, len;     // LITERAL: its bytes in MapPlan::lits
+    const int64_t* ints;   // INT64: one value per output row, on the device
+};
+struct MapPlan {
+    const uint8_t* lits;
+    int32_t npieces;
+    uint32_t col_mask;     // bit c: some piece reads column c
+    uint64_t fixed;        // bytes of the literals together
+    MapPiece p[CPH_MAP_MAX_PIECES];
+};
+
+__device__ __forceinline__ uint64_t int_magnitude(int64_t v) { return v < 0 ? 0ull - (uint64_t)v : (uint64_t)v; }
+
+// characters of strconv.FormatInt(v, 10): the digits of the unsigned magnitude (compares against 10^1 .. 10^19) + the sign
+__device__ __forceinline__ uint32_t int_chars(int64_t v) {
+    const uint64_t m = int_magnitude(v);
+    uint32_t d = 1;
+    uint64_t p = 10;
+#pragma unroll
+    for (int k = 1; k <= 19; k++) {
+        d += m >= p ? 1u : 0u;
+        p *= 10;   // 10^19 < 2^64; the product behind it is never compared
+    }
+    return d + (v < 0 ? 1u : 0u);
+}
+
+// the characters assembled in registers — at most 20, three 8-byte chunks — and put 8 at a time
+template <class Sink>
+__device__ __forceinline__ void put_int(Sink& s, int64_t v) {
+    uint64_t m = int_magnitude(v);
+    const uint32_t len = int_chars(v);
+    uint64_t c0 = v < 0 ? (uint64_t)'-' : 0, c1 = 0, c2 = 0;
+    uint32_t pos = len;
+    do {
+        const uint64_t q = m / 10;
+        const uint64_t ch = (uint64_t)'0' + (m - q * 10);
+        m = q;
+        pos--;
+        const uint64_t sh = ch << (8u * (pos & 7u));
+        if (pos < 8u) c0 |= sh;
+        else if (pos < 16u) c1 |= sh;
+        else c2 |= sh;
+    } while (m);
+    s.put8(c0, len < 8u ? len : 8u);
+    if (len > 8u) s.put8(c1, len < 16u ? len - 8u : 8u);
+    if (len > 16u) s.put8(c2, len - 16u);
+}
+
+// (begin, length, first chunk) of column c's value in the loaded record; c is uniform, the arrays stay in registers
+template <int NC>
+__device__ __forceinline__ void pick_field(const RecordFields<NC>& f, int c, uint64_t* b, uint64_t* l, uint64_t* c0) {
+    *b = 0, *l = 0, *c0 = 0;
+#pragma unroll
+    for (int k = 0; k < NC; k++)
+        if (k == c) *b = f.b[k], *l = f.l[k], *c0 = f.c0[k];
+}
+
+// lens[i] = bytes of value i
+template <int NC>
+__global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, uint64_t* __restrict__ lens) {
+    const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kMatThreads + threadIdx.x; i < n; i += stride) {
+        uint64_t total = plan.fixed;
+        RecordFields<NC> f;
+        if constexpr (NC > 0) f.load(cols, ids, i, 0);   // offsets only
+        for (int k = 0; k < plan.npieces; k++) {
+            const MapPiece& p = plan.p[k];
+            if (p.kind == CPH_MAP_INT64) {
+                total += int_chars(p.ints[i]);
+            } else if (p.kind == CPH_MAP_COLUMN) {
+                uint64_t b, l, c0;
+                if constexpr (NC > 0) pick_field(f, p.col, &b, &l, &c0);
+                else value_span(cols.c[p.col], source_row(ids.ids[p.col], i), &b, &l);
+                total += l;
+            }
+        }
+        lens[i] = total;
+    }
+}
+
+template <int NC, class Sink>
+__device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, const ColIds& ids, const MapPlan& plan, const RecordFields<NC>& f,
+                                               uint64_t i) {
+    for (int k = 0; k < plan.npieces; k++) {
+        const MapPiece& p = plan.p[k];
+        if (p.kind == CPH_MAP_LITERAL) {
+            for (uint32_t q = 0; q < p.len; q += 8)
+                s.put8(load_value_chunk(plan.lits, p.off, p.len, (int)(q >> 3)), p.len - q < 8u ? p.len - q : 8u);
+        } else if (p.kind == CPH_MAP_INT64) {
+            put_int(s, p.ints[i]);
+        } else {
+            const uint8_t* data = cols.c[p.col].data;
+            uint64_t b, l, c0;
+            if constexpr (NC > 0) {
+                pick_field(f, p.col, &b, &l, &c0);
+            } else {
+                value_span(cols.c[p.col], source_row(ids.ids[p.col], i), &b, &l);
+                c0 = l ? load_value_chunk(data, b, l, 0) : 0;
+            }
+            for (uint64_t q = 0; q < l; q += 8) {
+                const uint64_t chunk = q ? load_value_chunk(data, b, l, (int)(q >> 3)) : c0;
+                s.put8(chunk, (uint32_t)(l - q < 8 ? l - q : 8));
+            }
+        }
+    }
+}
+
+// value i at out + offs[i]
+template <int NC>
+__global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, const uint64_t* __restrict__ offs,
+                                                         uint8_t* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    CPH_LDS uint8_t* stage = (CPH_LDS uint8_t*)smem;
+    for (uint64_t t0 = (uint64_t)blockIdx.x * kMatThreads; t0 < n; t0 += (uint64_t)gridDim.x * kMatThreads) {
+        const uint64_t tend = t0 + kMatThreads < n ? t0 + kMatThreads : n;
+        const uint64_t obase = offs[t0];
+        const uint64_t span = offs[tend] - obase;
+        const bool staged = span + 48 <= (uint64_t)kMatStage;   // uniform
+        if (staged) {   // the words are OR-ed in: the stage starts out zero
+            stage_clear(stage, span);
+            __syncthreads();
+        }
+        const uint64_t i = t0 + threadIdx.x;
+        // threads past the tile's end load its last record (never written): the loads of a record stay unbranched
+        RecordFields<NC> f;
+        if constexpr (NC > 0) f.load(cols, ids, i < tend ? i : tend - 1, plan.col_mask);
+        if (i < tend) {
+            if (staged) {
+                WordSink s(reinterpret_cast<uint32_t*>(smem), (uint32_t)((offs[i] - obase) + (obase & 15)));
+                map_put_record<NC>(s, cols, ids, plan, f, i);
+                s.finish();
+            } else {
+                GlobalSink s{out + offs[i]};
+                map_put_record<NC>(s, cols, ids, plan, f, i);
+            }
+        }
+        if (staged) {
+            lds_atomics_barrier();
+            flush_stage(stage, out, obase, span);
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace cph
+
+using namespace cph;
+
+extern "C" {
+
+CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
+                               const cph_map_piece* pieces, int32_t npieces, int32_t out_mem, cph_colbuf** out) {
+    if (!ctx) return CPH_ERR_INVALID;
+    if (!out) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: out must not be NULL"});
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_with(ctx, {CPH_ERR_HIP, "hipSetDevice failed"});
+    *out = nullptr;
+    if (!pieces) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: pieces must not be NULL"});
+    if (npieces < 1 || npieces > CPH_MAP_MAX_PIECES) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: 1..16 pieces"});
+    if (ncols < 0 || ncols > CPH_MAX_KEY_COLS) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: 0..16 columns"});
+    if (ncols && !cols) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: cols must not be NULL"});
+    if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
+    const uint64_t n = nrows;
+    uint64_t lit_bytes = 0;
+    for (int k = 0; k < npieces; k++) {
+        const cph_map_piece& p = pieces[k];
+        switch (p.kind) {
+            case CPH_MAP_LITERAL:
+                if (!p.value.data && p.value.len) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: a literal with bytes but no data pointer"});
+                lit_bytes += p.value.len;
+                if (p.value.len > 0xFFFFFFFFull || lit_bytes > 0xFFFFFFFFull) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: literals beyond 4 GiB"});
+                break;
+            case CPH_MAP_COLUMN:
+                if (p.arg < 0 || p.arg >= ncols) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: a COLUMN piece outside 0..ncols-1"});
+                break;
+            case CPH_MAP_INT64:
+                if (p.arg != CPH_MEM_HOST && p.arg != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: bad memory space of an INT64 piece"});
+                if (!p.ints && n) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: an INT64 piece without values"});
+                break;
+            default:
+                return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: unknown piece kind (1..3)"});
+        }
+    }
+    {
+        Status s = check_row_sources(cols, sel, ncols, 0, n, true);
+        if (!s.ok()) return fail_with(ctx, s);
+    }
+    auto* r = new (std::nothrow) cph_colbuf_impl();
+    if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
+    r->own.ctx = ctx;
+    auto run = [&]() -> Status {
+        std::vector<DevBuf> staged;
+        ColsArg arg{};
+        ColIds ids{};
+        CPH_TRY(stage_row_sources(ctx, cols, sel, nullptr, ncols, 0, n, &staged, &arg, &ids));
+        CPH_TRY(r->d_offs.alloc(&ctx->pool, (n + 1) * sizeof(uint64_t)));
+        uint64_t* offs = r->d_offs.as<uint64_t>();
+        uint64_t total = 0;
+        if (n) {
+            MapPlan plan{};
+            plan.npieces = npieces;
+            std::string lits;
+            double in_bytes = 0;   // what the copy pass reads per row besides the value bytes
+            for (int k = 0; k < npieces; k++) {
+                const cph_map_piece& p = pieces[k];
+                MapPiece& d = plan.p[k];
+                d.kind = p.kind;
+                if (p.kind == CPH_MAP_LITERAL) {
+                    d.off = (uint32_t)lits.size();
+                    d.len = (uint32_t)p.value.len;
+                    if (d.len) lits.append(reinterpret_cast<const char*>(p.value.data), d.len);
+                } else if (p.kind == CPH_MAP_COLUMN) {
+                    d.col = p.arg;
+                    if (!((plan.col_mask >> p.arg) & 1u)) {
+                        in_bytes += arg.c[p.arg].fixed_width ? 0.0 : (double)(arg.c[p.arg].offset_bits / 8);
+                        if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
+                    }
+                    plan.col_mask |= 1u << p.arg;
+                } else {
+                    d.ints = p.ints;
+                    in_bytes += 8.0;
+                    if (p.arg == CPH_MEM_HOST) {   // staged like the row ids of a host column
+                        staged.emplace_back();
+                        CPH_TRY(staged.back().alloc(&ctx->pool, n * sizeof(int64_t)));
+                        CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), p.ints, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+                        d.ints = staged.back().as<int64_t>();
+                    }
+                }
+            }
+            plan.fixed = lits.size();
+            DevBuf litbuf;
+            CPH_TRY(litbuf.alloc(&ctx->pool, lits.size() + 16));
+            if (!lits.empty()) {
+                void* slot = nullptr;
+                CPH_TRY(pinned_upload(ctx, lits.size(), &slot));
+                memcpy(slot, lits.data(), lits.size());
+                CPH_HIP_TRY(hipMemcpyAsync(litbuf.get(), slot, lits.size(), hipMemcpyHostToDevice, ctx->stream));
+            }
+            plan.lits = litbuf.as<uint8_t>();
+            {
+                ProfScope ps(ctx, "k_map_lens", 0);
+                CPH_CSV_DISPATCH(k_map_lens, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, offs);
+            }
+            CPH_HIP_TRY(hipGetLastError());
+            CPH_TRY(scan_lengths(ctx, offs, n, &total));
+            CPH_TRY(r->d_data.alloc(&ctx->pool, total + 16));
+            if (total) {
+                ProfScope ps(ctx, "k_map_copy", 2.0 * (double)total + (8.0 + in_bytes) * (double)n);
+                CPH_CSV_DISPATCH(k_map_copy, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, offs, r->d_data.as<uint8_t>());
+                CPH_HIP_TRY(hipGetLastError());
+            }
+            // the kernels read the literal block and the staged arrays: they go back to the pool behind deliver's wait
+            r->pub.nbytes = total;
+            r->pub.col.nrows = n;
+            r->pub.col.offset_bits = 64;
+            r->pub.col.mem = out_mem;
+            r->pub.col.fixed_width = 0;
+            const ResultPart parts[2] = {{&r->d_offs, (size_t)(n + 1) * sizeof(uint64_t), &r->pub.col.offsets},
+                                         {&r->d_data, (size_t)total, &r->pub.col.data}};
+            return deliver(ctx, &r->own, parts, 2, out_mem);
+        }
+        CPH_HIP_TRY(hipMemsetAsync(offs, 0, sizeof(uint64_t), ctx->stream));
+        CPH_TRY(r->d_data.alloc(&ctx->pool, 16));
+        r->pub.nbytes = 0;
+        r->pub.col.nrows = 0;
+        r->pub.col.offset_bits = 64;
+        r->pub.col.mem = out_mem;
+        r->pub.col.fixed_width = 0;
+        const ResultPart parts[2] = {{&r->d_offs, sizeof(uint64_t), &r->pub.col.offsets}, {&r->d_data, 0, &r->pub.col.data}};
+        return deliver(ctx, &r->own, parts, 2, out_mem);
+    };
+    return finish_call(ctx, r, run(), out);
+}
+
+}  // extern "C"

@@ -888,12 +888,6 @@ static Status csv_onepass(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, i
 
 using namespace cph;
 
-struct cph_colbuf_impl {
-    cph_colbuf pub;   // first
-    ResultOwner own;
-    DevBuf d_data, d_offs;
-};
-
 extern "C" {
 
 CPH_API int32_t cph_gather_rows(cph_ctx* ctx, const cph_strcol* col, const void* row_ids, int32_t id_bits, uint64_t id_base,

@@ -1,5 +1,5 @@
 // materialize_device.hpp — the device pieces the writers share (materialize.hip: gather and ToCsv; json_write.hip: ToJSON;
-// filter.hip: Filter): the row-id lookup, the byte sinks, the LDS stage, the record loader, the column-count dispatch and the
+// filter.hip: Filter; map_format.hip: Map): the row-id lookup, the byte sinks, the LDS stage, the record loader, the column-count dispatch and the
 // length scan.  Their host side is shared too and lives in cph_internal.hpp / capi.hip: RowIds / ColIds, check_row_sources and
 // stage_row_sources (columns + row ids onto the device), deliver / finish_call / release_result (the result handed out).
 #pragma once
@@ -146,6 +146,13 @@ static Status scan_lengths(cph_ctx* ctx, uint64_t* lens, uint64_t n, uint64_t* t
 }
 
 }  // namespace cph
+
+// the library-owned string column behind cph_colbuf (cph_colbuf_release frees whichever call made it: the gather, Map)
+struct cph_colbuf_impl {
+    cph_colbuf pub;   // first
+    cph::ResultOwner own;
+    cph::DevBuf d_data, d_offs;
+};
 
 // the library-owned byte buffer behind cph_bytes (cph_bytes_release frees whichever writer made it)
 struct cph_bytes_impl {

@@ -14,6 +14,10 @@
 //   DataSource.Filter / TakeWhile / DropWhile / Top / Drop :276-374  DataSource::Filter / TakeWhile / DropWhile (over a
 //                                                declarative csvplus::Pred, evaluated on the GPU) / Top / Drop
 //   Like / All / Any / Not           :1243-1293  csvplus::Like / All / Any / Not (plain data, also callable on a Row)
+//   DataSource.Map                     :290-296  DataSource::Map over csvplus::Set(name, literal or Format{...}): a row
+//                                                template instead of a closure, rendered on the GPU (cph_map_format)
+//   DataSource.Validate                :300-310  DataSource::Validate(pred, message): a declarative Pred instead of a closure
+//   DataSource.Transform               :262-272  no entry of its own: it is the composition of Map, Filter and Validate
 //   Row.ValueAsInt / ValueAsFloat64  :165-205    csvplus::ValueAsInt / ValueAsFloat64 (one row, on the host);
 //                                                DataSource::ColumnAsInt / ColumnAsFloat64 (a whole column, on the GPU);
 //                                                csvplus::IntCmp / FloatCmp: `v, err := row.ValueAsInt(c); err == nil && v REL k`
@@ -324,6 +328,56 @@ template <class... P>
 inline Pred All(const Pred& first, const P&... more) { return All(std::vector<Pred>{first, more...}); }
 template <class... P>
 inline Pred Any(const Pred& first, const P&... more) { return Any(std::vector<Pred>{first, more...}); }
+
+// ---- Map (:290-296) as DATA ----------------------------------------------------------------------------------------------
+// `row["name"] = "Julia"` is Set("name", "Julia"); `row["full"] = row["name"] + " " + row["surname"]` is
+// Set("full", Format({Col("name"), " ", Col("surname")})).  A row that lacks a Col's column takes the Col's default
+// (Row.SafeGetValue, :69-75); without a default the iteration ends with the reference's `missing column` error at that row.
+struct Col {
+    std::string name, fallback;
+    bool has_default = false;
+    explicit Col(std::string n) : name(std::move(n)) {}
+    Col(std::string n, std::string dflt) : name(std::move(n)), fallback(std::move(dflt)), has_default(true) {}
+};
+struct Part {   // a literal or a column
+    bool is_col = false;
+    std::string text;   // the literal's bytes
+    Col col{""};
+    Part(const char* lit) : text(lit) {}                 // NOLINT: implicit, so that a template reads like the expression
+    Part(std::string lit) : text(std::move(lit)) {}      // NOLINT
+    Part(Col c) : is_col(true), col(std::move(c)) {}     // NOLINT
+};
+struct Format {
+    std::vector<Part> parts;
+    explicit Format(std::vector<Part> p) : parts(std::move(p)) {
+        if (parts.empty()) throw Panic("empty template in Format()");
+    }
+    // the template on one row, on the host (what the device computes for a whole batch); *missing gets the first absent column
+    bool render(const Row& row, std::string* out, std::string* missing) const {
+        out->clear();
+        for (const Part& p : parts) {
+            if (!p.is_col) {
+                *out += p.text;
+                continue;
+            }
+            auto it = row.find(p.col.name);
+            if (it != row.end()) *out += it->second;
+            else if (p.col.has_default) *out += p.col.fallback;
+            else {
+                *missing = p.col.name;
+                return false;
+            }
+        }
+        return true;
+    }
+};
+struct Assign {
+    std::string name;
+    Format value;
+};
+inline Assign Set(std::string name, std::string literal) { return Assign{std::move(name), Format({Part(std::move(literal))})}; }
+inline Assign Set(std::string name, const char* literal) { return Set(std::move(name), std::string(literal)); }
+inline Assign Set(std::string name, Format value) { return Assign{std::move(name), std::move(value)}; }
 
 using RowFunc = std::function<Error(Row)>;
 
@@ -682,6 +736,57 @@ public:
     DataSource Filter(const Pred& pred) const { return filterSource(fn_, detail::compilePred(pred), CPH_FILTER_WHERE); }
     DataSource TakeWhile(const Pred& pred) const { return filterSource(fn_, detail::compilePred(pred), CPH_FILTER_TAKE_WHILE); }
     DataSource DropWhile(const Pred& pred) const { return filterSource(fn_, detail::compilePred(pred), CPH_FILTER_DROP_WHILE); }
+    // Map (:290-296) with row templates: per batch of rows (Gpu::join_batch_rows) and assignment, the template's columns are
+    // staged and ONE cph_map_format call renders the new column; the assignments are applied in order (a later one reads what
+    // an earlier one wrote).  A row that lacks a column of a Col without default ends the iteration with `missing column`
+    // — after the rows in front of it went through, as in Join.
+    DataSource Map(const Assign& a) const { return Map(std::vector<Assign>{a}); }
+    DataSource Map(std::vector<Assign> assigns) const {
+        if (assigns.empty()) throw Panic("no assignments specified in Map()");
+        std::vector<std::string> required, written;
+        for (const Assign& a : assigns) {
+            std::set<std::string> cols;
+            for (const Part& p : a.value.parts) {
+                if (!p.is_col) continue;
+                cols.insert(p.col.name);
+                const bool known = std::find(written.begin(), written.end(), p.col.name) != written.end() ||
+                                   std::find(required.begin(), required.end(), p.col.name) != required.end();
+                if (!p.col.has_default && !known) required.push_back(p.col.name);
+            }
+            if (a.value.parts.size() > (size_t)CPH_MAP_MAX_PIECES) throw Panic("template of more than 16 parts in Map()");
+            if (cols.size() > (size_t)CPH_MAX_KEY_COLS) throw Panic("template over more than 16 columns in Map()");
+            written.push_back(a.name);
+        }
+        Fn src = fn_;
+        auto shared = std::make_shared<const std::vector<Assign>>(std::move(assigns));
+        return DataSource([src, shared, required](const RowFunc& fn) -> Error {
+            cph_ctx* ctx = Gpu::Default().ctx();
+            return batched(src, required, [&](std::vector<Row>* batch) -> Error {
+                for (const Assign& a : *shared) {
+                    Error e = mapBatch(ctx, a, batch);
+                    if (e) {
+                        batch->clear();
+                        return e;
+                    }
+                }
+                Error err;
+                for (size_t i = 0; i < batch->size() && !err; i++) err = fn(std::move((*batch)[i]));
+                batch->clear();
+                return err;
+            });
+        });
+    }
+    // Validate (:300-310) over a declarative predicate: the rows in front of the first row where `pred` fails are delivered,
+    // then the iteration ends with Error(message).  A batch is evaluated by ONE cph_filter_rows call in TAKE_WHILE mode, so the
+    // error surfaces when the failing row's batch is evaluated: like an error from a Join's batch it is wrapped by the source
+    // with the row it had reached (the failing row itself when Gpu::join_batch_rows is 1; a failure in the last, partial
+    // batch surfaces after the source has ended and comes back as it is).
+    DataSource Validate(const Pred& pred, std::string message) const {
+        return filterSource(fn_, detail::compilePred(pred), CPH_FILTER_TAKE_WHILE, std::make_shared<const std::string>(std::move(message)));
+    }
+    // cph_map_format calls made so far (tests: one per batch and assignment)
+    static uint64_t map_calls() { return map_calls_counter(); }
+
     // Top (:313-325) / Drop (:329-342): counters, no data involved
     DataSource Top(uint64_t n) const {
         Fn src = fn_;
@@ -912,8 +1017,59 @@ private:
         return n;
     }
 
-    static DataSource filterSource(Fn src, std::shared_ptr<const detail::PredProgram> prog, int32_t mode) {
-        return DataSource([src, prog, mode](const RowFunc& fn) -> Error {
+    // One assignment over a batch: row[a.name] = the template's value, for every row, by one cph_map_format call.  A row that
+    // lacks a column gets the Col's default in its place (the caller has turned away rows that lack a column without one).
+    static Error mapBatch(cph_ctx* ctx, const Assign& a, std::vector<Row>* batch) {
+        const size_t n = batch->size();
+        if (n == 0) return Error();
+        std::vector<std::string> columns;
+        std::vector<const std::string*> fallback;
+        std::vector<cph_map_piece> pieces;
+        for (const Part& p : a.value.parts) {
+            if (!p.is_col) {
+                pieces.push_back(cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr});
+                continue;
+            }
+            size_t c = (size_t)(std::find(columns.begin(), columns.end(), p.col.name) - columns.begin());
+            if (c == columns.size()) {
+                columns.push_back(p.col.name);
+                fallback.push_back(&p.col.fallback);
+            }
+            pieces.push_back(cph_map_piece{CPH_MAP_COLUMN, (int32_t)c, {nullptr, 0}, nullptr});
+        }
+        const size_t nc = columns.size();
+        std::vector<std::vector<const std::string*>> vals(nc);
+        for (size_t c = 0; c < nc; c++) {
+            vals[c].resize(n);
+            for (size_t i = 0; i < n; i++) {
+                auto it = (*batch)[i].find(columns[c]);
+                vals[c][i] = it == (*batch)[i].end() ? fallback[c] : &it->second;
+            }
+        }
+        cph_colbuf* cb = nullptr;
+        int32_t rc;
+        {
+            detail::StagedColumns st(ctx, nc);
+            st.stage(vals, n);
+            rc = cph_map_format(ctx, nc ? st.cols() : nullptr, nullptr, (int32_t)nc, n, pieces.data(), (int32_t)pieces.size(), CPH_MEM_HOST, &cb);
+        }
+        if (rc != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+        map_calls_counter()++;
+        const uint64_t* offs = static_cast<const uint64_t*>(cb->col.offsets);
+        const char* data = reinterpret_cast<const char*>(cb->col.data);
+        for (size_t i = 0; i < n; i++) (*batch)[i][a.name].assign(data + offs[i], (size_t)(offs[i + 1] - offs[i]));
+        cph_colbuf_release(cb);
+        return Error();
+    }
+    static uint64_t& map_calls_counter() {
+        static uint64_t n = 0;
+        return n;
+    }
+
+    // invalid != null: Validate — a failing row ends the iteration with that message instead of ending it cleanly
+    static DataSource filterSource(Fn src, std::shared_ptr<const detail::PredProgram> prog, int32_t mode,
+                                   std::shared_ptr<const std::string> invalid = nullptr) {
+        return DataSource([src, prog, mode, invalid](const RowFunc& fn) -> Error {
             cph_ctx* ctx = Gpu::Default().ctx();
             const size_t batch_rows = std::max<size_t>(1, Gpu::Default().join_batch_rows);
             std::vector<Row> batch;
@@ -924,7 +1080,8 @@ private:
                 uint64_t first = 0, count = 0;
                 Error e = filterBatch(ctx, *prog, mode, &batch, fn, &first, &count);
                 if (e) return e;
-                if (mode == CPH_FILTER_TAKE_WHILE && count < n) return io_EOF;   // the predicate failed: the iteration stops (:350-352)
+                if (mode == CPH_FILTER_TAKE_WHILE && count < n)   // the predicate failed: the iteration stops (:350-352; Validate: :303)
+                    return invalid ? Error(*invalid) : io_EOF;
                 if (mode == CPH_FILTER_DROP_WHILE && count) yield = true;
                 return Error();
             };

@@ -1,7 +1,8 @@
 """The step after the path: gathering columns through the joined row ids and writing the
 canonical CSV or JSON (cph_gather_rows / cph_csv_write / cph_json_write_rows; mergeRows csvplus.go:571-583,
-ToCsv :379-406, ToJSON :446-480), filtering rows (cph_filter_rows) and converting a column to numbers
-(cph_col_to_number; ValueAsInt / ValueAsFloat64 :165-205)."""
+ToCsv :379-406, ToJSON :446-480), filtering rows (cph_filter_rows), converting a column to numbers
+(cph_col_to_number; ValueAsInt / ValueAsFloat64 :165-205) and computing a column from a row template (cph_map_format;
+Map :290-296, Validate :300-310)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -403,3 +404,80 @@ def to_float(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, out_mem: int
     """Row.ValueAsFloat64 (csvplus.go:187-205): strconv.ParseFloat(s, 64), correctly rounded.  `host_rows` of the result
     counts the rows the device deferred to the library's host side (19+ significant digits, extreme exponents)."""
     return _to_number(ctx, col, row_ids, nrows, N.CPH_NUM_FLOAT64, out_mem)
+
+
+# ---- Map with a row template / Validate (cph_map_format; cph_filter_rows in TAKE_WHILE mode) ------------------------------
+
+def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None, out_mem: int = N.CPH_MEM_HOST):
+    """Map(row[new] = template(row)) for every row, on the device (cph_map_format): returns the NEW column as a ColBuf
+    (valid until release(); to_strcol() for a host result, as_device_strcol() for a device one).
+
+    cols_by_name: {column name: StrCol} — the row the template sees; a Col whose name the mapping lacks becomes its default
+    or raises mapping.MissingColumn.  template: mapping.Format / Const (or a bare part).  row_ids: {name: ids} as in
+    filter_rows, for columns read through row ids (a Join's); nrows: the number of rows (default: what the columns, the row
+    ids or the Int parts give).  An Int part's array is indexed by OUTPUT row and lives on the host (numpy) or on the device
+    (Int.on_device)."""
+    from . import mapping as M
+
+    names, pieces = M.compile(template, list(cols_by_name))
+    cols = [cols_by_name[nm] for nm in names]
+    ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
+    keep = []
+    if cols:
+        arr, sel, n = _rowsel(cols, ids, nrows, keep)
+    else:
+        arr, sel = None, None
+        counts = [p[2].count for p in pieces if p[0] == M.INT64]
+        if nrows is not None:
+            n = int(nrows)
+        elif counts:
+            n = min(counts)
+        elif cols_by_name:
+            n = min(c.nrows for c in cols_by_name.values())
+        else:
+            raise ValueError("map_column: a template without columns and Int parts needs nrows")
+    parr = (N.cph_map_piece * len(pieces))()
+    for k, (kind, arg, value) in enumerate(pieces):
+        parr[k].kind = kind
+        if kind == M.LITERAL:
+            b = np.frombuffer(value, dtype=np.uint8)
+            keep.append(b)
+            parr[k].value.data = b.ctypes.data if len(b) else None
+            parr[k].value.len = len(b)
+        elif kind == M.COLUMN:
+            parr[k].arg = arg
+        else:
+            if value.count < n:
+                raise ValueError(f"map_column: an Int part has {value.count} values for {n} rows")
+            if value.device:
+                parr[k].arg, parr[k].ints = N.CPH_MEM_DEVICE, value.values or None
+            else:
+                keep.append(value.values)
+                parr[k].arg, parr[k].ints = N.CPH_MEM_HOST, value.values.ctypes.data if value.count else None
+    out = C.POINTER(N.cph_colbuf)()
+    ctx._check(ctx.lib.cph_map_format(ctx.handle, arr, sel, len(cols), n, parr, len(pieces), out_mem, C.byref(out)))
+    del keep
+    return ColBuf(ctx, out)
+
+
+def validate_rows(ctx: N.Context, cols_by_name, pred, row_ids=None, nrows=None, first_row: int = 0):
+    """Validate (csvplus.go:300-310) with a declarative predicate: the number of the first row (a position in the selection,
+    first_row included) where `pred` FAILS — where the reference's iteration would stop with the validator's error — or None
+    when every row of [first_row, first_row + nrows) passes.  cph_filter_rows in TAKE_WHILE mode: the rows in front of the
+    first failing one come back as a range, nothing is materialised.  Arguments as in filter_rows."""
+    if nrows is None:   # the rows filter_rows would look at
+        from . import predicates as P
+        names = P.compile(pred, list(cols_by_name))[0]
+        if names:
+            ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
+            total = _rowsel([cols_by_name[nm] for nm in names], ids, None, [])[2]
+        else:
+            total = min((c.nrows for c in cols_by_name.values()), default=0)
+        nrows = max(total - first_row, 0)
+    rl = filter_rows(ctx, cols_by_name, pred, row_ids=row_ids, nrows=nrows, mode="take_while", first_row=first_row,
+                     out_bits=64, out_mem=N.CPH_MEM_HOST, as_handle=True)
+    try:
+        passed = len(rl)
+    finally:
+        rl.release()
+    return None if passed >= int(nrows) else first_row + passed

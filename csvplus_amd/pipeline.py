@@ -7,7 +7,8 @@ CSV bytes -> columns (cph_csv_parse) -> indices (cph_index_build) -> fused chain
 output columns (cph_gather_rows: mergeRows, csvplus.go:571-583, column by column) -> CSV bytes
 (cph_csv_write: ToCsv, :379-406; or JSON bytes, cph_json_write_rows: ToJSON, :446-480).  Nothing leaves HBM between
 the first and the last step — also not with a Filter(pred).Drop(skip).Top(limit) between the Join and the writer
-(`where`, `skip`, `limit`: cph_filter_rows over the joined rows, cph_rowsel_take on every column's row ids).
+(`where`, `skip`, `limit`: cph_filter_rows over the joined rows, cph_rowsel_take on every column's row ids) and not with
+computed columns behind that (`computed`: Map with row templates, cph_map_format over the joined rows).
 """
 from __future__ import annotations
 
@@ -45,7 +46,7 @@ def read_table(ctx: N.Context, text: bytes, select=None, **kw) -> Table:
 
 
 def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict | None = None, out_mem: int = N.CPH_MEM_HOST,
-                fused: bool = True, positions: bool | None = None, where=None, skip: int = 0, limit=None):
+                fused: bool = True, positions: bool | None = None, where=None, skip: int = 0, limit=None, computed=None):
     """steps: [(index_table, index_key_column, stream_key_column), ...] — each index must be unique on its key
     (UniqueIndexOn; a duplicate raises like the reference's error :751).  out_columns: [(output name, table,
     column)] where table is `stream` or one of the index tables; the caller resolves name collisions the way
@@ -60,13 +61,18 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
     where / skip / limit: Join(...).Filter(where).Drop(skip).Top(limit) in front of the writer — `where` is a predicate of
     csvplus_amd.predicates (Like, All, Any, Not) over the JOINED row: a name is looked up in the stream first, then in
     steps[0]'s table, steps[1]'s, ... (mergeRows: the stream's value wins); a name none of them has makes its Like false.
+    computed: {name: template} — ...Map(row[name] = template(row)) behind the filter, one template of csvplus_amd.mapping
+    (Format, Const) per new column, applied in dict order over the joined rows that are left: a Col is looked up among the
+    columns computed so far, then in the joined row as `where` does.  An out_columns entry whose output name is a computed
+    name takes the computed column (its table and column are ignored and may be None): `row[name] = ...` replaces a source
+    column of that name.  None (default): nothing is computed.
     Returns the CSV text (header + joined rows, stream order): bytes, or a DeviceBytes handle for out_mem DEVICE."""
     def lap(name, t0):
         if timings is not None:
             ctx.synchronize()
             timings[name] = timings.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
 
-    with _joined(ctx, stream, steps, out_columns, lap, positions, where, skip, limit) as (cols, ids, n, bufs):
+    with _joined(ctx, stream, steps, out_columns, lap, positions, where, skip, limit, computed) as (cols, ids, n, bufs):
         t0 = time.perf_counter()
         from .materialize import csv_write
         if fused:
@@ -89,26 +95,66 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
         return text
 
 
+def _compute_columns(ctx: N.Context, computed, source, n, bufs):
+    """Map with row templates: computed = {name: template}, applied in dict order over n rows.  source(name) -> (column,
+    row ids) of a source column, or None when the rows have no such column; a name computed earlier is read from its
+    result.  Returns {name: device column} (identity columns of n rows); their ColBufs are appended to `bufs`."""
+    from . import mapping as M
+    from .materialize import map_column
+
+    done = {}
+    for cname, tmpl in computed.items():
+        by_name, rid = {}, {}
+        for name in M.columns(tmpl):
+            if name in done:
+                by_name[name] = done[name]
+                continue
+            s = source(name)
+            if s is not None:
+                by_name[name], rid[name] = s
+        cb = map_column(ctx, by_name, tmpl, row_ids=rid, nrows=n, out_mem=N.CPH_MEM_DEVICE)
+        bufs.append(cb)
+        done[str(cname)] = cb.as_device_strcol()
+    return done
+
+
 @contextlib.contextmanager
-def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions, where=None, skip=0, limit=None):
+def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions, where=None, skip=0, limit=None, computed=None):
     """Index, chain and output columns of a Join(...) over `steps`: yields (cols, ids, n, bufs) — per output column the column
     to read and its row ids for the writers (csv_write / json_write row_ids), the joined row count, and a list whose
     ColBufs are released on exit (with the indexes and the chain).  where / skip / limit: see join_to_csv; the rows the
-    filter keeps replace the joined rows (every column's row ids narrowed on the device)."""
+    filter keeps replace the joined rows (every column's row ids narrowed on the device).  computed: see join_to_csv; the
+    templates run over the rows that are left and their results stand in for the output columns of their names."""
     filtered = where is not None or skip or limit is not None
     pred_columns = []   # (name, table, name) of the columns the predicate reads, resolved like mergeRows does
+    tmpl_columns = []   # the same for the source columns the templates read
+    merged = {}
+    if filtered or computed:
+        for tab in [stream] + [t for t, _, _ in steps]:
+            for name in tab.cols:
+                merged.setdefault(name, tab)
     if filtered:
         from . import predicates as P
         if where is None:
             where = P.All()   # Drop / Top alone: every row holds
-        merged = {}
-        for tab in [stream] + [t for t, _, _ in steps]:
-            for name in tab.cols:
-                merged.setdefault(name, tab)
         pred_columns = [(name, merged[name], name) for name in P.compile(where, list(merged))[0]]
+    if computed:
+        from . import mapping as M
+        computed = {str(k): v for k, v in computed.items()}
+        earlier = set()
+        for cname, tmpl in computed.items():
+            for name in M.columns(tmpl):
+                if name not in earlier and name in merged and all(name != t[0] for t in tmpl_columns):
+                    tmpl_columns.append((name, merged[name], name))
+            earlier.add(cname)
+        all_out = list(out_columns)
+        out_columns = [oc for oc in all_out if oc[0] not in computed] + tmpl_columns
+    for name, tab, _ in out_columns:
+        if tab is None:
+            raise ValueError(f"output column {name!r} names no table and no template computes it")
     if positions is None:
         payload = {}
-        for _, tab, col in list(out_columns) + pred_columns:
+        for _, tab, col in list(out_columns) + pred_columns:   # (out_columns holds the templates' columns too)
             if tab is not stream:
                 payload[(id(tab), col)] = tab.nrows
         positions = 1.0e-8 * stream.nrows > 3.0e-8 * sum(payload.values())
@@ -172,6 +218,15 @@ def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions, w
             lap("filter_ms", t0)
         if n == 0:
             cols, ids = [c.head(0) for c in cols], [None] * len(cols)
+        if computed:
+            t0 = time.perf_counter()
+            first = len(cols) - len(tmpl_columns)
+            src = {t[0]: (c, i) for t, c, i in zip(tmpl_columns, cols[first:], ids[first:])}
+            done = _compute_columns(ctx, computed, src.get, n, bufs)
+            real = iter(zip(cols[:first], ids[:first]))
+            pairs = [(done[oc[0]], None) if oc[0] in done else next(real) for oc in all_out]
+            cols, ids = [c for c, _ in pairs], [i for _, i in pairs]
+            lap("map_ms", t0)
         yield cols, ids, n, bufs
     finally:
         for cb in bufs:
@@ -183,12 +238,14 @@ def _joined(ctx: N.Context, stream: Table, steps, out_columns, lap, positions, w
 
 
 def join_to_json(ctx: N.Context, stream: Table, steps, out_columns=None, timings: dict | None = None, out_mem: int = N.CPH_MEM_HOST,
-                 positions: bool | None = None, where=None, skip: int = 0, limit=None):
+                 positions: bool | None = None, where=None, skip: int = 0, limit=None, computed=None):
     """Join(...).ToJSON() (csvplus.go:446-480) over the steps of join_to_csv, written by cph_json_write_rows with mergeRows
     folded into the writer.  out_columns: [(output name, table, column)] as in join_to_csv, the names all different; None
     (default): what the reference's joined rows hold — every column of the stream and of every index table, a name present
     in several of them taken from the first of stream, steps[0], steps[1], ... (nested mergeRows, :559-560, :571-583).
     where / skip / limit: Filter(where).Drop(skip).Top(limit) in front of the writer, as in join_to_csv.
+    computed: {name: template}, as in join_to_csv; with out_columns None every computed name is a key of the objects and
+    stands in for a source column of that name.
     Returns the JSON text: bytes, or a DeviceBytes handle for out_mem DEVICE."""
     if out_columns is None:
         out_columns, seen = [], set()
@@ -197,13 +254,14 @@ def join_to_json(ctx: N.Context, stream: Table, steps, out_columns=None, timings
                 if name not in seen:
                     seen.add(name)
                     out_columns.append((name, tab, name))
+        out_columns += [(str(name), None, None) for name in (computed or {}) if str(name) not in seen]
 
     def lap(name, t0):
         if timings is not None:
             ctx.synchronize()
             timings[name] = timings.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
 
-    with _joined(ctx, stream, steps, out_columns, lap, positions, where, skip, limit) as (cols, ids, n, _):
+    with _joined(ctx, stream, steps, out_columns, lap, positions, where, skip, limit, computed) as (cols, ids, n, _):
         t0 = time.perf_counter()
         from .materialize import json_write
         text = json_write(ctx, cols, [name for name, _, _ in out_columns], out_mem=out_mem, row_ids=ids, nrows=n)
@@ -212,15 +270,18 @@ def join_to_json(ctx: N.Context, stream: Table, steps, out_columns=None, timings
 
 
 def filter_to_csv(ctx: N.Context, table: Table, pred, out_columns, mode: str = "where", first_row: int = 0, nrows=None,
-                  skip: int = 0, limit=None, out_mem: int = N.CPH_MEM_HOST):
+                  skip: int = 0, limit=None, out_mem: int = N.CPH_MEM_HOST, computed=None):
     """The reference's headline shape, FromFile(...).Filter(Like(...)).ToCsv(...), on the device: the rows of ONE table
     where `pred` holds (mode "where"; "take_while" / "drop_while" for TakeWhile / DropWhile; first_row / nrows: Drop / Top
     in front of the filter, skip / limit: behind it), written as CSV.  out_columns: column names, or (output name, column)
-    pairs.  Returns the CSV text: bytes, or a DeviceBytes handle for out_mem DEVICE."""
+    pairs.  computed: {name: template} — .Map(row[name] = template(row)) behind the filter (csvplus_amd.mapping), in dict
+    order over the rows kept; an output column of a computed name takes the computed column.
+    Returns the CSV text: bytes, or a DeviceBytes handle for out_mem DEVICE."""
     from . import predicates as P
     from .materialize import csv_write, filter_rows
 
     pairs = [(c, c) if isinstance(c, str) else tuple(c) for c in out_columns]
+    bufs = []
     kept = filter_rows(ctx, table.cols, pred, nrows=nrows, mode=mode, first_row=first_row, skip=skip, limit=limit,
                        out_mem=N.CPH_MEM_DEVICE)
     try:
@@ -228,10 +289,19 @@ def filter_to_csv(ctx: N.Context, table: Table, pred, out_columns, mode: str = "
             rng = filter_rows(ctx, table.cols, P.All(), nrows=len(kept), first_row=kept.first, out_mem=N.CPH_MEM_DEVICE)
             kept.release()
             kept = rng
-        cols = [table[c] for _, c in pairs]
         header = [name for name, _ in pairs]
-        if kept.is_range:   # rows 0 .. len - 1 (or none)
-            return csv_write(ctx, [c.head(len(kept)) for c in cols], header, out_mem=out_mem)
-        return csv_write(ctx, cols, header, out_mem=out_mem, row_ids=[kept.as_row_ids()] * len(cols), nrows=len(kept))
+        rows = None if kept.is_range else kept.as_row_ids()   # a range: rows 0 .. len - 1 (or none)
+        view = (lambda c: c.head(len(kept))) if kept.is_range else (lambda c: c)
+        done = {}
+        if computed:
+            done = _compute_columns(ctx, {str(k): v for k, v in computed.items()},
+                                    lambda name: (view(table[name]), rows) if name in table.cols else None, len(kept), bufs)
+        cols = [done[name] if name in done else view(table[c]) for name, c in pairs]
+        if kept.is_range:
+            return csv_write(ctx, cols, header, out_mem=out_mem)
+        return csv_write(ctx, cols, header, out_mem=out_mem, row_ids=[None if name in done else rows for name, _ in pairs],
+                         nrows=len(kept))
     finally:
+        for cb in bufs:
+            cb.release()
         kept.release()

@@ -832,6 +832,49 @@ CPH_API int32_t cph_col_to_number(cph_ctx* ctx, const cph_strcol* col, const cph
                                   int32_t out_mem, cph_numcol** out);
 CPH_API void    cph_numcol_release(cph_numcol* col);
 
+/* ---- Map with a row template: a computed string column (csvplus.go:290-296) ---- */
+/*
+ * The reference's Map takes a closure (`row["name"] = "Julia"`, `row["full"] = row["name"] + " " + row["surname"]`, the
+ * README's Printf over a joined row); a closure cannot run on a GPU, a ROW TEMPLATE can: value i of the new column is the
+ * concatenation, in order, of the template's pieces —
+ *   CPH_MAP_LITERAL  the bytes of `value` (host memory, any length, any byte values);
+ *   CPH_MAP_COLUMN   the value of column `arg` (an index into cols) in row i;
+ *   CPH_MAP_INT64    ints[i] written as strconv.FormatInt(v, 10) does: '-' in front of a negative value, no '+', no leading
+ *                    zeros, 0 gives "0", INT64_MIN its 20 characters.  `ints` has nrows entries in the memory space `arg`
+ *                    (CPH_MEM_HOST / CPH_MEM_DEVICE); entry i belongs to OUTPUT row i (it is not read through row ids) —
+ *                    e.g. the values of cph_col_to_number after arithmetic on them.
+ * All bytes are copied verbatim (NUL and bytes >= 0x80 included); nothing is escaped.
+ *
+ * cols / sel / nrows mean exactly what they mean for cph_csv_write_rows (host or device columns, fixed-width or 32 / 64-bit
+ * offsets, per-column uint32 / uint64 row ids with a base living where the column lives; an identity column must have
+ * exactly nrows rows), so a template over JOINED rows reads every column through its own table's row ids and nothing is
+ * materialised.  ncols may be 0 (and cols NULL) for a template without COLUMN pieces.
+ *
+ * The result is an ordinary library-owned cph_colbuf (64-bit offsets, in out_mem, released by cph_colbuf_release): an
+ * identity column for every consumer — the writers, cph_filter_rows, cph_index_build.  nbytes is exact; nrows == 0 is
+ * legal and yields an empty column.
+ *
+ * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / pieces / out, npieces outside 1..CPH_MAP_MAX_PIECES, an
+ * unknown kind, a COLUMN index outside 0..ncols-1 (a column the rows lack is the host's business: it substitutes a literal
+ * or reports the reference's missing-column error), a literal with a length but no pointer, an INT64 piece with ints ==
+ * NULL while nrows > 0 or with an unknown memory space, ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
+ * than 32 / 64, an identity column whose row count is not nrows, an unknown out_mem.
+ *
+ * Out of scope: formatting float64 (Go's shortest round-trip FormatFloat is a project of its own), case mapping,
+ * trimming, substrings, conditional pieces.
+ */
+enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3 };
+#define CPH_MAP_MAX_PIECES 16
+typedef struct {
+    int32_t        kind;    /* CPH_MAP_* */
+    int32_t        arg;     /* COLUMN: index into cols; INT64: memory space of `ints` (CPH_MEM_*); LITERAL: ignored */
+    cph_strval     value;   /* LITERAL: its bytes (host memory, any length, any byte values) */
+    const int64_t* ints;    /* INT64: nrows values, entry i belongs to OUTPUT row i (no row ids) */
+} cph_map_piece;
+
+CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
+                               const cph_map_piece* pieces, int32_t npieces, int32_t out_mem, cph_colbuf** out);
+
 /* ---- CSV ingest: bytes -> SoA string columns (csvplus.go:1080-1146) ----------- */
 /*
  * Replaces the parse loop of Reader.Iterate (csv.NewReader + one map per line,
