@@ -952,21 +952,13 @@ static Status build_encode_sort(cph_ctx* ctx, BuildJob* job) {
         CPH_TRY(kb.alloc(&ctx->pool, n * kb_));
         const RadixPlan plan = radix_plan(ctx, n, cd.word_bits[0]);
         EncodeHist eh;
-        // distinct keys expected over a dense code space: slot[code] = row instead of radix passes (radix_sort.hip)
+        // distinct keys expected over a dense code space: slot[code] = row instead of radix passes (window_sort.hip)
         const uint64_t states = cd.word_states[0];
         const bool direct = job->unique && !job->no_direct && ctx->direct_sort != 0 && cd.key32 && !job->spec.active && n >= (1ull << 16) &&
                             states >= n && states <= 2 * n && states < 0xFFFFFFFFull;
         if (direct) {
             if (!job->miss) {
                 CPH_TRY(job_arm_miss(ctx, job));
-            }
-            // ctx option direct_sort = 3: over a full code space the encode kernel fills the slots itself (no code array).  Measured
-            // SLOWER than encode + a dedicated scatter kernel (1e7 rows: 0.26 against 0.047 + 0.164 ms — the scattered stores stall the
-            // LDS-heavy encode workgroups; profiles/r04_direct_sort.txt): an A/B switch, not the default.
-            if (states == n && ctx->direct_sort == 3) {
-                CPH_HIP_TRY(hipMemsetAsync(va.get(), 0xFF, n * sizeof(uint32_t), ctx->stream));
-                eh.slots = va.as<uint32_t>();
-                eh.slot_states = (uint32_t)states;
             }
             // fixed-width 8-byte keys under an arithmetic codec (decimal ids): the first partition level of the window sort codes the keys
             // itself — no encode kernel, no code array written and read again
@@ -992,12 +984,8 @@ static Status build_encode_sort(cph_ctx* ctx, BuildJob* job) {
                 return {};
             }
             CPH_TRY(codec_encode_build(ctx, cd, ix->codec_dev, dcols, n, ka.get(), &eh, nullptr, job->miss));
-            if (eh.scattered) CPH_TRY(direct_sort_finish_full(ctx, va.as<uint32_t>(), n, ka.as<uint32_t>(), job->miss));
-            else {
-                bool rt_written = false;
-                CPH_TRY(direct_sort_distinct(ctx, ka.as<uint32_t>(), n, states, va.as<uint32_t>(), ka.as<uint32_t>(), job->miss, rtp, rt_blocks, &rt_written));
-                if (rt_written) ix->ranktab = std::move(rt);
-            }
+            CPH_TRY(direct_sort_windows(ctx, ka.as<uint32_t>(), n, states, va.as<uint32_t>(), ka.as<uint32_t>(), job->miss, rtp, rt_blocks));
+            if (rtp) ix->ranktab = std::move(rt);
             ix->sorted_codes = std::move(ka);
             ix->perm = std::move(va);
             ix->sort_passes = 0;
@@ -1180,8 +1168,6 @@ CPH_API int32_t cph_ctx_set_option(cph_ctx* ctx, const char* name, int64_t value
     else if (k == "sort_xcd_tiles") ctx->sort_xcd_tiles = value != 0;
     else if (k == "codec_debug") ctx->codec_debug = (int)value;
     else if (k == "join_hash") ctx->join_hash = value != 0;
-    else if (k == "stream_role_streams") ctx->stream_role_streams = value != 0;
-    else if (k == "stream_zero_copy_out") ctx->stream_zero_copy_out = value != 0;
     else if (k == "chain_nt_streams") ctx->chain_nt_streams = value < 0 || value > 2 ? 0 : (int)value;
     else if (k == "chain_rank_lds") ctx->chain_rank_lds = value != 0;
     else if (k == "chain_rows4") ctx->chain_rows4 = value < 0 || value > 2 ? 1 : (int)value;
@@ -1194,21 +1180,22 @@ CPH_API int32_t cph_ctx_set_option(cph_ctx* ctx, const char* name, int64_t value
     else if (k == "host_threads") { ctx->host_threads = value < 0 || value > 256 ? 0 : (int)value; host_pool_destroy(ctx); }
     else if (k == "host_split") ctx->host_split = value < 0 || value > 2 ? 1 : (int)value;
     else if (k == "host_numa") ctx->host_numa = value != 0;
-    else if (k == "sample_lean") ctx->sample_lean = value != 0;
     else if (k == "hash_partitioned") ctx->hash_partitioned = value < 0 || value > 2 ? 1 : (int)value;
     else if (k == "host_split_threads") { ctx->host_split_threads = value < 0 || value > 256 ? 0 : (int)value; host_pool_destroy(ctx); }
     else if (k == "counted_sort") ctx->counted_sort = value != 0;
     else if (k == "csv_fast") ctx->csv_fast = value != 0;
     else if (k == "csv_onepass_debug") ctx->csv_onepass_debug = (int)value;
     else if (k == "csv_onepass") ctx->csv_onepass = value < 0 ? 0 : value > (1 << 20) ? (1 << 20) : (int)value;
-    else if (k == "direct_sort") ctx->direct_sort = value < 0 || value > 4 ? 1 : (int)value;   // 1: LDS windows (window_sort.hip); A/B: 4 plain scatter, 2 partition pass + scatter, 3 the encode kernel fills the slots
+    else if (k == "direct_sort") {   // 1: LDS windows (window_sort.hip); 0: the general sorts
+        if (value != 0 && value != 1) return fail_with(ctx, {CPH_ERR_INVALID, "direct_sort must be 0 or 1"});
+        ctx->direct_sort = (int)value;
+    }
     else if (k == "chain_arith") ctx->chain_arith = value != 0;
     else if (k == "chain_identity") ctx->chain_identity = value != 0;
     else if (k == "chain_prejoin") ctx->chain_prejoin = value != 0;
     else if (k == "direct_fused_encode") ctx->direct_fused_encode = value != 0;
     else if (k == "direct_ranktab") ctx->direct_ranktab = value != 0;
     else if (k == "hash_load_pct") ctx->hash_load_pct = value < 25 ? 25 : value > 90 ? 90 : (int)value;
-    else if (k == "probe_hash_rows") ctx->probe_hash_rows = value == 4 ? 4 : 2;
     else if (k == "small_build_rows") ctx->small_build_rows = value < 0 ? 0 : value > (1 << 20) ? (1 << 20) : (int)value;
     else if (k == "plan_threads") ctx->plan_threads = (int)value;
     else if (k == "gstats_threads") ctx->gstats_threads = (int)value;

@@ -342,14 +342,11 @@ struct cph_ctx {
     int sort_digit_stream = 1;     // scatter writes the next pass's digits as a byte stream for its histogram (radix_sort.hip)
     int sort_xcd_tiles = 1;        // scatter: contiguous tile ranges per XCD (radix_sort.hip)
     int small_build_rows = 8192;   // tables of at most this many rows (<= 16384) are indexed by ONE launch of one workgroup (small_build.hip); 0: never
-    int stream_role_streams = 0;   // cph_stream_join (fused mode): 1 = one stream for all uploads, one for all downloads; 0 (default, faster at 2 and 4 slots): everything of a slot on its own stream
-    int stream_zero_copy_out = 0;  // cph_stream_join (fused mode): the kernel stores the row ids straight into the slot's pinned block
     int chain_nt_streams = 0;      // chained join: non-temporal loads / stores for the stream's bytes and the results (0 never, 1 always, 2 positions mode)
     int chain_arith = 1;           // chained join: fixed-width key columns over contiguous alphabets are encoded arithmetically (codec_device.hpp: ArithPlan) and read with one aligned load (A/B switch)
     int chain_identity = 1;        // positions mode: an index whose code space is exactly as large as the index needs no lookup (A/B switch)
     int chain_rows4 = 1;           // chained join: register-heavy kernel variants walk 4 rows per lane and phase instead of 8 (0: never, 2: every non-lean chain; A/B switch)
     int chain_rank_lds = 1;        // positions mode: rank tables of small indexes are copied into LDS by every workgroup (A/B switch)
-    int probe_hash_rows = 2;       // rows per phase of the generic hash probe (2 / 4): 4 rows need 164 VGPRs (3 waves per SIMD) and measured 20 % slower
     int join_hash = 1;             // 0: indexes of this ctx never get a hash table (A/B switch: sorted search instead)
     int codec_debug = 0;           // prints the window choice of codec_try_groups to stderr
     uint64_t n_split_respec = 0;   // builds whose sampled split codec missed a row and that started over with the exact statistics (cph_ctx_get_stat)
@@ -369,13 +366,12 @@ struct cph_ctx {
     int csv_onepass = 1;           // cph_csv_write[_rows]: one pass over the joined rows (materialize.hip: k_csv_onepass; slot tables + decoupled look-back);
                                    // 0: the two-pass writer; N > 1: taken whatever the row count, with at most N workgroups (tests)
     int csv_onepass_debug = 0;     // measurement only (wrong text): 1 no look-back, 2 no record bytes, 4 one record per thread
-    int sample_lean = 1;           // the sample of a fixed-width key column of <= 8 bytes is taken by k_sample_fixed8 (A/B switch; 0: k_split_count)
     int hash_partitioned = 1;      // the hash table of a duplicate-free index of >= 2^21 keys is built slice by slice in LDS (probe.hip); 0: CAS into the whole
                                    // table; 2: slice by slice whatever the size (tests)
     int counted_sort = 1;          // IndexOn over 32-bit codes with duplicates: MSD sort through counted LDS windows (counted_sort.hip); 0: the classic passes
     int direct_sort = 1;           // a build that expects distinct keys (UniqueIndexOn) over a dense 32-bit code space (rows <= states <= 2 rows)
-                                   // sorts by ONE scatter, slot[code] = row (radix_sort.hip: direct_sort_distinct); a duplicate is noticed on
-                                   // the device and the build starts over the general way (A/B switch)
+                                   // sorts by placement, slot[code] = row, in LDS windows (window_sort.hip); a duplicate is noticed on
+                                   // the device and the build starts over the general way (A/B switch; 0: always the general way)
     int stats_sample = 1;          // IndexOn over ONE fixed-width key column of >= 2^20 rows takes its alphabets from a sample; the encode
                                    // kernel checks every row against them and the build starts over with exact statistics on a miss (A/B switch)
     int host_build = 1;            // cph_index_build over ONE key column of <= 8 byte positions in HOST memory: the codes are formed by host
@@ -611,12 +607,6 @@ struct EncodeHist {
     uint32_t bins = 0;            // digits per pass of the sort (256 or 512 >= digit_mask + 1)
     uint32_t* counts = nullptr;   // device [bins][ntiles], digit-major
     bool done = false;
-    // Direct sort of distinct keys over a FULL code space (radix_sort.hip): instead of writing the codes, the encode kernel stores
-    // slot[code] = row straight away (slots: device u32[states], preset to 0xFFFFFFFF).  scattered = the kernel that ran did so
-    // (only the single-column fast path can); otherwise the codes were written as usual.
-    uint32_t* slots = nullptr;
-    uint32_t slot_states = 0;
-    bool scattered = false;
 };
 // cols = the TABLE's key columns (a split codec's virtual columns are formed inside).  miss (optional, device u32): set
 // when a row did not code (split codecs only: see codec_try_split).
@@ -678,10 +668,8 @@ struct CountedSort {
 Status counted_sort(cph_ctx* ctx, const CountedSortPlan& p, const uint32_t* codes, uint64_t n, uint64_t states, uint32_t* perm_out,
                     uint32_t* sorted_out, uint32_t* first_dup_dev, uint32_t* over_host);
 void warm_counted_sort();
-// distinct 32-bit codes over a dense space: one scatter instead of radix passes (optimistic; *flag raised on a duplicate)
-Status direct_sort_distinct(cph_ctx* ctx, const uint32_t* codes, uint64_t n, uint64_t states, uint32_t* perm_out, uint32_t* sorted_out,
-                            uint32_t* flag, void* ranktab = nullptr, uint64_t rank_blocks = 0, bool* ranktab_written = nullptr);
-// the same through LDS windows: a partition by the top code bits, then every window placed in LDS and streamed out (window_sort.hip)
+// distinct 32-bit codes over a dense space (optimistic; *flag raised on a duplicate): a partition by the top code bits, then every
+// window placed in LDS and streamed out (window_sort.hip)
 struct ArithPlan;   // codec_device.hpp
 Status direct_sort_windows_keys(cph_ctx* ctx, const uint64_t* keys, const ArithPlan& ap, uint64_t n, uint64_t states, uint32_t* perm_out,
                                 uint32_t* sorted_out, uint32_t* flag, void* ranktab = nullptr, uint64_t rank_blocks = 0);
@@ -705,8 +693,6 @@ struct WindowSort {
     DevBuf* words = nullptr;
     uint32_t *cur1 = nullptr, *cur2 = nullptr;
 };
-// the second half of it for a full code space whose slots the encode kernel already filled: every slot taken? + the sorted codes
-Status direct_sort_finish_full(cph_ctx* ctx, const uint32_t* slots, uint64_t n, uint32_t* sorted_out, uint32_t* flag);
 Status exclusive_scan_u32(cph_ctx* ctx, uint32_t* data, uint64_t n);
 Status exclusive_scan_u32_total(cph_ctx* ctx, uint32_t* data, uint64_t n, uint32_t* total_out);   // total_out: device
 Status exclusive_scan_u64(cph_ctx* ctx, uint64_t* data, uint64_t n, uint64_t* total_out);

@@ -732,7 +732,7 @@ struct LookupArg {
     int32_t unique = 0;                  // the index has no duplicate keys: entries carry {lo, build row}
 };
 
-template <bool KEY32, int LOOKUP, int HROWS = 4>
+template <bool KEY32, int LOOKUP>
 __global__ __launch_bounds__(kProbeThreads) void k_probe(ColsArg cols, int ncols_used,
                                                         const uint8_t* __restrict__ g_codec,
                                                         const void* __restrict__ codes, uint64_t n_index,
@@ -750,8 +750,9 @@ __global__ __launch_bounds__(kProbeThreads) void k_probe(ColsArg cols, int ncols
     if constexpr (LOOKUP == kLookHash) {
         // Full-key probe through the hash table (hash_device.hpp).  kHashRows rows per phase: their keys are encoded
         // one after the other (the generic encoder walks columns and byte positions), then the home sectors of all of
-        // them are loaded together — the random accesses are what the kernel waits for.
-        constexpr int kHashRows = HROWS;
+        // them are loaded together — the random accesses are what the kernel waits for.  (4 rows per phase need 164 VGPRs,
+        // 3 waves per SIMD, and measured 20 % slower: HISTORY.md §5.3)
+        constexpr int kHashRows = 2;
         const uint64_t* cw = reinterpret_cast<const uint64_t*>(codes);
 #pragma unroll 1
         for (int ph = 0; ph < kProbeItems / kHashRows; ph++) {
@@ -1332,17 +1333,10 @@ static Status launch_probe(cph_ctx* ctx, const cph_index* ix, const ColsArg& arg
                            uint64_t nprobe, uint32_t* lo, uint32_t* cnt, uint64_t* tile_sums, unsigned ntiles, uint32_t* first_row) {
     const size_t lds = ix->codec_dev.bytes();
     ProfScope ps(ctx, look_name(LOOKUP), 0);
-    if (LOOKUP == kLookHash && ctx->probe_hash_rows != 4) {   // rows per phase of the hash probe (tuning: registers against loads in flight)
-        CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(&k_probe<KEY32, LOOKUP, 2>), kProbeThreads, lds, nullptr));
-        hipLaunchKernelGGL((k_probe<KEY32, LOOKUP, 2>), dim3(ntiles), dim3(kProbeThreads), lds, ctx->stream, arg, ncols,
-                           ix->codec_dev.as<uint8_t>(), ix->sorted_codes.get(), ix->nrows, look, row_sel, nprobe, lo, cnt, tile_sums,
-                           first_row);
-    } else {
-        CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(&k_probe<KEY32, LOOKUP, 4>), kProbeThreads, lds, nullptr));
-        hipLaunchKernelGGL((k_probe<KEY32, LOOKUP, 4>), dim3(ntiles), dim3(kProbeThreads), lds, ctx->stream, arg, ncols,
-                           ix->codec_dev.as<uint8_t>(), ix->sorted_codes.get(), ix->nrows, look, row_sel, nprobe, lo, cnt, tile_sums,
-                           first_row);
-    }
+    CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(&k_probe<KEY32, LOOKUP>), kProbeThreads, lds, nullptr));
+    hipLaunchKernelGGL((k_probe<KEY32, LOOKUP>), dim3(ntiles), dim3(kProbeThreads), lds, ctx->stream, arg, ncols,
+                       ix->codec_dev.as<uint8_t>(), ix->sorted_codes.get(), ix->nrows, look, row_sel, nprobe, lo, cnt, tile_sums,
+                       first_row);
     CPH_HIP_TRY(hipGetLastError());
     return {};
 }

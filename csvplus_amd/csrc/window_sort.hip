@@ -2,9 +2,10 @@
 // (UniqueIndexOn of ids: createUniqueIndex, csvplus.go:740-756; replaces sort.Sort(&index.impl), :736, for that case).
 //
 // When a table is expected to hold no duplicates and its codes fill their space densely (rows <= states <= 2 rows), the
-// sorted order IS the code: slot[code] = row.  radix_sort.hip's k_direct_scatter does exactly that with one random 4-byte
-// store per row — 62 G stores/s on this chip and 8x write amplification (a 32-byte partial sector per store), the kernel
-// furthest below its roofline in round 4.  Here the random placement happens in LDS instead:
+// sorted order IS the code: slot[code] = row.  No histogram, no count matrix, no scan per digit.  Done in global memory that
+// is one random 4-byte store per row — 62 G stores/s on this chip and 8x write amplification (a 32-byte partial sector per
+// store), the kernel furthest below its roofline in round 4 (profiles/r04_direct_sort.txt).  Here the random placement
+// happens in LDS instead:
 //
 //   k_win_partition   the rows are split by the TOP bits of their codes into buckets that each cover one WINDOW of
 //                     2^14 slots (64 KB of LDS).  Keys are distinct, so a bucket can never hold more entries than its
@@ -16,7 +17,7 @@
 //                     then the window leaves as ONE sequential stream: perm (rows in code order) and the sorted codes,
 //                     compacted over the empty slots of a code space that is larger than the table.
 //
-// Optimistic like the scatter it replaces: two rows with one code overwrite each other in LDS (or overflow a bucket); the
+// Optimistic: two rows with one code overwrite each other in LDS (or overflow a bucket); the
 // window then holds fewer rows than entries and *flag is raised — the caller builds the index the general way, which also
 // says WHERE the first duplicate is (csvplus.go:749-753).
 //

@@ -138,10 +138,6 @@ CPH_API int32_t cph_ctx_set_stream(cph_ctx* ctx, void* hip_stream);
  *                   pass's histogram reads 1 byte per key instead of 8
  *   "chain_nt_streams" 0 / 1 / 2 (default 0): the chained Join loads the stream's bytes and stores its results non-temporally — never,
  *                   always, in positions mode only (measured: within 1 %)
- *   "stream_role_streams" 0 / 1 (default 0): cph_stream_join in fused mode with one HIP stream for all uploads and one for all downloads
- *                   instead of one stream per slot (slower at 2 and 4 slots)
- *   "stream_zero_copy_out" 0 / 1 (default 0): cph_stream_join in fused mode lets the kernel store its results straight into the slot's
- *                   pinned host block
  *   "speculative_groups"  dictionary windows of long keys on large inputs: 0 = always the exact pass over all rows,
  *                   1 = dictionaries straight from the row sample when every value of every chosen window is COMMON in it
  *                   (met 16 times or more: a closed vocabulary; default),
@@ -196,9 +192,8 @@ CPH_API int32_t cph_ctx_set_stream(cph_ctx* ctx, void* hip_stream);
  *                   dense 32-bit code space (rows <= code states <= 2 rows: decimal ids, row numbers) sorts without radix passes: the rows
  *                   are split by the top bits of their codes into 2^14-slot windows, every window is filled in LDS (slot = code) and
  *                   streamed out — all global stores sequential; a duplicate is noticed on the device and the build starts over the
- *                   general way, which also reports where the first duplicate is.  (A/B switches: 4 = slot[code] = row as one random
- *                   4-byte store per row, the round-4 path; 2 = that behind one radix pass on the top 8 bits; 3 = the encode kernel
- *                   fills the slots of a full code space itself)
+ *                   general way, which also reports where the first duplicate is.  0: always the general way (A/B switch); any other
+ *                   value fails with CPH_ERR_INVALID and leaves the setting as it was
  *   "stats_sample"  0 / 1 (default 1): IndexOn over ONE fixed-width key column (<= 40 bytes) of >= 2^20 rows learns its per-position
  *                   alphabets from ~65 536 rows spread over the table instead of a pass over all rows; the encode kernel checks every
  *                   row against them, and a row with a byte the sample did not show makes the build start over with the exact
@@ -222,8 +217,6 @@ CPH_API int32_t cph_ctx_set_stream(cph_ctx* ctx, void* hip_stream);
  *                   it computes, where the 8-byte loops wait for memory)
  *   "host_numa"     0 / 1 (default 0): 1 binds that pool's workers to the CPUs of the NUMA node that holds the column's first page
  *                   (opt-in: its effect could not be measured on the quota-limited test hosts)
- *   "sample_lean"   0 / 1 (default 1): the sample of a fixed-width key column of at most 8 bytes is taken by a kernel that collects
- *                   nothing but the per-position byte presence (the only thing stats_sample uses; A/B switch)
  *   "hash_partitioned" 0 / 1 / 2 (default 1): the hash table of a duplicate-free index of >= 2^21 keys (sparse key codes: random ids,
  *                   hashes) is built SLICE BY SLICE: the rows grouped by the 64 KB slice of the table their home sector lies in, every
  *                   slice filled in LDS by one workgroup and written out once (probe sequences wrap inside a slice) instead of
@@ -235,7 +228,6 @@ CPH_API int32_t cph_ctx_set_stream(cph_ctx* ctx, void* hip_stream);
  *   "codec_debug"   1: the window choice of every index build (and the phase times of a one-launch build) go to stderr
  *   "small_build_rows"  tables of at most this many rows (default 8192, at most 16384) are indexed by ONE launch of one
  *                   workgroup and one synchronisation (small_build.hip); 0 = always the general path
- *   "probe_hash_rows"  2 / 4: rows per phase of the generic hash probe (default 2)
  *   "chain_rank_lds"  0 / 1: a Join that reports positions copies the rank tables of small indexes into LDS (default 1)
  *   "chain_rows4"   0 / 1 / 2 (default 1): the register-heavy variants of the fused chained Join (keys beyond 8 bytes with 64-bit codes
  *                   from two steps on, long or wide chains from three steps on) keep 4 rows per lane in flight instead of 8, which

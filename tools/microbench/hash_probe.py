@@ -73,10 +73,6 @@ def run(name, alphabet, width):
               f"bits={inf['code_bits']} unique={ix.first_dup is None} hash_mode={inf['hash_mode']} hash_MB={inf['hash_bytes'] / 1e6:.0f}", flush=True)
         reps = 3 if hash_on else 2
         timed("cph_join_probe bounds only", ctx, lambda: ix.probe([d_probe], want_pairs=False, out_mem=N.CPH_MEM_DEVICE).release(), reps)
-        if hash_on and inf["code_words"] > 1 and "--rows-ab" in sys.argv:   # generic kernel: rows per phase, A/B on this box
-            ctx.set_option("probe_hash_rows", 2)
-            timed("cph_join_probe bounds only (2 rows per phase)", ctx, lambda: ix.probe([d_probe], want_pairs=False, out_mem=N.CPH_MEM_DEVICE).release(), reps)
-            ctx.set_option("probe_hash_rows", 4)
         timed("cph_join_probe + pairs", ctx, lambda: ix.probe([d_probe], out_mem=N.CPH_MEM_DEVICE).release(), reps)
         if ix.first_dup is None and inf["code_words"] == 1:
             timed("cph_join_chain (1 step, fused kernel)", ctx, lambda: join_chain(ctx, [(ix, [d_probe])], out_mem=N.CPH_MEM_DEVICE).release(), reps)
