@@ -476,27 +476,50 @@ __global__ __launch_bounds__(256) void k_sum_counts(const uint32_t* __restrict__
     }
 }
 
-// The same, reporting straight to the host: the sum gathers in a SELF-CLEANING device accumulator (cph_ctx::SelfClean::sum:
-// {u64 total, u32 ticket}, zero at rest) and the LAST workgroup stores it into *host_out (pinned host memory: cph::host_word)
-// and zeroes the accumulator again — no memset in front of this launch, no device-to-host copy behind it.
+// The same, reporting straight to the host: the sum gathers in a SELF-CLEANING device accumulator (cph_ctx::SelfClean::sum: one
+// u64, zero at rest) and the LAST workgroup stores it into *host_out (pinned host memory: cph::host_word) and zeroes the
+// accumulator again — no memset in front of this launch, no device-to-host copy behind it.
+// Sized for latency (sum_counts_grid): the kernel stands in front of a host wait.  A device-wide atomic on one address
+// sustains ~90 per us (see the header), so there are at most kSumBlocks workgroups and each makes ONE: its partial sum and its
+// ticket travel in the same 64-bit add (the ticket in the bits from kSumTicketShift up; a total stays far below 2^56 rows), which
+// also orders them without a fence — the workgroup whose add returns the last ticket has the other sums in the value it got
+// back.  A thread keeps kSumLoads 16-byte loads in flight, which covers the flagship Join's 0.78 MB of counts in one round trip.
+constexpr int kSumBlocks = 32;
+constexpr int kSumLoads = 8;
+constexpr int kSumTicketShift = 56;
+static unsigned sum_counts_grid(uint64_t n) {
+    const uint64_t per_block = 256ull * 4 * kSumLoads;
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)kSumBlocks));
+}
 __global__ __launch_bounds__(256) void k_sum_counts_report(const uint32_t* __restrict__ counts, uint64_t n, unsigned long long* __restrict__ acc,
-                                                          uint32_t* __restrict__ ticket, unsigned long long* __restrict__ host_out) {
+                                                          unsigned long long* __restrict__ host_out) {
     __shared__ uint64_t s_w[256 / kWave];
     uint64_t t = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) t += counts[i];
+    const uint64_t stride = (uint64_t)gridDim.x * 256, gt = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    // whole 16-byte groups first (a count array that is not 16-byte aligned goes the scalar way altogether)
+    const uint64_t nv = ((uintptr_t)counts & 15) == 0 ? n >> 2 : 0;
+    const uint4* __restrict__ c4 = reinterpret_cast<const uint4*>(counts);
+    for (uint64_t v0 = gt; v0 < nv; v0 += stride * kSumLoads) {
+        uint4 x[kSumLoads];
+#pragma unroll
+        for (int k = 0; k < kSumLoads; k++) {
+            const uint64_t v = v0 + (uint64_t)k * stride;
+            x[k] = v < nv ? c4[v] : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int k = 0; k < kSumLoads; k++) t += (uint64_t)x[k].x + x[k].y + x[k].z + x[k].w;
+    }
+    for (uint64_t i = nv * 4 + gt; i < n; i += stride) t += counts[i];
     t = wave_sum(t);
     if (lane_id() == 0) s_w[wave_id()] = t;
     __syncthreads();
     if (threadIdx.x == 0) {
         uint64_t r = 0;
         for (int w = 0; w < 256 / kWave; w++) r += s_w[w];
-        if (r) atomicAdd(acc, (unsigned long long)r);
-        __threadfence();
-        if (atomicAdd(ticket, 1u) == gridDim.x - 1u) {   // every other workgroup's add happened before its ticket
-            const unsigned long long total = atomicExch(acc, 0ull);
-            atomicExch(ticket, 0u);
-            *host_out = total;
+        const unsigned long long before = atomicAdd(acc, (unsigned long long)r + (1ull << kSumTicketShift));
+        if ((before >> kSumTicketShift) == gridDim.x - 1u) {   // the last ticket: every other workgroup's sum is in `before`
+            atomicExch(acc, 0ull);
+            *host_out = (before & ((1ull << kSumTicketShift) - 1ull)) + r;
             __threadfence_system();
         }
     }
@@ -863,9 +886,9 @@ static Status enqueue_dense(cph_ctx* ctx, const ChainStep* steps, uint64_t nprob
         DevBuf& acc = ctx->self_clean[ctx->stream_slot].sum;
         CPH_TRY(self_clean_block(ctx, &acc, 16));
         ProfScope ps(ctx, "k_sum_counts", 4.0 * (double)ncounts);
-        const unsigned sgrid = (unsigned)std::min<uint64_t>((ncounts + 255) / 256, 512);
+        const unsigned sgrid = sum_counts_grid(ncounts);
         hipLaunchKernelGGL(k_sum_counts_report, dim3(sgrid), dim3(256), 0, ctx->stream, d_counts, ncounts, acc.as<unsigned long long>(),
-                           acc.as<uint32_t>() + 2, reinterpret_cast<unsigned long long*>(host_total));
+                           reinterpret_cast<unsigned long long*>(host_total));
     } else if (d_total) {   // (neither: the caller adds passes that change the counts and sums them itself — run_prejoined)
         ProfScope ps(ctx, "k_sum_counts", 4.0 * (double)ncounts);
         CPH_HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(uint64_t), ctx->stream));
@@ -1022,9 +1045,9 @@ static Status run_prejoined(cph_ctx* ctx, const ChainStep* steps, int S, uint64_
         DevBuf& acc = ctx->self_clean[ctx->stream_slot].sum;
         CPH_TRY(self_clean_block(ctx, &acc, 16));
         ProfScope ps(ctx, "k_sum_counts", 4.0 * (double)ncounts);
-        const unsigned sgrid = (unsigned)std::min<uint64_t>((ncounts + 255) / 256, 512);
+        const unsigned sgrid = sum_counts_grid(ncounts);
         hipLaunchKernelGGL(k_sum_counts_report, dim3(sgrid), dim3(256), 0, ctx->stream, counts, ncounts, acc.as<unsigned long long>(),
-                           acc.as<uint32_t>() + 2, reinterpret_cast<unsigned long long*>(host_total));
+                           reinterpret_cast<unsigned long long*>(host_total));
         CPH_HIP_TRY(hipGetLastError());
     }
     // the tables are released here: stream-ordered reuse keeps them alive for the kernels already enqueued
@@ -1128,9 +1151,9 @@ static Status prejoin_general_step(cph_ctx* ctx, const ChainStep* steps, int s, 
         DevBuf& acc = ctx->self_clean[ctx->stream_slot].sum;
         CPH_TRY(self_clean_block(ctx, &acc, 16));
         ProfScope ps(ctx, "k_sum_counts", 4.0 * (double)ntiles);
-        const unsigned sgrid = (unsigned)std::min<uint64_t>((ntiles + 255) / 256, 512);
+        const unsigned sgrid = sum_counts_grid(ntiles);
         hipLaunchKernelGGL(k_sum_counts_report, dim3(sgrid), dim3(256), 0, ctx->stream, counts.as<uint32_t>(), ntiles, acc.as<unsigned long long>(),
-                           acc.as<uint32_t>() + 2, reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(host_total)));
+                           reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(host_total)));
         CPH_HIP_TRY(hipGetLastError());
     }
     CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));

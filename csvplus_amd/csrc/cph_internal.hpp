@@ -329,7 +329,7 @@ struct cph_ctx {
     // fills one exports the result to a report word and zeroes it again): no memset in front of the kernel, no copy behind it.
     // One set per stream slot (the two streams of a build batch run concurrently).
     struct SelfClean {
-        cph::DevBuf sum;           // k_sum_counts_report: {u64 total, u32 ticket, u32 pad}
+        cph::DevBuf sum;           // k_sum_counts_report: one u64, ticket << 56 | total (16 bytes allocated)
         cph::DevBuf sample;        // k_split_count of a sampled build: SplitSample + ticket
         cph::DevBuf win;           // window_sort.hip: bucket cursors
         uint64_t win_words = 0;

@@ -1229,7 +1229,14 @@ __global__ __launch_bounds__(kSplitThreads) void k_encode_split(DevCol col, cons
 
 // The sample of a FIXED-WIDTH column of at most 8 bytes (ids): only the per-position byte presence is wanted (codec_sample_finish) —
 // one 8-byte load per row and 8 LDS bit sets instead of k_split_count's 40-byte windows and first-occurrence counts: the kernel sits
-// on the critical path of every UniqueIndexOn(ids) (bench step: 32 us -> ~10).  Same self-cleaning accumulator, same host block.
+// on the critical path of every UniqueIndexOn(ids).  Same self-cleaning accumulator, same host block.
+// The launch is sized for latency, not for occupancy (codec_sample_launch): at most kFixed8Blocks workgroups, every thread
+// with kFixed8Rows dependent-free loads in flight, so that the 65 536 .. 131 071 sampled rows are ONE round trip to memory and the
+// global atomics (a few mask words and one ticket per workgroup, all on the same few addresses: ~90 per us device-wide) stay
+// under a microsecond.  Wave 0 alone issues the workgroup's global atomics and takes its ticket, so one wave's release fence
+// orders them; the host block arrives zeroed (host_word), so only the 64 mask words a width <= 8 can set are stored.
+constexpr int kFixed8Rows = 8;
+constexpr int kFixed8Blocks = 64;             // x kSplitThreads x kFixed8Rows = 131 072 >= the largest sample
 __global__ __launch_bounds__(kSplitThreads) void k_sample_fixed8(DevCol col, uint64_t step, uint64_t n, SplitSample* __restrict__ out,
                                                                 SplitSample* __restrict__ host_out) {
     __shared__ uint32_t s_mask[8 * 8];
@@ -1238,32 +1245,43 @@ __global__ __launch_bounds__(kSplitThreads) void k_sample_fixed8(DevCol col, uin
     if (threadIdx.x < 64) s_mask[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t stride = (uint64_t)gridDim.x * kSplitThreads;
-    for (uint64_t i = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x; i < n; i += stride) {
-        uint64_t b, l;
-        value_span_whole(col, i * step, &b, &l);
-        ValueRegs<1> v;
-        v.load(col, b, l);
-        for (uint32_t q = 0; q < W; q++) {
-            const uint32_t byte = (uint32_t)(v.c[0] >> (8u * q)) & 0xFFu, bit = 1u << (byte & 31u);
-            uint32_t* w = &s_mask[q * 8u + (byte >> 5)];
-            if (!(*(volatile uint32_t*)w & bit)) atomicOr(w, bit);
+    for (uint64_t i0 = (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x; i0 < n; i0 += stride * kFixed8Rows) {
+        uint64_t c[kFixed8Rows];
+#pragma unroll
+        for (int k = 0; k < kFixed8Rows; k++) {   // a row past the end reads row i0 again (presence only: harmless)
+            const uint64_t i = i0 + (uint64_t)k * stride;
+            ValueRegs<1> v;   // (a plain fixed-width column, codec_sample_applies: the value's span needs no branch)
+            v.load(col, (i < n ? i : i0) * step * W, W);
+            c[k] = v.c[0];
+        }
+        for (uint32_t q = 0; q < W; q++) {   // the rows' LDS reads of a position overlap
+            uint32_t seen[kFixed8Rows];
+#pragma unroll
+            for (int k = 0; k < kFixed8Rows; k++) {
+                const uint32_t byte = (uint32_t)(c[k] >> (8u * q)) & 0xFFu;
+                seen[k] = *(volatile CPH_LDS uint32_t*)&s_mask[q * 8u + (byte >> 5)];   // (LDS-qualified: a ds_read, not a flat load)
+            }
+#pragma unroll
+            for (int k = 0; k < kFixed8Rows; k++) {
+                const uint32_t byte = (uint32_t)(c[k] >> (8u * q)) & 0xFFu, bit = 1u << (byte & 31u);
+                if (!(seen[k] & bit)) atomicOr(&s_mask[q * 8u + (byte >> 5)], bit);
+            }
         }
     }
     lds_atomics_barrier();
-    if (threadIdx.x < 64) {
+    uint32_t* ticket = reinterpret_cast<uint32_t*>(out + 1);
+    if (threadIdx.x < 64) {   // wave 0
         const uint32_t bits = s_mask[threadIdx.x];
         uint32_t* gm = &out->mask[0][0] + threadIdx.x;
         if (bits && (__hip_atomic_load(gm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bits) != bits) atomicOr(gm, bits);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // this wave's atomics are performed before its ticket
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
     }
-    uint32_t* ticket = reinterpret_cast<uint32_t*>(out + 1);
-    __threadfence();
     __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
-    __syncthreads();
-    if (s_last) {   // every other workgroup's atomics happened before its ticket
-        uint32_t* src = &out->mask[0][0];
-        uint32_t* dst = &host_out->mask[0][0];
-        for (uint32_t i = threadIdx.x; i < (uint32_t)(kSplitMaxValue * 8); i += kSplitThreads) dst[i] = i < 64u ? atomicExch(&src[i], 0u) : 0u;
+    if (s_last && threadIdx.x < 64) {   // every other workgroup's atomics happened before its ticket
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        (&host_out->mask[0][0])[threadIdx.x] = atomicExch(&out->mask[0][0] + threadIdx.x, 0u);   // (words 64 .. are zero already)
         if (threadIdx.x == 0) {
             host_out->maxlen = W;
             host_out->minlen_inv = ~W;
@@ -1499,7 +1517,7 @@ Status codec_sample_launch(cph_ctx* ctx, const DevCol& col, uint64_t n, const vo
     uint64_t nblk = (nsel + kSplitThreads - 1) / kSplitThreads;
     if (nblk > 1024) nblk = 1024;
     if (col.fixed_width <= 8)
-        hipLaunchKernelGGL(k_sample_fixed8, dim3((unsigned)nblk), dim3(kSplitThreads), 0, ctx->stream, col, step, nsel, acc.as<SplitSample>(),
+        hipLaunchKernelGGL(k_sample_fixed8, dim3((unsigned)std::min<uint64_t>(nblk, (uint64_t)kFixed8Blocks)), dim3(kSplitThreads), 0, ctx->stream, col, step, nsel, acc.as<SplitSample>(),
                            reinterpret_cast<SplitSample*>(hw));
     else
         hipLaunchKernelGGL(k_split_count, dim3((unsigned)nblk), dim3(kSplitThreads), 0, ctx->stream, col, step, nsel, acc.as<SplitSample>(),

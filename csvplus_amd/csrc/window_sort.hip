@@ -28,9 +28,19 @@
 
 namespace cph {
 
+// Tile geometry.  Both make tiles of 8192 rows — the tile sets how many global atomics a row costs (one per tile and
+// bucket) and how long a bucket's run of consecutive entries is; halving it made the 1e7-id pass 1.5x slower:
+//   two levels (1e8 ids):  512 threads x 16 rows, 125 VGPRs, 2 workgroups = 16 waves per CU
+//   one level  (1e7 ids): 1024 threads x  8 rows,  61 VGPRs, 2 workgroups = 32 waves per CU.  The phases of a tile are a chain
+//                         of latencies (key loads, LDS histogram, global atomics, staging, stores) with a workgroup barrier
+//                         between every two, and only the CU's other waves fill them: 1e7 ids 73 -> 53 us with twice the waves.
+//                         (The two-level passes keep the geometry they were tuned with.)
 constexpr int kWpThreads = 512;
 constexpr int kWpItems = 16;
+constexpr int kWpThreadsOneLevel = 1024;
+constexpr int kWpItemsOneLevel = 8;
 constexpr int kWpTile = kWpThreads * kWpItems;   // rows per partition tile
+static_assert(kWpThreadsOneLevel * kWpItemsOneLevel == kWpTile, "one tile size");
 constexpr int kWpMaxBuckets = 2048;              // buckets one partition level splits into
 constexpr int kWinBits = 14;                     // window = 2^14 slots = 64 KB of LDS
 constexpr uint32_t kWinSlots = 1u << kWinBits;
@@ -57,20 +67,21 @@ struct WpArgs {
 
 // entry = (code relative to its bucket's first code) << 32 | row
 // A tile's rows stay in REGISTERS (code, row, arrival rank inside the bucket) until they are staged, as whole 8-byte entries and
-// bucket by bucket, in LDS; the staged entries then leave as coalesced runs, 16 per thread in flight.  (Round 5's first version
+// bucket by bucket, in LDS; the staged entries then leave as coalesced runs, ITEMS per thread in flight.  (Round 5's first version
 // staged 16-bit row numbers and fetched code and row again per entry inside a rolled loop — a chain of four LDS loads and, for
 // the second level, a global load per iteration: 0.7 ms per level at 1e8 rows, 2 TB/s.)
 // SRC: 0 = entries of a source bucket (second level), 1 = the code array, 2 = the key column itself (an arithmetic codec over
 // fixed-width 8-byte keys, codec_device.hpp: ArithPlan — the encode kernel and its 4-byte code per row written and read again
 // are gone: 1e8 ids 0.26 + 0.31 -> one pass)
-template <int SRC>
-__global__ __launch_bounds__(kWpThreads) void k_win_partition(WpArgs a) {
+template <int SRC, int THREADS, int ITEMS>
+__global__ __launch_bounds__(THREADS) void k_win_partition(WpArgs a) {
     constexpr bool FROM_CODES = SRC != 0;
+    constexpr int TILE = THREADS * ITEMS;   // rows per tile
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    __shared__ uint32_t s_tmp[kWpThreads / kWave + 1];
-    const uint32_t nbp = (a.nb + (uint32_t)kWpThreads - 1u) & ~((uint32_t)kWpThreads - 1u);
-    uint64_t* s_ent = reinterpret_cast<uint64_t*>(smem);                    // [kWpTile] (code within the source bucket) << 32 | row
-    uint32_t* s_hist = reinterpret_cast<uint32_t*>(s_ent + kWpTile);        // [nbp]
+    __shared__ uint32_t s_tmp[THREADS / kWave + 1];
+    const uint32_t nbp = (a.nb + (uint32_t)THREADS - 1u) & ~((uint32_t)THREADS - 1u);
+    uint64_t* s_ent = reinterpret_cast<uint64_t*>(smem);                    // [TILE] (code within the source bucket) << 32 | row
+    uint32_t* s_hist = reinterpret_cast<uint32_t*>(s_ent + TILE);           // [nbp]
     uint32_t* s_start = s_hist + nbp;                                       // [nbp] first staged entry of the bucket
     uint32_t* s_delta = s_start + nbp;                                      // [nbp] its room in the destination bucket - s_start
     const uint32_t sb = blockIdx.x / a.tiles_per_src, tl = blockIdx.x % a.tiles_per_src;
@@ -79,22 +90,22 @@ __global__ __launch_bounds__(kWpThreads) void k_win_partition(WpArgs a) {
         const uint32_t c = a.src_count[sb];
         cnt = c < a.src_cap ? c : a.src_cap;   // (a count beyond the capacity: duplicates — the writer raised the flag)
     }
-    const uint64_t t0 = (uint64_t)tl * kWpTile;
+    const uint64_t t0 = (uint64_t)tl * TILE;
     if (t0 >= cnt) return;
-    const uint32_t m = cnt - t0 < (uint64_t)kWpTile ? (uint32_t)(cnt - t0) : (uint32_t)kWpTile;
+    const uint32_t m = cnt - t0 < (uint64_t)TILE ? (uint32_t)(cnt - t0) : (uint32_t)TILE;
     const uint64_t src0 = FROM_CODES ? t0 : (uint64_t)sb * a.src_cap + t0;
     const uint32_t t = threadIdx.x;
-    for (uint32_t i = t; i < nbp; i += kWpThreads) s_hist[i] = 0;
+    for (uint32_t i = t; i < nbp; i += THREADS) s_hist[i] = 0;
     __syncthreads();
     // ---- load, count per bucket; rank = arrival number inside the bucket (any order will do) ----
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    uint32_t code[kWpItems], row[kWpItems], rank[kWpItems];
+    uint32_t code[ITEMS], row[ITEMS], rank[ITEMS];
     if constexpr (SRC == 2) {
-        uint64_t c0[kWpItems];
+        uint64_t c0[ITEMS];
         uint32_t okm = 0;
 #pragma unroll
-        for (int j = 0; j < kWpItems / 4; j++) {
-            const uint32_t i4 = 4u * ((uint32_t)j * kWpThreads + t);
+        for (int j = 0; j < ITEMS / 4; j++) {
+            const uint32_t i4 = 4u * ((uint32_t)j * THREADS + t);
             if (i4 + 3 < m) {   // (the keys are 16-byte aligned: two 16-byte loads)
                 const u32x4 v0 = reinterpret_cast<const u32x4*>(a.keys + src0 + i4)[0], v1 = reinterpret_cast<const u32x4*>(a.keys + src0 + i4)[1];
                 c0[4 * j] = (uint64_t)v0.x | ((uint64_t)v0.y << 32);
@@ -113,20 +124,20 @@ __global__ __launch_bounds__(kWpThreads) void k_win_partition(WpArgs a) {
             for (int c = 0; c < 4; c++) row[4 * j + c] = a.row_base + (uint32_t)(t0 + i4 + c);
         }
         const uint32_t have = okm;
-        encode_rows_arith<kWpItems, uint32_t>(a.ap, c0, code, &okm);
+        encode_rows_arith<ITEMS, uint32_t>(a.ap, c0, code, &okm);
         bool bad = false;
 #pragma unroll
-        for (int k = 0; k < kWpItems; k++) {
+        for (int k = 0; k < ITEMS; k++) {
             const bool ok = ((okm >> k) & 1u) && code[k] < a.states;
             bad |= ((have >> k) & 1u) && !ok;   // a key the (sampled) alphabets cannot code: the build starts over
             code[k] = ok ? code[k] : kWinEmpty;
         }
         if (__ballot(bad) && lane_id() == 0) *a.flag = 1u;
     } else if constexpr (SRC == 1) {
-        const bool vec = m == (uint32_t)kWpTile && (((uintptr_t)(a.codes + src0)) & 15) == 0;
+        const bool vec = m == (uint32_t)TILE && (((uintptr_t)(a.codes + src0)) & 15) == 0;
 #pragma unroll
-        for (int j = 0; j < kWpItems / 4; j++) {
-            const uint32_t i4 = 4u * ((uint32_t)j * kWpThreads + t);
+        for (int j = 0; j < ITEMS / 4; j++) {
+            const uint32_t i4 = 4u * ((uint32_t)j * THREADS + t);
             uint32_t w[4];
             if (vec) {
                 const u32x4 v = reinterpret_cast<const u32x4*>(a.codes + src0)[i4 >> 2];
@@ -143,10 +154,10 @@ __global__ __launch_bounds__(kWpThreads) void k_win_partition(WpArgs a) {
             }
         }
     } else {
-        const bool vec = m == (uint32_t)kWpTile;   // (source buckets start at multiples of their capacity: 16-byte aligned)
+        const bool vec = m == (uint32_t)TILE;   // (source buckets start at multiples of their capacity: 16-byte aligned)
 #pragma unroll
-        for (int j = 0; j < kWpItems / 2; j++) {
-            const uint32_t i2 = 2u * ((uint32_t)j * kWpThreads + t);
+        for (int j = 0; j < ITEMS / 2; j++) {
+            const uint32_t i2 = 2u * ((uint32_t)j * THREADS + t);
             if (vec) {
                 const u32x4 v = reinterpret_cast<const u32x4*>(a.entries + src0)[i2 >> 1];
                 row[2 * j] = v.x; code[2 * j] = v.y; row[2 * j + 1] = v.z; code[2 * j + 1] = v.w;
@@ -161,21 +172,21 @@ __global__ __launch_bounds__(kWpThreads) void k_win_partition(WpArgs a) {
         }
     }
 #pragma unroll
-    for (int k = 0; k < kWpItems; k++) rank[k] = code[k] != kWinEmpty ? atomicAdd(&s_hist[code[k] >> a.shift], 1u) : 0u;
+    for (int k = 0; k < ITEMS; k++) rank[k] = code[k] != kWinEmpty ? atomicAdd(&s_hist[code[k] >> a.shift], 1u) : 0u;
     lds_atomics_barrier();
     // ---- tile-local starts (exclusive scan over the buckets) + room in the destination buckets ----
     uint32_t tot;
     {
-        const uint32_t per = nbp / kWpThreads;   // <= kWpMaxBuckets / kWpThreads
-        uint32_t h[kWpMaxBuckets / kWpThreads], sum = 0;
+        const uint32_t per = nbp / THREADS;   // <= kWpMaxBuckets / THREADS
+        uint32_t h[kWpMaxBuckets / THREADS], sum = 0;
 #pragma unroll
-        for (int k = 0; k < kWpMaxBuckets / kWpThreads; k++) {
+        for (int k = 0; k < kWpMaxBuckets / THREADS; k++) {
             h[k] = (uint32_t)k < per ? s_hist[t * per + k] : 0u;
             sum += h[k];
         }
-        uint32_t run = block_exclusive_sum<uint32_t, kWpThreads>(sum, s_tmp, &tot);
+        uint32_t run = block_exclusive_sum<uint32_t, THREADS>(sum, s_tmp, &tot);
 #pragma unroll
-        for (int k = 0; k < kWpMaxBuckets / kWpThreads; k++) {
+        for (int k = 0; k < kWpMaxBuckets / THREADS; k++) {
             if ((uint32_t)k < per) {
                 const uint32_t b = t * per + k;
                 s_start[b] = run;
@@ -187,27 +198,27 @@ __global__ __launch_bounds__(kWpThreads) void k_win_partition(WpArgs a) {
     __syncthreads();
     // ---- stage the tile's entries bucket by bucket ----
 #pragma unroll
-    for (int k = 0; k < kWpItems; k++)
+    for (int k = 0; k < ITEMS; k++)
         if (code[k] != kWinEmpty) s_ent[s_start[code[k] >> a.shift] + rank[k]] = ((uint64_t)code[k] << 32) | row[k];
     __syncthreads();
     // ---- write them out: consecutive threads, consecutive entries of one destination bucket ----
     const uint32_t cap = 1u << a.shift, mask = cap - 1u;
     bool over = false;
-    uint64_t e[kWpItems];
-    uint32_t pos[kWpItems];
+    uint64_t e[ITEMS];
+    uint32_t pos[ITEMS];
 #pragma unroll
-    for (int k = 0; k < kWpItems; k++) {
-        const uint32_t i = (uint32_t)k * kWpThreads + t;
+    for (int k = 0; k < ITEMS; k++) {
+        const uint32_t i = (uint32_t)k * THREADS + t;
         e[k] = s_ent[i < tot ? i : 0u];
     }
 #pragma unroll
-    for (int k = 0; k < kWpItems; k++) {
-        const uint32_t i = (uint32_t)k * kWpThreads + t;
+    for (int k = 0; k < ITEMS; k++) {
+        const uint32_t i = (uint32_t)k * THREADS + t;
         pos[k] = s_delta[i < tot ? (uint32_t)(e[k] >> 32) >> a.shift : 0u] + i;
     }
 #pragma unroll
-    for (int k = 0; k < kWpItems; k++) {
-        const uint32_t i = (uint32_t)k * kWpThreads + t;
+    for (int k = 0; k < ITEMS; k++) {
+        const uint32_t i = (uint32_t)k * THREADS + t;
         if (i < tot) {
             const uint32_t w = (uint32_t)(e[k] >> 32), b = w >> a.shift;
             if (pos[k] < cap) a.dst[(((uint64_t)sb * a.nb + b) << a.shift) + pos[k]] = ((uint64_t)(w & mask) << 32) | (uint32_t)e[k];
@@ -344,9 +355,14 @@ WindowSort::~WindowSort() {
     if (started && !finished && words) words->reset();
 }
 
-static size_t win_partition_lds(uint32_t nb) {
-    const uint32_t nbp = (nb + (uint32_t)kWpThreads - 1u) & ~((uint32_t)kWpThreads - 1u);
-    return (size_t)kWpTile * 8 + (size_t)nbp * 12;
+template <int SRC, int THREADS, int ITEMS>
+static Status win_partition_launch(cph_ctx* ctx, const WpArgs& a, unsigned grid, double bytes) {
+    const uint32_t nbp = (a.nb + (uint32_t)THREADS - 1u) & ~((uint32_t)THREADS - 1u);
+    const size_t lds = (size_t)THREADS * ITEMS * 8 + (size_t)nbp * 12;
+    CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(&k_win_partition<SRC, THREADS, ITEMS>), THREADS, lds, nullptr));
+    ProfScope ps(ctx, "k_win_partition", bytes);
+    hipLaunchKernelGGL((k_win_partition<SRC, THREADS, ITEMS>), dim3(grid), dim3(THREADS), lds, ctx->stream, a);
+    return {};
 }
 
 // rows [row0, row0 + m): codes[0] is row row0's code (keys != nullptr: keys[0] its 8-byte key, coded by *ap inside the pass)
@@ -365,15 +381,12 @@ Status WindowSort::add(cph_ctx* ctx, const uint32_t* codes, uint64_t row0, uint6
     a.states = (uint32_t)states;
     a.row_base = (uint32_t)row0;
     a.flag = flag;
-    const size_t lds = win_partition_lds(a.nb);
-    if (keys) {
-        CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(&k_win_partition<2>), kWpThreads, lds, nullptr));
-        ProfScope ps(ctx, "k_win_partition", 16.0 * (double)m);   // keys in (8), entries out (8)
-        hipLaunchKernelGGL(k_win_partition<2>, dim3(a.tiles_per_src), dim3(kWpThreads), lds, ctx->stream, a);
+    if (keys) {   // keys in (8), entries out (8)
+        if (two) CPH_TRY((win_partition_launch<2, kWpThreads, kWpItems>(ctx, a, a.tiles_per_src, 16.0 * (double)m)));
+        else CPH_TRY((win_partition_launch<2, kWpThreadsOneLevel, kWpItemsOneLevel>(ctx, a, a.tiles_per_src, 16.0 * (double)m)));
     } else {
-        CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(&k_win_partition<1>), kWpThreads, lds, nullptr));
-        ProfScope ps(ctx, "k_win_partition", 12.0 * (double)m);
-        hipLaunchKernelGGL(k_win_partition<1>, dim3(a.tiles_per_src), dim3(kWpThreads), lds, ctx->stream, a);
+        if (two) CPH_TRY((win_partition_launch<1, kWpThreads, kWpItems>(ctx, a, a.tiles_per_src, 12.0 * (double)m)));
+        else CPH_TRY((win_partition_launch<1, kWpThreadsOneLevel, kWpItemsOneLevel>(ctx, a, a.tiles_per_src, 12.0 * (double)m)));
     }
     CPH_HIP_TRY(hipGetLastError());
     return {};
@@ -395,10 +408,7 @@ Status WindowSort::finish(cph_ctx* ctx, uint32_t* perm_out, uint32_t* sorted_out
         a.dst = ent2.as<uint64_t>();
         a.dst_count = cur2;
         a.flag = flag;
-        const size_t lds = win_partition_lds(a.nb);
-        CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(&k_win_partition<0>), kWpThreads, lds, nullptr));
-        ProfScope ps(ctx, "k_win_partition", 16.0 * (double)n);
-        hipLaunchKernelGGL(k_win_partition<0>, dim3((unsigned)(nb1 * a.tiles_per_src)), dim3(kWpThreads), lds, ctx->stream, a);
+        CPH_TRY((win_partition_launch<0, kWpThreads, kWpItems>(ctx, a, (unsigned)(nb1 * a.tiles_per_src), 16.0 * (double)n)));
         CPH_HIP_TRY(hipGetLastError());
     }
     uint32_t* counts = two ? cur2 : cur1;
