@@ -531,6 +531,8 @@ static Status enter(cph_ctx* ctx) {
 // trips: (1) stage the columns, enqueue the alphabet statistics  | sync: statistics of every index |
 // (2) codec on the host, encode + sort + adjacent-equal scan enqueued  | sync: first duplicate of every index |
 // (3) table decision.
+// In a two-stream batch sync 1 is taken per stream: the jobs of the main stream run their phase 2 as soon as that stream has
+// delivered, the side stream's jobs behind its own synchronisation (build_run).
 struct BuildJob {
     cph_index* ix = nullptr;
     int32_t nkeycols = 0;
@@ -608,9 +610,22 @@ static void build_run(cph_ctx* ctx, std::vector<BuildJob>& jobs, std::vector<Sta
         total = (total + 63) & ~(size_t)63;
         if (status[i].ok() && !jobs[i].small) any_general = true;
     }
-    Status s = ensure_pinned_scratch(ctx, total > 64 ? total : 64);
+    bool any_side = false;
+    for (size_t i = 0; i < nj; i++) any_side = any_side || jobs[i].side;
+    // Two streams: phase 2 of the main stream's jobs runs while the side stream's read-backs are still on their way, and phase 2
+    // may use (and grow) ctx->pinned_scratch — the batch's read-backs then land in a block of their own.
+    struct ReadbackBlock {
+        cph_ctx* c;
+        void* p = nullptr;
+        size_t cap = 0;
+        bool settled = false;   // every stream that writes into the block has been synchronised
+        // (a return in between, after a failed synchronisation: copies may still be on their way — the block is not handed on)
+        ~ReadbackBlock() { if (settled) pinned_cache_put(c, p, cap); }
+    } rb{ctx};
+    Status s = any_side ? pinned_cache_get(ctx, result_block_bytes(total > 64 ? total : 64), &rb.p, &rb.cap)
+                        : ensure_pinned_scratch(ctx, total > 64 ? total : 64);
     if (!s.ok()) return fail_all(s);
-    uint8_t* h = static_cast<uint8_t*>(ctx->pinned_scratch);
+    uint8_t* h = static_cast<uint8_t*>(any_side ? rb.p : ctx->pinned_scratch);
     for (size_t i = 0; i < nj; i++) {
         if (!status[i].ok()) continue;
         if (jobs[i].small) {
@@ -624,39 +639,47 @@ static void build_run(cph_ctx* ctx, std::vector<BuildJob>& jobs, std::vector<Sta
                                       hipMemcpyDeviceToHost, jobs[i].side ? ctx->side_stream : ctx->stream);
         if (e != hipSuccess) status[i] = {CPH_ERR_HIP, std::string("statistics read-back: ") + hipGetErrorString(e)};
     }
-    bool any_side = false;
-    for (size_t i = 0; i < nj; i++) any_side = any_side || jobs[i].side;
     auto sync_streams = [&]() {
         return hipStreamSynchronize(ctx->stream) == hipSuccess && (!any_side || hipStreamSynchronize(ctx->side_stream) == hipSuccess);
     };
-    if (!sync_streams()) return fail_all({CPH_ERR_HIP, "hipStreamSynchronize failed"});
-    ctx->pool.flush_deferred();   // every stream that carries work of this batch is idle: parked blocks may change hands
-    // the host copies must survive phase 2 (which may reuse the scratch): take them out
+    // Per stream: a job's phase 2 needs what ITS stream brought to the host and nothing of the other's, so the main stream's jobs
+    // are on their way again before the host waits for the side stream (and a read-back is consumed only behind the
+    // synchronisation of the stream that carries it).
     std::vector<std::vector<uint8_t>> stats_host(nj);
     std::vector<size_t> retry;   // small-table candidates whose key needs the general path after all
-    for (size_t i = 0; i < nj; i++) {
-        if (!status[i].ok()) continue;
-        if (jobs[i].small) {
-            const SmallResult res = *reinterpret_cast<const SmallResult*>(h + jobs[i].scratch_off);
-            bool not_small = false;
-            status[i] = small_build_finish(ctx, jobs[i].ix, jobs[i].nkeycols, &jobs[i].sbufs, &res, &not_small);
-            jobs[i].sbufs = SmallBufs{};
-            if (status[i].ok() && not_small) retry.push_back(i);
-            else if (status[i].ok()) index_plan_table(jobs[i].ix);
-            continue;
+    for (int on = 0; on < (any_side ? 2 : 1); on++) {
+        if (hipStreamSynchronize(on ? ctx->side_stream : ctx->stream) != hipSuccess) return fail_all({CPH_ERR_HIP, "hipStreamSynchronize failed"});
+        // One stream: it is idle, parked blocks may change hands.  Two: there is no moment between the phases at which both are
+        // idle any more (the main stream's phase 2 is enqueued while the side stream still runs its phase 1), so the blocks
+        // parked so far wait for the flush behind sync 2.
+        if (!any_side) ctx->pool.flush_deferred();
+        // the host copies must survive phase 2 (which may reuse the scratch): take them out
+        for (size_t i = 0; i < nj; i++) {
+            if (!status[i].ok() || jobs[i].side != (on != 0)) continue;
+            if (jobs[i].small) {
+                const SmallResult res = *reinterpret_cast<const SmallResult*>(h + jobs[i].scratch_off);
+                bool not_small = false;
+                status[i] = small_build_finish(ctx, jobs[i].ix, jobs[i].nkeycols, &jobs[i].sbufs, &res, &not_small);
+                jobs[i].sbufs = SmallBufs{};
+                if (status[i].ok() && not_small) retry.push_back(i);
+                else if (status[i].ok()) index_plan_table(jobs[i].ix);
+                continue;
+            }
+            if (jobs[i].sampled) {
+                const uint8_t* sh = static_cast<const uint8_t*>(jobs[i].sample_host);
+                stats_host[i].assign(sh, sh + codec_sample_bytes());
+            } else if (!jobs[i].presplit) {
+                stats_host[i].assign(h + jobs[i].scratch_off, h + jobs[i].scratch_off + job_readback_bytes(jobs[i]));
+            }
         }
-        if (jobs[i].sampled) {
-            const uint8_t* sh = static_cast<const uint8_t*>(jobs[i].sample_host);
-            stats_host[i].assign(sh, sh + codec_sample_bytes());
-        } else if (!jobs[i].presplit) {
-            stats_host[i].assign(h + jobs[i].scratch_off, h + jobs[i].scratch_off + job_readback_bytes(jobs[i]));
-        }
+        for (size_t i = 0; i < nj; i++)
+            if (status[i].ok() && !jobs[i].small && jobs[i].side == (on != 0)) {
+                SideStream on_side(ctx, jobs[i].side);
+                status[i] = build_phase2(ctx, &jobs[i], stats_host[i].data());
+            }
     }
-    for (size_t i = 0; i < nj; i++)
-        if (status[i].ok() && !jobs[i].small) {
-            SideStream on_side(ctx, jobs[i].side);
-            status[i] = build_phase2(ctx, &jobs[i], stats_host[i].data());
-        }
+    rb.settled = true;
+    std::sort(retry.begin(), retry.end());   // (the order in which the small builds are tried again stays the jobs' order)
     // ---- sync 2: first duplicates ----
     std::vector<size_t> resplit;   // jobs whose split codec met a row it could not code: once more without the split
     std::vector<size_t> resort;    // jobs whose counted window sort met a window beyond its capacity: the classic passes over the same codes
@@ -941,7 +964,6 @@ static Status build_encode_sort(cph_ctx* ctx, BuildJob* job) {
 
     DevBuf va, vb;
     CPH_TRY(va.alloc(&ctx->pool, n * sizeof(uint32_t)));
-    CPH_TRY(vb.alloc(&ctx->pool, n * sizeof(uint32_t)));
     int passes = 0;
 
     if (cd.nwords == 1) {
@@ -949,14 +971,12 @@ static Status build_encode_sort(cph_ctx* ctx, BuildJob* job) {
         const size_t kb_ = cd.key32 ? sizeof(uint32_t) : sizeof(uint64_t);
         DevBuf ka, kb, counts;
         CPH_TRY(ka.alloc(&ctx->pool, n * kb_));
-        CPH_TRY(kb.alloc(&ctx->pool, n * kb_));
-        const RadixPlan plan = radix_plan(ctx, n, cd.word_bits[0]);
         EncodeHist eh;
         // distinct keys expected over a dense code space: slot[code] = row instead of radix passes (window_sort.hip)
         const uint64_t states = cd.word_states[0];
         const bool direct = job->unique && !job->no_direct && ctx->direct_sort != 0 && cd.key32 && !job->spec.active && n >= (1ull << 16) &&
                             states >= n && states <= 2 * n && states < 0xFFFFFFFFull;
-        if (direct) {
+        if (direct) {   // (writes va and ka alone: the second pair of buffers is not allocated)
             if (!job->miss) {
                 CPH_TRY(job_arm_miss(ctx, job));
             }
@@ -994,11 +1014,11 @@ static Status build_encode_sort(cph_ctx* ctx, BuildJob* job) {
         }
         // duplicates allowed, 32-bit codes, a window of the code space holds a few thousand rows: MSD sort through counted LDS windows
         // (counted_sort.hip) instead of 3-4 classic passes; the adjacent-equal scan falls out of it
+        CPH_TRY(kb.alloc(&ctx->pool, n * kb_));
         CountedSortPlan csp;
         if (cd.key32 && !job->spec.active && counted_sort_plan(ctx, n, states, &csp)) {
             uint32_t* over = host_word(ctx);
             if (!over) return {CPH_ERR_HIP, "no pinned host memory for the report words of a build"};
-            vb.reset();
             CountedSort cs;
             CPH_TRY(cs.begin(ctx, csp, n));
             CPH_TRY(codec_encode_build(ctx, cd, ix->codec_dev, dcols, n, ka.get(), &eh, &job->spec, job->miss));
@@ -1011,6 +1031,8 @@ static Status build_encode_sort(cph_ctx* ctx, BuildJob* job) {
             ix->sort_passes = 0;
             return {};
         }
+        CPH_TRY(vb.alloc(&ctx->pool, n * sizeof(uint32_t)));
+        const RadixPlan plan = radix_plan(ctx, n, cd.word_bits[0]);
         if (plan.npass > 0) {
             CPH_TRY(counts.alloc(&ctx->pool, plan.count_words() * sizeof(uint32_t)));
             eh.tile_rows = plan.tile;
@@ -1056,6 +1078,7 @@ static Status build_encode_sort(cph_ctx* ctx, BuildJob* job) {
     } else {
         // multi-word codes: LSD over the words, least significant word first
         DevBuf all;
+        CPH_TRY(vb.alloc(&ctx->pool, n * sizeof(uint32_t)));
         CPH_TRY(all.alloc(&ctx->pool, (size_t)cd.nwords * n * sizeof(uint64_t)));
         CPH_TRY(codec_encode_build(ctx, cd, ix->codec_dev, dcols, n, all.get(), nullptr, nullptr, job->miss));
         CPH_TRY(sort_words_lsd(ctx, ix, all.as<uint64_t>(), cd.nwords, cd.word_bits, n, va, vb));

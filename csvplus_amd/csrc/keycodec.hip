@@ -1516,7 +1516,7 @@ Status codec_sample_launch(cph_ctx* ctx, const DevCol& col, uint64_t n, const vo
     ProfScope ps(ctx, "k_split_count", 0);
     uint64_t nblk = (nsel + kSplitThreads - 1) / kSplitThreads;
     if (nblk > 1024) nblk = 1024;
-    if (col.fixed_width <= 8)
+    if (col.fixed_width >= 1 && col.fixed_width <= 8)
         hipLaunchKernelGGL(k_sample_fixed8, dim3((unsigned)std::min<uint64_t>(nblk, (uint64_t)kFixed8Blocks)), dim3(kSplitThreads), 0, ctx->stream, col, step, nsel, acc.as<SplitSample>(),
                            reinterpret_cast<SplitSample*>(hw));
     else

@@ -270,10 +270,26 @@ __global__ __launch_bounds__(kPlaceThreads) void k_win_place(const uint64_t* __r
         counts[g] = 0u;
         if (g < nclear) clear_also[g] = 0u;
     }
-    const uint64_t* src = entries + ((uint64_t)g << kWinBits);
-    for (uint32_t i = t; i < cnt; i += kPlaceThreads) {
-        const uint64_t e = src[i];
-        win[(uint32_t)(e >> 32) & (kWinSlots - 1u)] = (uint32_t)e;
+    // The window's entries, two per 16-byte load {row, code, row, code} (the bucket starts at a multiple of 2^14 entries: aligned),
+    // kPlaceLoads loads per thread in flight before the first is used.  A pair past the last one reads the last one again: every
+    // read stays inside entries [0, cnt) of the window's own bucket, rounded up to a pair (the bucket has room for 2^14), and
+    // only entries below cnt are stored to LDS.
+    constexpr uint32_t kPlaceLoads = 4, kRound = 2u * kPlaceLoads * kPlaceThreads;   // entries per round
+    const u32x4* src = reinterpret_cast<const u32x4*>(entries + ((uint64_t)g << kWinBits));
+    const uint32_t lastp = cnt ? (cnt - 1u) >> 1 : 0u;
+    for (uint32_t base = 0; base < cnt; base += kRound) {
+        u32x4 v[kPlaceLoads];
+#pragma unroll
+        for (uint32_t k = 0; k < kPlaceLoads; k++) {
+            const uint32_t p = (base >> 1) + k * kPlaceThreads + t;
+            v[k] = src[p < lastp ? p : lastp];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kPlaceLoads; k++) {
+            const uint32_t i = base + 2u * (k * kPlaceThreads + t);
+            if (i < cnt) win[v[k].y & (kWinSlots - 1u)] = v[k].x;
+            if (i + 1u < cnt) win[v[k].w & (kWinSlots - 1u)] = v[k].z;   // (an odd cnt: the last pair's second entry is stale)
+        }
     }
     __syncthreads();
     // every wave owns a contiguous stretch of the window: count, exchange, write
