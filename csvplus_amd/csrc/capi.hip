@@ -300,7 +300,7 @@ Status pinned_cache_get(cph_ctx* ctx, size_t bytes, void** out, size_t* cap) {
 
 // result blocks of per-batch calls: sizes rounded up to a power of two (>= 64 KB) so that consecutive batches find each other's block
 // — up to 4 MB; a larger result takes what it needs rounded to 2 MB (a 1.6 GB result used to page-lock 2 GiB, 2.1 GB 4 GiB)
-static size_t result_block_bytes(size_t need) {
+size_t result_block_bytes(size_t need) {
     constexpr size_t kSmall = 4u << 20, kStep = 2u << 20;
     if (need > kSmall) return (need + kStep - 1) / kStep * kStep;
     size_t b = 64 * 1024;
@@ -526,582 +526,10 @@ static Status enter(cph_ctx* ctx) {
     return {};
 }
 
-// ---- IndexOn ------------------------------------------------------------------------------------
-// One index build in three phases, so that a batch of builds (cph_index_build_many) shares its two host round
-// trips: (1) stage the columns, enqueue the alphabet statistics  | sync: statistics of every index |
-// (2) codec on the host, encode + sort + adjacent-equal scan enqueued  | sync: first duplicate of every index |
-// (3) table decision.
-// In a two-stream batch sync 1 is taken per stream: the jobs of the main stream run their phase 2 as soon as that stream has
-// delivered, the side stream's jobs behind its own synchronisation (build_run).
-struct BuildJob {
-    cph_index* ix = nullptr;
-    int32_t nkeycols = 0;
-    std::vector<DevBuf> staged;
-    DevCol dcols[kMaxKeyCols];
-    DevBuf stats_dev;
-    const void* sample_host = nullptr;   // sampled: where the sample kernel itself leaves its result (report words of the ctx: no read-back copy)
-    size_t scratch_off = 0;      // where this job's read-backs land in ctx->pinned_scratch
-    GroupSpec spec;              // speculative dictionaries (codec_try_groups)
-    bool small = false;          // one-launch build (small_build.hip): no statistics pass, no second synchronisation
-    SmallBufs sbufs;
-    bool presplit = false;       // a large single-column table whose split codec was built from a sample + one exact pass BEFORE any plain
-                                 // statistics (build_phase1): no statistics pass at all
-    bool sampled = false;        // alphabets from a sample of the rows (keycodec.hip: codec_sample_*): the encode kernel checks every row, a
-                                 // miss (BuildJob::miss) starts the build over with the exact statistics pass
-    bool no_sample = false;
-    bool unique = false;         // the caller expects distinct keys (UniqueIndexOn): the optimistic direct sort may be tried
-    bool no_direct = false;
-    bool side = false;           // this job's work is enqueued on the ctx's side stream (cph_index_build_many: it overlaps its neighbour's)
-    bool spec_split = false;     // presplit from the SAMPLE alone (codec_try_split speculate): a miss starts over with the exact split statistics
-    bool exact_split = false;    // ... that second attempt
-    bool no_split = false;       // second attempt after a split codec met a row it could not code (keycodec.hip: codec_try_split)
-    uint32_t* miss = nullptr;    // report word (pinned host memory, host_word) raised by the encode kernel of a split / sampled codec and by the
-                                 // optimistic direct sort; read after the build's last synchronisation
-    uint32_t* cs_over = nullptr; // counted window sort (counted_sort.hip): report word raised when a window does not fit — nothing was sorted then,
-    DevBuf cs_codes;             // ... and the classic passes run over these (untouched) codes after the build's last synchronisation
-};
-
-static Status build_phase1(cph_ctx* ctx, const cph_strcol* keycols, int32_t nkeycols, BuildJob* job) {
-    CPH_TRY(validate_cols(keycols, nkeycols));
-    cph_index* ix = job->ix;
-    ix->ctx = ctx;
-    ix->nrows = keycols[0].nrows;
-    ix->table_rows = ix->nrows;
-    ix->nkeycols = nkeycols;
-    job->nkeycols = nkeycols;
-    CPH_TRY(stage_cols(ctx, keycols, nkeycols, &job->staged, job->dcols));
-    job->small = small_build_applies(ctx, job->dcols, nkeycols, ix->nrows);   // launched by build_run (needs its result slot)
-    // "sample first": a large table over ONE variable-length key column asks a sample whether its keys want the delimiter split
-    // (keycodec.hip); when they do, the exact split statistics replace the plain statistics pass (one read of the strings less)
-    if (!job->small && !job->no_split && nkeycols == 1 && !job->dcols[0].fixed_width && ix->nrows >= (1ull << 22)) {
-        CPH_TRY(codec_try_split(ctx, job->dcols, 1, ix->nrows, nullptr, &ix->codec, !job->exact_split, &job->spec_split));
-        job->presplit = ix->codec.has_split();
-    }
-    job->sampled = !job->small && !job->presplit && !job->no_sample && codec_sample_applies(ctx, job->dcols, nkeycols, ix->nrows);
-    if (job->sampled) CPH_TRY(codec_sample_launch(ctx, job->dcols[0], ix->nrows, &job->sample_host));
-    else if (!job->small && !job->presplit) CPH_TRY(codec_stats_launch(ctx, job->dcols, nkeycols, &job->stats_dev));   // K0: alphabets
-    return {};
-}
-
-static Status build_phase2(cph_ctx* ctx, BuildJob* job, const void* stats_host);
-static Status job_arm_miss(cph_ctx* ctx, BuildJob* job) {
-    job->miss = host_word(ctx);
-    return job->miss ? Status{} : Status{CPH_ERR_HIP, "no pinned host memory for the report words of a build"};
-}
-static Status build_encode_sort(cph_ctx* ctx, BuildJob* job);
-
-static size_t job_readback_bytes(const BuildJob& j) {   // what sync 1 brings to the host for this job
-    return j.small ? sizeof(SmallResult) : (j.presplit || j.sampled) ? 0 : sizeof(ColStats) * (size_t)j.nkeycols;
-}
-
-// Runs a batch of jobs whose phase 1 succeeded (ok[i]); status[i] receives each job's outcome.
-static void build_run(cph_ctx* ctx, std::vector<BuildJob>& jobs, std::vector<Status>& status) {
-    const size_t nj = jobs.size();
-    auto fail_all = [&](const Status& s) {
-        for (size_t i = 0; i < nj; i++)
-            if (status[i].ok()) status[i] = s;
-    };
-    // ---- sync 1: statistics (general path) / the whole result (one-launch builds of small tables) ----
-    size_t total = 0;
-    bool any_general = false;
-    for (size_t i = 0; i < nj; i++) {
-        jobs[i].scratch_off = total;
-        total += job_readback_bytes(jobs[i]);
-        total = (total + 63) & ~(size_t)63;
-        if (status[i].ok() && !jobs[i].small) any_general = true;
-    }
-    bool any_side = false;
-    for (size_t i = 0; i < nj; i++) any_side = any_side || jobs[i].side;
-    // Two streams: phase 2 of the main stream's jobs runs while the side stream's read-backs are still on their way, and phase 2
-    // may use (and grow) ctx->pinned_scratch — the batch's read-backs then land in a block of their own.
-    struct ReadbackBlock {
-        cph_ctx* c;
-        void* p = nullptr;
-        size_t cap = 0;
-        bool settled = false;   // every stream that writes into the block has been synchronised
-        // (a return in between, after a failed synchronisation: copies may still be on their way — the block is not handed on)
-        ~ReadbackBlock() { if (settled) pinned_cache_put(c, p, cap); }
-    } rb{ctx};
-    Status s = any_side ? pinned_cache_get(ctx, result_block_bytes(total > 64 ? total : 64), &rb.p, &rb.cap)
-                        : ensure_pinned_scratch(ctx, total > 64 ? total : 64);
-    if (!s.ok()) return fail_all(s);
-    uint8_t* h = static_cast<uint8_t*>(any_side ? rb.p : ctx->pinned_scratch);
-    for (size_t i = 0; i < nj; i++) {
-        if (!status[i].ok()) continue;
-        if (jobs[i].small) {
-            SideStream on_side(ctx, jobs[i].side);   // (its columns were staged on that stream)
-            status[i] = small_build_launch(ctx, jobs[i].dcols, jobs[i].nkeycols, jobs[i].ix->nrows, &jobs[i].sbufs,
-                                           reinterpret_cast<SmallResult*>(h + jobs[i].scratch_off));
-            continue;
-        }
-        if (jobs[i].presplit || jobs[i].sampled) continue;   // (a sample's result is written to the host by its kernel)
-        hipError_t e = hipMemcpyAsync(h + jobs[i].scratch_off, jobs[i].stats_dev.get(), job_readback_bytes(jobs[i]),
-                                      hipMemcpyDeviceToHost, jobs[i].side ? ctx->side_stream : ctx->stream);
-        if (e != hipSuccess) status[i] = {CPH_ERR_HIP, std::string("statistics read-back: ") + hipGetErrorString(e)};
-    }
-    auto sync_streams = [&]() {
-        return hipStreamSynchronize(ctx->stream) == hipSuccess && (!any_side || hipStreamSynchronize(ctx->side_stream) == hipSuccess);
-    };
-    // Per stream: a job's phase 2 needs what ITS stream brought to the host and nothing of the other's, so the main stream's jobs
-    // are on their way again before the host waits for the side stream (and a read-back is consumed only behind the
-    // synchronisation of the stream that carries it).
-    std::vector<std::vector<uint8_t>> stats_host(nj);
-    std::vector<size_t> retry;   // small-table candidates whose key needs the general path after all
-    for (int on = 0; on < (any_side ? 2 : 1); on++) {
-        if (hipStreamSynchronize(on ? ctx->side_stream : ctx->stream) != hipSuccess) return fail_all({CPH_ERR_HIP, "hipStreamSynchronize failed"});
-        // One stream: it is idle, parked blocks may change hands.  Two: there is no moment between the phases at which both are
-        // idle any more (the main stream's phase 2 is enqueued while the side stream still runs its phase 1), so the blocks
-        // parked so far wait for the flush behind sync 2.
-        if (!any_side) ctx->pool.flush_deferred();
-        // the host copies must survive phase 2 (which may reuse the scratch): take them out
-        for (size_t i = 0; i < nj; i++) {
-            if (!status[i].ok() || jobs[i].side != (on != 0)) continue;
-            if (jobs[i].small) {
-                const SmallResult res = *reinterpret_cast<const SmallResult*>(h + jobs[i].scratch_off);
-                bool not_small = false;
-                status[i] = small_build_finish(ctx, jobs[i].ix, jobs[i].nkeycols, &jobs[i].sbufs, &res, &not_small);
-                jobs[i].sbufs = SmallBufs{};
-                if (status[i].ok() && not_small) retry.push_back(i);
-                else if (status[i].ok()) index_plan_table(jobs[i].ix);
-                continue;
-            }
-            if (jobs[i].sampled) {
-                const uint8_t* sh = static_cast<const uint8_t*>(jobs[i].sample_host);
-                stats_host[i].assign(sh, sh + codec_sample_bytes());
-            } else if (!jobs[i].presplit) {
-                stats_host[i].assign(h + jobs[i].scratch_off, h + jobs[i].scratch_off + job_readback_bytes(jobs[i]));
-            }
-        }
-        for (size_t i = 0; i < nj; i++)
-            if (status[i].ok() && !jobs[i].small && jobs[i].side == (on != 0)) {
-                SideStream on_side(ctx, jobs[i].side);
-                status[i] = build_phase2(ctx, &jobs[i], stats_host[i].data());
-            }
-    }
-    rb.settled = true;
-    std::sort(retry.begin(), retry.end());   // (the order in which the small builds are tried again stays the jobs' order)
-    // ---- sync 2: first duplicates ----
-    std::vector<size_t> resplit;   // jobs whose split codec met a row it could not code: once more without the split
-    std::vector<size_t> resort;    // jobs whose counted window sort met a window beyond its capacity: the classic passes over the same codes
-    if (any_general) {
-        s = ensure_pinned_scratch(ctx, 2 * sizeof(uint32_t) * nj + 64);
-        if (!s.ok()) return fail_all(s);
-        uint32_t* fd = static_cast<uint32_t*>(ctx->pinned_scratch);
-        uint32_t* sm = fd + nj;
-        for (size_t i = 0; i < nj; i++) {
-            if (!status[i].ok() || jobs[i].small) continue;
-            hipStream_t js = jobs[i].side ? ctx->side_stream : ctx->stream;
-            fd[i] = 0xFFFFFFFFu;   // no adjacent-equal scan ran (the direct sort): distinct keys, or the miss word sends the build round again
-            sm[i] = 0;
-            if (!jobs[i].ix->first_dup_dev) continue;
-            hipError_t e = hipMemcpyAsync(&fd[i], jobs[i].ix->first_dup_dev.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, js);
-            if (e != hipSuccess) status[i] = {CPH_ERR_HIP, std::string("first-duplicate read-back: ") + hipGetErrorString(e)};
-        }
-        if (!sync_streams()) return fail_all({CPH_ERR_HIP, "hipStreamSynchronize failed"});
-        ctx->pool.flush_deferred();
-        for (size_t i = 0; i < nj; i++) {
-            if (!status[i].ok() || jobs[i].small) continue;
-            cph_index* ix = jobs[i].ix;
-            if (jobs[i].miss) sm[i] = *(volatile uint32_t*)jobs[i].miss;   // written by the kernels themselves (pinned host memory)
-            if (sm[i]) { jobs[i].cs_codes.reset(); jobs[i].cs_over = nullptr; resplit.push_back(i); continue; }
-            if (jobs[i].cs_over && *(volatile uint32_t*)jobs[i].cs_over) { resort.push_back(i); continue; }
-            jobs[i].cs_codes.reset();
-            ix->first_dup = fd[i] != 0xFFFFFFFFu ? (uint64_t)fd[i] : UINT64_MAX;
-            ix->first_dup_dev.reset();
-            index_plan_table(ix);
-        }
-    }
-    for (size_t i : resort) {   // (both streams are idle here; the codes the encode kernel wrote are untouched)
-        BuildJob& j = jobs[i];
-        cph_index* ix = j.ix;
-        const uint64_t n = ix->nrows;
-        uint32_t* over = j.cs_over;
-        j.cs_over = nullptr;
-        ix->sorted_codes.reset(); ix->perm.reset(); ix->first_dup_dev.reset();
-        DevBuf kb, va, vb;
-        Status r = kb.alloc(&ctx->pool, n * sizeof(uint32_t));
-        if (r.ok()) r = va.alloc(&ctx->pool, n * sizeof(uint32_t));
-        // the rows cluster (a dense block in a sparse code space: the plan went by the average): windows a quarter as wide, then a
-        // sixteenth, before the classic passes — a retry costs the histogram + one wait (0.1 ms per 1e8 rows), the classic sort 2 ms
-        bool sorted_now = false;
-        {
-            CountedSortPlan first;
-            int wb = counted_sort_plan(ctx, n, ix->codec.word_states[0], &first) ? (int)first.wbits : 0;
-            for (int attempt = 0; attempt < 2 && r.ok() && !sorted_now && wb > 0; attempt++) {
-                wb -= 2;
-                CountedSortPlan csp;
-                if (!counted_sort_plan(ctx, n, ix->codec.word_states[0], &csp, wb) || (int)csp.wbits != wb) break;
-                r = ix->first_dup_dev.alloc(&ctx->pool, sizeof(uint32_t));
-                if (r.ok()) r = counted_sort(ctx, csp, j.cs_codes.as<uint32_t>(), n, ix->codec.word_states[0], va.as<uint32_t>(), kb.as<uint32_t>(),
-                                             ix->first_dup_dev.as<uint32_t>(), over);
-                if (r.ok() && hipStreamSynchronize(ctx->stream) != hipSuccess) r = {CPH_ERR_HIP, "hipStreamSynchronize failed"};
-                if (r.ok() && *(volatile uint32_t*)over == 0) {
-                    ix->sorted_codes = std::move(kb);
-                    ix->perm = std::move(va);
-                    ix->sort_passes = 0;
-                    r = index_first_dup_read(ctx, ix);
-                    sorted_now = true;
-                } else {
-                    ix->first_dup_dev.reset();
-                }
-            }
-        }
-        if (sorted_now) {
-            j.cs_codes.reset();
-            if (r.ok()) index_plan_table(ix);
-            status[i] = r;
-            continue;
-        }
-        if (r.ok()) r = vb.alloc(&ctx->pool, n * sizeof(uint32_t));
-        uint32_t *kout = nullptr, *vout = nullptr;
-        int passes = 0;
-        if (r.ok()) r = radix_sort_pairs<uint32_t>(ctx, j.cs_codes.as<uint32_t>(), kb.as<uint32_t>(), va.as<uint32_t>(), vb.as<uint32_t>(), true, n,
-                                                   ix->codec.word_bits[0], &kout, &vout, &passes);
-        if (r.ok()) {
-            ix->sorted_codes = std::move(kout == j.cs_codes.as<uint32_t>() ? j.cs_codes : kb);
-            ix->perm = std::move(vout == va.as<uint32_t>() ? va : vb);
-            ix->sort_passes = passes;
-            r = index_first_dup_launch(ctx, ix);
-        }
-        if (r.ok()) r = index_first_dup_read(ctx, ix);
-        j.cs_codes.reset();
-        if (r.ok()) index_plan_table(ix);
-        status[i] = r;
-    }
-    for (size_t i : resplit) {
-        std::vector<BuildJob> one;
-        one.push_back(std::move(jobs[i]));
-        std::vector<Status> st1(1);
-        BuildJob& j = one[0];
-        j.side = false;   // (both streams are idle here: the second attempt runs on the ctx's own)
-        const bool again_exact = j.spec_split;   // the sample's split codec met a row it could not code: the exact split statistics next
-        j.spec_split = false;
-        j.exact_split = again_exact;
-        j.no_split = !again_exact;
-        j.no_sample = true;
-        j.sampled = false;
-        j.no_direct = true;
-        j.presplit = false;
-        j.miss = nullptr;
-        cph_index* ix = j.ix;
-        ix->codec = CodecHost{};
-        ix->codec_dev.reset(); ix->sorted_codes.reset(); ix->perm.reset(); ix->first_dup_dev.reset(); ix->ranktab.reset();
-        if (again_exact) {
-            ctx->n_split_respec++;
-            st1[0] = codec_try_split(ctx, j.dcols, 1, ix->nrows, nullptr, &ix->codec, false, nullptr);
-            j.presplit = st1[0].ok() && ix->codec.has_split();
-        }
-        if (st1[0].ok() && !j.presplit) st1[0] = codec_stats_launch(ctx, j.dcols, j.nkeycols, &j.stats_dev);
-        if (st1[0].ok()) build_run(ctx, one, st1);
-        status[i] = st1[0];
-        jobs[i] = std::move(one[0]);
-    }
-    // keys the one-workgroup build could not take (more than kSmallMaxPos byte positions, codes of several words)
-    for (size_t i : retry) {
-        std::vector<BuildJob> one;
-        one.push_back(std::move(jobs[i]));
-        std::vector<Status> st1(1);
-        one[0].small = false;
-        one[0].side = false;
-        st1[0] = codec_stats_launch(ctx, one[0].dcols, one[0].nkeycols, &one[0].stats_dev);
-        if (st1[0].ok()) build_run(ctx, one, st1);
-        status[i] = st1[0];
-        jobs[i] = std::move(one[0]);
-    }
-    // staged input copies are released with the jobs (stream-ordered reuse is safe)
-}
-
-// Stable LSD sort over `nw` 64-bit code words per row (all[w][n], word 0 most significant; bits[w] significant
-// bits each): least significant word first, the later words gathered through the permutation so far.  Leaves the
-// sorted words (word-major) and the permutation in the index.
-static Status sort_words_lsd(cph_ctx* ctx, cph_index* ix, const uint64_t* all, int nw, const int* bits, uint64_t n, DevBuf& va,
-                             DevBuf& vb) {
-    DevBuf ka, kb;
-    CPH_TRY(ka.alloc(&ctx->pool, n * sizeof(uint64_t)));
-    CPH_TRY(kb.alloc(&ctx->pool, n * sizeof(uint64_t)));
-    uint32_t* vcur = va.as<uint32_t>();
-    uint32_t* vother = vb.as<uint32_t>();
-    uint64_t* kout = ka.as<uint64_t>();
-    bool first = true;
-    int passes = 0;
-    ix->sort_passes = 0;
-    for (int w = nw - 1; w >= 0; w--) {
-        const uint64_t* word = all + (uint64_t)w * n;
-        if (first) {
-            if (n) CPH_HIP_TRY(hipMemcpyAsync(ka.get(), word, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-        } else {
-            CPH_TRY(gather_u64(ctx, word, vcur, ka.as<uint64_t>(), n));
-        }
-        uint32_t* vout;
-        CPH_TRY(radix_sort_pairs<uint64_t>(ctx, ka.as<uint64_t>(), kb.as<uint64_t>(), vcur, vother, first, n, bits[w], &kout, &vout,
-                                           &passes));
-        ix->sort_passes += passes;
-        if (vout != vcur) { vother = vcur; vcur = vout; }
-        first = false;
-    }
-    // sorted codes, word-major: word 0 is the key output of the last sort (a streaming copy);
-    // only the less significant words need a gather through the final permutation
-    DevBuf sorted;
-    CPH_TRY(sorted.alloc(&ctx->pool, (size_t)nw * n * sizeof(uint64_t)));
-    if (n) CPH_HIP_TRY(hipMemcpyAsync(sorted.get(), kout, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-    for (int w = 1; w < nw; w++) CPH_TRY(gather_u64(ctx, all + (uint64_t)w * n, vcur, sorted.as<uint64_t>() + (uint64_t)w * n, n));
-    ix->sorted_codes = std::move(sorted);
-    ix->perm = std::move(vcur == va.as<uint32_t>() ? va : vb);
-    return {};
-}
-
-// Segment view of a staged key column for one window.
-static DevCol window_col(const DevCol* cols, const cph_key_window& w, int s) {
-    DevCol v = cols[w.seg_col[s]];
-    v.skip = w.seg_skip[s];
-    v.take = w.seg_take[s];
-    return v;
-}
-
-// Keys whose columns need more than kMaxKeyBytes byte positions: the positions (column-major) are cut into windows
-// of at most kMaxKeyBytes, every window gets its own codec over its column segments, and the rows are sorted LSD
-// over all the windows' words — the order Less (csvplus.go:794-807) defines has no length limit, only the tuned
-// single-window paths do.
-static Status build_multi_window(cph_ctx* ctx, BuildJob* job, const std::vector<ColStats>& raw) {
-    cph_index* ix = job->ix;
-    const uint64_t n = ix->nrows;
-    std::vector<cph_key_window>& W = ix->windows;
-    W.clear();
-    W.emplace_back();
-    uint32_t room = kMaxKeyBytes;
-    for (int c = 0; c < job->nkeycols; c++) {
-        uint32_t left = raw[(size_t)c].maxlen, skip = 0;
-        do {
-            if (room == 0 || W.back().nseg == kMaxKeyCols) {
-                W.emplace_back();
-                room = kMaxKeyBytes;
-            }
-            cph_key_window& w = W.back();
-            const uint32_t t = left < room ? left : room;
-            w.seg_col[w.nseg] = c;
-            w.seg_skip[w.nseg] = skip;
-            w.seg_take[w.nseg] = t == left ? 0xFFFFFFFFu : t;   // the column's last segment runs to the end of the value
-            w.nseg++;
-            skip += t;
-            left -= t;
-            room -= t;
-        } while (left > 0);
-    }
-    int total_words = 0;
-    for (auto& w : W) {
-        DevCol v[kMaxKeyCols];
-        for (int s = 0; s < w.nseg; s++) v[s] = window_col(job->dcols, w, s);
-        std::vector<ColStats> st;
-        CPH_TRY(codec_collect_stats(ctx, v, w.nseg, &st));
-        CPH_TRY(codec_build(st, &w.codec));
-        w.codec.key32 = false;   // window words are always stored as 64-bit words
-        CPH_TRY(codec_upload(ctx, w.codec, &w.codec_dev));
-        w.word_base = total_words;
-        total_words += w.codec.nwords;
-    }
-    ix->codec = W[0].codec;
-    DevBuf all, va, vb;
-    CPH_TRY(all.alloc(&ctx->pool, (size_t)total_words * n * sizeof(uint64_t)));
-    CPH_TRY(va.alloc(&ctx->pool, n * sizeof(uint32_t)));
-    CPH_TRY(vb.alloc(&ctx->pool, n * sizeof(uint32_t)));
-    std::vector<int> bits((size_t)total_words);
-    for (auto& w : W) {
-        DevCol v[kMaxKeyCols];
-        for (int s = 0; s < w.nseg; s++) v[s] = window_col(job->dcols, w, s);
-        CPH_TRY(codec_encode_build(ctx, w.codec, w.codec_dev, v, n, all.as<uint64_t>() + (uint64_t)w.word_base * n));
-        for (int k = 0; k < w.codec.nwords; k++) bits[(size_t)(w.word_base + k)] = w.codec.word_bits[k];
-    }
-    CPH_TRY(sort_words_lsd(ctx, ix, all.as<uint64_t>(), total_words, bits.data(), n, va, vb));
-    return index_first_dup_launch(ctx, ix);
-}
-
-static Status build_phase2(cph_ctx* ctx, BuildJob* job, const void* stats_host) {
-    cph_index* ix = job->ix;
-    const uint64_t n = ix->nrows;
-    const int32_t nkeycols = job->nkeycols;
-    const DevCol* dcols = job->dcols;
-    if (job->presplit) {   // the codec is there already (build_phase1)
-        CPH_TRY(job_arm_miss(ctx, job));
-        CPH_TRY(codec_upload(ctx, ix->codec, &ix->codec_dev));
-        return build_encode_sort(ctx, job);
-    }
-    std::vector<ColStats> stats;
-    if (job->sampled) {
-        codec_sample_finish(dcols[0], stats_host, &stats);
-        CPH_TRY(codec_build(stats, &ix->codec));
-        if (codec_sample_checked(ix->codec, dcols)) {
-            CPH_TRY(job_arm_miss(ctx, job));
-            CPH_TRY(codec_upload(ctx, ix->codec, &ix->codec_dev));
-            return build_encode_sort(ctx, job);
-        }
-        // a code the checking encode kernel does not handle (several words, ...): the exact pass after all, here and now
-        job->sampled = false;
-        ix->codec = CodecHost{};
-        CPH_TRY(codec_collect_stats(ctx, dcols, nkeycols, &stats));
-    } else {
-        codec_stats_finish(dcols, nkeycols, stats_host, &stats);
-    }
-    uint64_t positions = 0;
-    for (const auto& s : stats) positions += s.maxlen;
-    if (positions > (uint64_t)kMaxKeyBytes) return build_multi_window(ctx, job, stats);
-    CPH_TRY(codec_build(stats, &ix->codec));
-    if (!job->no_split) CPH_TRY(codec_try_split(ctx, dcols, nkeycols, n, &stats, &ix->codec));   // only acts on codes beyond 32 bits
-    if (ix->codec.has_split()) {
-        CPH_TRY(job_arm_miss(ctx, job));
-    } else {
-        CPH_TRY(codec_try_groups(ctx, dcols, nkeycols, n, &ix->codec, &job->spec));   // only acts on codes of several words
-    }
-    CPH_TRY(codec_upload(ctx, ix->codec, &ix->codec_dev));
-    return build_encode_sort(ctx, job);
-}
-
-// Encode with the index's codec, sort, launch the adjacent-equal scan.
-static Status build_encode_sort(cph_ctx* ctx, BuildJob* job) {
-    cph_index* ix = job->ix;
-    const uint64_t n = ix->nrows;
-    const DevCol* dcols = job->dcols;
-    const CodecHost& cd = ix->codec;
-
-    DevBuf va, vb;
-    CPH_TRY(va.alloc(&ctx->pool, n * sizeof(uint32_t)));
-    int passes = 0;
-
-    if (cd.nwords == 1) {
-        // single-word codes: the encode kernel leaves the first radix pass's histogram behind when it can
-        const size_t kb_ = cd.key32 ? sizeof(uint32_t) : sizeof(uint64_t);
-        DevBuf ka, kb, counts;
-        CPH_TRY(ka.alloc(&ctx->pool, n * kb_));
-        EncodeHist eh;
-        // distinct keys expected over a dense code space: slot[code] = row instead of radix passes (window_sort.hip)
-        const uint64_t states = cd.word_states[0];
-        const bool direct = job->unique && !job->no_direct && ctx->direct_sort != 0 && cd.key32 && !job->spec.active && n >= (1ull << 16) &&
-                            states >= n && states <= 2 * n && states < 0xFFFFFFFFull;
-        if (direct) {   // (writes va and ka alone: the second pair of buffers is not allocated)
-            if (!job->miss) {
-                CPH_TRY(job_arm_miss(ctx, job));
-            }
-            // fixed-width 8-byte keys under an arithmetic codec (decimal ids): the first partition level of the window sort codes the keys
-            // itself — no encode kernel, no code array written and read again
-            // a code space larger than the table: the Join's rank table (8 bytes per 32 codes) falls out of the window sort for free
-            DevBuf rt;
-            uint64_t rt_blocks = 0;
-            if (ctx->direct_ranktab && ctx->direct_sort == 1 && states != n && states <= (1ull << 30)) {   // (index_plan_table's limit)
-                rt_blocks = ranktab_blocks(states);
-                if (!rt.alloc(&ctx->pool, rt_blocks * 8).ok()) rt_blocks = 0;   // (then the first Join builds it, or does without)
-            }
-            void* rtp = rt_blocks ? rt.get() : nullptr;
-            ArithPlan ap;
-            codec_arith_plan(cd, &ap);
-            const DevCol& kc = dcols[0];
-            if (ctx->direct_sort == 1 && ctx->direct_fused_encode && job->nkeycols == 1 && ap.enabled && ap.keylen == 8 && kc.fixed_width == 8 &&
-                !kc.segmented() && ((uintptr_t)kc.data & 15) == 0) {
-                CPH_TRY(direct_sort_windows_keys(ctx, reinterpret_cast<const uint64_t*>(kc.data), ap, n, states, va.as<uint32_t>(), ka.as<uint32_t>(),
-                                                 job->miss, rtp, rt_blocks));
-                ix->sorted_codes = std::move(ka);
-                ix->perm = std::move(va);
-                ix->sort_passes = 0;
-                if (rtp) ix->ranktab = std::move(rt);   // (a miss starts the build over and drops it: build_run)
-                return {};
-            }
-            CPH_TRY(codec_encode_build(ctx, cd, ix->codec_dev, dcols, n, ka.get(), &eh, nullptr, job->miss));
-            CPH_TRY(direct_sort_windows(ctx, ka.as<uint32_t>(), n, states, va.as<uint32_t>(), ka.as<uint32_t>(), job->miss, rtp, rt_blocks));
-            if (rtp) ix->ranktab = std::move(rt);
-            ix->sorted_codes = std::move(ka);
-            ix->perm = std::move(va);
-            ix->sort_passes = 0;
-            // no adjacent-equal scan (first_dup_dev stays empty): either the keys are distinct or the miss word sends the build down the general path
-            return {};
-        }
-        // duplicates allowed, 32-bit codes, a window of the code space holds a few thousand rows: MSD sort through counted LDS windows
-        // (counted_sort.hip) instead of 3-4 classic passes; the adjacent-equal scan falls out of it
-        CPH_TRY(kb.alloc(&ctx->pool, n * kb_));
-        CountedSortPlan csp;
-        if (cd.key32 && !job->spec.active && counted_sort_plan(ctx, n, states, &csp)) {
-            uint32_t* over = host_word(ctx);
-            if (!over) return {CPH_ERR_HIP, "no pinned host memory for the report words of a build"};
-            CountedSort cs;
-            CPH_TRY(cs.begin(ctx, csp, n));
-            CPH_TRY(codec_encode_build(ctx, cd, ix->codec_dev, dcols, n, ka.get(), &eh, &job->spec, job->miss));
-            CPH_TRY(ix->first_dup_dev.alloc(&ctx->pool, sizeof(uint32_t)));
-            CPH_TRY(cs.run(ctx, ka.as<uint32_t>(), n, states, va.as<uint32_t>(), kb.as<uint32_t>(), ix->first_dup_dev.as<uint32_t>(), over, false));
-            job->cs_over = over;
-            job->cs_codes = std::move(ka);
-            ix->sorted_codes = std::move(kb);
-            ix->perm = std::move(va);
-            ix->sort_passes = 0;
-            return {};
-        }
-        CPH_TRY(vb.alloc(&ctx->pool, n * sizeof(uint32_t)));
-        const RadixPlan plan = radix_plan(ctx, n, cd.word_bits[0]);
-        if (plan.npass > 0) {
-            CPH_TRY(counts.alloc(&ctx->pool, plan.count_words() * sizeof(uint32_t)));
-            eh.tile_rows = plan.tile;
-            eh.digit_mask = (1u << plan.nb0) - 1u;
-            eh.bins = 1u << plan.rbits;
-            eh.counts = counts.as<uint32_t>();
-        }
-        CPH_TRY(codec_encode_build(ctx, cd, ix->codec_dev, dcols, n, ka.get(), &eh, &job->spec, job->miss));
-        if (job->spec.active) {
-            // speculative dictionaries (from a sample of the rows): did the encode kernel meet a window they lack?  Then
-            // it has added every such window to the device sets: rebuild the codec from the now complete sets and encode
-            // again.  (One more synchronisation, in exchange for the exact statistics pass over all rows.)
-            uint32_t miss = 0;
-            CPH_TRY(read_device_value(ctx, job->spec.miss.as<uint32_t>(), &miss));
-            job->spec.active = false;
-            if (miss) {
-                const int bits_before = cd.word_bits[0];
-                CPH_TRY(codec_groups_complete(ctx, dcols, job->nkeycols, n, miss, &job->spec, &ix->codec));
-                CPH_TRY(codec_upload(ctx, ix->codec, &ix->codec_dev));
-                // the same single-word shape (the usual outcome: a few more dictionary entries): encode into the same
-                // buffers; anything else starts over with the new codec
-                if (cd.nwords != 1 || cd.word_bits[0] != bits_before || radix_plan(ctx, n, cd.word_bits[0]).npass != plan.npass) {
-                    ka.reset(); kb.reset(); counts.reset(); va.reset(); vb.reset();
-                    return build_encode_sort(ctx, job);
-                }
-                CPH_TRY(codec_encode_build(ctx, cd, ix->codec_dev, dcols, n, ka.get(), &eh, nullptr));
-            }
-        }
-        uint32_t* vout;
-        if (cd.key32) {
-            uint32_t* kout;
-            CPH_TRY(radix_sort_pairs<uint32_t>(ctx, ka.as<uint32_t>(), kb.as<uint32_t>(), va.as<uint32_t>(), vb.as<uint32_t>(),
-                                               true, n, cd.word_bits[0], &kout, &vout, &passes, eh.counts, eh.done));
-            ix->sorted_codes = std::move(kout == ka.as<uint32_t>() ? ka : kb);
-        } else {
-            uint64_t* kout;
-            CPH_TRY(radix_sort_pairs<uint64_t>(ctx, ka.as<uint64_t>(), kb.as<uint64_t>(), va.as<uint32_t>(), vb.as<uint32_t>(),
-                                               true, n, cd.word_bits[0], &kout, &vout, &passes, eh.counts, eh.done));
-            ix->sorted_codes = std::move(kout == ka.as<uint64_t>() ? ka : kb);
-        }
-        ix->sort_passes = passes;
-        ix->perm = std::move(vout == va.as<uint32_t>() ? va : vb);
-    } else {
-        // multi-word codes: LSD over the words, least significant word first
-        DevBuf all;
-        CPH_TRY(vb.alloc(&ctx->pool, n * sizeof(uint32_t)));
-        CPH_TRY(all.alloc(&ctx->pool, (size_t)cd.nwords * n * sizeof(uint64_t)));
-        CPH_TRY(codec_encode_build(ctx, cd, ix->codec_dev, dcols, n, all.get(), nullptr, nullptr, job->miss));
-        CPH_TRY(sort_words_lsd(ctx, ix, all.as<uint64_t>(), cd.nwords, cd.word_bits, n, va, vb));
-    }
-
-    // adjacent-equal scan; its result is read back by build_run together with the other jobs'
-    CPH_TRY(index_first_dup_launch(ctx, ix));
-    return {};
-}
-
-static Status index_build_impl(cph_ctx* ctx, const cph_strcol* keycols, int32_t nkeycols, cph_index* ix, bool unique) {
-    if (nkeycols == 1 && keycols && keycols[0].mem == CPH_MEM_HOST && validate_cols(keycols, nkeycols).ok()) {
-        bool taken = false;
-        CPH_TRY(build_from_host_codes(ctx, keycols, nkeycols, ix, unique, &taken));   // only the key CODES cross PCIe
-        if (taken) return {};
-    }
-    std::vector<BuildJob> jobs(1);
-    std::vector<Status> st(1);
-    jobs[0].ix = ix;
-    jobs[0].unique = unique;
-    st[0] = build_phase1(ctx, keycols, nkeycols, &jobs[0]);
-    if (st[0].ok()) build_run(ctx, jobs, st);
-    return st[0];
+// "" when the index met no duplicate (or none matters: !unique)
+static std::string unique_violation(const cph_index* ix, bool unique) {
+    if (!unique || ix->first_dup == UINT64_MAX) return {};
+    return "duplicate value while creating unique index (sorted position " + std::to_string(ix->first_dup) + ")";
 }
 
 }  // namespace cph
@@ -1385,19 +813,15 @@ CPH_API int32_t cph_index_build(cph_ctx* ctx, const cph_strcol* keycols, int32_t
     if (first_dup_pos) *first_dup_pos = UINT64_MAX;
     cph_index* ix = new (std::nothrow) cph_index();
     if (!ix) return fail(ctx, {CPH_ERR_NOMEM, "out of host memory"});
-    s = index_build_impl(ctx, keycols, nkeycols, ix, unique != 0);
+    s = build_index(ctx, keycols, nkeycols, ix, unique != 0);
     if (!s.ok()) {
         delete ix;
         return fail(ctx, s);
     }
     if (first_dup_pos) *first_dup_pos = ix->first_dup;
     *out = ix;
-    if (unique && ix->first_dup != UINT64_MAX) {
-        char b[128];
-        snprintf(b, sizeof b, "duplicate value while creating unique index (sorted position %llu)",
-                 (unsigned long long)ix->first_dup);
-        return fail(ctx, {CPH_ERR_DUPLICATE, b});
-    }
+    const std::string dup = unique_violation(ix, unique != 0);
+    if (!dup.empty()) return fail(ctx, {CPH_ERR_DUPLICATE, dup});
     return CPH_OK;
 }
 
@@ -1406,65 +830,21 @@ CPH_API int32_t cph_index_build_many(cph_ctx* ctx, const cph_index_spec* specs, 
     Status s = enter(ctx);
     if (!s.ok()) return fail(ctx, s);
     if (!specs || !out || nspecs < 1 || nspecs > 64) return fail(ctx, {CPH_ERR_INVALID, "bad cph_index_build_many arguments"});
-    std::vector<BuildJob> jobs((size_t)nspecs);
-    std::vector<Status> st((size_t)nspecs);
     // every job may take one SplitSample of report words + a few single ones, all read by the host only at the batch's
     // synchronisation points: they must not wrap around the ring inside this call (64 jobs x 600 words < kHostWords)
     if (!host_words_reserve(ctx, (uint32_t)nspecs * (uint32_t)(codec_sample_bytes() / 4 + 16)))
         return fail(ctx, {CPH_ERR_INVALID, "cph_index_build_many: the batch needs more report words than the ctx holds"});
-    // Two streams for a batch: every second build is enqueued on the side stream, so a small table's launch-latency-bound
-    // kernels (products: 1e5 rows, ~15 launches of a few microseconds of work each) run inside the gaps and beside the kernels
-    // of its neighbour (customers: 1e7 rows) instead of behind them.  Both streams are idle again when the call returns.
-    bool two_streams = nspecs >= 2 && ctx->build_side_stream != 0;
-    if (two_streams && !ctx->side_stream && hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->side_stream = nullptr;
-        two_streams = false;
-    }
-    struct DeferGuard {   // no block changes hands between the two streams' kernels while both run
-        cph_ctx* c;
-        ~DeferGuard() {
-            if (!c) return;
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipStreamSynchronize(c->side_stream);
-            c->pool.end_defer();
-        }
-    } defer{two_streams ? ctx : nullptr};
-    if (two_streams) {
-        // The header's promise — all work of a ctx is ordered on the stream set with cph_ctx_set_stream — must hold for the side
-        // jobs too: they may read key columns that kernels of the CALLER, queued on ctx->stream, are still producing, and they take
-        // pool blocks whose last users run on ctx->stream.  So the side stream first waits for everything enqueued there so far.
-        hipError_t fe = ctx->side_fork ? hipSuccess : hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming);
-        if (fe == hipSuccess) fe = hipEventRecord(ctx->side_fork, ctx->stream);
-        if (fe == hipSuccess) fe = hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0);
-        if (fe != hipSuccess) {
-            (void)hipGetLastError();
-            two_streams = false;
-            defer.c = nullptr;
-        }
-    }
-    if (two_streams) ctx->pool.begin_defer();
-    for (int i = 0; i < nspecs; i++) {
-        out[i] = nullptr;
-        if (first_dup_pos) first_dup_pos[i] = UINT64_MAX;
-        jobs[i].ix = new (std::nothrow) cph_index();
-        jobs[i].side = two_streams && (i & 1);
-        jobs[i].unique = specs[i].unique != 0;
-        SideStream on_side(ctx, jobs[i].side);
-        if (!jobs[i].ix) st[i] = {CPH_ERR_NOMEM, "out of host memory"};
-        else st[i] = build_phase1(ctx, specs[i].keycols, specs[i].nkeycols, &jobs[i]);
-    }
-    build_run(ctx, jobs, st);
+    std::vector<cph_index*> built((size_t)nspecs);
+    std::vector<Status> st((size_t)nspecs);
+    build_indexes(ctx, specs, nspecs, built.data(), st.data());
     int32_t rc = CPH_OK;
     std::string msg;
     for (int i = 0; i < nspecs; i++) {
-        cph_index* ix = jobs[i].ix;
-        if (st[i].ok() && specs[i].unique && ix->first_dup != UINT64_MAX) {
-            char b[160];
-            snprintf(b, sizeof b, "index %d: duplicate value while creating unique index (sorted position %llu)", i,
-                     (unsigned long long)ix->first_dup);
-            st[i] = {CPH_ERR_DUPLICATE, b};
-        }
+        cph_index* ix = built[(size_t)i];
+        out[i] = nullptr;
+        if (first_dup_pos) first_dup_pos[i] = UINT64_MAX;
+        const std::string dup = st[i].ok() ? unique_violation(ix, specs[i].unique != 0) : std::string();
+        if (!dup.empty()) st[i] = {CPH_ERR_DUPLICATE, "index " + std::to_string(i) + ": " + dup};
         const bool keep = st[i].ok() || st[i].code == CPH_ERR_DUPLICATE;   // like cph_index_build: the index is returned
         if (keep) {
             out[i] = ix;

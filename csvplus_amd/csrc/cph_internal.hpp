@@ -70,7 +70,7 @@ public:
     uint64_t guard_violations = 0;
     std::string first_violation;
     void check_live();
-    // While a batch of builds runs on TWO streams (capi.hip: cph_index_build_many), reuse is no longer stream-ordered: a
+    // While a batch of builds runs on TWO streams (index_build.hip: build_indexes), reuse is no longer stream-ordered: a
     // block released by one build could be handed to the other while kernels still use it.  Between begin_defer and
     // end_defer released blocks are parked instead; end_defer (called once both streams are idle) really releases them.
     void begin_defer();
@@ -571,7 +571,7 @@ Status codec_collect_stats(cph_ctx* ctx, const DevCol* cols, int32_t ncols, std:
 Status codec_stats_launch(cph_ctx* ctx, const DevCol* cols, int32_t ncols, DevBuf* dev_stats);
 void codec_stats_finish(const DevCol* cols, int32_t ncols, const void* host_copy, std::vector<ColStats>* out);
 Status codec_build(const std::vector<ColStats>& stats, CodecHost* codec);   // host only
-// alphabets from a sample of the rows instead of a pass over all of them (keycodec.hip; capi.hip: BuildJob::sampled)
+// alphabets from a sample of the rows instead of a pass over all of them (keycodec.hip; index_build.hip: Alphabets::Sample)
 bool codec_sample_applies(const cph_ctx* ctx, const DevCol* cols, int32_t ncols, uint64_t n);
 size_t codec_sample_bytes();
 Status codec_sample_launch(cph_ctx* ctx, const DevCol& col, uint64_t n, const void** host_copy);
@@ -782,6 +782,18 @@ void warm_window_sort();
 // host_encode.hip: IndexOn over one short key column in host memory through host-formed codes; *taken = false: not applicable
 // (or a row the sampled alphabets could not code / duplicates under the direct sort): the index is untouched, the general path runs
 Status build_from_host_codes(cph_ctx* ctx, const cph_strcol* keycols, int32_t nkeycols, cph_index* ix, bool unique, bool* taken);
+// index_build.hip: what cph_index_build / cph_index_build_many run between their argument checks and their return codes.
+// build_indexes: ixs[i] = a new index (nullptr: out of host memory), st[i] = that build's outcome; duplicates are no error here.
+Status build_index(cph_ctx* ctx, const cph_strcol* keycols, int32_t nkeycols, cph_index* ix, bool unique);
+void build_indexes(cph_ctx* ctx, const cph_index_spec* specs, int32_t nspecs, cph_index** ixs, Status* st);
+// ... and the pieces the host-coded build shares with it
+bool direct_sort_applies(const cph_ctx* ctx, bool unique, uint64_t n, uint64_t states);   // distinct keys expected over a dense code space
+void index_set_sorted(cph_index* ix, DevBuf&& codes, DevBuf&& perm, int passes);          // sorted_codes, perm, sort_passes
+void index_reset_for_rebuild(cph_index* ix);   // drops what a failed attempt left: codec, sorted codes, perm, pending scan, rank table
+// one 32-bit code word that may hold duplicates: classic passes + publish + first-duplicate scan (read) + table plan | the same
+// after a counted-sort overflow, behind up to `narrower_attempts` retries with narrower windows
+Status sort_codes_classic(cph_ctx* ctx, cph_index* ix, DevBuf& codes, DevBuf& kb, DevBuf& va);
+Status sort_codes_after_overflow(cph_ctx* ctx, cph_index* ix, DevBuf& codes, DevBuf& kb, DevBuf& va, uint32_t* over, int narrower_attempts);
 void host_pool_destroy(cph_ctx* ctx);
 
 // small_build.hip: IndexOn of a small table in one launch (one workgroup) and one synchronisation
@@ -813,6 +825,7 @@ Status small_build_finish(cph_ctx* ctx, cph_index* ix, int32_t ncols, SmallBufs*
 Status ensure_pinned_scratch(cph_ctx* ctx, size_t bytes);
 Status pinned_cache_get(cph_ctx* ctx, size_t bytes, void** out, size_t* cap);   // a cached block of >= bytes, or a new one
 void pinned_cache_put(cph_ctx* ctx, void* p, size_t cap);                        // back into the cache (at most 2 blocks kept)
+size_t result_block_bytes(size_t need);                                          // the size such a block is asked for with, so that batches share it
 Status pinned_upload(cph_ctx* ctx, size_t bytes, void** out);   // staging slot valid until the ring wraps
 Status validate_cols(const cph_strcol* cols, int32_t ncols);
 // Makes columns device resident (host columns are copied into pool blocks kept alive by `storage`).

@@ -498,7 +498,7 @@ Status build_from_host_codes(cph_ctx* ctx, const cph_strcol* keycols, int32_t nk
     }
     // UniqueIndexOn over a dense code space: the direct sort (window_sort.hip), its first partition level chunk by chunk behind the uploads
     const uint64_t states = cd.word_states[0];
-    const bool direct = unique && ctx->direct_sort == 1 && n >= (1ull << 16) && states >= n && states <= 2 * n && states < 0xFFFFFFFFull;
+    const bool direct = ctx->direct_sort == 1 && direct_sort_applies(ctx, unique, n, states);
     WindowSort ws;
     uint32_t* miss = nullptr;
     hipEvent_t part_done = nullptr;
@@ -579,42 +579,25 @@ Status build_from_host_codes(cph_ctx* ctx, const cph_strcol* keycols, int32_t nk
             CPH_TRY(ws.finish(ctx, va.as<uint32_t>(), ka.as<uint32_t>(), miss));
             CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
             if (*(volatile uint32_t*)miss) return {CPH_ERR_DUPLICATE, "#direct-duplicates"};   // (caught below: the general path finds WHERE)
-            ix->sorted_codes = std::move(ka);
-            ix->perm = std::move(va);
-            ix->sort_passes = 0;
+            index_set_sorted(ix, std::move(ka), std::move(va), 0);
             ix->first_dup = UINT64_MAX;
-        } else {
-            DevBuf kb, vb;
-            CPH_TRY(kb.alloc(&ctx->pool, n * sizeof(uint32_t)));
-            // duplicates allowed, a window of the code space holds a few thousand rows: the counted LDS windows (counted_sort.hip)
-            CountedSortPlan csp;
-            if (ctx->counted_sort && counted_sort_plan(ctx, n, states, &csp)) {
-                uint32_t* over = host_word(ctx);
-                if (!over) return {CPH_ERR_HIP, "no pinned host memory for the report words of a build"};
-                CPH_TRY(ix->first_dup_dev.alloc(&ctx->pool, sizeof(uint32_t)));
-                CPH_TRY(counted_sort(ctx, csp, ka.as<uint32_t>(), n, states, va.as<uint32_t>(), kb.as<uint32_t>(), ix->first_dup_dev.as<uint32_t>(), over));
-                CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-                if (*(volatile uint32_t*)over == 0) {
-                    ix->sorted_codes = std::move(kb);
-                    ix->perm = std::move(va);
-                    ix->sort_passes = 0;
-                    CPH_TRY(index_first_dup_read(ctx, ix));
-                    index_plan_table(ix);
-                    return {};
-                }
-                ix->first_dup_dev.reset();   // a window beyond its capacity: the classic passes over the same codes
-            }
-            CPH_TRY(vb.alloc(&ctx->pool, n * sizeof(uint32_t)));
-            uint32_t *kout, *vout;
-            int passes = 0;
-            CPH_TRY(radix_sort_pairs<uint32_t>(ctx, ka.as<uint32_t>(), kb.as<uint32_t>(), va.as<uint32_t>(), vb.as<uint32_t>(), true, n,
-                                               cd.word_bits[0], &kout, &vout, &passes));
-            ix->sorted_codes = std::move(kout == ka.as<uint32_t>() ? ka : kb);
-            ix->perm = std::move(vout == va.as<uint32_t>() ? va : vb);
-            ix->sort_passes = passes;
-            CPH_TRY(index_first_dup_launch(ctx, ix));
-            CPH_TRY(index_first_dup_read(ctx, ix));
+            index_plan_table(ix);
+            return {};
         }
+        DevBuf kb;
+        CPH_TRY(kb.alloc(&ctx->pool, n * sizeof(uint32_t)));
+        // duplicates allowed, a window of the code space holds a few thousand rows: the counted LDS windows (counted_sort.hip)
+        CountedSortPlan csp;
+        if (!counted_sort_plan(ctx, n, states, &csp)) return sort_codes_classic(ctx, ix, ka, kb, va);
+        uint32_t* over = host_word(ctx);
+        if (!over) return {CPH_ERR_HIP, "no pinned host memory for the report words of a build"};
+        CPH_TRY(ix->first_dup_dev.alloc(&ctx->pool, sizeof(uint32_t)));
+        CPH_TRY(counted_sort(ctx, csp, ka.as<uint32_t>(), n, states, va.as<uint32_t>(), kb.as<uint32_t>(), ix->first_dup_dev.as<uint32_t>(), over));
+        CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        // a window beyond its capacity: the classic passes over the same codes (no narrower windows first, unlike the device-coded build)
+        if (*(volatile uint32_t*)over) return sort_codes_after_overflow(ctx, ix, ka, kb, va, over, 0);
+        index_set_sorted(ix, std::move(kb), std::move(va), 0);
+        CPH_TRY(index_first_dup_read(ctx, ix));
         index_plan_table(ix);
         return {};
     };
@@ -630,8 +613,7 @@ Status build_from_host_codes(cph_ctx* ctx, const cph_strcol* keycols, int32_t nk
         (void)hipStreamSynchronize(ctx->stream);
         const bool dup = st.code == CPH_ERR_DUPLICATE && st.msg == "#direct-duplicates";
         // leave the index as it came: the general path fills it
-        ix->codec = CodecHost{};
-        ix->codec_dev.reset(); ix->sorted_codes.reset(); ix->perm.reset(); ix->first_dup_dev.reset();
+        index_reset_for_rebuild(ix);
         ix->host_coded = false;
         ix->first_dup = UINT64_MAX;
         return dup ? Status{} : st;

@@ -1498,7 +1498,7 @@ static Status split_assemble(const cph_ctx* ctx, int c, int ncols, const std::ve
 // The statistics pass reads every key once only to learn which byte values occur at which position; for ids and the like a
 // few ten thousand rows spread over the table show them all.  k_split_count already collects per-position byte presence
 // over rows 0, step, 2 step, ...: its result stands in for the exact ColStats, the encode kernel (k_encode_build_fast) flags
-// any row the sampled alphabets cannot code, and a flagged build starts over with the exact pass (capi.hip).
+// any row the sampled alphabets cannot code, and a flagged build starts over with the exact pass (index_build.hip: next_attempt).
 bool codec_sample_applies(const cph_ctx* ctx, const DevCol* cols, int32_t ncols, uint64_t n) {
     return ctx->stats_sample != 0 && ncols == 1 && cols[0].fixed_width >= 1 && cols[0].fixed_width <= (uint32_t)kSplitMaxValue &&
            !cols[0].segmented() && n >= (1ull << 20);
@@ -2103,7 +2103,7 @@ __global__ __launch_bounds__(kEncodeThreads) void k_encode_build_fast(DevCol col
             uint32_t okm = wr.okm;   // every build key encodes under alphabets taken from ALL rows: only the existence bits matter
             encode_rows<kEncodeFastRows, W, B, OUT, LONG>(cv, sp, c0, c1, code, &okm,
                                                           col.fixed_width != 0 && (int)col.fixed_width == cv.hdr->col_maxlen[0]);
-            // alphabets from a SAMPLE of the rows (capi.hip: BuildJob::sampled): a row with a byte the sample never showed at
+            // alphabets from a SAMPLE of the rows (index_build.hip: Alphabets::Sample): a row with a byte the sample never showed at
             // that position does not encode — its code is meaningless, the caller starts over with exact statistics
             if (miss && okm != wr.okm) *miss = 1u;
 #pragma unroll

@@ -169,3 +169,69 @@ def test_host_split_codec_falls_back(case):
     np.testing.assert_array_equal(h.perm(), g.perm())
     assert h.first_dup == g.first_dup
     h.close(); g.close(); ctx.close()
+
+
+# ---- the sort tail the host-coded build shares with the device-coded one (csrc/index_build.hip: sort_codes_after_overflow) ----
+# counted_sort_plan takes tables of 1 << 21 rows and more: the smallest such table + a ragged tail.
+CS_ROWS = (1 << 21) + 3
+
+
+def _fixed8(ids: np.ndarray) -> StrCol:
+    b = np.empty((ids.size, 8), dtype=np.uint8)
+    for q in range(8):
+        b[:, 7 - q] = 48 + (ids // 10 ** q) % 10
+    return StrCol.from_arrays(b.reshape(-1), np.arange(ids.size + 1, dtype=np.uint32) * 8, fixed_width=8)
+
+
+@pytest.fixture(scope="module", params=["three_rows_per_key", "one_key_beyond_a_window"])
+def cs_input(request):
+    """(shape, column in host memory, numpy's stable order of its rows, first adjacent-equal sorted position), computed once."""
+    rng = np.random.default_rng(21)
+    ids = rng.integers(0, 700_000, CS_ROWS)                     # ~3 rows per key, no giant group
+    if request.param == "one_key_beyond_a_window":
+        ids[rng.choice(CS_ROWS, 20_000, replace=False)] = 424_242   # a window holds 16 384 rows
+    want = np.argsort(ids, kind="stable").astype(np.uint32)     # zero-padded decimal ids: numeric order == bytewise order
+    s = ids[want]
+    first_dup = int(np.flatnonzero(s[1:] == s[:-1])[0]) + 1
+    want.setflags(write=False)
+    return request.param, _fixed8(ids), want, first_dup
+
+
+def _profiled_build(ctx, col):
+    ctx.profile(True)
+    ctx.profile_read(reset=True)
+    ix = DeviceIndex(ctx, [col])
+    prof = ctx.profile_read(reset=True)
+    ctx.profile(False)
+    return ix, prof
+
+
+def test_host_coded_build_sorts_through_counted_windows(cs_input):
+    """Host-formed 32-bit codes with duplicates: the counted LDS windows; a key with more rows than a window holds raises the
+    overflow flag (one k_cs_scan: the host-coded build tries no narrower windows) and the classic passes sort the same codes."""
+    shape, col, want, first_dup = cs_input
+    ctx = Context(0)
+    ctx.set_option("host_build", 1)
+    h, prof = _profiled_build(ctx, col)
+    assert h.info()["build_path"] == 2 and h.status == N.CPH_OK     # host-coded
+    if shape == "three_rows_per_key":
+        assert "k_cs_window" in prof and "k_radix_scatter_u32" not in prof, sorted(prof)
+    else:
+        assert prof["k_cs_scan"]["launches"] == 1 and "k_radix_scatter_u32" in prof, sorted(prof)
+    np.testing.assert_array_equal(h.perm(), want)
+    assert h.first_dup == first_dup
+    h.close(); ctx.close()
+
+
+def test_host_coded_and_device_coded_builds_share_the_sort_tail(cs_input):
+    """The same rows as a device column: the identical permutation and first duplicate."""
+    _, col, want, first_dup = cs_input
+    ctx = Context(0)
+    ctx.set_option("host_build", 1)
+    h = DeviceIndex(ctx, [col])
+    d = DeviceIndex(ctx, [col.to_device("cuda:0")])
+    assert h.info()["build_path"] == 2 and d.info()["build_path"] == 0
+    np.testing.assert_array_equal(d.perm(), h.perm())
+    np.testing.assert_array_equal(d.perm(), want)
+    assert d.first_dup == h.first_dup == first_dup
+    h.close(); d.close(); ctx.close()
