@@ -9,6 +9,8 @@ allgatherv over RCCL), `streaming` (host -> device pipeline of join chunks), `in
 `materialize` (gather through row ids, ToCsv, ToJSON, Filter / TakeWhile / DropWhile over `predicates`: Like, All, Any,
 Not, IntCmp, FloatCmp as plain data; ValueAsInt / ValueAsFloat64 for a whole column: to_int / to_float), `dedup` (ResolveDuplicates over the device index: a callback over the groups, or a named rule — First, Last, DropAll,
 MinBy, MaxBy — resolved on the device: resolve_duplicates_device),
+`aggregate` (Totals per key of an index on the device — Sum, Min, Max as plain data: totals; the contract in pure Python:
+totals_model),
 `mapping` (Map as row templates — Format, Col, Int, Const — for computed columns: materialize.map_column; Validate:
 materialize.validate_rows),
 `pipeline` (CSV -> indices -> chained join -> CSV or JSON, all in HBM), `datagen` (deterministic synthetic tables).

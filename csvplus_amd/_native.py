@@ -206,6 +206,22 @@ class cph_resolved(C.Structure):
                 ("first_error_kind", C.c_int32), ("reserved2_", C.c_int32), ("host_rows", C.c_uint64)]
 
 
+CPH_AGG_SUM, CPH_AGG_MIN, CPH_AGG_MAX = 1, 2, 3
+CPH_AGG_MAX_SPECS = 8
+
+
+class cph_agg_spec(C.Structure):
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("col", C.POINTER(cph_strcol)), ("numbers", C.c_void_p),
+                ("numbers_mem", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class cph_aggregated(C.Structure):
+    _fields_ = [("ngroups", C.c_uint64), ("first_position", C.c_void_p), ("first_row", C.c_void_p), ("count", C.c_void_p),
+                ("values", C.c_void_p * CPH_AGG_MAX_SPECS), ("nspecs", C.c_int32), ("mem", C.c_int32), ("nerrors", C.c_uint64),
+                ("first_error_position", C.c_uint64), ("first_error_row", C.c_uint64),
+                ("first_error_kind", C.c_int32), ("first_error_spec", C.c_int32), ("host_rows", C.c_uint64)]
+
+
 CPH_DIST_ID_BYTES = 128
 CPH_MAX_GATHER = 8
 
@@ -329,6 +345,9 @@ PROTOTYPES = [
     ("cph_index_resolve", C.c_int32,
      [_P, _P, C.POINTER(cph_resolve_opts), C.POINTER(cph_strcol), C.c_int32, C.POINTER(_P), C.POINTER(C.POINTER(cph_resolved))]),
     ("cph_resolved_release", None, [C.POINTER(cph_resolved)]),
+    ("cph_index_aggregate", C.c_int32,
+     [_P, _P, C.POINTER(cph_agg_spec), C.c_int32, C.c_int32, C.POINTER(C.POINTER(cph_aggregated))]),
+    ("cph_aggregated_release", None, [C.POINTER(cph_aggregated)]),
     ("cph_index_save", C.c_int32, [_P, _P, C.c_char_p]),
     ("cph_index_load", C.c_int32, [_P, C.c_char_p, C.POINTER(_P)]),
     ("cph_index_find", C.c_int32,

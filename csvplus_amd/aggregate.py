@@ -1,0 +1,208 @@
+"""Totals: Count and Sum / Min / Max per key of an index, on the device (cph_index_aggregate).
+
+The reference's TestSimpleTotals (csvplus_test.go:516-571) reads the joined rows and accumulates `price * qty` per cust_id in
+a Go closure.  A closure cannot run on a GPU; the aggregate is data here, as Like / IntCmp / KeepMaxInt / Format are:
+
+    Sum(source, kind)   Min(source, kind)   Max(source, kind)        kind = "int" | "float"
+
+`source` is a StrCol of the index's build table in its original row order (host or device; converted as to_int / to_float
+convert it), or numbers with one entry per row of the build table: a numpy array (host), a (device_ptr, count) pair or an
+object with data_ptr() such as a torch tensor (device) — e.g. two to_int / to_float results multiplied on the device.
+
+A group is a maximal run of equal keys in the index, runs of ONE row included.  `totals` returns, per group in key order, the
+sorted position and the table row of its first row, its row count and one value per spec; `totals_model` states the same
+contract in pure Python over keys and values already in sorted order — documentation that runs, and what the tests expect.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _native as N
+from .columns import StrCol
+
+_KINDS = {"int": N.CPH_NUM_INT64, "float": N.CPH_NUM_FLOAT64}
+_MASK = (1 << 64) - 1
+
+
+class Spec:
+    """One aggregate as data.  `op` = CPH_AGG_*, `kind` = CPH_NUM_INT64 / CPH_NUM_FLOAT64."""
+    op = 0
+    name = ""
+
+    def __init__(self, source, kind=None):
+        if kind is None and isinstance(source, np.ndarray):
+            kind = "float" if source.dtype.kind == "f" else "int"
+        if kind not in _KINDS:
+            raise ValueError(f'{type(self).__name__}: kind must be "int" or "float"')
+        self.source, self.kind_name, self.kind = source, kind, _KINDS[kind]
+
+    def __repr__(self):
+        return f"{type(self).__name__}(<{type(self.source).__name__}>, {self.kind_name!r})"
+
+
+class Sum(Spec):
+    """int: wraps around as Go's `+=` on an int does.  float: IEEE addition in a fixed (unspecified) association order."""
+    op, name = N.CPH_AGG_SUM, "sum"
+
+
+class Min(Spec):
+    """float: math.Min — a NaN in the run gives NaN, Min(-0, +0) = -0."""
+    op, name = N.CPH_AGG_MIN, "min"
+
+
+class Max(Spec):
+    """float: math.Max — a NaN in the run gives NaN, Max(-0, +0) = +0."""
+    op, name = N.CPH_AGG_MAX, "max"
+
+
+class TotalsError(ValueError):
+    """A value of a StrCol source that does not convert (what a Go closure returning row.ValueAsInt's error hands back):
+    `position` = the lowest such sorted position, `row` = perm[position], `kind` = CPH_NUM_ERR_*, `spec` = the lowest spec
+    that fails there, `nerrors` = such values over all specs."""
+
+    def __init__(self, position: int, row: int, kind: int, nerrors: int, spec: int):
+        what = {N.CPH_NUM_ERR_SYNTAX: "invalid syntax", N.CPH_NUM_ERR_RANGE: "value out of range"}.get(kind, "unsupported syntax")
+        super().__init__(f"spec {spec}: the value of row {row} (sorted position {position}) does not convert: {what} ({nerrors} such values)")
+        self.position, self.row, self.kind, self.nerrors, self.spec = position, row, kind, nerrors, spec
+
+
+class Totals:
+    """What `totals` returns.  out_mem = HOST: first_position (uint64), first_row (uint32), count (uint64) and values[i] (int64 /
+    float64) are numpy arrays; DEVICE: (device pointer, count) pairs, valid until release()."""
+
+    def __init__(self, ngroups, first_position, first_row, count, values, host_rows, _release=None):
+        self.ngroups, self.first_position, self.first_row, self.count = ngroups, first_position, first_row, count
+        self.values, self.host_rows = values, host_rows
+        self._release = _release
+
+    def release(self):
+        """Gives the device blocks back (out_mem = DEVICE only)."""
+        if self._release:
+            self._release()
+            self._release = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _fill_spec(cs, spec, keep):
+    if not isinstance(spec, Spec):
+        raise TypeError(f"not an aggregate: {spec!r} (closures cannot run on the device; use Sum, Min, Max)")
+    cs.op, cs.kind = spec.op, spec.kind
+    src = spec.source
+    if isinstance(src, StrCol):
+        sc, k = src.as_c()
+        keep.append((sc, k))
+        cs.col = C.pointer(sc)
+    elif isinstance(src, tuple):   # (device pointer, count)
+        cs.numbers, cs.numbers_mem = int(src[0]) or None, N.CPH_MEM_DEVICE
+    elif hasattr(src, "data_ptr"):   # a device tensor
+        want = "int64" if spec.kind == N.CPH_NUM_INT64 else "float64"
+        if not str(getattr(src, "dtype", want)).endswith(want):
+            raise ValueError(f"{type(spec).__name__}: the tensor's dtype is {src.dtype}, the kind wants {want}")
+        if not getattr(src, "is_cuda", True):
+            raise ValueError(f"{type(spec).__name__}: a tensor source must live on the device (pass .numpy() for host values)")
+        keep.append(src)
+        cs.numbers, cs.numbers_mem = int(src.data_ptr()) or None, N.CPH_MEM_DEVICE
+    else:
+        arr = np.ascontiguousarray(np.asarray(src, dtype=np.int64 if spec.kind == N.CPH_NUM_INT64 else np.float64).reshape(-1))
+        if len(arr) == 0:
+            arr = np.zeros(1, arr.dtype)   # a pointer for an empty table
+        keep.append(arr)
+        cs.numbers, cs.numbers_mem = arr.ctypes.data, N.CPH_MEM_HOST
+
+
+def totals(index: N.DeviceIndex, specs=(), out_mem: int = N.CPH_MEM_HOST) -> Totals:
+    """Count and the specs' values per key of `index` (cph_index_aggregate); no specs: the distinct keys and their
+    frequencies.  A StrCol value that does not convert raises TotalsError."""
+    specs = list(specs)
+    ctx = index.ctx
+    arr = (N.cph_agg_spec * max(1, len(specs)))()
+    keep = []
+    for i, sp in enumerate(specs):
+        _fill_spec(arr[i], sp, keep)
+    out = C.POINTER(N.cph_aggregated)()
+    rc = ctx.lib.cph_index_aggregate(ctx.handle, index.handle, arr if specs else None, len(specs), out_mem, C.byref(out))
+    del keep
+    ctx._check(rc)
+    r = out.contents
+    if r.nerrors:
+        err = TotalsError(int(r.first_error_position), int(r.first_error_row), int(r.first_error_kind), int(r.nerrors), int(r.first_error_spec))
+        ctx.lib.cph_aggregated_release(out)
+        raise err
+    ng = int(r.ngroups)
+    dts = [np.int64 if sp.kind == N.CPH_NUM_INT64 else np.float64 for sp in specs]
+    if out_mem == N.CPH_MEM_HOST:
+        res = Totals(ng, N._ptr_array(r.first_position, ng, np.uint64).copy(), N._ptr_array(r.first_row, ng, np.uint32).copy(),
+                     N._ptr_array(r.count, ng, np.uint64).copy(), [N._ptr_array(r.values[i], ng, dt).copy() for i, dt in enumerate(dts)],
+                     int(r.host_rows))
+        ctx.lib.cph_aggregated_release(out)
+        return res
+    return Totals(ng, (int(r.first_position or 0), ng), (int(r.first_row or 0), ng), (int(r.count or 0), ng),
+                  [(int(r.values[i] or 0), ng) for i in range(len(specs))], int(r.host_rows),
+                  _release=lambda: ctx.lib.cph_aggregated_release(out))
+
+
+# ---- the contract in pure Python ----------------------------------------------------------------------------------------
+def _wrap64(v: int) -> int:
+    v &= _MASK
+    return v - (1 << 64) if v >> 63 else v
+
+
+def go_min(x: float, y: float) -> float:
+    """math.Min as documented: NaN if either is NaN, Min(-0, +0) = -0."""
+    if x != x or y != y:
+        return math.nan
+    if x == 0 and y == 0:
+        return x if math.copysign(1.0, x) < 0 else y
+    return x if x < y else y
+
+
+def go_max(x: float, y: float) -> float:
+    """math.Max as documented: NaN if either is NaN, Max(-0, +0) = +0."""
+    if x != x or y != y:
+        return math.nan
+    if x == 0 and y == 0:
+        return y if math.copysign(1.0, x) < 0 else x
+    return x if x > y else y
+
+
+def _fold(op: int, is_float: bool, vals):
+    if op == N.CPH_AGG_SUM:
+        if is_float:
+            acc = -0.0   # the identity of IEEE addition
+            for v in vals:
+                acc = acc + float(v)   # left to right: ONE of the association orders the contract allows
+            return acc
+        return _wrap64(sum(int(v) for v in vals))
+    if not is_float:
+        return min(int(v) for v in vals) if op == N.CPH_AGG_MIN else max(int(v) for v in vals)
+    f = go_min if op == N.CPH_AGG_MIN else go_max
+    acc = float(vals[0])
+    for v in vals[1:]:
+        acc = f(acc, float(v))
+    return acc
+
+
+def totals_model(keys_in_sorted_order, values_by_sorted_position=(), specs=()):
+    """The host statement of cph_index_aggregate.  keys_in_sorted_order[p] = the key at sorted position p (anything comparable
+    with ==; equal keys are adjacent); values_by_sorted_position[s][p] = the value spec s reads at position p (int or float);
+    specs = Sum / Min / Max objects or (op, kind) pairs of CPH_AGG_* / CPH_NUM_*.  Returns a dict: ngroups, first_position,
+    count, and values (one list per spec).  An int sum wraps to int64; a float sum is added left to right (the device's order
+    is unspecified: compare bit for bit only where every order is exact); float Min / Max are go_min / go_max."""
+    keys = list(keys_in_sorted_order)
+    n = len(keys)
+    starts = [p for p in range(n) if p == 0 or keys[p] != keys[p - 1]]
+    ends = starts[1:] + [n]
+    out = {"ngroups": len(starts), "first_position": starts, "count": [e - s for s, e in zip(starts, ends)], "values": []}
+    for s, sp in enumerate(specs):
+        op, kind = (sp.op, sp.kind) if isinstance(sp, Spec) else sp
+        vals = values_by_sorted_position[s]
+        out["values"].append([_fold(op, kind == N.CPH_NUM_FLOAT64, vals[lo:hi]) for lo, hi in zip(starts, ends)])
+    return out

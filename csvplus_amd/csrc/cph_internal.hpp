@@ -777,6 +777,7 @@ void warm_materialize();
 void warm_csv_ingest();
 void warm_index_ops();
 void warm_resolve();
+void warm_aggregate();
 void warm_small_build();
 void warm_window_sort();
 // host_encode.hip: IndexOn over one short key column in host memory through host-formed codes; *taken = false: not applicable

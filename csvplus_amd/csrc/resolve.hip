@@ -25,14 +25,11 @@
 #include <cstring>
 #include <new>
 
-#include "numparse_device.hpp"
+#include "runs_device.hpp"
 
 namespace cph {
 
-constexpr int kResRows  = 8;                          // consecutive rows per lane
-constexpr int kResTile  = kMatThreads * kResRows;     // 2048 rows = 32 bitmap words: tests/test_resolve.py calls it T
-constexpr int kResWords = kResTile / 64;
-constexpr int kResWaves = kMatThreads / kWave;
+// kResRows / kResTile / kResWords / kResWaves and equal_flags: runs_device.hpp
 constexpr uint32_t kNoPos = 0xFFFFFFFFu;
 
 enum : int { kOrdNone = 0, kOrdKey = 1, kOrdBytes = 2 };   // how k_resolve_tile orders the rows of a group
@@ -134,41 +131,6 @@ __device__ __forceinline__ Seg seg_shfl_up(const Seg& s, int d) {
     r.b.pos = __shfl_up(s.b.pos, d, kWave);
     r.start = __shfl_up(s.start, d, kWave);
     return r;
-}
-
-// e[j] (j = 0..kResRows) = sorted positions base + j - 1 and base + j exist and carry the same key
-template <bool KEY32>
-__device__ __forceinline__ uint32_t equal_flags(const void* __restrict__ codes, uint64_t n, int nwords, uint64_t base) {
-    uint32_t e = (1u << (kResRows + 1)) - 1;
-    if constexpr (KEY32) {
-        const uint32_t* c = reinterpret_cast<const uint32_t*>(codes);
-        uint32_t prev = c[base ? base - 1 : 0];
-#pragma unroll
-        for (int j = 0; j <= kResRows; j++) {
-            const uint64_t p = base + (uint64_t)j;
-            const uint32_t cur = c[p < n ? p : n - 1];
-            if (cur != prev) e &= ~(1u << j);
-            prev = cur;
-        }
-    } else {
-        const uint64_t* c = reinterpret_cast<const uint64_t*>(codes);
-        for (int w = 0; w < nwords; w++) {
-            const uint64_t* cw = c + (uint64_t)w * n;
-            uint64_t prev = cw[base ? base - 1 : 0];
-#pragma unroll
-            for (int j = 0; j <= kResRows; j++) {
-                const uint64_t p = base + (uint64_t)j;
-                const uint64_t cur = cw[p < n ? p : n - 1];
-                if (cur != prev) e &= ~(1u << j);
-                prev = cur;
-            }
-        }
-    }
-    if (base == 0) e &= ~1u;
-#pragma unroll
-    for (int j = 0; j <= kResRows; j++)
-        if (base + (uint64_t)j >= n) e &= ~(1u << j);
-    return e;
 }
 
 // bitmap[tile * 32 + w] bit b = sorted position tile * 2048 + 64 w + b survives (rows >= n: 0; the winners of runs that span

@@ -548,6 +548,30 @@ inline Resolver KeepMaxFloat(std::string col) { return {CPH_RESOLVE_MAX, CPH_NUM
 inline Resolver KeepMin(std::string col) { return {CPH_RESOLVE_MIN, CPH_ORDER_BYTES, std::move(col)}; }
 inline Resolver KeepMax(std::string col) { return {CPH_RESOLVE_MAX, CPH_ORDER_BYTES, std::move(col)}; }
 
+// ---- aggregates for Index::Totals, as DATA ---------------------------------------------------------------------------------
+// The reference's TestSimpleTotals (csvplus_test.go:516-571) accumulates per key in a closure; the sums people write are a
+// handful of fixed reductions, so they are declarative here and the device runs them (cph_index_aggregate): per key of the index
+// the row count and the sum / smallest / largest value of a column read as an integer or a float.
+struct Aggregate {
+    int32_t op = 0;       // CPH_AGG_*
+    int32_t kind = 0;     // CPH_NUM_INT64 / CPH_NUM_FLOAT64
+    std::string column;
+};
+inline Aggregate SumInt(std::string col) { return {CPH_AGG_SUM, CPH_NUM_INT64, std::move(col)}; }
+inline Aggregate SumFloat(std::string col) { return {CPH_AGG_SUM, CPH_NUM_FLOAT64, std::move(col)}; }
+inline Aggregate MinInt(std::string col) { return {CPH_AGG_MIN, CPH_NUM_INT64, std::move(col)}; }
+inline Aggregate MaxInt(std::string col) { return {CPH_AGG_MAX, CPH_NUM_INT64, std::move(col)}; }
+inline Aggregate MinFloat(std::string col) { return {CPH_AGG_MIN, CPH_NUM_FLOAT64, std::move(col)}; }
+inline Aggregate MaxFloat(std::string col) { return {CPH_AGG_MAX, CPH_NUM_FLOAT64, std::move(col)}; }
+// Group g (key order): keys[g] = the index columns of its rows, counts[g] its rows, and per aggregate a its value in ints[a][g]
+// (integer aggregates; floats[a] is empty) or floats[a][g] (float aggregates; ints[a] is empty).
+struct TotalsResult {
+    std::vector<Row> keys;
+    std::vector<uint64_t> counts;
+    std::vector<std::vector<int64_t>> ints;
+    std::vector<std::vector<double>> floats;
+};
+
 class Index {
 public:
     // Iterate (:618-620): rows sorted on the index columns, each handed out as a copy (:230)
@@ -569,6 +593,12 @@ public:
     // reference's `missing column` error (:170), one outside a pack is never looked at.
     Error ResolveDuplicates(const Resolver& resolver);
     static ResolveFunc resolver_func(const Resolver& resolver);   // the rule as a callback
+    // Totals: per key of the index (every run of equal keys, runs of one row included) the row count and the named aggregates
+    // (SumInt("qty"), MaxFloat("price"), ...), reduced on the device; no aggregates: the distinct keys and their frequencies.
+    // Integer sums wrap around as Go's `+=` does; float Min / Max follow math.Min / math.Max.  A row that lacks an aggregate's
+    // column is the reference's `missing column` error (:170 / :192), a value that does not convert the error of :176 / :198
+    // for the first such row in index order.  The index is left as it was.
+    std::pair<TotalsResult, Error> Totals(const std::vector<Aggregate>& aggregates) const;
     // WriteTo (:655-680) / LoadIndex (:682-705).  The reference gob-encodes columns + rows; this file is a
     // length-prefixed little-endian dump of the same two values and is NOT readable by the Go library.
     Error WriteTo(const std::string& fileName) const;
@@ -1431,6 +1461,71 @@ inline Error Index::ResolveDuplicates(const Resolver& rs) {
     impl_rows.resize((size_t)res->nrows);                                           // :862-864
     invalidate_device();
     return Error();
+}
+
+inline std::pair<TotalsResult, Error> Index::Totals(const std::vector<Aggregate>& aggs) const {
+    TotalsResult out;
+    if (aggs.size() > (size_t)CPH_AGG_MAX_SPECS) return {out, Error("too many aggregates in Index.Totals()")};
+    for (const Aggregate& a : aggs)
+        if (!impl_rows.empty() && column_presence(a.column) != kAll) return {out, Error("missing column " + quote(a.column))};
+    cph_ctx* ctx = Gpu::Default().ctx();
+    // value columns in the row order of the twin's BUILD TABLE (see ResolveDuplicates): row perm[p] = the value of impl_rows[p]
+    std::vector<cph_agg_spec> specs(aggs.size());
+    std::vector<std::unique_ptr<detail::StagedColumns>> scattered;
+    if (!aggs.empty() && !impl_rows.empty()) {
+        const uint32_t* perm = nullptr;
+        uint64_t pn = 0;
+        if (cph_index_perm(device().h, CPH_MEM_HOST, &perm, &pn) != CPH_OK || pn != impl_rows.size())
+            throw std::runtime_error(std::string("csvplus: ") + cph_last_error(ctx));
+        bool identity = true;
+        for (uint64_t p = 0; p < pn && identity; p++) identity = perm[p] == p;
+        for (size_t a = 0; a < aggs.size(); a++) {
+            specs[a] = cph_agg_spec{aggs[a].op, aggs[a].kind, nullptr, nullptr, CPH_MEM_HOST, 0};
+            if (identity) {
+                specs[a].col = side_column(ctx, aggs[a].column);
+                continue;
+            }
+            std::vector<std::vector<const std::string*>> vals(1);
+            vals[0].resize(impl_rows.size());
+            for (uint64_t p = 0; p < pn; p++) vals[0][perm[p]] = &impl_rows[(size_t)p].at(aggs[a].column);
+            scattered.push_back(std::make_unique<detail::StagedColumns>(ctx, 1));
+            scattered.back()->stage(vals, impl_rows.size());
+            specs[a].col = scattered.back()->cols();
+        }
+    }
+    out.ints.resize(aggs.size());
+    out.floats.resize(aggs.size());
+    if (impl_rows.empty()) return {out, Error()};
+    cph_aggregated* res = nullptr;
+    if (cph_index_aggregate(ctx, device().h, specs.data(), (int32_t)specs.size(), CPH_MEM_HOST, &res) != CPH_OK)
+        throw std::runtime_error(std::string("csvplus: ") + cph_last_error(ctx));
+    struct Release { cph_aggregated* r; ~Release() { cph_aggregated_release(r); } } rel{res};
+    if (res->nerrors) {
+        const Aggregate& a = aggs[(size_t)res->first_error_spec];
+        const std::string& v = impl_rows[(size_t)res->first_error_position].at(a.column);   // sorted position = subscript of impl_rows
+        const char* what = res->first_error_kind == CPH_NUM_ERR_SYNTAX  ? "invalid syntax"
+                           : res->first_error_kind == CPH_NUM_ERR_RANGE ? "value out of range"
+                                                                        : "not decided by this library (digit separators, hexadecimal floats)";
+        return {TotalsResult(), Error("column " + quote(a.column) + ": cannot convert " + quote(v) + " to " +
+                                      (a.kind == CPH_NUM_INT64 ? "integer" : "float") + ": " + what)};
+    }
+    const size_t ng = (size_t)res->ngroups;
+    out.keys.resize(ng);
+    out.counts.assign(res->count, res->count + ng);
+    for (size_t g = 0; g < ng; g++) {
+        const Row& first = impl_rows[(size_t)res->first_position[g]];
+        for (const std::string& c : impl_columns) out.keys[g][c] = first.at(c);
+    }
+    for (size_t a = 0; a < aggs.size(); a++) {
+        if (aggs[a].kind == CPH_NUM_INT64) {
+            const int64_t* v = static_cast<const int64_t*>(res->values[a]);
+            out.ints[a].assign(v, v + ng);
+        } else {
+            const double* v = static_cast<const double*>(res->values[a]);
+            out.floats[a].assign(v, v + ng);
+        }
+    }
+    return {out, Error()};
 }
 
 namespace detail {

@@ -305,3 +305,59 @@ def filter_to_csv(ctx: N.Context, table: Table, pred, out_columns, mode: str = "
         for cb in bufs:
             cb.release()
         kept.release()
+
+
+def totals_to_csv(ctx: N.Context, table: Table, by, specs, names=None, out_mem: int = N.CPH_MEM_HOST):
+    """IndexOn(by...) over `table`, then Count and the specs per key, written as CSV — the reference's TestSimpleTotals loop
+    (csvplus_test.go:516-571) ending in ToCsv, every step in HBM: cph_index_build, cph_index_aggregate, the key columns read
+    through the groups' first rows inside the writer, the count and the int64 results as computed columns (mapping.Int).
+    by: key column names.  specs: aggregate.Sum / Min / Max whose source is a column NAME of the table, a StrCol, or numbers
+    (see csvplus_amd.aggregate).  names: the header of the count column and of every spec's column (default "count",
+    "sum0", "min1", ...); the key columns keep their names.  One output row per distinct key, in key order.
+    Float results are refused: formatting float64 (Go's shortest round-trip FormatFloat) is out of scope, as for Map.
+    Returns bytes, or a DeviceBytes handle for out_mem DEVICE."""
+    from . import aggregate as A
+    from . import mapping as M
+    from .materialize import csv_write, map_column
+
+    by = [str(b) for b in by]
+    specs = list(specs)
+    for sp in specs:
+        if not isinstance(sp, A.Spec):
+            raise TypeError(f"not an aggregate: {sp!r}")
+        if sp.kind == N.CPH_NUM_FLOAT64:
+            raise ValueError("totals_to_csv: a float64 result cannot be written (formatting float64 is out of scope); "
+                             "use aggregate.totals and format the values on the host")
+    if names is None:
+        names = ["count"] + [f"{sp.name}{i}" for i, sp in enumerate(specs)]
+    if len(names) != 1 + len(specs):
+        raise ValueError(f"totals_to_csv: {1 + len(specs)} computed columns but {len(names)} names")
+    for b in by:
+        if b not in table.cols:
+            raise M.MissingColumn(b)
+    resolved = []
+    for sp in specs:
+        if isinstance(sp.source, str):
+            if sp.source not in table.cols:
+                raise M.MissingColumn(sp.source)
+            sp = type(sp)(table.cols[sp.source], sp.kind_name)
+        resolved.append(sp)
+    index = N.DeviceIndex(ctx, [table.cols[b] for b in by])
+    bufs, t = [], None
+    try:
+        t = A.totals(index, resolved, out_mem=N.CPH_MEM_DEVICE)
+        ng = t.ngroups
+        cols = [table.cols[b] for b in by]
+        ids = [(t.first_row[0], 32, ng) for _ in by]
+        for ptr, _ in [t.count] + t.values:   # count[g] < 2^32: the uint64 reads as the same int64
+            cb = map_column(ctx, {}, M.Format(M.Int.on_device(ptr, ng)), nrows=ng, out_mem=N.CPH_MEM_DEVICE)
+            bufs.append(cb)
+            cols.append(cb.as_device_strcol())
+            ids.append(None)
+        return csv_write(ctx, cols, by + [str(nm) for nm in names], out_mem=out_mem, row_ids=ids, nrows=ng)
+    finally:
+        for cb in bufs:
+            cb.release()
+        if t is not None:
+            t.release()
+        index.close()

@@ -1000,6 +1000,70 @@ CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* index, const cp
                                   int32_t out_mem, cph_index** out_index /* may be NULL */, cph_resolved** out);
 CPH_API void    cph_resolved_release(cph_resolved* r);
 
+/*
+ * Totals: one Count and up to CPH_AGG_MAX_SPECS Sum / Min / Max values per KEY of an index, on the device — the reduction the
+ * reference's TestSimpleTotals (csvplus_test.go:516-571) writes as a Go closure over the rows.  A closure cannot run on a GPU;
+ * the aggregate is data, as the rules of cph_index_resolve are.
+ *
+ * A GROUP is a maximal run of equal keys in the index; a run of ONE row is a group too (cph_index_dup_groups and
+ * cph_index_resolve report only runs of >= 2).  Group g is in key order; inside a run the rows are in input order.
+ *   first_position[g]  the sorted position of the run's first row, ascending: usable as `positions` of cph_index_select, which
+ *                      then builds the unique index over the distinct keys;
+ *   first_row[g]       perm[first_position[g]], the first INPUT row with that key: 32-bit row ids for cph_rowsel, so the key
+ *                      columns of the result are a gather (cph_gather_rows, the writers), not a copy;
+ *   count[g]           rows of the run;
+ *   values[s][g]       spec s over the run: int64_t[ngroups] for CPH_NUM_INT64, double[ngroups] for CPH_NUM_FLOAT64.
+ * All arrays lie in `mem` (= out_mem) and are owned by the library until cph_aggregated_release.
+ *
+ * The value of sorted position p for a spec is either row perm[p] of `col`, a column of the BUILD TABLE in its original row
+ * order (host or device, any cph_strcol layout, nrows >= the table's rows) converted exactly as cph_col_to_number converts it,
+ * or numbers[perm[p]] of an int64_t[] / double[] array with one entry per row of the build table (in numbers_mem).  Exactly
+ * one of col / numbers is set.
+ *   CPH_AGG_SUM  int64: two's-complement wrap-around, what Go's `+=` on an int does; never an error.
+ *                float64: IEEE double addition; NaN and inf - inf propagate.  The association order is unspecified but FIXED:
+ *                the same index and values give bit-identical sums on every call and for every out_mem (no floating-point
+ *                atomics, nothing that depends on scheduling; the partials of a run that spans tiles are folded in ascending
+ *                tile order).
+ *   CPH_AGG_MIN / CPH_AGG_MAX  int64: exact.  float64: math.Min / math.Max as documented — Min(-0, +0) = -0, Max(-0, +0) = +0,
+ *                and a NaN anywhere in the run gives NaN (also beside an infinity); the NaN returned has the bits of Go's
+ *                math.NaN().  Both are associative and commutative: the order does not matter.
+ *
+ * A `col` value that does not convert is DATA, as in cph_col_to_number / cph_index_resolve: the call returns CPH_OK with
+ * nerrors > 0 (the number of such values over all specs), ngroups = 0 and every array NULL; first_error_position is the lowest
+ * such sorted position (EVERY row lies in a group here, so every row is looked at), first_error_row = perm[that],
+ * first_error_kind its CPH_NUM_ERR_*, first_error_spec the lowest spec that fails there.  `numbers` cannot have errors.
+ * Floats outside Clinger's exact cases are finished on the library's host side as everywhere else (host_rows).
+ *
+ * nspecs == 0 is legal (specs may be NULL): groups, first rows and counts only — "the distinct keys and their frequencies".
+ * Indexes of 0 and 1 rows are legal, and so is every index cph_index_resolve accepts (32-bit, one-word and multi-word codes,
+ * several key columns, indexes out of cph_index_select / cph_index_resolve / cph_index_load).
+ * CPH_ERR_INVALID (with a message): NULL ctx / index / out, nspecs outside 0..CPH_AGG_MAX_SPECS, specs NULL with nspecs > 0,
+ * an unknown op, kind, numbers_mem or out_mem, both or neither of col / numbers, a col shorter than the build table.
+ */
+enum { CPH_AGG_SUM = 1, CPH_AGG_MIN = 2, CPH_AGG_MAX = 3 };
+#define CPH_AGG_MAX_SPECS 8
+typedef struct {
+    int32_t           op, kind;              /* CPH_AGG_*, CPH_NUM_INT64 / CPH_NUM_FLOAT64 */
+    const cph_strcol* col;                   /* a column of the build table, original row order ... */
+    const void*       numbers;               /* ... or int64_t[] / double[] with one entry per row of the build table */
+    int32_t           numbers_mem, reserved_;   /* CPH_MEM_HOST / CPH_MEM_DEVICE (numbers only) */
+} cph_agg_spec;
+typedef struct {
+    uint64_t        ngroups;
+    const uint64_t* first_position;          /* [ngroups] sorted position of every run's first row, ascending */
+    const uint32_t* first_row;               /* [ngroups] perm[first_position[g]] */
+    const uint64_t* count;                   /* [ngroups] rows per run */
+    const void*     values[CPH_AGG_MAX_SPECS];   /* [nspecs] int64_t[ngroups] / double[ngroups]; the others NULL */
+    int32_t         nspecs, mem;
+    uint64_t        nerrors;                 /* col values that did not convert */
+    uint64_t        first_error_position, first_error_row;   /* lowest such sorted position, perm[that]; UINT64_MAX */
+    int32_t         first_error_kind, first_error_spec;      /* CPH_NUM_ERR_*, index into specs */
+    uint64_t        host_rows;               /* float cols: values finished on the host, over all specs */
+} cph_aggregated;
+CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* index, const cph_agg_spec* specs, int32_t nspecs, int32_t out_mem,
+                                    cph_aggregated** out);
+CPH_API void    cph_aggregated_release(cph_aggregated* a);
+
 /* Index.WriteTo / LoadIndex (csvplus.go:655-705) for the device index: a flat
  * little-endian file with the key codec, sorted codes and perm.  NOT a gob
  * stream and without row payload: the row table stays with the caller (the
