@@ -45,6 +45,22 @@ def test_window_sort_over_two_partition_levels(shape):
         assert g.status == N.CPH_OK and g.first_dup is None
         chk = V.check_index_order(d, pg)
         assert chk["ok"], chk
+        # k_win_place also leaves the LEVEL-1 cursors zero (clear_also, nclear): a one-level sort on the same ctx starts from
+        # them — 65 536 distinct keys over a full code space of 4 windows, compared with numpy's stable order of the key bytes.
+        # (A cursor left behind shifts the entries: wrong rows, or the flag goes up and the radix passes show in the profile.)
+        from tests.test_gpu_window_sort_edges import fixture, reference
+
+        t, ref = fixture("full-4w"), reference("full-4w")
+        ctx.profile(True)
+        ctx.profile_read(reset=True)
+        s = DeviceIndex(ctx, [t.col], unique=True)
+        prof1 = ctx.profile_read(reset=True)
+        ctx.profile(False)
+        assert prof1["k_win_partition"]["launches"] == 1 and "k_win_place" in prof1, sorted(prof1)
+        assert not [k for k in prof1 if k.startswith(("k_radix_scatter", "k_cs_"))], sorted(prof1)
+        assert s.status == N.CPH_OK and s.first_dup is None and s.info()["table_entries"] == t.space.states == 65536
+        np.testing.assert_array_equal(s.perm(), ref.perm)
+        s.close()
     del pg, pr
     g.close(); r.close(); ctx.close()
 
