@@ -100,14 +100,28 @@ struct LeanArgs {
 //      per phase: step s gathers its value from row brow[source][k] of its column (through the source index's perm when the
 //      chain reports positions and the column is in the table's original order), so a step starts when its source step's
 //      lookups are back.  Instantiated for LONG && WIDE && !LEAN, R = 4 only (the general register types).
-template <int S, bool LONG, bool WIDE, bool DBG, uint32_t LEAN = 0, int R = kChainRows, bool DEP = false>
-__global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint64_t nprobe, uint64_t probe_base,
+// VAR: bit s set (a lean step only) = the step's stream column is variable-length with 32-bit offsets, or fixed-width of at most 8
+//      bytes at any address, and the index's keys of at most 8 bytes have different lengths or not the column's width
+//      (ArithPlan::var_enabled): the value's span comes from the offsets, its 8 bytes from ONE load at its first byte — unaligned, and
+//      running past the value into its neighbours, whose bytes the encode masks out.  Only the wave-tiles that reach the column's last 8
+//      bytes (a wave-uniform test on the tile's last offset) take load_chunk_nobranch, which stays inside the aligned words of the column.
+// SW:  the uniform switches of the lean kernels, compiled in: bit 0 = nt_streams, bit 1 = every lean step multiplies in 24 bits
+//      (ArithPlan::mul24).  kSwRuntime: both are read from the arguments (the general kernels, lean chains of three and four steps).
+constexpr int kSwNt = 1, kSwMul24 = 2, kSwRuntime = 4;
+// waves per SIMD the register allocator has to make room for: the lean kernels of one and two steps fit 128 VGPRs without scratch
+// (tools/kernel_usage.sh), and with no codec block in LDS four workgroups of the flagship chain fit a CU
+constexpr int chain_min_waves(int S, uint32_t lean) { return S <= 2 && lean == (1u << S) - 1u ? 4 : 1; }
+template <int S, bool LONG, bool WIDE, bool DBG, uint32_t LEAN = 0, int R = kChainRows, bool DEP = false, uint32_t VAR = 0, int SW = kSwRuntime>
+__global__ __launch_bounds__(kChainThreads, chain_min_waves(S, LEAN)) void k_chain_dense(ChainArgs a, uint64_t nprobe, uint64_t probe_base,
                                                               uint64_t ntiles, uint64_t* __restrict__ masks,
                                                               uint32_t* __restrict__ wave_counts, int dbg_flags, LeanArgs la) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     // dynamic LDS layout: [codec 0][codec 1]...   (no static LDS: keeps 16-B alignment)
     using B = std::conditional_t<WIDE, uint64_t, uint32_t>;    // byte offset of a value from its (uniform) base
     using CW = std::conditional_t<WIDE, uint64_t, uint32_t>;   // key code
+    static_assert((VAR & ~LEAN) == 0 && (LEAN != 0 || SW == kSwRuntime), "VAR and SW describe lean steps");
+    constexpr int kM24 = (SW & kSwRuntime) ? -1 : ((SW & kSwMul24) ? 1 : 0);
+    const bool nt_streams = (SW & kSwRuntime) ? a.nt_streams != 0 : (SW & kSwNt) != 0;
     const int dbg = DBG ? dbg_flags : 0;
     CodecView cv[S];
     {
@@ -122,6 +136,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
     // rank tables small enough to live in LDS next to the codecs (the 1e5-row products index: 2517 blocks), 12 bytes
     // per block there: {bits lo, bits hi, keys before}
     const CPH_LDS uint32_t* rank_lds[S];
+    bool rank_in_lds[S];   // (not "rank_lds[s] != nullptr": with no codec block in front of it a table sits at LDS address 0)
     {
         uint8_t* p = smem;
 #pragma unroll
@@ -130,6 +145,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
 #pragma unroll
         for (int s = 0; s < S; s++) {
             rank_lds[s] = nullptr;
+            rank_in_lds[s] = a.step[s].ranktab_lds != 0;
             const int nblk = a.step[s].ranktab_lds;
             if (LEAN != 0 && nblk) {   // the blocks as they are: 8 bytes per 32 codes, one ds_read_b64 and 32-bit arithmetic per lookup
                 uint2* dst = reinterpret_cast<uint2*>(p);
@@ -154,6 +170,16 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
     }
     const int lane = lane_id();
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(wave_id());
+    // VAR steps: the column's values end at byte vend[s] of col.data — an 8-byte load at byte b stays inside the column when b + 8 <= vend[s]
+    uint64_t vend[S];
+#pragma unroll
+    for (int s = 0; s < S; s++) {
+        vend[s] = 0;
+        if ((VAR >> s) & 1u) {
+            const DevCol& c = a.step[s].col;
+            vend[s] = c.fixed_width ? nprobe * (uint64_t)c.fixed_width : (uint64_t)reinterpret_cast<const uint32_t*>(c.offsets)[nprobe];
+        }
+    }
 
 #pragma unroll 1
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -161,12 +187,14 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
 #pragma unroll 1
       for (int part = 0; part < kChainRows / R; part++) {
         const uint64_t wbase = tile * kChainTile + (uint64_t)wave * kWaveTile + (uint64_t)part * (R * kWave);   // wave-uniform
-        const WaveRows<R> wr = wave_rows<R>(wbase, nprobe);
+        const WaveRows<R> wr = LEAN != 0 ? wave_rows_full_first<R>(wbase, nprobe) : wave_rows<R>(wbase, nprobe);
         uint32_t okm = wr.okm;                  // bit k: row k of this lane is (still) joined
         WaveSpans<R, B> sp[S];
         uint64_t c0[S][R], c1[LONG ? S : 1][R];
         CW code[S][R];
         uint32_t brow[S][R];
+        uint32_t vbeg[VAR ? S : 1][R], vstop[VAR ? S : 1][R], vlen[VAR ? S : 1][R];   // VAR steps: first byte of row k's value from vbase, the byte behind it, its length
+        uint64_t vbase[VAR ? S : 1], vlast[VAR ? S : 1];        // (uniform) byte of col.data vbeg counts from; end of the tile's last value
         // !DEP: ONE level, every phase covers all steps.  DEP: level l is step l alone (its source step's rows are known by then).
 #pragma unroll
       for (int lvl = 0; lvl < (DEP ? S : 1); lvl++) {
@@ -174,6 +202,31 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
 #pragma unroll
         for (int s = 0; s < S; s++) {
             if (DEP && s != lvl) continue;
+            if ((VAR >> s) & 1u) {
+                const DevCol& c = a.step[s].col;
+                if (c.fixed_width) {   // uniform
+                    vbase[s] = wr.rbase * (uint64_t)c.fixed_width;
+#pragma unroll
+                    for (int k = 0; k < R; k++) {
+                        vbeg[s][k] = wr.rel[k] * c.fixed_width;
+                        vstop[s][k] = vbeg[s][k] + c.fixed_width;
+                    }
+                } else {
+                    typedef const __attribute__((address_space(1))) uint32_t* global_u32_ptr;
+                    const global_u32_ptr off = (global_u32_ptr) reinterpret_cast<const uint32_t*>(c.offsets) + wr.rbase;
+                    auto load_offsets = [&](auto nt) {
+#pragma unroll
+                        for (int k = 0; k < R; k++) {
+                            vbeg[s][k] = decltype(nt)::value ? __builtin_nontemporal_load(&off[wr.rel[k]]) : off[wr.rel[k]];
+                            vstop[s][k] = decltype(nt)::value ? __builtin_nontemporal_load(&off[wr.rel[k] + 1]) : off[wr.rel[k] + 1];
+                        }
+                    };
+                    if (nt_streams) load_offsets(std::true_type{});   // uniform (a constant unless SW is kSwRuntime)
+                    else load_offsets(std::false_type{});
+                    vbase[s] = 0;
+                }
+                continue;   // nothing here waits for the offsets: phase B issues the other steps' loads first
+            }
             if ((LEAN >> s) & 1u) continue;   // a lean step needs no spans: value k is the 8-byte word rbase + rel[k]
             if constexpr (DEP) {
                 const int32_t src = a.step[s].src;
@@ -196,17 +249,49 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
                     continue;
                 }
             }
-            if (a.nt_streams) wave_spans<R, B, false, true>(a.step[s].col, wr, &sp[s]);   // uniform branch
+            if (nt_streams) wave_spans<R, B, false, true>(a.step[s].col, wr, &sp[s]);   // uniform branch
             else wave_spans<R, B>(a.step[s].col, wr, &sp[s]);
         }
-        // ---- B: first 8 (16) key bytes ---------------------------------------------------------------
+        // ---- B: first 8 (16) key bytes; the VAR steps, whose addresses are loaded values, behind the others ----------------------
+#pragma unroll
+        for (int pass = 0; pass < (VAR ? 2 : 1); pass++)
 #pragma unroll
         for (int s = 0; s < S; s++) {
             if (DEP && s != lvl) continue;
+            if ((int)((VAR >> s) & 1u) != pass) continue;
+            if ((VAR >> s) & 1u) {
+                const uint64_t p = (uint64_t)(uintptr_t)a.step[s].col.data + vbase[s];
+                // the end of row nvalid - 1, the tile's last (clamped lanes re-read it, the last lane among them)
+                vlast[s] = vbase[s] + (uint32_t)__builtin_amdgcn_readlane((int)vstop[s][R - 1], kWave - 1);
+#pragma unroll
+                for (int k = 0; k < R; k++) vlen[s][k] = vstop[s][k] - vbeg[s][k];
+                auto load_keys = [&](auto nt) {
+                    constexpr bool NT = decltype(nt)::value;
+                    if (vlast[s] + 8u <= vend[s]) {   // uniform: 8 bytes from any value of this wave-tile on are bytes of the column
+                        typedef const __attribute__((address_space(1))) uint8_t* global_u8_ptr;
+                        typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
+                        typedef const __attribute__((address_space(1))) u64_unaligned* global_u64u_ptr;
+                        const global_u8_ptr b8 = (global_u8_ptr)(uintptr_t)p;
+#pragma unroll
+                        for (int k = 0; k < R; k++) {
+                            const global_u64u_ptr wp = (global_u64u_ptr)(b8 + vbeg[s][k]);
+                            c0[s][k] = NT ? __builtin_nontemporal_load(wp) : *wp;
+                        }
+                    } else {   // the column's last bytes: aligned words that hold bytes of the column only
+                        const uint8_t* base8 = (const uint8_t*)(uintptr_t)(p & ~7ull);
+                        const uint32_t delta = (uint32_t)(p & 7ull);
+#pragma unroll
+                        for (int k = 0; k < R; k++) c0[s][k] = load_chunk_nobranch<uint32_t, NT>(base8, delta, vbeg[s][k], vlen[s][k], 0);
+                    }
+                };
+                if (nt_streams) load_keys(std::true_type{});   // uniform
+                else load_keys(std::false_type{});
+                continue;
+            }
             if ((LEAN >> s) & 1u) {
                 typedef const __attribute__((address_space(1))) uint64_t* global_u64_ptr;
                 const global_u64_ptr w = (global_u64_ptr)a.step[s].col.data + wr.rbase;
-                if (a.nt_streams) {   // uniform, outside the row loop
+                if (nt_streams) {   // uniform, outside the row loop
 #pragma unroll
                     for (int k = 0; k < R; k++) c0[s][k] = __builtin_nontemporal_load(&w[wr.rel[k]]);
                 } else {
@@ -217,8 +302,8 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
             }
 #pragma unroll
             for (int k = 0; k < R; k++) {
-                c0[s][k] = a.nt_streams ? sp[s].chunk_nt(k, 0) : sp[s].chunk(k, 0);
-                if constexpr (LONG) c1[s][k] = a.nt_streams ? sp[s].chunk_nt(k, 1) : sp[s].chunk(k, 1);
+                c0[s][k] = nt_streams ? sp[s].chunk_nt(k, 0) : sp[s].chunk(k, 0);
+                if constexpr (LONG) c1[s][k] = nt_streams ? sp[s].chunk_nt(k, 1) : sp[s].chunk(k, 1);
             }
         }
         // ---- C: codes -----------------------------------------------------------------------------------
@@ -228,8 +313,10 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
             if (DBG && (dbg & 2)) {
 #pragma unroll
                 for (int k = 0; k < R; k++) code[s][k] = (CW)((c0[s][k] ^ (LONG ? c1[LONG ? s : 0][k] : 0ull)) & 1023);
+            } else if ((VAR >> s) & 1u) {    // ... of the bytes the value has
+                encode_rows_arith_var<R, CW, kM24>(la.arith[s], c0[s], vlen[s], code[s], &okm);
             } else if ((LEAN >> s) & 1u) {   // the code is a dot product of the key's bytes
-                encode_rows_arith<R, CW>(la.arith[s], c0[s], code[s], &okm);
+                encode_rows_arith<R, CW, kM24>(la.arith[s], c0[s], code[s], &okm);
             } else if (!WIDE || cv[s].hdr->lutw_bits == 32) {
                 encode_rows<R, uint32_t, B, CW, LONG>(cv[s], sp[s], c0[s], c1[LONG ? s : 0], code[s], &okm,
                                                                a.step[s].col.fixed_width != 0 && (int)a.step[s].col.fixed_width == cv[s].hdr->col_maxlen[0]);
@@ -249,13 +336,20 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
 #pragma unroll
                     for (int k = 0; k < R; k++)
                         brow[s][k] = ((okm >> k) & 1u) && (uint32_t)code[s][k] < (uint32_t)st.n_index ? (uint32_t)code[s][k] : kTableAbsent;
-                } else if (rank_lds[s]) {   // 8-byte rank blocks in LDS
+                } else if (rank_in_lds[s]) {   // 8-byte rank blocks in LDS
+                    // one ds_read_b64 per row (a uint2 read is split in two, the second behind a branch on the first), all R issued
+                    // before the first is used
+                    uint64_t blk[R];
 #pragma unroll
                     for (int k = 0; k < R; k++) {
                         const uint32_t cidx = (okm >> k) & 1u ? (uint32_t)code[s][k] : 0u;
-                        const CPH_LDS uint32_t* e = rank_lds[s] + 2u * (cidx >> 5);
-                        const uint32_t bits = e[0], before = e[1], bit = cidx & 31u;
-                        brow[s][k] = (bits >> bit) & 1u ? before + (uint32_t)__popc(bits & ((1u << bit) - 1u)) : kTableAbsent;
+                        blk[k] = *(const CPH_LDS uint64_t*)(rank_lds[s] + 2u * (cidx >> 5));
+                    }
+#pragma unroll
+                    for (int k = 0; k < R; k++) {
+                        const uint32_t bits = (uint32_t)blk[k], before = (uint32_t)(blk[k] >> 32), bit = (uint32_t)code[s][k] & 31u;
+                        const uint32_t pos = before + (uint32_t)__popc(bits & ((1u << bit) - 1u));
+                        brow[s][k] = ((okm >> k) & 1u) && ((bits >> bit) & 1u) ? pos : kTableAbsent;
                     }
                 } else {             // rank blocks in global memory (L2-resident for a 1e7-row index)
                     uint2 blk[R];
@@ -274,7 +368,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
                 // the key's rank among the index keys = its sorted position: one 8-byte block per row from a table
                 // 1/16 the size of rowtab (L2-resident for the 1e7-row customers index: no Infinity-Fabric sector per
                 // row), or 12 bytes per 64 codes from LDS
-                if (rank_lds[s]) {   // uniform branch
+                if (rank_in_lds[s]) {   // uniform branch
 #pragma unroll
                     for (int k = 0; k < R; k++) {
                         const CW cidx = (okm >> k) & 1u ? code[s][k] : (CW)0;
@@ -368,7 +462,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_dense(ChainArgs a, uint
             if (ok && !(DBG && (dbg & 4))) {
 #pragma unroll
                 for (int s = 0; s < S; s++) {
-                    if (a.nt_streams) __builtin_nontemporal_store(brow[s][k], a.out_rows[s] + wr.rbase + wr.rel[k]);
+                    if (nt_streams) __builtin_nontemporal_store(brow[s][k], a.out_rows[s] + wr.rbase + wr.rel[k]);
                     else (a.out_rows[s] + wr.rbase)[wr.rel[k]] = brow[s][k];
                 }
             }
@@ -734,6 +828,22 @@ bool chain_fast_path_ok(const ChainStep* steps, int nsteps) {
     return true;
 }
 
+using ChainKernelFn = void (*)(ChainArgs, uint64_t, uint64_t, uint64_t, uint64_t*, uint32_t*, int, LeanArgs);
+// The lean instantiation <LEAN, VAR> with its uniform switches compiled in (chains of one and two steps: four kernels); longer
+// chains read the switches from their arguments.
+template <int S, uint32_t LEAN, uint32_t VAR>
+static ChainKernelFn lean_kernel(bool nt, bool mul24) {
+    if constexpr (S <= 2) {
+        static const ChainKernelFn k[4] = {&k_chain_dense<S, false, false, false, LEAN, kChainRows, false, VAR, 0>,
+                                           &k_chain_dense<S, false, false, false, LEAN, kChainRows, false, VAR, kSwNt>,
+                                           &k_chain_dense<S, false, false, false, LEAN, kChainRows, false, VAR, kSwMul24>,
+                                           &k_chain_dense<S, false, false, false, LEAN, kChainRows, false, VAR, kSwNt | kSwMul24>};
+        return k[(nt ? kSwNt : 0) | (mul24 ? kSwMul24 : 0)];
+    } else {
+        return &k_chain_dense<S, false, false, false, LEAN, kChainRows, false, VAR, kSwRuntime>;
+    }
+}
+
 // Enqueues the dense pass + the match total on ctx->stream; nothing here waits for the GPU.
 //   d_rows[s]  u32[nprobe]             build row of step s at slot == stream row (valid where the bit is set)
 //   d_masks    u64[chain_dense_mask_words(nprobe)]  bit r%64 of word r/64 == "stream row r joined" (a plain bitmap)
@@ -762,10 +872,14 @@ static Status enqueue_dense(cph_ctx* ctx, const ChainStep* steps, uint64_t nprob
         wide |= !col_is_narrow(c);
     }
     // lean steps (k_chain_dense's LEAN mask): a fixed-width-8 stream column at an 8-byte aligned address joined with an
-    // index whose 8-byte keys code arithmetically (codec_arith_plan: contiguous alphabets, no pad).  Every subset of the
-    // steps of chains of one or two Joins is instantiated; longer chains are lean in all steps or in none.
+    // index whose 8-byte keys code arithmetically (codec_arith_plan: contiguous alphabets, no pad); or (the VAR mask) a
+    // variable-length column with 32-bit offsets / a fixed-width column of at most 8 bytes joined with an index whose keys
+    // of at most 8 bytes code arithmetically, pad included (ArithPlan::var_enabled: the benchmark's unpadded product ids).
+    // Chains of one or two Joins are instantiated for every such mix of lean steps, and for one step of the first kind next to
+    // a general one; longer chains are lean in all steps, all of one kind, or in none.
     // A lean kernel reports POSITIONS and answers every step from the code itself (identity) or from a rank table.
-    uint32_t lean = 0;
+    uint32_t lean = 0, var = 0;
+    bool mul24 = true;
     bool ident[kMaxChain] = {false, false, false, false};
     if (positions)
         for (int s = 0; s < S; s++) {
@@ -780,19 +894,66 @@ static Status enqueue_dense(cph_ctx* ctx, const ChainStep* steps, uint64_t nprob
             const DevCol& c = steps[s].cols[0];
             ArithPlan ap;
             codec_arith_plan(ix->codec, &ap);
-            if (ap.enabled && ap.keylen == 8 && c.fixed_width == 8 && ((uintptr_t)c.data & 7u) == 0) lean |= 1u << s;
+            if (ap.enabled && ap.keylen == 8 && c.fixed_width == 8 && ((uintptr_t)c.data & 7u) == 0) {
+                lean |= 1u << s;
+                mul24 &= ap.mul24 != 0;
+            } else if (ap.var_enabled && !c.segmented() && !c.split && (c.fixed_width ? c.fixed_width <= 8 : c.offset_bits == 32)) {
+                var |= 1u << s;
+                mul24 &= ap.mul24 != 0;
+            }
             if (!ident[s]) {
                 CPH_TRY(index_ensure_ranktab(ctx, ix));
                 all_ranked &= (bool)ix->ranktab;
             }
         }
-        if (!all_ranked) lean = 0;
+        if (!all_ranked) lean = var = 0;
     }
-    if (S > 2 && lean != (1u << S) - 1u) lean = 0;
+    constexpr uint32_t kAll = (1u << S) - 1u;
+    if ((lean | var) == kAll && (S <= 2 || var == 0 || var == kAll)) lean |= var;
+    else var = 0;   // a VAR step has no kernel next to a general one
+    if (S > 2 && lean != kAll) lean = 0;
     if (!lean)
         for (int s = 0; s < S; s++) ident[s] = false;   // the general kernel looks every key up
     for (int s = 0; s < S; s++)
         if (!((lean >> s) & 1u)) lds += steps[s].index->codec_dev.bytes();
+    args.nt_streams = ctx->chain_nt_streams == 1 || (ctx->chain_nt_streams == 2 && positions) ? 1 : 0;
+    const uint64_t ncounts = ntiles * kChainWaves;   // one match count per (tile, wave), tile-major
+    using KernelFn = ChainKernelFn;
+    static const KernelFn variants[2][2][2] = {
+        {{&k_chain_dense<S, false, false, false>, &k_chain_dense<S, false, false, true>},
+         {&k_chain_dense<S, false, true, false>, &k_chain_dense<S, false, true, true>}},
+        {{&k_chain_dense<S, true, false, false>, &k_chain_dense<S, true, false, true>},
+         {&k_chain_dense<S, true, true, false>, &k_chain_dense<S, true, true, true>}}};
+    KernelFn kernel = variants[long_keys ? 1 : 0][wide ? 1 : 0][(dbg && !dep) ? 1 : 0];
+    // register-heavy instantiations (tools/kernel_usage.sh: 256 VGPRs + AGPR copies at 8 rows per lane = ONE wave per SIMD) walk the
+    // wave's rows 4 at a time: long keys with 64-bit codes from two steps on, any long or wide chain from three steps on
+    if (!dbg && ctx->chain_rows4 != 0 && ((S == 2 && long_keys && wide) || (S >= 3 && (long_keys || wide)) || S == 4 || ctx->chain_rows4 == 2)) {
+        static const KernelFn r4[2][2] = {{&k_chain_dense<S, false, false, false, 0u, 4>, &k_chain_dense<S, false, true, false, 0u, 4>},
+                                          {&k_chain_dense<S, true, false, false, 0u, 4>, &k_chain_dense<S, true, true, false, 0u, 4>}};
+        kernel = r4[long_keys ? 1 : 0][wide ? 1 : 0];
+    }
+    if constexpr (S >= 2) {
+        if (dep) kernel = &k_chain_dense<S, true, true, false, 0u, 4, true>;
+    }
+    if (lean) {
+        const bool nt = args.nt_streams != 0;
+        if (lean == kAll && var == 0) kernel = lean_kernel<S, kAll, 0u>(nt, mul24);
+        if (lean == kAll && var == kAll) kernel = lean_kernel<S, kAll, kAll>(nt, mul24);
+        if constexpr (S == 2) {
+            if (lean == kAll && var == 1u) kernel = lean_kernel<S, kAll, 1u>(nt, mul24);
+            if (lean == kAll && var == 2u) kernel = lean_kernel<S, kAll, 2u>(nt, mul24);
+            if (lean == 1u) kernel = lean_kernel<S, 1u, 0u>(nt, mul24);
+            if (lean == 2u) kernel = lean_kernel<S, 2u, 0u>(nt, mul24);
+        }
+    }
+    // A rank table goes into LDS while at least kRankLdsGroups workgroups per CU (twelve waves) stay resident — or as many as the
+    // kernel's registers and codec blocks allow, when that is fewer: the runtime's own occupancy figure for this kernel at that much
+    // dynamic LDS, which knows the device's LDS per CU (kernel_setup keeps the answers).  The benchmark's products table (40 KB) leaves
+    // four workgroups on a 160 KB CU now that no codec block sits next to it.
+    constexpr int kRankLdsGroups = 3;
+    constexpr size_t kMaxLdsPerGroup = 64 * 1024;
+    int per_cu_regs = 1;
+    CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(kernel), kChainThreads, lds, &per_cu_regs));
     for (int s = 0; s < S; s++) {
         const cph_index* ix = steps[s].index;
         ChainStepArg& st = args.step[s];
@@ -813,12 +974,15 @@ static Status enqueue_dense(cph_ctx* ctx, const ChainStep* steps, uint64_t nprob
         } else if (positions) {
             CPH_TRY(index_ensure_ranktab(ctx, ix));
             st.ranktab = ix->ranktab ? ix->ranktab.as<uint2>() : nullptr;
-            // in LDS when three workgroups per CU stay resident: a lean kernel keeps the plain 8-byte blocks (cheaper
-            // lookups), the general one packs pairs of blocks into 12 bytes
+            // a lean kernel keeps the plain 8-byte blocks in LDS (cheaper lookups), the general one packs pairs of blocks into 12 bytes
             const size_t nblk = ranktab_blocks(ix->table_entries) / 2, rb = lean ? nblk * 16 : (nblk * 12 + 15) & ~(size_t)15;
-            if (st.ranktab && ctx->chain_rank_lds && lds + rank_lds_bytes + rb <= 52 * 1024) {
-                st.ranktab_lds = (int32_t)nblk;
-                rank_lds_bytes += rb;
+            if (st.ranktab && ctx->chain_rank_lds && lds + rank_lds_bytes + rb <= kMaxLdsPerGroup) {
+                int per_cu_with = 0;
+                CPH_TRY(kernel_setup(ctx, reinterpret_cast<const void*>(kernel), kChainThreads, lds + rank_lds_bytes + rb, &per_cu_with));
+                if (per_cu_with >= std::min(per_cu_regs, kRankLdsGroups)) {
+                    st.ranktab_lds = (int32_t)nblk;
+                    rank_lds_bytes += rb;
+                }
             }
         } else {
             CPH_TRY(index_ensure_rowtab(ctx, ix));
@@ -844,33 +1008,6 @@ static Status enqueue_dense(cph_ctx* ctx, const ChainStep* steps, uint64_t nprob
         args.out_rows[s] = d_rows[s];
     }
     lds += rank_lds_bytes;
-    args.nt_streams = ctx->chain_nt_streams == 1 || (ctx->chain_nt_streams == 2 && positions) ? 1 : 0;
-    const uint64_t ncounts = ntiles * kChainWaves;   // one match count per (tile, wave), tile-major
-    using KernelFn = void (*)(ChainArgs, uint64_t, uint64_t, uint64_t, uint64_t*, uint32_t*, int, LeanArgs);
-    static const KernelFn variants[2][2][2] = {
-        {{&k_chain_dense<S, false, false, false>, &k_chain_dense<S, false, false, true>},
-         {&k_chain_dense<S, false, true, false>, &k_chain_dense<S, false, true, true>}},
-        {{&k_chain_dense<S, true, false, false>, &k_chain_dense<S, true, false, true>},
-         {&k_chain_dense<S, true, true, false>, &k_chain_dense<S, true, true, true>}}};
-    KernelFn kernel = variants[long_keys ? 1 : 0][wide ? 1 : 0][(dbg && !dep) ? 1 : 0];
-    // register-heavy instantiations (tools/kernel_usage.sh: 256 VGPRs + AGPR copies at 8 rows per lane = ONE wave per SIMD) walk the
-    // wave's rows 4 at a time: long keys with 64-bit codes from two steps on, any long or wide chain from three steps on
-    if (!dbg && ctx->chain_rows4 != 0 && ((S == 2 && long_keys && wide) || (S >= 3 && (long_keys || wide)) || S == 4 || ctx->chain_rows4 == 2)) {
-        static const KernelFn r4[2][2] = {{&k_chain_dense<S, false, false, false, 0u, 4>, &k_chain_dense<S, false, true, false, 0u, 4>},
-                                          {&k_chain_dense<S, true, false, false, 0u, 4>, &k_chain_dense<S, true, true, false, 0u, 4>}};
-        kernel = r4[long_keys ? 1 : 0][wide ? 1 : 0];
-    }
-    if constexpr (S >= 2) {
-        if (dep) kernel = &k_chain_dense<S, true, true, false, 0u, 4, true>;
-    }
-    if (lean) {
-        constexpr uint32_t kAll = (1u << S) - 1u;
-        if (lean == kAll) kernel = &k_chain_dense<S, false, false, false, kAll>;
-        if constexpr (S == 2) {
-            if (lean == 1u) kernel = &k_chain_dense<S, false, false, false, 1u>;
-            if (lean == 2u) kernel = &k_chain_dense<S, false, false, false, 2u>;
-        }
-    }
     // persistent workgroups: exactly as many as are resident at once (no tail wave), each walking
     // tiles blockIdx, blockIdx + grid, ...
     int per_cu = 1, cus = 256;

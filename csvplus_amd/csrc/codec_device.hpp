@@ -218,6 +218,22 @@ __device__ __forceinline__ WaveRows<R> wave_rows(uint64_t wbase, uint64_t nrows 
     }
     return w;
 }
+// The same with the clamps behind a wave-uniform test: a FULL wave-tile (all but the stream's last one) compares and selects
+// nothing per row.
+template <int R>
+__device__ __forceinline__ WaveRows<R> wave_rows_full_first(uint64_t wbase, uint64_t nrows /* >= 1 */) {
+    if (nrows >= wbase + (uint64_t)(R * kWave)) {
+        WaveRows<R> w;
+        w.rbase = wbase;
+        w.nvalid = (uint32_t)(R * kWave);
+        w.okm = (1u << R) - 1u;
+        const uint32_t lane = (uint32_t)lane_id();
+#pragma unroll
+        for (int k = 0; k < R; k++) w.rel[k] = (uint32_t)k * kWave + lane;
+        return w;
+    }
+    return wave_rows<R>(wbase, nrows);
+}
 
 // Value spans of a wave's rows in one column.  B = uint32_t keeps one register per row (needs 32-bit offsets or a
 // fixed-width column); B = uint64_t handles every column.  The value of row k starts base8 + delta + x[k].
@@ -448,6 +464,14 @@ struct ArithPlan {
     uint32_t wa[2], wb[2]; // word w (positions 4w..4w+3): dot weights of positions (4w, 4w+1) and of (4w+2, 4w+3)
     uint32_t ma[2];        // word w: states of positions (4w+2, 4w+3)
     uint32_t s1;           // states of word 1 (positions 4..7)
+    // keys of DIFFERENT lengths (at most 8 bytes): position p's alphabet holds the pad exactly for p >= minlen, the pad has
+    // rank 0 and a byte rank byte - lo_p + 1 there.  var_enabled covers the equal-length codecs too (minlen == maxlen, no pad
+    // anywhere); lo / rngc / the weights above mean the same in both plans (a radix counts the pad), `enabled` and `keylen`
+    // are set for equal-length keys only.
+    uint32_t var_enabled;  // 0: the codec does not qualify for the variable-length encode either
+    uint32_t minlen;       // shortest index key
+    uint32_t lenspan;      // longest - shortest index key
+    uint32_t padin[2];     // byte p: 1 when position p's alphabet holds the pad
 };
 
 // host (keycodec.hip): fills *ap; ap->enabled = 0 when the codec does not qualify
@@ -455,7 +479,21 @@ void codec_arith_plan(const CodecHost& codec, ArithPlan* ap);
 
 // c0[k] = the 8 bytes of row k's value (callers use the plan only when keylen == 8: chain.hip's lean steps).  Clears the okm bit of a row
 // whose key cannot occur in the index.
-template <int R, class CW>
+// The mixed-radix value of the ranks in the bytes of (zl, zh).  M24 = 1 / 0: the 24-bit / the full multiplies, compiled in alone.
+template <int M24>
+__device__ __forceinline__ uint32_t arith_dot(const ArithPlan& ap, uint32_t zl, uint32_t zh) {
+    const uint32_t pa0 = __builtin_amdgcn_udot4(zl, ap.wa[0], 0u, false);
+    const uint32_t pa1 = __builtin_amdgcn_udot4(zh, ap.wa[1], 0u, false);
+    if constexpr (M24 != 0) {
+        const uint32_t w0 = __builtin_amdgcn_udot4(zl, ap.wb[0], __umul24(pa0, ap.ma[0]), false);
+        return __builtin_amdgcn_udot4(zh, ap.wb[1], __umul24(pa1, ap.ma[1]) + __umul24(w0, ap.s1), false);
+    } else {
+        const uint32_t w0 = __builtin_amdgcn_udot4(zl, ap.wb[0], pa0 * ap.ma[0], false);
+        return __builtin_amdgcn_udot4(zh, ap.wb[1], pa1 * ap.ma[1] + w0 * ap.s1, false);
+    }
+}
+// M24 = -1: ap.mul24 decides at run time (a uniform branch around the rows)
+template <int R, class CW, int M24 = -1>
 __device__ __forceinline__ void encode_rows_arith(const ArithPlan& ap, const uint64_t (&c0)[R], CW (&code)[R], uint32_t* okmask) {
     uint32_t m = *okmask;
     uint32_t zl[R], zh[R];
@@ -468,22 +506,44 @@ __device__ __forceinline__ void encode_rows_arith(const ArithPlan& ap, const uin
         const uint32_t bad = ((xl | zl[k] | tl) | (xh | zh[k] | th)) & 0x80808080u;
         if (bad) m &= ~(1u << k);
     }
-    if (ap.mul24) {   // uniform, outside the row loop: one branch per wave-tile
+    if (M24 < 0 ? ap.mul24 != 0 : M24 != 0) {   // uniform, outside the row loop: one branch per wave-tile
 #pragma unroll
-        for (int k = 0; k < R; k++) {
-            const uint32_t pa0 = __builtin_amdgcn_udot4(zl[k], ap.wa[0], 0u, false);
-            const uint32_t pa1 = __builtin_amdgcn_udot4(zh[k], ap.wa[1], 0u, false);
-            const uint32_t w0 = __builtin_amdgcn_udot4(zl[k], ap.wb[0], __umul24(pa0, ap.ma[0]), false);
-            code[k] = (CW)__builtin_amdgcn_udot4(zh[k], ap.wb[1], __umul24(pa1, ap.ma[1]) + __umul24(w0, ap.s1), false);
-        }
+        for (int k = 0; k < R; k++) code[k] = (CW)arith_dot<1>(ap, zl[k], zh[k]);
     } else {
 #pragma unroll
-        for (int k = 0; k < R; k++) {
-            const uint32_t pa0 = __builtin_amdgcn_udot4(zl[k], ap.wa[0], 0u, false);
-            const uint32_t pa1 = __builtin_amdgcn_udot4(zh[k], ap.wa[1], 0u, false);
-            const uint32_t w0 = __builtin_amdgcn_udot4(zl[k], ap.wb[0], pa0 * ap.ma[0], false);
-            code[k] = (CW)__builtin_amdgcn_udot4(zh[k], ap.wb[1], pa1 * ap.ma[1] + w0 * ap.s1, false);
-        }
+        for (int k = 0; k < R; k++) code[k] = (CW)arith_dot<0>(ap, zl[k], zh[k]);
+    }
+    *okmask = m;
+}
+
+// The same for keys of different lengths (ap.var_enabled): c0[k] = 8 bytes from the first byte of row k's value on, len[k] its
+// length.  The bytes past the value belong to the next one: they are replaced by LO before anything looks at them, so they pass the
+// range test, give z = 0 and neither borrow nor carry.  A position that holds the pad ranks its bytes from 1 on: PADIN is added
+// where the value has a byte.  A value shorter than the shortest or longer than the longest index key cannot be in the index.
+template <int R, class CW, int M24 = -1>
+__device__ __forceinline__ void encode_rows_arith_var(const ArithPlan& ap, const uint64_t (&c0)[R], const uint32_t (&len)[R], CW (&code)[R],
+                                                      uint32_t* okmask) {
+    uint32_t m = *okmask;
+    uint32_t rl[R], rh[R];
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+        const uint32_t sh = (len[k] < 8u ? len[k] : 8u) << 2;
+        const uint64_t past = (~0ull << sh) << sh;   // the bytes past the value (none of 8, all of an empty one)
+        const uint32_t pl = (uint32_t)past, ph = (uint32_t)(past >> 32);
+        const uint32_t xl = (pl & ap.lo[0]) | (~pl & (uint32_t)c0[k]), xh = (ph & ap.lo[1]) | (~ph & (uint32_t)(c0[k] >> 32));
+        const uint32_t zl = xl - ap.lo[0], zh = xh - ap.lo[1];
+        const uint32_t tl = zl + ap.rngc[0], th = zh + ap.rngc[1];
+        const uint32_t bad = ((xl | zl | tl) | (xh | zh | th)) & 0x80808080u;
+        if (bad != 0u || len[k] - ap.minlen > ap.lenspan) m &= ~(1u << k);
+        rl[k] = zl + (~pl & ap.padin[0]);
+        rh[k] = zh + (~ph & ap.padin[1]);
+    }
+    if (M24 < 0 ? ap.mul24 != 0 : M24 != 0) {
+#pragma unroll
+        for (int k = 0; k < R; k++) code[k] = (CW)arith_dot<1>(ap, rl[k], rh[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < R; k++) code[k] = (CW)arith_dot<0>(ap, rl[k], rh[k]);
     }
     *okmask = m;
 }
