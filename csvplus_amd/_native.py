@@ -179,12 +179,13 @@ class cph_numcol(C.Structure):
                 ("host_rows", C.c_uint64)]
 
 
-CPH_MAP_LITERAL, CPH_MAP_COLUMN, CPH_MAP_INT64 = 1, 2, 3
+CPH_MAP_LITERAL, CPH_MAP_COLUMN, CPH_MAP_INT64, CPH_MAP_FLOAT64 = 1, 2, 3, 4
 CPH_MAP_MAX_PIECES = 16
 
 
 class cph_map_piece(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("arg", C.c_int32), ("value", cph_strval), ("ints", C.c_void_p)]
+    _fields_ = [("kind", C.c_int32), ("arg", C.c_int32), ("value", cph_strval), ("ints", C.c_void_p),
+                ("floats", C.c_void_p), ("prec", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class cph_groups(C.Structure):

@@ -2,25 +2,33 @@
 //
 //   cph_map_format  value i of the new column = the template's pieces in order: literal bytes, the value of a column in
 //                   row i (read through that column's row ids, as the writers read a joined row), an int64 written as
-//                   strconv.FormatInt(v, 10).  Bytes are copied verbatim; nothing is escaped.
+//                   strconv.FormatInt(v, 10), a float64 written as strconv.FormatFloat(v, 'f', prec, 64) (numformat_device.hpp).
+//                   Bytes are copied verbatim; nothing is escaped.
 //
 // The pipeline of the gather and of the two-pass CSV writer (materialize.hip): k_map_lens (bytes per row: offsets only, the
 // literals' total, digit counts by compares) -> exclusive scan, whose nrows + 1 entries ARE the result column's offsets ->
 // k_map_copy (a tile's rows assembled in the LDS stage 8 value bytes at a time, streamed out with 16-byte stores; a tile
 // beyond the stage writes its rows to global memory itself).  Two passes, no look-back and no waiting between workgroups.
 // The literals are packed into one small device block that every row reads 8 bytes at a time.
+// A template with a FLOAT64 piece runs its own instantiations of both kernels (k_map_lens_f64 / k_map_copy_f64): the others
+// carry no float code.  The length pass of those also finds the lowest row whose value is beyond the formatter's range; the
+// row number comes back in the same copy as the scan's total.
 #include <new>
 #include <string>
 
 #include "materialize_device.hpp"
+#include "numformat_device.hpp"
 
 namespace cph {
 
 struct MapPiece {
     int32_t kind;          // CPH_MAP_*
-    int32_t col;           // COLUMN: the column
+    int32_t col;           // COLUMN: the column; FLOAT64: prec
     uint32_t off, len;     // LITERAL: its bytes in MapPlan::lits
-    const int64_t* ints;   // INT64: one value per output row, on the device
+    union {
+        const int64_t* ints;    // INT64: one value per output row, on the device
+        const double* floats;   // FLOAT64: likewise
+    };
 };
 struct MapPlan {
     const uint8_t* lits;
@@ -76,8 +84,9 @@ __device__ __forceinline__ void pick_field(const RecordFields<NC>& f, int c, uin
         if (k == c) *b = f.b[k], *l = f.l[k], *c0 = f.c0[k];
 }
 
-// lens[i] = bytes of value i
-template <int NC>
+// lens[i] = bytes of value i.  FL (the plan has a FLOAT64 piece): lens[n + 1], preset to UINT64_MAX, = the lowest row with a
+// value the formatter refuses.
+template <int NC, bool FL = false>
 __global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, uint64_t* __restrict__ lens) {
     const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;
     for (uint64_t i = (uint64_t)blockIdx.x * kMatThreads + threadIdx.x; i < n; i += stride) {
@@ -88,6 +97,10 @@ __global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds i
             const MapPiece& p = plan.p[k];
             if (p.kind == CPH_MAP_INT64) {
                 total += int_chars(p.ints[i]);
+            } else if (FL && p.kind == CPH_MAP_FLOAT64) {
+                const FixedParts r = fixed_split(p.floats[i], p.col);
+                total += fixed_chars(r, p.col);
+                if (r.kind == FIXED_RANGE) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
             } else if (p.kind == CPH_MAP_COLUMN) {
                 uint64_t b, l, c0;
                 if constexpr (NC > 0) pick_field(f, p.col, &b, &l, &c0);
@@ -98,8 +111,11 @@ __global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds i
         lens[i] = total;
     }
 }
+// the float instantiations under names CPH_CSV_DISPATCH can take
+template <int NC>
+constexpr auto k_map_lens_f64 = k_map_lens<NC, true>;
 
-template <int NC, class Sink>
+template <int NC, bool FL, class Sink>
 __device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, const ColIds& ids, const MapPlan& plan, const RecordFields<NC>& f,
                                                uint64_t i) {
     for (int k = 0; k < plan.npieces; k++) {
@@ -109,6 +125,8 @@ __device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, con
                 s.put8(load_value_chunk(plan.lits, p.off, p.len, (int)(q >> 3)), p.len - q < 8u ? p.len - q : 8u);
         } else if (p.kind == CPH_MAP_INT64) {
             put_int(s, p.ints[i]);
+        } else if (FL && p.kind == CPH_MAP_FLOAT64) {
+            fixed_put(s, fixed_split(p.floats[i], p.col), p.col);
         } else {
             const uint8_t* data = cols.c[p.col].data;
             uint64_t b, l, c0;
@@ -127,7 +145,7 @@ __device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, con
 }
 
 // value i at out + offs[i]
-template <int NC>
+template <int NC, bool FL = false>
 __global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, const uint64_t* __restrict__ offs,
                                                          uint8_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -148,11 +166,11 @@ __global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds i
         if (i < tend) {
             if (staged) {
                 WordSink s(reinterpret_cast<uint32_t*>(smem), (uint32_t)((offs[i] - obase) + (obase & 15)));
-                map_put_record<NC>(s, cols, ids, plan, f, i);
+                map_put_record<NC, FL>(s, cols, ids, plan, f, i);
                 s.finish();
             } else {
                 GlobalSink s{out + offs[i]};
-                map_put_record<NC>(s, cols, ids, plan, f, i);
+                map_put_record<NC, FL>(s, cols, ids, plan, f, i);
             }
         }
         if (staged) {
@@ -162,6 +180,8 @@ __global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds i
         }
     }
 }
+template <int NC>
+constexpr auto k_map_copy_f64 = k_map_copy<NC, true>;
 
 }  // namespace cph
 
@@ -182,6 +202,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
     if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
     const uint64_t n = nrows;
     uint64_t lit_bytes = 0;
+    bool has_float = false;
     for (int k = 0; k < npieces; k++) {
         const cph_map_piece& p = pieces[k];
         switch (p.kind) {
@@ -197,8 +218,14 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                 if (p.arg != CPH_MEM_HOST && p.arg != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: bad memory space of an INT64 piece"});
                 if (!p.ints && n) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: an INT64 piece without values"});
                 break;
+            case CPH_MAP_FLOAT64:
+                if (p.arg != CPH_MEM_HOST && p.arg != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: bad memory space of a FLOAT64 piece"});
+                if (!p.floats && n) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: a FLOAT64 piece without values"});
+                if (p.prec < 0 || p.prec > kFixedMaxPrec) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: prec of a FLOAT64 piece outside 0..22"});
+                has_float = true;
+                break;
             default:
-                return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: unknown piece kind (1..3)"});
+                return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: unknown piece kind (1..4)"});
         }
     }
     {
@@ -213,7 +240,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         ColsArg arg{};
         ColIds ids{};
         CPH_TRY(stage_row_sources(ctx, cols, sel, nullptr, ncols, 0, n, &staged, &arg, &ids));
-        CPH_TRY(r->d_offs.alloc(&ctx->pool, (n + 1) * sizeof(uint64_t)));
+        CPH_TRY(r->d_offs.alloc(&ctx->pool, (n + (has_float ? 2 : 1)) * sizeof(uint64_t)));   // a float plan: + the refused row
         uint64_t* offs = r->d_offs.as<uint64_t>();
         uint64_t total = 0;
         if (n) {
@@ -236,14 +263,20 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                         if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
                     }
                     plan.col_mask |= 1u << p.arg;
-                } else {
-                    d.ints = p.ints;
+                } else {   // INT64 / FLOAT64: 8 bytes per row
+                    const void* vals = p.kind == CPH_MAP_INT64 ? static_cast<const void*>(p.ints) : static_cast<const void*>(p.floats);
                     in_bytes += 8.0;
                     if (p.arg == CPH_MEM_HOST) {   // staged like the row ids of a host column
                         staged.emplace_back();
                         CPH_TRY(staged.back().alloc(&ctx->pool, n * sizeof(int64_t)));
-                        CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), p.ints, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-                        d.ints = staged.back().as<int64_t>();
+                        CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), vals, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+                        vals = staged.back().get();
+                    }
+                    if (p.kind == CPH_MAP_INT64) {
+                        d.ints = static_cast<const int64_t*>(vals);
+                    } else {
+                        d.floats = static_cast<const double*>(vals);
+                        d.col = p.prec;
                     }
                 }
             }
@@ -257,16 +290,46 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                 CPH_HIP_TRY(hipMemcpyAsync(litbuf.get(), slot, lits.size(), hipMemcpyHostToDevice, ctx->stream));
             }
             plan.lits = litbuf.as<uint8_t>();
-            {
+            if (has_float) {
+                CPH_HIP_TRY(hipMemsetAsync(offs + n + 1, 0xFF, sizeof(uint64_t), ctx->stream));
+                ProfScope ps(ctx, "k_map_lens", 0);
+                CPH_CSV_DISPATCH(k_map_lens_f64, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, offs);
+            } else {
                 ProfScope ps(ctx, "k_map_lens", 0);
                 CPH_CSV_DISPATCH(k_map_lens, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, offs);
             }
             CPH_HIP_TRY(hipGetLastError());
-            CPH_TRY(scan_lengths(ctx, offs, n, &total));
+            if (has_float) {   // the total and the refused row in one copy: the call's one host wait
+                CPH_TRY(exclusive_scan_u64(ctx, offs, n, offs + n));
+                struct { uint64_t total, bad; } tail;
+                CPH_TRY(read_device_value(ctx, reinterpret_cast<const decltype(tail)*>(offs + n), &tail));
+                if (tail.bad != UINT64_MAX) {
+                    int piece = 0;   // the first FLOAT64 piece with such a value in that row
+                    for (int k = 0; k < npieces; k++) {
+                        if (pieces[k].kind != CPH_MAP_FLOAT64) continue;
+                        double v = 0;
+                        if (pieces[k].arg == CPH_MEM_HOST) v = pieces[k].floats[tail.bad];
+                        else CPH_HIP_TRY(hipMemcpy(&v, pieces[k].floats + tail.bad, sizeof v, hipMemcpyDeviceToHost));
+                        if (fixed_split(v, 0).kind == FIXED_RANGE) {
+                            piece = k;
+                            break;
+                        }
+                    }
+                    return Status{CPH_ERR_INVALID, "cph_map_format: FLOAT64 piece " + std::to_string(piece) + ", row " + std::to_string(tail.bad) +
+                                                       ": a finite value of 2^128 or more is not formatted"};
+                }
+                total = tail.total;
+            } else {
+                CPH_TRY(scan_lengths(ctx, offs, n, &total));
+            }
             CPH_TRY(r->d_data.alloc(&ctx->pool, total + 16));
             if (total) {
                 ProfScope ps(ctx, "k_map_copy", 2.0 * (double)total + (8.0 + in_bytes) * (double)n);
-                CPH_CSV_DISPATCH(k_map_copy, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, offs, r->d_data.as<uint8_t>());
+                if (has_float) {
+                    CPH_CSV_DISPATCH(k_map_copy_f64, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, offs, r->d_data.as<uint8_t>());
+                } else {
+                    CPH_CSV_DISPATCH(k_map_copy, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, offs, r->d_data.as<uint8_t>());
+                }
                 CPH_HIP_TRY(hipGetLastError());
             }
             // the kernels read the literal block and the staged arrays: they go back to the pool behind deliver's wait

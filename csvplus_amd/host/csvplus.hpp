@@ -52,6 +52,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -216,6 +217,21 @@ inline int32_t ParseFloat(const std::string& s, double* out) {
     *out = c_locale ? strtod_l(s.c_str(), nullptr, c_locale) : strtod(s.c_str(), nullptr);   // correctly rounded (glibc)
     return std::isinf(*out) ? CPH_NUM_ERR_RANGE : CPH_NUM_OK;
 }
+// the reference's message for a value that does not convert (:176 / :198); err = CPH_NUM_ERR_*
+inline std::string conversionError(const std::string& column, const std::string& value, int32_t kind, int32_t err) {
+    const char* what = err == CPH_NUM_ERR_SYNTAX  ? "invalid syntax"
+                       : err == CPH_NUM_ERR_RANGE ? "value out of range"
+                                                  : "not decided by this library (digit separators, hexadecimal floats)";
+    return "column " + quote(column) + ": cannot convert " + quote(value) + " to " + (kind == CPH_NUM_INT64 ? "integer" : "float") + ": " + what;
+}
+// strconv.FormatFloat(v, 'f', prec, 64) on the host: glibc's exact "%.*f" and Go's spellings of NaN and the infinities
+inline std::string FormatFixed(double v, int prec) {
+    if (std::isnan(v)) return "NaN";
+    if (std::isinf(v)) return v < 0 ? "-Inf" : "+Inf";
+    std::string out((size_t)snprintf(nullptr, 0, "%.*f", prec, v), '\0');
+    snprintf(&out[0], out.size() + 1, "%.*f", prec, v);
+    return out;
+}
 
 class Pred {
 public:
@@ -333,27 +349,40 @@ inline Pred Any(const Pred& first, const P&... more) { return Any(std::vector<Pr
 // `row["name"] = "Julia"` is Set("name", "Julia"); `row["full"] = row["name"] + " " + row["surname"]` is
 // Set("full", Format({Col("name"), " ", Col("surname")})).  A row that lacks a Col's column takes the Col's default
 // (Row.SafeGetValue, :69-75); without a default the iteration ends with the reference's `missing column` error at that row.
+// Fixed(Col("price"), 2) is the column's value read as Row.ValueAsFloat64 reads it and written back as
+// strconv.FormatFloat(v, 'f', 2, 64) writes it (prec 0..22; a finite value of 2^128 or more is refused by the device); a value
+// that does not parse ends the iteration at that row with ValueAsFloat64's error.  Arithmetic between columns is not part of it.
 struct Col {
     std::string name, fallback;
     bool has_default = false;
     explicit Col(std::string n) : name(std::move(n)) {}
     Col(std::string n, std::string dflt) : name(std::move(n)), fallback(std::move(dflt)), has_default(true) {}
 };
-struct Part {   // a literal or a column
+struct Fixed {
+    Col col;
+    int prec;
+    Fixed(Col c, int p) : col(std::move(c)), prec(p) {
+        if (p < 0 || p > 22) throw Panic("Fixed(): prec outside 0..22");
+    }
+};
+struct Part {   // a literal, a column, or a column as a fixed-precision number
     bool is_col = false;
     std::string text;   // the literal's bytes
     Col col{""};
+    int prec = -1;      // >= 0: Fixed
     Part(const char* lit) : text(lit) {}                 // NOLINT: implicit, so that a template reads like the expression
     Part(std::string lit) : text(std::move(lit)) {}      // NOLINT
     Part(Col c) : is_col(true), col(std::move(c)) {}     // NOLINT
+    Part(Fixed f) : is_col(true), col(std::move(f.col)), prec(f.prec) {}   // NOLINT
 };
 struct Format {
     std::vector<Part> parts;
     explicit Format(std::vector<Part> p) : parts(std::move(p)) {
         if (parts.empty()) throw Panic("empty template in Format()");
     }
-    // the template on one row, on the host (what the device computes for a whole batch); *missing gets the first absent column
-    bool render(const Row& row, std::string* out, std::string* missing) const {
+    // the template on one row, on the host (what the device computes for a whole batch); *missing gets the first absent column,
+    // *invalid (when given) ValueAsFloat64's message for a Fixed part's value that does not parse
+    bool render(const Row& row, std::string* out, std::string* missing, std::string* invalid = nullptr) const {
         out->clear();
         for (const Part& p : parts) {
             if (!p.is_col) {
@@ -361,12 +390,22 @@ struct Format {
                 continue;
             }
             auto it = row.find(p.col.name);
-            if (it != row.end()) *out += it->second;
-            else if (p.col.has_default) *out += p.col.fallback;
-            else {
+            const std::string* v = it != row.end() ? &it->second : p.col.has_default ? &p.col.fallback : nullptr;
+            if (!v) {
                 *missing = p.col.name;
                 return false;
             }
+            if (p.prec < 0) {
+                *out += *v;
+                continue;
+            }
+            double d;
+            const int32_t rc = ParseFloat(*v, &d);
+            if (rc != CPH_NUM_OK) {
+                if (invalid) *invalid = conversionError(p.col.name, *v, CPH_NUM_FLOAT64, rc);
+                return false;
+            }
+            *out += FormatFixed(d, p.prec);
         }
         return true;
     }
@@ -378,6 +417,7 @@ struct Assign {
 inline Assign Set(std::string name, std::string literal) { return Assign{std::move(name), Format({Part(std::move(literal))})}; }
 inline Assign Set(std::string name, const char* literal) { return Set(std::move(name), std::string(literal)); }
 inline Assign Set(std::string name, Format value) { return Assign{std::move(name), std::move(value)}; }
+inline Assign Set(std::string name, Fixed value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
 
 using RowFunc = std::function<Error(Row)>;
 
@@ -792,17 +832,22 @@ public:
         return DataSource([src, shared, required](const RowFunc& fn) -> Error {
             cph_ctx* ctx = Gpu::Default().ctx();
             return batched(src, required, [&](std::vector<Row>* batch) -> Error {
+                Error pending;   // a Fixed part's value did not parse: the rows in front of it go through, then this surfaces
                 for (const Assign& a : *shared) {
-                    Error e = mapBatch(ctx, a, batch);
-                    if (e) {
+                    size_t good = 0;
+                    Error e = mapBatch(ctx, a, batch, &good);
+                    if (!e) continue;
+                    if (good == 0) {
                         batch->clear();
                         return e;
                     }
+                    batch->resize(good);
+                    pending = e;
                 }
                 Error err;
                 for (size_t i = 0; i < batch->size() && !err; i++) err = fn(std::move((*batch)[i]));
                 batch->clear();
-                return err;
+                return err ? err : pending;
             });
         });
     }
@@ -897,11 +942,7 @@ private:
         if (rc != CPH_OK) throw Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
         if (nc->nerrors) {
             const uint64_t row = nc->first_error_row;
-            const char* what = nc->first_error_kind == CPH_NUM_ERR_SYNTAX  ? "invalid syntax"
-                               : nc->first_error_kind == CPH_NUM_ERR_RANGE ? "value out of range"
-                                                                           : "not decided by this library (digit separators, hexadecimal floats)";
-            const std::string msg = "column " + quote(name) + ": cannot convert " + quote(values[(size_t)row]) + " to " +
-                                    (kind == CPH_NUM_INT64 ? "integer" : "float") + ": " + what;
+            const std::string msg = conversionError(name, values[(size_t)row], kind, nc->first_error_kind);
             cph_numcol_release(nc);
             throw Error::DataSourceError(row, Error(msg));
         }
@@ -1049,15 +1090,56 @@ private:
 
     // One assignment over a batch: row[a.name] = the template's value, for every row, by one cph_map_format call.  A row that
     // lacks a column gets the Col's default in its place (the caller has turned away rows that lack a column without one).
-    static Error mapBatch(cph_ctx* ctx, const Assign& a, std::vector<Row>* batch) {
-        const size_t n = batch->size();
+    // A Fixed part's column goes through cph_col_to_number first (ColumnAsFloat64's path) and into a FLOAT64 piece.  Where
+    // such a value does not parse, the rows in front of it are mapped, *good is their number and ValueAsFloat64's error
+    // comes back; on any other error *good is 0.
+    static Error mapBatch(cph_ctx* ctx, const Assign& a, std::vector<Row>* batch, size_t* good) {
+        size_t n = batch->size();
+        *good = 0;
         if (n == 0) return Error();
         std::vector<std::string> columns;
         std::vector<const std::string*> fallback;
         std::vector<cph_map_piece> pieces;
+        struct NumCols {   // the converted columns live until the template has run
+            std::vector<cph_numcol*> v;
+            ~NumCols() {
+                for (cph_numcol* c : v) cph_numcol_release(c);
+            }
+        } nums;
+        Error pending;
+        for (const Part& p : a.value.parts) {
+            if (p.prec < 0) continue;
+            std::vector<std::vector<const std::string*>> vals(1);
+            vals[0].resize(n);
+            for (size_t i = 0; i < n; i++) {
+                auto it = (*batch)[i].find(p.col.name);
+                vals[0][i] = it == (*batch)[i].end() ? &p.col.fallback : &it->second;
+            }
+            cph_numcol* nc = nullptr;
+            int32_t rc;
+            {
+                detail::StagedColumns st(ctx, 1);
+                st.stage(vals, n);
+                rc = cph_col_to_number(ctx, st.cols(), nullptr, n, CPH_NUM_FLOAT64, CPH_MEM_HOST, &nc);
+            }
+            if (rc != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+            nums.v.push_back(nc);
+            if (nc->nerrors) {   // an earlier part's later row no longer counts
+                const size_t row = (size_t)nc->first_error_row;
+                pending = Error(conversionError(p.col.name, *vals[0][row], CPH_NUM_FLOAT64, nc->first_error_kind));
+                n = row;
+                if (n == 0) return pending;
+            }
+        }
+        size_t fixed_seen = 0;
         for (const Part& p : a.value.parts) {
             if (!p.is_col) {
                 pieces.push_back(cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr});
+                continue;
+            }
+            if (p.prec >= 0) {
+                pieces.push_back(cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr,
+                                               static_cast<const double*>(nums.v[fixed_seen++]->values), p.prec, 0});
                 continue;
             }
             size_t c = (size_t)(std::find(columns.begin(), columns.end(), p.col.name) - columns.begin());
@@ -1089,7 +1171,8 @@ private:
         const char* data = reinterpret_cast<const char*>(cb->col.data);
         for (size_t i = 0; i < n; i++) (*batch)[i][a.name].assign(data + offs[i], (size_t)(offs[i + 1] - offs[i]));
         cph_colbuf_release(cb);
-        return Error();
+        *good = pending ? n : batch->size();
+        return pending;
     }
     static uint64_t& map_calls_counter() {
         static uint64_t n = 0;

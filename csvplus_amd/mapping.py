@@ -8,21 +8,31 @@ the new column in row i is the concatenation of the template's parts —
     Col("name")          the row's value of that column; Col("name", default=b"x") substitutes the default where the
                          rows have no such column (Row.SafeGetValue, csvplus.go:69-75);
     Int(array)           array[i] written as strconv.Itoa writes it ('-' for negatives, no '+', no leading zeros); the array
-                         lives on the host, or on the device: Int.on_device(device_ptr, count).
+                         lives on the host, or on the device: Int.on_device(device_ptr, count);
+    Float(array, prec)   array[i] written as strconv.FormatFloat(v, 'f', prec, 64) writes it: prec digits behind the point,
+                         rounded half-even on the exact binary value — the reference's amounts column,
+                         `strconv.FormatFloat(price*float64(qty), 'f', 2, 64)` (csvplus_test.go:1391-1421).  prec is 0..22 and
+                         finite values of 2^128 or more are refused, on the device and by the host model alike; host or
+                         device array as for Int: Float.on_device(device_ptr, count, prec).
 
 `compile` turns a template into the piece list cph_map_format takes (include/csvplus_hip.h), `render` evaluates it on one
 row held as a dict — the host model, for callers without a GPU and as the cross-check of the device.  Nothing here
-touches the GPU.  Formatting floats, case mapping, trimming, substrings and conditional parts are out of scope.
+touches the GPU.  FormatFloat's other forms (shortest round-trip digits, 'e' and 'g'), case mapping, trimming, substrings
+and conditional parts are out of scope.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
 from .predicates import INT64_MAX, INT64_MIN, _bytes, _go_quote
 
-LITERAL, COLUMN, INT64 = 1, 2, 3   # CPH_MAP_*
+LITERAL, COLUMN, INT64, FLOAT64 = 1, 2, 3, 4   # CPH_MAP_*
 MAX_PIECES = 16                    # CPH_MAP_MAX_PIECES
 MAX_COLUMNS = 16                   # CPH_MAX_KEY_COLS
+MAX_PREC = 22                      # a FLOAT64 piece's prec: 0..22
+FLOAT_LIMIT = 2.0 ** 128           # finite |v| at or above it is not formatted
 
 
 class MissingColumn(LookupError):
@@ -70,6 +80,37 @@ class Int:
         return f"Int(<{self.count} values{' on the device' if self.device else ''}>)"
 
 
+def _check_prec(prec, who) -> int:
+    if isinstance(prec, bool) or int(prec) != prec or not 0 <= int(prec) <= MAX_PREC:
+        raise ValueError(f"{who}: prec must be within 0..{MAX_PREC}, not {prec!r}")
+    return int(prec)
+
+
+class Float:
+    """One float64 per OUTPUT row, formatted as strconv.FormatFloat(v, 'f', prec, 64) does.  Float(values, prec): anything
+    numpy turns into a float64 array (an integer array is converted, as Go's float64(qty) would), in host memory;
+    Float.on_device(device_ptr, count, prec): a float64 array on the device, e.g. NumCol.values of
+    materialize.to_float(..., out_mem=DEVICE) after arithmetic on it.  prec: 0..22."""
+
+    def __init__(self, values, prec):
+        self.prec = _check_prec(prec, "Float")
+        arr = np.asarray(values)
+        if arr.dtype.kind not in "fiub":
+            raise ValueError("Float: the array does not hold numbers")
+        self.device, self.values = False, np.ascontiguousarray(arr.astype(np.float64, copy=False).reshape(-1))
+        self.count = len(self.values)
+
+    @classmethod
+    def on_device(cls, device_ptr: int, count: int, prec: int) -> "Float":
+        self = cls.__new__(cls)
+        self.prec = _check_prec(prec, "Float.on_device")
+        self.device, self.values, self.count = True, int(device_ptr), int(count)
+        return self
+
+    def __repr__(self):
+        return f"Float(<{self.count} values{' on the device' if self.device else ''}>, {self.prec})"
+
+
 class Format:
     """Format(part, ...): the concatenation of the parts (see the module text)."""
 
@@ -78,12 +119,12 @@ class Format:
             raise ValueError("Format: no parts")
         self.parts = []
         for p in parts:
-            if isinstance(p, (Col, Int)):
+            if isinstance(p, (Col, Int, Float)):
                 self.parts.append(p)
             elif isinstance(p, (bytes, bytearray, memoryview, str)):
                 self.parts.append(_bytes(p))
             else:
-                raise TypeError(f"not a template part: {p!r} (closures cannot run on the device; use bytes / str, Col, Int)")
+                raise TypeError(f"not a template part: {p!r} (closures cannot run on the device; use bytes / str, Col, Int, Float)")
 
     def __repr__(self):
         return f"Format{tuple(self.parts)!r}"
@@ -97,7 +138,7 @@ def Const(value) -> Format:
 def _template(t) -> Format:
     if isinstance(t, Format):
         return t
-    if isinstance(t, (Col, Int, bytes, bytearray, memoryview, str)):
+    if isinstance(t, (Col, Int, Float, bytes, bytearray, memoryview, str)):
         return Format(t)
     raise TypeError(f"not a template: {t!r}")
 
@@ -113,7 +154,7 @@ def columns(template) -> list:
 
 def compile(template, column_names):   # noqa: A001 (the name predicates.compile uses)
     """(names of the columns used, pieces).  A piece is (LITERAL, 0, bytes), (COLUMN, k, None) with k indexing the returned
-    name list, or (INT64, 0, Int).  A Col whose name is not among `column_names` becomes its default as a literal — in
+    name list, (INT64, 0, Int) or (FLOAT64, 0, Float).  A Col whose name is not among `column_names` becomes its default as a literal — in
     structure-of-arrays a column is present for all rows or for none — and without a default raises MissingColumn.
     Neighbouring literals are joined.  Raises ValueError beyond the ABI's limits (16 pieces, 16 columns)."""
     known = [str(c) for c in column_names]
@@ -131,6 +172,8 @@ def compile(template, column_names):   # noqa: A001 (the name predicates.compile
             literal(p)
         elif isinstance(p, Int):
             pieces.append((INT64, 0, p))
+        elif isinstance(p, Float):
+            pieces.append((FLOAT64, 0, p))
         elif p.name in known:
             if p.name not in used:
                 used.append(p.name)
@@ -154,9 +197,24 @@ def itoa(v) -> bytes:
     return b"%d" % v
 
 
+def ftoa(v, prec) -> bytes:
+    """strconv.FormatFloat(v, 'f', prec, 64) of a float64, prec 0..22.  For finite values Python's own %.*f: correctly
+    rounded, half-even on the exact binary value, and the sign of a result that rounds to zero stays.  Raises ValueError for
+    a finite |v| of 2^128 or more: the model refuses what the device refuses."""
+    prec = _check_prec(prec, "ftoa")
+    v = float(v)
+    if math.isnan(v):
+        return b"NaN"
+    if math.isinf(v):
+        return b"-Inf" if v < 0 else b"+Inf"
+    if abs(v) >= FLOAT_LIMIT:
+        raise ValueError("ftoa: a finite value of 2^128 or more is not formatted")
+    return b"%.*f" % (prec, v)
+
+
 def render(template, row, i: int = 0) -> bytes:
     """The template on one row (a dict with str or bytes keys and values); `i` = the row's number, which is what an Int
-    part is indexed with (host arrays only)."""
+    or Float part is indexed with (host arrays only)."""
     out = []
     for p in _template(template).parts:
         if isinstance(p, bytes):
@@ -165,6 +223,10 @@ def render(template, row, i: int = 0) -> bytes:
             if p.device:
                 raise ValueError("render: an Int part on the device has no host values")
             out.append(itoa(p.values[i]))
+        elif isinstance(p, Float):
+            if p.device:
+                raise ValueError("render: a Float part on the device has no host values")
+            out.append(ftoa(p.values[i], p.prec))
         else:
             v = row.get(p.name)
             if v is None:

@@ -415,8 +415,8 @@ def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None,
     cols_by_name: {column name: StrCol} — the row the template sees; a Col whose name the mapping lacks becomes its default
     or raises mapping.MissingColumn.  template: mapping.Format / Const (or a bare part).  row_ids: {name: ids} as in
     filter_rows, for columns read through row ids (a Join's); nrows: the number of rows (default: what the columns, the row
-    ids or the Int parts give).  An Int part's array is indexed by OUTPUT row and lives on the host (numpy) or on the device
-    (Int.on_device)."""
+    ids or the Int / Float parts give).  An Int or Float part's array is indexed by OUTPUT row and lives on the host (numpy) or
+    on the device (Int.on_device, Float.on_device)."""
     from . import mapping as M
 
     names, pieces = M.compile(template, list(cols_by_name))
@@ -427,7 +427,7 @@ def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None,
         arr, sel, n = _rowsel(cols, ids, nrows, keep)
     else:
         arr, sel = None, None
-        counts = [p[2].count for p in pieces if p[0] == M.INT64]
+        counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64)]
         if nrows is not None:
             n = int(nrows)
         elif counts:
@@ -435,7 +435,7 @@ def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None,
         elif cols_by_name:
             n = min(c.nrows for c in cols_by_name.values())
         else:
-            raise ValueError("map_column: a template without columns and Int parts needs nrows")
+            raise ValueError("map_column: a template without columns and Int / Float parts needs nrows")
     parr = (N.cph_map_piece * len(pieces))()
     for k, (kind, arg, value) in enumerate(pieces):
         parr[k].kind = kind
@@ -448,12 +448,17 @@ def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None,
             parr[k].arg = arg
         else:
             if value.count < n:
-                raise ValueError(f"map_column: an Int part has {value.count} values for {n} rows")
+                raise ValueError(f"map_column: {'an Int' if kind == M.INT64 else 'a Float'} part has {value.count} values for {n} rows")
             if value.device:
-                parr[k].arg, parr[k].ints = N.CPH_MEM_DEVICE, value.values or None
+                mem, ptr = N.CPH_MEM_DEVICE, value.values or None
             else:
                 keep.append(value.values)
-                parr[k].arg, parr[k].ints = N.CPH_MEM_HOST, value.values.ctypes.data if value.count else None
+                mem, ptr = N.CPH_MEM_HOST, value.values.ctypes.data if value.count else None
+            parr[k].arg = mem
+            if kind == M.INT64:
+                parr[k].ints = ptr
+            else:
+                parr[k].floats, parr[k].prec = ptr, value.prec
     out = C.POINTER(N.cph_colbuf)()
     ctx._check(ctx.lib.cph_map_format(ctx.handle, arr, sel, len(cols), n, parr, len(pieces), out_mem, C.byref(out)))
     del keep

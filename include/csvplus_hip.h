@@ -835,6 +835,17 @@ CPH_API void    cph_numcol_release(cph_numcol* col);
  *                    zeros, 0 gives "0", INT64_MIN its 20 characters.  `ints` has nrows entries in the memory space `arg`
  *                    (CPH_MEM_HOST / CPH_MEM_DEVICE); entry i belongs to OUTPUT row i (it is not read through row ids) —
  *                    e.g. the values of cph_col_to_number after arithmetic on them.
+ *   CPH_MAP_FLOAT64  floats[i] written as strconv.FormatFloat(v, 'f', prec, 64) does: an optional '-', the integer digits (at
+ *                    least "0"), and with prec > 0 a '.' and exactly prec digits; rounded to nearest, ties to even, on the
+ *                    EXACT binary value (2.675 at prec 2 gives "2.67", 2.5 at prec 0 "2", 0.125 at prec 2 "0.12").  The sign
+ *                    stays when the result rounds to zero (-0.001 at prec 2: "-0.00"; -0.0: "-0", "-0.00").  NaN of any sign
+ *                    or payload gives "NaN", the infinities "+Inf" and "-Inf".  `floats` has nrows entries in the memory
+ *                    space `arg`, entry i belongs to OUTPUT row i, a host array is staged: all as for INT64.
+ *                    Two limits: prec must be within 0..22, and a FINITE value with |v| >= 2^128 is not formatted — the call
+ *                    fails with CPH_ERR_INVALID, the message names the piece and the LOWEST such output row, *out stays NULL
+ *                    (infinities and NaN are not such values).  Inside both limits the digits are exact with 128-bit
+ *                    integer arithmetic (the integer part is below 2^128, the scaled fraction below 2^53 * 10^22 < 2^127);
+ *                    outside them the exact decimal digits need a big-number loop, which this does not have.
  * All bytes are copied verbatim (NUL and bytes >= 0x80 included); nothing is escaped.
  *
  * cols / sel / nrows mean exactly what they mean for cph_csv_write_rows (host or device columns, fixed-width or 32 / 64-bit
@@ -849,19 +860,23 @@ CPH_API void    cph_numcol_release(cph_numcol* col);
  * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / pieces / out, npieces outside 1..CPH_MAP_MAX_PIECES, an
  * unknown kind, a COLUMN index outside 0..ncols-1 (a column the rows lack is the host's business: it substitutes a literal
  * or reports the reference's missing-column error), a literal with a length but no pointer, an INT64 piece with ints ==
- * NULL while nrows > 0 or with an unknown memory space, ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
+ * NULL while nrows > 0 or with an unknown memory space, a FLOAT64 piece with floats == NULL while nrows > 0, with an unknown
+ * memory space or with prec outside 0..22, a FLOAT64 value beyond the range above (found while the call runs), ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
  * than 32 / 64, an identity column whose row count is not nrows, an unknown out_mem.
  *
- * Out of scope: formatting float64 (Go's shortest round-trip FormatFloat is a project of its own), case mapping,
- * trimming, substrings, conditional pieces.
+ * Out of scope: the other forms of FormatFloat — the shortest round-trip digits (prec -1) and the 'e' / 'g' formats, a
+ * project of their own —, case mapping, trimming, substrings, conditional pieces.
  */
-enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3 };
+enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4 };
 #define CPH_MAP_MAX_PIECES 16
 typedef struct {
     int32_t        kind;    /* CPH_MAP_* */
-    int32_t        arg;     /* COLUMN: index into cols; INT64: memory space of `ints` (CPH_MEM_*); LITERAL: ignored */
+    int32_t        arg;     /* COLUMN: index into cols; INT64 / FLOAT64: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
     cph_strval     value;   /* LITERAL: its bytes (host memory, any length, any byte values) */
     const int64_t* ints;    /* INT64: nrows values, entry i belongs to OUTPUT row i (no row ids) */
+    const double*  floats;  /* FLOAT64: likewise */
+    int32_t        prec;    /* FLOAT64: digits behind the point, 0..22 */
+    int32_t        reserved_;
 } cph_map_piece;
 
 CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
