@@ -11,8 +11,10 @@ Not, IntCmp, FloatCmp as plain data; ValueAsInt / ValueAsFloat64 for a whole col
 MinBy, MaxBy — resolved on the device: resolve_duplicates_device),
 `aggregate` (Totals per key of an index on the device — Sum, Min, Max as plain data: totals; the contract in pure Python:
 totals_model),
-`mapping` (Map as row templates — Format, Col, Int, Const — for computed columns: materialize.map_column; Validate:
+`mapping` (Map as row templates — Format, Col, Int, Float, Const — for computed columns: materialize.map_column; Validate:
 materialize.validate_rows),
+`expr` (numeric expressions as plain data — IntCol, FloatCol, IntArr, FloatArr, ToFloat, ToInt and + - * / % with Go's
+arithmetic — evaluated per row on the device: materialize.eval_number, mapping.Float.of / Int.of, aggregate.Sum(expr)),
 `pipeline` (CSV -> indices -> chained join -> CSV or JSON, all in HBM), `datagen` (deterministic synthetic tables).
 """
 from . import _native as native  # noqa: F401

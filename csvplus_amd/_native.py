@@ -170,6 +170,7 @@ class cph_rowlist(C.Structure):
 
 CPH_NUM_INT64, CPH_NUM_FLOAT64 = 1, 2
 CPH_NUM_OK, CPH_NUM_ERR_SYNTAX, CPH_NUM_ERR_RANGE, CPH_NUM_ERR_UNSUPPORTED = 0, 1, 2, 3
+CPH_NUM_ERR_DIV_ZERO, CPH_NUM_ERR_CONVERT = 4, 5   # cph_num_eval only
 CPH_NO_ROW = 0xFFFFFFFFFFFFFFFF
 
 
@@ -177,6 +178,23 @@ class cph_numcol(C.Structure):
     _fields_ = [("nrows", C.c_uint64), ("values", C.c_void_p), ("status", C.c_void_p), ("kind", C.c_int32), ("mem", C.c_int32),
                 ("nerrors", C.c_uint64), ("first_error_row", C.c_uint64), ("first_error_kind", C.c_int32), ("reserved_", C.c_int32),
                 ("host_rows", C.c_uint64)]
+
+
+CPH_EXPR_COL_INT, CPH_EXPR_COL_FLT, CPH_EXPR_NUM_INT, CPH_EXPR_NUM_FLT, CPH_EXPR_LIT_INT, CPH_EXPR_LIT_FLT = 1, 2, 3, 4, 5, 6
+CPH_EXPR_TO_FLT, CPH_EXPR_TO_INT, CPH_EXPR_NEG, CPH_EXPR_ADD, CPH_EXPR_SUB, CPH_EXPR_MUL, CPH_EXPR_DIV, CPH_EXPR_MOD = 8, 9, 10, 11, 12, 13, 14, 15
+CPH_EXPR_MAX_OPS, CPH_EXPR_MAX_STACK, CPH_EXPR_MAX_NUMS = 32, 8, 8
+
+
+class cph_expr_lit(C.Union):
+    _fields_ = [("i", C.c_int64), ("f", C.c_double)]
+
+
+class cph_expr_op(C.Structure):
+    _fields_ = [("op", C.c_int32), ("arg", C.c_int32), ("lit", cph_expr_lit)]
+
+
+class cph_expr_nums(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("mem", C.c_int32), ("reserved_", C.c_int32)]
 
 
 CPH_MAP_LITERAL, CPH_MAP_COLUMN, CPH_MAP_INT64, CPH_MAP_FLOAT64 = 1, 2, 3, 4
@@ -333,6 +351,9 @@ PROTOTYPES = [
     ("cph_col_to_number", C.c_int32,
      [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.POINTER(cph_numcol))]),
     ("cph_numcol_release", None, [C.POINTER(cph_numcol)]),
+    ("cph_num_eval", C.c_int32,
+     [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_int32, C.c_uint64, C.POINTER(cph_expr_nums), C.c_int32,
+      C.POINTER(cph_expr_op), C.c_int32, C.c_int32, C.POINTER(C.POINTER(cph_numcol)), C.POINTER(C.c_int32)]),
     ("cph_map_format", C.c_int32,
      [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_int32, C.c_uint64, C.POINTER(cph_map_piece), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_colbuf))]),

@@ -7,7 +7,10 @@ a Go closure.  A closure cannot run on a GPU; the aggregate is data here, as Lik
 
 `source` is a StrCol of the index's build table in its original row order (host or device; converted as to_int / to_float
 convert it), or numbers with one entry per row of the build table: a numpy array (host), a (device_ptr, count) pair or an
-object with data_ptr() such as a torch tensor (device) — e.g. two to_int / to_float results multiplied on the device.
+object with data_ptr() such as a torch tensor (device), or an EXPRESSION of csvplus_amd.expr over the build table's columns —
+`Sum(FloatCol("price") * ToFloat(IntCol("qty")))`, the reference's own total: `totals(index, specs, columns={name: StrCol})`
+evaluates it on the device over the table's rows (cph_num_eval) and hands the result in as numbers; its kind is the
+expression's type.
 
 A group is a maximal run of equal keys in the index, runs of ONE row included.  `totals` returns, per group in key order, the
 sorted position and the table row of its first row, its row count and one value per spec; `totals_model` states the same
@@ -33,6 +36,12 @@ class Spec:
     name = ""
 
     def __init__(self, source, kind=None):
+        from . import expr as E
+        if isinstance(source, E.Expr):
+            found = "float" if E.kind_of(source) == E.FLOAT else "int"
+            if kind not in (None, found):
+                raise ValueError(f"{type(self).__name__}: the expression is {found!r}, not {kind!r}")
+            kind = found
         if kind is None and isinstance(source, np.ndarray):
             kind = "float" if source.dtype.kind == "f" else "int"
         if kind not in _KINDS:
@@ -118,17 +127,34 @@ def _fill_spec(cs, spec, keep):
         cs.numbers, cs.numbers_mem = arr.ctypes.data, N.CPH_MEM_HOST
 
 
-def totals(index: N.DeviceIndex, specs=(), out_mem: int = N.CPH_MEM_HOST) -> Totals:
+def totals(index: N.DeviceIndex, specs=(), out_mem: int = N.CPH_MEM_HOST, columns=None) -> Totals:
     """Count and the specs' values per key of `index` (cph_index_aggregate); no specs: the distinct keys and their
-    frequencies.  A StrCol value that does not convert raises TotalsError."""
+    frequencies.  A StrCol value that does not convert raises TotalsError.  columns: {name: StrCol} of the build table, in
+    its original row order — what a spec whose source is an expression reads; a row where the expression fails raises
+    expr.ExprError."""
+    from . import expr as E
+
     specs = list(specs)
     ctx = index.ctx
     arr = (N.cph_agg_spec * max(1, len(specs)))()
-    keep = []
-    for i, sp in enumerate(specs):
-        _fill_spec(arr[i], sp, keep)
-    out = C.POINTER(N.cph_aggregated)()
-    rc = ctx.lib.cph_index_aggregate(ctx.handle, index.handle, arr if specs else None, len(specs), out_mem, C.byref(out))
+    keep, evaluated = [], []
+    try:
+        for i, sp in enumerate(specs):
+            if isinstance(sp, Spec) and isinstance(sp.source, E.Expr):
+                from .materialize import eval_number, raise_expr_error
+                nc = eval_number(ctx, columns or {}, sp.source, out_mem=N.CPH_MEM_DEVICE)   # the identity selection
+                evaluated.append(nc)
+                if nc.nerrors:
+                    raise_expr_error(ctx, columns or {}, sp.source, nc)
+                arr[i].op, arr[i].kind = sp.op, sp.kind
+                arr[i].numbers, arr[i].numbers_mem = nc.values[0] or None, N.CPH_MEM_DEVICE
+            else:
+                _fill_spec(arr[i], sp, keep)
+        out = C.POINTER(N.cph_aggregated)()
+        rc = ctx.lib.cph_index_aggregate(ctx.handle, index.handle, arr if specs else None, len(specs), out_mem, C.byref(out))
+    finally:
+        for nc in evaluated:
+            nc.release()
     del keep
     ctx._check(rc)
     r = out.contents

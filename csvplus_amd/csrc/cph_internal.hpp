@@ -937,3 +937,10 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
                     DevBuf* status, NumColStats* st);
 
 }  // namespace cph
+
+// the library-owned result behind cph_numcol (numparse.hip: cph_col_to_number; expr_eval.hip: cph_num_eval)
+struct cph_numcol_impl {
+    cph_numcol pub;   // first
+    cph::ResultOwner own;
+    cph::DevBuf d_values, d_status;
+};

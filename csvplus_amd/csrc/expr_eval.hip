@@ -1,0 +1,476 @@
+// expr_eval.hip — numeric expressions per row: the reference's `price * float64(qty)` (csvplus_test.go:516-571, :1391-1421)
+// as a typed postfix program over string columns, number arrays and literals, with Go's arithmetic rules
+// (include/csvplus_hip.h: cph_num_eval).
+//
+//   k_expr_eval   the geometry of k_num_parse (numparse.hip): rows on lanes, row = tile + 64 k + lane, 2048-row tiles,
+//                 8 rows per lane and tile of which 4 are in flight.  The program is wave-uniform and lives in the kernel
+//                 arguments; every lane interprets it over its 4 rows with a stack held in registers (the stack slot is
+//                 uniform, so a slot is picked with compares against constants and nothing is indexed dynamically).  A
+//                 string leaf is converted on the fly with numparse_device.hpp — span through the row ids, the value's first
+//                 16 bytes with two branch-free loads, the SWAR conversion — with its 4 rows' loads issued together; a
+//                 number leaf is a coalesced 8-byte load.  Values and status bytes leave as coalesced stores.  A wave that
+//                 saw an error adds its count and sends ONE 64-bit atomicMin of (row << 8 | op << 3 | kind); a wave that
+//                 deferred float rows adds their count.
+//   The kernel is instantiated for stacks of 2, 4 and 8 values (the host knows the program's depth): the reference's own
+//   shape, COL_FLT COL_INT TO_FLT MUL, needs 2.
+//
+// The float rows the device defers (numparse.hip) make the call take the plain route: every string leaf goes through
+// convert_rows — host finishing included — into a temporary array with its status bytes, and the same kernel runs with
+// every leaf as a number array.  Both routes run the same conversion and the same arithmetic code: the bits agree.
+//
+// This file must never contract a*b+c into a fused multiply-add (Go on amd64 never fuses): the pragma below and the
+// Makefile's -ffp-contract=off for this file both say so.
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "numparse_device.hpp"
+
+#pragma clang fp contract(off)
+
+namespace cph {
+
+constexpr int kExprRows  = 8;                           // rows per lane and tile
+constexpr int kExprPhase = 4;                           // ... of which this many are in flight at once
+constexpr int kExprTile  = kMatThreads * kExprRows;     // 2048 rows
+constexpr int kExprKeyShift = 8;                        // first_error = row << 8 | op << 3 | kind (op < 32, kind < 8)
+static_assert(CPH_EXPR_MAX_OPS <= 32 && CPH_NUM_ERR_CONVERT < 8, "the error key holds 5 op bits and 3 kind bits");
+
+struct ExprOp {          // one op as the kernel sees it
+    int32_t op, arg;     // CPH_EXPR_*; COL_*: the column
+    uint64_t a;          // LIT_*: the value's bits; NUM_*: the array (on the device)
+    const uint8_t* st;   // NUM_*: CPH_NUM_* per row (a converted string leaf), or null (a caller's array: no errors)
+};
+struct ExprPlan {
+    int32_t nops, pad_;
+    ExprOp ops[CPH_EXPR_MAX_OPS];
+};
+struct ExprCounters {    // zeroed / preset by the host in front of k_expr_eval
+    unsigned long long nerrors, first_error, ndeferred;
+};
+
+template <int D>
+__device__ __forceinline__ uint64_t stack_get(const uint64_t (&s)[D][kExprPhase], int slot, int k) {
+    uint64_t v = 0;
+#pragma unroll
+    for (int j = 0; j < D; j++)
+        if (j == slot) v = s[j][k];
+    return v;
+}
+template <int D>
+__device__ __forceinline__ void stack_set(uint64_t (&s)[D][kExprPhase], int slot, int k, uint64_t v) {
+#pragma unroll
+    for (int j = 0; j < D; j++)
+        if (j == slot) s[j][k] = v;
+}
+
+__device__ __forceinline__ double as_f64(uint64_t b) { return __longlong_as_double((long long)b); }
+__device__ __forceinline__ uint64_t f64_bits(double v) { return (uint64_t)__double_as_longlong(v); }
+
+// a OP b on int64 with Go's rules; returns CPH_NUM_OK or CPH_NUM_ERR_DIV_ZERO
+__device__ __forceinline__ uint32_t int_binary(int32_t op, uint64_t a, uint64_t b, uint64_t* out) {
+    switch (op) {
+        case CPH_EXPR_ADD: *out = a + b; return CPH_NUM_OK;
+        case CPH_EXPR_SUB: *out = a - b; return CPH_NUM_OK;
+        case CPH_EXPR_MUL: *out = a * b; return CPH_NUM_OK;
+        default: break;
+    }
+    *out = 0;
+    if (b == 0) return CPH_NUM_ERR_DIV_ZERO;
+    if (b == ~0ull) {   // a / -1 wraps (INT64_MIN stays), a % -1 is 0: the hardware-free form of Go's rule
+        if (op == CPH_EXPR_DIV) *out = 0ull - a;
+        return CPH_NUM_OK;
+    }
+    const int64_t x = (int64_t)a, y = (int64_t)b;
+    *out = (uint64_t)(op == CPH_EXPR_DIV ? x / y : x % y);   // C++ and Go agree: toward zero, the dividend's sign
+    return CPH_NUM_OK;
+}
+
+// one correctly rounded IEEE operation (the file is compiled without contraction)
+__device__ __forceinline__ double flt_binary(int32_t op, double a, double b) {
+    switch (op) {
+        case CPH_EXPR_ADD: return a + b;
+        case CPH_EXPR_SUB: return a - b;
+        case CPH_EXPR_MUL: return a * b;
+        default: return a / b;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(kMatThreads) void k_expr_eval(ColsArg cols, ColIds ids, ExprPlan plan, uint64_t n, uint64_t* __restrict__ values,
+                                                          uint8_t* __restrict__ status, ExprCounters* cnt) {
+    const int lane = lane_id(), wave = wave_id();
+    const uint64_t ntiles = (n + kExprTile - 1) / kExprTile;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * kExprTile;
+        unsigned long long first = ~0ull;   // wave-uniform: the key of the wave's first error in this tile
+        uint32_t nerr = 0, ndef = 0;        // wave-uniform
+#pragma unroll 1
+        for (int ph = 0; ph < kExprRows / kExprPhase; ph++) {
+            uint64_t row[kExprPhase];       // rows past the end look at the last row; their result is dropped
+            bool live[kExprPhase];
+#pragma unroll
+            for (int k = 0; k < kExprPhase; k++) {
+                const uint64_t i = t0 + (uint64_t)((wave * kExprRows + ph * kExprPhase + k) * 64 + lane);
+                live[k] = i < n;
+                row[k] = live[k] ? i : n - 1;
+            }
+            uint64_t stk[D][kExprPhase];
+            uint32_t rst[kExprPhase], rop[kExprPhase];   // the row's status and the op that set it
+            bool deferred[kExprPhase];
+#pragma unroll
+            for (int k = 0; k < kExprPhase; k++) {
+                rst[k] = CPH_NUM_OK, rop[k] = 0, deferred[k] = false;
+#pragma unroll
+                for (int j = 0; j < D; j++) stk[j][k] = 0;
+            }
+            int sp = 0;   // uniform
+            for (int q = 0; q < plan.nops; q++) {
+                const int32_t op = plan.ops[q].op;
+                uint64_t r[kExprPhase];
+                uint32_t e[kExprPhase];
+                int slot = sp;   // where the result goes
+                if (op == CPH_EXPR_COL_INT || op == CPH_EXPR_COL_FLT) {
+                    const DevCol& col = cols.c[plan.ops[q].arg];
+                    const RowIds& rid = ids.ids[plan.ops[q].arg];
+                    uint64_t b[kExprPhase], l[kExprPhase], c0[kExprPhase], c1[kExprPhase];
+#pragma unroll
+                    for (int k = 0; k < kExprPhase; k++) value_span(col, source_row(rid, row[k]), &b[k], &l[k]);
+#pragma unroll
+                    for (int k = 0; k < kExprPhase; k++) load_head16(col, b[k], l[k], &c0[k], &c1[k]);
+                    if (op == CPH_EXPR_COL_FLT) {
+#pragma unroll
+                        for (int k = 0; k < kExprPhase; k++) {
+                            double v;
+                            e[k] = parse_float64(col, b[k], l[k], c0[k], c1[k], &v);
+                            r[k] = f64_bits(v);
+                            if (e[k] == kNumDeferred) deferred[k] = true, e[k] = CPH_NUM_OK;
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < kExprPhase; k++) {
+                            int64_t v;
+                            e[k] = parse_int64(col, b[k], l[k], c0[k], c1[k], &v);
+                            r[k] = (uint64_t)v;
+                        }
+                    }
+                    sp++;
+                } else if (op == CPH_EXPR_NUM_INT || op == CPH_EXPR_NUM_FLT) {
+                    const uint64_t* vals = reinterpret_cast<const uint64_t*>((uintptr_t)plan.ops[q].a);
+                    const uint8_t* st = plan.ops[q].st;
+#pragma unroll
+                    for (int k = 0; k < kExprPhase; k++) {
+                        r[k] = vals[row[k]];
+                        e[k] = st ? (uint32_t)st[row[k]] : (uint32_t)CPH_NUM_OK;
+                    }
+                    sp++;
+                } else if (op == CPH_EXPR_LIT_INT || op == CPH_EXPR_LIT_FLT) {
+#pragma unroll
+                    for (int k = 0; k < kExprPhase; k++) r[k] = plan.ops[q].a, e[k] = CPH_NUM_OK;
+                    sp++;
+                } else if (op == CPH_EXPR_TO_FLT || op == CPH_EXPR_TO_INT || op == CPH_EXPR_NEG) {
+                    slot = sp - 1;
+                    const bool flt = plan.ops[q].arg != 0;   // NEG: the host wrote the operand's type here
+#pragma unroll
+                    for (int k = 0; k < kExprPhase; k++) {
+                        const uint64_t x = stack_get<D>(stk, slot, k);
+                        e[k] = CPH_NUM_OK;
+                        if (op == CPH_EXPR_TO_FLT) {
+                            r[k] = f64_bits((double)(int64_t)x);
+                        } else if (op == CPH_EXPR_TO_INT) {
+                            const double v = as_f64(x);
+                            const bool fits = v >= -9223372036854775808.0 && v < 9223372036854775808.0;   // false for a NaN
+                            r[k] = fits ? (uint64_t)(int64_t)v : 0ull;
+                            if (!fits) e[k] = CPH_NUM_ERR_CONVERT;
+                        } else {
+                            r[k] = flt ? x ^ 0x8000000000000000ull : 0ull - x;
+                        }
+                    }
+                } else {   // ADD SUB MUL DIV MOD: arg = 1 for float64 operands
+                    slot = sp - 2;
+                    const bool flt = plan.ops[q].arg != 0;
+#pragma unroll
+                    for (int k = 0; k < kExprPhase; k++) {
+                        const uint64_t x = stack_get<D>(stk, slot, k), y = stack_get<D>(stk, slot + 1, k);
+                        if (flt) {
+                            r[k] = f64_bits(flt_binary(op, as_f64(x), as_f64(y)));
+                            e[k] = CPH_NUM_OK;
+                        } else {
+                            e[k] = int_binary(op, x, y, &r[k]);
+                        }
+                    }
+                    sp--;
+                }
+#pragma unroll
+                for (int k = 0; k < kExprPhase; k++) {
+                    stack_set<D>(stk, slot, k, r[k]);
+                    if (e[k] != CPH_NUM_OK && rst[k] == CPH_NUM_OK) rst[k] = e[k], rop[k] = (uint32_t)q;   // the first failing op decides
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kExprPhase; k++) {
+                const uint64_t g0 = t0 + (uint64_t)((wave * kExprRows + ph * kExprPhase + k) * 64);
+                if (live[k]) {
+                    values[g0 + lane] = rst[k] == CPH_NUM_OK ? stk[0][k] : 0ull;
+                    status[g0 + lane] = (uint8_t)rst[k];
+                }
+                const uint64_t bad = __ballot(live[k] && rst[k] != CPH_NUM_OK);
+                if (bad) {   // uniform
+                    const int fl = __builtin_ctzll(bad);
+                    const uint32_t tag = (rop[k] << 3) | rst[k];
+                    const unsigned long long key =
+                        ((unsigned long long)(g0 + (uint64_t)fl) << kExprKeyShift) | (unsigned long long)__shfl(tag, fl, kWave);
+                    if (key < first) first = key;
+                    nerr += (uint32_t)__popcll(bad);
+                }
+                ndef += (uint32_t)__popcll(__ballot(live[k] && deferred[k]));
+            }
+        }
+        if (lane == 0) {
+            if (nerr) {
+                atomicAdd(&cnt->nerrors, (unsigned long long)nerr);
+                atomicMin(&cnt->first_error, first);
+            }
+            if (ndef) atomicAdd(&cnt->ndeferred, (unsigned long long)ndef);
+        }
+    }
+}
+
+namespace {
+
+unsigned expr_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
+
+bool is_leaf(int32_t op) { return op >= CPH_EXPR_COL_INT && op <= CPH_EXPR_LIT_FLT; }
+
+// Go's typing, checked before anything is launched.  kinds[q] = the type op q pushes (CPH_NUM_*), *depth = the deepest stack.
+Status check_program(const cph_expr_op* prog, int32_t nops, int32_t ncols, int32_t nnums, int32_t* kinds, int32_t* depth, int32_t* result) {
+    int32_t stack[CPH_EXPR_MAX_STACK];
+    int sp = 0;
+    *depth = 0;
+    for (int q = 0; q < nops; q++) {
+        const int32_t op = prog[q].op;
+        const std::string where = "cph_num_eval: op " + std::to_string(q) + ": ";
+        int32_t push = 0;
+        switch (op) {
+            case CPH_EXPR_COL_INT:
+            case CPH_EXPR_COL_FLT:
+                if (prog[q].arg < 0 || prog[q].arg >= ncols) return {CPH_ERR_INVALID, where + "a column outside 0..ncols-1"};
+                push = op == CPH_EXPR_COL_INT ? CPH_NUM_INT64 : CPH_NUM_FLOAT64;
+                break;
+            case CPH_EXPR_NUM_INT:
+            case CPH_EXPR_NUM_FLT:
+                if (prog[q].arg < 0 || prog[q].arg >= nnums) return {CPH_ERR_INVALID, where + "a number array outside 0..nnums-1"};
+                push = op == CPH_EXPR_NUM_INT ? CPH_NUM_INT64 : CPH_NUM_FLOAT64;
+                break;
+            case CPH_EXPR_LIT_INT: push = CPH_NUM_INT64; break;
+            case CPH_EXPR_LIT_FLT: push = CPH_NUM_FLOAT64; break;
+            case CPH_EXPR_TO_FLT:
+            case CPH_EXPR_TO_INT:
+            case CPH_EXPR_NEG:
+                if (sp < 1) return {CPH_ERR_INVALID, where + "no operand on the stack"};
+                if (op == CPH_EXPR_TO_FLT && stack[sp - 1] != CPH_NUM_INT64) return {CPH_ERR_INVALID, where + "TO_FLT takes an int64"};
+                if (op == CPH_EXPR_TO_INT && stack[sp - 1] != CPH_NUM_FLOAT64) return {CPH_ERR_INVALID, where + "TO_INT takes a float64"};
+                push = op == CPH_EXPR_TO_FLT ? CPH_NUM_FLOAT64 : op == CPH_EXPR_TO_INT ? CPH_NUM_INT64 : stack[sp - 1];
+                sp -= 1;
+                break;
+            case CPH_EXPR_ADD:
+            case CPH_EXPR_SUB:
+            case CPH_EXPR_MUL:
+            case CPH_EXPR_DIV:
+            case CPH_EXPR_MOD:
+                if (sp < 2) return {CPH_ERR_INVALID, where + "a binary op needs two operands on the stack"};
+                if (stack[sp - 1] != stack[sp - 2])
+                    return {CPH_ERR_INVALID, where + "mismatched operand types (int64 and float64): there are no implicit conversions"};
+                if (op == CPH_EXPR_MOD && stack[sp - 1] != CPH_NUM_INT64) return {CPH_ERR_INVALID, where + "MOD takes int64 operands"};
+                push = stack[sp - 1];
+                sp -= 2;
+                break;
+            default:
+                return {CPH_ERR_INVALID, where + "unknown op (1..6, 8..15)"};
+        }
+        if (sp >= CPH_EXPR_MAX_STACK) return {CPH_ERR_INVALID, where + "a stack deeper than CPH_EXPR_MAX_STACK"};
+        stack[sp++] = push;
+        kinds[q] = push;
+        if (sp > *depth) *depth = sp;
+    }
+    if (sp != 1) return {CPH_ERR_INVALID, "cph_num_eval: the program leaves " + std::to_string(sp) + " values, not exactly one"};
+    *result = stack[0];
+    return {};
+}
+
+Status launch_eval(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, const ExprPlan& plan, int depth, uint64_t n, double bytes, DevBuf* values,
+                   DevBuf* status, ExprCounters* got) {
+    DevBuf cnt;
+    CPH_TRY(cnt.alloc(&ctx->pool, sizeof(ExprCounters)));
+    {
+        void* slot = nullptr;
+        CPH_TRY(pinned_upload(ctx, sizeof(ExprCounters), &slot));
+        const ExprCounters zero{0ull, ~0ull, 0ull};
+        memcpy(slot, &zero, sizeof zero);
+        CPH_HIP_TRY(hipMemcpyAsync(cnt.get(), slot, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const dim3 grid(expr_grid((n + kExprTile - 1) / kExprTile));
+    {
+        ProfScope ps(ctx, "k_expr_eval", bytes);
+        if (depth <= 2)
+            hipLaunchKernelGGL(k_expr_eval<2>, grid, dim3(kMatThreads), 0, ctx->stream, arg, ids, plan, n, values->as<uint64_t>(),
+                               status->as<uint8_t>(), cnt.as<ExprCounters>());
+        else if (depth <= 4)
+            hipLaunchKernelGGL(k_expr_eval<4>, grid, dim3(kMatThreads), 0, ctx->stream, arg, ids, plan, n, values->as<uint64_t>(),
+                               status->as<uint8_t>(), cnt.as<ExprCounters>());
+        else
+            hipLaunchKernelGGL(k_expr_eval<CPH_EXPR_MAX_STACK>, grid, dim3(kMatThreads), 0, ctx->stream, arg, ids, plan, n,
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<ExprCounters>());
+    }
+    CPH_HIP_TRY(hipGetLastError());
+    return read_device_value(ctx, cnt.as<ExprCounters>(), got);   // the call's host wait
+}
+
+}  // namespace
+}  // namespace cph
+
+using namespace cph;
+
+extern "C" {
+
+CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
+                             const cph_expr_nums* nums, int32_t nnums, const cph_expr_op* prog, int32_t nops, int32_t out_mem,
+                             cph_numcol** out, int32_t* first_error_op) {
+    if (!ctx) return CPH_ERR_INVALID;
+    if (!out) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: out must not be NULL"});
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_with(ctx, {CPH_ERR_HIP, "hipSetDevice failed"});
+    *out = nullptr;
+    if (first_error_op) *first_error_op = -1;
+    if (!prog) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: prog must not be NULL"});
+    if (nops < 1 || nops > CPH_EXPR_MAX_OPS) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: 1..CPH_EXPR_MAX_OPS (32) ops"});
+    if (ncols < 0 || ncols > CPH_MAX_KEY_COLS) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: 0..16 columns"});
+    if (ncols && !cols) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: cols must not be NULL"});
+    if (nnums < 0 || nnums > CPH_EXPR_MAX_NUMS) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: 0..CPH_EXPR_MAX_NUMS (8) number arrays"});
+    if (nnums && !nums) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: nums must not be NULL"});
+    if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: bad out_mem"});
+    for (int k = 0; k < nnums; k++) {
+        if (nums[k].mem != CPH_MEM_HOST && nums[k].mem != CPH_MEM_DEVICE)
+            return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: bad memory space of number array " + std::to_string(k)});
+        if (!nums[k].ptr && nrows) return fail_with(ctx, {CPH_ERR_INVALID, "cph_num_eval: number array " + std::to_string(k) + " without values"});
+    }
+    int32_t kinds[CPH_EXPR_MAX_OPS], depth = 0, result = 0;
+    {
+        Status s = check_program(prog, nops, ncols, nnums, kinds, &depth, &result);
+        if (!s.ok()) return fail_with(ctx, s);
+        s = check_row_sources(cols, sel, ncols, 0, nrows, true);
+        if (!s.ok()) return fail_with(ctx, s);
+    }
+    auto* r = new (std::nothrow) cph_numcol_impl();
+    if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
+    r->own.ctx = ctx;
+    r->pub.nrows = nrows;
+    r->pub.kind = result;
+    r->pub.mem = out_mem;
+    r->pub.first_error_row = UINT64_MAX;
+    const uint64_t n = nrows;
+    auto run = [&]() -> Status {
+        if (n == 0) return {};
+        std::vector<DevBuf> staged;
+        std::vector<DevBuf> converted(2 * 2 * CPH_MAX_KEY_COLS);   // the plain route: values and status per (column, type)
+        ColsArg arg{};
+        ColIds ids{};
+        CPH_TRY(stage_row_sources(ctx, cols, sel, nullptr, ncols, 0, n, &staged, &arg, &ids));
+        const void* dnums[CPH_EXPR_MAX_NUMS] = {};
+        for (int k = 0; k < nnums; k++) {
+            dnums[k] = nums[k].ptr;
+            bool used = false;
+            for (int q = 0; q < nops; q++) used = used || ((prog[q].op == CPH_EXPR_NUM_INT || prog[q].op == CPH_EXPR_NUM_FLT) && prog[q].arg == k);
+            if (nums[k].mem == CPH_MEM_HOST && used) {   // staged like the row ids of a host column
+                staged.emplace_back();
+                CPH_TRY(staged.back().alloc(&ctx->pool, (size_t)n * 8));
+                CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), nums[k].ptr, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+                dnums[k] = staged.back().get();
+            }
+        }
+        ExprPlan plan{};
+        plan.nops = nops;
+        double in_row = 0;   // byte model: per string leaf offsets (or nothing for a fixed width) + row ids + ~8 value bytes, 8 per array leaf
+        uint32_t col_seen = 0;
+        bool has_col = false;
+        for (int q = 0; q < nops; q++) {
+            ExprOp& d = plan.ops[q];
+            d.op = prog[q].op;
+            d.arg = 0;
+            switch (prog[q].op) {
+                case CPH_EXPR_COL_INT:
+                case CPH_EXPR_COL_FLT: {
+                    d.arg = prog[q].arg;
+                    has_col = true;
+                    const DevCol& c = arg.c[d.arg];
+                    if (!((col_seen >> d.arg) & 1u)) in_row += c.fixed_width ? 0.0 : (double)(c.offset_bits / 8);
+                    if (!((col_seen >> d.arg) & 1u) && ids.ids[d.arg].ptr) in_row += (double)(ids.ids[d.arg].bits / 8);
+                    col_seen |= 1u << d.arg;
+                    in_row += c.fixed_width ? (double)c.fixed_width : 8.0;
+                    break;
+                }
+                case CPH_EXPR_NUM_INT:
+                case CPH_EXPR_NUM_FLT:
+                    d.a = (uint64_t)(uintptr_t)dnums[prog[q].arg];
+                    in_row += 8.0;
+                    break;
+                case CPH_EXPR_LIT_INT:
+                case CPH_EXPR_LIT_FLT:
+                    memcpy(&d.a, &prog[q].lit, 8);
+                    break;
+                case CPH_EXPR_TO_FLT:
+                case CPH_EXPR_TO_INT:
+                    break;
+                default:   // NEG and the binary ops: the operands' type
+                    d.arg = kinds[q] == CPH_NUM_FLOAT64 ? 1 : 0;
+                    break;
+            }
+        }
+        CPH_TRY(r->d_values.alloc(&ctx->pool, (size_t)n * 8));
+        CPH_TRY(r->d_status.alloc(&ctx->pool, (size_t)n));
+        ExprCounters got{};
+        CPH_TRY(launch_eval(ctx, arg, ids, plan, depth, n, (in_row + 9.0) * (double)n, &r->d_values, &r->d_status, &got));
+        r->pub.host_rows = got.ndeferred;
+        if (got.ndeferred && has_col) {
+            // the plain route: every string leaf converted as cph_col_to_number converts it (one array per column and type),
+            // then the same program over number arrays that carry their status bytes
+            bool have[CPH_MAX_KEY_COLS][2] = {};
+            double row2 = 0;
+            for (int q = 0; q < nops; q++) {
+                ExprOp& d = plan.ops[q];
+                if (d.op != CPH_EXPR_COL_INT && d.op != CPH_EXPR_COL_FLT) {
+                    if (d.op == CPH_EXPR_NUM_INT || d.op == CPH_EXPR_NUM_FLT) row2 += 8.0;
+                    continue;
+                }
+                const int c = d.arg, f = d.op == CPH_EXPR_COL_FLT ? 1 : 0;
+                DevBuf& cv = converted[(size_t)(4 * c + 2 * f)];
+                DevBuf& cs = converted[(size_t)(4 * c + 2 * f + 1)];
+                if (!have[c][f]) {
+                    NumColStats st;
+                    CPH_TRY(convert_rows(ctx, arg.c[c], ids.ids[c], 0, n, f ? CPH_NUM_FLOAT64 : CPH_NUM_INT64, &cv, &cs, &st));
+                    have[c][f] = true;
+                }
+                d.op = f ? CPH_EXPR_NUM_FLT : CPH_EXPR_NUM_INT;
+                d.arg = 0;
+                d.a = (uint64_t)(uintptr_t)cv.get();
+                d.st = cs.as<uint8_t>();
+                row2 += 9.0;
+            }
+            CPH_TRY(launch_eval(ctx, arg, ids, plan, depth, n, (row2 + 9.0) * (double)n, &r->d_values, &r->d_status, &got));
+        }
+        r->pub.nerrors = got.nerrors;
+        if (got.nerrors) {
+            r->pub.first_error_row = got.first_error >> kExprKeyShift;
+            r->pub.first_error_kind = (int32_t)(got.first_error & 7ull);
+            if (first_error_op) *first_error_op = (int32_t)((got.first_error >> 3) & 31ull);
+        }
+        // the kernels read the staged arrays: they go back to the pool behind deliver's wait
+        const ResultPart parts[2] = {{&r->d_values, (size_t)n * 8, &r->pub.values}, {&r->d_status, (size_t)n, &r->pub.status}};
+        return deliver(ctx, &r->own, parts, 2, out_mem);
+    };
+    const Status s = run();
+    if (!s.ok() && first_error_op) *first_error_op = -1;
+    return finish_call(ctx, r, s, out);
+}
+
+}  // extern "C"

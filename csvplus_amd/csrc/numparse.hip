@@ -262,13 +262,6 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
 
 using namespace cph;
 
-// the library-owned result behind cph_numcol
-struct cph_numcol_impl {
-    cph_numcol pub;   // first
-    cph::ResultOwner own;
-    cph::DevBuf d_values, d_status;
-};
-
 extern "C" {
 
 CPH_API int32_t cph_col_to_number(cph_ctx* ctx, const cph_strcol* col, const cph_rowsel* sel, uint64_t nrows, int32_t kind,

@@ -15,7 +15,8 @@
 //                                                declarative csvplus::Pred, evaluated on the GPU) / Top / Drop
 //   Like / All / Any / Not           :1243-1293  csvplus::Like / All / Any / Not (plain data, also callable on a Row)
 //   DataSource.Map                     :290-296  DataSource::Map over csvplus::Set(name, literal or Format{...}): a row
-//                                                template instead of a closure, rendered on the GPU (cph_map_format)
+//                                                template instead of a closure, rendered on the GPU (cph_map_format);
+//                                                Fixed(expr, prec) / Itoa(expr): an Expr's value (cph_num_eval)
 //   DataSource.Validate                :300-310  DataSource::Validate(pred, message): a declarative Pred instead of a closure
 //   DataSource.Transform               :262-272  no entry of its own: it is the composition of Map, Filter and Validate
 //   Row.ValueAsInt / ValueAsFloat64  :165-205    csvplus::ValueAsInt / ValueAsFloat64 (one row, on the host);
@@ -351,29 +352,218 @@ inline Pred Any(const Pred& first, const P&... more) { return Any(std::vector<Pr
 // (Row.SafeGetValue, :69-75); without a default the iteration ends with the reference's `missing column` error at that row.
 // Fixed(Col("price"), 2) is the column's value read as Row.ValueAsFloat64 reads it and written back as
 // strconv.FormatFloat(v, 'f', 2, 64) writes it (prec 0..22; a finite value of 2^128 or more is refused by the device); a value
-// that does not parse ends the iteration at that row with ValueAsFloat64's error.  Arithmetic between columns is not part of it.
+// that does not parse ends the iteration at that row with ValueAsFloat64's error.  Arithmetic between columns is an Expr:
+// Fixed(AsFloat64(Col("price")) * Float64(AsInt(Col("qty"))), 2) is the reference's amount column (csvplus_test.go:1404-1412),
+// Itoa(expr) writes an integer expression as strconv.Itoa does.
 struct Col {
     std::string name, fallback;
     bool has_default = false;
     explicit Col(std::string n) : name(std::move(n)) {}
     Col(std::string n, std::string dflt) : name(std::move(n)), fallback(std::move(dflt)), has_default(true) {}
 };
+
+// ---- numeric expressions as DATA (cph_num_eval) ---------------------------------------------------------------------------
+// `price * float64(qty)` of the reference's closures, as a value: AsInt(Col) / AsFloat64(Col) read a column as Row.ValueAsInt /
+// Row.ValueAsFloat64 do, literals are C++ integers (int64) and doubles (float64), Float64(e) / Int(e) are Go's conversions, and
+// + - * / % and unary - are Go's operators: no implicit conversions (mixing the types is a Panic when the expression is built),
+// int64 wraps, / truncates toward zero, % has the dividend's sign, INT64_MIN / -1 == INT64_MIN; every float op is one IEEE
+// operation, never fused.  A zero integer divisor and an Int() of a NaN or of a value outside [-2^63, 2^63) are errors of
+// their row, like a value that does not convert; the first failing op in program order decides (include/csvplus_hip.h).
+class Expr {
+public:
+    struct Op {
+        int32_t op = 0;     // CPH_EXPR_*
+        int32_t arg = 0;    // COL_*: index into cols
+        bool flt = false;   // NEG and the binary ops: float64 operands
+        int64_t i = 0;
+        double f = 0;
+    };
+    std::vector<Op> ops;        // postfix
+    std::vector<Col> cols;      // the columns read, in order of first use
+    int32_t kind = 0;           // CPH_NUM_INT64 / CPH_NUM_FLOAT64: the result's type
+
+    Expr(int v) : Expr((long long)v) {}    // NOLINT: implicit, so that `AsInt(Col("qty")) * 2` reads like the expression
+    Expr(long v) : Expr((long long)v) {}   // NOLINT
+    Expr(long long v) : kind(CPH_NUM_INT64) {   // NOLINT
+        Op o;
+        o.op = CPH_EXPR_LIT_INT;
+        o.i = (int64_t)v;
+        ops.push_back(o);
+    }
+    Expr(double v) : kind(CPH_NUM_FLOAT64) {   // NOLINT
+        Op o;
+        o.op = CPH_EXPR_LIT_FLT;
+        o.f = v;
+        ops.push_back(o);
+    }
+    static Expr column(Col c, bool flt) {
+        Expr e(0);
+        e.ops[0].op = flt ? CPH_EXPR_COL_FLT : CPH_EXPR_COL_INT;
+        e.kind = flt ? CPH_NUM_FLOAT64 : CPH_NUM_INT64;
+        e.cols.push_back(std::move(c));
+        return e;
+    }
+    static Expr unary(int32_t op, Expr x) {
+        if (op == CPH_EXPR_TO_FLT && x.kind != CPH_NUM_INT64) throw Panic("Float64() of a float64 expression");
+        if (op == CPH_EXPR_TO_INT && x.kind != CPH_NUM_FLOAT64) throw Panic("Int() of an int64 expression");
+        Op o;
+        o.op = op;
+        o.flt = x.kind == CPH_NUM_FLOAT64;
+        x.ops.push_back(o);
+        x.kind = op == CPH_EXPR_TO_FLT ? CPH_NUM_FLOAT64 : op == CPH_EXPR_TO_INT ? CPH_NUM_INT64 : x.kind;
+        x.check();
+        return x;
+    }
+    static Expr binary(int32_t op, Expr a, const Expr& b) {
+        if (a.kind != b.kind) throw Panic("mismatched types int64 and float64 in an expression (there are no implicit conversions)");
+        if (op == CPH_EXPR_MOD && a.kind != CPH_NUM_INT64) throw Panic("operator % on float64 expressions");
+        for (Op o : b.ops) {
+            if (o.op == CPH_EXPR_COL_INT || o.op == CPH_EXPR_COL_FLT) {
+                const Col& c = b.cols[(size_t)o.arg];
+                size_t k = 0;
+                while (k < a.cols.size() && a.cols[k].name != c.name) k++;
+                if (k == a.cols.size()) a.cols.push_back(c);
+                o.arg = (int32_t)k;
+            }
+            a.ops.push_back(o);
+        }
+        Op o;
+        o.op = op;
+        o.flt = a.kind == CPH_NUM_FLOAT64;
+        a.ops.push_back(o);
+        a.check();
+        return a;
+    }
+    // the expression on one row, on the host (what the device computes for a whole batch).  Returns CPH_NUM_*: the status
+    // of the first failing op, whose index goes to *bad_op; -1 with *missing set for a row that lacks a column without default.
+    int32_t eval(const Row& row, int64_t* iv, double* fv, int* bad_op, std::string* missing) const {
+        int64_t si[CPH_EXPR_MAX_STACK] = {};
+        double sf[CPH_EXPR_MAX_STACK] = {};
+        int sp = 0, bad = -1;
+        int32_t status = CPH_NUM_OK;
+        for (size_t q = 0; q < ops.size(); q++) {
+            const Op& o = ops[q];
+            int32_t st = CPH_NUM_OK;
+            switch (o.op) {
+                case CPH_EXPR_COL_INT:
+                case CPH_EXPR_COL_FLT: {
+                    const Col& c = cols[(size_t)o.arg];
+                    auto it = row.find(c.name);
+                    const std::string* v = it != row.end() ? &it->second : c.has_default ? &c.fallback : nullptr;
+                    if (!v) {
+                        if (missing) *missing = c.name;
+                        return -1;
+                    }
+                    st = o.op == CPH_EXPR_COL_INT ? Atoi(*v, &si[sp]) : ParseFloat(*v, &sf[sp]);
+                    sp++;
+                    break;
+                }
+                case CPH_EXPR_LIT_INT: si[sp++] = o.i; break;
+                case CPH_EXPR_LIT_FLT: sf[sp++] = o.f; break;
+                case CPH_EXPR_TO_FLT: sf[sp - 1] = (double)si[sp - 1]; break;
+                case CPH_EXPR_TO_INT: {
+                    const double v = sf[sp - 1];
+                    const bool fits = v >= -9223372036854775808.0 && v < 9223372036854775808.0;   // false for a NaN
+                    si[sp - 1] = fits ? (int64_t)v : 0;
+                    if (!fits) st = CPH_NUM_ERR_CONVERT;
+                    break;
+                }
+                case CPH_EXPR_NEG:
+                    if (o.flt) sf[sp - 1] = -sf[sp - 1];
+                    else si[sp - 1] = (int64_t)(0ull - (uint64_t)si[sp - 1]);
+                    break;
+                default: {
+                    sp--;
+                    if (o.flt) {
+                        const double a = sf[sp - 1], b = sf[sp];
+                        sf[sp - 1] = o.op == CPH_EXPR_ADD ? a + b : o.op == CPH_EXPR_SUB ? a - b : o.op == CPH_EXPR_MUL ? a * b : a / b;
+                        break;
+                    }
+                    const uint64_t a = (uint64_t)si[sp - 1], b = (uint64_t)si[sp];
+                    uint64_t r = 0;
+                    if (o.op == CPH_EXPR_ADD) r = a + b;
+                    else if (o.op == CPH_EXPR_SUB) r = a - b;
+                    else if (o.op == CPH_EXPR_MUL) r = a * b;
+                    else if (b == 0) st = CPH_NUM_ERR_DIV_ZERO;
+                    else if (b == ~0ull) r = o.op == CPH_EXPR_DIV ? 0ull - a : 0ull;   // INT64_MIN / -1 wraps, % -1 is 0
+                    else r = (uint64_t)(o.op == CPH_EXPR_DIV ? (int64_t)a / (int64_t)b : (int64_t)a % (int64_t)b);
+                    si[sp - 1] = (int64_t)r;
+                    break;
+                }
+            }
+            if (st != CPH_NUM_OK && status == CPH_NUM_OK) status = st, bad = (int)q;
+        }
+        if (bad_op) *bad_op = bad;
+        if (iv) *iv = status == CPH_NUM_OK ? si[0] : 0;
+        if (fv) *fv = status == CPH_NUM_OK ? sf[0] : 0.0;
+        return status;
+    }
+    // the message of a row whose op `op` failed with `status`; value(column index) = the row's value of that column
+    std::string errorText(int32_t status, int op, const std::function<std::string(size_t)>& value) const {
+        const Op& o = ops[(size_t)op];
+        if (o.op == CPH_EXPR_COL_INT || o.op == CPH_EXPR_COL_FLT)
+            return conversionError(cols[(size_t)o.arg].name, value((size_t)o.arg), o.op == CPH_EXPR_COL_INT ? CPH_NUM_INT64 : CPH_NUM_FLOAT64, status);
+        return status == CPH_NUM_ERR_DIV_ZERO ? "integer divide by zero" : "float64 value does not fit an int64";
+    }
+    std::string errorText(int32_t status, int op, const Row& row) const {
+        return errorText(status, op, [&](size_t c) {
+            auto it = row.find(cols[c].name);
+            return it != row.end() ? it->second : cols[c].fallback;
+        });
+    }
+
+private:
+    void check() const {   // the ABI's limits
+        if (ops.size() > (size_t)CPH_EXPR_MAX_OPS) throw Panic("expression of more than 32 ops");
+        if (cols.size() > (size_t)CPH_MAX_KEY_COLS) throw Panic("expression over more than 16 columns");
+        int sp = 0;
+        for (const Op& o : ops) {
+            if (o.op <= CPH_EXPR_LIT_FLT) sp++;
+            else if (o.op >= CPH_EXPR_ADD) sp--;
+            if (sp > CPH_EXPR_MAX_STACK) throw Panic("expression needs a stack deeper than 8");
+        }
+    }
+};
+inline Expr AsInt(Col c) { return Expr::column(std::move(c), false); }       // row.ValueAsInt(name)
+inline Expr AsFloat64(Col c) { return Expr::column(std::move(c), true); }    // row.ValueAsFloat64(name)
+inline Expr Float64(Expr e) { return Expr::unary(CPH_EXPR_TO_FLT, std::move(e)); }   // float64(x)
+inline Expr Int(Expr e) { return Expr::unary(CPH_EXPR_TO_INT, std::move(e)); }       // int64(x)
+inline Expr operator-(Expr e) { return Expr::unary(CPH_EXPR_NEG, std::move(e)); }
+inline Expr operator+(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_ADD, std::move(a), b); }
+inline Expr operator-(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_SUB, std::move(a), b); }
+inline Expr operator*(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_MUL, std::move(a), b); }
+inline Expr operator/(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_DIV, std::move(a), b); }
+inline Expr operator%(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_MOD, std::move(a), b); }
+
 struct Fixed {
     Col col;
     int prec;
+    std::shared_ptr<const Expr> expr;   // Fixed(expression, prec)
     Fixed(Col c, int p) : col(std::move(c)), prec(p) {
         if (p < 0 || p > 22) throw Panic("Fixed(): prec outside 0..22");
     }
+    Fixed(Expr e, int p) : col(""), prec(p), expr(std::make_shared<const Expr>(std::move(e))) {
+        if (p < 0 || p > 22) throw Panic("Fixed(): prec outside 0..22");
+        if (expr->kind != CPH_NUM_FLOAT64) throw Panic("Fixed() of an int64 expression (use Itoa, or Float64)");
+    }
 };
-struct Part {   // a literal, a column, or a column as a fixed-precision number
+struct Itoa {   // an int64 expression written as strconv.Itoa writes it
+    std::shared_ptr<const Expr> expr;
+    explicit Itoa(Expr e) : expr(std::make_shared<const Expr>(std::move(e))) {
+        if (expr->kind != CPH_NUM_INT64) throw Panic("Itoa() of a float64 expression (use Fixed, or Int)");
+    }
+};
+struct Part {   // a literal, a column, a column as a fixed-precision number, or an expression's value
     bool is_col = false;
     std::string text;   // the literal's bytes
     Col col{""};
     int prec = -1;      // >= 0: Fixed
+    std::shared_ptr<const Expr> expr;   // Fixed(expr, prec) (prec >= 0) or Itoa(expr) (prec < 0)
     Part(const char* lit) : text(lit) {}                 // NOLINT: implicit, so that a template reads like the expression
     Part(std::string lit) : text(std::move(lit)) {}      // NOLINT
     Part(Col c) : is_col(true), col(std::move(c)) {}     // NOLINT
-    Part(Fixed f) : is_col(true), col(std::move(f.col)), prec(f.prec) {}   // NOLINT
+    Part(Fixed f) : is_col(!f.expr), col(std::move(f.col)), prec(f.prec), expr(std::move(f.expr)) {}   // NOLINT
+    Part(Itoa i) : expr(std::move(i.expr)) {}            // NOLINT
 };
 struct Format {
     std::vector<Part> parts;
@@ -385,6 +575,18 @@ struct Format {
     bool render(const Row& row, std::string* out, std::string* missing, std::string* invalid = nullptr) const {
         out->clear();
         for (const Part& p : parts) {
+            if (p.expr) {
+                int64_t iv = 0;
+                double fv = 0;
+                int op = -1;
+                const int32_t rc = p.expr->eval(row, &iv, &fv, &op, missing);
+                if (rc != CPH_NUM_OK) {
+                    if (rc > 0 && invalid) *invalid = p.expr->errorText(rc, op, row);
+                    return false;
+                }
+                *out += p.prec >= 0 ? FormatFixed(fv, p.prec) : std::to_string(iv);
+                continue;
+            }
             if (!p.is_col) {
                 *out += p.text;
                 continue;
@@ -418,6 +620,7 @@ inline Assign Set(std::string name, std::string literal) { return Assign{std::mo
 inline Assign Set(std::string name, const char* literal) { return Set(std::move(name), std::string(literal)); }
 inline Assign Set(std::string name, Format value) { return Assign{std::move(name), std::move(value)}; }
 inline Assign Set(std::string name, Fixed value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
+inline Assign Set(std::string name, Itoa value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
 
 using RowFunc = std::function<Error(Row)>;
 
@@ -495,6 +698,22 @@ private:
     std::vector<cph_strcol> cols_;
     std::vector<void*> pinned_;
 };
+
+// An expression over n rows by ONE cph_num_eval call: vals[c][i] = the value of the expression's column c in row i.
+inline int32_t evalStaged(cph_ctx* ctx, const Expr& e, const std::vector<std::vector<const std::string*>>& vals, size_t n, cph_numcol** out,
+                          int32_t* bad_op) {
+    std::vector<cph_expr_op> prog(e.ops.size());
+    for (size_t q = 0; q < prog.size(); q++) {
+        prog[q].op = e.ops[q].op;
+        prog[q].arg = e.ops[q].arg;
+        if (e.ops[q].op == CPH_EXPR_LIT_FLT) prog[q].lit.f = e.ops[q].f;
+        else prog[q].lit.i = e.ops[q].i;
+    }
+    StagedColumns st(ctx, vals.size());
+    st.stage(vals, n);
+    return cph_num_eval(ctx, vals.empty() ? nullptr : st.cols(), nullptr, (int32_t)vals.size(), n, nullptr, 0, prog.data(), (int32_t)prog.size(),
+                        CPH_MEM_HOST, out, bad_op);
+}
 
 struct DeviceIndex {   // owns a cph_index
     cph_index* h = nullptr;
@@ -596,7 +815,18 @@ struct Aggregate {
     int32_t op = 0;       // CPH_AGG_*
     int32_t kind = 0;     // CPH_NUM_INT64 / CPH_NUM_FLOAT64
     std::string column;
+    std::shared_ptr<const Expr> expr;   // instead of a column: an expression over the rows' columns, SumFloat(price * Float64(qty))
 };
+inline Aggregate aggregateOf(int32_t op, int32_t kind, Expr e, const char* who) {
+    if (e.kind != kind) throw Panic(std::string(who) + "() of an expression of the other type");
+    return {op, kind, std::string(), std::make_shared<const Expr>(std::move(e))};
+}
+inline Aggregate SumInt(Expr e) { return aggregateOf(CPH_AGG_SUM, CPH_NUM_INT64, std::move(e), "SumInt"); }
+inline Aggregate SumFloat(Expr e) { return aggregateOf(CPH_AGG_SUM, CPH_NUM_FLOAT64, std::move(e), "SumFloat"); }
+inline Aggregate MinInt(Expr e) { return aggregateOf(CPH_AGG_MIN, CPH_NUM_INT64, std::move(e), "MinInt"); }
+inline Aggregate MaxInt(Expr e) { return aggregateOf(CPH_AGG_MAX, CPH_NUM_INT64, std::move(e), "MaxInt"); }
+inline Aggregate MinFloat(Expr e) { return aggregateOf(CPH_AGG_MIN, CPH_NUM_FLOAT64, std::move(e), "MinFloat"); }
+inline Aggregate MaxFloat(Expr e) { return aggregateOf(CPH_AGG_MAX, CPH_NUM_FLOAT64, std::move(e), "MaxFloat"); }
 inline Aggregate SumInt(std::string col) { return {CPH_AGG_SUM, CPH_NUM_INT64, std::move(col)}; }
 inline Aggregate SumFloat(std::string col) { return {CPH_AGG_SUM, CPH_NUM_FLOAT64, std::move(col)}; }
 inline Aggregate MinInt(std::string col) { return {CPH_AGG_MIN, CPH_NUM_INT64, std::move(col)}; }
@@ -817,6 +1047,14 @@ public:
         for (const Assign& a : assigns) {
             std::set<std::string> cols;
             for (const Part& p : a.value.parts) {
+                if (p.expr) {
+                    for (const Col& c : p.expr->cols) {
+                        const bool known = std::find(written.begin(), written.end(), c.name) != written.end() ||
+                                           std::find(required.begin(), required.end(), c.name) != required.end();
+                        if (!c.has_default && !known) required.push_back(c.name);
+                    }
+                    continue;
+                }
                 if (!p.is_col) continue;
                 cols.insert(p.col.name);
                 const bool known = std::find(written.begin(), written.end(), p.col.name) != written.end() ||
@@ -898,6 +1136,65 @@ public:
     std::vector<double> ColumnAsFloat64(const std::string& name) const {
         std::vector<double> out;
         columnAsNumber(name, CPH_NUM_FLOAT64, &out);
+        return out;
+    }
+
+    // An expression for every row of the source — `price * float64(qty)` — by ONE cph_num_eval call over the staged columns:
+    // ints (an int64 expression) or floats (a float64 one), one value per row.  As the reference's iteration stops at the first
+    // row whose closure returns an error, the first failing row throws Error::DataSourceError(row number, counted from 0) with
+    // the reference's message for a value that does not convert (:176 / :198), "integer divide by zero" for a zero divisor; a row
+    // without a column throws its `missing column` error (:170 / :192).
+    struct Numbers {
+        int32_t kind = 0;   // CPH_NUM_INT64 / CPH_NUM_FLOAT64
+        std::vector<int64_t> ints;
+        std::vector<double> floats;
+    };
+    Numbers Evaluate(const Expr& e) const {
+        const size_t nc = e.cols.size();
+        std::vector<std::vector<std::string>> values(nc);
+        uint64_t missing = UINT64_MAX;
+        std::string missing_name;
+        uint64_t seen = 0;
+        Error err = fn_([&](Row row) -> Error {
+            for (size_t c = 0; c < nc; c++) {
+                auto it = row.find(e.cols[c].name);
+                if (it == row.end() && !e.cols[c].has_default) {
+                    missing = seen;
+                    missing_name = e.cols[c].name;
+                    for (size_t k = 0; k < c; k++) values[k].pop_back();
+                    return io_EOF;
+                }
+                values[c].push_back(it == row.end() ? e.cols[c].fallback : std::move(it->second));
+            }
+            seen++;
+            return Error();
+        });
+        if (err && !err.is_eof()) throw err;
+        const size_t n = (size_t)seen;
+        cph_ctx* ctx = Gpu::Default().ctx();
+        std::vector<std::vector<const std::string*>> vals(nc);
+        for (size_t c = 0; c < nc; c++) {
+            vals[c].resize(n);
+            for (size_t i = 0; i < n; i++) vals[c][i] = &values[c][i];
+        }
+        cph_numcol* res = nullptr;
+        int32_t op = -1;
+        if (detail::evalStaged(ctx, e, vals, n, &res, &op) != CPH_OK) throw Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+        struct Release { cph_numcol* r; ~Release() { cph_numcol_release(r); } } rel{res};
+        if (res->nerrors) {
+            const size_t row = (size_t)res->first_error_row;
+            throw Error::DataSourceError(row, Error(e.errorText(res->first_error_kind, op, [&](size_t c) { return values[c][row]; })));
+        }
+        if (missing != UINT64_MAX) throw Error::DataSourceError(missing, Error("missing column " + quote(missing_name)));
+        Numbers out;
+        out.kind = e.kind;
+        if (e.kind == CPH_NUM_INT64) {
+            out.ints.resize(n);
+            if (n) std::memcpy(out.ints.data(), res->values, n * sizeof(int64_t));
+        } else {
+            out.floats.resize(n);
+            if (n) std::memcpy(out.floats.data(), res->values, n * sizeof(double));
+        }
         return out;
     }
 
@@ -1108,6 +1405,28 @@ private:
         } nums;
         Error pending;
         for (const Part& p : a.value.parts) {
+            if (p.expr) {   // an expression's value: ONE cph_num_eval call over its columns, then an INT64 / FLOAT64 piece
+                const Expr& e = *p.expr;
+                std::vector<std::vector<const std::string*>> vals(e.cols.size());
+                for (size_t c = 0; c < e.cols.size(); c++) {
+                    vals[c].resize(n);
+                    for (size_t i = 0; i < n; i++) {
+                        auto it = (*batch)[i].find(e.cols[c].name);
+                        vals[c][i] = it == (*batch)[i].end() ? &e.cols[c].fallback : &it->second;
+                    }
+                }
+                cph_numcol* nc = nullptr;
+                int32_t op = -1;
+                if (detail::evalStaged(ctx, e, vals, n, &nc, &op) != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+                nums.v.push_back(nc);
+                if (nc->nerrors) {
+                    const size_t row = (size_t)nc->first_error_row;
+                    pending = Error(e.errorText(nc->first_error_kind, op, [&](size_t c) { return *vals[c][row]; }));
+                    n = row;
+                    if (n == 0) return pending;
+                }
+                continue;
+            }
             if (p.prec < 0) continue;
             std::vector<std::vector<const std::string*>> vals(1);
             vals[0].resize(n);
@@ -1133,6 +1452,16 @@ private:
         }
         size_t fixed_seen = 0;
         for (const Part& p : a.value.parts) {
+            if (p.expr && p.prec < 0) {
+                pieces.push_back(cph_map_piece{CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0}, static_cast<const int64_t*>(nums.v[fixed_seen++]->values),
+                                               nullptr, 0, 0});
+                continue;
+            }
+            if (p.expr) {
+                pieces.push_back(cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr,
+                                               static_cast<const double*>(nums.v[fixed_seen++]->values), p.prec, 0});
+                continue;
+            }
             if (!p.is_col) {
                 pieces.push_back(cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr});
                 continue;
@@ -1549,9 +1878,19 @@ inline Error Index::ResolveDuplicates(const Resolver& rs) {
 inline std::pair<TotalsResult, Error> Index::Totals(const std::vector<Aggregate>& aggs) const {
     TotalsResult out;
     if (aggs.size() > (size_t)CPH_AGG_MAX_SPECS) return {out, Error("too many aggregates in Index.Totals()")};
-    for (const Aggregate& a : aggs)
-        if (!impl_rows.empty() && column_presence(a.column) != kAll) return {out, Error("missing column " + quote(a.column))};
+    for (const Aggregate& a : aggs) {
+        if (impl_rows.empty()) break;
+        if (!a.expr) {
+            if (column_presence(a.column) != kAll) return {out, Error("missing column " + quote(a.column))};
+            continue;
+        }
+        for (const Col& c : a.expr->cols)
+            if (!c.has_default && column_presence(c.name) != kAll) return {out, Error("missing column " + quote(c.name))};
+    }
     cph_ctx* ctx = Gpu::Default().ctx();
+    // an expression is evaluated over the rows in index order by ONE cph_num_eval call (its lowest failing row is the first in
+    // index order) and handed in as numbers, scattered to the build table's row order
+    std::vector<std::vector<int64_t>> numbers(aggs.size());
     // value columns in the row order of the twin's BUILD TABLE (see ResolveDuplicates): row perm[p] = the value of impl_rows[p]
     std::vector<cph_agg_spec> specs(aggs.size());
     std::vector<std::unique_ptr<detail::StagedColumns>> scattered;
@@ -1564,6 +1903,31 @@ inline std::pair<TotalsResult, Error> Index::Totals(const std::vector<Aggregate>
         for (uint64_t p = 0; p < pn && identity; p++) identity = perm[p] == p;
         for (size_t a = 0; a < aggs.size(); a++) {
             specs[a] = cph_agg_spec{aggs[a].op, aggs[a].kind, nullptr, nullptr, CPH_MEM_HOST, 0};
+            if (aggs[a].expr) {
+                const Expr& e = *aggs[a].expr;
+                std::vector<std::vector<const std::string*>> vals(e.cols.size());
+                for (size_t c = 0; c < e.cols.size(); c++) {
+                    vals[c].resize(impl_rows.size());
+                    for (uint64_t q = 0; q < pn; q++) {
+                        auto it = impl_rows[(size_t)q].find(e.cols[c].name);
+                        vals[c][(size_t)q] = it == impl_rows[(size_t)q].end() ? &e.cols[c].fallback : &it->second;
+                    }
+                }
+                cph_numcol* nc = nullptr;
+                int32_t op = -1;
+                if (detail::evalStaged(ctx, e, vals, impl_rows.size(), &nc, &op) != CPH_OK)
+                    throw std::runtime_error(std::string("csvplus: ") + cph_last_error(ctx));
+                struct ReleaseNum { cph_numcol* r; ~ReleaseNum() { cph_numcol_release(r); } } reln{nc};
+                if (nc->nerrors) {
+                    const size_t row = (size_t)nc->first_error_row;
+                    return {TotalsResult(), Error(e.errorText(nc->first_error_kind, op, impl_rows[row]))};
+                }
+                numbers[a].resize(impl_rows.size());   // 8-byte values of either type
+                const int64_t* v = static_cast<const int64_t*>(nc->values);
+                for (uint64_t q = 0; q < pn; q++) numbers[a][perm[q]] = v[q];
+                specs[a].numbers = numbers[a].data();
+                continue;
+            }
             if (identity) {
                 specs[a].col = side_column(ctx, aggs[a].column);
                 continue;

@@ -14,6 +14,11 @@ the new column in row i is the concatenation of the template's parts —
                          `strconv.FormatFloat(price*float64(qty), 'f', 2, 64)` (csvplus_test.go:1391-1421).  prec is 0..22 and
                          finite values of 2^128 or more are refused, on the device and by the host model alike; host or
                          device array as for Int: Float.on_device(device_ptr, count, prec).
+    Int.of(expr)         the value of an int64 expression of csvplus_amd.expr over the same rows, written as Int writes it;
+    Float.of(expr, prec) likewise for a float64 expression: the amounts column is
+                         Float.of(FloatCol("price") * ToFloat(IntCol("qty")), 2) — converted, multiplied and formatted on
+                         the device (cph_num_eval feeding cph_map_format), evaluated by `render` with expr.evaluate.  A row
+                         whose expression fails raises expr.ExprError: the reference's conversion error, row and column named.
 
 `compile` turns a template into the piece list cph_map_format takes (include/csvplus_hip.h), `render` evaluates it on one
 row held as a dict — the host model, for callers without a GPU and as the cross-check of the device.  Nothing here
@@ -57,7 +62,9 @@ class Col:
 class Int:
     """One int64 per OUTPUT row, formatted as strconv.Itoa does.  Int(values): anything numpy turns into an int64 array, in
     host memory; Int.on_device(device_ptr, count): an int64 array on the device, e.g. NumCol.values of
-    materialize.to_int(..., out_mem=DEVICE) after arithmetic on it."""
+    materialize.to_int / eval_number(..., out_mem=DEVICE); Int.of(expr): an int64 expression of csvplus_amd.expr,
+    evaluated over the template's rows."""
+    expr = None
 
     def __init__(self, values):
         if isinstance(values, np.ndarray):
@@ -76,7 +83,18 @@ class Int:
         self.device, self.values, self.count = True, int(device_ptr), int(count)
         return self
 
+    @classmethod
+    def of(cls, expr) -> "Int":
+        from . import expr as E
+        if E.kind_of(expr) != E.INT:
+            raise TypeError("Int.of: the expression is a float64 (use Float.of, or ToInt)")
+        self = cls.__new__(cls)
+        self.device, self.values, self.count, self.expr = False, None, None, expr
+        return self
+
     def __repr__(self):
+        if self.expr is not None:
+            return f"Int.of({self.expr!r})"
         return f"Int(<{self.count} values{' on the device' if self.device else ''}>)"
 
 
@@ -90,7 +108,9 @@ class Float:
     """One float64 per OUTPUT row, formatted as strconv.FormatFloat(v, 'f', prec, 64) does.  Float(values, prec): anything
     numpy turns into a float64 array (an integer array is converted, as Go's float64(qty) would), in host memory;
     Float.on_device(device_ptr, count, prec): a float64 array on the device, e.g. NumCol.values of
-    materialize.to_float(..., out_mem=DEVICE) after arithmetic on it.  prec: 0..22."""
+    materialize.to_float / eval_number(..., out_mem=DEVICE); Float.of(expr, prec): a float64 expression of csvplus_amd.expr,
+    evaluated over the template's rows.  prec: 0..22."""
+    expr = None
 
     def __init__(self, values, prec):
         self.prec = _check_prec(prec, "Float")
@@ -107,7 +127,19 @@ class Float:
         self.device, self.values, self.count = True, int(device_ptr), int(count)
         return self
 
+    @classmethod
+    def of(cls, expr, prec: int) -> "Float":
+        from . import expr as E
+        if E.kind_of(expr) != E.FLOAT:
+            raise TypeError("Float.of: the expression is an int64 (use Int.of, or ToFloat)")
+        self = cls.__new__(cls)
+        self.prec = _check_prec(prec, "Float.of")
+        self.device, self.values, self.count, self.expr = False, None, None, expr
+        return self
+
     def __repr__(self):
+        if self.expr is not None:
+            return f"Float.of({self.expr!r}, {self.prec})"
         return f"Float(<{self.count} values{' on the device' if self.device else ''}>, {self.prec})"
 
 
@@ -144,11 +176,19 @@ def _template(t) -> Format:
 
 
 def columns(template) -> list:
-    """The names of the template's Col parts, in order of first use."""
+    """The names of the template's Col parts and of the columns its Int.of / Float.of expressions read, in order of first use."""
     names: list[str] = []
     for p in _template(template).parts:
-        if isinstance(p, Col) and p.name not in names:
-            names.append(p.name)
+        if isinstance(p, Col):
+            found = [p.name]
+        elif isinstance(p, (Int, Float)) and p.expr is not None:
+            from . import expr as E
+            found = E.columns(p.expr)
+        else:
+            continue
+        for name in found:
+            if name not in names:
+                names.append(name)
     return names
 
 
@@ -212,13 +252,27 @@ def ftoa(v, prec) -> bytes:
     return b"%.*f" % (prec, v)
 
 
+def _expr_value(p, row, i):
+    from . import expr as E
+    v, status, op = E.evaluate(p.expr, row, i)
+    if status:
+        names, ops = E.compile(p.expr, E.columns(p.expr))
+        column = names[ops[op][1]] if ops[op][0] in (E.COL_INT, E.COL_FLT) else None
+        raise E.ExprError(i, op, status, column, E.error_text(p.expr, row, status, op), 1)
+    return v
+
+
 def render(template, row, i: int = 0) -> bytes:
     """The template on one row (a dict with str or bytes keys and values); `i` = the row's number, which is what an Int
-    or Float part is indexed with (host arrays only)."""
+    or Float part is indexed with (host arrays only).  An Int.of / Float.of part is evaluated with expr.evaluate; a row
+    where it fails raises expr.ExprError."""
     out = []
     for p in _template(template).parts:
         if isinstance(p, bytes):
             out.append(p)
+        elif isinstance(p, (Int, Float)) and p.expr is not None:
+            v = _expr_value(p, row, i)
+            out.append(itoa(v) if isinstance(p, Int) else ftoa(v, p.prec))
         elif isinstance(p, Int):
             if p.device:
                 raise ValueError("render: an Int part on the device has no host values")

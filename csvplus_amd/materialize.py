@@ -1,7 +1,8 @@
 """The step after the path: gathering columns through the joined row ids and writing the
 canonical CSV or JSON (cph_gather_rows / cph_csv_write / cph_json_write_rows; mergeRows csvplus.go:571-583,
 ToCsv :379-406, ToJSON :446-480), filtering rows (cph_filter_rows), converting a column to numbers
-(cph_col_to_number; ValueAsInt / ValueAsFloat64 :165-205) and computing a column from a row template (cph_map_format;
+(cph_col_to_number; ValueAsInt / ValueAsFloat64 :165-205), evaluating a numeric expression per row (cph_num_eval:
+`price * float64(qty)`, csvplus_test.go:516-571) and computing a column from a row template (cph_map_format;
 Map :290-296, Validate :300-310)."""
 from __future__ import annotations
 
@@ -406,6 +407,92 @@ def to_float(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, out_mem: int
     return _to_number(ctx, col, row_ids, nrows, N.CPH_NUM_FLOAT64, out_mem)
 
 
+# ---- numeric expressions per row (cph_num_eval) ---------------------------------------------------------------------------
+
+def eval_number(ctx: N.Context, cols_by_name, expr, row_ids=None, nrows=None, out_mem: int = N.CPH_MEM_HOST) -> NumCol:
+    """An expression of csvplus_amd.expr — `FloatCol("price") * ToFloat(IntCol("qty"))` — for every row, on the device
+    (cph_num_eval): one kernel parses the string leaves and does the arithmetic with Go's rules.  cols_by_name: {column
+    name: StrCol}, the row the expression sees (a name it lacks raises mapping.MissingColumn); row_ids: {name: ids} as in
+    filter_rows, for columns read through row ids (a Join's); nrows: the number of rows (default: what the columns, the row
+    ids or the arrays give).  An IntArr / FloatArr leaf is indexed by OUTPUT row.
+
+    Returns a NumCol of the expression's type.  A failing row is data — status per row, nerrors, first_error_row,
+    first_error_kind and `first_error_op`, the index (into expr.compile's ops) of the op that failed there, None without
+    errors; raise_expr_error turns it into the reference's message."""
+    from . import expr as E
+
+    names, ops = E.compile(expr, list(cols_by_name))
+    cols = [cols_by_name[nm] for nm in names]
+    ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
+    arrs = E.arrays(ops)
+    keep = []
+    if cols:
+        arr, sel, n = _rowsel(cols, ids, nrows, keep)
+    else:
+        arr, sel = None, None
+        if nrows is not None:
+            n = int(nrows)
+        elif arrs:
+            n = min(a.count for a in arrs)
+        else:
+            raise ValueError("eval_number: an expression without columns and arrays needs nrows")
+    nums = (N.cph_expr_nums * max(len(arrs), 1))()
+    for k, a in enumerate(arrs):
+        if a.count < n:
+            raise ValueError(f"eval_number: {a!r} has {a.count} values for {n} rows")
+        if a.device:
+            nums[k].ptr, nums[k].mem = a.values or None, N.CPH_MEM_DEVICE
+        else:
+            keep.append(a.values)
+            nums[k].ptr, nums[k].mem = (a.values.ctypes.data if a.count else None), N.CPH_MEM_HOST
+    prog = (N.cph_expr_op * len(ops))()
+    for k, (op, arg, value) in enumerate(ops):
+        prog[k].op, prog[k].arg = op, arg
+        if op == E.LIT_INT:
+            prog[k].lit.i = value
+        elif op == E.LIT_FLT:
+            prog[k].lit.f = value
+    out = C.POINTER(N.cph_numcol)()
+    eop = C.c_int32(-1)
+    ctx._check(ctx.lib.cph_num_eval(ctx.handle, arr, sel, len(cols), n, nums if arrs else None, len(arrs), prog, len(ops), out_mem,
+                                    C.byref(out), C.byref(eop)))
+    del keep
+    res = NumCol(ctx, out)
+    res.first_error_op = None if eop.value < 0 else int(eop.value)
+    if out_mem == N.CPH_MEM_HOST:
+        res.release()   # the arrays are copies
+    return res
+
+
+def _value_at(ctx, col: StrCol, ids, row: int) -> bytes:
+    """The value of `col` that feeds output row `row` (ids: the column's row ids as the writers take them, or None)."""
+    one = np.array([row], dtype=np.uint64)
+    if col.mem == N.CPH_MEM_HOST:
+        src = take_rows(ctx, ids, one)
+        return gather_rows(ctx, col, np.asarray(src, dtype=np.uint64)).value(0)
+    rl = take_rows(ctx, ids, one, out_mem=N.CPH_MEM_DEVICE)
+    try:
+        return gather_rows(ctx, col, rl.as_row_ids()).value(0)
+    finally:
+        rl.release()
+
+
+def raise_expr_error(ctx, cols_by_name, expr, numcol, row_ids=None):
+    """Raises expr.ExprError for the lowest failing row of an eval_number result: the reference's conversion error with the
+    column named and the value quoted for a leaf that does not convert (csvplus.go:176, :198), a plain statement for a zero
+    divisor or a ToInt out of range."""
+    from . import expr as E
+
+    names, ops = E.compile(expr, list(cols_by_name))
+    row, op, kind = numcol.first_error_row, numcol.first_error_op, numcol.first_error_kind
+    column, values = None, {}
+    if ops[op][0] in (E.COL_INT, E.COL_FLT):
+        column = names[ops[op][1]]
+        values[column] = _value_at(ctx, cols_by_name[column], None if row_ids is None else row_ids.get(column), row)
+    # error_text compiles against the expression's own columns: the op index is the same (names are numbered by first use)
+    raise E.ExprError(row, op, kind, column, E.error_text(expr, values, kind, op), numcol.nerrors)
+
+
 # ---- Map with a row template / Validate (cph_map_format; cph_filter_rows in TAKE_WHILE mode) ------------------------------
 
 def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None, out_mem: int = N.CPH_MEM_HOST):
@@ -416,26 +503,43 @@ def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None,
     or raises mapping.MissingColumn.  template: mapping.Format / Const (or a bare part).  row_ids: {name: ids} as in
     filter_rows, for columns read through row ids (a Join's); nrows: the number of rows (default: what the columns, the row
     ids or the Int / Float parts give).  An Int or Float part's array is indexed by OUTPUT row and lives on the host (numpy) or
-    on the device (Int.on_device, Float.on_device)."""
+    on the device (Int.on_device, Float.on_device); an Int.of / Float.of part's expression is evaluated over the same rows
+    on the device (eval_number) and a row where it fails raises expr.ExprError."""
     from . import mapping as M
 
     names, pieces = M.compile(template, list(cols_by_name))
     cols = [cols_by_name[nm] for nm in names]
     ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
+    exprs = [p[2].expr for p in pieces if p[0] in (M.INT64, M.FLOAT64) and p[2].expr is not None]
     keep = []
     if cols:
         arr, sel, n = _rowsel(cols, ids, nrows, keep)
     else:
         arr, sel = None, None
-        counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64)]
+        counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64) and p[2].expr is None]
+        from . import expr as E
+        ecols = [nm for e in exprs for nm in E.columns(e) if nm in cols_by_name]
         if nrows is not None:
             n = int(nrows)
+        elif ecols:   # the rows an expression's columns give
+            n = _rowsel([cols_by_name[nm] for nm in ecols], None if row_ids is None else [row_ids.get(nm) for nm in ecols], None, [])[2]
         elif counts:
             n = min(counts)
         elif cols_by_name:
             n = min(c.nrows for c in cols_by_name.values())
         else:
             raise ValueError("map_column: a template without columns and Int / Float parts needs nrows")
+    computed = []   # the expressions' results, on the device until the template has run
+    try:
+        return _map_pieces(ctx, cols_by_name, row_ids, pieces, arr, sel, len(cols), n, out_mem, keep, computed)
+    finally:
+        for nc in computed:
+            nc.release()
+
+
+def _map_pieces(ctx, cols_by_name, row_ids, pieces, arr, sel, ncols, n, out_mem, keep, computed):
+    from . import mapping as M
+
     parr = (N.cph_map_piece * len(pieces))()
     for k, (kind, arg, value) in enumerate(pieces):
         parr[k].kind = kind
@@ -447,9 +551,15 @@ def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None,
         elif kind == M.COLUMN:
             parr[k].arg = arg
         else:
-            if value.count < n:
+            if value.expr is not None:   # evaluated over the same rows into a device array: cph_num_eval
+                nc = eval_number(ctx, cols_by_name, value.expr, row_ids=row_ids, nrows=n, out_mem=N.CPH_MEM_DEVICE)
+                computed.append(nc)
+                if nc.nerrors:
+                    raise_expr_error(ctx, cols_by_name, value.expr, nc, row_ids)
+                mem, ptr = N.CPH_MEM_DEVICE, nc.values[0] or None
+            elif value.count < n:
                 raise ValueError(f"map_column: {'an Int' if kind == M.INT64 else 'a Float'} part has {value.count} values for {n} rows")
-            if value.device:
+            elif value.device:
                 mem, ptr = N.CPH_MEM_DEVICE, value.values or None
             else:
                 keep.append(value.values)
@@ -460,7 +570,7 @@ def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None,
             else:
                 parr[k].floats, parr[k].prec = ptr, value.prec
     out = C.POINTER(N.cph_colbuf)()
-    ctx._check(ctx.lib.cph_map_format(ctx.handle, arr, sel, len(cols), n, parr, len(pieces), out_mem, C.byref(out)))
+    ctx._check(ctx.lib.cph_map_format(ctx.handle, arr, sel, ncols, n, parr, len(pieces), out_mem, C.byref(out)))
     del keep
     return ColBuf(ctx, out)
 

@@ -65,7 +65,10 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
     (Format, Const) per new column, applied in dict order over the joined rows that are left: a Col is looked up among the
     columns computed so far, then in the joined row as `where` does.  An out_columns entry whose output name is a computed
     name takes the computed column (its table and column are ignored and may be None): `row[name] = ...` replaces a source
-    column of that name.  None (default): nothing is computed.
+    column of that name.  A Float.of / Int.of part computes its value from an expression of csvplus_amd.expr over the same
+    rows on the device — {"amount": Format(Float.of(FloatCol("price") * ToFloat(IntCol("qty")), 2))} is the reference's
+    amounts column — and a row where it fails raises expr.ExprError with the row and the column.  None (default): nothing
+    is computed.
     Returns the CSV text (header + joined rows, stream order): bytes, or a DeviceBytes handle for out_mem DEVICE."""
     def lap(name, t0):
         if timings is not None:

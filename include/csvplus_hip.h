@@ -824,6 +824,81 @@ CPH_API int32_t cph_col_to_number(cph_ctx* ctx, const cph_strcol* col, const cph
                                   int32_t out_mem, cph_numcol** out);
 CPH_API void    cph_numcol_release(cph_numcol* col);
 
+/* ---- Numeric expressions per row: price * float64(qty) (csvplus_test.go:516-571, :1391-1421) ---- */
+/*
+ * The reference's numeric flows convert two columns of a (joined) row and do arithmetic on them in a Go closure:
+ * `price * float64(qty)`.  A closure cannot run on a GPU; a small typed POSTFIX PROGRAM can.  Every op works on a stack of
+ * int64 / float64 values, evaluated per output row i:
+ *   CPH_EXPR_COL_INT   push strconv.Atoi(value of column `arg` in this row)          -> int64   (cph_col_to_number's rules)
+ *   CPH_EXPR_COL_FLT   push strconv.ParseFloat(value of column `arg`, 64)            -> float64 (likewise)
+ *   CPH_EXPR_NUM_INT   push ((const int64_t*)nums[arg].ptr)[i]                       -> int64
+ *   CPH_EXPR_NUM_FLT   push ((const double*)nums[arg].ptr)[i]                        -> float64
+ *   CPH_EXPR_LIT_INT / CPH_EXPR_LIT_FLT   push lit.i / lit.f
+ *   CPH_EXPR_TO_FLT    float64(x) of an int64: rounded to nearest, ties to even
+ *   CPH_EXPR_TO_INT    int64(x) of a float64: truncation toward zero
+ *   CPH_EXPR_NEG       -x;   CPH_EXPR_ADD SUB MUL DIV: pop b, pop a, push a OP b;   CPH_EXPR_MOD: the same, int64 only
+ * Columns are read through their row ids as everywhere (cols / sel / ncols / nrows mean exactly what they mean for
+ * cph_map_format: host or device columns, fixed-width or 32 / 64-bit offsets, one cph_rowsel per column, so a Join's output
+ * evaluates without being materialised).  A number array has nrows entries in nums[k].mem (CPH_MEM_HOST / CPH_MEM_DEVICE; a
+ * host array is staged) and entry i belongs to OUTPUT row i — it is not read through row ids, like the pieces of Map.
+ *
+ * Typing is Go's: there are no implicit conversions.  The host checks the program before anything is launched: ADD SUB MUL
+ * DIV take two operands of the same type, MOD and TO_FLT take int64, TO_INT takes float64, NEG takes either, and exactly
+ * one value must be left — its type is the result's `kind`.
+ *
+ * Arithmetic.  int64: ADD SUB MUL NEG wrap in two's complement; DIV truncates toward zero and MOD has the dividend's sign
+ * (-7 / 2 == -3, -7 % 2 == -1, 7 / -2 == -3, 7 % -2 == 1); INT64_MIN / -1 == INT64_MIN and INT64_MIN % -1 == 0 (the Go
+ * specification, not a trap).  A zero divisor — a run-time panic in Go — is DATA here: status CPH_NUM_ERR_DIV_ZERO, value 0.
+ * float64: every op is ONE correctly rounded IEEE operation; a product feeding a sum is never contracted into a fused
+ * multiply-add (Go on amd64 never fuses); division by zero gives +-Inf or NaN as IEEE says and is no error.
+ * TO_INT of a NaN or of a value outside [-2^63, 2^63) is CPH_NUM_ERR_CONVERT with value 0: Go leaves that conversion
+ * implementation-defined and this library does not guess (the stance of CPH_NUM_ERR_UNSUPPORTED).
+ *
+ * Errors are DATA, as for cph_col_to_number: the call returns CPH_OK and the result says what failed.  A COL_* leaf that does
+ * not convert carries cph_col_to_number's status for that value.  Within one row the FIRST failing op in program order
+ * decides the row's status (the reference's closure returns at its first error); later ops do not matter.  An error row
+ * holds value 0.  nerrors counts rows; first_error_row is the lowest failing row, first_error_kind its status, and
+ * *first_error_op (may be NULL) the index of the op that failed there, -1 without errors — what a host needs to name the
+ * column in its message.
+ *
+ * The result is an ordinary cph_numcol (released with cph_numcol_release): kind = the program's result type, values and
+ * status per row in out_mem; it plugs into CPH_MAP_INT64 / CPH_MAP_FLOAT64 pieces and cph_agg_spec.numbers unchanged.
+ * One kernel reads the strings once and writes 9 bytes per row.  The float rows the device defers (cph_col_to_number) make
+ * the call convert every string leaf by that entry point's route first — the host finishing included — and evaluate over
+ * the converted arrays; both routes give the same bits, and host_rows counts the rows with a deferred float leaf.
+ *
+ * CPH_ERR_INVALID (with a message in cph_last_error, *out stays NULL): NULL ctx / prog / out, cols NULL with ncols > 0, nums
+ * NULL with nnums > 0, ncols outside 0..16, nops outside 1..CPH_EXPR_MAX_OPS, nnums outside 0..CPH_EXPR_MAX_NUMS, an unknown
+ * op, a COL_* arg outside 0..ncols-1, a NUM_* arg outside 0..nnums-1, a number array that is NULL while nrows > 0 or has an
+ * unknown memory space, a type violation, an operand missing, a stack deeper than CPH_EXPR_MAX_STACK, a program that does
+ * not leave exactly one value, an unknown out_mem, row-id bits other than 32 / 64, an identity column whose row count is
+ * not nrows.  nrows == 0 is legal (values and status are NULL).
+ *
+ * Out of scope: comparisons and boolean results (cph_filter_rows has INT_* / FLT_* terms), math functions and rounding
+ * helpers, string operands, more than one result per call.
+ */
+enum { CPH_NUM_ERR_DIV_ZERO = 4, CPH_NUM_ERR_CONVERT = 5 };   /* beside CPH_NUM_OK .. CPH_NUM_ERR_UNSUPPORTED = 0..3 */
+enum { CPH_EXPR_COL_INT = 1, CPH_EXPR_COL_FLT = 2, CPH_EXPR_NUM_INT = 3, CPH_EXPR_NUM_FLT = 4, CPH_EXPR_LIT_INT = 5,
+       CPH_EXPR_LIT_FLT = 6, CPH_EXPR_TO_FLT = 8, CPH_EXPR_TO_INT = 9, CPH_EXPR_NEG = 10, CPH_EXPR_ADD = 11, CPH_EXPR_SUB = 12,
+       CPH_EXPR_MUL = 13, CPH_EXPR_DIV = 14, CPH_EXPR_MOD = 15 };
+#define CPH_EXPR_MAX_OPS   32
+#define CPH_EXPR_MAX_STACK 8
+#define CPH_EXPR_MAX_NUMS  8
+typedef struct {
+    int32_t op;    /* CPH_EXPR_* */
+    int32_t arg;   /* COL_*: index into cols; NUM_*: index into nums; otherwise ignored */
+    union { int64_t i; double f; } lit;   /* LIT_INT / LIT_FLT */
+} cph_expr_op;
+typedef struct {
+    const void* ptr;   /* int64_t[nrows] or double[nrows]; entry i belongs to OUTPUT row i */
+    int32_t     mem;   /* CPH_MEM_HOST / CPH_MEM_DEVICE */
+    int32_t     reserved_;
+} cph_expr_nums;
+
+CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
+                             const cph_expr_nums* nums, int32_t nnums, const cph_expr_op* prog, int32_t nops,
+                             int32_t out_mem, cph_numcol** out, int32_t* first_error_op /* may be NULL */);
+
 /* ---- Map with a row template: a computed string column (csvplus.go:290-296) ---- */
 /*
  * The reference's Map takes a closure (`row["name"] = "Julia"`, `row["full"] = row["name"] + " " + row["surname"]`, the
@@ -834,7 +909,7 @@ CPH_API void    cph_numcol_release(cph_numcol* col);
  *   CPH_MAP_INT64    ints[i] written as strconv.FormatInt(v, 10) does: '-' in front of a negative value, no '+', no leading
  *                    zeros, 0 gives "0", INT64_MIN its 20 characters.  `ints` has nrows entries in the memory space `arg`
  *                    (CPH_MEM_HOST / CPH_MEM_DEVICE); entry i belongs to OUTPUT row i (it is not read through row ids) —
- *                    e.g. the values of cph_col_to_number after arithmetic on them.
+ *                    e.g. the values of cph_col_to_number, or of cph_num_eval (an expression over the same rows).
  *   CPH_MAP_FLOAT64  floats[i] written as strconv.FormatFloat(v, 'f', prec, 64) does: an optional '-', the integer digits (at
  *                    least "0"), and with prec > 0 a '.' and exactly prec digits; rounded to nearest, ties to even, on the
  *                    EXACT binary value (2.675 at prec 2 gives "2.67", 2.5 at prec 0 "2", 0.125 at prec 2 "0.12").  The sign
