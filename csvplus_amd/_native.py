@@ -241,6 +241,21 @@ class cph_aggregated(C.Structure):
                 ("first_error_kind", C.c_int32), ("first_error_spec", C.c_int32), ("host_rows", C.c_uint64)]
 
 
+CPH_CHAIN_AGG_LDS_GROUPS = 4096   # cph_chain_aggregate: group tables up to this many build rows are accumulated in LDS
+
+
+class cph_chain_agg_spec(C.Structure):
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("numbers", C.c_void_p), ("status", C.c_void_p),
+                ("numbers_mem", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class cph_chain_aggregated(C.Structure):
+    _fields_ = [("ngroups", C.c_uint64), ("count", C.c_void_p), ("values", C.c_void_p * CPH_AGG_MAX_SPECS),
+                ("nspecs", C.c_int32), ("mem", C.c_int32), ("positions", C.c_int32), ("reserved_", C.c_int32),
+                ("nerrors", C.c_uint64), ("first_error_row", C.c_uint64),
+                ("first_error_kind", C.c_int32), ("first_error_spec", C.c_int32)]
+
+
 CPH_DIST_ID_BYTES = 128
 CPH_MAX_GATHER = 8
 
@@ -370,6 +385,10 @@ PROTOTYPES = [
     ("cph_index_aggregate", C.c_int32,
      [_P, _P, C.POINTER(cph_agg_spec), C.c_int32, C.c_int32, C.POINTER(C.POINTER(cph_aggregated))]),
     ("cph_aggregated_release", None, [C.POINTER(cph_aggregated)]),
+    ("cph_chain_aggregate", C.c_int32,
+     [_P, C.POINTER(cph_chain), C.c_int32, _P, C.POINTER(cph_chain_agg_spec), C.c_int32, C.c_int32,
+      C.POINTER(C.POINTER(cph_chain_aggregated))]),
+    ("cph_chain_aggregated_release", None, [C.POINTER(cph_chain_aggregated)]),
     ("cph_index_save", C.c_int32, [_P, _P, C.c_char_p]),
     ("cph_index_load", C.c_int32, [_P, C.c_char_p, C.POINTER(_P)]),
     ("cph_index_find", C.c_int32,

@@ -15,6 +15,10 @@ expression's type.
 A group is a maximal run of equal keys in the index, runs of ONE row included.  `totals` returns, per group in key order, the
 sorted position and the table row of its first row, its row count and one value per spec; `totals_model` states the same
 contract in pure Python over keys and values already in sorted order — documentation that runs, and what the tests expect.
+
+Totals over a Join (`custAmounts[cid] += amount`, csvplus_test.go:754-806) group the JOINED rows by the build row the Join
+matched: `join_totals(chain, step, index, specs)` (cph_chain_aggregate) with one value per joined row per spec, and
+`join_totals_model` as its contract.  There a group is a row of the index, empty groups included.
 """
 from __future__ import annotations
 
@@ -231,4 +235,152 @@ def totals_model(keys_in_sorted_order, values_by_sorted_position=(), specs=()):
         op, kind = (sp.op, sp.kind) if isinstance(sp, Spec) else sp
         vals = values_by_sorted_position[s]
         out["values"].append([_fold(op, kind == N.CPH_NUM_FLOAT64, vals[lo:hi]) for lo, hi in zip(starts, ends)])
+    return out
+
+
+# ---- Totals over a Join: Count and Sum / Min / Max per BUILD ROW of a chain step (cph_chain_aggregate) --------------------
+class JoinTotals:
+    """What `join_totals` returns: one group per build row of the step's index (ngroups == index.nrows), empty groups
+    included.  `positions`: group g is a sorted position of the index (True) or an original row id of its table (False), as
+    in the chain.  out_mem = HOST: count (uint64) and values[i] (int64 / float64) are numpy arrays; DEVICE: (device pointer,
+    count) pairs, valid until release()."""
+
+    def __init__(self, ngroups, count, values, positions, _release=None):
+        self.ngroups, self.count, self.values, self.positions = ngroups, count, values, positions
+        self._release = _release
+
+    def release(self):
+        """Gives the device blocks back (out_mem = DEVICE only)."""
+        if self._release:
+            self._release()
+            self._release = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _chain_row_ids(chain, which):
+    """The row ids the writers / eval_number take for a column of the stream table (which None / "stream") or of step
+    `which`'s build table, for the joined rows of `chain`."""
+    n = chain.nrows
+    if chain.mem == N.CPH_MEM_HOST:
+        if which in (None, "stream"):
+            return None if chain.identity or n == 0 else (chain.stream_row, chain.probe_base)
+        return chain.build_row(int(which))
+    ptrs = chain.device_ptrs()
+    if which in (None, "stream"):
+        return None if chain.identity or n == 0 else (ptrs["stream_row"], 64, n, chain.probe_base)
+    return (ptrs["build_row"][int(which)], 32, n)
+
+
+def join_totals(chain: N.Chain, step: int, index: N.DeviceIndex, specs=(), out_mem: int = N.CPH_MEM_HOST, columns=None) -> JoinTotals:
+    """Count and the specs' values per build row of `index`, the index of chain step `step`, over the JOINED rows of `chain`
+    (cph_chain_aggregate): `qtyMap[id] += qty` of the reference's TestSimpleUniqueJoin without a second index.  specs: Sum /
+    Min / Max whose source holds ONE VALUE PER JOINED ROW: a numpy array (host), a (device_ptr, count) pair or a device
+    tensor, a materialize.NumCol over the joined rows (its status is handed through: a row that failed raises TotalsError), or
+    an expression of csvplus_amd.expr, evaluated over the joined rows on the device (eval_number through the chain's row
+    ids; a failing row raises expr.ExprError).  columns: what an expression reads — {name: StrCol} for a column of the
+    stream table, {name: (StrCol, k)} for a column of step k's build table: in that table's original row order for a chain
+    of row ids, in the index's sorted order (materialize.permute_col) for a chain of positions.  The columns live where the
+    chain does (host / device).  A group is a build row, not a key: over a duplicate-key index add the rows of a run."""
+    from . import expr as E
+    from .materialize import NumCol, eval_number, raise_expr_error
+
+    specs = list(specs)
+    ctx = chain.ctx
+    n = chain.nrows
+    arr = (N.cph_chain_agg_spec * max(1, len(specs)))()
+    keep, evaluated = [], []
+    try:
+        for i, sp in enumerate(specs):
+            if not isinstance(sp, Spec):
+                raise TypeError(f"not an aggregate: {sp!r} (closures cannot run on the device; use Sum, Min, Max)")
+            if isinstance(sp.source, StrCol):
+                raise TypeError(f"{type(sp).__name__}: a join total takes one value per JOINED row; read a column with an "
+                                'expression (IntCol / FloatCol) and `columns`')
+            arr[i].op, arr[i].kind = sp.op, sp.kind
+            src = sp.source
+            if isinstance(src, E.Expr):
+                by_name, rid = {}, {}
+                for name in E.columns(src):
+                    if name not in (columns or {}):
+                        continue   # eval_number raises MissingColumn
+                    c = columns[name]
+                    col, which = c if isinstance(c, tuple) else (c, None)
+                    by_name[name], rid[name] = col, _chain_row_ids(chain, which)
+                src = eval_number(ctx, by_name, src, row_ids=rid, nrows=n, out_mem=N.CPH_MEM_DEVICE)
+                evaluated.append(src)
+                if src.nerrors:
+                    raise_expr_error(ctx, by_name, sp.source, src, row_ids=rid)
+            if isinstance(src, NumCol):
+                if src.kind != sp.kind:
+                    raise ValueError(f"{type(sp).__name__}: the NumCol's kind differs from the spec's")
+                if src.nrows < n:
+                    raise ValueError(f"{type(sp).__name__}: {src.nrows} values for {n} joined rows")
+                if src.mem == N.CPH_MEM_DEVICE and n:
+                    arr[i].numbers, arr[i].status, arr[i].numbers_mem = src.values[0] or None, src.status[0] or None, N.CPH_MEM_DEVICE
+                elif src.mem == N.CPH_MEM_DEVICE:   # no joined rows: a pointer that is never read
+                    v = np.zeros(1, np.int64)
+                    keep.append(v)
+                    arr[i].numbers, arr[i].numbers_mem = v.ctypes.data, N.CPH_MEM_HOST
+                else:
+                    v, st = np.ascontiguousarray(src.values), np.ascontiguousarray(src.status)
+                    if len(v) == 0:
+                        v, st = np.zeros(1, v.dtype), np.zeros(1, np.uint8)
+                    keep += [v, st]
+                    arr[i].numbers, arr[i].status, arr[i].numbers_mem = v.ctypes.data, st.ctypes.data, N.CPH_MEM_HOST
+                keep.append(src)
+                continue
+            cs = N.cph_agg_spec()
+            _fill_spec(cs, sp, keep)
+            if cs.numbers_mem == N.CPH_MEM_HOST and len(keep[-1]) < n:
+                raise ValueError(f"{type(sp).__name__}: {len(keep[-1])} values for {n} joined rows")
+            arr[i].numbers, arr[i].numbers_mem = cs.numbers, cs.numbers_mem
+        out = C.POINTER(N.cph_chain_aggregated)()
+        rc = ctx.lib.cph_chain_aggregate(ctx.handle, chain.ptr, int(step), index.handle if index is not None else None,
+                                         arr if specs else None, len(specs), out_mem, C.byref(out))
+    finally:
+        for nc in evaluated:
+            nc.release()
+    del keep
+    ctx._check(rc)
+    r = out.contents
+    if r.nerrors:
+        row = int(r.first_error_row)
+        err = TotalsError(row, row, int(r.first_error_kind), int(r.nerrors), int(r.first_error_spec))
+        ctx.lib.cph_chain_aggregated_release(out)
+        raise err
+    ng = int(r.ngroups)
+    dts = [np.int64 if sp.kind == N.CPH_NUM_INT64 else np.float64 for sp in specs]
+    if out_mem == N.CPH_MEM_HOST:
+        res = JoinTotals(ng, N._ptr_array(r.count, ng, np.uint64).copy(), [N._ptr_array(r.values[i], ng, dt).copy() for i, dt in enumerate(dts)],
+                         bool(r.positions))
+        ctx.lib.cph_chain_aggregated_release(out)
+        return res
+    return JoinTotals(ng, (int(r.count or 0), ng), [(int(r.values[i] or 0), ng) for i in range(len(specs))], bool(r.positions),
+                      _release=lambda: ctx.lib.cph_chain_aggregated_release(out))
+
+
+def join_totals_model(build_rows, ngroups, values=(), specs=()):
+    """The host statement of cph_chain_aggregate.  build_rows[m] = the group (build row) of joined row m, below ngroups;
+    values[s][m] = the value spec s reads at joined row m; specs = Sum / Min / Max objects or (op, kind) pairs.  Returns a
+    dict: ngroups, count, and values (one list per spec; 0 / +0.0 for a group without rows).  An int sum wraps to int64; a
+    float sum adds the group's rows in ascending m, left to right from -0.0 (the device's order is fixed but unspecified:
+    compare bit for bit only where every order is exact); float Min / Max are go_min / go_max."""
+    ngroups = int(ngroups)
+    members = [[] for _ in range(ngroups)]
+    for m, g in enumerate(build_rows):
+        g = int(g)
+        if not 0 <= g < ngroups:
+            raise ValueError(f"join_totals_model: build row {g} of joined row {m} is not below {ngroups}")
+        members[g].append(m)
+    out = {"ngroups": ngroups, "count": [len(ms) for ms in members], "values": []}
+    for s, sp in enumerate(specs):
+        op, kind = (sp.op, sp.kind) if isinstance(sp, Spec) else sp
+        is_float = kind == N.CPH_NUM_FLOAT64
+        vals = values[s]
+        out["values"].append([_fold(op, is_float, [vals[m] for m in ms]) if ms else (0.0 if is_float else 0) for ms in members])
     return out

@@ -289,21 +289,30 @@ struct cph_aggregated_impl {
     cph::DevBuf d_pos, d_row, d_cnt, d_val[CPH_AGG_MAX_SPECS];
 };
 
-namespace {
+namespace cph {
 
 unsigned agg_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
 
-struct ReduceArgs {
-    const uint64_t* bitmap;
-    const uint32_t* offs;
-    const uint64_t* src;
-    const uint32_t* perm;
-    uint64_t n, ntiles;
-    uint64_t *out, *head, *tail;
-};
+void agg_launch_heads(cph_ctx* ctx, const void* codes, bool key32, int nwords, uint64_t n, double code_bytes, uint64_t* bitmap, uint32_t* counts) {
+    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    ProfScope ps(ctx, "k_agg_heads", (double)n * (code_bytes + 1.0 / 8.0) + 4.0 * (double)ntiles);
+    if (key32)
+        hipLaunchKernelGGL(k_agg_heads<true>, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, codes, n, nwords, bitmap, counts);
+    else
+        hipLaunchKernelGGL(k_agg_heads<false>, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, codes, n, nwords, bitmap, counts);
+}
+
+void agg_launch_emit(cph_ctx* ctx, const uint64_t* bitmap, const uint32_t* offs, const uint32_t* perm, uint64_t n, uint64_t ngroups,
+                     uint64_t* first_position, uint32_t* first_row) {
+    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    ProfScope ps(ctx, "k_agg_emit", (double)n / 8.0 + 4.0 * (double)ntiles + 16.0 * (double)ngroups);
+    hipLaunchKernelGGL(k_agg_emit, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap, offs, perm, ntiles, first_position, first_row);
+}
+
+namespace {
 
 template <int OP, bool FLT>
-void launch_reduce(cph_ctx* ctx, bool gather, const ReduceArgs& a) {
+void launch_reduce(cph_ctx* ctx, bool gather, const AggReduceArgs& a) {
     {
         // byte model: 8 B per row (+ 4 B of perm and a sector per row for a gathered spec), 1 bit of bitmap, 8 B per group out
         ProfScope ps(ctx, gather ? "k_agg_reduce_gather" : "k_agg_reduce", (double)a.n * (8.0 + (gather ? 4.0 : 0.0) + 1.0 / 8.0) + 20.0 * (double)a.ntiles);
@@ -320,11 +329,22 @@ void launch_reduce(cph_ctx* ctx, bool gather, const ReduceArgs& a) {
 }
 
 template <bool FLT>
-void launch_reduce_op(cph_ctx* ctx, int32_t op, bool gather, const ReduceArgs& a) {
+void launch_reduce_op(cph_ctx* ctx, int32_t op, bool gather, const AggReduceArgs& a) {
     if (op == CPH_AGG_SUM) launch_reduce<CPH_AGG_SUM, FLT>(ctx, gather, a);
     else if (op == CPH_AGG_MIN) launch_reduce<CPH_AGG_MIN, FLT>(ctx, gather, a);
     else launch_reduce<CPH_AGG_MAX, FLT>(ctx, gather, a);
 }
+
+}  // namespace
+
+void agg_launch_reduce(cph_ctx* ctx, int32_t op, bool flt, bool gather, const AggReduceArgs& a) {
+    if (flt) launch_reduce_op<true>(ctx, op, gather, a);
+    else launch_reduce_op<false>(ctx, op, gather, a);
+}
+
+}  // namespace cph
+
+namespace {
 
 Status check_specs(const cph_index* ix, const cph_agg_spec* specs, int32_t nspecs) {
     if (nspecs < 0 || nspecs > CPH_AGG_MAX_SPECS) return {CPH_ERR_INVALID, "cph_index_aggregate: nspecs must be 0..CPH_AGG_MAX_SPECS"};
@@ -414,15 +434,8 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* ix, const cph
         DevBuf bitmap, counts;
         CPH_TRY(bitmap.alloc(&ctx->pool, ntiles * kResWords * sizeof(uint64_t)));
         CPH_TRY(counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
-        {
-            ProfScope ps(ctx, "k_agg_heads", (double)n * ((double)index_code_bytes(ix) + 1.0 / 8.0) + 4.0 * (double)ntiles);
-            if (ix->codec.key32)
-                hipLaunchKernelGGL(k_agg_heads<true>, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, ix->sorted_codes.get(), n,
-                                   ix->total_words(), bitmap.as<uint64_t>(), counts.as<uint32_t>());
-            else
-                hipLaunchKernelGGL(k_agg_heads<false>, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, ix->sorted_codes.get(), n,
-                                   ix->total_words(), bitmap.as<uint64_t>(), counts.as<uint32_t>());
-        }
+        agg_launch_heads(ctx, ix->sorted_codes.get(), ix->codec.key32, ix->total_words(), n, (double)index_code_bytes(ix), bitmap.as<uint64_t>(),
+                         counts.as<uint32_t>());
         CPH_HIP_TRY(hipGetLastError());
         CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));
         uint32_t total = 0;
@@ -432,11 +445,7 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* ix, const cph
         CPH_TRY(r->d_pos.alloc(&ctx->pool, ng * sizeof(uint64_t)));
         CPH_TRY(r->d_row.alloc(&ctx->pool, ng * sizeof(uint32_t)));
         CPH_TRY(r->d_cnt.alloc(&ctx->pool, ng * sizeof(uint64_t)));
-        {
-            ProfScope ps(ctx, "k_agg_emit", (double)n / 8.0 + 4.0 * (double)ntiles + 16.0 * (double)ng);
-            hipLaunchKernelGGL(k_agg_emit, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap.as<uint64_t>(), counts.as<uint32_t>(), perm,
-                               ntiles, r->d_pos.as<uint64_t>(), r->d_row.as<uint32_t>());
-        }
+        agg_launch_emit(ctx, bitmap.as<uint64_t>(), counts.as<uint32_t>(), perm, n, ng, r->d_pos.as<uint64_t>(), r->d_row.as<uint32_t>());
         CPH_HIP_TRY(hipGetLastError());
         {
             ProfScope ps(ctx, "k_agg_counts", 16.0 * (double)ng);
@@ -448,10 +457,9 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* ix, const cph
         if (nspecs) CPH_TRY(partials.alloc(&ctx->pool, 2 * ntiles * sizeof(uint64_t)));
         for (int32_t s = 0; s < nspecs; s++) {
             CPH_TRY(r->d_val[s].alloc(&ctx->pool, ng * sizeof(uint64_t)));
-            const ReduceArgs a{bitmap.as<uint64_t>(), counts.as<uint32_t>(), src[s], perm, n, ntiles, r->d_val[s].as<uint64_t>(),
+            const AggReduceArgs a{bitmap.as<uint64_t>(), counts.as<uint32_t>(), src[s], perm, n, ntiles, r->d_val[s].as<uint64_t>(),
                                partials.as<uint64_t>(), partials.as<uint64_t>() + ntiles};
-            if (specs[s].kind == CPH_NUM_FLOAT64) launch_reduce_op<true>(ctx, specs[s].op, specs[s].col == nullptr, a);
-            else launch_reduce_op<false>(ctx, specs[s].op, specs[s].col == nullptr, a);
+            agg_launch_reduce(ctx, specs[s].op, specs[s].kind == CPH_NUM_FLOAT64, specs[s].col == nullptr, a);
             CPH_HIP_TRY(hipGetLastError());
         }
         r->pub.ngroups = ng;

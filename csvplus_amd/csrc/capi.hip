@@ -573,6 +573,7 @@ CPH_API int32_t cph_ctx_create(int32_t device_id, cph_ctx** out) {
     warm_index_ops();
     warm_resolve();
     warm_aggregate();
+    warm_join_totals();
     warm_small_build();
     warm_window_sort();
     warm_counted_sort();

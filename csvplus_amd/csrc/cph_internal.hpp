@@ -768,6 +768,25 @@ Status chain_enqueue_codes(cph_ctx* ctx, const cph_index* const* idx, const uint
 uint64_t chain_dense_mask_words(uint64_t nprobe);
 uint64_t chain_dense_count_words(uint64_t nprobe);
 
+// aggregate.hip: the segmented reduction over runs of equal SORTED keys, shared by cph_index_aggregate and the float Sum route of
+// cph_chain_aggregate (join_totals.hip).  Tiles are kResTile = 2048 positions (runs_device.hpp); all launches go on ctx->stream.
+struct AggReduceArgs {
+    const uint64_t* bitmap;    // run starts, 32 words per tile (agg_launch_heads)
+    const uint32_t* offs;      // [ntiles + 1] run starts in front of every tile (the scanned counts of agg_launch_heads)
+    const uint64_t* src;       // gather: one 8-byte value per row id (read through perm); else one per sorted position
+    const uint32_t* perm;      // [n] row id at every sorted position
+    uint64_t n, ntiles;
+    uint64_t *out, *head, *tail;   // out[run rank]; head / tail: ntiles partials each, scratch
+};
+unsigned agg_grid(uint64_t ntiles);
+// bitmap[ntiles * 32], counts[ntiles] (+ 1 for the scan's total) over n >= 1 sorted keys: u32[n] (key32) or u64[nwords][n] word-major
+void agg_launch_heads(cph_ctx* ctx, const void* codes, bool key32, int nwords, uint64_t n, double code_bytes, uint64_t* bitmap, uint32_t* counts);
+// first_position[rank] = the run's first sorted position, first_row[rank] = perm[that]; ngroups only prices the launch
+void agg_launch_emit(cph_ctx* ctx, const uint64_t* bitmap, const uint32_t* offs, const uint32_t* perm, uint64_t n, uint64_t ngroups,
+                     uint64_t* first_position, uint32_t* first_row);
+// k_agg_reduce + k_agg_carry for op = CPH_AGG_*, over int64 (flt = false) or double patterns
+void agg_launch_reduce(cph_ctx* ctx, int32_t op, bool flt, bool gather, const AggReduceArgs& a);
+
 // every translation unit with kernels: forces its code object to load (called once per process from cph_ctx_create)
 void warm_keycodec();
 void warm_radix_sort();
@@ -778,6 +797,7 @@ void warm_csv_ingest();
 void warm_index_ops();
 void warm_resolve();
 void warm_aggregate();
+void warm_join_totals();
 void warm_small_build();
 void warm_window_sort();
 // host_encode.hip: IndexOn over one short key column in host memory through host-formed codes; *taken = false: not applicable

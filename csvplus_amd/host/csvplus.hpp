@@ -1198,6 +1198,115 @@ public:
         return out;
     }
 
+    // Totals over a Join — `custAmounts[cid] += amount` of the reference's TestTransformedSource (csvplus_test.go:754-806) without
+    // a second index: on the result of Join(...)[.Join(...)] the row count and the named aggregates per ROW of the index of
+    // Join number `step` (0 = the first), reduced on the device over the joined rows (cph_chain_aggregate).  Group g is row g of
+    // that index (index->rows()[g], key order); a row no stream row matched has count 0 and values 0.  Over an index with
+    // duplicate keys every row of a run is its own group: add the rows of a run for a total per key.  An aggregate's column or
+    // expression (SumFloat(AsFloat64(Col("price")) * Float64(AsInt(Col("qty"))))) reads the JOINED row: a name is looked up in
+    // the stream row first, then in the rows of the first Join's index, the second's, ... (mergeRows).  A joined row that lacks
+    // a column is the reference's `missing column` error, a value that does not convert the error of :176 / :198 for the first
+    // such joined row.  All stream rows go through ONE device call; a chain with DropColumns between its Joins, or whose later
+    // keys come from different places row by row, is a Panic here (take ToRows() and an Index::Totals instead).
+    struct JoinTotalsResult {
+        std::vector<uint64_t> counts;                 // [index rows]
+        std::vector<std::vector<int64_t>> ints;       // [aggregate][index row]; empty for a float aggregate
+        std::vector<std::vector<double>> floats;      // likewise
+    };
+    std::pair<JoinTotalsResult, Error> TotalsBy(size_t step, const std::vector<Aggregate>& aggs) const {
+        JoinTotalsResult out;
+        if (!chain_) throw Panic("TotalsBy() on a source that is not the result of a Join()");
+        const ChainSpec& spec = *chain_;
+        const size_t S = spec.steps.size();
+        if (step >= S) throw Panic("TotalsBy() of a Join the chain does not have");
+        if (aggs.size() > (size_t)CPH_AGG_MAX_SPECS) return {out, Error("too many aggregates in TotalsBy()")};
+        for (const auto& st : spec.steps)
+            if (!st.drop_after.empty()) throw Panic("TotalsBy() over a chain with DropColumns between its Joins");
+        std::vector<Row> rows;
+        Error err = spec.upstream([&](Row row) -> Error {
+            std::vector<const std::string*> tmp;
+            if (Error e = SelectValues(row, spec.steps[0].columns, &tmp)) return e;   // :556
+            rows.push_back(std::move(row));
+            return Error();
+        });
+        if (err && !err.is_eof()) return {out, err};
+        cph_ctx* ctx = Gpu::Default().ctx();
+        const Index& index = *spec.steps[step].index;
+        const size_t ng = index.impl_rows.size();
+        out.ints.resize(aggs.size());
+        out.floats.resize(aggs.size());
+        out.counts.assign(ng, 0);
+        for (size_t a = 0; a < aggs.size(); a++) {
+            if (aggs[a].kind == CPH_NUM_INT64) out.ints[a].assign(ng, 0);
+            else out.floats[a].assign(ng, 0.0);
+        }
+        if (rows.empty() || ng == 0) return {out, Error()};
+        std::vector<int> origin(S, 0);
+        for (size_t k = 1; k < S; k++) {
+            int org = -2;
+            for (const auto& col : spec.steps[k].columns) {
+                const int o = columnOrigin(ctx, spec, k, col, rows);
+                if (o < 0 || (org != -2 && o != org)) throw Panic("TotalsBy() over a chain whose key columns have no single origin");
+                org = o;
+            }
+            origin[k] = org;
+        }
+        cph_chain* ch = nullptr;
+        if (Error je = fusedJoin(ctx, spec, origin, rows, &ch)) return {out, je};
+        struct ReleaseChain { cph_chain* c; ~ReleaseChain() { cph_chain_release(c); } } relc{ch};
+        const size_t n = (size_t)ch->nrows;
+        // the value of a column in joined row m: the stream's, else the first index row of the chain that carries it
+        auto value_of = [&](const Col& c, size_t m) -> const std::string* {
+            const Row& srow = rows[(size_t)(ch->stream_row ? ch->stream_row[m] : m)];
+            auto it = srow.find(c.name);
+            if (it != srow.end()) return &it->second;
+            for (size_t k = 0; k < S; k++) {
+                const Row& r = spec.steps[k].index->impl_rows[ch->build_row[k][m]];
+                auto jt = r.find(c.name);
+                if (jt != r.end()) return &jt->second;
+            }
+            return c.has_default ? &c.fallback : nullptr;
+        };
+        std::vector<cph_numcol*> nums;
+        struct ReleaseNums { std::vector<cph_numcol*>* v; ~ReleaseNums() { for (cph_numcol* p : *v) cph_numcol_release(p); } } reln{&nums};
+        std::vector<cph_chain_agg_spec> specs(aggs.size());
+        for (size_t a = 0; a < aggs.size() && n; a++) {
+            const Expr e = aggs[a].expr ? *aggs[a].expr : Expr::column(Col(aggs[a].column), aggs[a].kind == CPH_NUM_FLOAT64);
+            std::vector<std::vector<const std::string*>> vals(e.cols.size());
+            for (size_t c = 0; c < e.cols.size(); c++) {
+                vals[c].resize(n);
+                for (size_t m = 0; m < n; m++)
+                    if (!(vals[c][m] = value_of(e.cols[c], m))) return {JoinTotalsResult(), Error("missing column " + quote(e.cols[c].name))};
+            }
+            cph_numcol* nc = nullptr;
+            int32_t op = -1;
+            if (detail::evalStaged(ctx, e, vals, n, &nc, &op) != CPH_OK) throw std::runtime_error(std::string("csvplus: ") + cph_last_error(ctx));
+            nums.push_back(nc);
+            if (nc->nerrors) {
+                const size_t row = (size_t)nc->first_error_row;
+                return {JoinTotalsResult(), Error(e.errorText(nc->first_error_kind, op, [&](size_t c) { return *vals[c][row]; }))};
+            }
+            specs[a] = cph_chain_agg_spec{aggs[a].op, aggs[a].kind, nc->values, nullptr, CPH_MEM_HOST, 0};
+        }
+        if (!n) return {out, Error()};
+        cph_chain_aggregated* res = nullptr;
+        if (cph_chain_aggregate(ctx, ch, (int32_t)step, index.device().h, specs.data(), (int32_t)specs.size(), CPH_MEM_HOST, &res) != CPH_OK)
+            throw std::runtime_error(std::string("csvplus: ") + cph_last_error(ctx));
+        struct Release { cph_chain_aggregated* r; ~Release() { cph_chain_aggregated_release(r); } } rel{res};
+        if (res->ngroups != ng) throw std::runtime_error("csvplus: cph_chain_aggregate returned another number of groups than the index has rows");
+        out.counts.assign(res->count, res->count + ng);
+        for (size_t a = 0; a < aggs.size(); a++) {
+            if (aggs[a].kind == CPH_NUM_INT64) {
+                const int64_t* v = static_cast<const int64_t*>(res->values[a]);
+                out.ints[a].assign(v, v + ng);
+            } else {
+                const double* v = static_cast<const double*>(res->values[a]);
+                out.floats[a].assign(v, v + ng);
+            }
+        }
+        return {out, Error()};
+    }
+
     // cph_filter_rows calls made so far (tests: one per batch)
     static uint64_t filter_calls() { return filter_calls_counter(); }
 
@@ -1603,33 +1712,8 @@ private:
                 // errors as the nested closures: a later step sees the rows in emission order)
                 if (!fusable) return runSteps(ctx, *spec, 0, batch, fn);
                 // ---- fused: one device call ----
-                std::vector<std::unique_ptr<detail::StagedColumns>> staged;
-                std::vector<std::vector<cph_strcol>> side(S);
-                std::vector<cph_chain_step> steps(S);
-                for (size_t k = 0; k < S; k++) {
-                    const auto& cols = spec->steps[k].columns;
-                    steps[k] = cph_chain_step{};
-                    steps[k].index = spec->steps[k].index->device().h;
-                    steps[k].ncols = (int32_t)cols.size();
-                    if (origin[k] == 0) {
-                        std::vector<std::vector<const std::string*>> vals(cols.size());
-                        for (auto& v : vals) v.resize(batch->size());
-                        for (size_t i = 0; i < batch->size(); i++)
-                            for (size_t c = 0; c < cols.size(); c++) vals[c][i] = &(*batch)[i].at(cols[c]);
-                        staged.emplace_back(new detail::StagedColumns(ctx, cols.size()));
-                        staged.back()->stage(vals, batch->size());
-                        steps[k].cols = staged.back()->cols();
-                    } else {   // the index's own rows, in sorted order (impl_rows), staged once per index
-                        const Index& from = *spec->steps[(size_t)origin[k] - 1].index;
-                        (void)from.device();   // positions must refer to impl_rows as they are now
-                        for (const auto& c : cols) side[k].push_back(*from.side_column(ctx, c));
-                        steps[k].cols = side[k].data();
-                        steps[k].source = -origin[k];
-                    }
-                }
                 cph_chain* ch = nullptr;
-                if (cph_join_chain_ex(ctx, steps.data(), (int32_t)S, 0, CPH_MEM_HOST, CPH_CHAIN_POSITIONS, &ch) != CPH_OK)
-                    return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+                if (Error je = fusedJoin(ctx, *spec, origin, *batch, &ch)) return je;
                 fused_calls()++;
                 Error err;
                 for (uint64_t m = 0; m < ch->nrows && !err; m++) {
@@ -1646,6 +1730,39 @@ private:
                 return err;
             });
         });
+    }
+
+    // The fused device call of a chain over one batch of stream rows (origin[k] as columnOrigin gives it, none negative): the
+    // row-id tuples in host memory, build_row[k][m] = the subscript into steps[k].index->impl_rows.  The caller releases *ch.
+    static Error fusedJoin(cph_ctx* ctx, const ChainSpec& spec, const std::vector<int>& origin, const std::vector<Row>& batch, cph_chain** ch) {
+        const size_t S = spec.steps.size();
+        std::vector<std::unique_ptr<detail::StagedColumns>> staged;
+        std::vector<std::vector<cph_strcol>> side(S);
+        std::vector<cph_chain_step> steps(S);
+        for (size_t k = 0; k < S; k++) {
+            const auto& cols = spec.steps[k].columns;
+            steps[k] = cph_chain_step{};
+            steps[k].index = spec.steps[k].index->device().h;
+            steps[k].ncols = (int32_t)cols.size();
+            if (origin[k] == 0) {
+                std::vector<std::vector<const std::string*>> vals(cols.size());
+                for (auto& v : vals) v.resize(batch.size());
+                for (size_t i = 0; i < batch.size(); i++)
+                    for (size_t c = 0; c < cols.size(); c++) vals[c][i] = &batch[i].at(cols[c]);
+                staged.emplace_back(new detail::StagedColumns(ctx, cols.size()));
+                staged.back()->stage(vals, batch.size());
+                steps[k].cols = staged.back()->cols();
+            } else {   // the index's own rows, in sorted order (impl_rows), staged once per index
+                const Index& from = *spec.steps[(size_t)origin[k] - 1].index;
+                (void)from.device();   // positions must refer to impl_rows as they are now
+                for (const auto& c : cols) side[k].push_back(*from.side_column(ctx, c));
+                steps[k].cols = side[k].data();
+                steps[k].source = -origin[k];
+            }
+        }
+        if (cph_join_chain_ex(ctx, steps.data(), (int32_t)S, 0, CPH_MEM_HOST, CPH_CHAIN_POSITIONS, ch) != CPH_OK)
+            return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+        return Error();
     }
 
     // Where the value of `col` in the row that step k's Join sees comes from, for a whole batch: 0 = every stream row carries

@@ -364,3 +364,95 @@ def totals_to_csv(ctx: N.Context, table: Table, by, specs, names=None, out_mem: 
         if t is not None:
             t.release()
         index.close()
+
+
+def join_totals_to_csv(ctx: N.Context, stream_table: Table, build_table: Table, on, specs, names=None, out_mem: int = N.CPH_MEM_HOST,
+                       matched_only: bool = False, prec: int = 2):
+    """stream.Join(UniqueIndexOn(build, key)) and then Count and the specs per BUILD ROW over the joined rows, written as CSV —
+    the reference's TestSimpleUniqueJoin / TestTransformedSource loops (`custAmounts[cid] += amount`, csvplus_test.go:368-452,
+    :754-806) ending in ToCsv, every step in HBM: cph_index_build (unique), cph_join_chain_ex with positions,
+    cph_chain_aggregate, then the build table's columns read through cph_index_perm inside the writer, the count and the int64
+    results as computed columns (mapping.Int), the float64 results through mapping.Float with `prec` digits.
+    on: the key column's name in both tables, or (build key, stream key).  specs: aggregate.Sum / Min / Max whose source is an
+    expression of csvplus_amd.expr over the JOINED row (a name is looked up in the stream table first, then in the build
+    table: mergeRows lets the stream's value win) or one value per joined row (see aggregate.join_totals).  names: the header
+    of the count column and of every spec's column (default "count", "sum0", "min1", ...); the build columns keep theirs.
+    One output row per build row in key order; matched_only=True drops the build rows no stream row matched (count 0): what
+    the reference's inner Join would show.  Returns bytes, or a DeviceBytes handle for out_mem DEVICE."""
+    from . import aggregate as A
+    from . import expr as E
+    from . import mapping as M
+    from . import predicates as P
+    from .materialize import csv_write, filter_rows, map_column, permute_col, take_rows
+
+    bkey, skey = (on, on) if isinstance(on, str) else (str(on[0]), str(on[1]))
+    specs = list(specs)
+    for sp in specs:
+        if not isinstance(sp, A.Spec):
+            raise TypeError(f"not an aggregate: {sp!r}")
+    if names is None:
+        names = ["count"] + [f"{sp.name}{i}" for i, sp in enumerate(specs)]
+    if len(names) != 1 + len(specs):
+        raise ValueError(f"join_totals_to_csv: {1 + len(specs)} computed columns but {len(names)} names")
+    if bkey not in build_table.cols:
+        raise M.MissingColumn(bkey)
+    if skey not in stream_table.cols:
+        raise M.MissingColumn(skey)
+    index = N.DeviceIndex(ctx, [build_table[bkey]], unique=True)
+    bufs, t, ch, kept = [], None, None, None
+    try:
+        if index.status == N.CPH_ERR_DUPLICATE:
+            raise ValueError(f"duplicate value while creating unique index on {bkey!r} (sorted position {index.first_dup})")
+        ch = N.join_chain(ctx, [(index, [stream_table[skey]])], out_mem=N.CPH_MEM_DEVICE, positions=True)
+        columns = {}
+        for sp in specs:
+            if not isinstance(sp.source, E.Expr):
+                continue
+            for name in E.columns(sp.source):
+                if name in columns:
+                    continue
+                if name in stream_table.cols:
+                    columns[name] = stream_table[name]
+                elif name in build_table.cols:   # positions: the build column in index order
+                    cb = permute_col(ctx, index, build_table[name])
+                    bufs.append(cb)
+                    columns[name] = (cb.as_device_strcol(), 0)
+        t = A.join_totals(ch, 0, index, specs, out_mem=N.CPH_MEM_DEVICE, columns=columns)
+        ng = t.ngroups
+        computed = []
+        for sp, (ptr, _) in zip([None] + specs, [t.count] + t.values):   # count[g] < 2^32: the uint64 reads as the same int64
+            if sp is not None and sp.kind == N.CPH_NUM_FLOAT64:
+                part = M.Float.on_device(ptr, ng, prec)
+            else:
+                part = M.Int.on_device(ptr, ng)
+            cb = map_column(ctx, {}, M.Format(part), nrows=ng, out_mem=N.CPH_MEM_DEVICE)
+            bufs.append(cb)
+            computed.append(cb.as_device_strcol())
+        bnames = list(build_table.cols)
+        cols = [build_table[b] for b in bnames] + computed
+        header = bnames + [str(nm) for nm in names]
+        perm_ids = (index.perm_device_ptr(), 32, ng)
+        if not matched_only:
+            return csv_write(ctx, cols, header, out_mem=out_mem, row_ids=[perm_ids] * len(bnames) + [None] * len(computed), nrows=ng)
+        kept = filter_rows(ctx, {"count": computed[0]}, P.IntCmp("count", ">", 0), nrows=ng, out_mem=N.CPH_MEM_DEVICE)
+        nk = len(kept)
+        if kept.is_range and nk:   # every row kept: as an array, like any other answer
+            rng = filter_rows(ctx, {"count": computed[0]}, P.All(), nrows=nk, first_row=kept.first, out_mem=N.CPH_MEM_DEVICE)
+            kept.release()
+            kept = rng
+        if nk == 0:
+            return csv_write(ctx, cols, header, out_mem=out_mem, row_ids=[perm_ids] * len(bnames) + [None] * len(computed), nrows=0)
+        rows = take_rows(ctx, perm_ids, kept, out_mem=N.CPH_MEM_DEVICE)
+        bufs.append(rows)
+        return csv_write(ctx, cols, header, out_mem=out_mem,
+                         row_ids=[rows.as_row_ids()] * len(bnames) + [kept.as_row_ids()] * len(computed), nrows=nk)
+    finally:
+        for cb in bufs:
+            cb.release()
+        if kept is not None:
+            kept.release()
+        if t is not None:
+            t.release()
+        if ch is not None:
+            ch.release()
+        index.close()

@@ -1154,6 +1154,68 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* index, const 
                                     cph_aggregated** out);
 CPH_API void    cph_aggregated_release(cph_aggregated* a);
 
+/*
+ * Totals over a Join: one Count and up to CPH_AGG_MAX_SPECS Sum / Min / Max values per BUILD ROW of one step of a chain, on the
+ * device — the reduction the reference's TestSimpleUniqueJoin (`qtyMap[id] += qty`, csvplus_test.go:368-452) and
+ * TestTransformedSource (`custAmounts[cid] += amount`, csvplus_test.go:754-806) accumulate in a Go map over the JOINED stream.
+ * The Join has already found the group: chain->build_row[step][m] is a dense integer below cph_index_nrows(index) for every
+ * joined row m (the sorted position under CPH_CHAIN_POSITIONS, the original row id otherwise), so grouping by it needs no key
+ * strings, no codec and no second index.
+ *
+ * A GROUP is a BUILD ROW, not a key: group g collects the joined rows with build_row[step][m] == g, ngroups ==
+ * cph_index_nrows(index), and a build row no stream row matched is a group with count 0 and values 0 / +0.0.  Over an index with
+ * duplicate keys every row of a run of equal keys is its own group (a stream row that matches the key joins each of them); for a
+ * total per KEY the caller adds the groups of a run (cph_index_dup_groups gives the runs; with CPH_CHAIN_POSITIONS they are
+ * adjacent), or joins against the unique index.
+ *
+ * spec.numbers holds one int64_t / double per JOINED row m (chain->nrows of them, in numbers_mem) — what cph_num_eval over the
+ * joined rows returns; spec.status, when not NULL, its CPH_NUM_* byte per joined row in the same memory (cph_numcol.status).
+ * The semantics are cph_index_aggregate's: an int Sum wraps as Go's `+=` does; float Min / Max are math.Min / math.Max (-0 below
+ * +0, a NaN anywhere in the group gives the bits of Go's math.NaN(), also beside an infinity); a float Sum is IEEE addition in a
+ * FIXED association order — the same chain and values give bit-identical sums on every call, for every out_mem and numbers_mem
+ * (no floating-point atomics, nothing that depends on scheduling; the rows of a group are added in an order that is a function
+ * of their row numbers alone, starting from -0.0).
+ *
+ * A value whose status is not 0 is DATA, not a failure: the call returns CPH_OK with nerrors > 0 (such values over all specs),
+ * ngroups = 0 and every array NULL; first_error_row is the lowest such joined row m, first_error_spec the lowest spec that fails
+ * there and first_error_kind its status byte.
+ *
+ * Tables of up to CPH_CHAIN_AGG_LDS_GROUPS groups are accumulated per workgroup in LDS and flushed once; larger ones with
+ * device-scope integer atomics on the table itself, or — when a float Sum has the joined rows sorted by group anyway, or there
+ * are 2^20 of them or more — over the sorted runs like the float Sum.  The results are the same either way.
+ *
+ * nspecs == 0 is legal (counts only), so are chain->nrows == 0 (every count 0) and an index of 1 row.  The chain may lie in host
+ * or device memory, come from the fused pass or the general chain, with stream_row NULL or set (it is not read).
+ * Limit: chain->nrows < 2^32.
+ * CPH_ERR_INVALID (with a message): NULL ctx / chain / index / out, step outside 0..nsteps-1, chain->nrows >= 2^32, nspecs
+ * outside 0..CPH_AGG_MAX_SPECS, specs NULL with nspecs > 0, an unknown op / kind / numbers_mem / out_mem, NULL numbers, a chain
+ * without CPH_CHAIN_POSITIONS over an index that covers only part of its table (cph_index_select / cph_index_resolve: its row
+ * ids are not dense), and an index that is not the chain step's.  A cph_chain records nothing about its indexes, so the last
+ * check is by value: a build_row[step][m] that is not below cph_index_nrows(index) — an index with FEWER rows than the step's,
+ * wherever the Join reached the rows it lacks.  An index with more rows cannot be told apart and gives groups of count 0.
+ */
+#define CPH_CHAIN_AGG_LDS_GROUPS 4096
+typedef struct {
+    int32_t        op, kind;         /* CPH_AGG_SUM/MIN/MAX, CPH_NUM_INT64/FLOAT64 */
+    const void*    numbers;          /* int64_t[chain->nrows] / double[chain->nrows]: one value per JOINED row m */
+    const uint8_t* status;           /* optional CPH_NUM_* per joined row (cph_numcol.status); NULL = all valid */
+    int32_t        numbers_mem, reserved_;   /* CPH_MEM_HOST / CPH_MEM_DEVICE; `status` lies in the same mem */
+} cph_chain_agg_spec;
+typedef struct {
+    uint64_t        ngroups;         /* == cph_index_nrows(index): one group per BUILD ROW, dense, empty groups included */
+    const uint64_t* count;           /* [ngroups] joined rows whose build_row[step] == g; 0 = no stream row matched it */
+    const void*     values[CPH_AGG_MAX_SPECS];  /* int64_t[ngroups] / double[ngroups]; 0 / +0.0 where count[g] == 0 */
+    int32_t         nspecs, mem;
+    int32_t         positions;       /* copied from the chain: g is a sorted position (1) or an original row id (0) */
+    int32_t         reserved_;
+    uint64_t        nerrors, first_error_row;   /* status != 0 values; lowest such joined row m, UINT64_MAX if none */
+    int32_t         first_error_kind, first_error_spec;
+} cph_chain_aggregated;
+CPH_API int32_t cph_chain_aggregate(cph_ctx* ctx, const cph_chain* chain, int32_t step, const cph_index* index,
+                                    const cph_chain_agg_spec* specs, int32_t nspecs, int32_t out_mem,
+                                    cph_chain_aggregated** out);
+CPH_API void    cph_chain_aggregated_release(cph_chain_aggregated* a);
+
 /* Index.WriteTo / LoadIndex (csvplus.go:655-705) for the device index: a flat
  * little-endian file with the key codec, sorted codes and perm.  NOT a gob
  * stream and without row payload: the row table stays with the caller (the
