@@ -206,6 +206,13 @@ class cph_map_piece(C.Structure):
                 ("floats", C.c_void_p), ("prec", C.c_int32), ("reserved_", C.c_int32)]
 
 
+CPH_MAP_MAX_CASES, CPH_MAP_SWITCH_MAX_PIECES = 8, 32
+
+
+class cph_map_case(C.Structure):
+    _fields_ = [("prog", C.POINTER(cph_pred_op)), ("nops", C.c_int32), ("pieces", C.POINTER(cph_map_piece)), ("npieces", C.c_int32)]
+
+
 class cph_groups(C.Structure):
     _fields_ = [("ngroups", C.c_uint64), ("lower", C.c_void_p), ("upper", C.c_void_p)]
 
@@ -372,6 +379,9 @@ PROTOTYPES = [
     ("cph_map_format", C.c_int32,
      [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_int32, C.c_uint64, C.POINTER(cph_map_piece), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_colbuf))]),
+    ("cph_map_switch", C.c_int32,
+     [_P, C.POINTER(cph_strcol), C.POINTER(cph_rowsel), C.c_int32, C.c_uint64, C.POINTER(cph_map_case), C.c_int32,
+      C.POINTER(cph_map_piece), C.c_int32, C.c_int32, C.POINTER(C.POINTER(cph_colbuf)), _P]),
     ("cph_csv_parse", C.c_int32,
      [_P, _P, C.c_uint64, C.c_int32, C.POINTER(cph_csv_options), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_csv_table))]),

@@ -956,6 +956,24 @@ struct NumColStats {
 Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t first_row, uint64_t n, int32_t kind, DevBuf* values,
                     DevBuf* status, NumColStats* st);
 
+// filter.hip: a cph_pred_op program evaluated into one bit per row — what cph_filter_rows (WHERE) and cph_map_switch share.
+struct PredFloatCol {   // a column converted for the float terms of a call: one conversion, whichever program asks first
+    int col;
+    DevBuf values, status;
+};
+struct PredBitmap {
+    DevBuf bitmap;   // word w bit b = the program holds for row 64 w + b of the call (rows >= n: 0); whole tiles of 32 words
+    DevBuf counts;   // the set bits of every tile of 2048 rows, and one more entry for a scan's total
+    DevBuf lits;     // the program's literal block, which the evaluation reads
+    uint64_t ntiles = 0;
+};
+// every rule of cph_filter_rows' comment about the program that does not need the columns
+Status check_pred_program(const cph_pred_op* prog, int32_t nops, int32_t ncols);
+// Terms, literal block and float-column conversion (into *fcols, reused from it), then k_pred_eval<true, NUM> over rows
+// [first_row, first_row + n) of the staged row sources; n > 0 and the program has passed check_pred_program.
+Status pred_eval_bitmap(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, const cph_pred_op* prog, int32_t nops, uint64_t first_row,
+                        uint64_t n, std::vector<PredFloatCol>* fcols, PredBitmap* out);
+
 }  // namespace cph
 
 // the library-owned result behind cph_numcol (numparse.hip: cph_col_to_number; expr_eval.hip: cph_num_eval)

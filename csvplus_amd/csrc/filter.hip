@@ -25,6 +25,8 @@
 //            per column and call, deferred rows finished on the host and patched in) and k_pred_eval compares the
 //            resulting doubles — so a WHERE or WHILE answer never depends on where a value was converted.
 // A program without numeric terms launches the NUM = false instantiations: the kernels it always launched.
+// The way from a cph_pred_op program to the bitmap (terms, literal block, float columns, the k_pred_eval<true, NUM> launch) is
+// pred_eval_bitmap (cph_internal.hpp): the WHERE mode calls it, and so does cph_map_switch (map_switch.hip), once per case.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -331,14 +333,130 @@ uint32_t rel_outcomes(int32_t rel) {
     static const uint32_t m[6] = {kCmpLess, kCmpLess | kCmpEqual, kCmpEqual, kCmpLess | kCmpGreater | kCmpUnordered, kCmpEqual | kCmpGreater, kCmpGreater};
     return m[rel];
 }
-struct FloatCol {   // a column converted for this call's float terms
-    int col;
-    DevBuf values, status;
-};
-
 unsigned filter_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
 
+struct BuiltProg {   // a program as k_pred_eval takes it
+    PredProg pp{};
+    DevBuf litbuf;          // the literals beyond 8 bytes; the kernels read it
+    double col_bytes = 0;   // byte model: what the evaluation reads of the columns
+    bool numeric = false;   // the NUM instantiations
+};
+
+// fcols: the float columns converted so far in this call (reused, appended to)
+Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, const cph_pred_op* prog, int32_t nops, uint64_t first_row, uint64_t n,
+                       std::vector<PredFloatCol>* fcols, BuiltProg* bp) {
+    PredProg& pp = bp->pp;
+    // the program: LIKE terms over real columns get a bit each, the others are decided here
+    std::vector<uint64_t> lits;
+    uint32_t seen_cols = 0;
+    for (int q = 0; q < nops; q++) {
+        pp.op[q] = (uint8_t)prog[q].op;
+        pp.arg[q] = (uint8_t)prog[q].arg;
+        if (is_int_cmp(prog[q].op) || is_flt_cmp(prog[q].op)) {   // a term bit like a LIKE: the kernel's program sees a LIKE
+            const int c = prog[q].arg;
+            pp.op[q] = (uint8_t)CPH_PRED_LIKE;
+            if (c < 0) {
+                pp.arg[q] = kTermNever;
+                continue;
+            }
+            bp->numeric = true;
+            const bool flt = is_flt_cmp(prog[q].op);
+            PredTerm& t = pp.term[pp.nterms];
+            pp.arg[q] = (uint8_t)pp.nterms++;
+            t.col = c;
+            memcpy(&t.lit8, prog[q].value.data, 8);
+            t.kind = (flt ? kTermF64 : kTermInt) | (rel_outcomes(prog[q].op - (flt ? CPH_PRED_FLT_LT : CPH_PRED_INT_LT)) << 8);
+            if (flt) {
+                size_t f = 0;
+                while (f < fcols->size() && (*fcols)[f].col != c) f++;
+                if (f == fcols->size()) {
+                    fcols->emplace_back();
+                    (*fcols)[f].col = c;
+                    NumColStats st;
+                    CPH_TRY(convert_rows(ctx, arg.c[c], ids.ids[c], first_row, n, CPH_NUM_FLOAT64, &(*fcols)[f].values, &(*fcols)[f].status, &st));
+                    bp->col_bytes += 9.0 * (double)n;   // the converted column read back (its conversion is timed on its own)
+                }
+                t.fval = (*fcols)[f].values.as<double>();
+                t.fstat = (*fcols)[f].status.as<uint8_t>();
+            } else if (!((seen_cols >> c) & 1u)) {   // offsets (or nothing) + the value's head, once per column
+                seen_cols |= 1u << c;
+                bp->col_bytes += arg.c[c].fixed_width ? (double)arg.c[c].fixed_width * (double)n
+                                                  : ((double)(arg.c[c].offset_bits / 8) + 8.0) * (double)n;
+                if (ids.ids[c].ptr) bp->col_bytes += (double)(ids.ids[c].bits / 8) * (double)n;
+            }
+            continue;
+        }
+        if (prog[q].op != CPH_PRED_LIKE) continue;
+        const int c = prog[q].arg;
+        const uint64_t len = prog[q].value.len;
+        if (c < 0 || len > 0xFFFFFFFFull || (arg.c[c].fixed_width && arg.c[c].fixed_width != len)) {
+            pp.arg[q] = kTermNever;
+            continue;
+        }
+        PredTerm& t = pp.term[pp.nterms];
+        pp.arg[q] = (uint8_t)pp.nterms++;
+        t.col = c;
+        t.len = (uint32_t)len;
+        t.kind = arg.c[c].fixed_width == 8 && ((uintptr_t)arg.c[c].data & 7u) == 0 ? kTermFix8 : kTermBytes;
+        if (len <= 8) {
+            if (len) memcpy(&t.lit8, prog[q].value.data, (size_t)len);
+        } else {
+            t.lit_off = (uint32_t)lits.size();
+            lits.resize(lits.size() + (size_t)((len + 7) / 8), 0);
+            memcpy(lits.data() + t.lit_off, prog[q].value.data, (size_t)len);
+        }
+        if (!((seen_cols >> c) & 1u)) {   // byte model: a column's offsets and bytes count once
+            seen_cols |= 1u << c;
+            bp->col_bytes += arg.c[c].fixed_width ? (double)arg.c[c].fixed_width * (double)n
+                                              : ((double)(arg.c[c].offset_bits / 8) + (double)len) * (double)n;
+            if (ids.ids[c].ptr) bp->col_bytes += (double)(ids.ids[c].bits / 8) * (double)n;
+        }
+    }
+    pp.nops = nops;
+    if (!lits.empty()) {
+        if (lits.size() > 0xFFFFFFFFull / 8) return {CPH_ERR_INVALID, "cph_filter_rows: literals beyond 4 GiB"};
+        const size_t lb = lits.size() * sizeof(uint64_t);
+        CPH_TRY(bp->litbuf.alloc(&ctx->pool, lb));
+        void* slot = nullptr;
+        CPH_TRY(pinned_upload(ctx, lb, &slot));
+        memcpy(slot, lits.data(), lb);
+        CPH_HIP_TRY(hipMemcpyAsync(bp->litbuf.get(), slot, lb, hipMemcpyHostToDevice, ctx->stream));
+        pp.lits = bp->litbuf.as<uint64_t>();
+        pp.lit_words = (uint32_t)lits.size();
+        pp.lits_in_lds = lb <= (size_t)kLitLds;
+    }
+    return {};
+}
+
 }  // namespace
+
+namespace cph {
+
+Status check_pred_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) { return check_program(prog, nops, ncols); }
+
+Status pred_eval_bitmap(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, const cph_pred_op* prog, int32_t nops, uint64_t first_row,
+                        uint64_t n, std::vector<PredFloatCol>* fcols, PredBitmap* out) {
+    BuiltProg bp;
+    CPH_TRY(build_pred_prog(ctx, arg, ids, prog, nops, first_row, n, fcols, &bp));
+    const uint64_t ntiles = (n + kFiltTile - 1) / kFiltTile;
+    out->ntiles = ntiles;
+    CPH_TRY(out->bitmap.alloc(&ctx->pool, ntiles * kFiltWords * sizeof(uint64_t)));
+    CPH_TRY(out->counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
+    {
+        ProfScope ps(ctx, "k_pred_eval", bp.col_bytes + (double)n / 8.0 + 4.0 * (double)ntiles);
+        if (bp.numeric)
+            hipLaunchKernelGGL((k_pred_eval<true, true>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, bp.pp, first_row, n,
+                               out->bitmap.as<uint64_t>(), out->counts.as<uint32_t>(), (unsigned long long*)nullptr);
+        else
+            hipLaunchKernelGGL((k_pred_eval<true, false>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, bp.pp, first_row, n,
+                               out->bitmap.as<uint64_t>(), out->counts.as<uint32_t>(), (unsigned long long*)nullptr);
+    }
+    CPH_HIP_TRY(hipGetLastError());
+    out->lits = std::move(bp.litbuf);   // the kernel reads it: it lives as long as the bitmap
+    return {};
+}
+
+}  // namespace cph
 
 extern "C" {
 
@@ -381,94 +499,13 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         ColsArg arg{};
         ColIds ids{};
         CPH_TRY(stage_row_sources(ctx, cols, sel, nullptr, ncols, first_row, n, &staged, &arg, &ids));
-        // the program: LIKE terms over real columns get a bit each, the others are decided here
-        PredProg pp{};
-        std::vector<uint64_t> lits;
-        double col_bytes = 0;
-        uint32_t seen_cols = 0;
-        bool numeric = false;
-        std::vector<FloatCol> fcols;
-        fcols.reserve((size_t)ncols);
-        for (int q = 0; q < nops; q++) {
-            pp.op[q] = (uint8_t)prog[q].op;
-            pp.arg[q] = (uint8_t)prog[q].arg;
-            if (is_int_cmp(prog[q].op) || is_flt_cmp(prog[q].op)) {   // a term bit like a LIKE: the kernel's program sees a LIKE
-                const int c = prog[q].arg;
-                pp.op[q] = (uint8_t)CPH_PRED_LIKE;
-                if (c < 0) {
-                    pp.arg[q] = kTermNever;
-                    continue;
-                }
-                numeric = true;
-                const bool flt = is_flt_cmp(prog[q].op);
-                PredTerm& t = pp.term[pp.nterms];
-                pp.arg[q] = (uint8_t)pp.nterms++;
-                t.col = c;
-                memcpy(&t.lit8, prog[q].value.data, 8);
-                t.kind = (flt ? kTermF64 : kTermInt) | (rel_outcomes(prog[q].op - (flt ? CPH_PRED_FLT_LT : CPH_PRED_INT_LT)) << 8);
-                if (flt) {
-                    size_t f = 0;
-                    while (f < fcols.size() && fcols[f].col != c) f++;
-                    if (f == fcols.size()) {
-                        fcols.emplace_back();
-                        fcols[f].col = c;
-                        NumColStats st;
-                        CPH_TRY(convert_rows(ctx, arg.c[c], ids.ids[c], first_row, n, CPH_NUM_FLOAT64, &fcols[f].values, &fcols[f].status, &st));
-                        col_bytes += 9.0 * (double)n;   // the converted column read back (its conversion is timed on its own)
-                    }
-                    t.fval = fcols[f].values.as<double>();
-                    t.fstat = fcols[f].status.as<uint8_t>();
-                } else if (!((seen_cols >> c) & 1u)) {   // offsets (or nothing) + the value's head, once per column
-                    seen_cols |= 1u << c;
-                    col_bytes += arg.c[c].fixed_width ? (double)arg.c[c].fixed_width * (double)n
-                                                      : ((double)(arg.c[c].offset_bits / 8) + 8.0) * (double)n;
-                    if (ids.ids[c].ptr) col_bytes += (double)(ids.ids[c].bits / 8) * (double)n;
-                }
-                continue;
-            }
-            if (prog[q].op != CPH_PRED_LIKE) continue;
-            const int c = prog[q].arg;
-            const uint64_t len = prog[q].value.len;
-            if (c < 0 || len > 0xFFFFFFFFull || (arg.c[c].fixed_width && arg.c[c].fixed_width != len)) {
-                pp.arg[q] = kTermNever;
-                continue;
-            }
-            PredTerm& t = pp.term[pp.nterms];
-            pp.arg[q] = (uint8_t)pp.nterms++;
-            t.col = c;
-            t.len = (uint32_t)len;
-            t.kind = arg.c[c].fixed_width == 8 && ((uintptr_t)arg.c[c].data & 7u) == 0 ? kTermFix8 : kTermBytes;
-            if (len <= 8) {
-                if (len) memcpy(&t.lit8, prog[q].value.data, (size_t)len);
-            } else {
-                t.lit_off = (uint32_t)lits.size();
-                lits.resize(lits.size() + (size_t)((len + 7) / 8), 0);
-                memcpy(lits.data() + t.lit_off, prog[q].value.data, (size_t)len);
-            }
-            if (!((seen_cols >> c) & 1u)) {   // byte model: a column's offsets and bytes count once
-                seen_cols |= 1u << c;
-                col_bytes += arg.c[c].fixed_width ? (double)arg.c[c].fixed_width * (double)n
-                                                  : ((double)(arg.c[c].offset_bits / 8) + (double)len) * (double)n;
-                if (ids.ids[c].ptr) col_bytes += (double)(ids.ids[c].bits / 8) * (double)n;
-            }
-        }
-        pp.nops = nops;
-        DevBuf litbuf;
-        if (!lits.empty()) {
-            if (lits.size() > 0xFFFFFFFFull / 8) return {CPH_ERR_INVALID, "cph_filter_rows: literals beyond 4 GiB"};
-            const size_t lb = lits.size() * sizeof(uint64_t);
-            CPH_TRY(litbuf.alloc(&ctx->pool, lb));
-            void* slot = nullptr;
-            CPH_TRY(pinned_upload(ctx, lb, &slot));
-            memcpy(slot, lits.data(), lb);
-            CPH_HIP_TRY(hipMemcpyAsync(litbuf.get(), slot, lb, hipMemcpyHostToDevice, ctx->stream));
-            pp.lits = litbuf.as<uint64_t>();
-            pp.lit_words = (uint32_t)lits.size();
-            pp.lits_in_lds = lb <= (size_t)kLitLds;
-        }
+        std::vector<PredFloatCol> fcols;
         const uint64_t ntiles = (n + kFiltTile - 1) / kFiltTile;
         CPH_TRY(ensure_pinned_scratch(ctx, sizeof(uint64_t)));
         if (opts->mode != CPH_FILTER_WHERE) {
+            BuiltProg bp;
+            CPH_TRY(build_pred_prog(ctx, arg, ids, prog, nops, first_row, n, &fcols, &bp));
+            const PredProg& pp = bp.pp;
             DevBuf ff;
             CPH_TRY(ff.alloc(&ctx->pool, sizeof(uint64_t)));
             void* slot = nullptr;
@@ -476,8 +513,8 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
             memcpy(slot, &n, sizeof n);
             CPH_HIP_TRY(hipMemcpyAsync(ff.get(), slot, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
             {
-                ProfScope ps(ctx, "k_pred_eval", col_bytes);
-                if (numeric)
+                ProfScope ps(ctx, "k_pred_eval", bp.col_bytes);
+                if (bp.numeric)
                     hipLaunchKernelGGL((k_pred_eval<false, true>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
                                        (uint64_t*)nullptr, (uint32_t*)nullptr, ff.as<unsigned long long>());
                 else
@@ -494,19 +531,10 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
             set_range(r, first_row + lo, hi - lo, bits, out_mem);
             return {};
         }
-        DevBuf bitmap, counts;
-        CPH_TRY(bitmap.alloc(&ctx->pool, ntiles * kFiltWords * sizeof(uint64_t)));
-        CPH_TRY(counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
-        {
-            ProfScope ps(ctx, "k_pred_eval", col_bytes + (double)n / 8.0 + 4.0 * (double)ntiles);
-            if (numeric)
-                hipLaunchKernelGGL((k_pred_eval<true, true>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
-                                   bitmap.as<uint64_t>(), counts.as<uint32_t>(), (unsigned long long*)nullptr);
-            else
-                hipLaunchKernelGGL((k_pred_eval<true, false>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
-                                   bitmap.as<uint64_t>(), counts.as<uint32_t>(), (unsigned long long*)nullptr);
-        }
-        CPH_HIP_TRY(hipGetLastError());
+        PredBitmap pb;
+        CPH_TRY(pred_eval_bitmap(ctx, arg, ids, prog, nops, first_row, n, &fcols, &pb));
+        DevBuf& bitmap = pb.bitmap;
+        DevBuf& counts = pb.counts;
         CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));
         uint32_t total = 0;
         CPH_TRY(read_device_value(ctx, counts.as<uint32_t>() + ntiles, &total));   // the call's host wait

@@ -1,0 +1,99 @@
+// map_device.hpp — the device pieces the two Map entry points share (map_format.hip: one template per column;
+// map_switch.hip: the template of the first case that holds): a template piece as the kernels see it, FormatInt's digit
+// count and characters, the field of a loaded record, and the loop that puts a run of pieces into a byte sink.
+#pragma once
+
+#include "materialize_device.hpp"
+#include "numformat_device.hpp"
+
+namespace cph {
+
+struct MapPiece {
+    int32_t kind;          // CPH_MAP_*
+    int32_t col;           // COLUMN: the column; FLOAT64: prec
+    uint32_t off, len;     // LITERAL: its bytes in the plan's literal block
+    union {
+        const int64_t* ints;    // INT64: one value per output row, on the device
+        const double* floats;   // FLOAT64: likewise
+    };
+};
+
+__device__ __forceinline__ uint64_t int_magnitude(int64_t v) { return v < 0 ? 0ull - (uint64_t)v : (uint64_t)v; }
+
+// characters of strconv.FormatInt(v, 10): the digits of the unsigned magnitude (compares against 10^1 .. 10^19) + the sign
+__device__ __forceinline__ uint32_t int_chars(int64_t v) {
+    const uint64_t m = int_magnitude(v);
+    uint32_t d = 1;
+    uint64_t p = 10;
+#pragma unroll
+    for (int k = 1; k <= 19; k++) {
+        d += m >= p ? 1u : 0u;
+        p *= 10;   // 10^19 < 2^64; the product behind it is never compared
+    }
+    return d + (v < 0 ? 1u : 0u);
+}
+
+// the characters assembled in registers — at most 20, three 8-byte chunks — and put 8 at a time
+template <class Sink>
+__device__ __forceinline__ void put_int(Sink& s, int64_t v) {
+    uint64_t m = int_magnitude(v);
+    const uint32_t len = int_chars(v);
+    uint64_t c0 = v < 0 ? (uint64_t)'-' : 0, c1 = 0, c2 = 0;
+    uint32_t pos = len;
+    do {
+        const uint64_t q = m / 10;
+        const uint64_t ch = (uint64_t)'0' + (m - q * 10);
+        m = q;
+        pos--;
+        const uint64_t sh = ch << (8u * (pos & 7u));
+        if (pos < 8u) c0 |= sh;
+        else if (pos < 16u) c1 |= sh;
+        else c2 |= sh;
+    } while (m);
+    s.put8(c0, len < 8u ? len : 8u);
+    if (len > 8u) s.put8(c1, len < 16u ? len - 8u : 8u);
+    if (len > 16u) s.put8(c2, len - 16u);
+}
+
+// (begin, length, first chunk) of column c's value in the loaded record; the arrays stay in registers (c is uniform in
+// map_format.hip and may differ from lane to lane in map_switch.hip: a chain of selects either way)
+template <int NC>
+__device__ __forceinline__ void pick_field(const RecordFields<NC>& f, int c, uint64_t* b, uint64_t* l, uint64_t* c0) {
+    *b = 0, *l = 0, *c0 = 0;
+#pragma unroll
+    for (int k = 0; k < NC; k++)
+        if (k == c) *b = f.b[k], *l = f.l[k], *c0 = f.c0[k];
+}
+
+// pieces [k0, k1) of `pieces` for output row i, in order, into the sink; literals lie in `lits` (k0 and k1 may differ from lane
+// to lane)
+template <int NC, bool FL, class Sink>
+__device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, const ColIds& ids, const uint8_t* lits, const MapPiece* pieces,
+                                               int k0, int k1, const RecordFields<NC>& f, uint64_t i) {
+    for (int k = k0; k < k1; k++) {
+        const MapPiece& p = pieces[k];
+        if (p.kind == CPH_MAP_LITERAL) {
+            for (uint32_t q = 0; q < p.len; q += 8)
+                s.put8(load_value_chunk(lits, p.off, p.len, (int)(q >> 3)), p.len - q < 8u ? p.len - q : 8u);
+        } else if (p.kind == CPH_MAP_INT64) {
+            put_int(s, p.ints[i]);
+        } else if (FL && p.kind == CPH_MAP_FLOAT64) {
+            fixed_put(s, fixed_split(p.floats[i], p.col), p.col);
+        } else {
+            const uint8_t* data = cols.c[p.col].data;
+            uint64_t b, l, c0;
+            if constexpr (NC > 0) {
+                pick_field(f, p.col, &b, &l, &c0);
+            } else {
+                value_span(cols.c[p.col], source_row(ids.ids[p.col], i), &b, &l);
+                c0 = l ? load_value_chunk(data, b, l, 0) : 0;
+            }
+            for (uint64_t q = 0; q < l; q += 8) {
+                const uint64_t chunk = q ? load_value_chunk(data, b, l, (int)(q >> 3)) : c0;
+                s.put8(chunk, (uint32_t)(l - q < 8 ? l - q : 8));
+            }
+        }
+    }
+}
+
+}  // namespace cph

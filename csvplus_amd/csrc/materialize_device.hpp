@@ -1,5 +1,5 @@
 // materialize_device.hpp — the device pieces the writers share (materialize.hip: gather and ToCsv; json_write.hip: ToJSON;
-// filter.hip: Filter; map_format.hip: Map): the row-id lookup, the byte sinks, the LDS stage, the record loader, the column-count dispatch and the
+// filter.hip: Filter; map_format.hip and map_switch.hip: Map): the row-id lookup, the byte sinks, the LDS stage, the record loader, the column-count dispatch and the
 // length scan.  Their host side is shared too and lives in cph_internal.hpp / capi.hip: RowIds / ColIds, check_row_sources and
 // stage_row_sources (columns + row ids onto the device), deliver / finish_call / release_result (the result handed out).
 #pragma once

@@ -16,7 +16,10 @@
 //   Like / All / Any / Not           :1243-1293  csvplus::Like / All / Any / Not (plain data, also callable on a Row)
 //   DataSource.Map                     :290-296  DataSource::Map over csvplus::Set(name, literal or Format{...}): a row
 //                                                template instead of a closure, rendered on the GPU (cph_map_format);
-//                                                Fixed(expr, prec) / Itoa(expr): an Expr's value (cph_num_eval)
+//                                                Fixed(expr, prec) / Itoa(expr): an Expr's value (cph_num_eval);
+//                                                Set(name, Switch({Case(pred, Format)...}, otherwise)) / When(pred, then,
+//                                                otherwise): the `if` inside the closure — the template of the first case
+//                                                whose Pred holds (cph_map_switch)
 //   DataSource.Validate                :300-310  DataSource::Validate(pred, message): a declarative Pred instead of a closure
 //   DataSource.Transform               :262-272  no entry of its own: it is the composition of Map, Filter and Validate
 //   Row.ValueAsInt / ValueAsFloat64  :165-205    csvplus::ValueAsInt / ValueAsFloat64 (one row, on the host);
@@ -612,15 +615,41 @@ struct Format {
         return true;
     }
 };
+// A value that depends on a condition — `if row["name"] == "Amelia" { row["name"] = "Julia" }` (csvplus_test.go:283-288) — is a
+// Switch: the template of the FIRST case whose predicate holds for the row, else `otherwise` (cph_map_switch).  A Switch stands
+// where a whole template stands; it is no part of a Format and does not nest.  Every Col without default of EVERY alternative
+// must be present in a row, whichever alternative the row selects.
+struct Case {
+    Pred when;
+    Format then;
+    Case(Pred p, Format f) : when(std::move(p)), then(std::move(f)) {}
+};
+struct Switch {
+    std::vector<Case> cases;
+    Format otherwise;
+    Switch(std::vector<Case> c, Format o) : cases(std::move(c)), otherwise(std::move(o)) {
+        if (cases.empty()) throw Panic("no cases in Switch()");
+        if (cases.size() > (size_t)CPH_MAP_MAX_CASES) throw Panic("more than 8 cases in Switch()");
+    }
+    // the alternative a row selects: the index of the first case that holds, or cases.size() for `otherwise`
+    size_t which(const Row& row) const {
+        size_t a = 0;
+        while (a < cases.size() && !cases[a].when(row)) a++;
+        return a;
+    }
+};
+inline Switch When(Pred when, Format then, Format otherwise) { return Switch({Case(std::move(when), std::move(then))}, std::move(otherwise)); }
 struct Assign {
     std::string name;
-    Format value;
+    Format value;              // with cases: the value where none of them holds
+    std::vector<Case> cases;   // Set(name, Switch)
 };
 inline Assign Set(std::string name, std::string literal) { return Assign{std::move(name), Format({Part(std::move(literal))})}; }
 inline Assign Set(std::string name, const char* literal) { return Set(std::move(name), std::string(literal)); }
 inline Assign Set(std::string name, Format value) { return Assign{std::move(name), std::move(value)}; }
 inline Assign Set(std::string name, Fixed value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
 inline Assign Set(std::string name, Itoa value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
+inline Assign Set(std::string name, Switch value) { return Assign{std::move(name), std::move(value.otherwise), std::move(value.cases)}; }
 
 using RowFunc = std::function<Error(Row)>;
 
@@ -1046,7 +1075,22 @@ public:
         std::vector<std::string> required, written;
         for (const Assign& a : assigns) {
             std::set<std::string> cols;
-            for (const Part& p : a.value.parts) {
+            std::vector<const Part*> parts;   // of every alternative
+            for (const Part& p : a.value.parts) parts.push_back(&p);
+            size_t pred_cols = 0;
+            if (!a.cases.empty()) {
+                detail::PredProgram prog;
+                for (const Case& c : a.cases) {
+                    prog.emit(c.when);
+                    if (c.then.parts.size() > (size_t)CPH_MAP_MAX_PIECES) throw Panic("template of more than 16 parts in Map()");
+                    for (const Part& p : c.then.parts) parts.push_back(&p);
+                }
+                pred_cols = prog.columns.size();
+                if (a.cases.size() > (size_t)CPH_MAP_MAX_CASES) throw Panic("more than 8 cases in Map()");
+                if (parts.size() > (size_t)CPH_MAP_SWITCH_MAX_PIECES) throw Panic("Switch of more than 32 parts in Map()");
+            }
+            for (const Part* pp : parts) {
+                const Part& p = *pp;
                 if (p.expr) {
                     for (const Col& c : p.expr->cols) {
                         const bool known = std::find(written.begin(), written.end(), c.name) != written.end() ||
@@ -1062,7 +1106,7 @@ public:
                 if (!p.col.has_default && !known) required.push_back(p.col.name);
             }
             if (a.value.parts.size() > (size_t)CPH_MAP_MAX_PIECES) throw Panic("template of more than 16 parts in Map()");
-            if (cols.size() > (size_t)CPH_MAX_KEY_COLS) throw Panic("template over more than 16 columns in Map()");
+            if (pred_cols + cols.size() > (size_t)CPH_MAX_KEY_COLS) throw Panic("template over more than 16 columns in Map()");
             written.push_back(a.name);
         }
         Fn src = fn_;
@@ -1097,7 +1141,7 @@ public:
     DataSource Validate(const Pred& pred, std::string message) const {
         return filterSource(fn_, detail::compilePred(pred), CPH_FILTER_TAKE_WHILE, std::make_shared<const std::string>(std::move(message)));
     }
-    // cph_map_format calls made so far (tests: one per batch and assignment)
+    // cph_map_format / cph_map_switch calls made so far (tests: one per batch and assignment)
     static uint64_t map_calls() { return map_calls_counter(); }
 
     // Top (:313-325) / Drop (:329-342): counters, no data involved
@@ -1503,6 +1547,7 @@ private:
         size_t n = batch->size();
         *good = 0;
         if (n == 0) return Error();
+        if (!a.cases.empty()) return switchBatch(ctx, a, batch, good);
         std::vector<std::string> columns;
         std::vector<const std::string*> fallback;
         std::vector<cph_map_piece> pieces;
@@ -1610,6 +1655,134 @@ private:
         for (size_t i = 0; i < n; i++) (*batch)[i][a.name].assign(data + offs[i], (size_t)(offs[i + 1] - offs[i]));
         cph_colbuf_release(cb);
         *good = pending ? n : batch->size();
+        return pending;
+    }
+    // The same for Set(name, Switch): ONE cph_map_switch call.  The predicates' columns are staged as a Filter stages them (a row
+    // that lacks one gets a value that equals no literal and converts to no number), the templates' columns behind them with
+    // their defaults.  Fixed / Itoa parts are evaluated over all rows; a row where one fails counts only if the row selects
+    // the alternative that holds the part (`which`): the rows in front of the lowest such row are mapped, then its error surfaces.
+    static Error switchBatch(cph_ctx* ctx, const Assign& a, std::vector<Row>* batch, size_t* good) {
+        const size_t n = batch->size(), ncases = a.cases.size();
+        detail::PredProgram prog;   // every case's program over one column list
+        std::vector<size_t> op_first(ncases + 1);
+        for (size_t c = 0; c < ncases; c++) {
+            op_first[c] = prog.ops.size();
+            prog.emit(a.cases[c].when);
+        }
+        op_first[ncases] = prog.ops.size();
+        const size_t npred = prog.columns.size();
+        std::vector<std::string> columns = prog.columns;
+        std::vector<const std::string*> fallback;
+        for (size_t c = 0; c < npred; c++) fallback.push_back(&prog.absent[c]);
+        struct NumPart {   // a Fixed / Itoa part's values over the batch
+            size_t alt;
+            const Part* part;
+            cph_numcol* nc;
+            std::vector<std::vector<const std::string*>> vals;
+        };
+        struct NumParts {   // they live until the switch has run
+            std::vector<NumPart> v;
+            ~NumParts() {
+                for (NumPart& p : v) cph_numcol_release(p.nc);
+            }
+        } nums;
+        std::vector<std::vector<cph_map_piece>> pieces(ncases + 1);
+        for (size_t alt = 0; alt <= ncases; alt++) {
+            for (const Part& p : (alt < ncases ? a.cases[alt].then : a.value).parts) {
+                if (p.expr || p.prec >= 0) {
+                    NumPart np{alt, &p, nullptr, {}};
+                    const size_t nc = p.expr ? p.expr->cols.size() : 1;
+                    np.vals.resize(nc);
+                    for (size_t c = 0; c < nc; c++) {
+                        const Col& col = p.expr ? p.expr->cols[c] : p.col;
+                        np.vals[c].resize(n);
+                        for (size_t i = 0; i < n; i++) {
+                            auto it = (*batch)[i].find(col.name);
+                            np.vals[c][i] = it == (*batch)[i].end() ? &col.fallback : &it->second;
+                        }
+                    }
+                    int32_t rc, op = -1;
+                    if (p.expr) {
+                        rc = detail::evalStaged(ctx, *p.expr, np.vals, n, &np.nc, &op);
+                    } else {
+                        detail::StagedColumns st(ctx, 1);
+                        st.stage(np.vals, n);
+                        rc = cph_col_to_number(ctx, st.cols(), nullptr, n, CPH_NUM_FLOAT64, CPH_MEM_HOST, &np.nc);
+                    }
+                    if (rc != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+                    if (p.expr && p.prec < 0)
+                        pieces[alt].push_back(cph_map_piece{CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0}, static_cast<const int64_t*>(np.nc->values), nullptr, 0, 0});
+                    else
+                        pieces[alt].push_back(cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr, static_cast<const double*>(np.nc->values), p.prec, 0});
+                    nums.v.push_back(std::move(np));
+                    continue;
+                }
+                if (!p.is_col) {
+                    pieces[alt].push_back(cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr});
+                    continue;
+                }
+                size_t c = (size_t)(std::find(columns.begin() + (std::ptrdiff_t)npred, columns.end(), p.col.name) - columns.begin());
+                if (c == columns.size()) {
+                    columns.push_back(p.col.name);
+                    fallback.push_back(&p.col.fallback);
+                }
+                pieces[alt].push_back(cph_map_piece{CPH_MAP_COLUMN, (int32_t)c, {nullptr, 0}, nullptr});
+            }
+        }
+        const size_t nc = columns.size();
+        std::vector<std::vector<const std::string*>> vals(nc);
+        for (size_t c = 0; c < nc; c++) {
+            vals[c].resize(n);
+            for (size_t i = 0; i < n; i++) {
+                auto it = (*batch)[i].find(columns[c]);
+                vals[c][i] = it == (*batch)[i].end() ? fallback[c] : &it->second;
+            }
+        }
+        std::vector<cph_map_case> cases(ncases);
+        for (size_t c = 0; c < ncases; c++)
+            cases[c] = cph_map_case{prog.ops.data() + op_first[c], (int32_t)(op_first[c + 1] - op_first[c]), pieces[c].data(), (int32_t)pieces[c].size()};
+        std::vector<uint8_t> which(n);
+        cph_colbuf* cb = nullptr;
+        int32_t rc;
+        {
+            detail::StagedColumns st(ctx, nc);
+            st.stage(vals, n);
+            rc = cph_map_switch(ctx, nc ? st.cols() : nullptr, nullptr, (int32_t)nc, n, cases.data(), (int32_t)ncases, pieces[ncases].data(),
+                                (int32_t)pieces[ncases].size(), CPH_MEM_HOST, &cb, which.data());
+        }
+        if (rc != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+        map_calls_counter()++;
+        size_t bad = n;   // the lowest row whose own alternative holds a part that failed there
+        const NumPart* culprit = nullptr;
+        for (const NumPart& np : nums.v) {
+            if (!np.nc->nerrors) continue;
+            const uint8_t* st = static_cast<const uint8_t*>(np.nc->status);
+            for (size_t i = (size_t)np.nc->first_error_row; i < bad; i++) {
+                if (st[i] == CPH_NUM_OK || which[i] != np.alt) continue;
+                bad = i;
+                culprit = &np;
+                break;
+            }
+        }
+        Error pending;
+        if (culprit) {
+            const Part& p = *culprit->part;
+            const int32_t kind = static_cast<const uint8_t*>(culprit->nc->status)[bad];
+            if (p.expr) {
+                int64_t iv = 0;
+                double fv = 0;
+                int op = 0;
+                (void)p.expr->eval((*batch)[bad], &iv, &fv, &op, nullptr);   // the host model names the op that fails in that row
+                pending = Error(p.expr->errorText(kind, op < 0 ? 0 : op, [&](size_t c) { return *culprit->vals[c][bad]; }));
+            } else {
+                pending = Error(conversionError(p.col.name, *culprit->vals[0][bad], CPH_NUM_FLOAT64, kind));
+            }
+        }
+        const uint64_t* offs = static_cast<const uint64_t*>(cb->col.offsets);
+        const char* data = reinterpret_cast<const char*>(cb->col.data);
+        for (size_t i = 0; i < bad; i++) (*batch)[i][a.name].assign(data + offs[i], (size_t)(offs[i + 1] - offs[i]));
+        cph_colbuf_release(cb);
+        *good = culprit ? bad : batch->size();
         return pending;
     }
     static uint64_t& map_calls_counter() {

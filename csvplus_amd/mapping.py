@@ -22,8 +22,20 @@ the new column in row i is the concatenation of the template's parts —
 
 `compile` turns a template into the piece list cph_map_format takes (include/csvplus_hip.h), `render` evaluates it on one
 row held as a dict — the host model, for callers without a GPU and as the cross-check of the device.  Nothing here
-touches the GPU.  FormatFloat's other forms (shortest round-trip digits, 'e' and 'g'), case mapping, trimming, substrings
-and conditional parts are out of scope.
+touches the GPU.  FormatFloat's other forms (shortest round-trip digits, 'e' and 'g'), case mapping, trimming and
+substrings are out of scope.
+
+A value that depends on a condition is a Switch — Go's `if / else if / else` inside the closure, as data:
+
+    Switch((pred, template), ..., otherwise=template)   the template of the FIRST case whose predicate (csvplus_amd.predicates)
+                                                        holds for the row, else `otherwise`;
+    When(pred, then, otherwise)                         = Switch((pred, then), otherwise=otherwise): the reference's
+                                                        `if row["name"] == "Amelia" { row["name"] = "Julia" }` is
+                                                        When(Like(name="Amelia"), "Julia", Col("name")).
+
+A Switch stands where a whole template stands (cph_map_switch); it is not a part of a Format and does not nest.  One
+deviation from a closure: a Col without default that names a missing column raises MissingColumn when the Switch is
+compiled, even if no row would select that alternative — in structure-of-arrays a column exists for all rows or for none.
 """
 from __future__ import annotations
 
@@ -31,10 +43,13 @@ import math
 
 import numpy as np
 
+from . import predicates as _P
 from .predicates import INT64_MAX, INT64_MIN, _bytes, _go_quote
 
 LITERAL, COLUMN, INT64, FLOAT64 = 1, 2, 3, 4   # CPH_MAP_*
 MAX_PIECES = 16                    # CPH_MAP_MAX_PIECES
+MAX_CASES = 8                      # CPH_MAP_MAX_CASES
+SWITCH_MAX_PIECES = 32             # CPH_MAP_SWITCH_MAX_PIECES: the pieces of all alternatives together
 MAX_COLUMNS = 16                   # CPH_MAX_KEY_COLS
 MAX_PREC = 22                      # a FLOAT64 piece's prec: 0..22
 FLOAT_LIMIT = 2.0 ** 128           # finite |v| at or above it is not formatted
@@ -167,17 +182,68 @@ def Const(value) -> Format:
     return Format(value)
 
 
+class Switch:
+    """Switch((pred, template), ..., otherwise=template): the template of the first case whose predicate holds for the row,
+    else `otherwise`.  pred: a predicates.Pred; templates: what Format accepts (a Format, or a bare part).  At most 8 cases."""
+
+    def __init__(self, *cases, otherwise):
+        if not cases:
+            raise ValueError("Switch: no cases")
+        self.cases = []
+        for c in cases:
+            if not isinstance(c, (tuple, list)) or len(c) != 2:
+                raise TypeError(f"Switch: a case is a (predicate, template) pair, not {c!r}")
+            pred, tmpl = c
+            if not isinstance(pred, _P.Pred):
+                raise TypeError(f"Switch: not a predicate: {pred!r} (closures cannot run on the device; use csvplus_amd.predicates)")
+            self.cases.append((pred, _template(tmpl)))
+        self.otherwise = _template(otherwise)
+
+    def alternatives(self) -> list:
+        """The templates in selection order: the cases', then `otherwise`."""
+        return [t for _, t in self.cases] + [self.otherwise]
+
+    def __repr__(self):
+        return f"Switch({', '.join(repr(c) for c in self.cases)}, otherwise={self.otherwise!r})"
+
+
+def When(pred, then, otherwise) -> Switch:
+    """`if pred(row) { then } else { otherwise }`."""
+    return Switch((pred, then), otherwise=otherwise)
+
+
 def _template(t) -> Format:
     if isinstance(t, Format):
         return t
+    if isinstance(t, Switch):
+        raise TypeError("a Switch stands where a whole template stands: it is no part of a Format and does not nest")
     if isinstance(t, (Col, Int, Float, bytes, bytearray, memoryview, str)):
         return Format(t)
     raise TypeError(f"not a template: {t!r}")
 
 
+def _pred_columns(pred) -> list:
+    if isinstance(pred, _P.Like):
+        return [name for name, _ in pred.items]
+    if isinstance(pred, _P._NumCmp):
+        return [pred.column]
+    if isinstance(pred, _P.Not):
+        return _pred_columns(pred.pred)
+    if isinstance(pred, (_P.All, _P.Any)):
+        return [name for q in pred.preds for name in _pred_columns(q)]
+    raise TypeError(f"not a predicate: {pred!r}")
+
+
 def columns(template) -> list:
-    """The names of the template's Col parts and of the columns its Int.of / Float.of expressions read, in order of first use."""
+    """The names of the template's Col parts and of the columns its Int.of / Float.of expressions read, in order of first use.
+    A Switch: the columns of its predicates and templates, case by case, then those of `otherwise`."""
     names: list[str] = []
+    if isinstance(template, Switch):
+        for pred, tmpl in template.cases + [(_P.All(), template.otherwise)]:
+            for name in _pred_columns(pred) + columns(tmpl):
+                if name not in names:
+                    names.append(name)
+        return names
     for p in _template(template).parts:
         if isinstance(p, Col):
             found = [p.name]
@@ -229,6 +295,50 @@ def compile(template, column_names):   # noqa: A001 (the name predicates.compile
     return used, pieces
 
 
+def compile_switch(switch, column_names):
+    """(names of the columns used, [(predicate ops, pieces) per case], pieces of `otherwise`): what cph_map_switch takes.  The
+    ops are predicates.compile's and the pieces `compile`'s, with every column index pointing into the ONE returned name list,
+    which the predicates and the templates share.  A predicate column that is not among `column_names` compiles to column -1
+    (false); a Col part that is not becomes its default or raises MissingColumn — whether or not a row would select its
+    alternative.  Raises ValueError beyond the ABI's limits: 8 cases, 16 pieces per alternative, 32 pieces in all, 16 columns."""
+    if not isinstance(switch, Switch):
+        raise TypeError(f"not a Switch: {switch!r}")
+    if len(switch.cases) > MAX_CASES:
+        raise ValueError(f"Switch has {len(switch.cases)} cases, more than {MAX_CASES}")
+    known = [str(c) for c in column_names]
+    shared: list[str] = []
+
+    def index_of(name):
+        if name not in shared:
+            shared.append(name)
+        return shared.index(name)
+
+    def alternative(tmpl):
+        used, pieces = compile(tmpl, known)
+        return [(kind, index_of(used[arg]), v) if kind == COLUMN else (kind, arg, v) for kind, arg, v in pieces]
+
+    cases = []
+    for pred, tmpl in switch.cases:
+        used, ops = _P.compile(pred, known)
+        ops = [(op, index_of(used[arg]), v) if v is not None and arg >= 0 else (op, arg, v) for op, arg, v in ops]
+        cases.append((ops, alternative(tmpl)))
+    otherwise = alternative(switch.otherwise)
+    total = sum(len(pc) for _, pc in cases) + len(otherwise)
+    if total > SWITCH_MAX_PIECES:
+        raise ValueError(f"Switch compiles to {total} pieces in all, more than {SWITCH_MAX_PIECES}")
+    if len(shared) > MAX_COLUMNS:
+        raise ValueError(f"Switch reads {len(shared)} columns, more than {MAX_COLUMNS}")
+    return shared, cases, otherwise
+
+
+def which_of(switch, row) -> int:
+    """The alternative a row selects: the index of the first case whose predicate holds, or the number of cases (`otherwise`)."""
+    for k, (pred, _) in enumerate(switch.cases):
+        if _P.matches(pred, row):
+            return k
+    return len(switch.cases)
+
+
 def itoa(v) -> bytes:
     """strconv.Itoa / strconv.FormatInt(v, 10) of an int64."""
     v = int(v)
@@ -265,7 +375,10 @@ def _expr_value(p, row, i):
 def render(template, row, i: int = 0) -> bytes:
     """The template on one row (a dict with str or bytes keys and values); `i` = the row's number, which is what an Int
     or Float part is indexed with (host arrays only).  An Int.of / Float.of part is evaluated with expr.evaluate; a row
-    where it fails raises expr.ExprError."""
+    where it fails raises expr.ExprError.  A Switch renders the alternative the row selects (which_of): parts of the
+    other alternatives are not evaluated."""
+    if isinstance(template, Switch):
+        return render(template.alternatives()[which_of(template, row)], row, i)
     out = []
     for p in _template(template).parts:
         if isinstance(p, bytes):

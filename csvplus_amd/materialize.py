@@ -3,7 +3,7 @@ canonical CSV or JSON (cph_gather_rows / cph_csv_write / cph_json_write_rows; me
 ToCsv :379-406, ToJSON :446-480), filtering rows (cph_filter_rows), converting a column to numbers
 (cph_col_to_number; ValueAsInt / ValueAsFloat64 :165-205), evaluating a numeric expression per row (cph_num_eval:
 `price * float64(qty)`, csvplus_test.go:516-571) and computing a column from a row template (cph_map_format;
-Map :290-296, Validate :300-310)."""
+Map :290-296, Validate :300-310) or from the template of the first case that holds (cph_map_switch)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -500,44 +500,62 @@ def map_column(ctx: N.Context, cols_by_name, template, row_ids=None, nrows=None,
     (valid until release(); to_strcol() for a host result, as_device_strcol() for a device one).
 
     cols_by_name: {column name: StrCol} — the row the template sees; a Col whose name the mapping lacks becomes its default
-    or raises mapping.MissingColumn.  template: mapping.Format / Const (or a bare part).  row_ids: {name: ids} as in
+    or raises mapping.MissingColumn.  template: mapping.Format / Const (or a bare part), or a mapping.Switch / When, which
+    goes to map_switch.  row_ids: {name: ids} as in
     filter_rows, for columns read through row ids (a Join's); nrows: the number of rows (default: what the columns, the row
     ids or the Int / Float parts give).  An Int or Float part's array is indexed by OUTPUT row and lives on the host (numpy) or
     on the device (Int.on_device, Float.on_device); an Int.of / Float.of part's expression is evaluated over the same rows
     on the device (eval_number) and a row where it fails raises expr.ExprError."""
     from . import mapping as M
 
+    if isinstance(template, M.Switch):
+        return map_switch(ctx, cols_by_name, template, row_ids=row_ids, nrows=nrows, out_mem=out_mem)[0]
     names, pieces = M.compile(template, list(cols_by_name))
-    cols = [cols_by_name[nm] for nm in names]
-    ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
-    exprs = [p[2].expr for p in pieces if p[0] in (M.INT64, M.FLOAT64) and p[2].expr is not None]
     keep = []
-    if cols:
-        arr, sel, n = _rowsel(cols, ids, nrows, keep)
-    else:
-        arr, sel = None, None
-        counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64) and p[2].expr is None]
-        from . import expr as E
-        ecols = [nm for e in exprs for nm in E.columns(e) if nm in cols_by_name]
-        if nrows is not None:
-            n = int(nrows)
-        elif ecols:   # the rows an expression's columns give
-            n = _rowsel([cols_by_name[nm] for nm in ecols], None if row_ids is None else [row_ids.get(nm) for nm in ecols], None, [])[2]
-        elif counts:
-            n = min(counts)
-        elif cols_by_name:
-            n = min(c.nrows for c in cols_by_name.values())
-        else:
-            raise ValueError("map_column: a template without columns and Int / Float parts needs nrows")
+    arr, sel, n = _map_rows(cols_by_name, row_ids, nrows, names, pieces, keep, "map_column: a template")
     computed = []   # the expressions' results, on the device until the template has run
     try:
-        return _map_pieces(ctx, cols_by_name, row_ids, pieces, arr, sel, len(cols), n, out_mem, keep, computed)
+        parr = _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed)
+        out = C.POINTER(N.cph_colbuf)()
+        ctx._check(ctx.lib.cph_map_format(ctx.handle, arr, sel, len(names), n, parr, len(pieces), out_mem, C.byref(out)))
+        del keep
+        return ColBuf(ctx, out)
     finally:
         for nc in computed:
             nc.release()
 
 
-def _map_pieces(ctx, cols_by_name, row_ids, pieces, arr, sel, ncols, n, out_mem, keep, computed):
+def _map_rows(cols_by_name, row_ids, nrows, names, pieces, keep, who):
+    """cph_strcol array, cph_rowsel array and row count of a Map call over the columns `names`; without columns the rows
+    come from nrows, an expression's columns, the Int / Float arrays or the mapping's columns, in that order."""
+    from . import mapping as M
+
+    cols = [cols_by_name[nm] for nm in names]
+    ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
+    if cols:
+        return _rowsel(cols, ids, nrows, keep)
+    exprs = [p[2].expr for p in pieces if p[0] in (M.INT64, M.FLOAT64) and p[2].expr is not None]
+    counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64) and p[2].expr is None]
+    from . import expr as E
+    ecols = [nm for e in exprs for nm in E.columns(e) if nm in cols_by_name]
+    if nrows is not None:
+        n = int(nrows)
+    elif ecols:   # the rows an expression's columns give
+        n = _rowsel([cols_by_name[nm] for nm in ecols], None if row_ids is None else [row_ids.get(nm) for nm in ecols], None, [])[2]
+    elif counts:
+        n = min(counts)
+    elif cols_by_name:
+        n = min(c.nrows for c in cols_by_name.values())
+    else:
+        raise ValueError(f"{who} without columns and Int / Float parts needs nrows")
+    return None, None, n
+
+
+def _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending=None, tag=None):
+    """The cph_map_piece array of `pieces` (mapping.compile).  An Int.of / Float.of part is evaluated over the n rows into a
+    device array (cph_num_eval, appended to `computed`).  A failing row raises expr.ExprError at once — or, with a `pending`
+    list, the part is evaluated again into host memory and (tag, expression, NumCol with host status) is appended, for a
+    caller that decides per row whether the failure counts."""
     from . import mapping as M
 
     parr = (N.cph_map_piece * len(pieces))()
@@ -554,9 +572,15 @@ def _map_pieces(ctx, cols_by_name, row_ids, pieces, arr, sel, ncols, n, out_mem,
             if value.expr is not None:   # evaluated over the same rows into a device array: cph_num_eval
                 nc = eval_number(ctx, cols_by_name, value.expr, row_ids=row_ids, nrows=n, out_mem=N.CPH_MEM_DEVICE)
                 computed.append(nc)
-                if nc.nerrors:
-                    raise_expr_error(ctx, cols_by_name, value.expr, nc, row_ids)
                 mem, ptr = N.CPH_MEM_DEVICE, nc.values[0] or None
+                if nc.nerrors and pending is None:
+                    raise_expr_error(ctx, cols_by_name, value.expr, nc, row_ids)
+                elif nc.nerrors:   # the status bytes on the host; the values travel from there too
+                    nc.release()
+                    nc = eval_number(ctx, cols_by_name, value.expr, row_ids=row_ids, nrows=n, out_mem=N.CPH_MEM_HOST)
+                    pending.append((tag, value.expr, nc))
+                    keep.append(nc.values)
+                    mem, ptr = N.CPH_MEM_HOST, nc.values.ctypes.data if n else None
             elif value.count < n:
                 raise ValueError(f"map_column: {'an Int' if kind == M.INT64 else 'a Float'} part has {value.count} values for {n} rows")
             elif value.device:
@@ -569,10 +593,69 @@ def _map_pieces(ctx, cols_by_name, row_ids, pieces, arr, sel, ncols, n, out_mem,
                 parr[k].ints = ptr
             else:
                 parr[k].floats, parr[k].prec = ptr, value.prec
-    out = C.POINTER(N.cph_colbuf)()
-    ctx._check(ctx.lib.cph_map_format(ctx.handle, arr, sel, ncols, n, parr, len(pieces), out_mem, C.byref(out)))
-    del keep
-    return ColBuf(ctx, out)
+    return parr
+
+
+def map_switch(ctx: N.Context, cols_by_name, switch, row_ids=None, nrows=None, out_mem: int = N.CPH_MEM_HOST, want_which: bool = False):
+    """Map with a condition, on the device (cph_map_switch): the value of row i is the template of the first case of
+    `switch` (mapping.Switch / When) whose predicate holds for row i, else its `otherwise`.  Arguments as in map_column; a
+    column only a predicate names and the mapping lacks makes that term false.
+
+    Returns (ColBuf, which): the new column, and with want_which the alternative every row selected as a numpy uint8 array
+    (the case's index, or the number of cases for `otherwise`), else None.
+
+    Int.of / Float.of parts are evaluated over ALL rows; a failing row raises expr.ExprError only if that row selects an
+    alternative that contains the part — the lowest such row is reported."""
+    from . import mapping as M
+
+    names, cases, otherwise = M.compile_switch(switch, list(cols_by_name))
+    alts = [pc for _, pc in cases] + [otherwise]
+    keep = []
+    arr, sel, n = _map_rows(cols_by_name, row_ids, nrows, names, [p for pc in alts for p in pc], keep, "map_switch: a Switch")
+    computed, pending = [], []
+    try:
+        carr = (N.cph_map_case * len(cases))()
+        for a, (ops, pieces) in enumerate(cases):
+            prog = _pred_program(ops, keep)
+            parr = _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending, a)
+            keep += [prog, parr]
+            carr[a].prog, carr[a].nops = prog, len(ops)
+            carr[a].pieces, carr[a].npieces = parr, len(pieces)
+        oarr = _fill_pieces(ctx, cols_by_name, row_ids, otherwise, n, keep, computed, pending, len(cases))
+        which = np.zeros(n, dtype=np.uint8) if want_which or pending else None
+        out = C.POINTER(N.cph_colbuf)()
+        ctx._check(ctx.lib.cph_map_switch(ctx.handle, arr, sel, len(names), n, carr, len(cases), oarr, len(otherwise), out_mem,
+                                          C.byref(out), which.ctypes.data if which is not None and n else None))
+        del keep
+        cb = ColBuf(ctx, out)
+        worst = None   # (row, expression, NumCol, failing rows) of the lowest row whose own alternative holds a failed part
+        for a, expr, nc in pending:
+            rows = np.flatnonzero((nc.status != N.CPH_NUM_OK) & (which == a))
+            if len(rows) and (worst is None or int(rows[0]) < worst[0]):
+                worst = (int(rows[0]), expr, nc, len(rows))
+        if worst is not None:
+            cb.release()
+            _raise_expr_error_at(ctx, cols_by_name, worst[1], worst[2], worst[0], worst[3], row_ids)
+        return cb, (which if want_which else None)
+    finally:
+        for nc in computed:
+            nc.release()
+
+
+def _raise_expr_error_at(ctx, cols_by_name, expr, numcol, row, nerrors, row_ids=None):
+    """raise_expr_error for a row that need not be the result's first failing one: the failing op is found by evaluating
+    the expression on that row's values with the host model."""
+    from . import expr as E
+
+    if row == numcol.first_error_row:
+        numcol.nerrors = nerrors
+        raise_expr_error(ctx, cols_by_name, expr, numcol, row_ids)
+    names, ops = E.compile(expr, list(cols_by_name))
+    values = {nm: _value_at(ctx, cols_by_name[nm], None if row_ids is None else row_ids.get(nm), row) for nm in names}
+    _, status, op = E.evaluate(expr, values, row)
+    kind = int(numcol.status[row])
+    column = names[ops[op][1]] if ops[op][0] in (E.COL_INT, E.COL_FLT) else None
+    raise E.ExprError(row, op, kind, column, E.error_text(expr, values, kind, op), nerrors)
 
 
 def validate_rows(ctx: N.Context, cols_by_name, pred, row_ids=None, nrows=None, first_row: int = 0):

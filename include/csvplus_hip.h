@@ -940,7 +940,7 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  * than 32 / 64, an identity column whose row count is not nrows, an unknown out_mem.
  *
  * Out of scope: the other forms of FormatFloat — the shortest round-trip digits (prec -1) and the 'e' / 'g' formats, a
- * project of their own —, case mapping, trimming, substrings, conditional pieces.
+ * project of their own —, case mapping, trimming, substrings.  A value that depends on a condition is cph_map_switch's.
  */
 enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4 };
 #define CPH_MAP_MAX_PIECES 16
@@ -956,6 +956,56 @@ typedef struct {
 
 CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
                                const cph_map_piece* pieces, int32_t npieces, int32_t out_mem, cph_colbuf** out);
+
+/* ---- conditional Map: the template of the first case that holds (csvplus.go:290-296) ---- */
+/*
+ * The reference's Map closures branch: `if row["name"] == "Amelia" { row["name"] = "Julia" }` (csvplus_test.go:283-288).  As
+ * data, that is a SWITCH: value i of the new column is the template of the FIRST case whose condition holds for row i, and
+ * the template `otherwise` where none does — Go's if / else if / else, or switch { case ...: }.
+ *
+ * Columns.  cols / sel / nrows mean exactly what they mean for cph_map_format: an identity column has exactly nrows rows,
+ * every column is read through its own row ids, so a Switch over JOINED rows materialises nothing.  The conditions and the
+ * templates index the SAME cols array and share its limit of 16 columns.
+ *
+ * Conditions.  A case's `prog` is a cph_filter_rows program over cols, evaluated with first_row = 0: a LIKE or numeric term on
+ * column -1 is false; a numeric term on a value that does not convert is false under every relation; float terms compare
+ * the doubles cph_col_to_number produces, so an answer never depends on where a value was converted.  A float column several
+ * cases compare is converted once per call.
+ *
+ * Selection.  Row i takes the alternative a = the lowest case index whose program holds, or ncases (`otherwise`) if none
+ * does.  Its value is that alternative's pieces rendered exactly as cph_map_format renders them (LITERAL / COLUMN / INT64 /
+ * FLOAT64; verbatim bytes; FormatInt and FormatFloat 'f' rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
+ * memory, written when the call succeeds).
+ *
+ * Number pieces.  INT64 / FLOAT64 arrays have nrows entries indexed by OUTPUT row.  Entries of rows that select ANOTHER
+ * alternative are never interpreted and may hold anything; in particular the FLOAT64 refusal (a finite |v| >= 2^128) fails
+ * the call only for a row that selects the alternative holding that piece.  The message then names the alternative, the
+ * piece and the lowest such row, and *out stays NULL.
+ *
+ * Result.  An ordinary library-owned cph_colbuf: 64-bit offsets, exact nbytes, in out_mem.  nrows == 0 is legal, and so is a
+ * call in which every row selects an empty value (nbytes == 0).
+ *
+ * CPH_ERR_INVALID, with a message in cph_last_error that names the case: NULL ctx / cases / otherwise / out; ncases outside
+ * 1..CPH_MAP_MAX_CASES; a case with NULL prog or pieces; npieces / notherwise outside 1..CPH_MAP_MAX_PIECES; more than
+ * CPH_MAP_SWITCH_MAX_PIECES pieces in all alternatives together; everything cph_filter_rows rejects in a program; everything
+ * cph_map_format rejects in a piece or in the row sources.  CPH_ERR_TOO_MANY_ROWS for nrows > 2^32 - 1 (the predicate
+ * evaluator's limit).
+ *
+ * Out of scope: nested switches; a conditional part inside a template (use one Switch over whole templates); case mapping,
+ * trimming and substrings; the other forms of FormatFloat.
+ */
+#define CPH_MAP_MAX_CASES         8
+#define CPH_MAP_SWITCH_MAX_PIECES 32      /* the pieces of all alternatives together */
+typedef struct {
+    const cph_pred_op*   prog;    int32_t nops;     /* the condition: a cph_filter_rows program over `cols` */
+    const cph_map_piece* pieces;  int32_t npieces;  /* the value where this is the FIRST case that holds; 1..CPH_MAP_MAX_PIECES */
+} cph_map_case;
+
+CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
+                               const cph_map_case* cases, int32_t ncases,                 /* 1..CPH_MAP_MAX_CASES */
+                               const cph_map_piece* otherwise, int32_t notherwise,        /* 1..CPH_MAP_MAX_PIECES */
+                               int32_t out_mem, cph_colbuf** out,
+                               uint8_t* which /* NULL, or nrows bytes of HOST memory */);
 
 /* ---- CSV ingest: bytes -> SoA string columns (csvplus.go:1080-1146) ----------- */
 /*
