@@ -20,7 +20,7 @@ all: hip datagen oracle host
 hip: $(LIBDIR)/libcsvplus_hip.so
 datagen: $(LIBDIR)/libcph_datagen.so
 oracle: oracle/_build/liboracle.so oracle/_build/libfaithful.so
-host: tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_host_encode tests/cpp/test_numformat tests/c/abi_demo tests/c/libnccl_standin.so
+host: tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_host_encode tests/cpp/test_numformat tests/cpp/test_hash_model tests/c/abi_demo tests/c/libnccl_standin.so
 
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(LIBDIR)/obj
@@ -82,6 +82,10 @@ tests/cpp/test_numformat: tests/cpp/test_numformat.cpp $(CSRC)/numformat_device.
 tests/cpp/test_host_encode: tests/cpp/test_host_encode.cpp $(CSRC)/host_encode_kernels.hpp
 	$(CXX) -O2 -std=c++17 -Wall -pthread $< -o $@
 
+# the Join hash table's hash, home sector and probe-sequence step evaluated on the host (CPU only: no HIP call)
+tests/cpp/test_hash_model: tests/cpp/test_hash_model.hip $(HIP_HDRS)
+	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Wall -Wno-unused-function $< -o $@
+
 tests/c/abi_demo: tests/c/abi_demo.c include/csvplus_hip.h $(LIBDIR)/libcsvplus_hip.so
 	$(CC) -O2 -std=c99 -Wall -Wextra -Iinclude $< -L$(LIBDIR) -lcsvplus_hip -Wl,-rpath,'$$ORIGIN/../../csvplus_amd/lib' -o $@
 
@@ -104,6 +108,6 @@ oracle/_build/datagen_asan: tests/c/datagen_check.c $(CSRC)/datagen.c
 	$(CC) $(SAN) -fopenmp -Wall tests/c/datagen_check.c -o $@
 
 clean:
-	rm -rf $(LIBDIR) oracle/_build tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_numformat tests/cpp/test_host_encode tests/c/abi_demo tests/c/libnccl_standin.so
+	rm -rf $(LIBDIR) oracle/_build tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_numformat tests/cpp/test_host_encode tests/cpp/test_hash_model tests/c/abi_demo tests/c/libnccl_standin.so
 
 .PHONY: all hip datagen oracle host asan clean
