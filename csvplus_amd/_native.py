@@ -150,6 +150,8 @@ class cph_rowsel(C.Structure):
 CPH_PRED_LIKE, CPH_PRED_NOT, CPH_PRED_ALL, CPH_PRED_ANY = 1, 2, 3, 4
 CPH_PRED_INT_LT, CPH_PRED_INT_LE, CPH_PRED_INT_EQ, CPH_PRED_INT_NE, CPH_PRED_INT_GE, CPH_PRED_INT_GT = 16, 17, 18, 19, 20, 21
 CPH_PRED_FLT_LT, CPH_PRED_FLT_LE, CPH_PRED_FLT_EQ, CPH_PRED_FLT_NE, CPH_PRED_FLT_GE, CPH_PRED_FLT_GT = 24, 25, 26, 27, 28, 29
+CPH_PRED_STR_LT, CPH_PRED_STR_LE, CPH_PRED_STR_EQ, CPH_PRED_STR_NE, CPH_PRED_STR_GE, CPH_PRED_STR_GT = 32, 33, 34, 35, 36, 37
+CPH_PRED_HAS_PREFIX, CPH_PRED_HAS_SUFFIX, CPH_PRED_CONTAINS = 40, 41, 42
 CPH_PRED_MAX_OPS, CPH_PRED_MAX_LIKE, CPH_PRED_MAX_STACK = 64, 32, 32
 CPH_FILTER_WHERE, CPH_FILTER_TAKE_WHILE, CPH_FILTER_DROP_WHILE = 0, 1, 2
 CPH_NO_LIMIT = 0xFFFFFFFFFFFFFFFF
@@ -198,6 +200,13 @@ class cph_expr_nums(C.Structure):
 
 
 CPH_MAP_LITERAL, CPH_MAP_COLUMN, CPH_MAP_INT64, CPH_MAP_FLOAT64 = 1, 2, 3, 4
+CPH_MAP_SLICE = 8
+
+
+class cph_map_slice(C.Structure):
+    _fields_ = [("from_", C.c_int64), ("to", C.c_int64)]
+
+
 CPH_MAP_MAX_PIECES = 16
 
 

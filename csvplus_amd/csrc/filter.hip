@@ -25,6 +25,11 @@
 //            per column and call, deferred rows finished on the host and patched in) and k_pred_eval compares the
 //            resulting doubles — so a WHERE or WHILE answer never depends on where a value was converted.
 // A program without numeric terms launches the NUM = false instantiations: the kernels it always launched.
+//
+// String terms that look INSIDE a value (CPH_PRED_STR_* / HAS_PREFIX / HAS_SUFFIX / CONTAINS) are term bits too.  Their
+// per-value routines live in strpred_device.hpp (host-compilable, tested on the CPU); here they read the value through
+// load_value_chunk and the literal as a LIKE's literal is kept: lit8, or the literal block in LDS / global memory.  A program
+// with such a term launches the STR = true instantiations; every other program launches exactly what it launched before.
 // The way from a cph_pred_op program to the bitmap (terms, literal block, float columns, the k_pred_eval<true, NUM> launch) is
 // pred_eval_bitmap (cph_internal.hpp): the WHERE mode calls it, and so does cph_map_switch (map_switch.hip), once per case.
 #include <algorithm>
@@ -32,6 +37,7 @@
 #include <new>
 
 #include "numparse_device.hpp"
+#include "strpred_device.hpp"
 
 namespace cph {
 
@@ -42,8 +48,9 @@ constexpr int kFiltWords = kFiltTile / 64;
 constexpr int kFiltWaveWords = kFiltWords / (kMatThreads / kWave);   // 8 words per wave
 constexpr int kLitLds    = 4096;                       // literal bytes kept in LDS; more than that stay in global memory
 
-enum : uint32_t { kTermBytes = 0, kTermFix8 = 1, kTermInt = 2, kTermF64 = 3 };   // low byte of PredTerm::kind
-// bits 8..11 of a numeric term's kind: which outcomes of (value ? literal) make the relation hold
+enum : uint32_t { kTermBytes = 0, kTermFix8 = 1, kTermInt = 2, kTermF64 = 3,     // low byte of PredTerm::kind
+                  kTermStrCmp = 4, kTermPrefix = 5, kTermSuffix = 6, kTermContains = 7 };   // STR instantiations only
+// bits 8..11 of a numeric or kTermStrCmp term's kind: which outcomes of (value ? literal) make the relation hold
 enum : uint32_t { kCmpLess = 1, kCmpEqual = 2, kCmpGreater = 4, kCmpUnordered = 8 };
 constexpr uint8_t kTermNever = 0xFF;                   // a LIKE decided on the host: no such column, or a fixed width other than the literal's
 
@@ -55,6 +62,7 @@ struct PredTerm {
     int32_t  col;
     uint32_t kind;   // kTermFix8: a fixed-width column of 8 bytes on an 8-byte aligned base — one aligned load and one compare
                      // kTermInt / kTermF64: lit8 = the literal's bits, the relation in bits 8..11
+                     // kTermStrCmp .. kTermContains: the literal as a LIKE's (lit8 / lit_off, len); kTermStrCmp: the relation in bits 8..11
     const double*  fval;   // kTermF64: the converted column, entry i = row first_row + i of the selection ...
     const uint8_t* fstat;  // ... and its CPH_NUM_* status bytes
 };
@@ -81,10 +89,39 @@ __device__ __forceinline__ bool like_bytes(const DevCol& col, uint64_t begin, co
     return true;
 }
 
+// the two functors of strpred_device.hpp over a column's value and a term's literal
+struct ValueChunks {
+    const uint8_t* data;
+    uint64_t begin;
+    __device__ __forceinline__ uint64_t operator()(uint64_t off, uint64_t len, int j) const { return load_value_chunk(data, begin + off, len, j); }
+};
+struct LiteralWords {
+    const PredTerm& t;
+    const uint64_t* glits;
+    const CPH_LDS uint64_t* slits;
+    bool in_lds;
+    __device__ __forceinline__ uint64_t operator()(uint64_t j) const { return t.len <= 8 ? t.lit8 : in_lds ? slits[t.lit_off + j] : glits[t.lit_off + j]; }
+};
+
+// one string term on one value (what: kTermStrCmp .. kTermContains, uniform; rel: kCmp* outcomes of a kTermStrCmp)
+__device__ __forceinline__ bool str_term(uint32_t what, uint32_t rel, const DevCol& col, uint64_t begin, uint64_t vlen, const PredTerm& t,
+                                         const uint64_t* glits, const CPH_LDS uint64_t* slits, bool in_lds) {
+    const ValueChunks v{col.data, begin};
+    const LiteralWords lit{t, glits, slits, in_lds};
+    if (what == kTermStrCmp) {
+        const int c = str_compare(v, vlen, lit, (uint64_t)t.len);
+        return (rel & (c < 0 ? kCmpLess : c == 0 ? kCmpEqual : kCmpGreater)) != 0;
+    }
+    if (what == kTermPrefix) return str_has_prefix(v, vlen, lit, (uint64_t)t.len);
+    if (what == kTermSuffix) return str_has_suffix(v, vlen, lit, (uint64_t)t.len);
+    return str_contains(v, vlen, lit, (uint64_t)t.len);
+}
+
 // BITMAP: bitmap[tile * 32 + w] bit b = the predicate holds for row tile * 2048 + 64 w + b of the call (rows >= n: 0),
 //         counts[tile] = the tile's set bits.
 // else:   *first_fail = min(*first_fail, the first row where it does not hold); the host presets it to n.
-template <bool BITMAP, bool NUM>
+// STR: the program has a term of strpred_device.hpp; NUM: a numeric one
+template <bool BITMAP, bool NUM, bool STR = false>
 __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds ids, PredProg prog, uint64_t first_row, uint64_t n,
                                                           uint64_t* __restrict__ bitmap, uint32_t* __restrict__ counts,
                                                           unsigned long long* first_fail) {
@@ -157,6 +194,14 @@ __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds 
                         const uint32_t cls = v[k] < lit ? kCmpLess : v[k] == lit ? kCmpEqual : v[k] > lit ? kCmpGreater : kCmpUnordered;
                         mask[k] |= (uint32_t)(st[k] == CPH_NUM_OK && (rel & cls) != 0) << t;
                     }
+                } else if (STR && (tm.kind & 0xFFu) >= kTermStrCmp) {
+                    const uint32_t what = tm.kind & 0xFFu, rel = tm.kind >> 8;   // uniform: the wave diverges on the values' lengths alone
+                    uint64_t b[kFiltPhase], l[kFiltPhase];
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) value_span(col, source_row(rid, pos[k]), &b[k], &l[k]);
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++)
+                        mask[k] |= (uint32_t)str_term(what, rel, col, b[k], l[k], tm, prog.lits, slits, in_lds) << t;
                 } else {
                     uint64_t b[kFiltPhase], l[kFiltPhase];
 #pragma unroll
@@ -295,6 +340,14 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
     for (int q = 0; q < nops; q++) {
         const cph_pred_op& o = prog[q];
         switch (o.op) {
+            case CPH_PRED_STR_LT: case CPH_PRED_STR_LE: case CPH_PRED_STR_EQ: case CPH_PRED_STR_NE: case CPH_PRED_STR_GE: case CPH_PRED_STR_GT:
+            case CPH_PRED_HAS_PREFIX: case CPH_PRED_HAS_SUFFIX: case CPH_PRED_CONTAINS:
+                if (o.arg < -1 || o.arg >= ncols) return {CPH_ERR_INVALID, "cph_filter_rows: string term column outside -1..ncols-1"};
+                if (!o.value.data && o.value.len) return {CPH_ERR_INVALID, "cph_filter_rows: a string term's literal with bytes but no data pointer"};
+                if (o.value.len > 0xFFFFFFFFull) return {CPH_ERR_INVALID, "cph_filter_rows: a string term's literal beyond 4 GiB"};
+                if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE, numeric and string terms"};
+                depth++;
+                break;
             case CPH_PRED_LIKE:
                 if (o.arg < -1 || o.arg >= ncols) return {CPH_ERR_INVALID, "cph_filter_rows: LIKE column outside -1..ncols-1"};
                 if (!o.value.data && o.value.len) return {CPH_ERR_INVALID, "cph_filter_rows: a LIKE value with bytes but no data pointer"};
@@ -318,7 +371,7 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
                 depth += 1 - o.arg;
                 break;
             default:
-                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4, 16..21, 24..29)"};
+                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4, 16..21, 24..29, 32..37, 40..42)"};
         }
         if (depth > CPH_PRED_MAX_STACK) return {CPH_ERR_INVALID, "cph_filter_rows: stack deeper than 32"};
     }
@@ -328,6 +381,8 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
 
 bool is_int_cmp(int32_t op) { return op >= CPH_PRED_INT_LT && op <= CPH_PRED_INT_GT; }
 bool is_flt_cmp(int32_t op) { return op >= CPH_PRED_FLT_LT && op <= CPH_PRED_FLT_GT; }
+bool is_str_cmp(int32_t op) { return op >= CPH_PRED_STR_LT && op <= CPH_PRED_STR_GT; }
+bool is_str_term(int32_t op) { return is_str_cmp(op) || (op >= CPH_PRED_HAS_PREFIX && op <= CPH_PRED_CONTAINS); }
 // LT LE EQ NE GE GT -> the outcomes under which the relation holds (IEEE: unordered satisfies NE alone)
 uint32_t rel_outcomes(int32_t rel) {
     static const uint32_t m[6] = {kCmpLess, kCmpLess | kCmpEqual, kCmpEqual, kCmpLess | kCmpGreater | kCmpUnordered, kCmpEqual | kCmpGreater, kCmpGreater};
@@ -340,6 +395,7 @@ struct BuiltProg {   // a program as k_pred_eval takes it
     DevBuf litbuf;          // the literals beyond 8 bytes; the kernels read it
     double col_bytes = 0;   // byte model: what the evaluation reads of the columns
     bool numeric = false;   // the NUM instantiations
+    bool strings = false;   // the STR instantiations
 };
 
 // fcols: the float columns converted so far in this call (reused, appended to)
@@ -386,10 +442,12 @@ Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, cons
             }
             continue;
         }
-        if (prog[q].op != CPH_PRED_LIKE) continue;
+        const bool str = is_str_term(prog[q].op);
+        if (prog[q].op != CPH_PRED_LIKE && !str) continue;
         const int c = prog[q].arg;
         const uint64_t len = prog[q].value.len;
-        if (c < 0 || len > 0xFFFFFFFFull || (arg.c[c].fixed_width && arg.c[c].fixed_width != len)) {
+        pp.op[q] = (uint8_t)CPH_PRED_LIKE;   // a string term: a term bit like a LIKE
+        if (c < 0 || len > 0xFFFFFFFFull || (!str && arg.c[c].fixed_width && arg.c[c].fixed_width != len)) {
             pp.arg[q] = kTermNever;
             continue;
         }
@@ -397,7 +455,15 @@ Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, cons
         pp.arg[q] = (uint8_t)pp.nterms++;
         t.col = c;
         t.len = (uint32_t)len;
-        t.kind = arg.c[c].fixed_width == 8 && ((uintptr_t)arg.c[c].data & 7u) == 0 ? kTermFix8 : kTermBytes;
+        if (str) {
+            bp->strings = true;
+            t.kind = is_str_cmp(prog[q].op)               ? kTermStrCmp | (rel_outcomes(prog[q].op - CPH_PRED_STR_LT) << 8)
+                     : prog[q].op == CPH_PRED_HAS_PREFIX ? kTermPrefix
+                     : prog[q].op == CPH_PRED_HAS_SUFFIX ? kTermSuffix
+                                                         : kTermContains;
+        } else {
+            t.kind = arg.c[c].fixed_width == 8 && ((uintptr_t)arg.c[c].data & 7u) == 0 ? kTermFix8 : kTermBytes;
+        }
         if (len <= 8) {
             if (len) memcpy(&t.lit8, prog[q].value.data, (size_t)len);
         } else {
@@ -428,6 +494,21 @@ Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, cons
     return {};
 }
 
+// the instantiation a program needs: NUM / STR only where it has such a term
+template <bool BITMAP>
+void launch_pred_eval(cph_ctx* ctx, const BuiltProg& bp, const ColsArg& arg, const ColIds& ids, uint64_t first_row, uint64_t n, uint64_t ntiles,
+                      uint64_t* bitmap, uint32_t* counts, unsigned long long* first_fail) {
+    const dim3 grid(filter_grid(ntiles)), block(kMatThreads);
+    if (bp.strings && bp.numeric)
+        hipLaunchKernelGGL((k_pred_eval<BITMAP, true, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+    else if (bp.strings)
+        hipLaunchKernelGGL((k_pred_eval<BITMAP, false, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+    else if (bp.numeric)
+        hipLaunchKernelGGL((k_pred_eval<BITMAP, true, false>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+    else
+        hipLaunchKernelGGL((k_pred_eval<BITMAP, false, false>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+}
+
 }  // namespace
 
 namespace cph {
@@ -443,13 +524,8 @@ Status pred_eval_bitmap(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, con
     CPH_TRY(out->bitmap.alloc(&ctx->pool, ntiles * kFiltWords * sizeof(uint64_t)));
     CPH_TRY(out->counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
     {
-        ProfScope ps(ctx, "k_pred_eval", bp.col_bytes + (double)n / 8.0 + 4.0 * (double)ntiles);
-        if (bp.numeric)
-            hipLaunchKernelGGL((k_pred_eval<true, true>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, bp.pp, first_row, n,
-                               out->bitmap.as<uint64_t>(), out->counts.as<uint32_t>(), (unsigned long long*)nullptr);
-        else
-            hipLaunchKernelGGL((k_pred_eval<true, false>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, bp.pp, first_row, n,
-                               out->bitmap.as<uint64_t>(), out->counts.as<uint32_t>(), (unsigned long long*)nullptr);
+        ProfScope ps(ctx, bp.strings ? "k_pred_eval_str" : "k_pred_eval", bp.col_bytes + (double)n / 8.0 + 4.0 * (double)ntiles);
+        launch_pred_eval<true>(ctx, bp, arg, ids, first_row, n, ntiles, out->bitmap.as<uint64_t>(), out->counts.as<uint32_t>(), nullptr);
     }
     CPH_HIP_TRY(hipGetLastError());
     out->lits = std::move(bp.litbuf);   // the kernel reads it: it lives as long as the bitmap
@@ -505,7 +581,6 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         if (opts->mode != CPH_FILTER_WHERE) {
             BuiltProg bp;
             CPH_TRY(build_pred_prog(ctx, arg, ids, prog, nops, first_row, n, &fcols, &bp));
-            const PredProg& pp = bp.pp;
             DevBuf ff;
             CPH_TRY(ff.alloc(&ctx->pool, sizeof(uint64_t)));
             void* slot = nullptr;
@@ -513,13 +588,8 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
             memcpy(slot, &n, sizeof n);
             CPH_HIP_TRY(hipMemcpyAsync(ff.get(), slot, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
             {
-                ProfScope ps(ctx, "k_pred_eval", bp.col_bytes);
-                if (bp.numeric)
-                    hipLaunchKernelGGL((k_pred_eval<false, true>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
-                                       (uint64_t*)nullptr, (uint32_t*)nullptr, ff.as<unsigned long long>());
-                else
-                    hipLaunchKernelGGL((k_pred_eval<false, false>), dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, arg, ids, pp, first_row, n,
-                                       (uint64_t*)nullptr, (uint32_t*)nullptr, ff.as<unsigned long long>());
+                ProfScope ps(ctx, bp.strings ? "k_pred_eval_str" : "k_pred_eval", bp.col_bytes);
+                launch_pred_eval<false>(ctx, bp, arg, ids, first_row, n, ntiles, nullptr, nullptr, ff.as<unsigned long long>());
             }
             CPH_HIP_TRY(hipGetLastError());
             uint64_t stop = 0;   // rows in front of the first failing one

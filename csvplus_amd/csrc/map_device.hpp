@@ -5,18 +5,32 @@
 
 #include "materialize_device.hpp"
 #include "numformat_device.hpp"
+#include "strpred_device.hpp"
 
 namespace cph {
 
 struct MapPiece {
     int32_t kind;          // CPH_MAP_*
-    int32_t col;           // COLUMN: the column; FLOAT64: prec
-    uint32_t off, len;     // LITERAL: its bytes in the plan's literal block
+    int32_t col;           // COLUMN / SLICE: the column; FLOAT64: prec
+    union {
+        struct {
+            uint32_t off, len;   // LITERAL: its bytes in the plan's literal block
+        };
+        int64_t from;            // SLICE: bytes [from, to) of the value, Python's slice rules (strpred_device.hpp: slice_span)
+    };
     union {
         const int64_t* ints;    // INT64: one value per output row, on the device
         const double* floats;   // FLOAT64: likewise
+        int64_t to;             // SLICE
     };
 };
+
+// The piece kinds an instantiation of the Map kernels carries code for.  A template launches the smallest set that holds
+// its pieces, so one of LITERAL / COLUMN / INT64 pieces alone launches the kernels it always launched.
+enum : int { kPiecesBase = 0,     // LITERAL, COLUMN, INT64
+             kPiecesSlice = 1,    // + SLICE
+             kPiecesFloat = 2 };  // + SLICE and FLOAT64 (the formatter's registers)
+__host__ __device__ constexpr int pieces_set(bool has_float, bool has_slice) { return has_float ? kPiecesFloat : has_slice ? kPiecesSlice : kPiecesBase; }
 
 __device__ __forceinline__ uint64_t int_magnitude(int64_t v) { return v < 0 ? 0ull - (uint64_t)v : (uint64_t)v; }
 
@@ -65,9 +79,23 @@ __device__ __forceinline__ void pick_field(const RecordFields<NC>& f, int c, uin
         if (k == c) *b = f.b[k], *l = f.l[k], *c0 = f.c0[k];
 }
 
+// bytes a COLUMN or SLICE piece adds to row i: from the value's span alone, no data read
+template <int NC, int PK>
+__device__ __forceinline__ uint64_t map_field_bytes(const ColsArg& cols, const ColIds& ids, const MapPiece& p, const RecordFields<NC>& f, uint64_t i) {
+    uint64_t b, l, c0;
+    if constexpr (NC > 0) pick_field(f, p.col, &b, &l, &c0);
+    else value_span(cols.c[p.col], source_row(ids.ids[p.col], i), &b, &l);
+    if (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE) {
+        uint64_t so, sn;
+        slice_span(l, p.from, p.to, &so, &sn);
+        return sn;
+    }
+    return l;
+}
+
 // pieces [k0, k1) of `pieces` for output row i, in order, into the sink; literals lie in `lits` (k0 and k1 may differ from lane
 // to lane)
-template <int NC, bool FL, class Sink>
+template <int NC, int PK, class Sink>
 __device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, const ColIds& ids, const uint8_t* lits, const MapPiece* pieces,
                                                int k0, int k1, const RecordFields<NC>& f, uint64_t i) {
     for (int k = k0; k < k1; k++) {
@@ -77,8 +105,15 @@ __device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, con
                 s.put8(load_value_chunk(lits, p.off, p.len, (int)(q >> 3)), p.len - q < 8u ? p.len - q : 8u);
         } else if (p.kind == CPH_MAP_INT64) {
             put_int(s, p.ints[i]);
-        } else if (FL && p.kind == CPH_MAP_FLOAT64) {
+        } else if (PK == kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
             fixed_put(s, fixed_split(p.floats[i], p.col), p.col);
+        } else if (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE) {   // the record's preloaded first chunk is the whole field's: a slice loads its own
+            const uint8_t* data = cols.c[p.col].data;
+            uint64_t b, l, c0, so, sn;
+            if constexpr (NC > 0) pick_field(f, p.col, &b, &l, &c0);
+            else value_span(cols.c[p.col], source_row(ids.ids[p.col], i), &b, &l);
+            slice_span(l, p.from, p.to, &so, &sn);
+            for (uint64_t q = 0; q < sn; q += 8) s.put8(load_value_chunk(data, b + so, sn, (int)(q >> 3)), (uint32_t)(sn - q < 8 ? sn - q : 8));
         } else {
             const uint8_t* data = cols.c[p.col].data;
             uint64_t b, l, c0;

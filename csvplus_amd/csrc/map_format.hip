@@ -2,7 +2,8 @@
 //
 //   cph_map_format  value i of the new column = the template's pieces in order: literal bytes, the value of a column in
 //                   row i (read through that column's row ids, as the writers read a joined row), an int64 written as
-//                   strconv.FormatInt(v, 10), a float64 written as strconv.FormatFloat(v, 'f', prec, 64) (numformat_device.hpp).
+//                   strconv.FormatInt(v, 10), a float64 written as strconv.FormatFloat(v, 'f', prec, 64) (numformat_device.hpp),
+//                   a slice [from, to) of a column's value in row i.
 //                   Bytes are copied verbatim; nothing is escaped.
 //
 // The pipeline of the gather and of the two-pass CSV writer (materialize.hip): k_map_lens (bytes per row: offsets only, the
@@ -13,6 +14,9 @@
 // A template with a FLOAT64 piece runs its own instantiations of both kernels (k_map_lens_f64 / k_map_copy_f64): the others
 // carry no float code.  The length pass of those also finds the lowest row whose value is beyond the formatter's range; the
 // row number comes back in the same copy as the scan's total.
+// A template with a SLICE piece (bytes [from, to) of a column's value, strpred_device.hpp: slice_span) and no FLOAT64 piece runs
+// a third pair (k_map_lens_sl / k_map_copy_sl); with both it runs the float pair, which carries the slice code too.  The length
+// pass takes a slice from the value's span alone; the copy pass puts (begin + from', len') through a COLUMN piece's chunk loop.
 // The digit counts, the integer writer and the loop over a run of pieces are shared with map_switch.hip (map_device.hpp).
 #include <new>
 #include <string>
@@ -29,9 +33,9 @@ struct MapPlan {
     MapPiece p[CPH_MAP_MAX_PIECES];
 };
 
-// lens[i] = bytes of value i.  FL (the plan has a FLOAT64 piece): lens[n + 1], preset to UINT64_MAX, = the lowest row with a
+// lens[i] = bytes of value i.  PK == kPiecesFloat (the plan has a FLOAT64 piece): lens[n + 1], preset to UINT64_MAX, = the lowest row with a
 // value the formatter refuses.
-template <int NC, bool FL = false>
+template <int NC, int PK = kPiecesBase>
 __global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, uint64_t* __restrict__ lens) {
     const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;
     for (uint64_t i = (uint64_t)blockIdx.x * kMatThreads + threadIdx.x; i < n; i += stride) {
@@ -42,15 +46,12 @@ __global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds i
             const MapPiece& p = plan.p[k];
             if (p.kind == CPH_MAP_INT64) {
                 total += int_chars(p.ints[i]);
-            } else if (FL && p.kind == CPH_MAP_FLOAT64) {
+            } else if (PK == kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
                 const FixedParts r = fixed_split(p.floats[i], p.col);
                 total += fixed_chars(r, p.col);
                 if (r.kind == FIXED_RANGE) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
-            } else if (p.kind == CPH_MAP_COLUMN) {
-                uint64_t b, l, c0;
-                if constexpr (NC > 0) pick_field(f, p.col, &b, &l, &c0);
-                else value_span(cols.c[p.col], source_row(ids.ids[p.col], i), &b, &l);
-                total += l;
+            } else if (p.kind == CPH_MAP_COLUMN || (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE)) {
+                total += map_field_bytes<NC, PK>(cols, ids, p, f, i);
             }
         }
         lens[i] = total;
@@ -58,10 +59,12 @@ __global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds i
 }
 // the float instantiations under names CPH_CSV_DISPATCH can take
 template <int NC>
-constexpr auto k_map_lens_f64 = k_map_lens<NC, true>;
+constexpr auto k_map_lens_f64 = k_map_lens<NC, kPiecesFloat>;
+template <int NC>
+constexpr auto k_map_lens_sl = k_map_lens<NC, kPiecesSlice>;
 
 // value i at out + offs[i]
-template <int NC, bool FL = false>
+template <int NC, int PK = kPiecesBase>
 __global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, const uint64_t* __restrict__ offs,
                                                          uint8_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -82,11 +85,11 @@ __global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds i
         if (i < tend) {
             if (staged) {
                 WordSink s(reinterpret_cast<uint32_t*>(smem), (uint32_t)((offs[i] - obase) + (obase & 15)));
-                map_put_record<NC, FL>(s, cols, ids, plan.lits, plan.p, 0, plan.npieces, f, i);
+                map_put_record<NC, PK>(s, cols, ids, plan.lits, plan.p, 0, plan.npieces, f, i);
                 s.finish();
             } else {
                 GlobalSink s{out + offs[i]};
-                map_put_record<NC, FL>(s, cols, ids, plan.lits, plan.p, 0, plan.npieces, f, i);
+                map_put_record<NC, PK>(s, cols, ids, plan.lits, plan.p, 0, plan.npieces, f, i);
             }
         }
         if (staged) {
@@ -97,7 +100,9 @@ __global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds i
     }
 }
 template <int NC>
-constexpr auto k_map_copy_f64 = k_map_copy<NC, true>;
+constexpr auto k_map_copy_f64 = k_map_copy<NC, kPiecesFloat>;
+template <int NC>
+constexpr auto k_map_copy_sl = k_map_copy<NC, kPiecesSlice>;
 
 }  // namespace cph
 
@@ -118,7 +123,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
     if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
     const uint64_t n = nrows;
     uint64_t lit_bytes = 0;
-    bool has_float = false;
+    bool has_float = false, has_slice = false;
     for (int k = 0; k < npieces; k++) {
         const cph_map_piece& p = pieces[k];
         switch (p.kind) {
@@ -140,8 +145,14 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                 if (p.prec < 0 || p.prec > kFixedMaxPrec) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: prec of a FLOAT64 piece outside 0..22"});
                 has_float = true;
                 break;
+            case CPH_MAP_SLICE:
+                if (p.arg < 0 || p.arg >= ncols) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: a SLICE piece's column outside 0..ncols-1"});
+                if (!p.value.data || p.value.len != sizeof(cph_map_slice))
+                    return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: a SLICE piece's value is exactly 16 bytes (a cph_map_slice) behind a non-NULL pointer"});
+                has_slice = true;
+                break;
             default:
-                return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: unknown piece kind (1..4)"});
+                return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: unknown piece kind (1..4, 8)"});
         }
     }
     {
@@ -164,6 +175,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
             plan.npieces = npieces;
             std::string lits;
             double in_bytes = 0;   // what the copy pass reads per row besides the value bytes
+            uint32_t slice_cols = 0;
             for (int k = 0; k < npieces; k++) {
                 const cph_map_piece& p = pieces[k];
                 MapPiece& d = plan.p[k];
@@ -179,6 +191,17 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                         if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
                     }
                     plan.col_mask |= 1u << p.arg;
+                } else if (p.kind == CPH_MAP_SLICE) {   // not in col_mask: a slice loads its own first chunk
+                    cph_map_slice sl;
+                    memcpy(&sl, p.value.data, sizeof sl);
+                    d.col = p.arg;
+                    d.from = sl.from;
+                    d.to = sl.to;
+                    if (!((slice_cols >> p.arg) & 1u) && !((plan.col_mask >> p.arg) & 1u)) {
+                        in_bytes += arg.c[p.arg].fixed_width ? 0.0 : (double)(arg.c[p.arg].offset_bits / 8);
+                        if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
+                    }
+                    slice_cols |= 1u << p.arg;
                 } else {   // INT64 / FLOAT64: 8 bytes per row
                     const void* vals = p.kind == CPH_MAP_INT64 ? static_cast<const void*>(p.ints) : static_cast<const void*>(p.floats);
                     in_bytes += 8.0;
@@ -210,6 +233,9 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                 CPH_HIP_TRY(hipMemsetAsync(offs + n + 1, 0xFF, sizeof(uint64_t), ctx->stream));
                 ProfScope ps(ctx, "k_map_lens", 0);
                 CPH_CSV_DISPATCH(k_map_lens_f64, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, offs);
+            } else if (has_slice) {
+                ProfScope ps(ctx, "k_map_lens_sl", 0);
+                CPH_CSV_DISPATCH(k_map_lens_sl, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, offs);
             } else {
                 ProfScope ps(ctx, "k_map_lens", 0);
                 CPH_CSV_DISPATCH(k_map_lens, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, offs);
@@ -240,9 +266,11 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
             }
             CPH_TRY(r->d_data.alloc(&ctx->pool, total + 16));
             if (total) {
-                ProfScope ps(ctx, "k_map_copy", 2.0 * (double)total + (8.0 + in_bytes) * (double)n);
+                ProfScope ps(ctx, has_slice && !has_float ? "k_map_copy_sl" : "k_map_copy", 2.0 * (double)total + (8.0 + in_bytes) * (double)n);
                 if (has_float) {
                     CPH_CSV_DISPATCH(k_map_copy_f64, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, offs, r->d_data.as<uint8_t>());
+                } else if (has_slice) {
+                    CPH_CSV_DISPATCH(k_map_copy_sl, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, offs, r->d_data.as<uint8_t>());
                 } else {
                     CPH_CSV_DISPATCH(k_map_copy, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, offs, r->d_data.as<uint8_t>());
                 }

@@ -12,7 +12,8 @@
 // may take different alternatives: every lane walks its own run [first[a], first[a + 1]) of the one flat piece array, so the
 // k-th pieces of two alternatives run together where they are of one kind and one after the other where they are not; the
 // stage sink ORs words into LDS, so no lane depends on another's progress and rows are not sorted by alternative.
-// A plan with a FLOAT64 piece runs float instantiations of both kernels, as map_format.hip does.
+// A plan with a FLOAT64 piece runs float instantiations of both kernels, as map_format.hip does, and one with a SLICE piece
+// but no FLOAT64 piece the slice instantiations (k_switch_lens_sl / k_switch_copy_sl).
 #include <new>
 #include <string>
 
@@ -32,9 +33,9 @@ struct SwitchPlan {   // travels in the kernel arguments (~1 KB beside ColsArg a
     MapPiece p[CPH_MAP_SWITCH_MAX_PIECES];
 };
 
-// which[i] = the alternative of row i, lens[i] = bytes of its value.  FL: lens[n + 1], preset to UINT64_MAX, = the lowest row
+// which[i] = the alternative of row i, lens[i] = bytes of its value.  PK == kPiecesFloat: lens[n + 1], preset to UINT64_MAX, = the lowest row
 // whose OWN alternative holds a value the float formatter refuses.
-template <int NC, bool FL = false>
+template <int NC, int PK = kPiecesBase>
 __global__ __launch_bounds__(kMatThreads) void k_switch_lens(ColsArg cols, ColIds ids, SwitchPlan plan, uint64_t n, uint8_t* __restrict__ which,
                                                             uint64_t* __restrict__ lens) {
     const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;   // a multiple of 64: a wave's rows share their bitmap words
@@ -53,32 +54,31 @@ __global__ __launch_bounds__(kMatThreads) void k_switch_lens(ColsArg cols, ColId
             const MapPiece& p = plan.p[k];
             if (p.kind == CPH_MAP_INT64) {
                 total += int_chars(p.ints[i]);
-            } else if (FL && p.kind == CPH_MAP_FLOAT64) {
+            } else if (PK == kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
                 const FixedParts r = fixed_split(p.floats[i], p.col);
                 total += fixed_chars(r, p.col);
                 if (r.kind == FIXED_RANGE) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
-            } else if (p.kind == CPH_MAP_COLUMN) {
-                uint64_t b, l, c0;
-                if constexpr (NC > 0) pick_field(f, p.col, &b, &l, &c0);
-                else value_span(cols.c[p.col], source_row(ids.ids[p.col], i), &b, &l);
-                total += l;
+            } else if (p.kind == CPH_MAP_COLUMN || (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE)) {
+                total += map_field_bytes<NC, PK>(cols, ids, p, f, i);
             }
         }
         lens[i] = total;
     }
 }
 template <int NC>
-constexpr auto k_switch_lens_f64 = k_switch_lens<NC, true>;
+constexpr auto k_switch_lens_f64 = k_switch_lens<NC, kPiecesFloat>;
+template <int NC>
+constexpr auto k_switch_lens_sl = k_switch_lens<NC, kPiecesSlice>;
 
 // row i's own run of pieces [first[a], first[a + 1]): the bounds and the piece index differ from lane to lane
-template <int NC, bool FL, class Sink>
+template <int NC, int PK, class Sink>
 __device__ __forceinline__ void switch_put_record(Sink& s, const ColsArg& cols, const ColIds& ids, const SwitchPlan& plan, int a,
                                                   const RecordFields<NC>& f, uint64_t i) {
-    map_put_record<NC, FL>(s, cols, ids, plan.lits, plan.p, plan.first[a], plan.first[a + 1], f, i);
+    map_put_record<NC, PK>(s, cols, ids, plan.lits, plan.p, plan.first[a], plan.first[a + 1], f, i);
 }
 
 // value i at out + offs[i]
-template <int NC, bool FL = false>
+template <int NC, int PK = kPiecesBase>
 __global__ __launch_bounds__(kMatThreads) void k_switch_copy(ColsArg cols, ColIds ids, SwitchPlan plan, uint64_t n, const uint8_t* __restrict__ which,
                                                             const uint64_t* __restrict__ offs, uint8_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -102,11 +102,11 @@ __global__ __launch_bounds__(kMatThreads) void k_switch_copy(ColsArg cols, ColId
             const int a = which[i];
             if (staged) {
                 WordSink s(reinterpret_cast<uint32_t*>(smem), (uint32_t)((offs[i] - obase) + (obase & 15)));
-                switch_put_record<NC, FL>(s, cols, ids, plan, a, f, i);
+                switch_put_record<NC, PK>(s, cols, ids, plan, a, f, i);
                 s.finish();
             } else {
                 GlobalSink s{out + offs[i]};
-                switch_put_record<NC, FL>(s, cols, ids, plan, a, f, i);
+                switch_put_record<NC, PK>(s, cols, ids, plan, a, f, i);
             }
         }
         if (staged) {
@@ -117,7 +117,9 @@ __global__ __launch_bounds__(kMatThreads) void k_switch_copy(ColsArg cols, ColId
     }
 }
 template <int NC>
-constexpr auto k_switch_copy_f64 = k_switch_copy<NC, true>;
+constexpr auto k_switch_copy_f64 = k_switch_copy<NC, kPiecesFloat>;
+template <int NC>
+constexpr auto k_switch_copy_sl = k_switch_copy<NC, kPiecesSlice>;
 
 }  // namespace cph
 
@@ -129,7 +131,7 @@ std::string alt_name(int a, int ncases) { return a < ncases ? "case " + std::to_
 
 // the rules of cph_map_format for the pieces of one alternative
 Status check_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t ncols, uint64_t n, const std::string& who, uint64_t* lit_bytes,
-                    bool* has_float) {
+                    bool* has_float, bool* has_slice) {
     for (int k = 0; k < npieces; k++) {
         const cph_map_piece& p = pieces[k];
         const std::string at = "cph_map_switch: " + who + ", piece " + std::to_string(k) + ": ";
@@ -152,8 +154,14 @@ Status check_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t ncols,
                 if (p.prec < 0 || p.prec > kFixedMaxPrec) return {CPH_ERR_INVALID, at + "prec of a FLOAT64 piece outside 0..22"};
                 *has_float = true;
                 break;
+            case CPH_MAP_SLICE:
+                if (p.arg < 0 || p.arg >= ncols) return {CPH_ERR_INVALID, at + "a SLICE piece's column outside 0..ncols-1"};
+                if (!p.value.data || p.value.len != sizeof(cph_map_slice))
+                    return {CPH_ERR_INVALID, at + "a SLICE piece's value is exactly 16 bytes (a cph_map_slice) behind a non-NULL pointer"};
+                *has_slice = true;
+                break;
             default:
-                return {CPH_ERR_INVALID, at + "unknown piece kind (1..4)"};
+                return {CPH_ERR_INVALID, at + "unknown piece kind (1..4, 8)"};
         }
     }
     return {};
@@ -190,14 +198,14 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
     const uint64_t n = nrows;
     if (n > 0xFFFFFFFFull) return fail_with(ctx, {CPH_ERR_TOO_MANY_ROWS, "cph_map_switch: more than 2^32-1 rows in one call"});
     uint64_t lit_bytes = 0;
-    bool has_float = false;
+    bool has_float = false, has_slice = false;
     for (int a = 0; a <= ncases; a++) {
         if (a < ncases) {
             Status s = check_pred_program(cases[a].prog, cases[a].nops, ncols);
             if (!s.ok()) return fail_with(ctx, {s.code, "cph_map_switch: case " + std::to_string(a) + ": " + s.msg});
         }
         Status s = check_pieces(a < ncases ? cases[a].pieces : otherwise, a < ncases ? cases[a].npieces : notherwise, ncols, n,
-                                alt_name(a, ncases), &lit_bytes, &has_float);
+                                alt_name(a, ncases), &lit_bytes, &has_float, &has_slice);
         if (!s.ok()) return fail_with(ctx, s);
     }
     {
@@ -236,6 +244,7 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         // the alternatives' pieces in one flat array, their literals in one block
         std::string lits;
         double in_bytes = 0;   // what the copy pass reads per row besides the value bytes and the alternative
+        uint32_t slice_cols = 0;
         int np = 0;
         for (int a = 0; a <= ncases; a++) {
             const cph_map_piece* pieces = a < ncases ? cases[a].pieces : otherwise;
@@ -257,6 +266,17 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                         if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
                     }
                     plan.col_mask |= 1u << p.arg;
+                } else if (p.kind == CPH_MAP_SLICE) {   // not in col_mask: a slice loads its own first chunk
+                    cph_map_slice sl;
+                    memcpy(&sl, p.value.data, sizeof sl);
+                    d.col = p.arg;
+                    d.from = sl.from;
+                    d.to = sl.to;
+                    if (!((slice_cols >> p.arg) & 1u) && !((plan.col_mask >> p.arg) & 1u)) {
+                        in_bytes += arg.c[p.arg].fixed_width ? 0.0 : (double)(arg.c[p.arg].offset_bits / 8);
+                        if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
+                    }
+                    slice_cols |= 1u << p.arg;
                 } else {   // INT64 / FLOAT64: 8 bytes per row
                     const void* vals = p.kind == CPH_MAP_INT64 ? static_cast<const void*>(p.ints) : static_cast<const void*>(p.floats);
                     in_bytes += 8.0;
@@ -293,9 +313,11 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         uint64_t* offs = r->d_offs.as<uint64_t>();
         if (has_float) CPH_HIP_TRY(hipMemsetAsync(offs + n + 1, 0xFF, sizeof(uint64_t), ctx->stream));
         {
-            ProfScope ps(ctx, "k_switch_lens", (8.0 + 1.0 + (double)ncases / 8.0 + in_bytes) * (double)n);
+            ProfScope ps(ctx, has_slice && !has_float ? "k_switch_lens_sl" : "k_switch_lens", (8.0 + 1.0 + (double)ncases / 8.0 + in_bytes) * (double)n);
             if (has_float) {
                 CPH_CSV_DISPATCH(k_switch_lens_f64, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, which_dev, offs);
+            } else if (has_slice) {
+                CPH_CSV_DISPATCH(k_switch_lens_sl, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, which_dev, offs);
             } else {
                 CPH_CSV_DISPATCH(k_switch_lens, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, which_dev, offs);
             }
@@ -331,9 +353,12 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         }
         CPH_TRY(r->d_data.alloc(&ctx->pool, total + 16));
         if (total) {
-            ProfScope ps(ctx, "k_switch_copy", 2.0 * (double)total + (8.0 + 1.0 + in_bytes) * (double)n);
+            ProfScope ps(ctx, has_slice && !has_float ? "k_switch_copy_sl" : "k_switch_copy", 2.0 * (double)total + (8.0 + 1.0 + in_bytes) * (double)n);
             if (has_float) {
                 CPH_CSV_DISPATCH(k_switch_copy_f64, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, which_dev, offs,
+                                 r->d_data.as<uint8_t>());
+            } else if (has_slice) {
+                CPH_CSV_DISPATCH(k_switch_copy_sl, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, which_dev, offs,
                                  r->d_data.as<uint8_t>());
             } else {
                 CPH_CSV_DISPATCH(k_switch_copy, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, which_dev, offs,

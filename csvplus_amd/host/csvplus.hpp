@@ -239,9 +239,22 @@ inline std::string FormatFixed(double v, int prec) {
 
 class Pred {
 public:
-    enum Kind { kLike, kNot, kAll, kAny, kIntCmp, kFloatCmp };
+    enum Kind { kLike, kNot, kAll, kAny, kIntCmp, kFloatCmp, kStrCmp, kHasPrefix, kHasSuffix, kContains };
     bool operator()(const Row& row) const {
         switch (kind_) {
+            case kStrCmp:
+            case kHasPrefix:
+            case kHasSuffix:
+            case kContains: {   // byte operations, as Go's; a row without the column is false under every one of them, NE included
+                auto it = row.find(column_);
+                if (it == row.end()) return false;
+                const std::string& v = it->second;
+                if (kind_ == kStrCmp) return holds(v.compare(slit_), 0);   // char_traits<char>::compare: bytewise, unsigned, the shorter first
+                if (slit_.size() > v.size()) return false;
+                if (kind_ == kHasPrefix) return v.compare(0, slit_.size(), slit_) == 0;
+                if (kind_ == kHasSuffix) return v.compare(v.size() - slit_.size(), slit_.size(), slit_) == 0;
+                return v.find(slit_) != std::string::npos;
+            }
             case kIntCmp:
             case kFloatCmp: {   // a row without the column, or whose value does not convert, is false under every relation
                 auto it = row.find(column_);
@@ -276,6 +289,7 @@ public:
     const std::string& column() const { return column_; }
     Rel rel() const { return rel_; }
     const void* literal() const { return kind_ == kIntCmp ? (const void*)&ilit_ : (const void*)&flit_; }   // 8 bytes
+    const std::string& text() const { return slit_; }   // kStrCmp .. kContains: the literal's bytes
 
 private:
     template <class T>
@@ -291,7 +305,9 @@ private:
     }
     friend Pred IntCmp(std::string column, Rel rel, int64_t k);
     friend Pred FloatCmp(std::string column, Rel rel, double x);
-    std::string column_;
+    friend Pred StrCmp(std::string column, Rel rel, std::string literal);
+    friend Pred StrTest(Pred::Kind kind, std::string column, std::string literal);
+    std::string column_, slit_;
     Rel rel_ = EQ;
     int64_t ilit_ = 0;
     double flit_ = 0.0;
@@ -326,6 +342,27 @@ inline Pred FloatCmp(std::string column, Rel rel, double x) {
     p.flit_ = x;
     return p;
 }
+// Conditions that look INSIDE a string, as data: StrCmp("ts", GE, "2016-09") is `row["ts"] >= "2016-09"`, HasPrefix / HasSuffix /
+// Contains are strings.HasPrefix / HasSuffix / Contains — all byte operations.  On the device each of them also checks that the
+// row HAS the column (a staged presence flag), so one such term costs two of the 32 terms and its column two of the 16 columns.
+inline Pred StrCmp(std::string column, Rel rel, std::string literal) {
+    Pred p;
+    p.kind_ = Pred::kStrCmp;
+    p.column_ = std::move(column);
+    p.rel_ = rel;
+    p.slit_ = std::move(literal);
+    return p;
+}
+inline Pred StrTest(Pred::Kind kind, std::string column, std::string literal) {
+    Pred p;
+    p.kind_ = kind;
+    p.column_ = std::move(column);
+    p.slit_ = std::move(literal);
+    return p;
+}
+inline Pred HasPrefix(std::string column, std::string literal) { return StrTest(Pred::kHasPrefix, std::move(column), std::move(literal)); }
+inline Pred HasSuffix(std::string column, std::string literal) { return StrTest(Pred::kHasSuffix, std::move(column), std::move(literal)); }
+inline Pred Contains(std::string column, std::string literal) { return StrTest(Pred::kContains, std::move(column), std::move(literal)); }
 inline Pred Not(Pred q) {
     Pred p;
     p.kind_ = Pred::kNot;
@@ -556,8 +593,24 @@ struct Itoa {   // an int64 expression written as strconv.Itoa writes it
         if (expr->kind != CPH_NUM_INT64) throw Panic("Itoa() of a float64 expression (use Fixed, or Int)");
     }
 };
-struct Part {   // a literal, a column, a column as a fixed-precision number, or an expression's value
+// Substr(Col("ts"), 0, 10) is Go's `row["ts"][0:10]`: the bytes [from, to) of the column's value (of its default where the row
+// lacks the column).  Python's slice rules: a negative index counts from the end, both ends are clamped into the value, from >=
+// to gives "", to == INT64_MAX (the default) means "to the end".  One deviation from Go: an index out of range clamps, no panic.
+struct Substr {
+    Col col;
+    int64_t from, to;
+    Substr(Col c, int64_t f, int64_t t = INT64_MAX) : col(std::move(c)), from(f), to(t) {}
+    static std::string of(const std::string& v, int64_t from, int64_t to) {
+        const int64_t l = (int64_t)v.size();
+        const int64_t f = from < 0 ? (from + l < 0 ? 0 : from + l) : (from < l ? from : l);
+        const int64_t t = to < 0 ? (to + l < 0 ? 0 : to + l) : (to < l ? to : l);
+        return t > f ? v.substr((size_t)f, (size_t)(t - f)) : std::string();
+    }
+};
+struct Part {   // a literal, a column, a slice of a column, a column as a fixed-precision number, or an expression's value
     bool is_col = false;
+    bool is_slice = false;        // Substr: bytes [slice.from, slice.to) of the column
+    cph_map_slice slice{0, 0};
     std::string text;   // the literal's bytes
     Col col{""};
     int prec = -1;      // >= 0: Fixed
@@ -567,6 +620,7 @@ struct Part {   // a literal, a column, a column as a fixed-precision number, or
     Part(Col c) : is_col(true), col(std::move(c)) {}     // NOLINT
     Part(Fixed f) : is_col(!f.expr), col(std::move(f.col)), prec(f.prec), expr(std::move(f.expr)) {}   // NOLINT
     Part(Itoa i) : expr(std::move(i.expr)) {}            // NOLINT
+    Part(Substr s) : is_col(true), is_slice(true), slice{s.from, s.to}, col(std::move(s.col)) {}   // NOLINT
 };
 struct Format {
     std::vector<Part> parts;
@@ -599,6 +653,10 @@ struct Format {
             if (!v) {
                 *missing = p.col.name;
                 return false;
+            }
+            if (p.is_slice) {
+                *out += Substr::of(*v, p.slice.from, p.slice.to);
+                continue;
             }
             if (p.prec < 0) {
                 *out += *v;
@@ -765,10 +823,45 @@ inline bool allColumnsUnique(const std::vector<std::string>& columns) {
 struct PredProgram {
     std::vector<std::string> columns;   // distinct names, in order of first use
     std::vector<std::string> absent;    // per column
+    std::vector<int> flag_of;           // per column: -1, or this staged column is the PRESENCE FLAG of that column ("1" / "")
     std::vector<cph_pred_op> ops;       // literal pointers point into `pred`
     std::shared_ptr<const Pred> pred;
+    // what column c holds for `row` on the device
+    const std::string* value(size_t c, const Row& row) const {
+        static const std::string one("1"), none;
+        if (c < flag_of.size() && flag_of[c] >= 0) return row.find(columns[(size_t)flag_of[c]]) == row.end() ? &none : &one;
+        auto it = row.find(columns[c]);
+        return it == row.end() ? &absent[c] : &it->second;
+    }
+    size_t column(const std::string& name) {
+        size_t c = (size_t)(std::find(columns.begin(), columns.end(), name) - columns.begin());
+        if (c == columns.size()) {
+            columns.push_back(name);
+            absent.emplace_back();
+        }
+        flag_of.resize(columns.size(), -1);
+        return c;
+    }
     void emit(const Pred& p) {
         switch (p.kind()) {
+            case Pred::kStrCmp:
+            case Pred::kHasPrefix:
+            case Pred::kHasSuffix:
+            case Pred::kContains: {
+                // No `absent` value is false under all of these (NE wants it equal to the literal, LT above it, ...): the term is
+                // AND-ed with a presence flag, a staged column that holds "1" where the row has the column and "" where not.
+                const size_t c = column(p.column());
+                const size_t f = column(std::string("\0present\0", 9) + p.column());
+                flag_of[f] = (int)c;
+                const int32_t op = p.kind() == Pred::kStrCmp      ? (int32_t)CPH_PRED_STR_LT + (int32_t)p.rel()
+                                   : p.kind() == Pred::kHasPrefix ? (int32_t)CPH_PRED_HAS_PREFIX
+                                   : p.kind() == Pred::kHasSuffix ? (int32_t)CPH_PRED_HAS_SUFFIX
+                                                                  : (int32_t)CPH_PRED_CONTAINS;
+                ops.push_back(cph_pred_op{op, (int32_t)c, {reinterpret_cast<const uint8_t*>(p.text().data()), p.text().size()}});
+                ops.push_back(cph_pred_op{CPH_PRED_LIKE, (int32_t)f, {reinterpret_cast<const uint8_t*>("1"), 1}});
+                ops.push_back(cph_pred_op{CPH_PRED_ALL, 2, {nullptr, 0}});
+                break;
+            }
             case Pred::kLike:
                 for (const auto& kv : p.match()) {
                     size_t c = (size_t)(std::find(columns.begin(), columns.end(), kv.first) - columns.begin());
@@ -1506,8 +1599,7 @@ private:
         for (size_t c = 0; c < nc; c++) {
             vals[c].resize(n);
             for (size_t i = 0; i < n; i++) {
-                auto it = (*batch)[i].find(prog.columns[c]);
-                vals[c][i] = it == (*batch)[i].end() ? &prog.absent[c] : &it->second;   // see detail::PredProgram
+                vals[c][i] = prog.value(c, (*batch)[i]);   // see detail::PredProgram
             }
         }
         cph_rowlist* rl = nullptr;
@@ -1630,7 +1722,10 @@ private:
                 columns.push_back(p.col.name);
                 fallback.push_back(&p.col.fallback);
             }
-            pieces.push_back(cph_map_piece{CPH_MAP_COLUMN, (int32_t)c, {nullptr, 0}, nullptr});
+            if (p.is_slice)
+                pieces.push_back(cph_map_piece{CPH_MAP_SLICE, (int32_t)c, {reinterpret_cast<const uint8_t*>(&p.slice), sizeof p.slice}, nullptr});
+            else
+                pieces.push_back(cph_map_piece{CPH_MAP_COLUMN, (int32_t)c, {nullptr, 0}, nullptr});
         }
         const size_t nc = columns.size();
         std::vector<std::vector<const std::string*>> vals(nc);
@@ -1726,7 +1821,10 @@ private:
                     columns.push_back(p.col.name);
                     fallback.push_back(&p.col.fallback);
                 }
-                pieces[alt].push_back(cph_map_piece{CPH_MAP_COLUMN, (int32_t)c, {nullptr, 0}, nullptr});
+                if (p.is_slice)
+                    pieces[alt].push_back(cph_map_piece{CPH_MAP_SLICE, (int32_t)c, {reinterpret_cast<const uint8_t*>(&p.slice), sizeof p.slice}, nullptr});
+                else
+                    pieces[alt].push_back(cph_map_piece{CPH_MAP_COLUMN, (int32_t)c, {nullptr, 0}, nullptr});
             }
         }
         const size_t nc = columns.size();
@@ -1735,7 +1833,7 @@ private:
             vals[c].resize(n);
             for (size_t i = 0; i < n; i++) {
                 auto it = (*batch)[i].find(columns[c]);
-                vals[c][i] = it == (*batch)[i].end() ? fallback[c] : &it->second;
+                vals[c][i] = c < npred ? prog.value(c, (*batch)[i]) : it == (*batch)[i].end() ? fallback[c] : &it->second;
             }
         }
         std::vector<cph_map_case> cases(ncases);

@@ -7,6 +7,10 @@ the new column in row i is the concatenation of the template's parts —
     bytes / str          a literal (str: its UTF-8 bytes);
     Col("name")          the row's value of that column; Col("name", default=b"x") substitutes the default where the
                          rows have no such column (Row.SafeGetValue, csvplus.go:69-75);
+    Col("ts")[0:10]      a Slice: the bytes [from, to) of that value, Go's `row["ts"][:10]` — bytes, not runes.  The ends follow
+                         Python's slice rules (negative counts from the end, open ends, both clamped into the value, crossing
+                         ends give the empty string); one deviation from Go: an index out of range clamps instead of panicking.
+                         No step.  A Col with a default over a missing column slices the default;
     Int(array)           array[i] written as strconv.Itoa writes it ('-' for negatives, no '+', no leading zeros); the array
                          lives on the host, or on the device: Int.on_device(device_ptr, count);
     Float(array, prec)   array[i] written as strconv.FormatFloat(v, 'f', prec, 64) writes it: prec digits behind the point,
@@ -22,8 +26,8 @@ the new column in row i is the concatenation of the template's parts —
 
 `compile` turns a template into the piece list cph_map_format takes (include/csvplus_hip.h), `render` evaluates it on one
 row held as a dict — the host model, for callers without a GPU and as the cross-check of the device.  Nothing here
-touches the GPU.  FormatFloat's other forms (shortest round-trip digits, 'e' and 'g'), case mapping, trimming and
-substrings are out of scope.
+touches the GPU.  Out of scope: FormatFloat's other forms (shortest round-trip digits, 'e' and 'g'); case mapping and
+TrimSpace (Go's are Unicode-aware); splitting a value on a delimiter; regular expressions; timestamp parsing.
 
 A value that depends on a condition is a Switch — Go's `if / else if / else` inside the closure, as data:
 
@@ -46,7 +50,7 @@ import numpy as np
 from . import predicates as _P
 from .predicates import INT64_MAX, INT64_MIN, _bytes, _go_quote
 
-LITERAL, COLUMN, INT64, FLOAT64 = 1, 2, 3, 4   # CPH_MAP_*
+LITERAL, COLUMN, INT64, FLOAT64, SLICE = 1, 2, 3, 4, 8   # CPH_MAP_*
 MAX_PIECES = 16                    # CPH_MAP_MAX_PIECES
 MAX_CASES = 8                      # CPH_MAP_MAX_CASES
 SWITCH_MAX_PIECES = 32             # CPH_MAP_SWITCH_MAX_PIECES: the pieces of all alternatives together
@@ -72,6 +76,36 @@ class Col:
 
     def __repr__(self):
         return f"Col({self.name!r})" if self.default is None else f"Col({self.name!r}, default={self.default!r})"
+
+    def __getitem__(self, key) -> "Slice":
+        if not isinstance(key, slice) or key.step is not None:
+            raise TypeError(f"Col[...]: only a slice without a step, e.g. Col({self.name!r})[0:10], not {key!r}")
+        return Slice(self, key.start, key.stop)
+
+
+class Slice:
+    """Slice(col, start, stop) = col[start:stop]: the bytes [start, stop) of the column's value under Python's slice rules.
+    None is an open end; `to` travels as INT64_MAX ("to the end")."""
+
+    def __init__(self, col, start=None, stop=None):
+        if not isinstance(col, Col):
+            raise TypeError(f"Slice: not a Col: {col!r}")
+        for v in (start, stop):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not INT64_MIN <= int(v) <= INT64_MAX):
+                raise TypeError(f"Slice: an end is an int64 or None, not {v!r}")
+        self.col = col
+        self.start = 0 if start is None else int(start)
+        self.stop = INT64_MAX if stop is None else int(stop)
+
+    @property
+    def name(self):
+        return self.col.name
+
+    def apply(self, value: bytes) -> bytes:
+        return value[self.start:(None if self.stop == INT64_MAX else self.stop)]
+
+    def __repr__(self):
+        return f"{self.col!r}[{self.start or ''}:{'' if self.stop == INT64_MAX else self.stop}]"
 
 
 class Int:
@@ -166,12 +200,12 @@ class Format:
             raise ValueError("Format: no parts")
         self.parts = []
         for p in parts:
-            if isinstance(p, (Col, Int, Float)):
+            if isinstance(p, (Col, Slice, Int, Float)):
                 self.parts.append(p)
             elif isinstance(p, (bytes, bytearray, memoryview, str)):
                 self.parts.append(_bytes(p))
             else:
-                raise TypeError(f"not a template part: {p!r} (closures cannot run on the device; use bytes / str, Col, Int, Float)")
+                raise TypeError(f"not a template part: {p!r} (closures cannot run on the device; use bytes / str, Col, Col[a:b], Int, Float)")
 
     def __repr__(self):
         return f"Format{tuple(self.parts)!r}"
@@ -217,7 +251,7 @@ def _template(t) -> Format:
         return t
     if isinstance(t, Switch):
         raise TypeError("a Switch stands where a whole template stands: it is no part of a Format and does not nest")
-    if isinstance(t, (Col, Int, Float, bytes, bytearray, memoryview, str)):
+    if isinstance(t, (Col, Slice, Int, Float, bytes, bytearray, memoryview, str)):
         return Format(t)
     raise TypeError(f"not a template: {t!r}")
 
@@ -225,7 +259,7 @@ def _template(t) -> Format:
 def _pred_columns(pred) -> list:
     if isinstance(pred, _P.Like):
         return [name for name, _ in pred.items]
-    if isinstance(pred, _P._NumCmp):
+    if isinstance(pred, (_P._NumCmp, _P.StrCmp, _P._StrTest)):
         return [pred.column]
     if isinstance(pred, _P.Not):
         return _pred_columns(pred.pred)
@@ -245,7 +279,7 @@ def columns(template) -> list:
                     names.append(name)
         return names
     for p in _template(template).parts:
-        if isinstance(p, Col):
+        if isinstance(p, (Col, Slice)):
             found = [p.name]
         elif isinstance(p, (Int, Float)) and p.expr is not None:
             from . import expr as E
@@ -260,7 +294,7 @@ def columns(template) -> list:
 
 def compile(template, column_names):   # noqa: A001 (the name predicates.compile uses)
     """(names of the columns used, pieces).  A piece is (LITERAL, 0, bytes), (COLUMN, k, None) with k indexing the returned
-    name list, (INT64, 0, Int) or (FLOAT64, 0, Float).  A Col whose name is not among `column_names` becomes its default as a literal — in
+    name list, (SLICE, k, (from, to)), (INT64, 0, Int) or (FLOAT64, 0, Float).  A Col (or the Col of a Slice) whose name is not among `column_names` becomes its default as a literal — in
     structure-of-arrays a column is present for all rows or for none — and without a default raises MissingColumn.
     Neighbouring literals are joined.  Raises ValueError beyond the ABI's limits (16 pieces, 16 columns)."""
     known = [str(c) for c in column_names]
@@ -283,8 +317,13 @@ def compile(template, column_names):   # noqa: A001 (the name predicates.compile
         elif p.name in known:
             if p.name not in used:
                 used.append(p.name)
-            pieces.append((COLUMN, used.index(p.name), None))
-        elif p.default is not None:
+            if isinstance(p, Slice):
+                pieces.append((SLICE, used.index(p.name), (p.start, p.stop)))
+            else:
+                pieces.append((COLUMN, used.index(p.name), None))
+        elif isinstance(p, Slice) and p.col.default is not None:   # the default, sliced on the host
+            literal(p.apply(p.col.default))
+        elif isinstance(p, Col) and p.default is not None:
             literal(p.default)
         else:
             raise MissingColumn(p.name)
@@ -315,7 +354,7 @@ def compile_switch(switch, column_names):
 
     def alternative(tmpl):
         used, pieces = compile(tmpl, known)
-        return [(kind, index_of(used[arg]), v) if kind == COLUMN else (kind, arg, v) for kind, arg, v in pieces]
+        return [(kind, index_of(used[arg]), v) if kind in (COLUMN, SLICE) else (kind, arg, v) for kind, arg, v in pieces]
 
     cases = []
     for pred, tmpl in switch.cases:
@@ -395,12 +434,13 @@ def render(template, row, i: int = 0) -> bytes:
                 raise ValueError("render: a Float part on the device has no host values")
             out.append(ftoa(p.values[i], p.prec))
         else:
-            v = row.get(p.name)
+            col = p.col if isinstance(p, Slice) else p
+            v = row.get(col.name)
             if v is None:
-                v = row.get(p.name.encode("utf-8"))
+                v = row.get(col.name.encode("utf-8"))
             if v is None:
-                if p.default is None:
-                    raise MissingColumn(p.name)
-                v = p.default
-            out.append(_bytes(v))
+                if col.default is None:
+                    raise MissingColumn(col.name)
+                v = col.default
+            out.append(p.apply(_bytes(v)) if isinstance(p, Slice) else _bytes(v))
     return b"".join(out)

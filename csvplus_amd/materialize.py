@@ -568,6 +568,12 @@ def _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending=
             parr[k].value.len = len(b)
         elif kind == M.COLUMN:
             parr[k].arg = arg
+        elif kind == M.SLICE:   # value: a cph_map_slice {from, to}, 16 bytes
+            b = np.array(value, dtype=np.int64)
+            keep.append(b)
+            parr[k].arg = arg
+            parr[k].value.data = b.ctypes.data
+            parr[k].value.len = 16
         else:
             if value.expr is not None:   # evaluated over the same rows into a device array: cph_num_eval
                 nc = eval_number(ctx, cols_by_name, value.expr, row_ids=row_ids, nrows=n, out_mem=N.CPH_MEM_DEVICE)

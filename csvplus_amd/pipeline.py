@@ -59,10 +59,10 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
     order costs ~0.3 ms per 1e7 table rows, reporting positions saves ~1.0 ms per 1e8 stream rows, so a one-shot pipeline
     whose stream is only a few times longer than its build tables keeps row ids.
     where / skip / limit: Join(...).Filter(where).Drop(skip).Top(limit) in front of the writer — `where` is a predicate of
-    csvplus_amd.predicates (Like, All, Any, Not) over the JOINED row: a name is looked up in the stream first, then in
+    csvplus_amd.predicates (Like, All, Any, Not, IntCmp, FloatCmp, StrCmp, HasPrefix, HasSuffix, Contains) over the JOINED row: a name is looked up in the stream first, then in
     steps[0]'s table, steps[1]'s, ... (mergeRows: the stream's value wins); a name none of them has makes its Like false.
     computed: {name: template} — ...Map(row[name] = template(row)) behind the filter, one template of csvplus_amd.mapping
-    (Format, Const) per new column, applied in dict order over the joined rows that are left: a Col is looked up among the
+    (Format, Const, Switch; parts may be slices, Col("ts")[0:10]) per new column, applied in dict order over the joined rows that are left: a Col is looked up among the
     columns computed so far, then in the joined row as `where` does.  An out_columns entry whose output name is a computed
     name takes the computed column (its table and column are ignored and may be None): `row[name] = ...` replaces a source
     column of that name.  A Float.of / Int.of part computes its value from an expression of csvplus_amd.expr over the same

@@ -1,6 +1,8 @@
 """The reference's named predicates as plain data (csvplus.go:1243-1293): Like, All, Any, Not — and the numeric
 conditions its users write as closures over Row.ValueAsInt / ValueAsFloat64 (csvplus.go:165-205, csvplus_test.go:272-281):
-IntCmp, FloatCmp.
+IntCmp, FloatCmp — and the conditions that look inside a string (`row["ts"] >= "2016-09"`, strings.HasPrefix / HasSuffix /
+Contains): StrCmp, HasPrefix, HasSuffix, Contains.  Those are byte operations in Go; Python's bytes comparison, startswith,
+endswith and `in` are their exact host model.
 
 A Go closure cannot run on a GPU; these are declarative and can.  `compile` flattens any nesting of them into the
 postfix program cph_filter_rows takes (include/csvplus_hip.h), `matches` evaluates a predicate on one row held as a dict —
@@ -16,6 +18,8 @@ import struct
 
 LIKE, NOT, ALL, ANY = 1, 2, 3, 4   # CPH_PRED_*
 INT_LT, FLT_LT = 16, 24            # CPH_PRED_INT_LT / CPH_PRED_FLT_LT; + the relation's index in RELS
+STR_LT = 32                        # CPH_PRED_STR_LT; + the relation's index in RELS
+HAS_PREFIX, HAS_SUFFIX, CONTAINS = 40, 41, 42   # CPH_PRED_*
 RELS = ("<", "<=", "==", "!=", ">=", ">")
 MAX_OPS, MAX_LIKE, MAX_STACK = 64, 32, 32
 NUM_OK, NUM_ERR_SYNTAX, NUM_ERR_RANGE, NUM_ERR_UNSUPPORTED = 0, 1, 2, 3   # CPH_NUM_*
@@ -107,10 +111,50 @@ class FloatCmp(_NumCmp):
         super().__init__(column, rel, float(x))
 
 
+class StrCmp(Pred):
+    """StrCmp("ts", ">=", "2016-09"): `row[column] REL literal`, Go's string comparison: bytewise and unsigned, the shorter
+    of two values that agree on the common prefix is the smaller ("10" < "9", "a" < "a\0").  A row that lacks the column
+    is false under every relation, "!=" included."""
+
+    def __init__(self, column, rel, literal):
+        if rel not in RELS:
+            raise ValueError(f"unknown relation {rel!r}: one of {' '.join(RELS)}")
+        self.column, self.rel, self.literal = str(column), rel, _bytes(literal)
+
+    def __repr__(self):
+        return f"StrCmp({self.column!r}, {self.rel!r}, {self.literal!r})"
+
+
+class _StrTest(Pred):
+    op = None
+
+    def __init__(self, column, literal):
+        self.column, self.literal = str(column), _bytes(literal)
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.column!r}, {self.literal!r})"
+
+
+class HasPrefix(_StrTest):
+    """HasPrefix("ts", "2016-09-14"): strings.HasPrefix(row[column], literal), on bytes.  The empty literal holds for
+    every present value; a row that lacks the column is false."""
+    op = HAS_PREFIX
+
+
+class HasSuffix(_StrTest):
+    """HasSuffix("ts", "+01:00"): strings.HasSuffix(row[column], literal), on bytes."""
+    op = HAS_SUFFIX
+
+
+class Contains(_StrTest):
+    """Contains("surname", "Smith"): strings.Contains(row[column], literal), on bytes."""
+    op = CONTAINS
+
+
 def _operands(preds):
     for p in preds:
         if not isinstance(p, Pred):
-            raise TypeError(f"not a predicate: {p!r} (closures cannot run on the device; use Like / All / Any / Not / IntCmp / FloatCmp)")
+            raise TypeError(f"not a predicate: {p!r} (closures cannot run on the device; use Like / All / Any / Not / IntCmp / FloatCmp / StrCmp / HasPrefix / HasSuffix / Contains)")
     return list(preds)
 
 
@@ -236,6 +280,22 @@ def _cmp(rel, a, b) -> bool:
     return {"<": a < b, "<=": a <= b, "==": a == b, "!=": a != b, ">=": a >= b, ">": a > b}[rel]
 
 
+def _str_holds(op, value, literal) -> bool:
+    """One string term (STR_LT + relation, HAS_PREFIX, HAS_SUFFIX, CONTAINS) on a present value: Python's bytes operations."""
+    v = _bytes(value)
+    if op == HAS_PREFIX:
+        return v.startswith(literal)
+    if op == HAS_SUFFIX:
+        return v.endswith(literal)
+    if op == CONTAINS:
+        return literal in v
+    return _cmp(RELS[op - STR_LT], v, literal)
+
+
+def _is_str_op(op) -> bool:
+    return STR_LT <= op < STR_LT + len(RELS) or op in (HAS_PREFIX, HAS_SUFFIX, CONTAINS)
+
+
 def _num_holds(is_float, rel, value, literal) -> bool:
     v, kind = parse_float(value) if is_float else atoi(value)
     return kind == NUM_OK and _cmp(rel, v, literal)
@@ -243,7 +303,9 @@ def _num_holds(is_float, rel, value, literal) -> bool:
 
 def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of record uses)
     """(names of the columns used, postfix ops).  An op is (LIKE, column, value bytes) with `column` indexing the returned
-    name list, or -1 for a name that is not among `column_names` (the row has no such column: false, :1286); (NOT, 0, None);
+    name list, or -1 for a name that is not among `column_names` (the row has no such column: false, :1286); a numeric term
+    (INT_LT / FLT_LT + relation, column, 8 literal bytes); a string term (STR_LT + relation / HAS_PREFIX / HAS_SUFFIX /
+    CONTAINS, column, literal bytes); (NOT, 0, None);
     (ALL, k, None); (ANY, k, None).  Raises ValueError beyond the ABI's limits (64 ops, 32 LIKE terms, stack of 32)."""
     known = [str(c) for c in column_names]
     used: list[str] = []
@@ -270,6 +332,14 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
                 if p.column not in used:
                     used.append(p.column)
                 ops.append((op, used.index(p.column), lit))
+        elif isinstance(p, (StrCmp, _StrTest)):
+            op = STR_LT + RELS.index(p.rel) if isinstance(p, StrCmp) else p.op
+            if p.column not in known:
+                ops.append((op, -1, p.literal))
+            else:
+                if p.column not in used:
+                    used.append(p.column)
+                ops.append((op, used.index(p.column), p.literal))
         elif isinstance(p, Not):
             emit(p.pred)
             ops.append((NOT, 0, None))
@@ -293,7 +363,7 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
     if len(ops) > MAX_OPS:
         raise ValueError(f"predicate compiles to {len(ops)} ops, more than {MAX_OPS}")
     if likes > MAX_LIKE:
-        raise ValueError(f"predicate has {likes} Like and numeric terms, more than {MAX_LIKE}")
+        raise ValueError(f"predicate has {likes} Like, numeric and string terms, more than {MAX_LIKE}")
     return used, ops
 
 
@@ -312,6 +382,12 @@ def matches(pred: Pred, row) -> bool:
         if v is None:
             v = row.get(pred.column.encode("utf-8"))
         return v is not None and _num_holds(isinstance(pred, FloatCmp), pred.rel, v, pred.literal)
+    if isinstance(pred, (StrCmp, _StrTest)):
+        v = row.get(pred.column)
+        if v is None:
+            v = row.get(pred.column.encode("utf-8"))
+        op = STR_LT + RELS.index(pred.rel) if isinstance(pred, StrCmp) else pred.op
+        return v is not None and _str_holds(op, v, pred.literal)
     if isinstance(pred, Not):
         return not matches(pred.pred, row)
     if isinstance(pred, All):
@@ -327,6 +403,8 @@ def run_ops(ops, values) -> bool:
     for op, arg, value in ops:
         if op == LIKE:
             st.append(arg >= 0 and _bytes(values[arg]) == value)
+        elif _is_str_op(op):
+            st.append(arg >= 0 and _str_holds(op, values[arg], value))
         elif op >= INT_LT:
             flt = op >= FLT_LT
             (lit,) = struct.unpack("<d" if flt else "<q", value)

@@ -712,18 +712,41 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
  * cph_col_to_number converts it; a row that does NOT convert (syntax, range, unsupported) pushes FALSE under every
  * relation, NE included — what the reference's closure does with the error — and arg = -1 (no such column) pushes false.
  * Float relations are IEEE: with a NaN on either side only NE holds.  A numeric term counts against CPH_PRED_MAX_LIKE
- * like a LIKE term (LIKE plus numeric terms <= 32).  Ops 0, 5..15, 22, 23 and 30.. are invalid.
+ * like a LIKE term.
+ *
+ * String terms that look INSIDE a value — `row["ts"] >= "2016-09"`, `strings.HasPrefix(row["ts"], "2016-09-14")`,
+ * `strings.Contains(row["surname"], "Smith")` as data:
+ *   CPH_PRED_STR_LT .. CPH_PRED_STR_GT (32..37, in the order LT LE EQ NE GE GT)   push strings.Compare(value of column `arg`, literal) REL 0
+ *   CPH_PRED_HAS_PREFIX (40)   push strings.HasPrefix(value, literal)
+ *   CPH_PRED_HAS_SUFFIX (41)   push strings.HasSuffix(value, literal)
+ *   CPH_PRED_CONTAINS   (42)   push strings.Contains(value, literal)
+ * `arg` is the column and `value` the literal's bytes exactly as for CPH_PRED_LIKE: host memory, any length below 4 GiB, any
+ * byte values, a NULL pointer allowed with len == 0.  These are BYTE operations, as in Go.  Compare is bytewise and unsigned
+ * ("\x7f" < "\x80", "10" < "9"), and of two values that agree on their common prefix the shorter is the smaller ("a" <
+ * "a\0").  An empty literal holds for every present value under PREFIX / SUFFIX / CONTAINS, the empty value included; a
+ * literal longer than the value fails all three.  arg = -1 (no such column) pushes FALSE under every one of the nine ops, NE
+ * included — the rule of LIKE and of the numeric terms.  CONTAINS is a per-row search whose worst case is quadratic in the
+ * value's length (a value that repeats the literal's first byte and mismatches late).
+ *
+ * Every LIKE, numeric and string term counts against CPH_PRED_MAX_LIKE (32 terms in all).  The valid ops are 1..4, 16..21,
+ * 24..29, 32..37 and 40..42; every other op (0, 5..15, 22, 23, 30, 31, 38, 39, 43..) is invalid.
+ *
+ * Out of scope for a condition: comparing a column against ANOTHER COLUMN; case mapping and TrimSpace (Go's are
+ * Unicode-aware: a project of their own); splitting on a delimiter; regular expressions; parsing a timestamp (an RFC3339
+ * column in one zone orders as its bytes do, which is what the compare ops give).
  */
 enum { CPH_PRED_LIKE = 1, CPH_PRED_NOT = 2, CPH_PRED_ALL = 3, CPH_PRED_ANY = 4 };
 enum { CPH_PRED_INT_LT = 16, CPH_PRED_INT_LE = 17, CPH_PRED_INT_EQ = 18, CPH_PRED_INT_NE = 19, CPH_PRED_INT_GE = 20, CPH_PRED_INT_GT = 21 };
 enum { CPH_PRED_FLT_LT = 24, CPH_PRED_FLT_LE = 25, CPH_PRED_FLT_EQ = 26, CPH_PRED_FLT_NE = 27, CPH_PRED_FLT_GE = 28, CPH_PRED_FLT_GT = 29 };
+enum { CPH_PRED_STR_LT = 32, CPH_PRED_STR_LE = 33, CPH_PRED_STR_EQ = 34, CPH_PRED_STR_NE = 35, CPH_PRED_STR_GE = 36, CPH_PRED_STR_GT = 37 };
+enum { CPH_PRED_HAS_PREFIX = 40, CPH_PRED_HAS_SUFFIX = 41, CPH_PRED_CONTAINS = 42 };
 #define CPH_PRED_MAX_OPS   64
 #define CPH_PRED_MAX_LIKE  32
 #define CPH_PRED_MAX_STACK 32
 typedef struct {
     int32_t    op;      /* CPH_PRED_* */
-    int32_t    arg;     /* LIKE / INT_* / FLT_*: column (index into cols) or -1; ALL / ANY: operand count; NOT: ignored */
-    cph_strval value;   /* LIKE: the literal's bytes; INT_* / FLT_*: 8 bytes, an int64_t / a double; host memory */
+    int32_t    arg;     /* LIKE / INT_* / FLT_* / STR_* / HAS_* / CONTAINS: column (index into cols) or -1; ALL / ANY: operand count; NOT: ignored */
+    cph_strval value;   /* LIKE / STR_* / HAS_* / CONTAINS: the literal's bytes; INT_* / FLT_*: 8 bytes, an int64_t / a double; host memory */
 } cph_pred_op;
 
 enum { CPH_FILTER_WHERE = 0, CPH_FILTER_TAKE_WHILE = 1, CPH_FILTER_DROP_WHILE = 2 };
@@ -759,7 +782,8 @@ typedef struct {
  * its two kernels.  The result is complete when the call returns (the other calls' rule).
  *
  * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / prog / opts / out, cols NULL with ncols > 0, nops outside
- * 1..CPH_PRED_MAX_OPS, an unknown op, a LIKE / numeric column outside -1..ncols-1, a LIKE value with a length but no pointer,
+ * 1..CPH_PRED_MAX_OPS, an unknown op, a LIKE / numeric / string-term column outside -1..ncols-1, a LIKE or string-term value
+ * with a length but no pointer, a string-term literal of 4 GiB or more,
  * a numeric literal that is not exactly 8 bytes behind a non-NULL pointer,
  * a negative or too large ALL / ANY count (stack underflow), a NOT on an empty stack, a program that does not leave
  * exactly one value, the limits above, out_bits or row-id bits other than 32 / 64, an unknown mode or out_mem, a short
@@ -921,6 +945,11 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  *                    (infinities and NaN are not such values).  Inside both limits the digits are exact with 128-bit
  *                    integer arithmetic (the integer part is below 2^128, the scaled fraction below 2^53 * 10^22 < 2^127);
  *                    outside them the exact decimal digits need a big-number loop, which this does not have.
+ *   CPH_MAP_SLICE    the bytes [from, to) of the value of column `arg` in row i — Go's `row["ts"][:10]`.  `value` points at
+ *                    exactly 16 host bytes, a cph_map_slice {from, to}.  Python's slice rules: a negative index counts from
+ *                    the value's end, both ends are then clamped into [0, len], from >= to gives the empty string, and
+ *                    to == INT64_MAX means "to the end".  Bytes, not runes, as in Go.  One deviation: where Go panics on an
+ *                    index out of range, this clamps.
  * All bytes are copied verbatim (NUL and bytes >= 0x80 included); nothing is escaped.
  *
  * cols / sel / nrows mean exactly what they mean for cph_csv_write_rows (host or device columns, fixed-width or 32 / 64-bit
@@ -933,21 +962,25 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  * legal and yields an empty column.
  *
  * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / pieces / out, npieces outside 1..CPH_MAP_MAX_PIECES, an
- * unknown kind, a COLUMN index outside 0..ncols-1 (a column the rows lack is the host's business: it substitutes a literal
- * or reports the reference's missing-column error), a literal with a length but no pointer, an INT64 piece with ints ==
+ * unknown kind (5..7 included), a COLUMN or SLICE index outside 0..ncols-1 (a column the rows lack is the host's business:
+ * it substitutes a literal or reports the reference's missing-column error), a SLICE whose value is not exactly 16 bytes
+ * behind a non-NULL pointer, a literal with a length but no pointer, an INT64 piece with ints ==
  * NULL while nrows > 0 or with an unknown memory space, a FLOAT64 piece with floats == NULL while nrows > 0, with an unknown
  * memory space or with prec outside 0..22, a FLOAT64 value beyond the range above (found while the call runs), ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
  * than 32 / 64, an identity column whose row count is not nrows, an unknown out_mem.
  *
  * Out of scope: the other forms of FormatFloat — the shortest round-trip digits (prec -1) and the 'e' / 'g' formats, a
- * project of their own —, case mapping, trimming, substrings.  A value that depends on a condition is cph_map_switch's.
+ * project of their own —; case mapping and TrimSpace (Go's are Unicode-aware: a project of their own); splitting a value
+ * on a delimiter; regular expressions; timestamp parsing; a slice whose ends come from another column.  A value that
+ * depends on a condition is cph_map_switch's.
  */
-enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4 };
+enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4, CPH_MAP_SLICE = 8 };   /* 5..7: invalid */
 #define CPH_MAP_MAX_PIECES 16
+typedef struct { int64_t from, to; } cph_map_slice;   /* what a SLICE piece's `value` points at: 16 bytes */
 typedef struct {
     int32_t        kind;    /* CPH_MAP_* */
-    int32_t        arg;     /* COLUMN: index into cols; INT64 / FLOAT64: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
-    cph_strval     value;   /* LITERAL: its bytes (host memory, any length, any byte values) */
+    int32_t        arg;     /* COLUMN / SLICE: index into cols; INT64 / FLOAT64: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
+    cph_strval     value;   /* LITERAL: its bytes (host memory, any length, any byte values); SLICE: a cph_map_slice, len == 16 */
     const int64_t* ints;    /* INT64: nrows values, entry i belongs to OUTPUT row i (no row ids) */
     const double*  floats;  /* FLOAT64: likewise */
     int32_t        prec;    /* FLOAT64: digits behind the point, 0..22 */
@@ -974,7 +1007,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  *
  * Selection.  Row i takes the alternative a = the lowest case index whose program holds, or ncases (`otherwise`) if none
  * does.  Its value is that alternative's pieces rendered exactly as cph_map_format renders them (LITERAL / COLUMN / INT64 /
- * FLOAT64; verbatim bytes; FormatInt and FormatFloat 'f' rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
+ * FLOAT64 / SLICE; verbatim bytes; FormatInt and FormatFloat 'f' rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
  * memory, written when the call succeeds).
  *
  * Number pieces.  INT64 / FLOAT64 arrays have nrows entries indexed by OUTPUT row.  Entries of rows that select ANOTHER
@@ -991,8 +1024,9 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  * cph_map_format rejects in a piece or in the row sources.  CPH_ERR_TOO_MANY_ROWS for nrows > 2^32 - 1 (the predicate
  * evaluator's limit).
  *
- * Out of scope: nested switches; a conditional part inside a template (use one Switch over whole templates); case mapping,
- * trimming and substrings; the other forms of FormatFloat.
+ * Out of scope: nested switches; a conditional part inside a template (use one Switch over whole templates); a condition
+ * that compares a column against another column; case mapping and TrimSpace; splitting on a delimiter; regular expressions;
+ * timestamp parsing; the other forms of FormatFloat.
  */
 #define CPH_MAP_MAX_CASES         8
 #define CPH_MAP_SWITCH_MAX_PIECES 32      /* the pieces of all alternatives together */
