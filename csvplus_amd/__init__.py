@@ -15,6 +15,8 @@ totals_model),
 materialize.validate_rows),
 `expr` (numeric expressions as plain data — IntCol, FloatCol, IntArr, FloatArr, ToFloat, ToInt and + - * / % with Go's
 arithmetic — evaluated per row on the device: materialize.eval_number, mapping.Float.of / Int.of, aggregate.Sum(expr)),
+`ordering` (OrderBy as plain data — Asc, Desc over int / float / bytes keys — sorted on the device with Top-N select:
+materialize.order_rows; the contract in pure Python: order_model),
 `pipeline` (CSV -> indices -> chained join -> CSV or JSON, all in HBM), `datagen` (deterministic synthetic tables).
 """
 from . import _native as native  # noqa: F401

@@ -272,6 +272,20 @@ class cph_chain_aggregated(C.Structure):
                 ("first_error_kind", C.c_int32), ("first_error_spec", C.c_int32)]
 
 
+CPH_ORDER_MAX_KEYS = 8
+
+
+class cph_order_key(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("descending", C.c_int32), ("values", C.c_void_p), ("status", C.c_void_p),
+                ("values_mem", C.c_int32), ("reserved_", C.c_int32), ("index", C.c_void_p)]
+
+
+class cph_ordered(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("ids", C.c_void_p), ("mem", C.c_int32), ("select_used", C.c_int32),
+                ("candidates", C.c_uint64), ("nerrors", C.c_uint64), ("first_error_row", C.c_uint64),
+                ("first_error_kind", C.c_int32), ("first_error_key", C.c_int32)]
+
+
 CPH_DIST_ID_BYTES = 128
 CPH_MAX_GATHER = 8
 
@@ -408,6 +422,9 @@ PROTOTYPES = [
      [_P, C.POINTER(cph_chain), C.c_int32, _P, C.POINTER(cph_chain_agg_spec), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_chain_aggregated))]),
     ("cph_chain_aggregated_release", None, [C.POINTER(cph_chain_aggregated)]),
+    ("cph_order_rows", C.c_int32,
+     [_P, C.POINTER(cph_order_key), C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(C.POINTER(cph_ordered))]),
+    ("cph_ordered_release", None, [C.POINTER(cph_ordered)]),
     ("cph_index_save", C.c_int32, [_P, _P, C.c_char_p]),
     ("cph_index_load", C.c_int32, [_P, C.c_char_p, C.POINTER(_P)]),
     ("cph_index_find", C.c_int32,

@@ -574,6 +574,7 @@ CPH_API int32_t cph_ctx_create(int32_t device_id, cph_ctx** out) {
     warm_resolve();
     warm_aggregate();
     warm_join_totals();
+    warm_order();
     warm_small_build();
     warm_window_sort();
     warm_counted_sort();
@@ -637,6 +638,7 @@ CPH_API int32_t cph_ctx_set_option(cph_ctx* ctx, const char* name, int64_t value
     else if (k == "host_split_threads") { ctx->host_split_threads = value < 0 || value > 256 ? 0 : (int)value; host_pool_destroy(ctx); }
     else if (k == "counted_sort") ctx->counted_sort = value != 0;
     else if (k == "csv_fast") ctx->csv_fast = value != 0;
+    else if (k == "order_select") ctx->order_select = value < 0 || value > 2 ? 1 : (int)value;
     else if (k == "csv_onepass_debug") ctx->csv_onepass_debug = (int)value;
     else if (k == "csv_onepass") ctx->csv_onepass = value < 0 ? 0 : value > (1 << 20) ? (1 << 20) : (int)value;
     else if (k == "direct_sort") {   // 1: LDS windows (window_sort.hip); 0: the general sorts

@@ -363,6 +363,7 @@ struct cph_ctx {
         uint32_t tickets = 0;
     } scan[2];                     // one per stream slot (scans of the two streams of a build batch run concurrently)
     int csv_fast = 1;              // cph_csv_parse: byte-parallel passes over text tiles for texts without quotes (csv_ingest.hip: k_csv_fast); 0: the record-parallel kernels
+    int order_select = 1;          // cph_order_rows: radix select in front of the sort when skip + limit is small against the rows (order.hip; A/B switch)
     int csv_onepass = 1;           // cph_csv_write[_rows]: one pass over the joined rows (materialize.hip: k_csv_onepass; slot tables + decoupled look-back);
                                    // 0: the two-pass writer; N > 1: taken whatever the row count, with at most N workgroups (tests)
     int csv_onepass_debug = 0;     // measurement only (wrong text): 1 no look-back, 2 no record bytes, 4 one record per thread
@@ -798,6 +799,7 @@ void warm_index_ops();
 void warm_resolve();
 void warm_aggregate();
 void warm_join_totals();
+void warm_order();
 void warm_small_build();
 void warm_window_sort();
 // host_encode.hip: IndexOn over one short key column in host memory through host-formed codes; *taken = false: not applicable

@@ -955,6 +955,31 @@ inline Aggregate MinInt(std::string col) { return {CPH_AGG_MIN, CPH_NUM_INT64, s
 inline Aggregate MaxInt(std::string col) { return {CPH_AGG_MAX, CPH_NUM_INT64, std::move(col)}; }
 inline Aggregate MinFloat(std::string col) { return {CPH_AGG_MIN, CPH_NUM_FLOAT64, std::move(col)}; }
 inline Aggregate MaxFloat(std::string col) { return {CPH_AGG_MAX, CPH_NUM_FLOAT64, std::move(col)}; }
+// ---- keys for DataSource::OrderBy, as DATA ----------------------------------------------------------------------------------
+// The reference orders rows only through an Index (by bytes, ascending).  A key here names a column read as an integer, as a
+// float or as bytes — or an int64 / float64 expression over the row — and a direction; the device sorts (cph_order_rows).
+// The statement is slices.SortStableFunc over cmp.Compare per key (a NaN below every number, -0 == +0; bytes: strings.Compare);
+// Desc swaps the comparison's arguments, and rows equal on every key keep their input order either way.
+struct OrderKey {
+    int32_t kind = 0;     // CPH_NUM_INT64 / CPH_NUM_FLOAT64 / CPH_ORDER_BYTES
+    bool descending = false;
+    std::string column;
+    std::shared_ptr<const Expr> expr;   // instead of a column: an expression over the rows' columns, FloatKey(price * Float64(qty))
+};
+inline OrderKey orderKeyOf(int32_t kind, Expr e, const char* who) {
+    if (e.kind != kind) throw Panic(std::string(who) + "() of an expression of the other type");
+    return {kind, false, std::string(), std::make_shared<const Expr>(std::move(e))};
+}
+inline OrderKey IntKey(std::string col) { return {CPH_NUM_INT64, false, std::move(col), nullptr}; }
+inline OrderKey IntKey(const char* col) { return IntKey(std::string(col)); }
+inline OrderKey FloatKey(std::string col) { return {CPH_NUM_FLOAT64, false, std::move(col), nullptr}; }
+inline OrderKey FloatKey(const char* col) { return FloatKey(std::string(col)); }
+inline OrderKey StrKey(std::string col) { return {CPH_ORDER_BYTES, false, std::move(col), nullptr}; }
+inline OrderKey IntKey(Expr e) { return orderKeyOf(CPH_NUM_INT64, std::move(e), "IntKey"); }
+inline OrderKey FloatKey(Expr e) { return orderKeyOf(CPH_NUM_FLOAT64, std::move(e), "FloatKey"); }
+inline OrderKey Asc(OrderKey k) { k.descending = false; return k; }
+inline OrderKey Desc(OrderKey k) { k.descending = true; return k; }
+
 // Group g (key order): keys[g] = the index columns of its rows, counts[g] its rows, and per aggregate a its value in ints[a][g]
 // (integer aggregates; floats[a] is empty) or floats[a][g] (float aggregates; ints[a] is empty).
 struct TotalsResult {
@@ -1239,6 +1264,11 @@ public:
 
     // Top (:313-325) / Drop (:329-342): counters, no data involved
     DataSource Top(uint64_t n) const {
+        if (order_) {   // behind an OrderBy: the sort's limit (the device then selects before it sorts)
+            auto spec = std::make_shared<OrderSpec>(*order_);
+            spec->limit = std::min(spec->limit, n);
+            return orderSource(spec);
+        }
         Fn src = fn_;
         return DataSource([src, n](const RowFunc& fn) {
             uint64_t counter = n;
@@ -1250,6 +1280,13 @@ public:
         });
     }
     DataSource Drop(uint64_t n) const {
+        if (order_) {   // behind an OrderBy: the sort's skip
+            auto spec = std::make_shared<OrderSpec>(*order_);
+            const uint64_t room = UINT64_MAX - spec->skip;
+            spec->skip += std::min(n, room);
+            if (spec->limit != UINT64_MAX) spec->limit -= std::min(spec->limit, n);
+            return orderSource(spec);
+        }
         Fn src = fn_;
         return DataSource([src, n](const RowFunc& fn) {
             uint64_t counter = n;
@@ -1259,6 +1296,22 @@ public:
                 return Error();
             });
         });
+    }
+
+    // OrderBy: the rows of the source in the order of the keys — OrderBy({Desc(IntKey("qty")), Asc(FloatKey("price")),
+    // Asc(StrKey("name"))}) — sorted on the device by ONE cph_order_rows call over all rows (a sort reads its whole input before
+    // its first row comes out).  Stable: rows equal on every key keep the source's order, under Asc and Desc alike.  Top / Drop
+    // directly behind it become the sort's limit / skip: OrderBy(...).Top(10) lets the device select the ten rows before it sorts.
+    // A row without a key's column ends the iteration with the reference's `missing column %q` (:170 / :192), a value that does
+    // not convert with the ValueAsInt / ValueAsFloat64 error of its row (:176 / :198) — the first such row, as a
+    // DataSourceError(row number, counted from 0); no row is handed out then.
+    DataSource OrderBy(std::vector<OrderKey> keys) const {
+        if (keys.empty()) throw Panic("empty key list in OrderBy()");
+        if (keys.size() > (size_t)CPH_ORDER_MAX_KEYS) throw Panic("too many keys in OrderBy()");
+        auto spec = std::make_shared<OrderSpec>();
+        spec->upstream = fn_;
+        spec->keys = std::move(keys);
+        return orderSource(spec);
     }
 
     // Row.ValueAsInt (:165-183) / Row.ValueAsFloat64 (:187-205) for every row of the source: the column is staged once and
@@ -1446,6 +1499,9 @@ public:
 
     // cph_filter_rows calls made so far (tests: one per batch)
     static uint64_t filter_calls() { return filter_calls_counter(); }
+    // cph_order_rows calls made so far, and the rows that entered the sort of the last one (tests: Top behind OrderBy selects)
+    static uint64_t order_calls() { return order_calls_counter(); }
+    static uint64_t order_candidates() { return last_order_candidates(); }
 
     // ToRows (:481-490)
     std::pair<std::vector<Row>, Error> ToRows() const {
@@ -1504,6 +1560,115 @@ private:
         std::vector<ChainStepSpec> steps;
     };
     std::shared_ptr<const ChainSpec> chain_;
+    struct OrderSpec {   // this source == upstream.OrderBy(keys).Drop(skip).Top(limit)
+        Fn upstream;
+        std::vector<OrderKey> keys;
+        uint64_t skip = 0, limit = UINT64_MAX;
+    };
+    std::shared_ptr<const OrderSpec> order_;
+
+    static DataSource orderSource(std::shared_ptr<const OrderSpec> spec) {
+        DataSource out([spec](const RowFunc& fn) -> Error {
+            std::vector<Row> rows;
+            if (Error err = spec->upstream([&](Row row) { rows.push_back(std::move(row)); return Error(); })) return err;
+            if (rows.size() > 0xFFFFFFFFull) return Error("too many rows for a GPU sort (2^32-1 max)");
+            const size_t nk = spec->keys.size();
+            // the first row that lacks a key's column: the rows behind it are never reached
+            size_t n = rows.size();
+            std::string missing;
+            for (size_t i = 0; i < n && missing.empty(); i++)
+                for (size_t k = 0; k < nk && missing.empty(); k++) {
+                    const OrderKey& key = spec->keys[k];
+                    if (!key.expr) {
+                        if (!rows[i].count(key.column)) missing = key.column;
+                    } else {
+                        for (const Col& c : key.expr->cols)
+                            if (!c.has_default && !rows[i].count(c.name) && missing.empty()) missing = c.name;
+                    }
+                    if (!missing.empty()) n = i;
+                }
+            cph_ctx* ctx = Gpu::Default().ctx();
+            auto fail = [&]() { return Error(std::string("csvplus_hip: ") + cph_last_error(ctx)); };
+            // every key on the device (numbers: values + status bytes; bytes: an index over the column), over rows [0, n)
+            std::vector<cph_order_key> ck(nk);
+            std::vector<cph_numcol*> nums(nk, nullptr);
+            std::vector<int32_t> bad_op(nk, -1);
+            std::vector<std::unique_ptr<detail::DeviceIndex>> indexes;
+            struct Release {
+                std::vector<cph_numcol*>* v;
+                ~Release() { for (cph_numcol* c : *v) if (c) cph_numcol_release(c); }
+            } release{&nums};
+            for (size_t k = 0; k < nk && n; k++) {
+                const OrderKey& key = spec->keys[k];
+                ck[k] = cph_order_key{key.kind, key.descending ? 1 : 0, nullptr, nullptr, CPH_MEM_HOST, 0, nullptr};
+                if (key.expr) {
+                    const Expr& e = *key.expr;
+                    std::vector<std::vector<const std::string*>> vals(e.cols.size());
+                    for (size_t c = 0; c < e.cols.size(); c++) {
+                        vals[c].resize(n);
+                        for (size_t i = 0; i < n; i++) {
+                            auto it = rows[i].find(e.cols[c].name);
+                            vals[c][i] = it == rows[i].end() ? &e.cols[c].fallback : &it->second;
+                        }
+                    }
+                    if (detail::evalStaged(ctx, e, vals, n, &nums[k], &bad_op[k]) != CPH_OK) return fail();
+                    continue;
+                }
+                std::vector<std::vector<const std::string*>> vals(1);
+                vals[0].resize(n);
+                for (size_t i = 0; i < n; i++) vals[0][i] = &rows[i].at(key.column);
+                detail::StagedColumns st(ctx, 1);
+                st.stage(vals, n);
+                if (key.kind == CPH_ORDER_BYTES) {
+                    indexes.push_back(std::make_unique<detail::DeviceIndex>());
+                    uint64_t dup = 0;
+                    if (cph_index_build(ctx, st.cols(), 1, 0, &indexes.back()->h, &dup) != CPH_OK) return fail();
+                    ck[k].index = indexes.back()->h;
+                } else if (cph_col_to_number(ctx, st.cols(), nullptr, n, key.kind, CPH_MEM_DEVICE, &nums[k]) != CPH_OK) {
+                    return fail();
+                }
+            }
+            // the first row with a value that does not convert, the lowest key there
+            size_t bad_row = SIZE_MAX, bad_key = 0;
+            for (size_t k = 0; k < nk; k++)
+                if (nums[k] && nums[k]->nerrors && (size_t)nums[k]->first_error_row < bad_row) {
+                    bad_row = (size_t)nums[k]->first_error_row;
+                    bad_key = k;
+                }
+            if (bad_row != SIZE_MAX) {
+                const OrderKey& key = spec->keys[bad_key];
+                const int32_t kind = nums[bad_key]->first_error_kind;
+                if (key.expr) return Error::DataSourceError(bad_row, Error(key.expr->errorText(kind, bad_op[bad_key], rows[bad_row])));
+                return Error::DataSourceError(bad_row, Error(conversionError(key.column, rows[bad_row].at(key.column), key.kind, kind)));
+            }
+            if (!missing.empty()) return Error::DataSourceError(n, Error("missing column " + quote(missing)));
+            if (!n) return Error();
+            for (size_t k = 0; k < nk; k++)
+                if (nums[k]) {
+                    ck[k].values = nums[k]->values;
+                    ck[k].status = nums[k]->status;
+                    ck[k].values_mem = nums[k]->mem;
+                }
+            cph_ordered* res = nullptr;
+            if (cph_order_rows(ctx, ck.data(), (int32_t)nk, n, spec->skip, spec->limit, CPH_MEM_HOST, &res) != CPH_OK) return fail();
+            struct ReleaseOrdered { cph_ordered* r; ~ReleaseOrdered() { cph_ordered_release(r); } } rel{res};
+            order_calls_counter()++;
+            last_order_candidates() = res->candidates;
+            for (uint64_t i = 0; i < res->nrows; i++)
+                if (Error e = fn(std::move(rows[res->ids[i]]))) return e.is_eof() ? Error() : e;
+            return Error();
+        });
+        out.order_ = std::move(spec);
+        return out;
+    }
+    static uint64_t& order_calls_counter() {
+        static uint64_t n = 0;
+        return n;
+    }
+    static uint64_t& last_order_candidates() {
+        static uint64_t n = 0;
+        return n;
+    }
 
     // createIndex (:707-738) + createUniqueIndex (:740-756)
     std::pair<std::shared_ptr<Index>, Error> createIndex(const std::vector<std::string>& columns, bool unique) const {

@@ -306,7 +306,7 @@ def _take_rowlist(ctx, out, out_mem, as_handle):
 def take_rows(ctx: N.Context, row_ids, rows, out_mem: int = N.CPH_MEM_HOST, as_handle: bool = False):
     """out[i] = row_ids[rows[i]] - base (cph_rowsel_take): the row ids of a Join narrowed to the rows a Filter kept.
     row_ids: numpy uint32 / uint64 or (numpy ids, base) (host), (device_ptr, bits, count[, base]) (device), or None
-    (identity: a copy of `rows`).  rows: a RowList, or a numpy uint32 / uint64 array.  Returns numpy (HOST) or a RowList (DEVICE / as_handle)."""
+    (identity: a copy of `rows`).  rows: a RowList, an Ordered (order_rows), or a numpy uint32 / uint64 array.  Returns numpy (HOST) or a RowList (DEVICE / as_handle)."""
     keep = []
     sel, sel_mem = None, N.CPH_MEM_HOST
     if row_ids is not None:
@@ -326,6 +326,10 @@ def take_rows(ctx: N.Context, row_ids, rows, out_mem: int = N.CPH_MEM_HOST, as_h
             sel_mem = N.CPH_MEM_DEVICE
     if isinstance(rows, RowList):
         lst = rows.ptr
+    elif isinstance(rows, Ordered):   # an ordered list is a list of row numbers like any other
+        rl = N.cph_rowlist(rows.nrows, 0, rows.ids_ptr or None, 32, rows.mem)
+        keep.append(rl)
+        lst = C.pointer(rl)
     else:
         a = np.asarray(rows)
         if a.dtype != np.uint64:
@@ -685,3 +689,117 @@ def validate_rows(ctx: N.Context, cols_by_name, pred, row_ids=None, nrows=None, 
     finally:
         rl.release()
     return None if passed >= int(nrows) else first_row + passed
+
+
+# ---- OrderBy with Drop / Top behind it (cph_order_rows) --------------------------------------------------------------------
+
+class Ordered:
+    """cph_ordered: the row numbers (positions in the selection, uint32) of order[skip : skip + limit], valid until
+    release().  select_used: the Top-N select ran in front of the sort; candidates: rows that entered the sort."""
+
+    def __init__(self, ctx, ptr):
+        self.ctx, self.ptr = ctx, ptr
+        c = ptr.contents
+        self.nrows, self.mem, self.bits = int(c.nrows), int(c.mem), 32
+        self.ids_ptr = int(c.ids or 0)
+        self.select_used, self.candidates = bool(c.select_used), int(c.candidates)
+        ctx._children.add(self)
+
+    def __len__(self):
+        return self.nrows
+
+    def to_numpy(self) -> np.ndarray:
+        """The row numbers on the host (a copy): only for a result in host memory."""
+        assert self.mem == N.CPH_MEM_HOST or self.nrows == 0, "a device result has no host view: consume it on the device"
+        return N._ptr_array(self.ids_ptr, self.nrows, np.uint32).copy()
+
+    def as_row_ids(self):
+        """(device_ptr, bits, count): the tuple csv_write / json_write / map_column / to_int / take_rows take as row ids of
+        a device column."""
+        assert self.mem == N.CPH_MEM_DEVICE, "a host result is a numpy array: use to_numpy()"
+        return (self.ids_ptr, 32, self.nrows)
+
+    def release(self):
+        if self.ptr:
+            self.ctx.lib.cph_ordered_release(self.ptr)
+            self.ptr = None
+
+    close = release
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def order_rows(ctx: N.Context, keys, nrows: int, skip: int = 0, limit=None, out_mem: int = N.CPH_MEM_HOST) -> Ordered:
+    """OrderBy(keys) with Drop(skip) / Top(limit) behind it, sorted on the device (cph_order_rows): rows 0..nrows-1 of a
+    selection in the order of ordering.Asc / ordering.Desc keys — slices.SortStableFunc, stable for ascending and
+    descending keys alike (ordering.order_model is the contract).  A key's source is a numpy int64 / float64 array (host), a
+    NumCol (it stays where it lives, its status bytes are handed through: a row that failed raises ordering.OrderError), a
+    (device_ptr, count) pair or a device tensor, or a DeviceIndex over the table being ordered (kind "bytes").  With a limit
+    that is small against nrows the rows are cut down by a radix select over the first key before anything is sorted
+    (Ordered.select_used, Ordered.candidates; ctx.set_option("order_select", 0) turns it off)."""
+    from . import ordering as O
+
+    keys = list(keys)
+    n = int(nrows)
+    arr = (N.cph_order_key * max(1, len(keys)))()
+    keep = []
+    for i, key in enumerate(keys):
+        if not isinstance(key, O.OrderKey):
+            raise TypeError(f"not an order key: {key!r} (use ordering.Asc / ordering.Desc)")
+        if not key.kind:
+            raise TypeError(f"{type(key).__name__}({key.source!r}): a name is a key of pipeline.totals_to_csv / filter_to_csv, not of order_rows")
+        ck, src = arr[i], key.source
+        ck.kind, ck.descending = key.kind, 1 if key.descending else 0
+        if key.kind == N.CPH_ORDER_BYTES:
+            if not isinstance(src, N.DeviceIndex):
+                raise TypeError(f'{type(key).__name__}: a "bytes" key takes a DeviceIndex over the table being ordered')
+            ck.index = src.handle
+            keep.append(src)
+            continue
+        dt = np.int64 if key.kind == N.CPH_NUM_INT64 else np.float64
+        if isinstance(src, NumCol):
+            if src.kind != key.kind:
+                raise ValueError(f"{type(key).__name__}: the NumCol's kind differs from the key's")
+            if src.nrows < n:
+                raise ValueError(f"{type(key).__name__}: {src.nrows} values for {n} rows")
+            if src.mem == N.CPH_MEM_DEVICE:
+                ck.values, ck.status, ck.values_mem = src.values[0] or None, src.status[0] or None, N.CPH_MEM_DEVICE
+            else:
+                v, st = np.ascontiguousarray(src.values, dtype=dt), np.ascontiguousarray(src.status, dtype=np.uint8)
+                keep += [v, st]
+                ck.values, ck.status, ck.values_mem = (v.ctypes.data, st.ctypes.data, N.CPH_MEM_HOST) if n else (None, None, N.CPH_MEM_HOST)
+            keep.append(src)
+        elif isinstance(src, tuple):   # (device pointer, count)
+            if int(src[1]) < n:
+                raise ValueError(f"{type(key).__name__}: {int(src[1])} values for {n} rows")
+            ck.values, ck.values_mem = int(src[0]) or None, N.CPH_MEM_DEVICE
+        elif hasattr(src, "data_ptr"):   # a device tensor
+            want = "int64" if key.kind == N.CPH_NUM_INT64 else "float64"
+            if not str(getattr(src, "dtype", want)).endswith(want):
+                raise ValueError(f"{type(key).__name__}: the tensor's dtype is {src.dtype}, the kind wants {want}")
+            if not getattr(src, "is_cuda", True):
+                raise ValueError(f"{type(key).__name__}: a tensor source must live on the device (pass .numpy() for host values)")
+            if int(src.numel()) < n:
+                raise ValueError(f"{type(key).__name__}: {int(src.numel())} values for {n} rows")
+            keep.append(src)
+            ck.values, ck.values_mem = int(src.data_ptr()) or None, N.CPH_MEM_DEVICE
+        else:
+            v = np.ascontiguousarray(np.asarray(src, dtype=dt).reshape(-1))
+            if len(v) < n:
+                raise ValueError(f"{type(key).__name__}: {len(v)} values for {n} rows")
+            keep.append(v)
+            ck.values, ck.values_mem = v.ctypes.data if len(v) else None, N.CPH_MEM_HOST
+    out = C.POINTER(N.cph_ordered)()
+    ctx._check(ctx.lib.cph_order_rows(ctx.handle, arr if keys else None, len(keys), n, int(skip),
+                                      N.CPH_NO_LIMIT if limit is None else int(limit), out_mem, C.byref(out)))
+    del keep
+    r = out.contents
+    if r.nerrors:
+        err = O.OrderError(int(r.first_error_row), int(r.first_error_key), int(r.first_error_kind), int(r.nerrors))
+        ctx.lib.cph_ordered_release(out)
+        raise err
+    return Ordered(ctx, out)

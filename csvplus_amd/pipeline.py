@@ -273,17 +273,22 @@ def join_to_json(ctx: N.Context, stream: Table, steps, out_columns=None, timings
 
 
 def filter_to_csv(ctx: N.Context, table: Table, pred, out_columns, mode: str = "where", first_row: int = 0, nrows=None,
-                  skip: int = 0, limit=None, out_mem: int = N.CPH_MEM_HOST, computed=None):
+                  skip: int = 0, limit=None, out_mem: int = N.CPH_MEM_HOST, computed=None, order_by=None):
     """The reference's headline shape, FromFile(...).Filter(Like(...)).ToCsv(...), on the device: the rows of ONE table
     where `pred` holds (mode "where"; "take_while" / "drop_while" for TakeWhile / DropWhile; first_row / nrows: Drop / Top
     in front of the filter, skip / limit: behind it), written as CSV.  out_columns: column names, or (output name, column)
     pairs.  computed: {name: template} — .Map(row[name] = template(row)) behind the filter (csvplus_amd.mapping), in dict
     order over the rows kept; an output column of a computed name takes the computed column.
+    order_by: ordering.Asc / ordering.Desc over a column NAME with kind "int" / "float" / "bytes" — .OrderBy(keys) over the
+    rows the filter kept, IN FRONT OF skip / limit ("the ten largest"), sorted on the device (materialize.order_rows); a key
+    value that does not convert raises ordering.OrderError, its row counted among the rows kept.  None (default): row order.
     Returns the CSV text: bytes, or a DeviceBytes handle for out_mem DEVICE."""
     from . import predicates as P
     from .materialize import csv_write, filter_rows
 
     pairs = [(c, c) if isinstance(c, str) else tuple(c) for c in out_columns]
+    if order_by is not None:
+        return _filter_ordered_to_csv(ctx, table, pred, pairs, mode, first_row, nrows, skip, limit, out_mem, computed, list(order_by))
     bufs = []
     kept = filter_rows(ctx, table.cols, pred, nrows=nrows, mode=mode, first_row=first_row, skip=skip, limit=limit,
                        out_mem=N.CPH_MEM_DEVICE)
@@ -310,7 +315,67 @@ def filter_to_csv(ctx: N.Context, table: Table, pred, out_columns, mode: str = "
         kept.release()
 
 
-def totals_to_csv(ctx: N.Context, table: Table, by, specs, names=None, out_mem: int = N.CPH_MEM_HOST):
+def _filter_ordered_to_csv(ctx, table, pred, pairs, mode, first_row, nrows, skip, limit, out_mem, computed, order_by):
+    """filter_to_csv with order_by: Filter | OrderBy | Drop(skip) | Top(limit) | Map | ToCsv, every step on the device."""
+    from . import mapping as M
+    from . import ordering as O
+    from . import predicates as P
+    from .materialize import csv_write, filter_rows, gather_rows, order_rows, take_rows, to_float, to_int
+
+    if not order_by:
+        raise ValueError("filter_to_csv: order_by needs at least one key")
+    for key in order_by:
+        if not isinstance(key, O.OrderKey) or not isinstance(key.source, str):
+            raise TypeError(f"filter_to_csv: an order key is Asc / Desc over a column name, not {key!r}")
+        if key.source not in table.cols:
+            raise M.MissingColumn(key.source)
+        if not key.kind:
+            raise ValueError(f'filter_to_csv: the order key over {key.source!r} needs a kind: "int", "float" or "bytes"')
+    bufs, handles = [], []
+    kept = filter_rows(ctx, table.cols, pred, nrows=nrows, mode=mode, first_row=first_row, out_mem=N.CPH_MEM_DEVICE)
+    handles.append(kept)
+    try:
+        if kept.is_range and len(kept):   # a WHILE mode's answer: as an array of row numbers
+            kept = filter_rows(ctx, table.cols, P.All(), nrows=len(kept), first_row=kept.first, out_mem=N.CPH_MEM_DEVICE)
+            handles.append(kept)
+        n = len(kept)
+        header = [name for name, _ in pairs]
+        if n == 0:
+            return csv_write(ctx, [table[c].head(0) for _, c in pairs], header, out_mem=out_mem)
+        rows = kept.as_row_ids()
+        keys = []
+        for key in order_by:
+            col = table[key.source]
+            if key.kind == N.CPH_ORDER_BYTES:   # the index's comparison over the values of the rows kept
+                cb = gather_rows(ctx, col, rows, out_mem=N.CPH_MEM_DEVICE)
+                bufs.append(cb)
+                src = N.DeviceIndex(ctx, [cb.as_device_strcol()])
+            else:
+                src = (to_int if key.kind == N.CPH_NUM_INT64 else to_float)(ctx, col, row_ids=rows, nrows=n, out_mem=N.CPH_MEM_DEVICE)
+            handles.append(src)
+            keys.append(type(key)(src, key.kind_name))
+        ordered = order_rows(ctx, keys, n, skip=skip, limit=limit, out_mem=N.CPH_MEM_DEVICE)
+        handles.append(ordered)
+        m = len(ordered)
+        if m == 0:
+            return csv_write(ctx, [table[c].head(0) for _, c in pairs], header, out_mem=out_mem)
+        final = take_rows(ctx, rows, ordered, out_mem=N.CPH_MEM_DEVICE)   # table rows in output order
+        handles.append(final)
+        ids = final.as_row_ids()
+        done = {}
+        if computed:
+            done = _compute_columns(ctx, {str(k): v for k, v in computed.items()},
+                                    lambda name: (table[name], ids) if name in table.cols else None, m, bufs)
+        cols = [done[name] if name in done else table[c] for name, c in pairs]
+        return csv_write(ctx, cols, header, out_mem=out_mem, row_ids=[None if name in done else ids for name, _ in pairs], nrows=m)
+    finally:
+        for cb in bufs:
+            cb.release()
+        for h in reversed(handles):
+            h.close()
+
+
+def totals_to_csv(ctx: N.Context, table: Table, by, specs, names=None, out_mem: int = N.CPH_MEM_HOST, order_by=None, limit=None):
     """IndexOn(by...) over `table`, then Count and the specs per key, written as CSV — the reference's TestSimpleTotals loop
     (csvplus_test.go:516-571) ending in ToCsv, every step in HBM: cph_index_build, cph_index_aggregate, the key columns read
     through the groups' first rows inside the writer, the count and the int64 results as computed columns (mapping.Int).
@@ -318,6 +383,9 @@ def totals_to_csv(ctx: N.Context, table: Table, by, specs, names=None, out_mem: 
     (see csvplus_amd.aggregate).  names: the header of the count column and of every spec's column (default "count",
     "sum0", "min1", ...); the key columns keep their names.  One output row per distinct key, in key order.
     Float results are refused: formatting float64 (Go's shortest round-trip FormatFloat) is out of scope, as for Map.
+    order_by: ordering.Asc / ordering.Desc over a NAME — the count column's or a spec's column's name (see `names`), or "by"
+    for the key order — .OrderBy(keys).Top(limit) over the groups, sorted on the device (materialize.order_rows): "the ten
+    customers with the largest amount".  None (default): key order, every group.
     Returns bytes, or a DeviceBytes handle for out_mem DEVICE."""
     from . import aggregate as A
     from . import mapping as M
@@ -357,13 +425,55 @@ def totals_to_csv(ctx: N.Context, table: Table, by, specs, names=None, out_mem: 
             bufs.append(cb)
             cols.append(cb.as_device_strcol())
             ids.append(None)
-        return csv_write(ctx, cols, by + [str(nm) for nm in names], out_mem=out_mem, row_ids=ids, nrows=ng)
+        header = by + [str(nm) for nm in names]
+        if order_by is None and limit is None:
+            return csv_write(ctx, cols, header, out_mem=out_mem, row_ids=ids, nrows=ng)
+        return _ordered_groups_to_csv(ctx, t, cols, len(by), header, [str(nm) for nm in names], resolved, order_by, limit, out_mem)
     finally:
         for cb in bufs:
             cb.release()
         if t is not None:
             t.release()
         index.close()
+
+
+def _ordered_groups_to_csv(ctx, t, cols, nby, header, names, specs, order_by, limit, out_mem):
+    """totals_to_csv with order_by / limit: the groups of `t` (device) in the order of the keys, cut to `limit`.  cols = the
+    table's key columns (read through the groups' first rows) followed by the computed columns (one row per group)."""
+    import numpy as np
+
+    from . import ordering as O
+    from .materialize import csv_write, order_rows, take_rows
+
+    ng = t.ngroups
+    keys = []
+    for key in ([O.Asc("by")] if order_by is None else list(order_by)):
+        if not isinstance(key, O.OrderKey) or not isinstance(key.source, str):
+            raise TypeError(f"totals_to_csv: an order key is Asc / Desc over a name, not {key!r}")
+        if key.source == "by" and "by" not in names:   # the groups are in key order: a group's number is its key's rank
+            keys.append(type(key)(np.arange(ng, dtype=np.int64), "int"))
+        elif key.source in names:
+            j = names.index(key.source)   # 0: the count (below 2^32: the uint64 reads as the same int64)
+            keys.append(type(key)(t.count if j == 0 else t.values[j - 1], "int" if j == 0 else specs[j - 1].kind_name))
+        else:
+            raise ValueError(f"totals_to_csv: order_by names {key.source!r}; the names are {names + ['by']}")
+    if not keys:
+        raise ValueError("totals_to_csv: order_by needs at least one key")
+    if ng == 0:
+        return csv_write(ctx, [c.head(0) for c in cols], header, out_mem=out_mem)
+    ordered = order_rows(ctx, keys, ng, limit=limit, out_mem=N.CPH_MEM_DEVICE)
+    first = None
+    try:
+        m = len(ordered)
+        if m == 0:
+            return csv_write(ctx, [c.head(0) for c in cols], header, out_mem=out_mem)
+        first = take_rows(ctx, (t.first_row[0], 32, ng), ordered, out_mem=N.CPH_MEM_DEVICE)   # table rows of the groups, in output order
+        ids = [first.as_row_ids()] * nby + [ordered.as_row_ids()] * (len(cols) - nby)
+        return csv_write(ctx, cols, header, out_mem=out_mem, row_ids=ids, nrows=m)
+    finally:
+        if first is not None:
+            first.release()
+        ordered.release()
 
 
 def join_totals_to_csv(ctx: N.Context, stream_table: Table, build_table: Table, on, specs, names=None, out_mem: int = N.CPH_MEM_HOST,

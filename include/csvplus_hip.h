@@ -236,6 +236,9 @@ CPH_API int32_t cph_ctx_set_stream(cph_ctx* ctx, void* hip_stream);
  *                   (decimal ids) arithmetically — one aligned 8-byte load and a dot product instead of a LUT walk (A/B switch)
  *   "chain_identity" 0 / 1 (default 1): reporting positions, an index whose code space has exactly as many states as the
  *                   index has rows needs no lookup: the position of a key is its code (A/B switch)
+ *   "order_select"  0 / 1 / 2 (default 1): cph_order_rows with a limit that is small against the row count radix-selects the rows
+ *                   that can reach the result and sorts only those; 0 = always the full sort, 2 = the select for every limit,
+ *                   whatever the row count (measuring where the two routes cross; A/B switch: the answer is the same)
  *   "pool_reserve_mb"  reserves ONE device slab of that many MiB now; later requests are carved out of it first
  *                   (first fit, coalesced on release) and only fall back to hipMalloc when it cannot serve them —
  *                   a one-shot caller pays its device allocations here, not inside its first call
@@ -1299,6 +1302,57 @@ CPH_API int32_t cph_chain_aggregate(cph_ctx* ctx, const cph_chain* chain, int32_
                                     const cph_chain_agg_spec* specs, int32_t nspecs, int32_t out_mem,
                                     cph_chain_aggregated** out);
 CPH_API void    cph_chain_aggregated_release(cph_chain_aggregated* a);
+
+/*
+ * OrderBy: the rows of a selection in the order of up to CPH_ORDER_MAX_KEYS typed keys, on the device, with Drop / Top behind
+ * it.  The reference has no sort by value (an Index orders by bytes, ascending only); the statement is Go's
+ * slices.SortStableFunc(rows, f) where f compares key 0 first, then key 1, ...; a DESCENDING key swaps its two arguments.
+ * The sort is stable: rows equal on every key keep their input order, under ascending and descending keys alike (descending
+ * is not the reverse of ascending).  The answer is order[skip : skip + limit], as selection positions 0 .. nrows-1: 32-bit
+ * row ids for cph_rowsel, so every writer, Map and conversion consumes an ordered list unchanged.
+ *   CPH_NUM_INT64    cmp.Compare on int64.  values = int64_t[nrows] by selection position.
+ *   CPH_NUM_FLOAT64  cmp.Compare on float64: a NaN is less than every non-NaN, all NaNs are equal whatever their bits,
+ *                    -0 equals +0.  values = double[nrows].
+ *   CPH_ORDER_BYTES  the comparison of `index` (strings.Compare per key column, csvplus.go:794-806; several key columns = the
+ *                    tuple), an index built over the table being ordered: cph_index_nrows(index) == nrows and the index's
+ *                    table rows are the selection positions.  Any index cph_index_aggregate accepts (32-bit, one-word and
+ *                    multi-word codes, indexes out of cph_index_select / cph_index_resolve / cph_index_load).
+ * Number keys lie in values_mem (a host array is uploaded); `status` (optional, same memory) holds a CPH_NUM_* byte per row, as
+ * cph_col_to_number / cph_num_eval leave it, so a cph_numcol in device memory is a key without a copy.
+ *
+ * The keys are mapped to unsigned integers of the same order and sorted by the stable radix sort of the index build, least
+ * significant key first.  With a limit, skip + limit <= nrows / 4 and option "order_select" on, the rows are first cut down
+ * to the CANDIDATES: a radix select over key 0 finds the key of ascending rank skip + limit - 1, every row whose key 0 is at or
+ * below it is kept in input order (all ties at the threshold included), and only those are sorted.  `select_used` tells which
+ * route ran, `candidates` how many rows entered the sort (nrows without the select); the ids are the same either way.
+ *
+ * A row whose status is not CPH_NUM_OK is DATA, as in cph_index_aggregate: the call returns CPH_OK with nerrors > 0 (over all
+ * keys), nrows = 0 and ids = NULL; first_error_row is the lowest such row, first_error_key the lowest key that fails there,
+ * first_error_kind its status byte.
+ *
+ * nrows == 0 is legal.  More than 2^32-1 rows: CPH_ERR_TOO_MANY_ROWS.  CPH_ERR_INVALID (with a message): NULL ctx / keys / out,
+ * nkeys outside 1..CPH_ORDER_MAX_KEYS, an unknown kind, values_mem or out_mem, a number key without values, a BYTES key without
+ * an index or with an index of another row count.
+ */
+#define CPH_ORDER_MAX_KEYS 8
+typedef struct {
+    int32_t          kind, descending;     /* CPH_NUM_INT64 / CPH_NUM_FLOAT64 / CPH_ORDER_BYTES; 0 ascending, else descending */
+    const void*      values;               /* numbers: int64_t[nrows] / double[nrows] by selection position */
+    const uint8_t*   status;               /* optional CPH_NUM_* per row, same memory as values */
+    int32_t          values_mem, reserved_;   /* CPH_MEM_HOST / CPH_MEM_DEVICE (numbers only) */
+    const cph_index* index;                /* BYTES: an index over the table being ordered */
+} cph_order_key;
+typedef struct {
+    uint64_t        nrows;                 /* min(limit, nrows_in - skip), 0 when skip >= nrows_in */
+    const uint32_t* ids;                   /* selection positions in output order, in `mem` */
+    int32_t         mem, select_used;
+    uint64_t        candidates;            /* rows that entered the sort */
+    uint64_t        nerrors, first_error_row;      /* lowest row with a status != OK in any key; UINT64_MAX */
+    int32_t         first_error_kind, first_error_key;
+} cph_ordered;
+CPH_API int32_t cph_order_rows(cph_ctx* ctx, const cph_order_key* keys, int32_t nkeys, uint64_t nrows, uint64_t skip,
+                               uint64_t limit /* UINT64_MAX = none */, int32_t out_mem, cph_ordered** out);
+CPH_API void    cph_ordered_release(cph_ordered* o);
 
 /* Index.WriteTo / LoadIndex (csvplus.go:655-705) for the device index: a flat
  * little-endian file with the key codec, sorted codes and perm.  NOT a gob
