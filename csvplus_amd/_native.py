@@ -408,6 +408,9 @@ PROTOTYPES = [
     ("cph_csv_parse", C.c_int32,
      [_P, _P, C.c_uint64, C.c_int32, C.POINTER(cph_csv_options), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
       C.POINTER(C.POINTER(cph_csv_table))]),
+    ("cph_csv_parse_lazy", C.c_int32,
+     [_P, _P, C.c_uint64, C.c_int32, C.POINTER(cph_csv_options), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+      C.POINTER(C.POINTER(cph_csv_table))]),
     ("cph_csv_table_release", None, [C.POINTER(cph_csv_table)]),
     ("cph_index_dup_groups", C.c_int32, [_P, _P, C.POINTER(C.POINTER(cph_groups))]),
     ("cph_groups_release", None, [C.POINTER(cph_groups)]),

@@ -4,7 +4,7 @@
 // stays on the host, which passes the field INDICES of the wanted columns.
 //
 // Semantics = Go's encoding/csv Reader as csvplus configures it (Comma, Comment, TrimLeadingSpace,
-// FieldsPerRecord; LazyQuotes is not supported): "\r\n" line ends become "\n" (also inside quoted
+// FieldsPerRecord; LazyQuotes through cph_csv_parse_lazy, below): "\r\n" line ends become "\n" (also inside quoted
 // fields), empty lines and comment lines between records are skipped, `""` is a literal quote, a
 // quote inside an unquoted field is ErrBareQuote, anything but Comma / end of line after a closing
 // quote (or EOF inside quotes) is ErrQuote, field counts follow FieldsPerRecord.  The FIRST error in
@@ -25,10 +25,44 @@
 //      each column's bytes of the tile in LDS, then streams them out
 // A bare quote flips the parity of everything after it, but everything BEFORE the first error is
 // segmented correctly, and only the first error (smallest record index) is reported.
+//
+// LazyQuotes (cph_csv_parse_lazy; Reader.LazyQuotes, csvplus.go:982-987): a quote inside an unquoted field is a byte, a quote
+// inside a quoted field that is followed by neither a quote, Comma nor the line end is a byte, the end of the text inside
+// quotes ends the field; ErrFieldCount is the only error left.  Parity says nothing about such a text, so passes 1 and 2 are
+// replaced by a scan of the seven-state byte automaton of csv_lazy_device.hpp (the tile geometry stays: 16 KiB tiles, 16-byte
+// chunks, j-major text order):
+//   1L. k_csv_lazy_tile_maps     every chunk's state map (16 bytes walked with two v_perm_b32 each), composed over the wave with
+//                                shuffles, over the tile's 4 waves x 4 rounds through LDS: one packed map per tile
+//   1M. k_csv_lazy_tile_entry    exclusive compose-scan over the tile maps, RS in front of the text: every tile's entry STATE.
+//                                One workgroup takes kLazyScanStep tiles per step and carries a single state to the next step
+//                                (plain stream order, no look-back between workgroups: nothing here needs a resident grid).
+//                                4 bytes per 16 KiB of text: 0.03 % of the bytes the passes beside it read.
+//   2L. k_csv_lazy_marks         the same walk again with the entry state known: a 16-bit mask per chunk of the newlines that end
+//                                a record, and their number per tile (-> the existing exclusive_scan_u64)
+//   2M. k_csv_lazy_separators    reads the masks only (1/8 of the text, 16 bytes = 8 chunks per thread) and writes the positions
+// Choices.  (a) The second text pass RECOMPUTES the automaton instead of reading per-chunk maps saved by the first: a saved map
+// is 4-8 bytes per 16 bytes of text, written once and read once — 0.5 byte of traffic per byte of text to save about 250 VALU
+// instructions per chunk, on passes that run at a small fraction of the HBM roof either way; the bytes would also have to be
+// kept for a text of any size.  What IS saved is the result of the second walk, 2 bytes per chunk, so that positions are written
+// without a third walk (their place needs the scan of the counts, which needs the walk).  (b) Four launches + the count scan, as
+// the strict side has two + two scans.  (c) Per byte: a select chain picks the class map, two v_perm_b32 apply it to all seven
+// start states at once — no per-state registers, no branches, no run-length shortcut for plain bytes (it would diverge within
+// the wave; left as the follow-up if the walk's VALU time matters).  TrimLeadingSpace and the comment character each add a
+// class test per byte: the walk is instantiated four ways and a uniform branch picks one.
+// Behind the separators everything is shared with the strict side: k_csv_classify (a segment starts in RS, so its first byte
+// still decides "comment line"; a comment's quotes were kept from meaning anything by the CM state, so the strict side's
+// "comment line containing a quote" refusal does not apply), k_csv_compact, RecIndex, and the record-parallel kernels in their
+// LAZY instantiation of csv_parse_record.  A text without any quote reads the same under both rules: k_csv_fast is tried first.
+// One detected limit: the automaton trims ASCII spaces only (the multi-byte spaces of unicode.IsSpace would need eight more
+// states); the per-record parser trims them all and reports a field whose trimmed-off prefix held a multi-byte space and
+// whose next byte is a quote — Go reads it as quoted, the automaton read it as unquoted.  Everything in front of the
+// earliest such field is segmented correctly and the field's first bytes lie inside its own record's segment, so the
+// earliest occurrence is always seen: the call fails with CPH_ERR_INVALID.
 #include <cstdlib>
 #include <new>
 
 #include "lds_stage.hpp"
+#include "csv_lazy_device.hpp"   // (behind the HIP runtime's __forceinline__)
 
 namespace cph {
 
@@ -201,6 +235,185 @@ __global__ __launch_bounds__(kCsvThreads) void k_csv_separators(const uint8_t* _
     }
 }
 
+// ---- 1L / 1M / 2L / 2M: the separator passes under LazyQuotes (the automaton: csv_lazy_device.hpp) --------------------
+constexpr int kLazyScanThreads = 1024;
+constexpr int kLazyScanStep = kLazyScanThreads;   // tiles per step of k_csv_lazy_tile_entry: one per thread (16 MiB of text)
+constexpr int kLazyMarkChunks = 8;                // k_csv_lazy_separators: masks per thread = one 16-byte load
+constexpr int kLazySepTiles = kCsvThreads * kLazyMarkChunks * 16 / kCsvTile;   // text tiles per workgroup there
+static_assert(kLazySepTiles * kCsvTile == kCsvThreads * kLazyMarkChunks * 16, "a separator workgroup covers whole tiles");
+
+__device__ __forceinline__ LzMap lz_shfl_up(const LzMap& v, int d) {
+    return LzMap{(uint32_t)__shfl_up(v.lo, d, kWave), (uint32_t)__shfl_up(v.hi, d, kWave)};
+}
+// lane l gets the composition of the maps of lanes 0 .. l, in lane order
+__device__ __forceinline__ LzMap lz_wave_inclusive(LzMap v) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const LzMap o = lz_shfl_up(v, d);
+        if (lane_id() >= d) v = lz_compose(o, v);
+    }
+    return v;
+}
+__device__ __forceinline__ LzMap lz_wave_exclusive(const LzMap& incl) {
+    const LzMap ex = lz_shfl_up(incl, 1);
+    return lane_id() == 0 ? lz_identity() : ex;
+}
+
+// This thread's kCsvChunks chunks of the tile (w[j] = the 16 bytes at tile_base + (j*256 + t)*16, zeros past the text's end: a zero
+// byte is no newline, and the map of the text's last tile is never applied), each chunk's map scanned over its wave (incl[j]) and
+// every (round, wave) stretch's map in s_map[j * kCsvWaves + wave].  Ends with a __syncthreads.
+template <bool TRIM, bool CMT>
+__device__ __forceinline__ void lazy_scan_tile(const uint8_t* __restrict__ d, uint64_t size, uint64_t tile_base, const LzTable& tb,
+                                               uint32_t (&w)[kCsvChunks][4], LzMap (&incl)[kCsvChunks], LzMap* s_map) {
+#pragma unroll
+    for (int j = 0; j < kCsvChunks; j++) {
+        const uint64_t pos = tile_base + ((uint64_t)j * kCsvThreads + threadIdx.x) * 16;
+        w[j][0] = w[j][1] = w[j][2] = w[j][3] = 0;
+        if (pos + 16 <= size) {
+            const uint4 v = *reinterpret_cast<const uint4*>(d + pos);
+            w[j][0] = v.x; w[j][1] = v.y; w[j][2] = v.z; w[j][3] = v.w;
+        } else {
+            for (uint64_t k = pos; k < size; k++) w[j][(k - pos) >> 2] |= (uint32_t)d[k] << (8 * ((k - pos) & 3));
+        }
+        incl[j] = lz_wave_inclusive(lz_walk16<TRIM, CMT, false>(w[j], tb, lz_identity(), nullptr));
+        if (lane_id() == kWave - 1) s_map[j * kCsvWaves + wave_id()] = incl[j];
+    }
+    __syncthreads();
+}
+
+template <bool TRIM, bool CMT>
+__device__ __forceinline__ void lazy_tile_map(const uint8_t* __restrict__ d, uint64_t size, const LzTable& tb, uint32_t* __restrict__ tile_map,
+                                              LzMap* s_map) {
+    uint32_t w[kCsvChunks][4];
+    LzMap incl[kCsvChunks];
+    lazy_scan_tile<TRIM, CMT>(d, size, (uint64_t)blockIdx.x * kCsvTile, tb, w, incl, s_map);
+    if (threadIdx.x == 0) {
+        LzMap run = lz_identity();
+#pragma unroll
+        for (int k = 0; k < kCsvChunks * kCsvWaves; k++) run = lz_compose(run, s_map[k]);
+        tile_map[blockIdx.x] = lz_pack(run);
+    }
+}
+__global__ __launch_bounds__(kCsvThreads) void k_csv_lazy_tile_maps(const uint8_t* __restrict__ d, uint64_t size, LzTable tb,
+                                                                   uint32_t* __restrict__ tile_map) {
+    __shared__ LzMap s_map[kCsvChunks * kCsvWaves];
+    if (tb.trim) {   // (uniform)
+        if (tb.comment < 0x100u) lazy_tile_map<true, true>(d, size, tb, tile_map, s_map);
+        else lazy_tile_map<true, false>(d, size, tb, tile_map, s_map);
+    } else {
+        if (tb.comment < 0x100u) lazy_tile_map<false, true>(d, size, tb, tile_map, s_map);
+        else lazy_tile_map<false, false>(d, size, tb, tile_map, s_map);
+    }
+}
+
+// tile_map[t] (packed map of tile t) -> the state in front of tile t, RS in front of tile 0.  ONE workgroup.
+__global__ __launch_bounds__(kLazyScanThreads) void k_csv_lazy_tile_entry(uint32_t* __restrict__ tile_map, uint64_t ntiles) {
+    constexpr int kW = kLazyScanThreads / kWave;
+    __shared__ LzMap s_w[kW];
+    uint32_t carry = kLzRS;
+    const uint32_t id = lz_pack(lz_identity());
+    uint32_t nxt = threadIdx.x < ntiles ? tile_map[threadIdx.x] : id;
+    for (uint64_t base = 0; base < ntiles; base += kLazyScanStep) {
+        const uint64_t t = base + threadIdx.x;
+        const LzMap m = lz_unpack(nxt);
+        nxt = t + kLazyScanStep < ntiles ? tile_map[t + kLazyScanStep] : id;   // in flight while this step is scanned
+        const LzMap incl = lz_wave_inclusive(m);
+        if (lane_id() == kWave - 1) s_w[wave_id()] = incl;
+        const LzMap ex = lz_wave_exclusive(incl);
+        __syncthreads();
+        LzMap pre = lz_identity(), tot = lz_identity();
+#pragma unroll
+        for (int w = 0; w < kW; w++) {
+            if (w == wave_id()) pre = tot;
+            tot = lz_compose(tot, s_w[w]);
+        }
+        if (t < ntiles) tile_map[t] = lz_apply(lz_compose(pre, ex), carry);
+        carry = lz_apply(tot, carry);
+        __syncthreads();   // s_w is rewritten by the next step
+    }
+}
+
+template <bool TRIM, bool CMT>
+__device__ __forceinline__ void lazy_tile_marks(const uint8_t* __restrict__ d, uint64_t size, const LzTable& tb, uint32_t entry,
+                                                uint16_t* __restrict__ marks, uint64_t* __restrict__ counts, LzMap* s_map, uint32_t* s_cnt) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    uint32_t w[kCsvChunks][4];
+    LzMap incl[kCsvChunks];
+    const uint64_t t = blockIdx.x;
+    lazy_scan_tile<TRIM, CMT>(d, size, t * kCsvTile, tb, w, incl, s_map);
+    LzMap run = lz_constant(entry);   // every byte = the one true state, from here on
+    uint32_t total = 0;
+#pragma unroll
+    for (int j = 0; j < kCsvChunks; j++) {
+        LzMap mine = run;
+#pragma unroll
+        for (int wv = 0; wv < kCsvWaves; wv++) {
+            if (wv == wave_id()) mine = run;
+            run = lz_compose(run, s_map[j * kCsvWaves + wv]);
+        }
+        uint32_t mk = 0;
+        lz_walk16<TRIM, CMT, true>(w[j], tb, lz_compose(mine, lz_wave_exclusive(incl[j])), &mk);
+        total += (uint32_t)__popc(mk);
+        // eight lanes' masks = one 16-byte store
+        const uint32_t v = mk | ((uint32_t)__shfl_down(mk, 1, kWave) << 16);
+        u32x4 q;
+        q.x = v;
+        q.y = (uint32_t)__shfl_down(v, 2, kWave);
+        q.z = (uint32_t)__shfl_down(v, 4, kWave);
+        q.w = (uint32_t)__shfl_down(v, 6, kWave);
+        if ((threadIdx.x & 7u) == 0) *reinterpret_cast<u32x4*>(marks + t * (kCsvTile / 16) + (uint64_t)j * kCsvThreads + threadIdx.x) = q;
+    }
+    total = wave_sum(total);
+    if (lane_id() == 0) s_cnt[wave_id()] = total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t s = 0;
+        for (int wv = 0; wv < kCsvWaves; wv++) s += s_cnt[wv];
+        counts[t] = s;
+    }
+}
+// marks: one 16-bit mask per 16-byte chunk of every tile (ntiles * 1024 of them, 16-byte aligned); counts[t] = separators of tile t
+__global__ __launch_bounds__(kCsvThreads) void k_csv_lazy_marks(const uint8_t* __restrict__ d, uint64_t size, LzTable tb,
+                                                               const uint32_t* __restrict__ tile_entry, uint16_t* __restrict__ marks,
+                                                               uint64_t* __restrict__ counts) {
+    __shared__ LzMap s_map[kCsvChunks * kCsvWaves];
+    __shared__ uint32_t s_cnt[kCsvWaves];
+    const uint32_t entry = tile_entry[blockIdx.x];
+    if (tb.trim) {   // (uniform)
+        if (tb.comment < 0x100u) lazy_tile_marks<true, true>(d, size, tb, entry, marks, counts, s_map, s_cnt);
+        else lazy_tile_marks<true, false>(d, size, tb, entry, marks, counts, s_map, s_cnt);
+    } else {
+        if (tb.comment < 0x100u) lazy_tile_marks<false, true>(d, size, tb, entry, marks, counts, s_map, s_cnt);
+        else lazy_tile_marks<false, false>(d, size, tb, entry, marks, counts, s_map, s_cnt);
+    }
+}
+
+// positions of the separators, in text order, from the masks alone.  Workgroup b: the chunks of the tiles [b * kLazySepTiles, ...),
+// eight consecutive chunks per thread; sep_base = exclusive scan of k_csv_lazy_marks' counts.
+__global__ __launch_bounds__(kCsvThreads) void k_csv_lazy_separators(const uint16_t* __restrict__ marks, uint64_t nchunks,
+                                                                    const uint64_t* __restrict__ sep_base, uint64_t* __restrict__ seps) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    __shared__ uint32_t s_scan[kCsvWaves + 1];
+    const uint64_t c0 = ((uint64_t)blockIdx.x * kCsvThreads + threadIdx.x) * kLazyMarkChunks;
+    u32x4 q = {0, 0, 0, 0};
+    if (c0 < nchunks) q = *reinterpret_cast<const u32x4*>(marks + c0);   // (nchunks is a multiple of kLazyMarkChunks)
+    const uint32_t m[4] = {q.x, q.y, q.z, q.w};
+    const uint32_t cnt = (uint32_t)(__popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]));
+    uint32_t total;
+    const uint32_t ex = block_exclusive_sum<uint32_t, kCsvThreads>(cnt, s_scan, &total);
+    if (!cnt) return;
+    uint64_t o = sep_base[(uint64_t)blockIdx.x * kLazySepTiles] + ex;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint32_t mk = m[k];   // two chunks: bit b = byte b of the 32 bytes at chunk c0 + 2k
+        while (mk) {
+            const int b = __ffs(mk) - 1;
+            mk &= mk - 1;
+            seps[o++] = (c0 + 2 * (uint64_t)k) * 16 + (uint64_t)b;
+        }
+    }
+}
+
 // ---- 3. classify segments ---------------------------------------------------------------------------------
 // segment s = bytes [s ? seps[s-1]+1 : 0, seps[s]) (the separator itself excluded; seps[nseg-1] may be `size`).
 // keep[s] = 1 for a record, 0 for an empty or comment line.  rec range written for kept segments later.
@@ -299,11 +512,15 @@ __device__ __forceinline__ bool rune_is_space_at(const Src& d, uint64_t p, uint6
 }
 
 enum { kCsvOk = 0, kCsvBareQuote = CPH_CSV_ERR_BARE_QUOTE, kCsvQuote = CPH_CSV_ERR_QUOTE,
-       kCsvFieldCount = CPH_CSV_ERR_FIELD_COUNT };
+       kCsvFieldCount = CPH_CSV_ERR_FIELD_COUNT,
+       kCsvLazySpace = 8 };   // LAZY + TrimLeadingSpace: a multi-byte space in front of an opening quote (its error key's kind bits are 0: it
+                              // outranks a field count error of the same record, whose field count means nothing)
 
 // Sink: begin(field) ... put(byte)* ... end(field) for every COMPLETE field.  Returns the number of fields;
 // *err = kind of the first problem (the field it happens in is never end()ed).
-template <class Src, class Sink>
+// LAZY (Reader.LazyQuotes): a quote in an unquoted field is a byte; in a quoted field a quote that is followed by neither a quote,
+// Comma nor the record's end is a byte, and the record's end closes the field.  No ErrBareQuote, no ErrQuote.
+template <bool LAZY = false, class Src, class Sink>
 __device__ __forceinline__ int csv_parse_record(const Src& d, uint64_t b, uint64_t e, const CsvOpts& o, Sink& s, int* err) {
     uint64_t p = b;
     int field = 0;
@@ -311,8 +528,11 @@ __device__ __forceinline__ int csv_parse_record(const Src& d, uint64_t b, uint64
     for (;;) {
         if (o.trim) {
             int l;
-            while (p < e && rune_is_space_at(d, p, e, &l)) p += l;
+            bool wide = false;
+            while (p < e && rune_is_space_at(d, p, e, &l)) { p += l; wide |= l > 1; }
             if (p > e) p = e;
+            // the separator scan trims ASCII spaces only and took this field for an unquoted one (csv_lazy_device.hpp)
+            if (LAZY && wide && p < e && d[p] == '"') { *err = kCsvLazySpace; return field + 1; }
         }
         if (p >= e || d[p] != '"') {   // unquoted field
             uint64_t i = p;
@@ -323,7 +543,7 @@ __device__ __forceinline__ int csv_parse_record(const Src& d, uint64_t b, uint64
                 bare |= c == '"';
                 i++;
             }
-            if (bare) { *err = kCsvBareQuote; return field + 1; }
+            if (!LAZY && bare) { *err = kCsvBareQuote; return field + 1; }
             s.begin(field);
             if (s.wanted())
                 for (uint64_t k = p; k < i; k++) s.put(d[k]);
@@ -344,11 +564,16 @@ __device__ __forceinline__ int csv_parse_record(const Src& d, uint64_t b, uint64
                 s.put(c);
                 p++;
             }
-            if (p >= e) { *err = kCsvQuote; return field + 1; }   // no closing quote before the record ends
+            if (p >= e) {   // no closing quote before the record ends
+                if (LAZY) { s.end(field); return field + 1; }
+                *err = kCsvQuote;
+                return field + 1;
+            }
             p++;
             if (p < e && d[p] == '"') { s.put('"'); p++; continue; }
             if (p < e && d[p] == o.comma) { p++; s.end(field); field++; break; }
             if (p == e) { s.end(field); return field + 1; }
+            if (LAZY) { s.put('"'); continue; }   // a literal quote; the byte behind it is content of the same field
             *err = kCsvQuote;
             return field + 1;
         }
@@ -470,7 +695,7 @@ __device__ __forceinline__ int csv_split_plain(const LdsSrc& src, const CPH_LDS 
 // starts a tile: the copy pass walks the same tiles, and tile_tot[c * ntile + T] = the bytes of column c in tile T is all it
 // needs of a scan — the offsets of a tile's records are a workgroup-local prefix sum on top of the tile's base (round 5:
 // the per-record scans over every column, 1.2 of the parse's 4.9 ms, are gone).
-template <class OT>
+template <class OT, bool LAZY = false>
 __global__ __launch_bounds__(kCsvThreads) void k_csv_fields(const uint8_t* __restrict__ d, uint64_t size, RecIndex ri, uint64_t nrec,
                                                            CsvOpts o, CsvCols cols, OT* __restrict__ lens /* column c at lens + c * lens_stride */,
                                                            uint64_t lens_stride, uint32_t* __restrict__ nfields,
@@ -521,11 +746,11 @@ __global__ __launch_bounds__(kCsvThreads) void k_csv_fields(const uint8_t* __res
                 if (!o.trim && next_set((const CPH_LDS uint64_t*)s_qm, (uint32_t)(b - gb), (uint32_t)(e - gb)) == (uint32_t)(e - gb))
                     nf = csv_split_plain(src, (const CPH_LDS uint64_t*)s_cm, b, e, s);
                 else
-                    nf = csv_parse_record(src, b, e, o, s, &err);
+                    nf = csv_parse_record<LAZY>(src, b, e, o, s, &err);
             } else {
                 const GlobalSrc src{d};
                 if (e > b && src[e - 1] == '\r') e--;
-                nf = csv_parse_record(src, b, e, o, s, &err);
+                nf = csv_parse_record<LAZY>(src, b, e, o, s, &err);
             }
             nfields[r] = (uint32_t)nf;
             for (int c = 0; c < cols.ncols; c++)   // a record with fewer fields: the value is ""
@@ -533,7 +758,7 @@ __global__ __launch_bounds__(kCsvThreads) void k_csv_fields(const uint8_t* __res
                     lens[(uint64_t)c * lens_stride + r] = 0;
                     s_len[c * kCsvThreads + threadIdx.x] = 0;
                 }
-            if (err) atomicMin(err_key, ((unsigned long long)r << 3) | (unsigned long long)err);
+            if (err) atomicMin(err_key, ((unsigned long long)r << 3) | (unsigned long long)(err & 7));
         }
         if (tile_tot) {   // uniform
             for (int c = 0; c < cols.ncols; c++) {   // (a thread reads back its own LDS words: no barrier needed in front)
@@ -587,7 +812,7 @@ struct LdsDest {
 // (k_csv_fields) and its OFFSET on exit (entry nout: the column's size).  tile_scan = exclusive scan of k_csv_fields' tile totals
 // over the concatenation [ncols][ntile] (+ the grand total): column c's bytes in front of output tile t are
 // tile_scan[c * ntile + T0 + t] - tile_scan[c * ntile + T0].
-template <class OT>
+template <class OT, bool LAZY = false>
 __global__ __launch_bounds__(kCsvThreads) void k_csv_copy_fields(const uint8_t* __restrict__ d, uint64_t size, RecIndex ri, uint64_t first,
                                                                 uint64_t nout, CsvOpts o, CsvCols cols, OT* __restrict__ offs,
                                                                 uint64_t stride, uint8_t* const* __restrict__ out_data, int stage_bytes,
@@ -683,12 +908,12 @@ __global__ __launch_bounds__(kCsvThreads) void k_csv_copy_fields(const uint8_t* 
                 if (!o.trim && next_set((const CPH_LDS uint64_t*)qmask, (uint32_t)(b - gb), (uint32_t)(e - gb)) == (uint32_t)(e - gb))
                     csv_split_plain(src, (const CPH_LDS uint64_t*)cmask, b, e, s);
                 else
-                    csv_parse_record(src, b, e, o, s, &err);
+                    csv_parse_record<LAZY>(src, b, e, o, s, &err);
             } else {
                 const GlobalSrc src{d};
                 if (e > b && src[e - 1] == '\r') e--;
                 CopySink<uint8_t*, GlobalDest> s{&cols, GlobalDest{out_data, s_obase, off32, (uint32_t)threadIdx.x}, nullptr, 0, 0};
-                csv_parse_record(src, b, e, o, s, &err);
+                csv_parse_record<LAZY>(src, b, e, o, s, &err);
             }
         }
         __syncthreads();
@@ -1211,16 +1436,53 @@ static Status csv_fast_path(cph_ctx* ctx, cph_csv_table_impl* t, const uint8_t* 
     return {};
 }
 
-extern "C" {
+// The separator stage under LazyQuotes: the state scan (passes 1L-2M of the header comment) in place of the parity passes.
+// cnt: ntiles + 1 words, on return the exclusive scan of the tiles' separator counts (+ their total, also in *nsep); seps is
+// allocated here (nsep + 1 entries: the caller appends the text's end).
+static Status csv_lazy_separators(cph_ctx* ctx, const uint8_t* d, uint64_t size, const CsvOpts& o, uint64_t ntiles, DevBuf* cnt, DevBuf* seps,
+                                  uint64_t* nsep) {
+    const LzTable tb = lz_table(o.comma, o.comment, o.trim != 0);
+    const uint64_t nchunks = ntiles * (kCsvTile / 16);
+    DevBuf tmap, marks;
+    CPH_TRY(tmap.alloc(&ctx->pool, ntiles * sizeof(uint32_t)));
+    CPH_TRY(marks.alloc(&ctx->pool, nchunks * sizeof(uint16_t)));
+    {
+        ProfScope ps(ctx, "k_csv_lazy_tile_maps", (double)size);
+        hipLaunchKernelGGL(k_csv_lazy_tile_maps, dim3((unsigned)ntiles), dim3(kCsvThreads), 0, ctx->stream, d, size, tb, tmap.as<uint32_t>());
+    }
+    {
+        ProfScope ps(ctx, "k_csv_lazy_tile_entry", 8.0 * (double)ntiles);
+        hipLaunchKernelGGL(k_csv_lazy_tile_entry, dim3(1), dim3(kLazyScanThreads), 0, ctx->stream, tmap.as<uint32_t>(), ntiles);
+    }
+    {
+        ProfScope ps(ctx, "k_csv_lazy_marks", (double)size + 2.0 * (double)nchunks);
+        hipLaunchKernelGGL(k_csv_lazy_marks, dim3((unsigned)ntiles), dim3(kCsvThreads), 0, ctx->stream, d, size, tb, tmap.as<uint32_t>(),
+                           marks.as<uint16_t>(), cnt->as<uint64_t>());
+    }
+    CPH_HIP_TRY(hipGetLastError());
+    CPH_TRY(exclusive_scan_u64(ctx, cnt->as<uint64_t>(), ntiles, cnt->as<uint64_t>() + ntiles));
+    CPH_TRY(read_device_value(ctx, cnt->as<uint64_t>() + ntiles, nsep));
+    if (*nsep + 1 > 0xFFFFFFFFull) return {CPH_ERR_TOO_MANY_ROWS, "more than 2^32-1 lines"};
+    CPH_TRY(seps->alloc(&ctx->pool, (*nsep + 1) * sizeof(uint64_t)));
+    {
+        ProfScope ps(ctx, "k_csv_lazy_separators", 2.0 * (double)nchunks + 8.0 * (double)*nsep);
+        hipLaunchKernelGGL(k_csv_lazy_separators, dim3((unsigned)((ntiles + kLazySepTiles - 1) / kLazySepTiles)), dim3(kCsvThreads), 0, ctx->stream,
+                           marks.as<uint16_t>(), nchunks, cnt->as<uint64_t>(), seps->as<uint64_t>());
+    }
+    CPH_HIP_TRY(hipGetLastError());
+    return {};
+}
 
-CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, int32_t mem, const cph_csv_options* opt,
-                              const int32_t* col_index, int32_t ncols, int32_t out_mem, cph_csv_table** out) {
+// cph_csv_parse (lazy = false) and cph_csv_parse_lazy (lazy = true)
+static int32_t csv_parse_any(cph_ctx* ctx, const uint8_t* data, uint64_t size, int32_t mem, const cph_csv_options* opt,
+                             const int32_t* col_index, int32_t ncols, int32_t out_mem, cph_csv_table** out, const bool lazy) {
     if (!ctx || !out || !opt || !col_index || ncols < 1 || ncols > CPH_MAX_KEY_COLS || (size && !data)) return CPH_ERR_INVALID;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail_with(ctx, {CPH_ERR_HIP, "hipSetDevice failed"});
     *out = nullptr;
     if ((mem != CPH_MEM_HOST && mem != CPH_MEM_DEVICE) || (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE))
         return fail_with(ctx, {CPH_ERR_INVALID, "bad memory space"});
-    if (opt->lazy_quotes) return fail_with(ctx, {CPH_ERR_INVALID, "LazyQuotes is not supported by the GPU parser"});
+    if (!lazy && opt->lazy_quotes) return fail_with(ctx, {CPH_ERR_INVALID, "LazyQuotes is not supported by the GPU parser"});
+    if (lazy && opt->lazy_quotes != 1) return fail_with(ctx, {CPH_ERR_INVALID, "cph_csv_parse_lazy takes lazy_quotes = 1"});
     if (opt->comma == '"' || opt->comma == '\n' || opt->comma == '\r' || opt->comma == 0 || opt->comma >= 0x80 ||
         opt->comment >= 0x80 || (opt->comment && opt->comment == opt->comma))
         return fail_with(ctx, {CPH_ERR_INVALID, "unsupported delimiter / comment character"});
@@ -1267,11 +1529,15 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
         if (size && !fast_done) {
             const uint64_t ntiles = (size + kCsvTile - 1) / kCsvTile;
             if (ntiles > 0x7FFFFFFFull) return {CPH_ERR_INVALID, "text too large"};
-            DevBuf tq, tev, tod, cnt;
+            DevBuf tq, tev, tod, cnt, seps;
+            CPH_TRY(cnt.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint64_t)));
+            uint64_t nsep = 0;
+            if (lazy) {
+                CPH_TRY(csv_lazy_separators(ctx, d, size, o, ntiles, &cnt, &seps, &nsep));
+            } else {
             CPH_TRY(tq.alloc(&ctx->pool, ntiles * sizeof(uint32_t)));
             CPH_TRY(tev.alloc(&ctx->pool, ntiles * sizeof(uint32_t)));
             CPH_TRY(tod.alloc(&ctx->pool, ntiles * sizeof(uint32_t)));
-            CPH_TRY(cnt.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint64_t)));
             {
                 ProfScope ps(ctx, "k_csv_tile_stats", (double)size);
                 hipLaunchKernelGGL(k_csv_tile_stats, dim3((unsigned)ntiles), dim3(kCsvThreads), 0, ctx->stream, d, size,
@@ -1281,18 +1547,17 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
             hipLaunchKernelGGL(k_csv_pick_counts, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, ctx->stream, tq.as<uint32_t>(),
                                tev.as<uint32_t>(), tod.as<uint32_t>(), cnt.as<uint64_t>(), ntiles);
             CPH_TRY(exclusive_scan_u64(ctx, cnt.as<uint64_t>(), ntiles, cnt.as<uint64_t>() + ntiles));
-            uint64_t nsep = 0;
             CPH_TRY(read_device_value(ctx, cnt.as<uint64_t>() + ntiles, &nsep));
-            const uint64_t nseg = nsep + 1;   // the bytes after the last separator (possibly none) form the last segment
-            if (nseg > 0xFFFFFFFFull) return {CPH_ERR_TOO_MANY_ROWS, "more than 2^32-1 lines"};
-            {
-            DevBuf seps;
-            CPH_TRY(seps.alloc(&ctx->pool, nseg * sizeof(uint64_t)));
+            if (nsep + 1 > 0xFFFFFFFFull) return {CPH_ERR_TOO_MANY_ROWS, "more than 2^32-1 lines"};
+            CPH_TRY(seps.alloc(&ctx->pool, (nsep + 1) * sizeof(uint64_t)));
             {
                 ProfScope ps(ctx, "k_csv_separators", (double)size + 8.0 * (double)nsep);
                 hipLaunchKernelGGL(k_csv_separators, dim3((unsigned)ntiles), dim3(kCsvThreads), 0, ctx->stream, d, size,
                                    tq.as<uint32_t>(), cnt.as<uint64_t>(), seps.as<uint64_t>());
             }
+            }   // (!lazy)
+            const uint64_t nseg = nsep + 1;   // the bytes after the last separator (possibly none) form the last segment
+            {
             hipLaunchKernelGGL(k_csv_set_u64, dim3(1), dim3(1), 0, ctx->stream, seps.as<uint64_t>() + nsep, size);
             // classify; compact only when a line in the middle of the text was dropped (blank / comment)
             DevBuf keep_flag, stats;
@@ -1310,7 +1575,7 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
             const unsigned long long* hs = static_cast<const unsigned long long*>(ctx->pinned_scratch);
             nrec = hs[0];
             const bool dropped_inner = hs[1] != 0;
-            if (hs[2]) return {CPH_ERR_INVALID, "comment line containing a quote: not supported by the GPU parser"};
+            if (hs[2] && !lazy) return {CPH_ERR_INVALID, "comment line containing a quote: not supported by the GPU parser"};
             if (nrec > 0xFFFFFFFFull) return {CPH_ERR_TOO_MANY_ROWS, "more than 2^32-1 records"};
             if (!dropped_inner) {
                 ri.seps = seps.as<uint64_t>();   // record r is segment r
@@ -1358,14 +1623,14 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
                 ProfScope ps(ctx, "k_csv_fields", (double)size + (double)nrec * (12.0 + (double)osz * ncols));
                 const size_t fsmem = (size_t)stage_bytes + 16 + 2 * (size_t)csv_mask_halves(stage_bytes) * sizeof(uint16_t) +
                                      (size_t)ncols * kCsvThreads * sizeof(uint32_t);
-                if (off32)
-                    hipLaunchKernelGGL(k_csv_fields<uint32_t>, dim3(grid_for_items(nrec)), dim3(kCsvThreads), fsmem, ctx->stream, d, size, ri, nrec,
-                                       o, cc, reinterpret_cast<uint32_t*>(offs_all), stride, nfields.as<uint32_t>(), errk.as<unsigned long long>(),
-                                       stage_bytes, pad, ntile, tile_tot.as<uint64_t>());
-                else
-                    hipLaunchKernelGGL(k_csv_fields<uint64_t>, dim3(grid_for_items(nrec)), dim3(kCsvThreads), fsmem, ctx->stream, d, size, ri, nrec,
-                                       o, cc, reinterpret_cast<uint64_t*>(offs_all), stride, nfields.as<uint32_t>(), errk.as<unsigned long long>(),
-                                       stage_bytes, pad, ntile, tile_tot.as<uint64_t>());
+                auto go = [&](auto kernel, auto* lens) {
+                    hipLaunchKernelGGL(kernel, dim3(grid_for_items(nrec)), dim3(kCsvThreads), fsmem, ctx->stream, d, size, ri, nrec, o, cc, lens, stride,
+                                       nfields.as<uint32_t>(), errk.as<unsigned long long>(), stage_bytes, pad, ntile, tile_tot.as<uint64_t>());
+                };
+                if (off32 && !lazy) go(&k_csv_fields<uint32_t>, reinterpret_cast<uint32_t*>(offs_all));
+                else if (!lazy) go(&k_csv_fields<uint64_t>, reinterpret_cast<uint64_t*>(offs_all));
+                else if (off32) go(&k_csv_fields<uint32_t, true>, reinterpret_cast<uint32_t*>(offs_all));
+                else go(&k_csv_fields<uint64_t, true>, reinterpret_cast<uint64_t*>(offs_all));
             }
             if (opt->fields_per_record >= 0)
                 hipLaunchKernelGGL(k_csv_check_counts, dim3(grid_for_items(nrec)), dim3(256), 0, ctx->stream, nfields.as<uint32_t>(),
@@ -1374,6 +1639,9 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
             unsigned long long key = 0;
             CPH_TRY(read_device_value(ctx, errk.as<unsigned long long>(), &key));
             if (key != ~0ull) {
+                if ((key & 7) == 0)   // kCsvLazySpace
+                    return {CPH_ERR_INVALID, "LazyQuotes with TrimLeadingSpace: a non-ASCII Unicode space in front of an opening quote is not "
+                                             "supported by the GPU parser"};
                 t->pub.error_kind = (int32_t)(key & 7);
                 t->pub.error_record = key >> 3;
                 good = key >> 3;
@@ -1419,16 +1687,20 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
             ProfScope ps(ctx, "k_csv_copy_fields", (double)size + out_bytes + (double)nout * (8.0 + (double)osz * ncols));
             const size_t smem = (size_t)(stage_bytes + 16) + (size_t)(stage_bytes + 32 * kMaxKeyCols) +
                                 2 * (size_t)csv_mask_halves(stage_bytes) * sizeof(uint16_t) + (size_t)ncols * (kCsvThreads + 1) * sizeof(uint32_t);
-            CPH_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_csv_copy_fields<uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            CPH_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_csv_copy_fields<uint64_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            if (off32)
-                hipLaunchKernelGGL(k_csv_copy_fields<uint32_t>, dim3(grid_for_items(nout)), dim3(kCsvThreads), smem, ctx->stream, d, size, ri, first,
-                                   nout, o, cc, reinterpret_cast<uint32_t*>(offs_all) + first, stride, ptrs.as<uint8_t*>(), stage_bytes,
-                                   tile_tot.as<uint64_t>(), ntile, T0);
-            else
-                hipLaunchKernelGGL(k_csv_copy_fields<uint64_t>, dim3(grid_for_items(nout)), dim3(kCsvThreads), smem, ctx->stream, d, size, ri, first,
-                                   nout, o, cc, reinterpret_cast<uint64_t*>(offs_all) + first, stride, ptrs.as<uint8_t*>(), stage_bytes,
-                                   tile_tot.as<uint64_t>(), ntile, T0);
+            Status st{};
+            auto go = [&](auto kernel, auto* offs) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
+                    st = {CPH_ERR_HIP, "hipFuncSetAttribute failed (k_csv_copy_fields)"};
+                    return;
+                }
+                hipLaunchKernelGGL(kernel, dim3(grid_for_items(nout)), dim3(kCsvThreads), smem, ctx->stream, d, size, ri, first, nout, o, cc, offs + first,
+                                   stride, ptrs.as<uint8_t*>(), stage_bytes, tile_tot.as<uint64_t>(), ntile, T0);
+            };
+            if (off32 && !lazy) go(&k_csv_copy_fields<uint32_t>, reinterpret_cast<uint32_t*>(offs_all));
+            else if (!lazy) go(&k_csv_copy_fields<uint64_t>, reinterpret_cast<uint64_t*>(offs_all));
+            else if (off32) go(&k_csv_copy_fields<uint32_t, true>, reinterpret_cast<uint32_t*>(offs_all));
+            else go(&k_csv_copy_fields<uint64_t, true>, reinterpret_cast<uint64_t*>(offs_all));
+            CPH_TRY(st);
             CPH_HIP_TRY(hipGetLastError());
         }
         }   // (!fast_done)
@@ -1448,6 +1720,18 @@ CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, 
         return deliver(ctx, &t->own, parts, 2 * ncols, out_mem);
     };
     return finish_call(ctx, t, run(), out);
+}
+
+extern "C" {
+
+CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, int32_t mem, const cph_csv_options* opt,
+                              const int32_t* col_index, int32_t ncols, int32_t out_mem, cph_csv_table** out) {
+    return csv_parse_any(ctx, data, size, mem, opt, col_index, ncols, out_mem, out, false);
+}
+
+CPH_API int32_t cph_csv_parse_lazy(cph_ctx* ctx, const uint8_t* data, uint64_t size, int32_t mem, const cph_csv_options* opt,
+                                   const int32_t* col_index, int32_t ncols, int32_t out_mem, cph_csv_table** out) {
+    return csv_parse_any(ctx, data, size, mem, opt, col_index, ncols, out_mem, out, true);
 }
 
 CPH_API void cph_csv_table_release(cph_csv_table* pub) { release_result<cph_csv_table_impl>(pub); }

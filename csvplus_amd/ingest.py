@@ -69,8 +69,9 @@ class _Raw:   # minimal object with data_ptr()
 
 def csv_parse(ctx: N.Context, data, col_index, *, comma=b",", comment=None, trim_leading_space=False,
               lazy_quotes=False, fields_per_record=0, skip_records=0, out_mem=N.CPH_MEM_HOST,
-              device_ptr=None, size=None) -> CsvTable:
-    """data: bytes / numpy uint8 (host), or pass device_ptr + size for text already in HBM."""
+              device_ptr=None, size=None, _entry="strict") -> CsvTable:
+    """data: bytes / numpy uint8 (host), or pass device_ptr + size for text already in HBM.
+    cph_csv_parse: lazy_quotes=True is passed on and refused by the library; csv_parse_lazy is the call that takes it."""
     opt = N.cph_csv_options(ord(comma), ord(comment) if comment else 0, 1 if trim_leading_space else 0,
                             1 if lazy_quotes else 0, int(fields_per_record), int(skip_records))
     idx = (C.c_int32 * len(col_index))(*[int(i) for i in col_index])
@@ -80,9 +81,20 @@ def csv_parse(ctx: N.Context, data, col_index, *, comma=b",", comment=None, trim
     else:
         keep = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data)
         ptr, n, mem = C.c_void_p(keep.ctypes.data if len(keep) else 0), len(keep), N.CPH_MEM_HOST
-    ctx._check(ctx.lib.cph_csv_parse(ctx.handle, ptr, n, mem, C.byref(opt), idx, len(col_index), out_mem, C.byref(out)))
+    fn = ctx.lib.cph_csv_parse_lazy if _entry == "lazy" else ctx.lib.cph_csv_parse
+    ctx._check(fn(ctx.handle, ptr, n, mem, C.byref(opt), idx, len(col_index), out_mem, C.byref(out)))
     del keep
     return CsvTable(ctx, out, out_mem)
+
+
+def csv_parse_lazy(ctx: N.Context, data, col_index, *, comma=b",", comment=None, trim_leading_space=False,
+                   fields_per_record=0, skip_records=0, out_mem=N.CPH_MEM_HOST, device_ptr=None, size=None) -> CsvTable:
+    """csv_parse under Reader.LazyQuotes() (cph_csv_parse_lazy): a quote inside an unquoted field, and a quote inside a
+    quoted field that is followed by neither a quote, the delimiter nor the line end, are bytes; the text's end inside
+    quotes ends the field.  The only error kind left is the field count."""
+    return csv_parse(ctx, data, col_index, comma=comma, comment=comment, trim_leading_space=trim_leading_space,
+                     lazy_quotes=True, fields_per_record=fields_per_record, skip_records=skip_records, out_mem=out_mem,
+                     device_ptr=device_ptr, size=size, _entry="lazy")
 
 
 class CsvError(ValueError):
@@ -116,12 +128,14 @@ def _trim_left_go(line: bytes) -> bytes:
     return line[i:]
 
 
-def first_record(text: bytes, comma=b",", comment=None, trim_leading_space=False):
+def first_record(text: bytes, comma=b",", comment=None, trim_leading_space=False, lazy_quotes=False):
     """The first record of `text` by the rules of Go's encoding/csv Reader.readRecord — the record makeHeader
     (csvplus.go:1149-1206) reads before the body is handed to the device.  Line endings: "\r\n" counts as "\n",
     a final "\r" before EOF is dropped; lines that are empty after that, or start with the comment rune, are
     skipped ("\r\r\n" is NOT empty: it is the record ["\r"]); a quote inside an unquoted field is ErrBareQuote,
     anything but a separator or the line end behind a closing quote is ErrQuote, a quoted field may span lines.
+    lazy_quotes (Reader.LazyQuotes): neither is an error — a quote in an unquoted field is a byte, a quote in a quoted
+    field that is followed by neither a quote, a separator nor the line end is a byte, EOF inside quotes ends the field.
     Returns the list of fields (bytes), or None at EOF.  Raises CsvError."""
     pos, n, lineno = 0, len(text), 0
     sep = comma[0]
@@ -159,7 +173,7 @@ def first_record(text: bytes, comma=b",", comment=None, trim_leading_space=False
         if not line.startswith(b'"'):                       # unquoted field
             i = line.find(comma)
             field = line[:i] if i >= 0 else line[:len(line) - (1 if line.endswith(b"\n") else 0)]
-            if b'"' in field:
+            if b'"' in field and not lazy_quotes:
                 raise CsvError("bare \" in non-quoted field", rec_line)
             fields.append(field)
             if i >= 0:
@@ -183,14 +197,22 @@ def first_record(text: bytes, comma=b",", comment=None, trim_leading_space=False
                 elif line in (b"", b"\n"):                  # closing quote at the end of the line
                     fields.append(bytes(buf))
                     return fields
+                elif lazy_quotes:                            # a literal quote; the field stays quoted
+                    buf += b'"'
                 else:
                     raise CsvError("extraneous or missing \" in quoted-field", rec_line)
             elif line:                                       # the field continues on the next line
                 buf += line
                 nxt = read_line()
                 if nxt is None:                              # EOF inside quotes
+                    if lazy_quotes:
+                        fields.append(bytes(buf))
+                        return fields
                     raise CsvError("extraneous or missing \" in quoted-field", rec_line)
                 line = nxt
+            elif lazy_quotes:                                # EOF right behind the opening quote or a literal one
+                fields.append(bytes(buf))
+                return fields
             else:
                 raise CsvError("extraneous or missing \" in quoted-field", rec_line)
 
@@ -244,12 +266,11 @@ def read_csv(ctx: N.Context, text: bytes, *, select=None, expect_header=None, as
 
     Header modes as in the reference (resolve_header; assume_header = {name: index}, no header line: AssumeHeader
     :963-980).  num_fields is csv.Reader.FieldsPerRecord (0 = as the first record, the header included; <0 = any,
-    short records padded with "" :1121-1122).
+    short records padded with "" :1121-1122).  lazy_quotes = Reader.LazyQuotes() (csvplus.go:982-987): the header line and
+    the body are read by the lazy rules (first_record(lazy_quotes=True), csv_parse_lazy).
     Returns the table with `.names`; `.error_kind/.error_record` report a parse error the way the reference
     returns it after delivering the rows before it.  Header problems raise (the reference fails at line 1).
     """
-    if lazy_quotes:   # Reader.LazyQuotes (csvplus.go:1040-1043): the device parser has no lazy mode
-        raise NotImplementedError("LazyQuotes is not supported by the device CSV reader")
     skip = 0
     if assume_header is not None:
         if not assume_header:
@@ -258,13 +279,13 @@ def read_csv(ctx: N.Context, text: bytes, *, select=None, expect_header=None, as
         if any(v < 0 for v in hdr.values()):
             raise ValueError("header spec: negative index")
         if num_fields >= 0:   # csvplus.go:1123-1127: an index beyond the record is an error unless padding is allowed
-            first = first_record(text, comma, comment, trim_leading_space)
+            first = first_record(text, comma, comment, trim_leading_space, lazy_quotes)
             if first is not None:
                 for nm, ix in hdr.items():
                     if ix >= (num_fields if num_fields > 0 else len(first)):
                         raise KeyError(f"column not found: {nm!r} ({ix})")
     else:
-        first = first_record(text, comma, comment, trim_leading_space)
+        first = first_record(text, comma, comment, trim_leading_space, lazy_quotes)
         if first is None:
             raise EOFError("EOF")   # io.EOF from the header read, csvplus.go:1150-1154
         skip = 1
@@ -273,9 +294,9 @@ def read_csv(ctx: N.Context, text: bytes, *, select=None, expect_header=None, as
     parts = []
     for i in range(0, len(names), N.CPH_MAX_KEY_COLS):   # the C ABI takes up to 16 columns per call
         batch = names[i:i + N.CPH_MAX_KEY_COLS]
-        parts.append(csv_parse(ctx, text, [hdr[n] for n in batch], comma=comma, comment=comment,
-                               trim_leading_space=trim_leading_space, fields_per_record=num_fields, skip_records=skip,
-                               out_mem=out_mem))
+        parts.append((csv_parse_lazy if lazy_quotes else csv_parse)(
+            ctx, text, [hdr[n] for n in batch], comma=comma, comment=comment, trim_leading_space=trim_leading_space,
+            fields_per_record=num_fields, skip_records=skip, out_mem=out_mem))
     t = parts[0] if len(parts) == 1 else CsvTableGroup(parts)
     t.names = names
     return t

@@ -37,6 +37,10 @@ class Table:
 
 
 def read_table(ctx: N.Context, text: bytes, select=None, **kw) -> Table:
+    """A CSV file as device columns: ingest.read_csv with its keywords (expect_header, assume_header, comma, comment,
+    trim_leading_space, num_fields, lazy_quotes).  lazy_quotes=True is Reader.LazyQuotes(): header line and body are read
+    by Go's lazy rules (cph_csv_parse_lazy), so a file with `5" nails` or `He said "hi"` in it reaches join_to_csv /
+    filter_to_csv / totals_to_csv like any other table.  A parse error raises ingest.CsvError."""
     t = ingest.read_csv(ctx, text, select=select, out_mem=N.CPH_MEM_DEVICE, **kw)
     if t.error_kind:
         err = ingest.CsvError(t.error_kind, t.error_record)
@@ -47,7 +51,9 @@ def read_table(ctx: N.Context, text: bytes, select=None, **kw) -> Table:
 
 def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict | None = None, out_mem: int = N.CPH_MEM_HOST,
                 fused: bool = True, positions: bool | None = None, where=None, skip: int = 0, limit=None, computed=None):
-    """steps: [(index_table, index_key_column, stream_key_column), ...] — each index must be unique on its key
+    """stream and the index tables come from read_table (read_table(..., lazy_quotes=True) for files that need
+    Reader.LazyQuotes()).
+    steps: [(index_table, index_key_column, stream_key_column), ...] — each index must be unique on its key
     (UniqueIndexOn; a duplicate raises like the reference's error :751).  out_columns: [(output name, table,
     column)] where table is `stream` or one of the index tables; the caller resolves name collisions the way
     mergeRows does (the stream's column wins, :578-580) by naming the table it wants.
@@ -275,7 +281,7 @@ def join_to_json(ctx: N.Context, stream: Table, steps, out_columns=None, timings
 def filter_to_csv(ctx: N.Context, table: Table, pred, out_columns, mode: str = "where", first_row: int = 0, nrows=None,
                   skip: int = 0, limit=None, out_mem: int = N.CPH_MEM_HOST, computed=None, order_by=None):
     """The reference's headline shape, FromFile(...).Filter(Like(...)).ToCsv(...), on the device: the rows of ONE table
-    where `pred` holds (mode "where"; "take_while" / "drop_while" for TakeWhile / DropWhile; first_row / nrows: Drop / Top
+    (read_table; with lazy_quotes=True for FromFile(...).LazyQuotes()) where `pred` holds (mode "where"; "take_while" / "drop_while" for TakeWhile / DropWhile; first_row / nrows: Drop / Top
     in front of the filter, skip / limit: behind it), written as CSV.  out_columns: column names, or (output name, column)
     pairs.  computed: {name: template} — .Map(row[name] = template(row)) behind the filter (csvplus_amd.mapping), in dict
     order over the rows kept; an output column of a computed name takes the computed column.

@@ -1052,9 +1052,25 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  * string column per requested index.  Semantics are Go's encoding/csv Reader
  * as csvplus configures it (csvplus.go:1088-1093): Comma, Comment,
  * TrimLeadingSpace, FieldsPerRecord; "\r\n" -> "\n"; empty and comment lines
- * skipped; `""` = literal quote.  LazyQuotes = 1 is rejected (CPH_ERR_INVALID),
- * and so is a comment line that contains a '"' (Go skips it uninterpreted; the
- * parallel quote-parity scan cannot).  A record with fewer fields than a
+ * skipped; `""` = literal quote.  cph_csv_parse rejects LazyQuotes = 1
+ * (CPH_ERR_INVALID; cph_csv_parse_lazy takes it), and so it does a comment line
+ * that contains a '"' (Go skips it uninterpreted; the parallel quote-parity scan
+ * cannot — the state scan of cph_csv_parse_lazy can, and accepts such lines).
+ *
+ * cph_csv_parse_lazy = Reader.LazyQuotes() (csvplus.go:982-987): readRecord with
+ * LazyQuotes = true.  A field whose first byte (after trimming, if on) is not '"'
+ * is unquoted and runs to the next Comma or line end; quotes inside it are bytes
+ * (`a""b` stays `a""b`).  In a quoted field `""` is one '"', '"' + Comma ends the
+ * field, '"' + line end ("\n", "\r\n", the text's end, "\r" + the text's end) ends
+ * field and record, '"' + anything else is a literal '"' and the field stays
+ * quoted; a line end inside it is content (comment character and blank lines are
+ * not looked at there), and the text's end inside it ends it silently.  There is
+ * no ErrBareQuote and no ErrQuote: CPH_CSV_ERR_FIELD_COUNT is the only error_kind.
+ * Everything else is as in cph_csv_parse.  One limit, detected: with
+ * trim_leading_space, a field whose trimmed-off prefix holds a NON-ASCII Unicode
+ * space (U+0085, U+00A0, U+1680, U+2000..) and whose next byte is '"' — Go reads
+ * it as quoted, the device's separator scan trims ASCII spaces only — fails the
+ * call with CPH_ERR_INVALID (the message names the case).  A record with fewer fields than a
  * requested index yields "" for that column — callers that want the
  * reference's "missing column" error (csvplus.go:1121-1124) set
  * fields_per_record > 0, as csvplus itself does with NumFields.
@@ -1069,7 +1085,7 @@ typedef struct {
     uint8_t  comma;               /* Reader.delimiter (csvplus.go:1088); ASCII, not '"' '\r' '\n' */
     uint8_t  comment;             /* Reader.comment   (csvplus.go:1089); 0 = none                 */
     uint8_t  trim_leading_space;  /* csvplus.go:1092                                              */
-    uint8_t  lazy_quotes;         /* csvplus.go:1091; must be 0                                   */
+    uint8_t  lazy_quotes;         /* csvplus.go:1091; 0 here; cph_csv_parse_lazy takes 1          */
     int32_t  fields_per_record;   /* csv.Reader.FieldsPerRecord: >0 exact, 0 = as the first record, <0 = any */
     uint64_t skip_records;        /* leading records to drop from the output (the header line; they are
                                      still parsed, validated and counted in error_record)          */
@@ -1089,6 +1105,9 @@ typedef struct {
  * col_index[ncols] = 0-based field indices wanted, 1 <= ncols <= CPH_MAX_KEY_COLS. */
 CPH_API int32_t cph_csv_parse(cph_ctx* ctx, const uint8_t* data, uint64_t size, int32_t mem, const cph_csv_options* opt,
                               const int32_t* col_index, int32_t ncols, int32_t out_mem, cph_csv_table** out);
+/* The same call under LazyQuotes rules (above): opt->lazy_quotes must be 1, CPH_ERR_INVALID otherwise. */
+CPH_API int32_t cph_csv_parse_lazy(cph_ctx* ctx, const uint8_t* data, uint64_t size, int32_t mem, const cph_csv_options* opt,
+                                   const int32_t* col_index, int32_t ncols, int32_t out_mem, cph_csv_table** out);
 CPH_API void    cph_csv_table_release(cph_csv_table* t);
 
 /* ---- Find / SubIndex bounds (csvplus.go:870-891) ----------------------------- */
