@@ -152,6 +152,7 @@ CPH_PRED_INT_LT, CPH_PRED_INT_LE, CPH_PRED_INT_EQ, CPH_PRED_INT_NE, CPH_PRED_INT
 CPH_PRED_FLT_LT, CPH_PRED_FLT_LE, CPH_PRED_FLT_EQ, CPH_PRED_FLT_NE, CPH_PRED_FLT_GE, CPH_PRED_FLT_GT = 24, 25, 26, 27, 28, 29
 CPH_PRED_STR_LT, CPH_PRED_STR_LE, CPH_PRED_STR_EQ, CPH_PRED_STR_NE, CPH_PRED_STR_GE, CPH_PRED_STR_GT = 32, 33, 34, 35, 36, 37
 CPH_PRED_HAS_PREFIX, CPH_PRED_HAS_SUFFIX, CPH_PRED_CONTAINS = 40, 41, 42
+CPH_PRED_TIME_LT, CPH_PRED_TIME_LE, CPH_PRED_TIME_EQ, CPH_PRED_TIME_NE, CPH_PRED_TIME_GE, CPH_PRED_TIME_GT = 48, 49, 50, 51, 52, 53
 CPH_PRED_MAX_OPS, CPH_PRED_MAX_LIKE, CPH_PRED_MAX_STACK = 64, 32, 32
 CPH_FILTER_WHERE, CPH_FILTER_TAKE_WHILE, CPH_FILTER_DROP_WHILE = 0, 1, 2
 CPH_NO_LIMIT = 0xFFFFFFFFFFFFFFFF
@@ -171,6 +172,7 @@ class cph_rowlist(C.Structure):
 
 
 CPH_NUM_INT64, CPH_NUM_FLOAT64 = 1, 2
+CPH_NUM_TIME_UNIX, CPH_NUM_TIME_UNIXNANO = 4, 5   # RFC 3339 text -> t.Unix() / t.UnixNano(), int64
 CPH_NUM_OK, CPH_NUM_ERR_SYNTAX, CPH_NUM_ERR_RANGE, CPH_NUM_ERR_UNSUPPORTED = 0, 1, 2, 3
 CPH_NUM_ERR_DIV_ZERO, CPH_NUM_ERR_CONVERT = 4, 5   # cph_num_eval only
 CPH_NO_ROW = 0xFFFFFFFFFFFFFFFF
@@ -201,6 +203,7 @@ class cph_expr_nums(C.Structure):
 
 CPH_MAP_LITERAL, CPH_MAP_COLUMN, CPH_MAP_INT64, CPH_MAP_FLOAT64 = 1, 2, 3, 4
 CPH_MAP_SLICE = 8
+CPH_MAP_TIME = 10   # Unix seconds written as RFC 3339; prec = the zone in minutes east of UTC
 
 
 class cph_map_slice(C.Structure):

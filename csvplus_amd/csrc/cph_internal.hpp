@@ -959,8 +959,9 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
                     DevBuf* status, NumColStats* st);
 
 // filter.hip: a cph_pred_op program evaluated into one bit per row — what cph_filter_rows (WHERE) and cph_map_switch share.
-struct PredFloatCol {   // a column converted for the float terms of a call: one conversion, whichever program asks first
+struct PredFloatCol {   // a column converted for the float or time terms of a call: one conversion, whichever program asks first
     int col;
+    int32_t kind = CPH_NUM_FLOAT64;   // ... or CPH_NUM_TIME_UNIX: the same column may be converted once as each
     DevBuf values, status;
 };
 struct PredBitmap {

@@ -30,14 +30,21 @@
 // per-value routines live in strpred_device.hpp (host-compilable, tested on the CPU); here they read the value through
 // load_value_chunk and the literal as a LIKE's literal is kept: lit8, or the literal block in LDS / global memory.  A program
 // with such a term launches the STR = true instantiations; every other program launches exactly what it launched before.
+//
+// Time terms (CPH_PRED_TIME_*) take the route of the float terms: the column is converted first through convert_rows
+// (CPH_NUM_TIME_UNIX, once per column and call) and k_pred_eval compares the int64 seconds with their status; the literal is RFC
+// 3339 text the host converts with the same routine (timeparse_device.hpp).  A program with such a term launches the TIM = true
+// instantiations (which carry the numeric code too); every other program launches exactly what it launched before.
 // The way from a cph_pred_op program to the bitmap (terms, literal block, float columns, the k_pred_eval<true, NUM> launch) is
 // pred_eval_bitmap (cph_internal.hpp): the WHERE mode calls it, and so does cph_map_switch (map_switch.hip), once per case.
 #include <algorithm>
 #include <cstring>
 #include <new>
+#include <string>
 
 #include "numparse_device.hpp"
 #include "strpred_device.hpp"
+#include "timeparse_device.hpp"
 
 namespace cph {
 
@@ -49,7 +56,8 @@ constexpr int kFiltWaveWords = kFiltWords / (kMatThreads / kWave);   // 8 words 
 constexpr int kLitLds    = 4096;                       // literal bytes kept in LDS; more than that stay in global memory
 
 enum : uint32_t { kTermBytes = 0, kTermFix8 = 1, kTermInt = 2, kTermF64 = 3,     // low byte of PredTerm::kind
-                  kTermStrCmp = 4, kTermPrefix = 5, kTermSuffix = 6, kTermContains = 7 };   // STR instantiations only
+                  kTermStrCmp = 4, kTermPrefix = 5, kTermSuffix = 6, kTermContains = 7,    // STR instantiations only
+                  kTermTime = 8 };                                                          // TIM instantiations only
 // bits 8..11 of a numeric or kTermStrCmp term's kind: which outcomes of (value ? literal) make the relation hold
 enum : uint32_t { kCmpLess = 1, kCmpEqual = 2, kCmpGreater = 4, kCmpUnordered = 8 };
 constexpr uint8_t kTermNever = 0xFF;                   // a LIKE decided on the host: no such column, or a fixed width other than the literal's
@@ -61,9 +69,9 @@ struct PredTerm {
     uint32_t lit_off, len;
     int32_t  col;
     uint32_t kind;   // kTermFix8: a fixed-width column of 8 bytes on an 8-byte aligned base — one aligned load and one compare
-                     // kTermInt / kTermF64: lit8 = the literal's bits, the relation in bits 8..11
+                     // kTermInt / kTermF64 / kTermTime: lit8 = the literal's bits (kTermTime: its Unix seconds), the relation in bits 8..11
                      // kTermStrCmp .. kTermContains: the literal as a LIKE's (lit8 / lit_off, len); kTermStrCmp: the relation in bits 8..11
-    const double*  fval;   // kTermF64: the converted column, entry i = row first_row + i of the selection ...
+    const double*  fval;   // kTermF64 / kTermTime: the converted column (kTermTime: int64 seconds), entry i = row first_row + i of the selection ...
     const uint8_t* fstat;  // ... and its CPH_NUM_* status bytes
 };
 struct PredProg {    // travels in the kernel arguments (~0.9 KB): a wave reads it with scalar loads
@@ -120,8 +128,8 @@ __device__ __forceinline__ bool str_term(uint32_t what, uint32_t rel, const DevC
 // BITMAP: bitmap[tile * 32 + w] bit b = the predicate holds for row tile * 2048 + 64 w + b of the call (rows >= n: 0),
 //         counts[tile] = the tile's set bits.
 // else:   *first_fail = min(*first_fail, the first row where it does not hold); the host presets it to n.
-// STR: the program has a term of strpred_device.hpp; NUM: a numeric one
-template <bool BITMAP, bool NUM, bool STR = false>
+// STR: the program has a term of strpred_device.hpp; NUM: a numeric one; TIM (with NUM): a time term
+template <bool BITMAP, bool NUM, bool STR = false, bool TIM = false>
 __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds ids, PredProg prog, uint64_t first_row, uint64_t n,
                                                           uint64_t* __restrict__ bitmap, uint32_t* __restrict__ counts,
                                                           unsigned long long* first_fail) {
@@ -193,6 +201,22 @@ __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds 
                     for (int k = 0; k < kFiltPhase; k++) {
                         const uint32_t cls = v[k] < lit ? kCmpLess : v[k] == lit ? kCmpEqual : v[k] > lit ? kCmpGreater : kCmpUnordered;
                         mask[k] |= (uint32_t)(st[k] == CPH_NUM_OK && (rel & cls) != 0) << t;
+                    }
+                } else if (TIM && (tm.kind & 0xFFu) == kTermTime) {
+                    const uint32_t rel = tm.kind >> 8;
+                    const int64_t lit = (int64_t)tm.lit8;
+                    const int64_t* tval = reinterpret_cast<const int64_t*>(tm.fval);
+                    int64_t v[kFiltPhase];
+                    uint32_t st[kFiltPhase];
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {
+                        v[k] = tval[pos[k] - first_row];
+                        st[k] = tm.fstat[pos[k] - first_row];
+                    }
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {
+                        const uint32_t cls = v[k] < lit ? kCmpLess : v[k] == lit ? kCmpEqual : kCmpGreater;
+                        mask[k] |= (uint32_t)(st[k] == CPH_NUM_OK && (rel & cls) != 0) << t;   // a row that does not convert: false
                     }
                 } else if (STR && (tm.kind & 0xFFu) >= kTermStrCmp) {
                     const uint32_t what = tm.kind & 0xFFu, rel = tm.kind >> 8;   // uniform: the wave diverges on the values' lengths alone
@@ -333,6 +357,32 @@ void set_range(cph_rowlist_impl* r, uint64_t first, uint64_t n, int32_t bits, in
     r->pub.mem = out_mem;
 }
 
+// the functor of timeparse_device.hpp over a literal in host memory
+struct HostTimeChunks {
+    const uint8_t* p;
+    uint64_t len;
+    uint64_t operator()(int j) const {
+        uint64_t w = 0;
+        const uint64_t at = 8ull * (uint64_t)j;
+        if (at < len) memcpy(&w, p + at, (size_t)(len - at < 8 ? len - at : 8));
+        return w;
+    }
+};
+
+// a time term's literal -> its Unix seconds, with the routine the device runs; a literal with a fraction is refused
+Status time_literal(const cph_strval& value, int64_t* secs) {
+    const HostTimeChunks v{value.data, value.len};
+    const std::string text(reinterpret_cast<const char*>(value.data ? value.data : (const uint8_t*)""), (size_t)(value.len < 64 ? value.len : 64));
+    if (value.len > 35) return {CPH_ERR_INVALID, "cph_filter_rows: a time term's literal is no RFC 3339 timestamp: \"" + text + "...\""};
+    const uint32_t st = parse_rfc3339(value.len, v(0), v(1), v(2), v(3), v, false, secs);
+    if (st != CPH_NUM_OK)
+        return {CPH_ERR_INVALID, "cph_filter_rows: a time term's literal \"" + text + "\" does not convert (" +
+                                     (st == CPH_NUM_ERR_SYNTAX ? "invalid syntax" : st == CPH_NUM_ERR_RANGE ? "a field out of range" : "not decided by this library") + ")"};
+    if (value.len > 20 && value.data[19] == '.')
+        return {CPH_ERR_INVALID, "cph_filter_rows: a time term's literal \"" + text + "\" has a fraction: the term compares whole seconds"};
+    return {};
+}
+
 // the program's shape: every rule of the header's comment that does not need the columns
 Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
     if (nops < 1 || nops > CPH_PRED_MAX_OPS) return {CPH_ERR_INVALID, "cph_filter_rows: a program has 1..64 ops"};
@@ -362,6 +412,16 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
                 if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE and numeric terms"};
                 depth++;
                 break;
+            case CPH_PRED_TIME_LT: case CPH_PRED_TIME_LE: case CPH_PRED_TIME_EQ: case CPH_PRED_TIME_NE: case CPH_PRED_TIME_GE: case CPH_PRED_TIME_GT: {
+                if (o.arg < -1 || o.arg >= ncols) return {CPH_ERR_INVALID, "cph_filter_rows: time term column outside -1..ncols-1"};
+                if (!o.value.data && o.value.len) return {CPH_ERR_INVALID, "cph_filter_rows: a time term's literal with bytes but no data pointer"};
+                int64_t secs = 0;
+                Status s = time_literal(o.value, &secs);
+                if (!s.ok()) return s;
+                if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE, numeric, string and time terms"};
+                depth++;
+                break;
+            }
             case CPH_PRED_NOT:
                 if (depth < 1) return {CPH_ERR_INVALID, "cph_filter_rows: stack underflow (NOT on an empty stack)"};
                 break;
@@ -371,7 +431,7 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
                 depth += 1 - o.arg;
                 break;
             default:
-                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4, 16..21, 24..29, 32..37, 40..42)"};
+                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4, 16..21, 24..29, 32..37, 40..42, 48..53)"};
         }
         if (depth > CPH_PRED_MAX_STACK) return {CPH_ERR_INVALID, "cph_filter_rows: stack deeper than 32"};
     }
@@ -382,6 +442,7 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
 bool is_int_cmp(int32_t op) { return op >= CPH_PRED_INT_LT && op <= CPH_PRED_INT_GT; }
 bool is_flt_cmp(int32_t op) { return op >= CPH_PRED_FLT_LT && op <= CPH_PRED_FLT_GT; }
 bool is_str_cmp(int32_t op) { return op >= CPH_PRED_STR_LT && op <= CPH_PRED_STR_GT; }
+bool is_time_cmp(int32_t op) { return op >= CPH_PRED_TIME_LT && op <= CPH_PRED_TIME_GT; }
 bool is_str_term(int32_t op) { return is_str_cmp(op) || (op >= CPH_PRED_HAS_PREFIX && op <= CPH_PRED_CONTAINS); }
 // LT LE EQ NE GE GT -> the outcomes under which the relation holds (IEEE: unordered satisfies NE alone)
 uint32_t rel_outcomes(int32_t rel) {
@@ -396,6 +457,7 @@ struct BuiltProg {   // a program as k_pred_eval takes it
     double col_bytes = 0;   // byte model: what the evaluation reads of the columns
     bool numeric = false;   // the NUM instantiations
     bool strings = false;   // the STR instantiations
+    bool times = false;     // the TIM instantiations
 };
 
 // fcols: the float columns converted so far in this call (reused, appended to)
@@ -408,6 +470,35 @@ Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, cons
     for (int q = 0; q < nops; q++) {
         pp.op[q] = (uint8_t)prog[q].op;
         pp.arg[q] = (uint8_t)prog[q].arg;
+        if (is_time_cmp(prog[q].op)) {   // a term bit too: the column converted first, as for a float term
+            const int c = prog[q].arg;
+            pp.op[q] = (uint8_t)CPH_PRED_LIKE;
+            if (c < 0) {
+                pp.arg[q] = kTermNever;
+                continue;
+            }
+            bp->numeric = bp->times = true;
+            PredTerm& t = pp.term[pp.nterms];
+            pp.arg[q] = (uint8_t)pp.nterms++;
+            t.col = c;
+            int64_t secs = 0;
+            CPH_TRY(time_literal(prog[q].value, &secs));
+            t.lit8 = (uint64_t)secs;
+            t.kind = kTermTime | (rel_outcomes(prog[q].op - CPH_PRED_TIME_LT) << 8);
+            size_t f = 0;
+            while (f < fcols->size() && ((*fcols)[f].col != c || (*fcols)[f].kind != CPH_NUM_TIME_UNIX)) f++;
+            if (f == fcols->size()) {
+                fcols->emplace_back();
+                (*fcols)[f].col = c;
+                (*fcols)[f].kind = CPH_NUM_TIME_UNIX;
+                NumColStats st;
+                CPH_TRY(convert_rows(ctx, arg.c[c], ids.ids[c], first_row, n, CPH_NUM_TIME_UNIX, &(*fcols)[f].values, &(*fcols)[f].status, &st));
+                bp->col_bytes += 9.0 * (double)n;   // the converted column read back (its conversion is timed on its own)
+            }
+            t.fval = (*fcols)[f].values.as<double>();
+            t.fstat = (*fcols)[f].status.as<uint8_t>();
+            continue;
+        }
         if (is_int_cmp(prog[q].op) || is_flt_cmp(prog[q].op)) {   // a term bit like a LIKE: the kernel's program sees a LIKE
             const int c = prog[q].arg;
             pp.op[q] = (uint8_t)CPH_PRED_LIKE;
@@ -424,7 +515,7 @@ Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, cons
             t.kind = (flt ? kTermF64 : kTermInt) | (rel_outcomes(prog[q].op - (flt ? CPH_PRED_FLT_LT : CPH_PRED_INT_LT)) << 8);
             if (flt) {
                 size_t f = 0;
-                while (f < fcols->size() && (*fcols)[f].col != c) f++;
+                while (f < fcols->size() && ((*fcols)[f].col != c || (*fcols)[f].kind != CPH_NUM_FLOAT64)) f++;
                 if (f == fcols->size()) {
                     fcols->emplace_back();
                     (*fcols)[f].col = c;
@@ -499,7 +590,11 @@ template <bool BITMAP>
 void launch_pred_eval(cph_ctx* ctx, const BuiltProg& bp, const ColsArg& arg, const ColIds& ids, uint64_t first_row, uint64_t n, uint64_t ntiles,
                       uint64_t* bitmap, uint32_t* counts, unsigned long long* first_fail) {
     const dim3 grid(filter_grid(ntiles)), block(kMatThreads);
-    if (bp.strings && bp.numeric)
+    if (bp.times && bp.strings)
+        hipLaunchKernelGGL((k_pred_eval<BITMAP, true, true, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+    else if (bp.times)
+        hipLaunchKernelGGL((k_pred_eval<BITMAP, true, false, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+    else if (bp.strings && bp.numeric)
         hipLaunchKernelGGL((k_pred_eval<BITMAP, true, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
     else if (bp.strings)
         hipLaunchKernelGGL((k_pred_eval<BITMAP, false, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);

@@ -6,12 +6,13 @@
 #include "materialize_device.hpp"
 #include "numformat_device.hpp"
 #include "strpred_device.hpp"
+#include "timeparse_device.hpp"
 
 namespace cph {
 
 struct MapPiece {
     int32_t kind;          // CPH_MAP_*
-    int32_t col;           // COLUMN / SLICE: the column; FLOAT64: prec
+    int32_t col;           // COLUMN / SLICE: the column; FLOAT64: prec; TIME: the zone, minutes east of UTC
     union {
         struct {
             uint32_t off, len;   // LITERAL: its bytes in the plan's literal block
@@ -19,7 +20,7 @@ struct MapPiece {
         int64_t from;            // SLICE: bytes [from, to) of the value, Python's slice rules (strpred_device.hpp: slice_span)
     };
     union {
-        const int64_t* ints;    // INT64: one value per output row, on the device
+        const int64_t* ints;    // INT64 / TIME: one value per output row, on the device
         const double* floats;   // FLOAT64: likewise
         int64_t to;             // SLICE
     };
@@ -29,7 +30,7 @@ struct MapPiece {
 // its pieces, so one of LITERAL / COLUMN / INT64 pieces alone launches the kernels it always launched.
 enum : int { kPiecesBase = 0,     // LITERAL, COLUMN, INT64
              kPiecesSlice = 1,    // + SLICE
-             kPiecesFloat = 2 };  // + SLICE and FLOAT64 (the formatter's registers)
+             kPiecesFloat = 2 };  // + SLICE, FLOAT64 (the formatter's registers) and TIME: the pieces whose values can be refused
 __host__ __device__ constexpr int pieces_set(bool has_float, bool has_slice) { return has_float ? kPiecesFloat : has_slice ? kPiecesSlice : kPiecesBase; }
 
 __device__ __forceinline__ uint64_t int_magnitude(int64_t v) { return v < 0 ? 0ull - (uint64_t)v : (uint64_t)v; }
@@ -67,6 +68,17 @@ __device__ __forceinline__ void put_int(Sink& s, int64_t v) {
     s.put8(c0, len < 8u ? len : 8u);
     if (len > 8u) s.put8(c1, len < 16u ? len - 8u : 8u);
     if (len > 16u) s.put8(c2, len - 16u);
+}
+
+// the 20 or 25 characters of a CPH_MAP_TIME piece (timeparse_device.hpp), assembled in registers
+template <class Sink>
+__device__ __forceinline__ void put_time(Sink& s, int64_t v, int32_t zone) {
+    uint64_t w0, w1, w2, w3;
+    rfc3339_words(v, zone, &w0, &w1, &w2, &w3);
+    s.put8(w0, 8u);
+    s.put8(w1, 8u);
+    s.put8(w2, zone == 0 ? 4u : 8u);
+    if (zone != 0) s.put8(w3, 1u);
 }
 
 // (begin, length, first chunk) of column c's value in the loaded record; the arrays stay in registers (c is uniform in
@@ -107,6 +119,8 @@ __device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, con
             put_int(s, p.ints[i]);
         } else if (PK == kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
             fixed_put(s, fixed_split(p.floats[i], p.col), p.col);
+        } else if (PK == kPiecesFloat && p.kind == CPH_MAP_TIME) {
+            put_time(s, p.ints[i], p.col);
         } else if (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE) {   // the record's preloaded first chunk is the whole field's: a slice loads its own
             const uint8_t* data = cols.c[p.col].data;
             uint64_t b, l, c0, so, sn;

@@ -14,6 +14,8 @@
 // A template with a FLOAT64 piece runs its own instantiations of both kernels (k_map_lens_f64 / k_map_copy_f64): the others
 // carry no float code.  The length pass of those also finds the lowest row whose value is beyond the formatter's range; the
 // row number comes back in the same copy as the scan's total.
+// A template with a TIME piece (Unix seconds written as RFC 3339, timeparse_device.hpp) runs the float pair as well: its values can be
+// refused too (a local year outside 0000..9999), and the lowest refused row travels the same way.
 // A template with a SLICE piece (bytes [from, to) of a column's value, strpred_device.hpp: slice_span) and no FLOAT64 piece runs
 // a third pair (k_map_lens_sl / k_map_copy_sl); with both it runs the float pair, which carries the slice code too.  The length
 // pass takes a slice from the value's span alone; the copy pass puts (begin + from', len') through a COLUMN piece's chunk loop.
@@ -50,6 +52,9 @@ __global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds i
                 const FixedParts r = fixed_split(p.floats[i], p.col);
                 total += fixed_chars(r, p.col);
                 if (r.kind == FIXED_RANGE) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
+            } else if (PK == kPiecesFloat && p.kind == CPH_MAP_TIME) {   // the length needs no look at the value; the refusal does
+                total += rfc3339_chars(p.col);
+                if (!rfc3339_in_range(p.ints[i], p.col)) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
             } else if (p.kind == CPH_MAP_COLUMN || (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE)) {
                 total += map_field_bytes<NC, PK>(cols, ids, p, f, i);
             }
@@ -145,6 +150,13 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                 if (p.prec < 0 || p.prec > kFixedMaxPrec) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: prec of a FLOAT64 piece outside 0..22"});
                 has_float = true;
                 break;
+            case CPH_MAP_TIME:
+                if (p.arg != CPH_MEM_HOST && p.arg != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: bad memory space of a TIME piece"});
+                if (!p.ints && n) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: a TIME piece without values"});
+                if (p.prec < -kTimeMaxZone || p.prec > kTimeMaxZone)
+                    return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: prec of a TIME piece (the zone in minutes east of UTC) outside -1439..1439"});
+                has_float = true;   // the instantiations that report a refused value
+                break;
             case CPH_MAP_SLICE:
                 if (p.arg < 0 || p.arg >= ncols) return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: a SLICE piece's column outside 0..ncols-1"});
                 if (!p.value.data || p.value.len != sizeof(cph_map_slice))
@@ -152,7 +164,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                 has_slice = true;
                 break;
             default:
-                return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: unknown piece kind (1..4, 8)"});
+                return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_format: unknown piece kind (1..4, 8, 10)"});
         }
     }
     {
@@ -202,8 +214,8 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                         if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
                     }
                     slice_cols |= 1u << p.arg;
-                } else {   // INT64 / FLOAT64: 8 bytes per row
-                    const void* vals = p.kind == CPH_MAP_INT64 ? static_cast<const void*>(p.ints) : static_cast<const void*>(p.floats);
+                } else {   // INT64 / FLOAT64 / TIME: 8 bytes per row
+                    const void* vals = p.kind == CPH_MAP_FLOAT64 ? static_cast<const void*>(p.floats) : static_cast<const void*>(p.ints);
                     in_bytes += 8.0;
                     if (p.arg == CPH_MEM_HOST) {   // staged like the row ids of a host column
                         staged.emplace_back();
@@ -213,6 +225,9 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                     }
                     if (p.kind == CPH_MAP_INT64) {
                         d.ints = static_cast<const int64_t*>(vals);
+                    } else if (p.kind == CPH_MAP_TIME) {
+                        d.ints = static_cast<const int64_t*>(vals);
+                        d.col = p.prec;
                     } else {
                         d.floats = static_cast<const double*>(vals);
                         d.col = p.prec;
@@ -246,8 +261,17 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                 struct { uint64_t total, bad; } tail;
                 CPH_TRY(read_device_value(ctx, reinterpret_cast<const decltype(tail)*>(offs + n), &tail));
                 if (tail.bad != UINT64_MAX) {
-                    int piece = 0;   // the first FLOAT64 piece with such a value in that row
+                    int piece = 0;   // the first FLOAT64 or TIME piece with such a value in that row
                     for (int k = 0; k < npieces; k++) {
+                        if (pieces[k].kind == CPH_MAP_TIME) {
+                            int64_t t = 0;
+                            if (pieces[k].arg == CPH_MEM_HOST) t = pieces[k].ints[tail.bad];
+                            else CPH_HIP_TRY(hipMemcpy(&t, pieces[k].ints + tail.bad, sizeof t, hipMemcpyDeviceToHost));
+                            if (!rfc3339_in_range(t, pieces[k].prec))
+                                return Status{CPH_ERR_INVALID, "cph_map_format: TIME piece " + std::to_string(k) + ", row " + std::to_string(tail.bad) +
+                                                                   ": the local year of " + std::to_string(t) + " is outside 0000..9999"};
+                            continue;
+                        }
                         if (pieces[k].kind != CPH_MAP_FLOAT64) continue;
                         double v = 0;
                         if (pieces[k].arg == CPH_MEM_HOST) v = pieces[k].floats[tail.bad];

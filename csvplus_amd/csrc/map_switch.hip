@@ -12,7 +12,7 @@
 // may take different alternatives: every lane walks its own run [first[a], first[a + 1]) of the one flat piece array, so the
 // k-th pieces of two alternatives run together where they are of one kind and one after the other where they are not; the
 // stage sink ORs words into LDS, so no lane depends on another's progress and rows are not sorted by alternative.
-// A plan with a FLOAT64 piece runs float instantiations of both kernels, as map_format.hip does, and one with a SLICE piece
+// A plan with a FLOAT64 or TIME piece runs float instantiations of both kernels, as map_format.hip does, and one with a SLICE piece
 // but no FLOAT64 piece the slice instantiations (k_switch_lens_sl / k_switch_copy_sl).
 #include <new>
 #include <string>
@@ -58,6 +58,9 @@ __global__ __launch_bounds__(kMatThreads) void k_switch_lens(ColsArg cols, ColId
                 const FixedParts r = fixed_split(p.floats[i], p.col);
                 total += fixed_chars(r, p.col);
                 if (r.kind == FIXED_RANGE) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
+            } else if (PK == kPiecesFloat && p.kind == CPH_MAP_TIME) {   // the length needs no look at the value; the refusal does
+                total += rfc3339_chars(p.col);
+                if (!rfc3339_in_range(p.ints[i], p.col)) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
             } else if (p.kind == CPH_MAP_COLUMN || (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE)) {
                 total += map_field_bytes<NC, PK>(cols, ids, p, f, i);
             }
@@ -154,6 +157,13 @@ Status check_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t ncols,
                 if (p.prec < 0 || p.prec > kFixedMaxPrec) return {CPH_ERR_INVALID, at + "prec of a FLOAT64 piece outside 0..22"};
                 *has_float = true;
                 break;
+            case CPH_MAP_TIME:
+                if (p.arg != CPH_MEM_HOST && p.arg != CPH_MEM_DEVICE) return {CPH_ERR_INVALID, at + "bad memory space of a TIME piece"};
+                if (!p.ints && n) return {CPH_ERR_INVALID, at + "a TIME piece without values"};
+                if (p.prec < -kTimeMaxZone || p.prec > kTimeMaxZone)
+                    return {CPH_ERR_INVALID, at + "prec of a TIME piece (the zone in minutes east of UTC) outside -1439..1439"};
+                *has_float = true;   // the instantiations that report a refused value
+                break;
             case CPH_MAP_SLICE:
                 if (p.arg < 0 || p.arg >= ncols) return {CPH_ERR_INVALID, at + "a SLICE piece's column outside 0..ncols-1"};
                 if (!p.value.data || p.value.len != sizeof(cph_map_slice))
@@ -161,7 +171,7 @@ Status check_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t ncols,
                 *has_slice = true;
                 break;
             default:
-                return {CPH_ERR_INVALID, at + "unknown piece kind (1..4, 8)"};
+                return {CPH_ERR_INVALID, at + "unknown piece kind (1..4, 8, 10)"};
         }
     }
     return {};
@@ -277,8 +287,8 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                         if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
                     }
                     slice_cols |= 1u << p.arg;
-                } else {   // INT64 / FLOAT64: 8 bytes per row
-                    const void* vals = p.kind == CPH_MAP_INT64 ? static_cast<const void*>(p.ints) : static_cast<const void*>(p.floats);
+                } else {   // INT64 / FLOAT64 / TIME: 8 bytes per row
+                    const void* vals = p.kind == CPH_MAP_FLOAT64 ? static_cast<const void*>(p.floats) : static_cast<const void*>(p.ints);
                     in_bytes += 8.0;
                     if (p.arg == CPH_MEM_HOST) {   // staged like the row ids of a host column
                         staged.emplace_back();
@@ -288,6 +298,9 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                     }
                     if (p.kind == CPH_MAP_INT64) {
                         d.ints = static_cast<const int64_t*>(vals);
+                    } else if (p.kind == CPH_MAP_TIME) {
+                        d.ints = static_cast<const int64_t*>(vals);
+                        d.col = p.prec;
                     } else {
                         d.floats = static_cast<const double*>(vals);
                         d.col = p.prec;
@@ -333,8 +346,17 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                 CPH_HIP_TRY(hipMemcpy(&a, which_dev + tail.bad, 1, hipMemcpyDeviceToHost));
                 const cph_map_piece* pieces = a < ncases ? cases[a].pieces : otherwise;
                 const int npieces = a < ncases ? cases[a].npieces : notherwise;
-                int piece = 0;   // the first FLOAT64 piece of that row's alternative with such a value
+                int piece = 0;   // the first FLOAT64 or TIME piece of that row's alternative with such a value
                 for (int k = 0; k < npieces; k++) {
+                    if (pieces[k].kind == CPH_MAP_TIME) {
+                        int64_t t = 0;
+                        if (pieces[k].arg == CPH_MEM_HOST) t = pieces[k].ints[tail.bad];
+                        else CPH_HIP_TRY(hipMemcpy(&t, pieces[k].ints + tail.bad, sizeof t, hipMemcpyDeviceToHost));
+                        if (!rfc3339_in_range(t, pieces[k].prec))
+                            return Status{CPH_ERR_INVALID, "cph_map_switch: " + alt_name(a, ncases) + ", TIME piece " + std::to_string(k) + ", row " +
+                                                               std::to_string(tail.bad) + ": the local year of " + std::to_string(t) + " is outside 0000..9999"};
+                        continue;
+                    }
                     if (pieces[k].kind != CPH_MAP_FLOAT64) continue;
                     double v = 0;
                     if (pieces[k].arg == CPH_MEM_HOST) v = pieces[k].floats[tail.bad];

@@ -1,5 +1,5 @@
 // numparse.hip — Row.ValueAsInt / Row.ValueAsFloat64 (csvplus.go:165-205) for a whole column: strings -> int64 / float64
-// with Go's strconv semantics, plus the error report the reference's callers act on (which row failed first, and how).
+// with Go's strconv semantics (and RFC 3339 timestamps -> Unix time, the third typed value), plus the error report the reference's callers act on (which row failed first, and how).
 //
 //   cph_col_to_number   one column read through an optional row selection -> values, one status byte per row, the
 //                       number of errors, the first error row and its kind
@@ -10,6 +10,9 @@
 //                  numparse_device.hpp.  Values and status bytes leave as coalesced stores.  A wave that saw an error
 //                  adds its count and sends ONE 64-bit atomicMin of (row << 2 | kind), so the first error row and its
 //                  kind arrive together; a wave that deferred float rows adds their count.
+//                  The time instantiation (CPH_NUM_TIME_UNIX / CPH_NUM_TIME_UNIXNANO: RFC 3339 text -> t.Unix() / t.UnixNano(),
+//                  timeparse_device.hpp) loads bytes 16..31 with two more unbranched loads per row, issued for the phase's rows
+//                  together; it defers nothing.
 //   The device decides every row's syntax and every value Clinger's exact cases cover.  The float rows it DEFERS (19+
 //   significant digits, a mantissa >= 2^53, exponents outside the exact range) are rare:
 //   k_num_collect  (only when there are any) gathers position, span and the first bytes of each deferred row into 128-byte
@@ -28,8 +31,11 @@
 #include <locale.h>
 
 #include "numparse_device.hpp"
+#include "timeparse_device.hpp"
 
 namespace cph {
+
+constexpr int kParseInt = 0, kParseFloat = 1, kParseTime = 2;   // the instantiations of k_num_parse
 
 constexpr int kNumRows  = 8;                          // rows per lane and tile
 constexpr int kNumPhase = 4;                          // ... of which this many are in flight at once
@@ -50,9 +56,30 @@ struct NumPatch {
     uint32_t status, pad_;
 };
 
-template <bool FLT>
+// bytes 32.. of a value for parse_rfc3339 (and every chunk for the byte loop of a malformed value)
+struct TimeChunks {
+    const uint8_t* data;
+    uint64_t begin, len;
+    __device__ __forceinline__ uint64_t operator()(int j) const { return load_value_chunk(data, begin, len, j); }
+};
+
+// bytes 16..23 and 24..31 of a value, unbranched like the head (a chunk past the value's end reads the word at the value's
+// own first byte and is not used)
+__device__ __forceinline__ void load_tail16(const DevCol& col, uint64_t begin, uint64_t len, uint64_t* t0, uint64_t* t1) {
+    const uint64_t p = (uint64_t)(uintptr_t)col.data;
+    const uint8_t* base8 = (const uint8_t*)(uintptr_t)(p & ~7ull);
+    const uint32_t delta = (uint32_t)(p & 7ull);
+    const uint32_t l32 = len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)len;
+    *t0 = load_chunk_nobranch<uint64_t>(base8, delta, begin, l32, 2);
+    *t1 = load_chunk_nobranch<uint64_t>(base8, delta, begin, l32, 3);
+}
+
+// KIND: kParseInt / kParseFloat / kParseTime; nano (kParseTime alone): UnixNano instead of Unix
+template <int KIND>
 __global__ __launch_bounds__(kMatThreads) void k_num_parse(DevCol col, RowIds rid, uint64_t first_row, uint64_t n,
-                                                          uint64_t* __restrict__ values, uint8_t* __restrict__ status, NumCounters* cnt) {
+                                                          uint64_t* __restrict__ values, uint8_t* __restrict__ status, NumCounters* cnt,
+                                                          uint32_t nano) {
+    constexpr bool FLT = KIND == kParseFloat;
     const int lane = lane_id(), wave = wave_id();
     const uint64_t ntiles = (n + kNumTile - 1) / kNumTile;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -71,12 +98,21 @@ __global__ __launch_bounds__(kMatThreads) void k_num_parse(DevCol col, RowIds ri
             }
 #pragma unroll
             for (int k = 0; k < kNumPhase; k++) load_head16(col, b[k], l[k], &c0[k], &c1[k]);
+            uint64_t c2[KIND == kParseTime ? kNumPhase : 1], c3[KIND == kParseTime ? kNumPhase : 1];   // bytes 16..31
+            if constexpr (KIND == kParseTime) {
+#pragma unroll
+                for (int k = 0; k < kNumPhase; k++) load_tail16(col, b[k], l[k], &c2[k], &c3[k]);
+            }
 #pragma unroll
             for (int k = 0; k < kNumPhase; k++) {
                 const uint64_t g0 = t0 + (uint64_t)((wave * kNumWaveRows + ph * kNumPhase + k) * 64);
                 uint64_t bits;
                 uint32_t st;
-                if constexpr (FLT) {
+                if constexpr (KIND == kParseTime) {
+                    int64_t v;
+                    st = parse_rfc3339(l[k], c0[k], c1[k], c2[k], c3[k], TimeChunks{col.data, b[k], l[k]}, nano != 0, &v);
+                    bits = (uint64_t)v;
+                } else if constexpr (FLT) {
                     double v;
                     st = parse_float64(col, b[k], l[k], c0[k], c1[k], &v);
                     bits = (uint64_t)__double_as_longlong(v);
@@ -178,6 +214,7 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
     *st = NumColStats{};
     if (n == 0) return {};
     const bool flt = kind == CPH_NUM_FLOAT64;
+    const bool tim = kind == CPH_NUM_TIME_UNIX || kind == CPH_NUM_TIME_UNIXNANO;
     CPH_TRY(values->alloc(&ctx->pool, (size_t)n * 8));
     CPH_TRY(status->alloc(&ctx->pool, (size_t)n));
     DevBuf cnt;
@@ -193,13 +230,18 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
     {
         // byte model: offsets (or nothing for a fixed width) + row ids + ~8 value bytes in, 9 bytes out per row
         const double in_row = (col.fixed_width ? (double)col.fixed_width : (double)(col.offset_bits / 8) + 8.0) + (ids.ptr ? (double)(ids.bits / 8) : 0.0);
-        ProfScope ps(ctx, flt ? "k_num_parse_f64" : "k_num_parse_i64", (in_row + 9.0) * (double)n);
-        if (flt)
-            hipLaunchKernelGGL(k_num_parse<true>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
-                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>());
+        // (a timestamp: 20..35 value bytes, counted as 25)
+        const double in_time = tim && !col.fixed_width ? 17.0 : 0.0;
+        ProfScope ps(ctx, tim ? "k_num_parse_time" : flt ? "k_num_parse_f64" : "k_num_parse_i64", (in_row + in_time + 9.0) * (double)n);
+        if (tim)
+            hipLaunchKernelGGL(k_num_parse<kParseTime>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), kind == CPH_NUM_TIME_UNIXNANO ? 1u : 0u);
+        else if (flt)
+            hipLaunchKernelGGL(k_num_parse<kParseFloat>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
         else
-            hipLaunchKernelGGL(k_num_parse<false>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
-                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>());
+            hipLaunchKernelGGL(k_num_parse<kParseInt>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
     }
     CPH_HIP_TRY(hipGetLastError());
     NumCounters got{};
@@ -270,8 +312,8 @@ CPH_API int32_t cph_col_to_number(cph_ctx* ctx, const cph_strcol* col, const cph
     if (hipSetDevice(ctx->device) != hipSuccess) return fail_with(ctx, {CPH_ERR_HIP, "hipSetDevice failed"});
     *out = nullptr;
     if (!col) return fail_with(ctx, {CPH_ERR_INVALID, "cph_col_to_number: col must not be NULL"});
-    if (kind != CPH_NUM_INT64 && kind != CPH_NUM_FLOAT64)
-        return fail_with(ctx, {CPH_ERR_INVALID, "cph_col_to_number: kind must be CPH_NUM_INT64 or CPH_NUM_FLOAT64"});
+    if (kind != CPH_NUM_INT64 && kind != CPH_NUM_FLOAT64 && kind != CPH_NUM_TIME_UNIX && kind != CPH_NUM_TIME_UNIXNANO)
+        return fail_with(ctx, {CPH_ERR_INVALID, "cph_col_to_number: kind must be CPH_NUM_INT64, CPH_NUM_FLOAT64, CPH_NUM_TIME_UNIX or CPH_NUM_TIME_UNIXNANO"});
     if (out_mem != CPH_MEM_HOST && out_mem != CPH_MEM_DEVICE) return fail_with(ctx, {CPH_ERR_INVALID, "bad out_mem"});
     {
         Status s = check_row_sources(col, sel, 1, 0, nrows, true);

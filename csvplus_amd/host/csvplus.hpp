@@ -26,6 +26,10 @@
 //                                                DataSource::ColumnAsInt / ColumnAsFloat64 (a whole column, on the GPU);
 //                                                csvplus::IntCmp / FloatCmp: `v, err := row.ValueAsInt(c); err == nil && v REL k`
 //                                                as a predicate that composes with Like / All / Any / Not
+//   time.Parse(time.RFC3339, row[c])   (closures) DataSource::ColumnAsTime / ColumnAsTimeNano (t.Unix() / t.UnixNano() of a whole
+//                                                column, on the GPU); csvplus::TimeCmp(c, REL, "2016-09-14T00:00:00Z"): instants, not
+//                                                bytes; Rfc3339(expr or Col, zone_minutes) as a Format part: Unix seconds written
+//                                                back as RFC 3339; ParseRfc3339 / FormatRfc3339 (one value, on the host)
 //   Index.Iterate / Find / SubIndex    :618-641  Index::Iterate / Find / SubIndex
 //   Index.ResolveDuplicates            :643-653  Index::ResolveDuplicates (groups found on the GPU)
 //   Index.WriteTo / LoadIndex          :655-705  Index::WriteTo / LoadIndex (own binary format, not gob)
@@ -226,6 +230,11 @@ inline std::string conversionError(const std::string& column, const std::string&
     const char* what = err == CPH_NUM_ERR_SYNTAX  ? "invalid syntax"
                        : err == CPH_NUM_ERR_RANGE ? "value out of range"
                                                   : "not decided by this library (digit separators, hexadecimal floats)";
+    if (kind == CPH_NUM_TIME_UNIX || kind == CPH_NUM_TIME_UNIXNANO)
+        return "column " + quote(column) + ": cannot convert " + quote(value) + " to time: " +
+               (err == CPH_NUM_ERR_SYNTAX  ? "invalid syntax"
+                : err == CPH_NUM_ERR_RANGE ? "a field out of range"
+                                           : "not decided by this library (one-digit hour, ',' fraction, more than 9 fraction digits, zone beyond 23:59, UnixNano overflow)");
     return "column " + quote(column) + ": cannot convert " + quote(value) + " to " + (kind == CPH_NUM_INT64 ? "integer" : "float") + ": " + what;
 }
 // strconv.FormatFloat(v, 'f', prec, 64) on the host: glibc's exact "%.*f" and Go's spellings of NaN and the infinities
@@ -237,11 +246,99 @@ inline std::string FormatFixed(double v, int prec) {
     return out;
 }
 
+// `t, err := time.Parse(time.RFC3339, s)` then t.Unix() (nano false: whole seconds, the floor) or t.UnixNano() on the host, by the
+// rules of the header's cph_col_to_number comment (CPH_NUM_TIME_UNIX / CPH_NUM_TIME_UNIXNANO): returns CPH_NUM_*, *out = 0 at an error.
+inline int64_t DaysFromCivil(int64_t y, int64_t m, int64_t d) {   // days since 1970-01-01, proleptic Gregorian
+    y -= m <= 2;
+    const int64_t era = (y >= 0 ? y : y - 399) / 400, yoe = y - era * 400;
+    const int64_t doy = (153 * (m > 2 ? m - 3 : m + 9) + 2) / 5 + d - 1;
+    return era * 146097 + yoe * 365 + yoe / 4 - yoe / 100 + doy - 719468;
+}
+inline int32_t ParseRfc3339(const std::string& s, bool nano, int64_t* out) {
+    *out = 0;
+    size_t i = 0;
+    bool relaxed = false;
+    auto digit = [&](size_t at) { return at < s.size() && s[at] >= '0' && s[at] <= '9'; };
+    auto number = [&](size_t n, int64_t* v) {   // exactly n digits at i
+        *v = 0;
+        for (size_t k = 0; k < n; k++, i++) {
+            if (!digit(i)) return false;
+            *v = *v * 10 + (s[i] - '0');
+        }
+        return true;
+    };
+    auto byte = [&](char c) { return i < s.size() && s[i] == c ? (i++, true) : false; };
+    int64_t year, month, day, hour, minute, second, frac = 0, zh = 0, zm = 0, sign = 1;
+    if (!number(4, &year) || !byte('-') || !number(2, &month) || !byte('-') || !number(2, &day) || !byte('T')) return CPH_NUM_ERR_SYNTAX;
+    if (digit(i) && !digit(i + 1)) {   // the hour written with one digit: not decided
+        relaxed = true;
+        number(1, &hour);
+    } else if (!number(2, &hour)) {
+        return CPH_NUM_ERR_SYNTAX;
+    }
+    if (!byte(':') || !number(2, &minute) || !byte(':') || !number(2, &second)) return CPH_NUM_ERR_SYNTAX;
+    if (i < s.size() && (s[i] == '.' || s[i] == ',')) {
+        relaxed = relaxed || s[i] == ',';
+        i++;
+        size_t nd = 0;
+        for (; digit(i); i++, nd++)
+            if (nd < 9) frac = frac * 10 + (s[i] - '0');
+        if (nd == 0) return CPH_NUM_ERR_SYNTAX;
+        relaxed = relaxed || nd > 9;
+        for (; nd < 9; nd++) frac *= 10;
+    }
+    if (byte('Z')) {
+        if (i != s.size()) return CPH_NUM_ERR_SYNTAX;
+    } else {
+        if (i >= s.size() || (s[i] != '+' && s[i] != '-')) return CPH_NUM_ERR_SYNTAX;
+        sign = s[i++] == '-' ? -1 : 1;
+        if (!number(2, &zh) || !byte(':') || !number(2, &zm) || i != s.size()) return CPH_NUM_ERR_SYNTAX;
+    }
+    if (relaxed) return CPH_NUM_ERR_UNSUPPORTED;
+    static const int mdays[12] = {31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31};
+    const bool leap = (year % 4 == 0 && year % 100 != 0) || year % 400 == 0;
+    if (month < 1 || month > 12 || day < 1 || day > mdays[month - 1] + (month == 2 && leap) || hour > 23 || minute > 59 || second > 59)
+        return CPH_NUM_ERR_RANGE;
+    if (zh > 23 || zm > 59) return CPH_NUM_ERR_UNSUPPORTED;
+    const int64_t secs = DaysFromCivil(year, month, day) * 86400 + hour * 3600 + minute * 60 + second - sign * (zh * 3600 + zm * 60);
+    if (!nano) {
+        *out = secs;
+        return CPH_NUM_OK;
+    }
+    const __int128 ns = (__int128)secs * 1000000000 + frac;
+    if (ns < (__int128)INT64_MIN || ns > (__int128)INT64_MAX) return CPH_NUM_ERR_UNSUPPORTED;
+    *out = (int64_t)ns;
+    return CPH_NUM_OK;
+}
+// time.Unix(v, 0).In(time.FixedZone("", 60 * zone)).Format(time.RFC3339) on the host; false where the local year leaves 0000..9999
+inline bool FormatRfc3339(int64_t v, int zone, std::string* out) {
+    if (v < -62167219200ll - 86400 || v > 253402300799ll + 86400) return false;
+    const int64_t local = v + 60ll * zone;
+    if (local < -62167219200ll || local > 253402300799ll) return false;
+    int64_t days = local / 86400, sod = local % 86400;
+    if (sod < 0) sod += 86400, days--;
+    int64_t z = days + 719468;   // civil from days
+    const int64_t era = (z >= 0 ? z : z - 146096) / 146097, doe = z - era * 146097;
+    const int64_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365, doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
+    const int64_t mp = (5 * doy + 2) / 153, d = doy - (153 * mp + 2) / 5 + 1, m = mp < 10 ? mp + 3 : mp - 9, y = yoe + era * 400 + (m <= 2);
+    char buf[40];
+    int len = snprintf(buf, sizeof buf, "%04d-%02d-%02dT%02d:%02d:%02d", (int)y, (int)m, (int)d, (int)(sod / 3600), (int)(sod / 60 % 60), (int)(sod % 60));
+    if (zone == 0) len += snprintf(buf + len, sizeof buf - (size_t)len, "Z");
+    else len += snprintf(buf + len, sizeof buf - (size_t)len, "%c%02d:%02d", zone < 0 ? '-' : '+', std::abs(zone) / 60, std::abs(zone) % 60);
+    out->assign(buf, (size_t)len);
+    return true;
+}
+
 class Pred {
 public:
-    enum Kind { kLike, kNot, kAll, kAny, kIntCmp, kFloatCmp, kStrCmp, kHasPrefix, kHasSuffix, kContains };
+    enum Kind { kLike, kNot, kAll, kAny, kIntCmp, kFloatCmp, kStrCmp, kHasPrefix, kHasSuffix, kContains, kTimeCmp };
     bool operator()(const Row& row) const {
         switch (kind_) {
+            case kTimeCmp: {   // a row without the column, or whose stamp does not convert, is false under every relation
+                auto it = row.find(column_);
+                int64_t v;
+                return it != row.end() && ParseRfc3339(it->second, false, &v) == CPH_NUM_OK && holds(v, ilit_);
+            }
             case kStrCmp:
             case kHasPrefix:
             case kHasSuffix:
@@ -307,6 +404,7 @@ private:
     friend Pred FloatCmp(std::string column, Rel rel, double x);
     friend Pred StrCmp(std::string column, Rel rel, std::string literal);
     friend Pred StrTest(Pred::Kind kind, std::string column, std::string literal);
+    friend Pred TimeCmp(std::string column, Rel rel, std::string literal);
     std::string column_, slit_;
     Rel rel_ = EQ;
     int64_t ilit_ = 0;
@@ -357,6 +455,19 @@ inline Pred StrTest(Pred::Kind kind, std::string column, std::string literal) {
     Pred p;
     p.kind_ = kind;
     p.column_ = std::move(column);
+    p.slit_ = std::move(literal);
+    return p;
+}
+// TimeCmp("ts", GE, "2016-09-14T00:00:00Z") is `t, err := time.Parse(time.RFC3339, row["ts"]); err == nil && t.Unix() >= u.Unix()`:
+// instants, not bytes — two stamps of one instant in different zones are equal.  The literal is RFC 3339 text without a fraction
+// (the term compares whole seconds); anything else panics here, as the C ABI would refuse it.
+inline Pred TimeCmp(std::string column, Rel rel, std::string literal) {
+    Pred p;
+    p.kind_ = Pred::kTimeCmp;
+    p.column_ = std::move(column);
+    p.rel_ = rel;
+    if (ParseRfc3339(literal, false, &p.ilit_) != CPH_NUM_OK) throw Panic("TimeCmp(): the literal is no RFC 3339 timestamp this library converts");
+    if (literal.find('.') != std::string::npos) throw Panic("TimeCmp(): the literal has a fraction (the term compares whole seconds)");
     p.slit_ = std::move(literal);
     return p;
 }
@@ -593,6 +704,19 @@ struct Itoa {   // an int64 expression written as strconv.Itoa writes it
         if (expr->kind != CPH_NUM_INT64) throw Panic("Itoa() of a float64 expression (use Fixed, or Int)");
     }
 };
+// Rfc3339(expr, zone_minutes) writes an int64 expression — Unix seconds, e.g. AsInt(Col("t")) / 3600 * 3600 — as
+// time.Unix(v, 0).In(time.FixedZone("", 60 * zone_minutes)).Format(time.RFC3339) does: "...Z" for zone 0, "...+HH:MM" otherwise
+// (a CPH_MAP_TIME piece).  Rfc3339(Col("t")) reads the column as ValueAsInt reads it.  A value whose local year leaves 0000..9999
+// fails the Map with the library's message.
+struct Rfc3339 {
+    std::shared_ptr<const Expr> expr;
+    int zone;
+    explicit Rfc3339(Expr e, int zone_minutes = 0) : expr(std::make_shared<const Expr>(std::move(e))), zone(zone_minutes) {
+        if (expr->kind != CPH_NUM_INT64) throw Panic("Rfc3339() of a float64 expression (Unix seconds are an int64: use Int)");
+        if (zone < -1439 || zone > 1439) throw Panic("Rfc3339(): zone outside -1439..1439 minutes");
+    }
+    explicit Rfc3339(Col c, int zone_minutes = 0) : Rfc3339(AsInt(std::move(c)), zone_minutes) {}
+};
 // Substr(Col("ts"), 0, 10) is Go's `row["ts"][0:10]`: the bytes [from, to) of the column's value (of its default where the row
 // lacks the column).  Python's slice rules: a negative index counts from the end, both ends are clamped into the value, from >=
 // to gives "", to == INT64_MAX (the default) means "to the end".  One deviation from Go: an index out of range clamps, no panic.
@@ -614,7 +738,10 @@ struct Part {   // a literal, a column, a slice of a column, a column as a fixed
     std::string text;   // the literal's bytes
     Col col{""};
     int prec = -1;      // >= 0: Fixed
-    std::shared_ptr<const Expr> expr;   // Fixed(expr, prec) (prec >= 0) or Itoa(expr) (prec < 0)
+    std::shared_ptr<const Expr> expr;   // Fixed(expr, prec) (prec >= 0), Itoa(expr) or Rfc3339(expr, zone) (prec < 0)
+    bool is_time = false;               // Rfc3339: the int64 value is Unix seconds, written in the zone `zone`
+    int zone = 0;
+    Part(Rfc3339 t) : expr(std::move(t.expr)), is_time(true), zone(t.zone) {}   // NOLINT
     Part(const char* lit) : text(lit) {}                 // NOLINT: implicit, so that a template reads like the expression
     Part(std::string lit) : text(std::move(lit)) {}      // NOLINT
     Part(Col c) : is_col(true), col(std::move(c)) {}     // NOLINT
@@ -640,6 +767,15 @@ struct Format {
                 if (rc != CPH_NUM_OK) {
                     if (rc > 0 && invalid) *invalid = p.expr->errorText(rc, op, row);
                     return false;
+                }
+                if (p.is_time) {
+                    std::string t;
+                    if (!FormatRfc3339(iv, p.zone, &t)) {
+                        if (invalid) *invalid = "the local year of " + std::to_string(iv) + " is outside 0000..9999";
+                        return false;
+                    }
+                    *out += t;
+                    continue;
                 }
                 *out += p.prec >= 0 ? FormatFixed(fv, p.prec) : std::to_string(iv);
                 continue;
@@ -707,6 +843,7 @@ inline Assign Set(std::string name, const char* literal) { return Set(std::move(
 inline Assign Set(std::string name, Format value) { return Assign{std::move(name), std::move(value)}; }
 inline Assign Set(std::string name, Fixed value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
 inline Assign Set(std::string name, Itoa value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
+inline Assign Set(std::string name, Rfc3339 value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
 inline Assign Set(std::string name, Switch value) { return Assign{std::move(name), std::move(value.otherwise), std::move(value.cases)}; }
 
 using RowFunc = std::function<Error(Row)>;
@@ -885,6 +1022,13 @@ struct PredProgram {
                 if (absent[c].empty()) absent[c].assign(1, '\0');   // a NUL converts to no number
                 const int32_t base = p.kind() == Pred::kIntCmp ? (int32_t)CPH_PRED_INT_LT : (int32_t)CPH_PRED_FLT_LT;
                 ops.push_back(cph_pred_op{base + (int32_t)p.rel(), (int32_t)c, {static_cast<const uint8_t*>(p.literal()), 8}});
+                break;
+            }
+            case Pred::kTimeCmp: {   // a row without the column gets a NUL, which is no timestamp: false under every relation
+                const size_t c = column(p.column());
+                if (absent[c].empty()) absent[c].assign(1, '\0');
+                ops.push_back(cph_pred_op{(int32_t)CPH_PRED_TIME_LT + (int32_t)p.rel(), (int32_t)c,
+                                          {reinterpret_cast<const uint8_t*>(p.text().data()), p.text().size()}});
                 break;
             }
             case Pred::kNot:
@@ -1326,6 +1470,19 @@ public:
     std::vector<double> ColumnAsFloat64(const std::string& name) const {
         std::vector<double> out;
         columnAsNumber(name, CPH_NUM_FLOAT64, &out);
+        return out;
+    }
+    // `t, err := time.Parse(time.RFC3339, row[name])` for every row, the same way: t.Unix() (whole seconds, the floor) or
+    // t.UnixNano().  The accepted set is the strict RFC 3339 profile of the header's cph_col_to_number comment; the first row whose
+    // stamp does not convert throws Error::DataSourceError(row number) — `column "ts": cannot convert "..." to time: ...`.
+    std::vector<int64_t> ColumnAsTime(const std::string& name) const {
+        std::vector<int64_t> out;
+        columnAsNumber(name, CPH_NUM_TIME_UNIX, &out);
+        return out;
+    }
+    std::vector<int64_t> ColumnAsTimeNano(const std::string& name) const {
+        std::vector<int64_t> out;
+        columnAsNumber(name, CPH_NUM_TIME_UNIXNANO, &out);
         return out;
     }
 
@@ -1864,8 +2021,8 @@ private:
         size_t fixed_seen = 0;
         for (const Part& p : a.value.parts) {
             if (p.expr && p.prec < 0) {
-                pieces.push_back(cph_map_piece{CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0}, static_cast<const int64_t*>(nums.v[fixed_seen++]->values),
-                                               nullptr, 0, 0});
+                pieces.push_back(cph_map_piece{p.is_time ? CPH_MAP_TIME : CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0},
+                                               static_cast<const int64_t*>(nums.v[fixed_seen++]->values), nullptr, p.is_time ? p.zone : 0, 0});
                 continue;
             }
             if (p.expr) {
@@ -1971,7 +2128,8 @@ private:
                     }
                     if (rc != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
                     if (p.expr && p.prec < 0)
-                        pieces[alt].push_back(cph_map_piece{CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0}, static_cast<const int64_t*>(np.nc->values), nullptr, 0, 0});
+                        pieces[alt].push_back(cph_map_piece{p.is_time ? CPH_MAP_TIME : CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0},
+                                                            static_cast<const int64_t*>(np.nc->values), nullptr, p.is_time ? p.zone : 0, 0});
                     else
                         pieces[alt].push_back(cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr, static_cast<const double*>(np.nc->values), p.prec, 0});
                     nums.v.push_back(std::move(np));

@@ -18,6 +18,13 @@ the new column in row i is the concatenation of the template's parts —
                          `strconv.FormatFloat(price*float64(qty), 'f', 2, 64)` (csvplus_test.go:1391-1421).  prec is 0..22 and
                          finite values of 2^128 or more are refused, on the device and by the host model alike; host or
                          device array as for Int: Float.on_device(device_ptr, count, prec).
+    Time(array, zone)    array[i] = Unix seconds, written as RFC 3339 in the fixed zone `zone_minutes` east of UTC:
+                         `time.Unix(v, 0).In(time.FixedZone("", 60*zone)).Format(time.RFC3339)` — "YYYY-MM-DDTHH:MM:SSZ" for
+                         zone 0, "...+HH:MM" / "...-HH:MM" otherwise (timeconv.format_model).  The zone is within -1439..1439
+                         and a value whose local year leaves 0000..9999 is refused, on the device and by the host model
+                         alike; host or device array as for Int: Time.on_device(device_ptr, count, zone_minutes);
+                         Time.of(expr, zone_minutes) for an int64 expression, e.g. the hour bucket of a parsed column:
+                         Time.of((IntArr(t) / 3600) * 3600).
     Int.of(expr)         the value of an int64 expression of csvplus_amd.expr over the same rows, written as Int writes it;
     Float.of(expr, prec) likewise for a float64 expression: the amounts column is
                          Float.of(FloatCol("price") * ToFloat(IntCol("qty")), 2) — converted, multiplied and formatted on
@@ -27,7 +34,8 @@ the new column in row i is the concatenation of the template's parts —
 `compile` turns a template into the piece list cph_map_format takes (include/csvplus_hip.h), `render` evaluates it on one
 row held as a dict — the host model, for callers without a GPU and as the cross-check of the device.  Nothing here
 touches the GPU.  Out of scope: FormatFloat's other forms (shortest round-trip digits, 'e' and 'g'); case mapping and
-TrimSpace (Go's are Unicode-aware); splitting a value on a delimiter; regular expressions; timestamp parsing.
+TrimSpace (Go's are Unicode-aware); splitting a value on a delimiter; regular expressions; time layouts other than
+RFC 3339, named zones and DST rules.
 
 A value that depends on a condition is a Switch — Go's `if / else if / else` inside the closure, as data:
 
@@ -48,9 +56,10 @@ import math
 import numpy as np
 
 from . import predicates as _P
+from . import timeconv as _T
 from .predicates import INT64_MAX, INT64_MIN, _bytes, _go_quote
 
-LITERAL, COLUMN, INT64, FLOAT64, SLICE = 1, 2, 3, 4, 8   # CPH_MAP_*
+LITERAL, COLUMN, INT64, FLOAT64, SLICE, TIME = 1, 2, 3, 4, 8, 10   # CPH_MAP_*
 MAX_PIECES = 16                    # CPH_MAP_MAX_PIECES
 MAX_CASES = 8                      # CPH_MAP_MAX_CASES
 SWITCH_MAX_PIECES = 32             # CPH_MAP_SWITCH_MAX_PIECES: the pieces of all alternatives together
@@ -147,6 +156,41 @@ class Int:
         return f"Int(<{self.count} values{' on the device' if self.device else ''}>)"
 
 
+class Time(Int):
+    """One int64 per OUTPUT row, Unix seconds, formatted as RFC 3339 in a fixed zone (timeconv.format_model).
+    Time(values, zone_minutes=0): host values as for Int, e.g. NumCol.values of materialize.to_time;
+    Time.on_device(device_ptr, count, zone_minutes=0); Time.of(expr, zone_minutes=0): an int64 expression of csvplus_amd.expr."""
+
+    def __init__(self, values, zone_minutes=0):
+        self.zone = _T.check_zone(zone_minutes, "Time")
+        try:
+            super().__init__(values)
+        except ValueError as e:
+            raise ValueError(str(e).replace("Int:", "Time:")) from None
+
+    @classmethod
+    def on_device(cls, device_ptr: int, count: int, zone_minutes=0) -> "Time":
+        self = cls.__new__(cls)
+        self.zone = _T.check_zone(zone_minutes, "Time.on_device")
+        self.device, self.values, self.count = True, int(device_ptr), int(count)
+        return self
+
+    @classmethod
+    def of(cls, expr, zone_minutes=0) -> "Time":
+        from . import expr as E
+        if E.kind_of(expr) != E.INT:
+            raise TypeError("Time.of: the expression is a float64 (Unix seconds are an int64: use ToInt)")
+        self = cls.__new__(cls)
+        self.zone = _T.check_zone(zone_minutes, "Time.of")
+        self.device, self.values, self.count, self.expr = False, None, None, expr
+        return self
+
+    def __repr__(self):
+        if self.expr is not None:
+            return f"Time.of({self.expr!r}, {self.zone})"
+        return f"Time(<{self.count} values{' on the device' if self.device else ''}>, {self.zone})"
+
+
 def _check_prec(prec, who) -> int:
     if isinstance(prec, bool) or int(prec) != prec or not 0 <= int(prec) <= MAX_PREC:
         raise ValueError(f"{who}: prec must be within 0..{MAX_PREC}, not {prec!r}")
@@ -205,7 +249,7 @@ class Format:
             elif isinstance(p, (bytes, bytearray, memoryview, str)):
                 self.parts.append(_bytes(p))
             else:
-                raise TypeError(f"not a template part: {p!r} (closures cannot run on the device; use bytes / str, Col, Col[a:b], Int, Float)")
+                raise TypeError(f"not a template part: {p!r} (closures cannot run on the device; use bytes / str, Col, Col[a:b], Int, Float, Time)")
 
     def __repr__(self):
         return f"Format{tuple(self.parts)!r}"
@@ -259,7 +303,7 @@ def _template(t) -> Format:
 def _pred_columns(pred) -> list:
     if isinstance(pred, _P.Like):
         return [name for name, _ in pred.items]
-    if isinstance(pred, (_P._NumCmp, _P.StrCmp, _P._StrTest)):
+    if isinstance(pred, (_P._NumCmp, _P.StrCmp, _P._StrTest, _P.TimeCmp)):
         return [pred.column]
     if isinstance(pred, _P.Not):
         return _pred_columns(pred.pred)
@@ -294,7 +338,7 @@ def columns(template) -> list:
 
 def compile(template, column_names):   # noqa: A001 (the name predicates.compile uses)
     """(names of the columns used, pieces).  A piece is (LITERAL, 0, bytes), (COLUMN, k, None) with k indexing the returned
-    name list, (SLICE, k, (from, to)), (INT64, 0, Int) or (FLOAT64, 0, Float).  A Col (or the Col of a Slice) whose name is not among `column_names` becomes its default as a literal — in
+    name list, (SLICE, k, (from, to)), (INT64, 0, Int), (FLOAT64, 0, Float) or (TIME, 0, Time).  A Col (or the Col of a Slice) whose name is not among `column_names` becomes its default as a literal — in
     structure-of-arrays a column is present for all rows or for none — and without a default raises MissingColumn.
     Neighbouring literals are joined.  Raises ValueError beyond the ABI's limits (16 pieces, 16 columns)."""
     known = [str(c) for c in column_names]
@@ -310,6 +354,8 @@ def compile(template, column_names):   # noqa: A001 (the name predicates.compile
     for p in _template(template).parts:
         if isinstance(p, bytes):
             literal(p)
+        elif isinstance(p, Time):
+            pieces.append((TIME, 0, p))
         elif isinstance(p, Int):
             pieces.append((INT64, 0, p))
         elif isinstance(p, Float):
@@ -424,7 +470,11 @@ def render(template, row, i: int = 0) -> bytes:
             out.append(p)
         elif isinstance(p, (Int, Float)) and p.expr is not None:
             v = _expr_value(p, row, i)
-            out.append(itoa(v) if isinstance(p, Int) else ftoa(v, p.prec))
+            out.append(_T.format_model(v, p.zone) if isinstance(p, Time) else itoa(v) if isinstance(p, Int) else ftoa(v, p.prec))
+        elif isinstance(p, Time):
+            if p.device:
+                raise ValueError("render: a Time part on the device has no host values")
+            out.append(_T.format_model(p.values[i], p.zone))
         elif isinstance(p, Int):
             if p.device:
                 raise ValueError("render: an Int part on the device has no host values")

@@ -359,7 +359,7 @@ class NumCol:
         self.nerrors, self.host_rows = int(c.nerrors), int(c.host_rows)
         self.first_error_row = None if int(c.first_error_row) == N.CPH_NO_ROW else int(c.first_error_row)
         self.first_error_kind = int(c.first_error_kind)
-        dt = np.int64 if self.kind == N.CPH_NUM_INT64 else np.float64
+        dt = np.float64 if self.kind == N.CPH_NUM_FLOAT64 else np.int64   # INT64 and the two TIME kinds
         if self.mem == N.CPH_MEM_HOST:
             self.values = N._ptr_array(c.values, self.nrows, dt).copy() if self.nrows else np.zeros(0, dt)
             self.status = N._ptr_array(c.status, self.nrows, np.uint8).copy() if self.nrows else np.zeros(0, np.uint8)
@@ -409,6 +409,17 @@ def to_float(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, out_mem: int
     """Row.ValueAsFloat64 (csvplus.go:187-205): strconv.ParseFloat(s, 64), correctly rounded.  `host_rows` of the result
     counts the rows the device deferred to the library's host side (19+ significant digits, extreme exponents)."""
     return _to_number(ctx, col, row_ids, nrows, N.CPH_NUM_FLOAT64, out_mem)
+
+
+def to_time(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, unit: str = "s", out_mem: int = N.CPH_MEM_HOST):
+    """`t, err := time.Parse(time.RFC3339, row[col])` for every row, on the device: a NumCol of int64 like to_int's, holding
+    t.Unix() (unit "s": whole seconds since 1970-01-01T00:00:00Z, the floor) or t.UnixNano() (unit "ns").  The accepted set
+    is the strict RFC 3339 profile stated in include/csvplus_hip.h; csvplus_amd.timeconv.parse_model is the host model.  A row
+    that does not convert is data (status, nerrors, first_error_row, first_error_kind), its value 0; host_rows is always 0.
+    row_ids / nrows as in to_int."""
+    if unit not in ("s", "ns"):
+        raise ValueError(f"to_time: unit must be 's' or 'ns', not {unit!r}")
+    return _to_number(ctx, col, row_ids, nrows, N.CPH_NUM_TIME_UNIX if unit == "s" else N.CPH_NUM_TIME_UNIXNANO, out_mem)
 
 
 # ---- numeric expressions per row (cph_num_eval) ---------------------------------------------------------------------------
@@ -538,8 +549,8 @@ def _map_rows(cols_by_name, row_ids, nrows, names, pieces, keep, who):
     ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
     if cols:
         return _rowsel(cols, ids, nrows, keep)
-    exprs = [p[2].expr for p in pieces if p[0] in (M.INT64, M.FLOAT64) and p[2].expr is not None]
-    counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64) and p[2].expr is None]
+    exprs = [p[2].expr for p in pieces if p[0] in (M.INT64, M.FLOAT64, M.TIME) and p[2].expr is not None]
+    counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64, M.TIME) and p[2].expr is None]
     from . import expr as E
     ecols = [nm for e in exprs for nm in E.columns(e) if nm in cols_by_name]
     if nrows is not None:
@@ -592,7 +603,7 @@ def _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending=
                     keep.append(nc.values)
                     mem, ptr = N.CPH_MEM_HOST, nc.values.ctypes.data if n else None
             elif value.count < n:
-                raise ValueError(f"map_column: {'an Int' if kind == M.INT64 else 'a Float'} part has {value.count} values for {n} rows")
+                raise ValueError(f"map_column: {'an Int' if kind == M.INT64 else 'a Time' if kind == M.TIME else 'a Float'} part has {value.count} values for {n} rows")
             elif value.device:
                 mem, ptr = N.CPH_MEM_DEVICE, value.values or None
             else:
@@ -601,6 +612,8 @@ def _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending=
             parr[k].arg = mem
             if kind == M.INT64:
                 parr[k].ints = ptr
+            elif kind == M.TIME:
+                parr[k].ints, parr[k].prec = ptr, value.zone
             else:
                 parr[k].floats, parr[k].prec = ptr, value.prec
     return parr
@@ -762,7 +775,7 @@ def order_rows(ctx: N.Context, keys, nrows: int, skip: int = 0, limit=None, out_
             continue
         dt = np.int64 if key.kind == N.CPH_NUM_INT64 else np.float64
         if isinstance(src, NumCol):
-            if src.kind != key.kind:
+            if (N.CPH_NUM_FLOAT64 if src.kind == N.CPH_NUM_FLOAT64 else N.CPH_NUM_INT64) != key.kind:   # to_time's kinds hold int64
                 raise ValueError(f"{type(key).__name__}: the NumCol's kind differs from the key's")
             if src.nrows < n:
                 raise ValueError(f"{type(key).__name__}: {src.nrows} values for {n} rows")

@@ -2,7 +2,9 @@
 conditions its users write as closures over Row.ValueAsInt / ValueAsFloat64 (csvplus.go:165-205, csvplus_test.go:272-281):
 IntCmp, FloatCmp — and the conditions that look inside a string (`row["ts"] >= "2016-09"`, strings.HasPrefix / HasSuffix /
 Contains): StrCmp, HasPrefix, HasSuffix, Contains.  Those are byte operations in Go; Python's bytes comparison, startswith,
-endswith and `in` are their exact host model.
+endswith and `in` are their exact host model.  TimeCmp compares a column of RFC 3339 timestamps as INSTANTS
+(`t, err := time.Parse(time.RFC3339, row["ts"]); return err == nil && t.Unix() REL u.Unix()`): two stamps of one instant in
+different zones are equal, which their bytes are not; csvplus_amd.timeconv is its host model.
 
 A Go closure cannot run on a GPU; these are declarative and can.  `compile` flattens any nesting of them into the
 postfix program cph_filter_rows takes (include/csvplus_hip.h), `matches` evaluates a predicate on one row held as a dict —
@@ -20,6 +22,7 @@ LIKE, NOT, ALL, ANY = 1, 2, 3, 4   # CPH_PRED_*
 INT_LT, FLT_LT = 16, 24            # CPH_PRED_INT_LT / CPH_PRED_FLT_LT; + the relation's index in RELS
 STR_LT = 32                        # CPH_PRED_STR_LT; + the relation's index in RELS
 HAS_PREFIX, HAS_SUFFIX, CONTAINS = 40, 41, 42   # CPH_PRED_*
+TIME_LT = 48                       # CPH_PRED_TIME_LT; + the relation's index in RELS
 RELS = ("<", "<=", "==", "!=", ">=", ">")
 MAX_OPS, MAX_LIKE, MAX_STACK = 64, 32, 32
 NUM_OK, NUM_ERR_SYNTAX, NUM_ERR_RANGE, NUM_ERR_UNSUPPORTED = 0, 1, 2, 3   # CPH_NUM_*
@@ -125,6 +128,28 @@ class StrCmp(Pred):
         return f"StrCmp({self.column!r}, {self.rel!r}, {self.literal!r})"
 
 
+class TimeCmp(Pred):
+    """TimeCmp("ts", ">=", "2016-09-14T00:00:00Z"): the column's RFC 3339 stamp REL the literal's, both as Unix seconds
+    (t.Unix(): a fraction in the column is floored).  The literal is RFC 3339 text that must convert (timeconv.parse_model)
+    and carry no fraction — the term compares whole seconds — else ValueError.  A row whose value does not convert (or that
+    lacks the column) is false under every relation, "!=" included."""
+
+    def __init__(self, column, rel, literal):
+        from . import timeconv as T
+        if rel not in RELS:
+            raise ValueError(f"unknown relation {rel!r}: one of {' '.join(RELS)}")
+        lit = _bytes(literal)
+        status, secs = T.parse_model(lit, "s")
+        if status != NUM_OK:
+            raise ValueError(f"TimeCmp: the literal {lit!r} is no RFC 3339 timestamp this library converts (status {status})")
+        if b"." in lit:
+            raise ValueError(f"TimeCmp: the literal {lit!r} has a fraction: the term compares whole seconds")
+        self.column, self.rel, self.literal, self.seconds = str(column), rel, lit, secs
+
+    def __repr__(self):
+        return f"TimeCmp({self.column!r}, {self.rel!r}, {self.literal!r})"
+
+
 class _StrTest(Pred):
     op = None
 
@@ -154,7 +179,7 @@ class Contains(_StrTest):
 def _operands(preds):
     for p in preds:
         if not isinstance(p, Pred):
-            raise TypeError(f"not a predicate: {p!r} (closures cannot run on the device; use Like / All / Any / Not / IntCmp / FloatCmp / StrCmp / HasPrefix / HasSuffix / Contains)")
+            raise TypeError(f"not a predicate: {p!r} (closures cannot run on the device; use Like / All / Any / Not / IntCmp / FloatCmp / StrCmp / HasPrefix / HasSuffix / Contains / TimeCmp)")
     return list(preds)
 
 
@@ -292,6 +317,17 @@ def _str_holds(op, value, literal) -> bool:
     return _cmp(RELS[op - STR_LT], v, literal)
 
 
+def _is_time_op(op) -> bool:
+    return TIME_LT <= op < TIME_LT + len(RELS)
+
+
+def _time_holds(rel, value, literal) -> bool:
+    """One time term on a present value: both sides through timeconv.parse_model, whole seconds."""
+    from . import timeconv as T
+    status, v = T.parse_model(value, "s")
+    return status == NUM_OK and _cmp(rel, v, T.parse_model(literal, "s")[1])
+
+
 def _is_str_op(op) -> bool:
     return STR_LT <= op < STR_LT + len(RELS) or op in (HAS_PREFIX, HAS_SUFFIX, CONTAINS)
 
@@ -305,7 +341,7 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
     """(names of the columns used, postfix ops).  An op is (LIKE, column, value bytes) with `column` indexing the returned
     name list, or -1 for a name that is not among `column_names` (the row has no such column: false, :1286); a numeric term
     (INT_LT / FLT_LT + relation, column, 8 literal bytes); a string term (STR_LT + relation / HAS_PREFIX / HAS_SUFFIX /
-    CONTAINS, column, literal bytes); (NOT, 0, None);
+    CONTAINS, column, literal bytes); a time term (TIME_LT + relation, column, the literal's RFC 3339 text); (NOT, 0, None);
     (ALL, k, None); (ANY, k, None).  Raises ValueError beyond the ABI's limits (64 ops, 32 LIKE terms, stack of 32)."""
     known = [str(c) for c in column_names]
     used: list[str] = []
@@ -332,8 +368,8 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
                 if p.column not in used:
                     used.append(p.column)
                 ops.append((op, used.index(p.column), lit))
-        elif isinstance(p, (StrCmp, _StrTest)):
-            op = STR_LT + RELS.index(p.rel) if isinstance(p, StrCmp) else p.op
+        elif isinstance(p, (StrCmp, _StrTest, TimeCmp)):
+            op = TIME_LT + RELS.index(p.rel) if isinstance(p, TimeCmp) else STR_LT + RELS.index(p.rel) if isinstance(p, StrCmp) else p.op
             if p.column not in known:
                 ops.append((op, -1, p.literal))
             else:
@@ -388,6 +424,11 @@ def matches(pred: Pred, row) -> bool:
             v = row.get(pred.column.encode("utf-8"))
         op = STR_LT + RELS.index(pred.rel) if isinstance(pred, StrCmp) else pred.op
         return v is not None and _str_holds(op, v, pred.literal)
+    if isinstance(pred, TimeCmp):
+        v = row.get(pred.column)
+        if v is None:
+            v = row.get(pred.column.encode("utf-8"))
+        return v is not None and _time_holds(pred.rel, v, pred.literal)
     if isinstance(pred, Not):
         return not matches(pred.pred, row)
     if isinstance(pred, All):
@@ -405,6 +446,8 @@ def run_ops(ops, values) -> bool:
             st.append(arg >= 0 and _bytes(values[arg]) == value)
         elif _is_str_op(op):
             st.append(arg >= 0 and _str_holds(op, values[arg], value))
+        elif _is_time_op(op):
+            st.append(arg >= 0 and _time_holds(RELS[op - TIME_LT], values[arg], value))
         elif op >= INT_LT:
             flt = op >= FLT_LT
             (lit,) = struct.unpack("<d" if flt else "<q", value)

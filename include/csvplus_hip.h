@@ -731,25 +731,35 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
  * included — the rule of LIKE and of the numeric terms.  CONTAINS is a per-row search whose worst case is quadratic in the
  * value's length (a value that repeats the literal's first byte and mismatches late).
  *
- * Every LIKE, numeric and string term counts against CPH_PRED_MAX_LIKE (32 terms in all).  The valid ops are 1..4, 16..21,
- * 24..29, 32..37 and 40..42; every other op (0, 5..15, 22, 23, 30, 31, 38, 39, 43..) is invalid.
+ * Time terms — `t, err := time.Parse(time.RFC3339, row["ts"]); return err == nil && !t.Before(start)` as data:
+ *   CPH_PRED_TIME_LT .. CPH_PRED_TIME_GT (48..53, in the order LT LE EQ NE GE GT)   push (t.Unix() of column `arg`) REL (u.Unix() of the literal)
+ * `value` is the literal as RFC 3339 TEXT (host memory); the host converts it with the routine the device runs.  A literal
+ * that does not convert with CPH_NUM_OK (cph_col_to_number, CPH_NUM_TIME_UNIX) fails the call with CPH_ERR_INVALID, and so does
+ * a literal with a fraction: the term compares WHOLE SECONDS, a fraction would mislead.  The column is converted first through
+ * the path of cph_col_to_number (once per column and call); a row that does not convert pushes FALSE under every relation, NE
+ * included, and arg = -1 pushes false.  Two stamps of the same instant in different zones are equal here, which their bytes
+ * (CPH_PRED_STR_*) are not.
+ *
+ * Every LIKE, numeric, string and time term counts against CPH_PRED_MAX_LIKE (32 terms in all).  The valid ops are 1..4, 16..21,
+ * 24..29, 32..37, 40..42 and 48..53; every other op (0, 5..15, 22, 23, 30, 31, 38, 39, 43..47, 54..) is invalid.
  *
  * Out of scope for a condition: comparing a column against ANOTHER COLUMN; case mapping and TrimSpace (Go's are
- * Unicode-aware: a project of their own); splitting on a delimiter; regular expressions; parsing a timestamp (an RFC3339
- * column in one zone orders as its bytes do, which is what the compare ops give).
+ * Unicode-aware: a project of their own); splitting on a delimiter; regular expressions; time layouts other than RFC 3339,
+ * named zones, and comparing below the second.
  */
 enum { CPH_PRED_LIKE = 1, CPH_PRED_NOT = 2, CPH_PRED_ALL = 3, CPH_PRED_ANY = 4 };
 enum { CPH_PRED_INT_LT = 16, CPH_PRED_INT_LE = 17, CPH_PRED_INT_EQ = 18, CPH_PRED_INT_NE = 19, CPH_PRED_INT_GE = 20, CPH_PRED_INT_GT = 21 };
 enum { CPH_PRED_FLT_LT = 24, CPH_PRED_FLT_LE = 25, CPH_PRED_FLT_EQ = 26, CPH_PRED_FLT_NE = 27, CPH_PRED_FLT_GE = 28, CPH_PRED_FLT_GT = 29 };
 enum { CPH_PRED_STR_LT = 32, CPH_PRED_STR_LE = 33, CPH_PRED_STR_EQ = 34, CPH_PRED_STR_NE = 35, CPH_PRED_STR_GE = 36, CPH_PRED_STR_GT = 37 };
 enum { CPH_PRED_HAS_PREFIX = 40, CPH_PRED_HAS_SUFFIX = 41, CPH_PRED_CONTAINS = 42 };
+enum { CPH_PRED_TIME_LT = 48, CPH_PRED_TIME_LE = 49, CPH_PRED_TIME_EQ = 50, CPH_PRED_TIME_NE = 51, CPH_PRED_TIME_GE = 52, CPH_PRED_TIME_GT = 53 };
 #define CPH_PRED_MAX_OPS   64
 #define CPH_PRED_MAX_LIKE  32
 #define CPH_PRED_MAX_STACK 32
 typedef struct {
     int32_t    op;      /* CPH_PRED_* */
-    int32_t    arg;     /* LIKE / INT_* / FLT_* / STR_* / HAS_* / CONTAINS: column (index into cols) or -1; ALL / ANY: operand count; NOT: ignored */
-    cph_strval value;   /* LIKE / STR_* / HAS_* / CONTAINS: the literal's bytes; INT_* / FLT_*: 8 bytes, an int64_t / a double; host memory */
+    int32_t    arg;     /* LIKE / INT_* / FLT_* / STR_* / HAS_* / CONTAINS / TIME_*: column (index into cols) or -1; ALL / ANY: operand count; NOT: ignored */
+    cph_strval value;   /* LIKE / STR_* / HAS_* / CONTAINS: the literal's bytes; INT_* / FLT_*: 8 bytes, an int64_t / a double; TIME_*: RFC 3339 text; host memory */
 } cph_pred_op;
 
 enum { CPH_FILTER_WHERE = 0, CPH_FILTER_TAKE_WHILE = 1, CPH_FILTER_DROP_WHILE = 2 };
@@ -787,7 +797,7 @@ typedef struct {
  * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / prog / opts / out, cols NULL with ncols > 0, nops outside
  * 1..CPH_PRED_MAX_OPS, an unknown op, a LIKE / numeric / string-term column outside -1..ncols-1, a LIKE or string-term value
  * with a length but no pointer, a string-term literal of 4 GiB or more,
- * a numeric literal that is not exactly 8 bytes behind a non-NULL pointer,
+ * a numeric literal that is not exactly 8 bytes behind a non-NULL pointer, a time literal that is no whole-second RFC 3339 stamp,
  * a negative or too large ALL / ANY count (stack underflow), a NOT on an empty stack, a program that does not leave
  * exactly one value, the limits above, out_bits or row-id bits other than 32 / 64, an unknown mode or out_mem, a short
  * identity column.  CPH_ERR_TOO_MANY_ROWS when out_bits == 32 and first_row + nrows > 2^32 - 1, and when nrows alone is
@@ -829,17 +839,36 @@ CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel
  * significant digits, none dropped but zeros) is below 2^53 and whose decimal exponent lies in -22..37 (Clinger's exact
  * cases: one IEEE operation); the other valid rows are finished on the library's host side, and `host_rows` counts them.
  *
+ * CPH_NUM_TIME_UNIX / CPH_NUM_TIME_UNIXNANO = `t, err := time.Parse(time.RFC3339, s)` followed by t.Unix() (whole seconds
+ * since 1970-01-01T00:00:00Z, the FLOOR: "1969-12-31T23:59:59.5Z" is -1) / t.UnixNano(); both write int64_t[nrows], and
+ * host_rows is always 0.  The reference pins nothing about timestamps, so the accepted set is the strict RFC 3339 profile
+ * that time.Parse(time.RFC3339, s) and Time.UnmarshalText accept with the same meaning.  With D a byte '0'..'9' the value
+ * must be, in full:   DDDD-DD-DDTDD:DD:DD  [ '.' D{1,9} ]  ( 'Z' | ('+'|'-') DD:DD )
+ * A row's status is decided in this order:
+ *   1. CPH_NUM_ERR_UNSUPPORTED  the value matches only after one or more of these relaxations: the hour written with one
+ *      digit ("...T8:48:22Z"), ',' in place of the fraction's '.', more than 9 fraction digits.  Go's lenient Parse accepts or
+ *      truncates these and Go versions differ on them; this library does not decide (the stance of '_' and 0x above).
+ *   2. CPH_NUM_ERR_SYNTAX       every other value that does not match: "", a lower-case t or z, a blank for the T, a missing
+ *      zone, "+0100", '.' without digits, trailing bytes.
+ *   3. CPH_NUM_ERR_RANGE        month outside 1..12, day outside 1..days(month, year) (proleptic Gregorian; year 0000 is valid
+ *      and a leap year), hour > 23, minute > 59, second > 59 ("23:59:60" is a range error, as in Go).
+ *   4. CPH_NUM_ERR_UNSUPPORTED  zone hour > 23 or zone minute > 59.
+ *   5. CPH_NUM_ERR_UNSUPPORTED  CPH_NUM_TIME_UNIXNANO only: the result does not fit an int64 (before 1677-09-21T00:12:43.145224192Z
+ *      or after 2262-04-11T23:47:16.854775807Z); Go documents UnixNano as undefined there.
+ * The value at every error row is 0.  The instant is civil(date, time) - offset; "-00:00" is offset 0; years 0000..9999 all
+ * fit CPH_NUM_TIME_UNIX.  Other layouts, named zones and DST rules are out of scope.
+ *
  * A conversion error is DATA: the call returns CPH_OK and the struct says what failed.  col / sel / nrows mean what they
  * mean for cph_csv_write_rows with one column (host or device, fixed-width or 32 / 64-bit offsets, optional row ids with
  * a base: a Join's output converts without being materialised).  CPH_ERR_INVALID (with a message): NULL ctx / col / out,
  * an unknown kind or out_mem, row-id bits other than 32 / 64, an identity column whose row count is not nrows.
  * nrows == 0 is legal (values and status are NULL).
  */
-enum { CPH_NUM_INT64 = 1, CPH_NUM_FLOAT64 = 2 };
+enum { CPH_NUM_INT64 = 1, CPH_NUM_FLOAT64 = 2, CPH_NUM_TIME_UNIX = 4, CPH_NUM_TIME_UNIXNANO = 5 };   /* 0, 3: invalid */
 enum { CPH_NUM_OK = 0, CPH_NUM_ERR_SYNTAX = 1, CPH_NUM_ERR_RANGE = 2, CPH_NUM_ERR_UNSUPPORTED = 3 };
 typedef struct {
     uint64_t       nrows;
-    const void*    values;          /* int64_t[nrows] or double[nrows], in `mem`; what Go returns beside the error at error rows */
+    const void*    values;          /* int64_t[nrows] (INT64, TIME_*) or double[nrows], in `mem`; what Go returns beside the error at error rows */
     const uint8_t* status;          /* CPH_NUM_* per row, in `mem` */
     int32_t        kind, mem;
     uint64_t       nerrors;
@@ -953,6 +982,12 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  *                    the value's end, both ends are then clamped into [0, len], from >= to gives the empty string, and
  *                    to == INT64_MAX means "to the end".  Bytes, not runes, as in Go.  One deviation: where Go panics on an
  *                    index out of range, this clamps.
+ *   CPH_MAP_TIME     ints[i] = Unix seconds of OUTPUT row i (the rules of INT64: `arg` is the memory space, a host array is
+ *                    staged, no row ids), written as time.Unix(v, 0).In(time.FixedZone("", 60 * prec)).Format(time.RFC3339)
+ *                    does.  `prec` carries the zone as minutes east of UTC, -1439..1439: "YYYY-MM-DDTHH:MM:SSZ" (20 bytes) when
+ *                    prec == 0, otherwise "YYYY-MM-DDTHH:MM:SS+HH:MM" / "-HH:MM" (25 bytes).  A value whose LOCAL year falls
+ *                    outside 0000..9999 is not formatted: the call fails with CPH_ERR_INVALID, the message names the piece and
+ *                    the LOWEST such output row, *out stays NULL — exactly as for the FLOAT64 limit.
  * All bytes are copied verbatim (NUL and bytes >= 0x80 included); nothing is escaped.
  *
  * cols / sel / nrows mean exactly what they mean for cph_csv_write_rows (host or device columns, fixed-width or 32 / 64-bit
@@ -965,28 +1000,31 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  * legal and yields an empty column.
  *
  * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / pieces / out, npieces outside 1..CPH_MAP_MAX_PIECES, an
- * unknown kind (5..7 included), a COLUMN or SLICE index outside 0..ncols-1 (a column the rows lack is the host's business:
+ * unknown kind (5..7 and 9 included), a COLUMN or SLICE index outside 0..ncols-1 (a column the rows lack is the host's business:
  * it substitutes a literal or reports the reference's missing-column error), a SLICE whose value is not exactly 16 bytes
  * behind a non-NULL pointer, a literal with a length but no pointer, an INT64 piece with ints ==
  * NULL while nrows > 0 or with an unknown memory space, a FLOAT64 piece with floats == NULL while nrows > 0, with an unknown
- * memory space or with prec outside 0..22, a FLOAT64 value beyond the range above (found while the call runs), ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
+ * memory space or with prec outside 0..22, a FLOAT64 value beyond the range above (found while the call runs), a TIME piece with
+ * ints == NULL while nrows > 0, with an unknown memory space or with prec outside -1439..1439, a TIME value whose local year is
+ * outside 0000..9999 (found while the call runs), ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
  * than 32 / 64, an identity column whose row count is not nrows, an unknown out_mem.
  *
  * Out of scope: the other forms of FormatFloat — the shortest round-trip digits (prec -1) and the 'e' / 'g' formats, a
  * project of their own —; case mapping and TrimSpace (Go's are Unicode-aware: a project of their own); splitting a value
- * on a delimiter; regular expressions; timestamp parsing; a slice whose ends come from another column.  A value that
+ * on a delimiter; regular expressions; a slice whose ends come from another column; time layouts other than RFC 3339, named
+ * zones and DST rules.  A value that
  * depends on a condition is cph_map_switch's.
  */
-enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4, CPH_MAP_SLICE = 8 };   /* 5..7: invalid */
+enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4, CPH_MAP_SLICE = 8, CPH_MAP_TIME = 10 };   /* 5..7, 9: invalid */
 #define CPH_MAP_MAX_PIECES 16
 typedef struct { int64_t from, to; } cph_map_slice;   /* what a SLICE piece's `value` points at: 16 bytes */
 typedef struct {
     int32_t        kind;    /* CPH_MAP_* */
-    int32_t        arg;     /* COLUMN / SLICE: index into cols; INT64 / FLOAT64: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
+    int32_t        arg;     /* COLUMN / SLICE: index into cols; INT64 / FLOAT64 / TIME: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
     cph_strval     value;   /* LITERAL: its bytes (host memory, any length, any byte values); SLICE: a cph_map_slice, len == 16 */
-    const int64_t* ints;    /* INT64: nrows values, entry i belongs to OUTPUT row i (no row ids) */
+    const int64_t* ints;    /* INT64 / TIME: nrows values, entry i belongs to OUTPUT row i (no row ids) */
     const double*  floats;  /* FLOAT64: likewise */
-    int32_t        prec;    /* FLOAT64: digits behind the point, 0..22 */
+    int32_t        prec;    /* FLOAT64: digits behind the point, 0..22; TIME: the zone, minutes east of UTC, -1439..1439 */
     int32_t        reserved_;
 } cph_map_piece;
 
@@ -1010,11 +1048,12 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  *
  * Selection.  Row i takes the alternative a = the lowest case index whose program holds, or ncases (`otherwise`) if none
  * does.  Its value is that alternative's pieces rendered exactly as cph_map_format renders them (LITERAL / COLUMN / INT64 /
- * FLOAT64 / SLICE; verbatim bytes; FormatInt and FormatFloat 'f' rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
+ * FLOAT64 / SLICE / TIME; verbatim bytes; FormatInt, FormatFloat 'f' and RFC 3339 rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
  * memory, written when the call succeeds).
  *
- * Number pieces.  INT64 / FLOAT64 arrays have nrows entries indexed by OUTPUT row.  Entries of rows that select ANOTHER
- * alternative are never interpreted and may hold anything; in particular the FLOAT64 refusal (a finite |v| >= 2^128) fails
+ * Number pieces.  INT64 / FLOAT64 / TIME arrays have nrows entries indexed by OUTPUT row.  Entries of rows that select ANOTHER
+ * alternative are never interpreted and may hold anything; in particular the FLOAT64 refusal (a finite |v| >= 2^128) and the
+ * TIME refusal (a local year outside 0000..9999) fail
  * the call only for a row that selects the alternative holding that piece.  The message then names the alternative, the
  * piece and the lowest such row, and *out stays NULL.
  *
@@ -1029,7 +1068,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  *
  * Out of scope: nested switches; a conditional part inside a template (use one Switch over whole templates); a condition
  * that compares a column against another column; case mapping and TrimSpace; splitting on a delimiter; regular expressions;
- * timestamp parsing; the other forms of FormatFloat.
+ * the other forms of FormatFloat; time layouts other than RFC 3339.
  */
 #define CPH_MAP_MAX_CASES         8
 #define CPH_MAP_SWITCH_MAX_PIECES 32      /* the pieces of all alternatives together */

@@ -3,6 +3,8 @@
 
     to_int               over `rows` values of 1-7 decimal digits
     to_float             over `rows` price-like values ("%d.%02d", integer part < 100 000)
+    to_time              over `rows` RFC 3339 stamps of 25 bytes ("YYYY-MM-DDTHH:MM:SS+HH:MM", three zone offsets); its yardstick
+                         is the to_int line of the same run: the same kernel geometry over 8-byte values
     filter_rows(IntCmp)  WHERE v > median over the integer column
     filter_rows(Like)    WHERE v == one of its values over the same column — the yardstick: it reads the same bytes
                          through the same evaluation kernel (it runs without this feature too: measure it at the parent
@@ -69,6 +71,27 @@ def decimal_column(v, frac=None):
     return StrCol(data, offs.astype(np.uint32), len(v), 32)
 
 
+def two_digits(out, at, v):
+    out[:, at] = 0x30 + v // 10
+    out[:, at + 1] = 0x30 + v % 10
+
+
+def stamp_column(n, rng):
+    """n stamps "2016-MM-DDTHH:MM:SS+HH:MM" (25 bytes each, variable-length layout with 32-bit offsets), built with numpy."""
+    out = np.empty((n, 25), dtype=np.uint8)
+    out[:] = np.frombuffer(b"2016-00-00T00:00:00+00:00", dtype=np.uint8)
+    two_digits(out, 5, rng.integers(1, 13, n))
+    two_digits(out, 8, rng.integers(1, 29, n))
+    two_digits(out, 11, rng.integers(0, 24, n))
+    two_digits(out, 14, rng.integers(0, 60, n))
+    two_digits(out, 17, rng.integers(0, 60, n))
+    zone = rng.integers(0, 3, n)
+    out[:, 19] = np.array([0x2B, 0x2B, 0x2D], dtype=np.uint8)[zone]
+    two_digits(out, 20, np.array([0, 2, 5])[zone])
+    two_digits(out, 23, np.array([0, 0, 30])[zone])
+    return StrCol(out.reshape(-1), (np.arange(n + 1, dtype=np.uint64) * 25).astype(np.uint32), n, 32, fixed_width=0)
+
+
 def profiled(fn):
     ctx.profile(True)
     ctx.profile_read(reset=True)
@@ -130,4 +153,15 @@ if not LIKE_ONLY:
     host_rows = r.host_rows
     r.release()
     report("to_float", timed(f, REPS), hflt.nbytes_values() + hflt.nbytes_offsets() + 9 * M, f"host_rows {host_rows} | " + profiled(f))
+    del dflt, hflt
+    torch.cuda.empty_cache()
+    from csvplus_amd.materialize import to_time
+
+    htim = stamp_column(M, rng)
+    dtim = htim.to_device()
+    f = lambda: to_time(ctx, dtim, out_mem=N.CPH_MEM_DEVICE).release()   # noqa: E731
+    r = to_time(ctx, dtim, out_mem=N.CPH_MEM_DEVICE)
+    assert r.nerrors == 0
+    r.release()
+    report("to_time", timed(f, REPS), htim.nbytes_values() + htim.nbytes_offsets() + 9 * M, profiled(f))
 ctx.close()
