@@ -645,6 +645,10 @@ CPH_API int32_t cph_ctx_set_option(cph_ctx* ctx, const char* name, int64_t value
         if (value != 0 && value != 1) return fail_with(ctx, {CPH_ERR_INVALID, "direct_sort must be 0 or 1"});
         ctx->direct_sort = (int)value;
     }
+    else if (k == "float_device") {   // 1: float conversions decide the values beyond Clinger's cases on the device (numparse.hip); 0: the host does
+        if (value != 0 && value != 1) return fail_with(ctx, {CPH_ERR_INVALID, "float_device must be 0 or 1"});
+        ctx->float_device = (int)value;
+    }
     else if (k == "chain_arith") ctx->chain_arith = value != 0;
     else if (k == "chain_identity") ctx->chain_identity = value != 0;
     else if (k == "chain_prejoin") ctx->chain_prejoin = value != 0;

@@ -370,6 +370,8 @@ struct cph_ctx {
     int hash_partitioned = 1;      // the hash table of a duplicate-free index of >= 2^21 keys is built slice by slice in LDS (probe.hip); 0: CAS into the whole
                                    // table; 2: slice by slice whatever the size (tests)
     int counted_sort = 1;          // IndexOn over 32-bit codes with duplicates: MSD sort through counted LDS windows (counted_sort.hip); 0: the classic passes
+    int float_device = 0;          // float conversions (convert_rows, numparse.hip): 1 = the values outside Clinger's exact cases are decided on the
+                                   // device by the Eisel-Lemire conversion and only those it cannot decide go to the host; 0 = all of them do
     int direct_sort = 1;           // a build that expects distinct keys (UniqueIndexOn) over a dense 32-bit code space (rows <= states <= 2 rows)
                                    // sorts by placement, slot[code] = row, in LDS windows (window_sort.hip); a duplicate is noticed on
                                    // the device and the build starts over the general way (A/B switch; 0: always the general way)

@@ -436,6 +436,7 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
             // then the same program over number arrays that carry their status bytes
             bool have[CPH_MAX_KEY_COLS][2] = {};
             double row2 = 0;
+            uint64_t host_rows = 0;   // "float_device": the values the leaves' conversions finished on the host
             for (int q = 0; q < nops; q++) {
                 ExprOp& d = plan.ops[q];
                 if (d.op != CPH_EXPR_COL_INT && d.op != CPH_EXPR_COL_FLT) {
@@ -449,6 +450,7 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
                     NumColStats st;
                     CPH_TRY(convert_rows(ctx, arg.c[c], ids.ids[c], 0, n, f ? CPH_NUM_FLOAT64 : CPH_NUM_INT64, &cv, &cs, &st));
                     have[c][f] = true;
+                    host_rows += st.host_rows;
                 }
                 d.op = f ? CPH_EXPR_NUM_FLT : CPH_EXPR_NUM_INT;
                 d.arg = 0;
@@ -457,6 +459,7 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
                 row2 += 9.0;
             }
             CPH_TRY(launch_eval(ctx, arg, ids, plan, depth, n, (row2 + 9.0) * (double)n, &r->d_values, &r->d_status, &got));
+            if (ctx->float_device) r->pub.host_rows = host_rows;
         }
         r->pub.nerrors = got.nerrors;
         if (got.nerrors) {

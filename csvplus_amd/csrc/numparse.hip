@@ -18,6 +18,9 @@
 //   k_num_collect  (only when there are any) gathers position, span and the first bytes of each deferred row into 128-byte
 //                  slots; the host converts those with a correctly rounded routine and
 //   k_num_patch    writes the values and status bytes back.
+//   With cph_ctx_set_option "float_device" = 1 the float conversion runs the kParseFloatFull instantiation: behind Clinger's
+//   cases it converts with Eisel-Lemire (floatparse_device.hpp, one out-of-line body) and defers only what that leaves
+//   undecided, so collect / host / patch see a few rows per thousand truncated values instead of every 17-digit one.
 #include <algorithm>
 #include <cerrno>
 #include <charconv>
@@ -30,12 +33,36 @@
 
 #include <locale.h>
 
+#include "floatparse_device.hpp"
 #include "numparse_device.hpp"
 #include "timeparse_device.hpp"
 
 namespace cph {
 
-constexpr int kParseInt = 0, kParseFloat = 1, kParseTime = 2;   // the instantiations of k_num_parse
+// the instantiations of k_num_parse; kParseFloatFull (cph_ctx_set_option "float_device" = 1) is kParseFloat with the
+// Eisel-Lemire conversion behind Clinger's cases: it defers only what that cannot decide
+constexpr int kParseInt = 0, kParseFloat = 1, kParseTime = 2, kParseFloatFull = 3;
+
+// A valid value outside Clinger's exact cases, decided on the device where Eisel-Lemire can (floatparse_device.hpp).  One
+// out-of-line body per kernel: k_num_parse unrolls 8 rows per lane, and the two call sites in parse_float64 would make
+// sixteen copies of it.  +-Inf is a range error, as the host route reports it; underflow to +-0 or a subnormal is no error.
+// Arguments and result travel in registers (no pointer: an address would need a stack).
+struct FloatBeyondResult {
+    uint64_t bits;   // 0 for a deferred row until it is patched
+    uint32_t st;
+};
+__device__ __noinline__ FloatBeyondResult float_beyond_exact(uint64_t mant, int exp10, uint32_t trunc, uint32_t neg) {
+    uint64_t bits = 0;
+    if (!float_eisel_lemire(mant, (int32_t)exp10, trunc != 0u, &bits)) return {0ull, (uint32_t)kNumDeferred};
+    return {bits | ((uint64_t)neg << 63), bits == kFloatInfBits ? (uint32_t)CPH_NUM_ERR_RANGE : (uint32_t)CPH_NUM_OK};
+}
+struct FloatBeyondDevice {
+    __device__ __forceinline__ uint32_t operator()(uint64_t mant, int exp10, bool trunc, bool neg, double* out) const {
+        const FloatBeyondResult r = float_beyond_exact(mant, exp10, trunc ? 1u : 0u, neg ? 1u : 0u);
+        *out = __longlong_as_double((long long)r.bits);
+        return r.st;
+    }
+};
 
 constexpr int kNumRows  = 8;                          // rows per lane and tile
 constexpr int kNumPhase = 4;                          // ... of which this many are in flight at once
@@ -74,12 +101,12 @@ __device__ __forceinline__ void load_tail16(const DevCol& col, uint64_t begin, u
     *t1 = load_chunk_nobranch<uint64_t>(base8, delta, begin, l32, 3);
 }
 
-// KIND: kParseInt / kParseFloat / kParseTime; nano (kParseTime alone): UnixNano instead of Unix
+// KIND: kParseInt / kParseFloat / kParseFloatFull / kParseTime; nano (kParseTime alone): UnixNano instead of Unix
 template <int KIND>
 __global__ __launch_bounds__(kMatThreads) void k_num_parse(DevCol col, RowIds rid, uint64_t first_row, uint64_t n,
                                                           uint64_t* __restrict__ values, uint8_t* __restrict__ status, NumCounters* cnt,
                                                           uint32_t nano) {
-    constexpr bool FLT = KIND == kParseFloat;
+    constexpr bool FLT = KIND == kParseFloat || KIND == kParseFloatFull;
     const int lane = lane_id(), wave = wave_id();
     const uint64_t ntiles = (n + kNumTile - 1) / kNumTile;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -114,7 +141,8 @@ __global__ __launch_bounds__(kMatThreads) void k_num_parse(DevCol col, RowIds ri
                     bits = (uint64_t)v;
                 } else if constexpr (FLT) {
                     double v;
-                    st = parse_float64(col, b[k], l[k], c0[k], c1[k], &v);
+                    if constexpr (KIND == kParseFloatFull) st = parse_float64(col, b[k], l[k], c0[k], c1[k], &v, FloatBeyondDevice{});
+                    else st = parse_float64(col, b[k], l[k], c0[k], c1[k], &v);
                     bits = (uint64_t)__double_as_longlong(v);
                 } else {
                     int64_t v;
@@ -232,10 +260,15 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
         const double in_row = (col.fixed_width ? (double)col.fixed_width : (double)(col.offset_bits / 8) + 8.0) + (ids.ptr ? (double)(ids.bits / 8) : 0.0);
         // (a timestamp: 20..35 value bytes, counted as 25)
         const double in_time = tim && !col.fixed_width ? 17.0 : 0.0;
-        ProfScope ps(ctx, tim ? "k_num_parse_time" : flt ? "k_num_parse_f64" : "k_num_parse_i64", (in_row + in_time + 9.0) * (double)n);
+        const bool full = flt && ctx->float_device;
+        ProfScope ps(ctx, tim ? "k_num_parse_time" : full ? "k_num_parse_f64_full" : flt ? "k_num_parse_f64" : "k_num_parse_i64",
+                     (in_row + in_time + 9.0) * (double)n);
         if (tim)
             hipLaunchKernelGGL(k_num_parse<kParseTime>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
                                values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), kind == CPH_NUM_TIME_UNIXNANO ? 1u : 0u);
+        else if (full)
+            hipLaunchKernelGGL(k_num_parse<kParseFloatFull>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
         else if (flt)
             hipLaunchKernelGGL(k_num_parse<kParseFloat>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
                                values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);

@@ -148,9 +148,18 @@ __device__ __forceinline__ bool float_exact(uint64_t mant, int exp10, bool neg, 
 __device__ __forceinline__ double signed_zero(bool neg) { return neg ? -0.0 : 0.0; }
 __device__ __forceinline__ double signed_inf(bool neg) { return __longlong_as_double(neg ? 0xFFF0000000000000ll : 0x7FF0000000000000ll); }
 
+// What becomes of a valid value outside Clinger's exact cases — (first <= 19 significant digits != 0, decimal exponent, non-zero
+// digits dropped behind them, sign) -> CPH_NUM_* with *out set, or kNumDeferred.  This one defers them all.
+struct FloatBeyondDefer {
+    __device__ __forceinline__ uint32_t operator()(uint64_t, int, bool, bool, double*) const { return kNumDeferred; }
+};
+
 // strconv.ParseFloat(s, 64).  Returns CPH_NUM_* or kNumDeferred (valid syntax; the library's host side finishes the value);
-// *out = what Go returns beside the error (0 for a deferred row until it is patched).
-__device__ __forceinline__ uint32_t parse_float64(const DevCol& col, uint64_t begin, uint64_t len, uint64_t c0, uint64_t c1, double* out) {
+// *out = what Go returns beside the error (0 for a deferred row until it is patched).  `beyond` decides the values Clinger's
+// cases leave (numparse.hip: the Eisel-Lemire conversion of floatparse_device.hpp).
+template <class Beyond = FloatBeyondDefer>
+__device__ __forceinline__ uint32_t parse_float64(const DevCol& col, uint64_t begin, uint64_t len, uint64_t c0, uint64_t c1, double* out,
+                                                  const Beyond beyond = Beyond{}) {
     *out = 0.0;
     if (len == 0) return CPH_NUM_ERR_SYNTAX;
     const uint32_t b0 = (uint32_t)c0 & 0xFFu;
@@ -183,7 +192,7 @@ __device__ __forceinline__ uint32_t parse_float64(const DevCol& col, uint64_t be
                     return CPH_NUM_OK;
                 }
                 const int exp10 = ndots ? -(int)(nd - 1u - p) : 0;   // at least -15
-                return float_exact(mant, exp10, neg, out) ? CPH_NUM_OK : kNumDeferred;
+                return float_exact(mant, exp10, neg, out) ? CPH_NUM_OK : beyond(mant, exp10, false, neg, out);
             }
         }
     }
@@ -258,8 +267,8 @@ __device__ __forceinline__ uint32_t parse_float64(const DevCol& col, uint64_t be
         *out = signed_zero(neg);
         return CPH_NUM_OK;
     }
-    if (trunc) return kNumDeferred;
-    return float_exact(mant, dp - ndmant, neg, out) ? CPH_NUM_OK : kNumDeferred;
+    if (trunc) return beyond(mant, dp - ndmant, true, neg, out);
+    return float_exact(mant, dp - ndmant, neg, out) ? CPH_NUM_OK : beyond(mant, dp - ndmant, false, neg, out);
 }
 
 }  // namespace cph

@@ -865,6 +865,11 @@ public:
         }
         return ctx_;
     }
+    // cph_ctx_set_option on the process-wide ctx, e.g. SetOption("float_device", 1): ColumnAsFloat64, FloatCmp and float totals
+    // then convert the values outside Clinger's exact cases on the device too.
+    void SetOption(const char* name, int64_t value) {
+        if (cph_ctx_set_option(ctx(), name, value) != CPH_OK) throw std::runtime_error(std::string("csvplus: ") + cph_last_error(ctx()));
+    }
     // The process-wide ctx is deliberately never destroyed: indexes held in static storage may
     // outlive it during exit, and they return their device blocks to this ctx's pool.
     // Rows read ahead per GPU probe call in Join/Except.  1 reproduces the reference's

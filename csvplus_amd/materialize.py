@@ -407,7 +407,11 @@ def to_int(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, out_mem: int =
 
 def to_float(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, out_mem: int = N.CPH_MEM_HOST):
     """Row.ValueAsFloat64 (csvplus.go:187-205): strconv.ParseFloat(s, 64), correctly rounded.  `host_rows` of the result
-    counts the rows the device deferred to the library's host side (19+ significant digits, extreme exponents)."""
+    counts the rows the device deferred to the library's host side: by default every valid value outside Clinger's exact
+    cases (a mantissa of 2^53 or more — anything with 17 significant digits —, 19+ digits, a decimal exponent outside
+    -22..37).  After ctx.set_option("float_device", 1) the device converts those too (Eisel-Lemire) and defers only what
+    that cannot decide: a fraction of a per cent of the values with non-zero digits behind the 19th, and no others.  The
+    values, status bytes and error report are the same either way."""
     return _to_number(ctx, col, row_ids, nrows, N.CPH_NUM_FLOAT64, out_mem)
 
 

@@ -194,6 +194,14 @@ CPH_API int32_t cph_ctx_set_stream(cph_ctx* ctx, void* hip_stream);
  *                   streamed out — all global stores sequential; a duplicate is noticed on the device and the build starts over the
  *                   general way, which also reports where the first duplicate is.  0: always the general way (A/B switch); any other
  *                   value fails with CPH_ERR_INVALID and leaves the setting as it was
+ *   "float_device"  0 / 1 (default 0): 1 = every float conversion (cph_col_to_number with CPH_NUM_FLOAT64 and what shares its path: float
+ *                   compare terms of cph_filter_rows, float specs of cph_index_aggregate, a float order column of cph_index_resolve, the
+ *                   float leaves of cph_num_eval) decides the valid values OUTSIDE Clinger's exact cases on the device as well, with the
+ *                   Eisel-Lemire conversion (one or two 64 x 64 -> 128-bit multiplies by a tabulated power of five); only a value that
+ *                   routine cannot decide — a few per thousand of those with non-zero digits behind the 19th significant one, none
+ *                   of the others — is finished on the host, and `host_rows` of every result counts just those.  0: all values
+ *                   outside Clinger's cases are finished on the host, 128 bytes per row over the bus.  Same values, status bytes and
+ *                   error report either way; any other value fails with CPH_ERR_INVALID and leaves the setting as it was
  *   "stats_sample"  0 / 1 (default 1): IndexOn over ONE fixed-width key column (<= 40 bytes) of >= 2^20 rows learns its per-position
  *                   alphabets from ~65 536 rows spread over the table instead of a pass over all rows; the encode kernel checks every
  *                   row against them, and a row with a byte the sample did not show makes the build start over with the exact
@@ -838,6 +846,10 @@ CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel
  * decide — a stated limit, never a silent wrong answer.  The device converts every value whose mantissa (the first 19
  * significant digits, none dropped but zeros) is below 2^53 and whose decimal exponent lies in -22..37 (Clinger's exact
  * cases: one IEEE operation); the other valid rows are finished on the library's host side, and `host_rows` counts them.
+ * With cph_ctx_set_option "float_device" = 1 the device also converts those other rows (Eisel-Lemire: any mantissa of up to 19
+ * digits with any exponent, overflow to a range error with +-Inf and underflow to +-0 or a denormal included) and hands on only
+ * the ones that conversion leaves undecided — values with non-zero digits behind the 19th whose two neighbours w and w + 1 round
+ * differently, under 1 % of such values; `host_rows` then counts exactly those.  The results are the same bits either way.
  *
  * CPH_NUM_TIME_UNIX / CPH_NUM_TIME_UNIXNANO = `t, err := time.Parse(time.RFC3339, s)` followed by t.Unix() (whole seconds
  * since 1970-01-01T00:00:00Z, the FLOOR: "1969-12-31T23:59:59.5Z" is -1) / t.UnixNano(); both write int64_t[nrows], and

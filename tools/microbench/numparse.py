@@ -10,11 +10,22 @@
                          through the same evaluation kernel (it runs without this feature too: measure it at the parent
                          commit for the comparison; `like` alone as the third argument skips the rest)
 
+    `float` as the third argument measures only the float conversion, over three columns and under both settings of
+    cph_ctx_set_option "float_device" (a library without the option runs setting 0 alone: the parent commit's build, named by
+    CSVPLUS_HIP_LIB, gives the baseline rows):
+        prices       the price column of the to_float line
+        deferred     repr of random doubles in -1e6..1e6 with 17 significant digits: every value outside Clinger's cases
+        mixed        prices with 1 % of the rows replaced by such values
+    (`prices` has `rows` rows, the other two at most 4e6: their texts are made value by value.)
+    The cases are measured round-robin, `rounds` (fourth argument, default 3) times each, so that drift hits all alike.
+
 Per case: warm-up, then REPS synchronised calls with the profiler off (wall time per call), and a second pass with
 cph_ctx_profile on for the kernel times.  Next to it cph_calibrate kind 0, this box's streaming-copy rate.
 
     python tools/microbench/numparse.py [rows=1e8] [reps=20] [like]
+    python tools/microbench/numparse.py 4e6 5 float [rounds=3]
 """
+import os
 import sys
 import time
 from pathlib import Path
@@ -30,6 +41,9 @@ from csvplus_amd.predicates import Like  # noqa: E402
 M = int(float(sys.argv[1])) if len(sys.argv) > 1 else 100_000_000
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 LIKE_ONLY = len(sys.argv) > 3 and sys.argv[3] == "like"
+FLOAT_ONLY = len(sys.argv) > 3 and sys.argv[3] == "float"
+ROUNDS = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+SLOW_ROWS = 4_000_000   # rows of the float mode's `deferred` and `mixed` columns (at most `rows`)
 ctx = Context(0)
 
 
@@ -107,6 +121,79 @@ copy_ms = ctx.calibrate("copy", copy_bytes, reps=10)
 copy_rate = 2 * copy_bytes / (copy_ms * 1e-3)
 print(f"rows {M}, reps {REPS}; streaming copy (cph_calibrate kind 0): {copy_rate / 1e9:.0f} GB/s", flush=True)
 
+
+
+def report(label, wall, bytes_moved, extra):
+    print(f"{label:22s}: call {wall * 1e3:8.3f} ms  {bytes_moved / wall / 1e9:7.1f} GB/s by the model ({100 * bytes_moved / wall / copy_rate:4.1f} % of copy) | {extra}",
+          flush=True)
+
+
+def text_column(values):
+    """A StrCol (32-bit offsets) over a list of bytes."""
+    offs = np.zeros(len(values) + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter((len(v) for v in values), dtype=np.uint64, count=len(values)), out=offs[1:])
+    return StrCol(np.frombuffer(b"".join(values), dtype=np.uint8).copy(), offs.astype(np.uint32), len(values), 32)
+
+
+def deferred_texts(n, rng):
+    """repr of random doubles, those with 17 significant digits: a mantissa >= 10^16 > 2^53 is outside Clinger's cases."""
+    out = []
+    while len(out) < n:
+        for x in rng.uniform(-1e6, 1e6, n - len(out) + 1024).tolist():
+            t = repr(x).encode()
+            if b"e" not in t and len(t.lstrip(b"-").replace(b".", b"").lstrip(b"0")) >= 17 and len(out) < n:
+                out.append(t)
+    return out
+
+
+def float_columns():
+    from csvplus_amd.materialize import to_float
+
+    rng = np.random.default_rng(2)
+    whole, cents = rng.integers(0, 100000, M), rng.integers(0, 100, M)
+    prices = decimal_column(whole.copy(), cents)
+    S = min(M, SLOW_ROWS)   # the columns built value by value in Python
+    slow = deferred_texts(S, rng)
+    mixed = [b"%d.%02d" % (a, b) for a, b in zip(whole[:S].tolist(), cents[:S].tolist())]
+    for i in rng.choice(S, S // 100, replace=False).tolist():
+        mixed[i] = slow[i]
+    cols = {"prices": prices, "deferred": text_column(slow), "mixed": text_column(mixed)}
+    del mixed, slow
+    dev = {k: c.to_device() for k, c in cols.items()}
+    try:
+        ctx.set_option("float_device", 1)
+        ctx.set_option("float_device", 0)
+        settings = (0, 1)
+    except N.CphError:
+        settings = (0,)   # a library from before the option
+    print(f"library {os.environ.get('CSVPLUS_HIP_LIB', N.LIB_PATH)}; float_device settings {settings}; {ROUNDS} rounds of up to {REPS} calls per case "
+          f"(fewer where a call takes long: about 2 s per case); rows: " + ", ".join(f"{k} {c.nrows}" for k, c in cols.items()), flush=True)
+    for rnd in range(ROUNDS):
+        for name, col in dev.items():
+            for opt in settings:
+                if len(settings) > 1:
+                    ctx.set_option("float_device", opt)
+                f = lambda: to_float(ctx, col, out_mem=N.CPH_MEM_DEVICE).release()   # noqa: E731
+                r = to_float(ctx, col, out_mem=N.CPH_MEM_DEVICE)
+                host_rows, nerr = r.host_rows, r.nerrors
+                r.release()
+                sync()
+                t0 = time.perf_counter()
+                f()
+                sync()
+                reps = max(1, min(REPS, int(2.0 / (time.perf_counter() - t0))))
+                wall = timed(f, reps)
+                report(f"{name} opt {opt} round {rnd}", wall, cols[name].nbytes_values() + cols[name].nbytes_offsets() + 9 * cols[name].nrows,
+                       f"{reps} calls | host_rows {host_rows} nerrors {nerr} | " + profiled(f))
+    if len(settings) > 1:
+        ctx.set_option("float_device", 0)
+
+
+if FLOAT_ONLY:
+    float_columns()
+    ctx.close()
+    sys.exit(0)
+
 rng = np.random.default_rng(1)
 digits = rng.integers(1, 8, M)
 ints = (rng.random(M) * 10.0 ** digits).astype(np.int64)
@@ -115,11 +202,6 @@ dint = hint.to_device()
 in_bytes = hint.nbytes_values() + hint.nbytes_offsets()
 cols = {"v": dint}
 like = Like(v=hint.value(0))
-
-
-def report(label, wall, bytes_moved, extra):
-    print(f"{label:22s}: call {wall * 1e3:8.3f} ms  {bytes_moved / wall / 1e9:7.1f} GB/s by the model ({100 * bytes_moved / wall / copy_rate:4.1f} % of copy) | {extra}",
-          flush=True)
 
 
 f = lambda: filter_rows(ctx, cols, like, out_mem=N.CPH_MEM_DEVICE).release()   # noqa: E731
