@@ -1,6 +1,8 @@
 // map_device.hpp — the device pieces the two Map entry points share (map_format.hip: one template per column;
 // map_switch.hip: the template of the first case that holds): a template piece as the kernels see it, FormatInt's digit
-// count and characters, the field of a loaded record, and the loop that puts a run of pieces into a byte sink.
+// count and characters, the field of a loaded record, the bytes one piece adds to a row (map_piece_bytes: the length pass)
+// and the loop that puts a run of pieces into a byte sink (map_put_record: the copy pass).  The kernels keep their row and
+// tile loops and what tells a row its run of pieces; what the entry points share on the host is in map_plan.hpp.
 #pragma once
 
 #include "materialize_device.hpp"
@@ -103,6 +105,28 @@ __device__ __forceinline__ uint64_t map_field_bytes(const ColsArg& cols, const C
         return sn;
     }
     return l;
+}
+
+// The length pass of one piece: the bytes piece p adds to output row i besides its literal (digit counts by compares, spans
+// from offsets alone).  PK == kPiecesFloat: *refused, preset to UINT64_MAX, takes the lowest row with a value the FLOAT64 or
+// TIME formatter refuses.
+template <int NC, int PK>
+__device__ __forceinline__ uint64_t map_piece_bytes(const ColsArg& cols, const ColIds& ids, const MapPiece& p, const RecordFields<NC>& f, uint64_t i,
+                                                    uint64_t* refused) {
+    uint64_t bytes = 0;
+    if (p.kind == CPH_MAP_INT64) {
+        bytes = int_chars(p.ints[i]);
+    } else if (PK == kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
+        const FixedParts r = fixed_split(p.floats[i], p.col);
+        bytes = fixed_chars(r, p.col);
+        if (r.kind == FIXED_RANGE) atomicMin(reinterpret_cast<unsigned long long*>(refused), (unsigned long long)i);
+    } else if (PK == kPiecesFloat && p.kind == CPH_MAP_TIME) {   // the length needs no look at the value; the refusal does
+        bytes = rfc3339_chars(p.col);
+        if (!rfc3339_in_range(p.ints[i], p.col)) atomicMin(reinterpret_cast<unsigned long long*>(refused), (unsigned long long)i);
+    } else if (p.kind == CPH_MAP_COLUMN || (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE)) {
+        bytes = map_field_bytes<NC, PK>(cols, ids, p, f, i);
+    }
+    return bytes;
 }
 
 // pieces [k0, k1) of `pieces` for output row i, in order, into the sink; literals lie in `lits` (k0 and k1 may differ from lane

@@ -12,12 +12,14 @@
 // may take different alternatives: every lane walks its own run [first[a], first[a + 1]) of the one flat piece array, so the
 // k-th pieces of two alternatives run together where they are of one kind and one after the other where they are not; the
 // stage sink ORs words into LDS, so no lane depends on another's progress and rows are not sorted by alternative.
-// A plan with a FLOAT64 or TIME piece runs float instantiations of both kernels, as map_format.hip does, and one with a SLICE piece
-// but no FLOAT64 piece the slice instantiations (k_switch_lens_sl / k_switch_copy_sl).
+// The kernels come in map_format.hip's three piece sets, chosen over the pieces of all alternatives together.
+// Where things live: this file has what Switch adds to map_format.hip — the bitmaps, the byte per row, the plan with one run
+// of pieces per alternative, and the alternative in the messages.  What a row does in either pass is map_device.hpp's; the
+// piece rules, the plan's pieces and literals, the scan with the refused-row report, the result column and the launch by
+// piece set are map_plan.hpp's.
 #include <new>
-#include <string>
 
-#include "map_device.hpp"
+#include "map_plan.hpp"
 
 namespace cph {
 
@@ -50,21 +52,7 @@ __global__ __launch_bounds__(kMatThreads) void k_switch_lens(ColsArg cols, ColId
         if constexpr (NC > 0) f.load(cols, ids, i, 0);   // offsets only
         // the lane's own run of pieces: the k-th pieces of two alternatives that are of one kind run together
         uint64_t total = plan.fixed[a];
-        for (int k = plan.first[a]; k < plan.first[a + 1]; k++) {
-            const MapPiece& p = plan.p[k];
-            if (p.kind == CPH_MAP_INT64) {
-                total += int_chars(p.ints[i]);
-            } else if (PK == kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
-                const FixedParts r = fixed_split(p.floats[i], p.col);
-                total += fixed_chars(r, p.col);
-                if (r.kind == FIXED_RANGE) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
-            } else if (PK == kPiecesFloat && p.kind == CPH_MAP_TIME) {   // the length needs no look at the value; the refusal does
-                total += rfc3339_chars(p.col);
-                if (!rfc3339_in_range(p.ints[i], p.col)) atomicMin(reinterpret_cast<unsigned long long*>(lens + n + 1), (unsigned long long)i);
-            } else if (p.kind == CPH_MAP_COLUMN || (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE)) {
-                total += map_field_bytes<NC, PK>(cols, ids, p, f, i);
-            }
-        }
+        for (int k = plan.first[a]; k < plan.first[a + 1]; k++) total += map_piece_bytes<NC, PK>(cols, ids, plan.p[k], f, i, lens + n + 1);
         lens[i] = total;
     }
 }
@@ -128,57 +116,6 @@ constexpr auto k_switch_copy_sl = k_switch_copy<NC, kPiecesSlice>;
 
 using namespace cph;
 
-namespace {
-
-std::string alt_name(int a, int ncases) { return a < ncases ? "case " + std::to_string(a) : std::string("otherwise"); }
-
-// the rules of cph_map_format for the pieces of one alternative
-Status check_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t ncols, uint64_t n, const std::string& who, uint64_t* lit_bytes,
-                    bool* has_float, bool* has_slice) {
-    for (int k = 0; k < npieces; k++) {
-        const cph_map_piece& p = pieces[k];
-        const std::string at = "cph_map_switch: " + who + ", piece " + std::to_string(k) + ": ";
-        switch (p.kind) {
-            case CPH_MAP_LITERAL:
-                if (!p.value.data && p.value.len) return {CPH_ERR_INVALID, at + "a literal with bytes but no data pointer"};
-                *lit_bytes += p.value.len;
-                if (p.value.len > 0xFFFFFFFFull || *lit_bytes > 0xFFFFFFFFull) return {CPH_ERR_INVALID, at + "literals beyond 4 GiB"};
-                break;
-            case CPH_MAP_COLUMN:
-                if (p.arg < 0 || p.arg >= ncols) return {CPH_ERR_INVALID, at + "a COLUMN piece outside 0..ncols-1"};
-                break;
-            case CPH_MAP_INT64:
-                if (p.arg != CPH_MEM_HOST && p.arg != CPH_MEM_DEVICE) return {CPH_ERR_INVALID, at + "bad memory space of an INT64 piece"};
-                if (!p.ints && n) return {CPH_ERR_INVALID, at + "an INT64 piece without values"};
-                break;
-            case CPH_MAP_FLOAT64:
-                if (p.arg != CPH_MEM_HOST && p.arg != CPH_MEM_DEVICE) return {CPH_ERR_INVALID, at + "bad memory space of a FLOAT64 piece"};
-                if (!p.floats && n) return {CPH_ERR_INVALID, at + "a FLOAT64 piece without values"};
-                if (p.prec < 0 || p.prec > kFixedMaxPrec) return {CPH_ERR_INVALID, at + "prec of a FLOAT64 piece outside 0..22"};
-                *has_float = true;
-                break;
-            case CPH_MAP_TIME:
-                if (p.arg != CPH_MEM_HOST && p.arg != CPH_MEM_DEVICE) return {CPH_ERR_INVALID, at + "bad memory space of a TIME piece"};
-                if (!p.ints && n) return {CPH_ERR_INVALID, at + "a TIME piece without values"};
-                if (p.prec < -kTimeMaxZone || p.prec > kTimeMaxZone)
-                    return {CPH_ERR_INVALID, at + "prec of a TIME piece (the zone in minutes east of UTC) outside -1439..1439"};
-                *has_float = true;   // the instantiations that report a refused value
-                break;
-            case CPH_MAP_SLICE:
-                if (p.arg < 0 || p.arg >= ncols) return {CPH_ERR_INVALID, at + "a SLICE piece's column outside 0..ncols-1"};
-                if (!p.value.data || p.value.len != sizeof(cph_map_slice))
-                    return {CPH_ERR_INVALID, at + "a SLICE piece's value is exactly 16 bytes (a cph_map_slice) behind a non-NULL pointer"};
-                *has_slice = true;
-                break;
-            default:
-                return {CPH_ERR_INVALID, at + "unknown piece kind (1..4, 8, 10)"};
-        }
-    }
-    return {};
-}
-
-}  // namespace
-
 extern "C" {
 
 CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
@@ -207,6 +144,10 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         return fail_with(ctx, {CPH_ERR_INVALID, "cph_map_switch: " + std::to_string(total_pieces) + " pieces in all alternatives together, more than 32"});
     const uint64_t n = nrows;
     if (n > 0xFFFFFFFFull) return fail_with(ctx, {CPH_ERR_TOO_MANY_ROWS, "cph_map_switch: more than 2^32-1 rows in one call"});
+    // alternative a: its pieces, and its name in front of a message
+    auto alt_pieces = [&](int a) { return a < ncases ? cases[a].pieces : otherwise; };
+    auto alt_npieces = [&](int a) { return a < ncases ? cases[a].npieces : notherwise; };
+    auto alt_name = [&](int a) { return "cph_map_switch: " + (a < ncases ? "case " + std::to_string(a) : std::string("otherwise")) + ", "; };
     uint64_t lit_bytes = 0;
     bool has_float = false, has_slice = false;
     for (int a = 0; a <= ncases; a++) {
@@ -214,8 +155,8 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
             Status s = check_pred_program(cases[a].prog, cases[a].nops, ncols);
             if (!s.ok()) return fail_with(ctx, {s.code, "cph_map_switch: case " + std::to_string(a) + ": " + s.msg});
         }
-        Status s = check_pieces(a < ncases ? cases[a].pieces : otherwise, a < ncases ? cases[a].npieces : notherwise, ncols, n,
-                                alt_name(a, ncases), &lit_bytes, &has_float, &has_slice);
+        Status s = check_map_pieces(alt_pieces(a), alt_npieces(a), ncols, n, [&](int k) { return alt_name(a) + "piece " + std::to_string(k) + ": "; },
+                                    &lit_bytes, &has_float, &has_slice);
         if (!s.ok()) return fail_with(ctx, s);
     }
     {
@@ -226,18 +167,7 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
     if (!r) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
     r->own.ctx = ctx;
     auto run = [&]() -> Status {
-        r->pub.col.offset_bits = 64;
-        r->pub.col.mem = out_mem;
-        r->pub.col.fixed_width = 0;
-        if (n == 0) {
-            CPH_TRY(r->d_offs.alloc(&ctx->pool, sizeof(uint64_t)));
-            CPH_HIP_TRY(hipMemsetAsync(r->d_offs.get(), 0, sizeof(uint64_t), ctx->stream));
-            CPH_TRY(r->d_data.alloc(&ctx->pool, 16));
-            r->pub.nbytes = 0;
-            r->pub.col.nrows = 0;
-            const ResultPart parts[2] = {{&r->d_offs, sizeof(uint64_t), &r->pub.col.offsets}, {&r->d_data, 0, &r->pub.col.data}};
-            return deliver(ctx, &r->own, parts, 2, out_mem);
-        }
+        if (n == 0) return deliver_map_column(ctx, r, 0, 0, out_mem);
         std::vector<DevBuf> staged;
         ColsArg arg{};
         ColIds ids{};
@@ -252,72 +182,14 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
             plan.bits[c] = maps[c].bitmap.as<uint64_t>();
         }
         // the alternatives' pieces in one flat array, their literals in one block
-        std::string lits;
-        double in_bytes = 0;   // what the copy pass reads per row besides the value bytes and the alternative
-        uint32_t slice_cols = 0;
-        int np = 0;
+        MapPlanBuild build;
         for (int a = 0; a <= ncases; a++) {
-            const cph_map_piece* pieces = a < ncases ? cases[a].pieces : otherwise;
-            const int npieces = a < ncases ? cases[a].npieces : notherwise;
-            plan.first[a] = np;
-            const size_t lit0 = lits.size();
-            for (int k = 0; k < npieces; k++) {
-                const cph_map_piece& p = pieces[k];
-                MapPiece& d = plan.p[np++];
-                d.kind = p.kind;
-                if (p.kind == CPH_MAP_LITERAL) {
-                    d.off = (uint32_t)lits.size();
-                    d.len = (uint32_t)p.value.len;
-                    if (d.len) lits.append(reinterpret_cast<const char*>(p.value.data), d.len);
-                } else if (p.kind == CPH_MAP_COLUMN) {
-                    d.col = p.arg;
-                    if (!((plan.col_mask >> p.arg) & 1u)) {
-                        in_bytes += arg.c[p.arg].fixed_width ? 0.0 : (double)(arg.c[p.arg].offset_bits / 8);
-                        if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
-                    }
-                    plan.col_mask |= 1u << p.arg;
-                } else if (p.kind == CPH_MAP_SLICE) {   // not in col_mask: a slice loads its own first chunk
-                    cph_map_slice sl;
-                    memcpy(&sl, p.value.data, sizeof sl);
-                    d.col = p.arg;
-                    d.from = sl.from;
-                    d.to = sl.to;
-                    if (!((slice_cols >> p.arg) & 1u) && !((plan.col_mask >> p.arg) & 1u)) {
-                        in_bytes += arg.c[p.arg].fixed_width ? 0.0 : (double)(arg.c[p.arg].offset_bits / 8);
-                        if (ids.ids[p.arg].ptr) in_bytes += (double)(ids.ids[p.arg].bits / 8);
-                    }
-                    slice_cols |= 1u << p.arg;
-                } else {   // INT64 / FLOAT64 / TIME: 8 bytes per row
-                    const void* vals = p.kind == CPH_MAP_FLOAT64 ? static_cast<const void*>(p.floats) : static_cast<const void*>(p.ints);
-                    in_bytes += 8.0;
-                    if (p.arg == CPH_MEM_HOST) {   // staged like the row ids of a host column
-                        staged.emplace_back();
-                        CPH_TRY(staged.back().alloc(&ctx->pool, n * sizeof(int64_t)));
-                        CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), vals, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-                        vals = staged.back().get();
-                    }
-                    if (p.kind == CPH_MAP_INT64) {
-                        d.ints = static_cast<const int64_t*>(vals);
-                    } else if (p.kind == CPH_MAP_TIME) {
-                        d.ints = static_cast<const int64_t*>(vals);
-                        d.col = p.prec;
-                    } else {
-                        d.floats = static_cast<const double*>(vals);
-                        d.col = p.prec;
-                    }
-                }
-            }
-            plan.fixed[a] = lits.size() - lit0;
+            CPH_TRY(append_map_pieces(ctx, alt_pieces(a), alt_npieces(a), n, arg, ids, &build, plan.p + plan.first[a], &staged, &plan.fixed[a]));
+            plan.first[a + 1] = plan.first[a] + alt_npieces(a);
         }
-        plan.first[ncases + 1] = np;
+        plan.col_mask = build.col_mask;
         DevBuf litbuf;
-        CPH_TRY(litbuf.alloc(&ctx->pool, lits.size() + 16));
-        if (!lits.empty()) {
-            void* slot = nullptr;
-            CPH_TRY(pinned_upload(ctx, lits.size(), &slot));
-            memcpy(slot, lits.data(), lits.size());
-            CPH_HIP_TRY(hipMemcpyAsync(litbuf.get(), slot, lits.size(), hipMemcpyHostToDevice, ctx->stream));
-        }
+        CPH_TRY(upload_map_literals(ctx, build.lits, &litbuf));
         plan.lits = litbuf.as<uint8_t>();
         DevBuf whichbuf;
         CPH_TRY(whichbuf.alloc(&ctx->pool, n));
@@ -325,76 +197,26 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         CPH_TRY(r->d_offs.alloc(&ctx->pool, (n + (has_float ? 2 : 1)) * sizeof(uint64_t)));   // a float plan: + the refused row
         uint64_t* offs = r->d_offs.as<uint64_t>();
         if (has_float) CPH_HIP_TRY(hipMemsetAsync(offs + n + 1, 0xFF, sizeof(uint64_t), ctx->stream));
-        {
-            ProfScope ps(ctx, has_slice && !has_float ? "k_switch_lens_sl" : "k_switch_lens", (8.0 + 1.0 + (double)ncases / 8.0 + in_bytes) * (double)n);
-            if (has_float) {
-                CPH_CSV_DISPATCH(k_switch_lens_f64, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, which_dev, offs);
-            } else if (has_slice) {
-                CPH_CSV_DISPATCH(k_switch_lens_sl, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, which_dev, offs);
-            } else {
-                CPH_CSV_DISPATCH(k_switch_lens, ncols, dim3(grid_rows(n)), 0, ctx->stream, arg, ids, plan, n, which_dev, offs);
-            }
-        }
-        CPH_HIP_TRY(hipGetLastError());
+        const int pk = pieces_set(has_float, has_slice);
+        // besides the value bytes, both passes read or write the alternative's byte
+        CPH_MAP_DISPATCH(ctx, k_switch_lens, pk, (8.0 + 1.0 + (double)ncases / 8.0 + build.in_bytes) * (double)n, ncols, n, 0, arg, ids, plan, n, which_dev,
+                         offs);
         uint64_t total = 0;
-        if (has_float) {   // the total and the refused row in one copy: the call's one host wait
-            CPH_TRY(exclusive_scan_u64(ctx, offs, n, offs + n));
-            struct { uint64_t total, bad; } tail;
-            CPH_TRY(read_device_value(ctx, reinterpret_cast<const decltype(tail)*>(offs + n), &tail));
-            if (tail.bad != UINT64_MAX) {
-                uint8_t a = 0;
-                CPH_HIP_TRY(hipMemcpy(&a, which_dev + tail.bad, 1, hipMemcpyDeviceToHost));
-                const cph_map_piece* pieces = a < ncases ? cases[a].pieces : otherwise;
-                const int npieces = a < ncases ? cases[a].npieces : notherwise;
-                int piece = 0;   // the first FLOAT64 or TIME piece of that row's alternative with such a value
-                for (int k = 0; k < npieces; k++) {
-                    if (pieces[k].kind == CPH_MAP_TIME) {
-                        int64_t t = 0;
-                        if (pieces[k].arg == CPH_MEM_HOST) t = pieces[k].ints[tail.bad];
-                        else CPH_HIP_TRY(hipMemcpy(&t, pieces[k].ints + tail.bad, sizeof t, hipMemcpyDeviceToHost));
-                        if (!rfc3339_in_range(t, pieces[k].prec))
-                            return Status{CPH_ERR_INVALID, "cph_map_switch: " + alt_name(a, ncases) + ", TIME piece " + std::to_string(k) + ", row " +
-                                                               std::to_string(tail.bad) + ": the local year of " + std::to_string(t) + " is outside 0000..9999"};
-                        continue;
-                    }
-                    if (pieces[k].kind != CPH_MAP_FLOAT64) continue;
-                    double v = 0;
-                    if (pieces[k].arg == CPH_MEM_HOST) v = pieces[k].floats[tail.bad];
-                    else CPH_HIP_TRY(hipMemcpy(&v, pieces[k].floats + tail.bad, sizeof v, hipMemcpyDeviceToHost));
-                    if (fixed_split(v, 0).kind == FIXED_RANGE) {
-                        piece = k;
-                        break;
-                    }
-                }
-                return Status{CPH_ERR_INVALID, "cph_map_switch: " + alt_name(a, ncases) + ", FLOAT64 piece " + std::to_string(piece) + ", row " +
-                                                   std::to_string(tail.bad) + ": a finite value of 2^128 or more is not formatted"};
-            }
-            total = tail.total;
-        } else {
-            CPH_TRY(scan_lengths(ctx, offs, n, &total));
-        }
+        CPH_TRY(scan_with_refusal(ctx, offs, n, has_float,
+                                  [&](uint64_t row, const cph_map_piece** ps, int32_t* nps, std::string* prefix) -> Status {
+                                      uint8_t a = 0;   // the refused row's own alternative
+                                      CPH_HIP_TRY(hipMemcpy(&a, which_dev + row, 1, hipMemcpyDeviceToHost));
+                                      *ps = alt_pieces(a), *nps = alt_npieces(a), *prefix = alt_name(a);
+                                      return {};
+                                  },
+                                  &total));
         CPH_TRY(r->d_data.alloc(&ctx->pool, total + 16));
         if (total) {
-            ProfScope ps(ctx, has_slice && !has_float ? "k_switch_copy_sl" : "k_switch_copy", 2.0 * (double)total + (8.0 + 1.0 + in_bytes) * (double)n);
-            if (has_float) {
-                CPH_CSV_DISPATCH(k_switch_copy_f64, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, which_dev, offs,
-                                 r->d_data.as<uint8_t>());
-            } else if (has_slice) {
-                CPH_CSV_DISPATCH(k_switch_copy_sl, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, which_dev, offs,
-                                 r->d_data.as<uint8_t>());
-            } else {
-                CPH_CSV_DISPATCH(k_switch_copy, ncols, dim3(grid_rows(n)), kMatStage, ctx->stream, arg, ids, plan, n, which_dev, offs,
-                                 r->d_data.as<uint8_t>());
-            }
-            CPH_HIP_TRY(hipGetLastError());
+            CPH_MAP_DISPATCH(ctx, k_switch_copy, pk, 2.0 * (double)total + (8.0 + 1.0 + build.in_bytes) * (double)n, ncols, n, kMatStage, arg, ids, plan, n,
+                             which_dev, offs, r->d_data.as<uint8_t>());
         }
         if (which) CPH_HIP_TRY(hipMemcpyAsync(which, which_dev, n, hipMemcpyDeviceToHost, ctx->stream));
-        // the kernels read the bitmaps, the literal block and the staged arrays: they go back to the pool behind deliver's wait
-        r->pub.nbytes = total;
-        r->pub.col.nrows = n;
-        const ResultPart parts[2] = {{&r->d_offs, (size_t)(n + 1) * sizeof(uint64_t), &r->pub.col.offsets},
-                                     {&r->d_data, (size_t)total, &r->pub.col.data}};
-        return deliver(ctx, &r->own, parts, 2, out_mem);
+        return deliver_map_column(ctx, r, n, total, out_mem);   // the bitmaps go back to the pool behind its wait, too
     };
     return finish_call(ctx, r, run(), out);
 }

@@ -1957,6 +1957,45 @@ private:
         return n;
     }
 
+    // What mapBatch and switchBatch hand to the device for one template part.  A number part (an expression, or a Fixed
+    // column) shows the converted values `num`; a Col or Substr part reads staged column `col`; a literal needs neither.
+    static cph_map_piece partPiece(const Part& p, const cph_numcol* num, size_t col) {
+        if (p.expr && p.prec < 0)
+            return cph_map_piece{p.is_time ? CPH_MAP_TIME : CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0}, static_cast<const int64_t*>(num->values), nullptr,
+                                 p.is_time ? p.zone : 0, 0};
+        if (p.expr || p.prec >= 0) return cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr, static_cast<const double*>(num->values), p.prec, 0};
+        if (!p.is_col) return cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr};
+        if (p.is_slice) return cph_map_piece{CPH_MAP_SLICE, (int32_t)col, {reinterpret_cast<const uint8_t*>(&p.slice), sizeof p.slice}, nullptr};
+        return cph_map_piece{CPH_MAP_COLUMN, (int32_t)col, {nullptr, 0}, nullptr};
+    }
+    // the columns a number part converts
+    static std::vector<const Col*> numberColumns(const Part& p) {
+        std::vector<const Col*> cols;
+        if (!p.expr) cols.push_back(&p.col);
+        else
+            for (const Col& c : p.expr->cols) cols.push_back(&c);
+        return cols;
+    }
+    // vals[c][i] = the value of column cols[c] in row i of the batch (rows 0 .. n-1), its default where the row lacks the column
+    static std::vector<std::vector<const std::string*>> columnValues(const std::vector<Row>& batch, size_t n, const std::vector<const Col*>& cols) {
+        std::vector<std::vector<const std::string*>> vals(cols.size());
+        for (size_t c = 0; c < cols.size(); c++) {
+            vals[c].resize(n);
+            for (size_t i = 0; i < n; i++) {
+                auto it = batch[i].find(cols[c]->name);
+                vals[c][i] = it == batch[i].end() ? &cols[c]->fallback : &it->second;
+            }
+        }
+        return vals;
+    }
+    // the index of a template's column in `cols`, appended where it is new (the first mention's default counts)
+    static size_t columnIndex(std::vector<const Col*>* cols, const Col& col) {
+        size_t c = 0;
+        while (c < cols->size() && (*cols)[c]->name != col.name) c++;
+        if (c == cols->size()) cols->push_back(&col);
+        return c;
+    }
+
     // One assignment over a batch: row[a.name] = the template's value, for every row, by one cph_map_format call.  A row that
     // lacks a column gets the Col's default in its place (the caller has turned away rows that lack a column without one).
     // A Fixed part's column goes through cph_col_to_number first (ColumnAsFloat64's path) and into a FLOAT64 piece.  Where
@@ -1967,8 +2006,7 @@ private:
         *good = 0;
         if (n == 0) return Error();
         if (!a.cases.empty()) return switchBatch(ctx, a, batch, good);
-        std::vector<std::string> columns;
-        std::vector<const std::string*> fallback;
+        std::vector<const Col*> columns;
         std::vector<cph_map_piece> pieces;
         struct NumCols {   // the converted columns live until the template has run
             std::vector<cph_numcol*> v;
@@ -1978,16 +2016,10 @@ private:
         } nums;
         Error pending;
         for (const Part& p : a.value.parts) {
+            if (!p.expr && p.prec < 0) continue;
+            const std::vector<std::vector<const std::string*>> vals = columnValues(*batch, n, numberColumns(p));
             if (p.expr) {   // an expression's value: ONE cph_num_eval call over its columns, then an INT64 / FLOAT64 piece
                 const Expr& e = *p.expr;
-                std::vector<std::vector<const std::string*>> vals(e.cols.size());
-                for (size_t c = 0; c < e.cols.size(); c++) {
-                    vals[c].resize(n);
-                    for (size_t i = 0; i < n; i++) {
-                        auto it = (*batch)[i].find(e.cols[c].name);
-                        vals[c][i] = it == (*batch)[i].end() ? &e.cols[c].fallback : &it->second;
-                    }
-                }
                 cph_numcol* nc = nullptr;
                 int32_t op = -1;
                 if (detail::evalStaged(ctx, e, vals, n, &nc, &op) != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
@@ -1999,13 +2031,6 @@ private:
                     if (n == 0) return pending;
                 }
                 continue;
-            }
-            if (p.prec < 0) continue;
-            std::vector<std::vector<const std::string*>> vals(1);
-            vals[0].resize(n);
-            for (size_t i = 0; i < n; i++) {
-                auto it = (*batch)[i].find(p.col.name);
-                vals[0][i] = it == (*batch)[i].end() ? &p.col.fallback : &it->second;
             }
             cph_numcol* nc = nullptr;
             int32_t rc;
@@ -2025,44 +2050,11 @@ private:
         }
         size_t fixed_seen = 0;
         for (const Part& p : a.value.parts) {
-            if (p.expr && p.prec < 0) {
-                pieces.push_back(cph_map_piece{p.is_time ? CPH_MAP_TIME : CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0},
-                                               static_cast<const int64_t*>(nums.v[fixed_seen++]->values), nullptr, p.is_time ? p.zone : 0, 0});
-                continue;
-            }
-            if (p.expr) {
-                pieces.push_back(cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr,
-                                               static_cast<const double*>(nums.v[fixed_seen++]->values), p.prec, 0});
-                continue;
-            }
-            if (!p.is_col) {
-                pieces.push_back(cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr});
-                continue;
-            }
-            if (p.prec >= 0) {
-                pieces.push_back(cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr,
-                                               static_cast<const double*>(nums.v[fixed_seen++]->values), p.prec, 0});
-                continue;
-            }
-            size_t c = (size_t)(std::find(columns.begin(), columns.end(), p.col.name) - columns.begin());
-            if (c == columns.size()) {
-                columns.push_back(p.col.name);
-                fallback.push_back(&p.col.fallback);
-            }
-            if (p.is_slice)
-                pieces.push_back(cph_map_piece{CPH_MAP_SLICE, (int32_t)c, {reinterpret_cast<const uint8_t*>(&p.slice), sizeof p.slice}, nullptr});
-            else
-                pieces.push_back(cph_map_piece{CPH_MAP_COLUMN, (int32_t)c, {nullptr, 0}, nullptr});
+            if (p.expr || p.prec >= 0) pieces.push_back(partPiece(p, nums.v[fixed_seen++], 0));
+            else pieces.push_back(partPiece(p, nullptr, p.is_col ? columnIndex(&columns, p.col) : 0));
         }
         const size_t nc = columns.size();
-        std::vector<std::vector<const std::string*>> vals(nc);
-        for (size_t c = 0; c < nc; c++) {
-            vals[c].resize(n);
-            for (size_t i = 0; i < n; i++) {
-                auto it = (*batch)[i].find(columns[c]);
-                vals[c][i] = it == (*batch)[i].end() ? fallback[c] : &it->second;
-            }
-        }
+        const std::vector<std::vector<const std::string*>> vals = columnValues(*batch, n, columns);
         cph_colbuf* cb = nullptr;
         int32_t rc;
         {
@@ -2093,9 +2085,7 @@ private:
         }
         op_first[ncases] = prog.ops.size();
         const size_t npred = prog.columns.size();
-        std::vector<std::string> columns = prog.columns;
-        std::vector<const std::string*> fallback;
-        for (size_t c = 0; c < npred; c++) fallback.push_back(&prog.absent[c]);
+        std::vector<const Col*> columns;   // the templates' columns, staged behind the predicates'
         struct NumPart {   // a Fixed / Itoa part's values over the batch
             size_t alt;
             const Part* part;
@@ -2111,59 +2101,31 @@ private:
         std::vector<std::vector<cph_map_piece>> pieces(ncases + 1);
         for (size_t alt = 0; alt <= ncases; alt++) {
             for (const Part& p : (alt < ncases ? a.cases[alt].then : a.value).parts) {
-                if (p.expr || p.prec >= 0) {
-                    NumPart np{alt, &p, nullptr, {}};
-                    const size_t nc = p.expr ? p.expr->cols.size() : 1;
-                    np.vals.resize(nc);
-                    for (size_t c = 0; c < nc; c++) {
-                        const Col& col = p.expr ? p.expr->cols[c] : p.col;
-                        np.vals[c].resize(n);
-                        for (size_t i = 0; i < n; i++) {
-                            auto it = (*batch)[i].find(col.name);
-                            np.vals[c][i] = it == (*batch)[i].end() ? &col.fallback : &it->second;
-                        }
-                    }
-                    int32_t rc, op = -1;
-                    if (p.expr) {
-                        rc = detail::evalStaged(ctx, *p.expr, np.vals, n, &np.nc, &op);
-                    } else {
-                        detail::StagedColumns st(ctx, 1);
-                        st.stage(np.vals, n);
-                        rc = cph_col_to_number(ctx, st.cols(), nullptr, n, CPH_NUM_FLOAT64, CPH_MEM_HOST, &np.nc);
-                    }
-                    if (rc != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
-                    if (p.expr && p.prec < 0)
-                        pieces[alt].push_back(cph_map_piece{p.is_time ? CPH_MAP_TIME : CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0},
-                                                            static_cast<const int64_t*>(np.nc->values), nullptr, p.is_time ? p.zone : 0, 0});
-                    else
-                        pieces[alt].push_back(cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr, static_cast<const double*>(np.nc->values), p.prec, 0});
-                    nums.v.push_back(std::move(np));
+                if (!p.expr && p.prec < 0) {
+                    pieces[alt].push_back(partPiece(p, nullptr, p.is_col ? npred + columnIndex(&columns, p.col) : 0));
                     continue;
                 }
-                if (!p.is_col) {
-                    pieces[alt].push_back(cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr});
-                    continue;
+                NumPart np{alt, &p, nullptr, columnValues(*batch, n, numberColumns(p))};
+                int32_t rc, op = -1;
+                if (p.expr) {
+                    rc = detail::evalStaged(ctx, *p.expr, np.vals, n, &np.nc, &op);
+                } else {
+                    detail::StagedColumns st(ctx, 1);
+                    st.stage(np.vals, n);
+                    rc = cph_col_to_number(ctx, st.cols(), nullptr, n, CPH_NUM_FLOAT64, CPH_MEM_HOST, &np.nc);
                 }
-                size_t c = (size_t)(std::find(columns.begin() + (std::ptrdiff_t)npred, columns.end(), p.col.name) - columns.begin());
-                if (c == columns.size()) {
-                    columns.push_back(p.col.name);
-                    fallback.push_back(&p.col.fallback);
-                }
-                if (p.is_slice)
-                    pieces[alt].push_back(cph_map_piece{CPH_MAP_SLICE, (int32_t)c, {reinterpret_cast<const uint8_t*>(&p.slice), sizeof p.slice}, nullptr});
-                else
-                    pieces[alt].push_back(cph_map_piece{CPH_MAP_COLUMN, (int32_t)c, {nullptr, 0}, nullptr});
+                if (rc != CPH_OK) return Error(std::string("csvplus_hip: ") + cph_last_error(ctx));
+                pieces[alt].push_back(partPiece(p, np.nc, 0));
+                nums.v.push_back(std::move(np));
             }
         }
-        const size_t nc = columns.size();
-        std::vector<std::vector<const std::string*>> vals(nc);
-        for (size_t c = 0; c < nc; c++) {
+        const size_t nc = npred + columns.size();
+        std::vector<std::vector<const std::string*>> vals(npred);
+        for (size_t c = 0; c < npred; c++) {
             vals[c].resize(n);
-            for (size_t i = 0; i < n; i++) {
-                auto it = (*batch)[i].find(columns[c]);
-                vals[c][i] = c < npred ? prog.value(c, (*batch)[i]) : it == (*batch)[i].end() ? fallback[c] : &it->second;
-            }
+            for (size_t i = 0; i < n; i++) vals[c][i] = prog.value(c, (*batch)[i]);
         }
+        for (auto& v : columnValues(*batch, n, columns)) vals.push_back(std::move(v));
         std::vector<cph_map_case> cases(ncases);
         for (size_t c = 0; c < ncases; c++)
             cases[c] = cph_map_case{prog.ops.data() + op_first[c], (int32_t)(op_first[c + 1] - op_first[c]), pieces[c].data(), (int32_t)pieces[c].size()};
