@@ -13,7 +13,7 @@ LIBDIR  = csvplus_amd/lib
 CSRC    = csvplus_amd/csrc
 HIP_SRCS = $(CSRC)/capi.hip $(CSRC)/index_build.hip $(CSRC)/keycodec.hip $(CSRC)/radix_sort.hip $(CSRC)/probe.hip $(CSRC)/chain.hip $(CSRC)/stream_join.hip $(CSRC)/materialize.hip $(CSRC)/json_write.hip $(CSRC)/map_format.hip $(CSRC)/map_switch.hip $(CSRC)/filter.hip $(CSRC)/numparse.hip $(CSRC)/expr_eval.hip $(CSRC)/csv_ingest.hip $(CSRC)/index_ops.hip $(CSRC)/resolve.hip $(CSRC)/aggregate.hip $(CSRC)/join_totals.hip $(CSRC)/order.hip $(CSRC)/dist.hip $(CSRC)/calibrate.hip $(CSRC)/small_build.hip $(CSRC)/host_encode.hip $(CSRC)/window_sort.hip $(CSRC)/counted_sort.hip
 HIP_OBJS = $(patsubst $(CSRC)/%.hip,$(LIBDIR)/obj/%.o,$(HIP_SRCS))
-HIP_HDRS = $(CSRC)/cph_internal.hpp $(CSRC)/device_utils.hpp $(CSRC)/codec_device.hpp $(CSRC)/probe_device.hpp $(CSRC)/hash_device.hpp $(CSRC)/lds_stage.hpp $(CSRC)/materialize_device.hpp $(CSRC)/map_device.hpp $(CSRC)/map_plan.hpp $(CSRC)/numparse_device.hpp $(CSRC)/floatparse_device.hpp $(CSRC)/pow5_table.inc $(CSRC)/numformat_device.hpp $(CSRC)/strpred_device.hpp $(CSRC)/timeparse_device.hpp $(CSRC)/runs_device.hpp $(CSRC)/order_device.hpp $(CSRC)/csv_lazy_device.hpp $(CSRC)/host_encode_kernels.hpp include/csvplus_hip.h
+HIP_HDRS = $(CSRC)/cph_internal.hpp $(CSRC)/device_utils.hpp $(CSRC)/codec_device.hpp $(CSRC)/probe_device.hpp $(CSRC)/hash_device.hpp $(CSRC)/lds_stage.hpp $(CSRC)/materialize_device.hpp $(CSRC)/map_device.hpp $(CSRC)/map_plan.hpp $(CSRC)/numparse_device.hpp $(CSRC)/floatparse_device.hpp $(CSRC)/pow5_table.inc $(CSRC)/numformat_device.hpp $(CSRC)/strpred_device.hpp $(CSRC)/timeparse_device.hpp $(CSRC)/runs_device.hpp $(CSRC)/tile_bitmap.hpp $(CSRC)/order_device.hpp $(CSRC)/csv_lazy_device.hpp $(CSRC)/host_encode_kernels.hpp include/csvplus_hip.h
 
 all: hip datagen oracle host
 

@@ -3,9 +3,9 @@
 // are adjacent in the sorted codes, input order inside a run), so the reduction is segmented, not hashed:
 //
 //   k_agg_heads    one pass over the sorted codes, kResRows CONSECUTIVE rows per lane (equal_flags, runs_device.hpp): the bitmap
-//                  of RUN STARTS (a run of one row is a group here) and the starts per tile.
-//   exclusive scan of the tile counts (radix_sort.hip): offs[tile] = groups in front of the tile, offs[ntiles] = ngroups.
-//   k_agg_emit     bitmap word -> rank by popcount + mbcnt -> first_position[rank], first_row[rank] = perm[position].
+//                  of RUN STARTS (a run of one row is a group here) and the starts per tile, in the layout of tile_bitmap.hpp.
+//   exclusive scan of the tile counts (TileBitmap::scan): offs[tile] = groups in front of the tile, offs[ntiles] = ngroups.
+//   k_agg_emit     the rank walker of tile_bitmap.hpp: first_position[rank], first_row[rank] = perm[position].
 //   k_agg_counts   count[g] = first_position[g + 1] - first_position[g] (n for the last group): no reduction needed.
 //   per spec:
 //   convert_rows   (col specs, numparse.hip) the column read through perm: values in SORTED order, read coalesced below.
@@ -65,30 +65,20 @@ __device__ __forceinline__ AggSeg agg_seg_join(const AggSeg left, const AggSeg r
     return r;
 }
 
-// bitmap[tile * 32 + w] bit b = a run starts at sorted position tile * 2048 + 64 w + b (rows >= n: 0); counts[tile] = its set bits.
-// n >= 1.
+// bit = a run starts at that sorted position (tile_bitmap.hpp).  n >= 1.
 template <bool KEY32>
 __global__ __launch_bounds__(kMatThreads) void k_agg_heads(const void* __restrict__ codes, uint64_t n, int nwords, uint64_t* __restrict__ bitmap,
                                                           uint32_t* __restrict__ counts) {
     __shared__ uint64_t s_word[kResWords];
     uint8_t* s_byte = reinterpret_cast<uint8_t*>(s_word);   // kResRows == 8: one byte per lane
-    const int lane = lane_id(), wave = wave_id();
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    const uint64_t ntiles = tile_count(n);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kResTile;
         const uint64_t tend = t0 + kResTile < n ? t0 + kResTile : n;
         const uint64_t base = t0 + (uint64_t)threadIdx.x * kResRows;
         const uint32_t e = base < n ? equal_flags<KEY32>(codes, n, nwords, base) : 0u;
-        const uint32_t live = base >= tend ? 0u : (tend - base >= (uint64_t)kResRows ? (1u << kResRows) - 1 : (1u << (uint32_t)(tend - base)) - 1);
-        s_byte[threadIdx.x] = (uint8_t)(live & ~e);
-        __syncthreads();
-        if (wave == 0) {
-            const uint64_t word = lane < kResWords ? s_word[lane & (kResWords - 1)] : 0;
-            if (lane < kResWords) bitmap[tile * kResWords + lane] = word;
-            const uint32_t c = wave_sum((uint32_t)__popcll(word));
-            if (lane == 0) counts[tile] = c;
-        }
-        __syncthreads();
+        s_byte[threadIdx.x] = (uint8_t)(tile_live_rows(base, tend) & ~e);
+        tile_store_words(s_word, tile, bitmap, counts);
     }
 }
 
@@ -96,27 +86,14 @@ __global__ __launch_bounds__(kMatThreads) void k_agg_heads(const void* __restric
 __global__ __launch_bounds__(kMatThreads) void k_agg_emit(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ offs,
                                                          const uint32_t* __restrict__ perm, uint64_t ntiles, uint64_t* __restrict__ first_position,
                                                          uint32_t* __restrict__ first_row) {
-    const int lane = lane_id(), wave = wave_id();
-    constexpr int kWaveWords = kResWords / kResWaves;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t o0 = offs[tile], o1 = offs[tile + 1];
         if (o0 == o1) continue;   // uniform
-        const uint64_t word = lane < kResWords ? bitmap[tile * kResWords + lane] : 0;
-        const uint32_t pc = (uint32_t)__popcll(word);
-        const uint32_t before = wave_inclusive_sum(pc) - pc;
-#pragma unroll
-        for (int k = 0; k < kWaveWords; k++) {
-            const int w = wave * kWaveWords + k;
-            const uint32_t lo = __shfl((uint32_t)word, w, kWave), hi = __shfl((uint32_t)(word >> 32), w, kWave);
-            const uint32_t pre = __shfl(before, w, kWave);
-            const uint64_t bits = (uint64_t)lo | ((uint64_t)hi << 32);
-            if ((bits >> lane) & 1ull) {
-                const uint64_t rank = o0 + pre + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
-                const uint64_t pos = tile * kResTile + (uint64_t)(w * 64 + lane);
-                first_position[rank] = pos;
-                first_row[rank] = perm[pos];
-            }
-        }
+        tile_for_each_set(bitmap, tile, o0, [&](uint64_t rank, int r) {
+            const uint64_t pos = tile * kResTile + (uint64_t)r;
+            first_position[rank] = pos;
+            first_row[rank] = perm[pos];
+        });
     }
 }
 
@@ -141,30 +118,19 @@ __global__ __launch_bounds__(kMatThreads) void k_agg_reduce(const uint64_t* __re
     __shared__ uint64_t s_wave_v[kResWaves];
     __shared__ uint32_t s_wave_start[kResWaves];
     const int lane = lane_id(), wave = wave_id();
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    const uint64_t ntiles = tile_count(n);
     constexpr uint64_t ident = agg_identity<OP, FLT>();
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kResTile;
         const uint64_t tend = t0 + kResTile < n ? t0 + kResTile : n;   // one past the tile's last row
-        if (wave == 0) {
-            const uint64_t w = lane < kResWords ? bitmap[tile * kResWords + lane] : 0;
-            const uint32_t pc = (uint32_t)__popcll(w);
-            const uint32_t incl = wave_inclusive_sum(pc);
-            if (lane < kResWords) {
-                s_word[lane] = w;
-                s_pre[lane] = incl - pc;
-            }
-        }
-        __syncthreads();
+        tile_load_words(bitmap, tile, s_word, s_pre);
         const uint32_t r0 = threadIdx.x * kResRows;   // the lane's first row inside the tile
         const uint64_t base = t0 + r0;
-        const uint64_t word = s_word[r0 >> 6];
-        const uint32_t sh = r0 & 63u;                 // <= 56: the lane's 8 rows never straddle a word
-        const uint32_t starts = (uint32_t)(word >> sh) & 0xFFu;
-        const uint32_t before = s_pre[r0 >> 6] + (uint32_t)__popcll(word & ((1ull << sh) - 1ull));   // starts of the tile in front of the lane
+        uint32_t starts, before;                      // the lane's run starts, and the tile's in front of the lane
+        tile_lane_bits(s_word, s_pre, r0, &starts, &before);
         const uint32_t rn = r0 + kResRows;
         const uint32_t next_start = rn < (uint32_t)kResTile ? (uint32_t)(s_word[rn >> 6] >> (rn & 63u)) & 1u : 0u;
-        const uint32_t live = base >= tend ? 0u : (tend - base >= (uint64_t)kResRows ? (1u << kResRows) - 1 : (1u << (uint32_t)(tend - base)) - 1);
+        const uint32_t live = tile_live_rows(base, tend);
 
         uint64_t v[kResRows];
         if (live == (1u << kResRows) - 1) {   // 16-byte streams: 4 loads of values, or 2 of perm
@@ -291,22 +257,20 @@ struct cph_aggregated_impl {
 
 namespace cph {
 
-unsigned agg_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
-
 void agg_launch_heads(cph_ctx* ctx, const void* codes, bool key32, int nwords, uint64_t n, double code_bytes, uint64_t* bitmap, uint32_t* counts) {
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    const uint64_t ntiles = tile_count(n);
     ProfScope ps(ctx, "k_agg_heads", (double)n * (code_bytes + 1.0 / 8.0) + 4.0 * (double)ntiles);
     if (key32)
-        hipLaunchKernelGGL(k_agg_heads<true>, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, codes, n, nwords, bitmap, counts);
+        hipLaunchKernelGGL(k_agg_heads<true>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, codes, n, nwords, bitmap, counts);
     else
-        hipLaunchKernelGGL(k_agg_heads<false>, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, codes, n, nwords, bitmap, counts);
+        hipLaunchKernelGGL(k_agg_heads<false>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, codes, n, nwords, bitmap, counts);
 }
 
 void agg_launch_emit(cph_ctx* ctx, const uint64_t* bitmap, const uint32_t* offs, const uint32_t* perm, uint64_t n, uint64_t ngroups,
                      uint64_t* first_position, uint32_t* first_row) {
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    const uint64_t ntiles = tile_count(n);
     ProfScope ps(ctx, "k_agg_emit", (double)n / 8.0 + 4.0 * (double)ntiles + 16.0 * (double)ngroups);
-    hipLaunchKernelGGL(k_agg_emit, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap, offs, perm, ntiles, first_position, first_row);
+    hipLaunchKernelGGL(k_agg_emit, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap, offs, perm, ntiles, first_position, first_row);
 }
 
 namespace {
@@ -317,10 +281,10 @@ void launch_reduce(cph_ctx* ctx, bool gather, const AggReduceArgs& a) {
         // byte model: 8 B per row (+ 4 B of perm and a sector per row for a gathered spec), 1 bit of bitmap, 8 B per group out
         ProfScope ps(ctx, gather ? "k_agg_reduce_gather" : "k_agg_reduce", (double)a.n * (8.0 + (gather ? 4.0 : 0.0) + 1.0 / 8.0) + 20.0 * (double)a.ntiles);
         if (gather)
-            hipLaunchKernelGGL((k_agg_reduce<OP, FLT, true>), dim3(agg_grid(a.ntiles)), dim3(kMatThreads), 0, ctx->stream, a.bitmap, a.offs, a.src, a.perm,
+            hipLaunchKernelGGL((k_agg_reduce<OP, FLT, true>), dim3(tile_grid(a.ntiles)), dim3(kMatThreads), 0, ctx->stream, a.bitmap, a.offs, a.src, a.perm,
                                a.n, a.out, a.head, a.tail);
         else
-            hipLaunchKernelGGL((k_agg_reduce<OP, FLT, false>), dim3(agg_grid(a.ntiles)), dim3(kMatThreads), 0, ctx->stream, a.bitmap, a.offs, a.src, a.perm,
+            hipLaunchKernelGGL((k_agg_reduce<OP, FLT, false>), dim3(tile_grid(a.ntiles)), dim3(kMatThreads), 0, ctx->stream, a.bitmap, a.offs, a.src, a.perm,
                                a.n, a.out, a.head, a.tail);
     }
     ProfScope ps(ctx, "k_agg_carry", 24.0 * (double)a.ntiles);
@@ -392,7 +356,6 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* ix, const cph
     auto run = [&]() -> Status {
         const uint64_t n = ix->nrows;
         if (!n) return {};   // no rows, no groups: every array stays NULL
-        const uint64_t ntiles = (n + kResTile - 1) / kResTile;
         const uint32_t* perm = ix->perm.as<uint32_t>();
         // the values of every spec on the device: col specs converted through perm (sorted order), host numbers uploaded
         std::vector<DevBuf> staged;
@@ -431,21 +394,20 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* ix, const cph
             return {};
         }
         // run starts, group slots
-        DevBuf bitmap, counts;
-        CPH_TRY(bitmap.alloc(&ctx->pool, ntiles * kResWords * sizeof(uint64_t)));
-        CPH_TRY(counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
-        agg_launch_heads(ctx, ix->sorted_codes.get(), ix->codec.key32, ix->total_words(), n, (double)index_code_bytes(ix), bitmap.as<uint64_t>(),
-                         counts.as<uint32_t>());
+        TileBitmap tb;
+        CPH_TRY(tb.alloc(ctx, n));
+        const uint64_t ntiles = tb.ntiles;
+        agg_launch_heads(ctx, ix->sorted_codes.get(), ix->codec.key32, ix->total_words(), n, (double)index_code_bytes(ix), tb.words(), tb.counts());
         CPH_HIP_TRY(hipGetLastError());
-        CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));
+        CPH_TRY(tb.scan(ctx));
         uint32_t total = 0;
-        CPH_TRY(read_device_value(ctx, counts.as<uint32_t>() + ntiles, &total));   // the call's host wait (beside the conversions')
+        CPH_TRY(tb.read_total(ctx, &total));   // the call's host wait (beside the conversions')
         const uint64_t ng = total;
         if (ng == 0 || ng > n) return {CPH_ERR_HIP, "cph_index_aggregate: the run count is out of range"};   // n >= 1 has a run
         CPH_TRY(r->d_pos.alloc(&ctx->pool, ng * sizeof(uint64_t)));
         CPH_TRY(r->d_row.alloc(&ctx->pool, ng * sizeof(uint32_t)));
         CPH_TRY(r->d_cnt.alloc(&ctx->pool, ng * sizeof(uint64_t)));
-        agg_launch_emit(ctx, bitmap.as<uint64_t>(), counts.as<uint32_t>(), perm, n, ng, r->d_pos.as<uint64_t>(), r->d_row.as<uint32_t>());
+        agg_launch_emit(ctx, tb.words(), tb.counts(), perm, n, ng, r->d_pos.as<uint64_t>(), r->d_row.as<uint32_t>());
         CPH_HIP_TRY(hipGetLastError());
         {
             ProfScope ps(ctx, "k_agg_counts", 16.0 * (double)ng);
@@ -457,8 +419,8 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* ix, const cph
         if (nspecs) CPH_TRY(partials.alloc(&ctx->pool, 2 * ntiles * sizeof(uint64_t)));
         for (int32_t s = 0; s < nspecs; s++) {
             CPH_TRY(r->d_val[s].alloc(&ctx->pool, ng * sizeof(uint64_t)));
-            const AggReduceArgs a{bitmap.as<uint64_t>(), counts.as<uint32_t>(), src[s], perm, n, ntiles, r->d_val[s].as<uint64_t>(),
-                               partials.as<uint64_t>(), partials.as<uint64_t>() + ntiles};
+            const AggReduceArgs a{tb.words(), tb.counts(), src[s], perm, n, ntiles, r->d_val[s].as<uint64_t>(), partials.as<uint64_t>(),
+                               partials.as<uint64_t>() + ntiles};
             agg_launch_reduce(ctx, specs[s].op, specs[s].kind == CPH_NUM_FLOAT64, specs[s].col == nullptr, a);
             CPH_HIP_TRY(hipGetLastError());
         }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/csvplus_hip.h"
+#include "tile_bitmap.hpp"   // the constants of the row bitmaps TileBitmap (below) allocates
 
 namespace cph {
 
@@ -772,17 +773,16 @@ uint64_t chain_dense_mask_words(uint64_t nprobe);
 uint64_t chain_dense_count_words(uint64_t nprobe);
 
 // aggregate.hip: the segmented reduction over runs of equal SORTED keys, shared by cph_index_aggregate and the float Sum route of
-// cph_chain_aggregate (join_totals.hip).  Tiles are kResTile = 2048 positions (runs_device.hpp); all launches go on ctx->stream.
+// cph_chain_aggregate (join_totals.hip).  Tiles are kTileRows = 2048 positions (tile_bitmap.hpp); all launches go on ctx->stream.
 struct AggReduceArgs {
-    const uint64_t* bitmap;    // run starts, 32 words per tile (agg_launch_heads)
+    const uint64_t* bitmap;    // run starts (agg_launch_heads into a TileBitmap)
     const uint32_t* offs;      // [ntiles + 1] run starts in front of every tile (the scanned counts of agg_launch_heads)
     const uint64_t* src;       // gather: one 8-byte value per row id (read through perm); else one per sorted position
     const uint32_t* perm;      // [n] row id at every sorted position
     uint64_t n, ntiles;
     uint64_t *out, *head, *tail;   // out[run rank]; head / tail: ntiles partials each, scratch
 };
-unsigned agg_grid(uint64_t ntiles);
-// bitmap[ntiles * 32], counts[ntiles] (+ 1 for the scan's total) over n >= 1 sorted keys: u32[n] (key32) or u64[nwords][n] word-major
+// the run starts of n >= 1 sorted keys, u32[n] (key32) or u64[nwords][n] word-major, into the words and counts of a TileBitmap over n rows
 void agg_launch_heads(cph_ctx* ctx, const void* codes, bool key32, int nwords, uint64_t n, double code_bytes, uint64_t* bitmap, uint32_t* counts);
 // first_position[rank] = the run's first sorted position, first_row[rank] = perm[that]; ngroups only prices the launch
 void agg_launch_emit(cph_ctx* ctx, const uint64_t* bitmap, const uint32_t* offs, const uint32_t* perm, uint64_t n, uint64_t ngroups,
@@ -934,6 +934,27 @@ inline unsigned grid_for_items(uint64_t n, unsigned cap = 8192) {
     return (unsigned)(b ? b : 1);
 }
 
+// Grid for a kernel whose workgroups stride over tiles (of a row bitmap, or any other kind).
+inline unsigned tile_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
+
+// One bit per row and one count per tile of kTileRows rows, in the layout of tile_bitmap.hpp: the buffers every stage that selects
+// rows allocates, scans and reads the total of.  The stage's first kernel fills words() and counts(); scan() turns the counts into
+// the set bits in front of every tile and leaves their total behind them; read_total() is a host wait.
+struct TileBitmap {
+    DevBuf bitmap, tile_counts;
+    uint64_t ntiles = 0;
+    Status alloc(cph_ctx* ctx, uint64_t n) {
+        ntiles = tile_count(n);
+        CPH_TRY(bitmap.alloc(&ctx->pool, ntiles * kTileWords * sizeof(uint64_t)));
+        return tile_counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t));
+    }
+    uint64_t* words() const { return bitmap.as<uint64_t>(); }
+    uint32_t* counts() const { return tile_counts.as<uint32_t>(); }   // [ntiles], behind scan(): the exclusive prefix
+    uint32_t* total() const { return counts() + ntiles; }              // device; valid behind scan()
+    Status scan(cph_ctx* ctx) const { return exclusive_scan_u32_total(ctx, counts(), ntiles, total()); }
+    Status read_total(cph_ctx* ctx, uint32_t* host) const { return read_device_value(ctx, total(), host); }
+};
+
 // Times everything enqueued on ctx->stream during its lifetime when ctx->profiling is on
 // (two HIP events on that stream); `bytes` = algorithmic bytes of the launch.
 class ProfScope {
@@ -967,10 +988,8 @@ struct PredFloatCol {   // a column converted for the float or time terms of a c
     DevBuf values, status;
 };
 struct PredBitmap {
-    DevBuf bitmap;   // word w bit b = the program holds for row 64 w + b of the call (rows >= n: 0); whole tiles of 32 words
-    DevBuf counts;   // the set bits of every tile of 2048 rows, and one more entry for a scan's total
-    DevBuf lits;     // the program's literal block, which the evaluation reads
-    uint64_t ntiles = 0;
+    TileBitmap rows;   // bit = the program holds for that row of the call
+    DevBuf lits;       // the program's literal block, which the evaluation reads
 };
 // every rule of cph_filter_rows' comment about the program that does not need the columns
 Status check_pred_program(const cph_pred_op* prog, int32_t nops, int32_t ncols);

@@ -239,7 +239,6 @@ __global__ __launch_bounds__(kMatThreads) void k_expr_eval(ColsArg cols, ColIds 
 
 namespace {
 
-unsigned expr_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
 
 bool is_leaf(int32_t op) { return op >= CPH_EXPR_COL_INT && op <= CPH_EXPR_LIT_FLT; }
 
@@ -310,7 +309,7 @@ Status launch_eval(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, const Ex
         memcpy(slot, &zero, sizeof zero);
         CPH_HIP_TRY(hipMemcpyAsync(cnt.get(), slot, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
     }
-    const dim3 grid(expr_grid((n + kExprTile - 1) / kExprTile));
+    const dim3 grid(tile_grid((n + kExprTile - 1) / kExprTile));
     {
         ProfScope ps(ctx, "k_expr_eval", bytes);
         if (depth <= 2)

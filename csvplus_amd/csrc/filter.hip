@@ -8,11 +8,11 @@
 //   k_pred_eval   rows on lanes (row = tile + 64 k + lane, 4 rows per lane in flight).  Every LIKE term over a real column
 //                 (at most 32) becomes one bit of a per-row mask; the boolean program then runs over that mask on a bit
 //                 stack — it is wave-uniform, only the data differs per lane.  __ballot is 64 bits wide on gfx950: a
-//                 wave's ballot IS the bitmap word of its 64 rows.  A tile's 32 words go through LDS and leave as one
-//                 coalesced store by 32 lanes, whose popcounts add up to the tile's count.
-//   exclusive scan of the tile counts (radix_sort.hip); its total is the result size — the call's host wait.
-//   k_pred_emit   per tile: bitmap words -> rank inside the tile by popcount + mbcnt -> out[rank - skip] = first_row + row
-//                 for the ranks in [skip, skip + limit).  No atomics in either kernel of the WHERE mode.
+//                 wave's ballot IS the bitmap word of its 64 rows.  The tile's words and count leave through the tile
+//                 store of tile_bitmap.hpp, which describes the layout.
+//   exclusive scan of the tile counts (TileBitmap::scan); its total is the result size — the call's host wait.
+//   k_pred_emit   the rank walker of tile_bitmap.hpp: out[rank - skip] = first_row + row for the ranks in
+//                 [skip, skip + limit).  No atomics in either kernel of the WHERE mode.
 // The two WHILE modes only need the first failing row: the same evaluation without the bitmap, one 64-bit atomicMin per
 // wave that saw a failure (none when the value it read at the tile's start is already smaller; tiles behind that value
 // are not read at all).  Their answer is a range: nothing is materialised.
@@ -44,15 +44,14 @@
 
 #include "numparse_device.hpp"
 #include "strpred_device.hpp"
+#include "tile_bitmap.hpp"
 #include "timeparse_device.hpp"
 
 namespace cph {
 
-constexpr int kFiltRows  = 8;                          // rows per lane and tile
+constexpr int kFiltRows  = kTileWaveWords;             // rows per lane and tile: one of each word of the lane's wave
 constexpr int kFiltPhase = 4;                          // ... of which this many are in flight at once
-constexpr int kFiltTile  = kMatThreads * kFiltRows;    // 2048 rows = 32 bitmap words
-constexpr int kFiltWords = kFiltTile / 64;
-constexpr int kFiltWaveWords = kFiltWords / (kMatThreads / kWave);   // 8 words per wave
+static_assert(kMatThreads == kTileWaves * kWave, "one workgroup per tile");
 constexpr int kLitLds    = 4096;                       // literal bytes kept in LDS; more than that stay in global memory
 
 enum : uint32_t { kTermBytes = 0, kTermFix8 = 1, kTermInt = 2, kTermF64 = 3,     // low byte of PredTerm::kind
@@ -125,8 +124,7 @@ __device__ __forceinline__ bool str_term(uint32_t what, uint32_t rel, const DevC
     return str_contains(v, vlen, lit, (uint64_t)t.len);
 }
 
-// BITMAP: bitmap[tile * 32 + w] bit b = the predicate holds for row tile * 2048 + 64 w + b of the call (rows >= n: 0),
-//         counts[tile] = the tile's set bits.
+// BITMAP: bit = the predicate holds for that row of the call, in the layout of tile_bitmap.hpp.
 // else:   *first_fail = min(*first_fail, the first row where it does not hold); the host presets it to n.
 // STR: the program has a term of strpred_device.hpp; NUM: a numeric one; TIM (with NUM): a time term
 template <bool BITMAP, bool NUM, bool STR = false, bool TIM = false>
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds 
                                                           uint64_t* __restrict__ bitmap, uint32_t* __restrict__ counts,
                                                           unsigned long long* first_fail) {
     __shared__ uint64_t s_lits[kLitLds / 8];
-    __shared__ uint64_t s_words[kFiltWords];
+    __shared__ uint64_t s_words[kTileWords];
     const CPH_LDS uint64_t* slits = (const CPH_LDS uint64_t*)s_lits;
     const bool in_lds = prog.lits_in_lds != 0;
     if (in_lds) {
@@ -142,9 +140,9 @@ __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds 
         __syncthreads();
     }
     const int lane = lane_id(), wave = wave_id();
-    const uint64_t ntiles = (n + kFiltTile - 1) / kFiltTile;
+    const uint64_t ntiles = tile_count(n);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * kFiltTile;
+        const uint64_t t0 = tile * kTileRows;
         unsigned long long seen = 0;
         if constexpr (!BITMAP) {
             seen = __hip_atomic_load(first_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -158,7 +156,7 @@ __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds 
             uint32_t mask[kFiltPhase];
 #pragma unroll
             for (int k = 0; k < kFiltPhase; k++) {
-                const uint64_t i = t0 + (uint64_t)((wave * kFiltWaveWords + ph * kFiltPhase + k) * 64 + lane);
+                const uint64_t i = t0 + (uint64_t)((wave * kTileWaveWords + ph * kFiltPhase + k) * 64 + lane);
                 pos[k] = first_row + (i < n ? i : n - 1);
                 mask[k] = 0;
             }
@@ -259,28 +257,21 @@ __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds 
 #pragma unroll
             for (int k = 0; k < kFiltPhase; k++) {
                 const int w = ph * kFiltPhase + k;
-                const uint64_t i = t0 + (uint64_t)((wave * kFiltWaveWords + w) * 64 + lane);
+                const uint64_t i = t0 + (uint64_t)((wave * kTileWaveWords + w) * 64 + lane);
                 const bool holds = (st[k] & 1ull) != 0;
                 if constexpr (BITMAP) {
                     const uint64_t word = __ballot(i < n && holds);
                     if (lane == w) myword = word;
                 } else {
                     const uint64_t bad = __ballot(i < n && !holds);
-                    const unsigned long long at = t0 + (uint64_t)((wave * kFiltWaveWords + w) * 64) + (uint64_t)__builtin_ctzll(bad | (1ull << 63));
+                    const unsigned long long at = t0 + (uint64_t)((wave * kTileWaveWords + w) * 64) + (uint64_t)__builtin_ctzll(bad | (1ull << 63));
                     if (bad && at < fail) fail = at;
                 }
             }
         }
         if constexpr (BITMAP) {
-            if (lane < kFiltWaveWords) s_words[wave * kFiltWaveWords + lane] = myword;
-            __syncthreads();
-            if (wave == 0) {   // one lane per word: a 256-byte store
-                const uint64_t word = lane < kFiltWords ? s_words[lane] : 0;
-                if (lane < kFiltWords) bitmap[tile * kFiltWords + lane] = word;
-                const uint32_t c = wave_sum((uint32_t)__popcll(word));
-                if (lane == 0) counts[tile] = c;
-            }
-            __syncthreads();
+            if (lane < kTileWaveWords) s_words[wave * kTileWaveWords + lane] = myword;
+            tile_store_words(s_words, tile, bitmap, counts);
         } else {
             if (lane == 0 && fail < seen) atomicMin(first_fail, fail);
         }
@@ -293,24 +284,12 @@ template <class T>
 __global__ __launch_bounds__(kMatThreads) void k_pred_emit(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ offs,
                                                           uint64_t ntiles, uint64_t first_row, uint64_t skip, uint64_t end,
                                                           T* __restrict__ out) {
-    const int lane = lane_id(), wave = wave_id();
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t o0 = offs[tile], o1 = offs[tile + 1];
         if (o0 == o1 || o1 <= skip || o0 >= end) continue;   // uniform
-        const uint64_t word = lane < kFiltWords ? bitmap[tile * kFiltWords + lane] : 0;
-        const uint32_t pc = (uint32_t)__popcll(word);
-        const uint32_t before = wave_inclusive_sum(pc) - pc;
-#pragma unroll
-        for (int k = 0; k < kFiltWaveWords; k++) {
-            const int w = wave * kFiltWaveWords + k;
-            const uint32_t lo = __shfl((uint32_t)word, w, kWave), hi = __shfl((uint32_t)(word >> 32), w, kWave);
-            const uint32_t pre = __shfl(before, w, kWave);
-            const uint64_t bits = (uint64_t)lo | ((uint64_t)hi << 32);
-            if ((bits >> lane) & 1ull) {
-                const uint64_t rank = o0 + pre + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
-                if (rank >= skip && rank < end) out[rank - skip] = (T)(first_row + tile * kFiltTile + (uint64_t)(w * 64 + lane));
-            }
-        }
+        tile_for_each_set(bitmap, tile, o0, [&](uint64_t rank, int r) {
+            if (rank >= skip && rank < end) out[rank - skip] = (T)(first_row + tile * kTileRows + (uint64_t)r);
+        });
     }
 }
 
@@ -449,7 +428,6 @@ uint32_t rel_outcomes(int32_t rel) {
     static const uint32_t m[6] = {kCmpLess, kCmpLess | kCmpEqual, kCmpEqual, kCmpLess | kCmpGreater | kCmpUnordered, kCmpEqual | kCmpGreater, kCmpGreater};
     return m[rel];
 }
-unsigned filter_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
 
 struct BuiltProg {   // a program as k_pred_eval takes it
     PredProg pp{};
@@ -589,7 +567,7 @@ Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, cons
 template <bool BITMAP>
 void launch_pred_eval(cph_ctx* ctx, const BuiltProg& bp, const ColsArg& arg, const ColIds& ids, uint64_t first_row, uint64_t n, uint64_t ntiles,
                       uint64_t* bitmap, uint32_t* counts, unsigned long long* first_fail) {
-    const dim3 grid(filter_grid(ntiles)), block(kMatThreads);
+    const dim3 grid(tile_grid(ntiles)), block(kMatThreads);
     if (bp.times && bp.strings)
         hipLaunchKernelGGL((k_pred_eval<BITMAP, true, true, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
     else if (bp.times)
@@ -614,13 +592,11 @@ Status pred_eval_bitmap(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, con
                         uint64_t n, std::vector<PredFloatCol>* fcols, PredBitmap* out) {
     BuiltProg bp;
     CPH_TRY(build_pred_prog(ctx, arg, ids, prog, nops, first_row, n, fcols, &bp));
-    const uint64_t ntiles = (n + kFiltTile - 1) / kFiltTile;
-    out->ntiles = ntiles;
-    CPH_TRY(out->bitmap.alloc(&ctx->pool, ntiles * kFiltWords * sizeof(uint64_t)));
-    CPH_TRY(out->counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
+    TileBitmap& tb = out->rows;
+    CPH_TRY(tb.alloc(ctx, n));
     {
-        ProfScope ps(ctx, bp.strings ? "k_pred_eval_str" : "k_pred_eval", bp.col_bytes + (double)n / 8.0 + 4.0 * (double)ntiles);
-        launch_pred_eval<true>(ctx, bp, arg, ids, first_row, n, ntiles, out->bitmap.as<uint64_t>(), out->counts.as<uint32_t>(), nullptr);
+        ProfScope ps(ctx, bp.strings ? "k_pred_eval_str" : "k_pred_eval", bp.col_bytes + (double)n / 8.0 + 4.0 * (double)tb.ntiles);
+        launch_pred_eval<true>(ctx, bp, arg, ids, first_row, n, tb.ntiles, tb.words(), tb.counts(), nullptr);
     }
     CPH_HIP_TRY(hipGetLastError());
     out->lits = std::move(bp.litbuf);   // the kernel reads it: it lives as long as the bitmap
@@ -671,7 +647,7 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         ColIds ids{};
         CPH_TRY(stage_row_sources(ctx, cols, sel, nullptr, ncols, first_row, n, &staged, &arg, &ids));
         std::vector<PredFloatCol> fcols;
-        const uint64_t ntiles = (n + kFiltTile - 1) / kFiltTile;
+        const uint64_t ntiles = tile_count(n);
         CPH_TRY(ensure_pinned_scratch(ctx, sizeof(uint64_t)));
         if (opts->mode != CPH_FILTER_WHERE) {
             BuiltProg bp;
@@ -698,11 +674,10 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         }
         PredBitmap pb;
         CPH_TRY(pred_eval_bitmap(ctx, arg, ids, prog, nops, first_row, n, &fcols, &pb));
-        DevBuf& bitmap = pb.bitmap;
-        DevBuf& counts = pb.counts;
-        CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));
+        const TileBitmap& tb = pb.rows;
+        CPH_TRY(tb.scan(ctx));
         uint32_t total = 0;
-        CPH_TRY(read_device_value(ctx, counts.as<uint32_t>() + ntiles, &total));   // the call's host wait
+        CPH_TRY(tb.read_total(ctx, &total));   // the call's host wait
         uint64_t kept = total > opts->skip ? total - opts->skip : 0;
         if (kept > opts->limit) kept = opts->limit;
         if (kept == 0) {
@@ -714,11 +689,11 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         {
             ProfScope ps(ctx, "k_pred_emit", (double)n / 8.0 + 4.0 * (double)ntiles + (double)kept * (double)(bits / 8));
             if (bits == 32)
-                hipLaunchKernelGGL(k_pred_emit<uint32_t>, dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap.as<uint64_t>(),
-                                   counts.as<uint32_t>(), ntiles, first_row, opts->skip, opts->skip + kept, outb.as<uint32_t>());
+                hipLaunchKernelGGL(k_pred_emit<uint32_t>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, tb.words(), tb.counts(), ntiles,
+                                   first_row, opts->skip, opts->skip + kept, outb.as<uint32_t>());
             else
-                hipLaunchKernelGGL(k_pred_emit<uint64_t>, dim3(filter_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap.as<uint64_t>(),
-                                   counts.as<uint32_t>(), ntiles, first_row, opts->skip, opts->skip + kept, outb.as<uint64_t>());
+                hipLaunchKernelGGL(k_pred_emit<uint64_t>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, tb.words(), tb.counts(), ntiles,
+                                   first_row, opts->skip, opts->skip + kept, outb.as<uint64_t>());
         }
         CPH_HIP_TRY(hipGetLastError());
         return deliver_ids(ctx, r, std::move(outb), kept, bits, out_mem);

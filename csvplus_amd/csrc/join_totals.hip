@@ -282,9 +282,10 @@ int bits_for(uint64_t max_value) {
 
 // what the float Sum specs of one call share: the joined rows sorted by group, the run starts, the key of every run
 struct SortedRuns {
-    DevBuf ka, kb, va, vb, bitmap, counts, run_pos, run_key, partials, sums;
+    DevBuf ka, kb, va, vb, run_pos, run_key, partials, sums;
+    TileBitmap starts;                           // the run starts over the sorted keys
     uint32_t *keys = nullptr, *rows = nullptr;   // sorted group per position, joined row m per position
-    uint64_t ntiles = 0, max_runs = 0;
+    uint64_t max_runs = 0;
 };
 
 Status sort_runs(cph_ctx* ctx, const uint32_t* build_rows, uint64_t n, uint32_t ng, uint32_t* bad, SortedRuns* sr) {
@@ -300,20 +301,18 @@ Status sort_runs(cph_ctx* ctx, const uint32_t* build_rows, uint64_t n, uint32_t 
     int passes = 0;
     CPH_TRY(radix_sort_pairs<uint32_t>(ctx, sr->ka.as<uint32_t>(), sr->kb.as<uint32_t>(), sr->va.as<uint32_t>(), sr->vb.as<uint32_t>(), true, n,
                                        bits_for((uint64_t)ng - 1), &sr->keys, &sr->rows, &passes));
-    sr->ntiles = (n + kResTile - 1) / kResTile;
     sr->max_runs = std::min<uint64_t>(n, ng);
-    CPH_TRY(sr->bitmap.alloc(&ctx->pool, sr->ntiles * kResWords * sizeof(uint64_t)));
-    CPH_TRY(sr->counts.alloc(&ctx->pool, (sr->ntiles + 1) * sizeof(uint32_t)));
-    agg_launch_heads(ctx, sr->keys, true, 1, n, 4.0, sr->bitmap.as<uint64_t>(), sr->counts.as<uint32_t>());
+    CPH_TRY(sr->starts.alloc(ctx, n));
+    agg_launch_heads(ctx, sr->keys, true, 1, n, 4.0, sr->starts.words(), sr->starts.counts());
     CPH_HIP_TRY(hipGetLastError());
-    CPH_TRY(exclusive_scan_u32_total(ctx, sr->counts.as<uint32_t>(), sr->ntiles, sr->counts.as<uint32_t>() + sr->ntiles));
+    CPH_TRY(sr->starts.scan(ctx));
     // the keys are below ng and sorted, so there are at most min(n, ng) runs: no host trip for the count
     CPH_TRY(sr->run_pos.alloc(&ctx->pool, sr->max_runs * sizeof(uint64_t)));
     CPH_TRY(sr->run_key.alloc(&ctx->pool, sr->max_runs * sizeof(uint32_t)));
-    agg_launch_emit(ctx, sr->bitmap.as<uint64_t>(), sr->counts.as<uint32_t>(), sr->keys, n, sr->max_runs, sr->run_pos.as<uint64_t>(),
+    agg_launch_emit(ctx, sr->starts.words(), sr->starts.counts(), sr->keys, n, sr->max_runs, sr->run_pos.as<uint64_t>(),
                     sr->run_key.as<uint32_t>());   // "perm" = the sorted keys: first_row[r] = the key of run r
     CPH_HIP_TRY(hipGetLastError());
-    CPH_TRY(sr->partials.alloc(&ctx->pool, 2 * sr->ntiles * sizeof(uint64_t)));
+    CPH_TRY(sr->partials.alloc(&ctx->pool, 2 * sr->starts.ntiles * sizeof(uint64_t)));
     CPH_TRY(sr->sums.alloc(&ctx->pool, sr->max_runs * sizeof(uint64_t)));
     return {};
 }
@@ -424,13 +423,13 @@ CPH_API int32_t cph_chain_aggregate(cph_ctx* ctx, const cph_chain* chain, int32_
         };
         // one spec over the sorted runs: the segmented reduce with the sorted m as gather permutation, each run's value to its group
         auto reduce_runs = [&](int32_t op, bool flt, const uint64_t* v, uint64_t* table) -> Status {
-            const AggReduceArgs a{sr.bitmap.as<uint64_t>(), sr.counts.as<uint32_t>(), v, sr.rows, n, sr.ntiles, sr.sums.as<uint64_t>(),
-                                  sr.partials.as<uint64_t>(), sr.partials.as<uint64_t>() + sr.ntiles};
+            const AggReduceArgs a{sr.starts.words(), sr.starts.counts(), v, sr.rows, n, sr.starts.ntiles, sr.sums.as<uint64_t>(),
+                                  sr.partials.as<uint64_t>(), sr.partials.as<uint64_t>() + sr.starts.ntiles};
             agg_launch_reduce(ctx, op, flt, true, a);
             CPH_HIP_TRY(hipGetLastError());
             ProfScope ps(ctx, "k_jt_scatter", 20.0 * (double)sr.max_runs);
             hipLaunchKernelGGL(k_jt_scatter, dim3(grid_for_items(sr.max_runs)), dim3(kJtThreads), 0, ctx->stream, sr.sums.as<uint64_t>(),
-                               sr.run_key.as<uint32_t>(), sr.counts.as<uint32_t>() + sr.ntiles, sr.max_runs, ng, table);
+                               sr.run_key.as<uint32_t>(), sr.starts.total(), sr.max_runs, ng, table);
             CPH_HIP_TRY(hipGetLastError());
             return {};
         };
@@ -441,7 +440,7 @@ CPH_API int32_t cph_chain_aggregate(cph_ctx* ctx, const cph_chain* chain, int32_
             CPH_TRY(fill(count, 0ull));
             ProfScope ps(ctx, "k_jt_run_counts", 20.0 * (double)sr.max_runs);
             hipLaunchKernelGGL(k_jt_run_counts, dim3(grid_for_items(sr.max_runs)), dim3(kJtThreads), 0, ctx->stream, sr.run_pos.as<uint64_t>(),
-                               sr.run_key.as<uint32_t>(), sr.counts.as<uint32_t>() + sr.ntiles, sr.max_runs, n, ng, count);
+                               sr.run_key.as<uint32_t>(), sr.starts.total(), sr.max_runs, n, ng, count);
         } else {
             launch_direct<kJtAdd, kJtOne>(ctx, "k_jt_direct_count", rows, nullptr, n, ng, count, d_bad);
         }

@@ -179,7 +179,7 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         plan.ncases = ncases;
         for (int c = 0; c < ncases; c++) {
             CPH_TRY(pred_eval_bitmap(ctx, arg, ids, cases[c].prog, cases[c].nops, 0, n, &fcols, &maps[c]));
-            plan.bits[c] = maps[c].bitmap.as<uint64_t>();
+            plan.bits[c] = maps[c].rows.words();
         }
         // the alternatives' pieces in one flat array, their literals in one block
         MapPlanBuild build;

@@ -206,7 +206,6 @@ __global__ __launch_bounds__(kMatThreads) void k_num_patch(const NumPatch* __res
 
 namespace {
 
-unsigned num_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
 
 // One syntactically valid decimal value the device deferred: correctly rounded, locale independent.  A finite result
 // is never an error (underflow to 0 or a denormal included, as in Go); +-HUGE_VAL is a range error with value +-Inf.
@@ -264,16 +263,16 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
         ProfScope ps(ctx, tim ? "k_num_parse_time" : full ? "k_num_parse_f64_full" : flt ? "k_num_parse_f64" : "k_num_parse_i64",
                      (in_row + in_time + 9.0) * (double)n);
         if (tim)
-            hipLaunchKernelGGL(k_num_parse<kParseTime>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+            hipLaunchKernelGGL(k_num_parse<kParseTime>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
                                values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), kind == CPH_NUM_TIME_UNIXNANO ? 1u : 0u);
         else if (full)
-            hipLaunchKernelGGL(k_num_parse<kParseFloatFull>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+            hipLaunchKernelGGL(k_num_parse<kParseFloatFull>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
                                values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
         else if (flt)
-            hipLaunchKernelGGL(k_num_parse<kParseFloat>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+            hipLaunchKernelGGL(k_num_parse<kParseFloat>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
                                values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
         else
-            hipLaunchKernelGGL(k_num_parse<kParseInt>, dim3(num_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
+            hipLaunchKernelGGL(k_num_parse<kParseInt>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
                                values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
     }
     CPH_HIP_TRY(hipGetLastError());

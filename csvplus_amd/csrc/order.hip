@@ -6,7 +6,8 @@
 //                            whose status byte is not OK are counted and the lowest (row, key) is kept (integer atomics, one
 //                            pair per wave).
 //   k_order_key_rank         a BYTES key: the index's run starts (k_agg_heads, aggregate.hip) and their scan give every sorted
-//                            position the DENSE RANK of its run; key[perm[p]] = rank (ngroups - 1 - rank when descending):
+//                            position the DENSE RANK of its run (the reverse lookup of tile_bitmap.hpp); key[perm[p]] = rank
+//                            (ngroups - 1 - rank when descending):
 //                            32 bits, of which the sort looks at bit_length(ngroups - 1).
 //   sort                     least significant key first: k_order_gather reads the key through the current order, then
 //                            radix_sort_pairs<uint64_t / uint32_t> over (key, row id).  The first sort of a call without
@@ -19,7 +20,8 @@
 //   k_order_select_pick      one workgroup: scans the 256 counters, picks the bin that holds the wanted rank, leaves the longer
 //                            prefix and the rank inside the bin in device memory for the next pass.  No host wait in between.
 //   k_order_select_flag      bitmap of the rows with key 0 <= threshold (every tie at the threshold included) + counts per tile
-//   k_order_select_emit      bitmap -> candidate row ids in input order (scan of the tile counts in between)
+//                            (tile_bitmap.hpp: the layout, the tile store)
+//   k_order_select_emit      its rank walker: bitmap -> candidate row ids in input order (scan of the tile counts in between)
 // The host reads the candidate count once (allocation and sort plan need it); the multi-key sort then runs over the candidates.
 #include <algorithm>
 #include <cstring>
@@ -79,26 +81,14 @@ __global__ __launch_bounds__(kMatThreads) void k_order_key_rank(const uint64_t* 
                                                                uint32_t descending, uint32_t* __restrict__ out) {
     __shared__ uint64_t s_word[kResWords];
     __shared__ uint32_t s_pre[kResWords];
-    const int lane = lane_id(), wave = wave_id();
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    const uint64_t ntiles = tile_count(n);
     const uint32_t top = offs[ntiles] - 1u;   // ngroups - 1 (n >= 1 has a run)
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        if (wave == 0) {
-            const uint64_t w = lane < kResWords ? bitmap[tile * kResWords + lane] : 0;
-            const uint32_t pc = (uint32_t)__popcll(w);
-            const uint32_t incl = wave_inclusive_sum(pc);
-            if (lane < kResWords) {
-                s_word[lane] = w;
-                s_pre[lane] = incl - pc;
-            }
-        }
-        __syncthreads();
+        tile_load_words(bitmap, tile, s_word, s_pre);
         const uint32_t r0 = threadIdx.x * kResRows;
         const uint64_t base = tile * kResTile + r0;
-        const uint64_t word = s_word[r0 >> 6];
-        const uint32_t sh = r0 & 63u;   // <= 56: the lane's 8 rows never straddle a word
-        const uint32_t starts = (uint32_t)(word >> sh) & 0xFFu;
-        const uint32_t before = s_pre[r0 >> 6] + (uint32_t)__popcll(word & ((1ull << sh) - 1ull));
+        uint32_t starts, before;
+        tile_lane_bits(s_word, s_pre, r0, &starts, &before);
         const uint32_t o0 = offs[tile];
 #pragma unroll
         for (int k = 0; k < kResRows; k++) {
@@ -186,15 +176,14 @@ __global__ __launch_bounds__(kMatThreads) void k_order_select_pick(const uint32_
     }
 }
 
-// bitmap[tile * 32 + w] bit b = row tile * 2048 + 64 w + b has key <= st->prefix (rows >= n: 0); counts[tile] = its set bits
+// bit = that row has key <= st->prefix (tile_bitmap.hpp)
 template <class K>
 __global__ __launch_bounds__(kMatThreads) void k_order_select_flag(const K* __restrict__ keys, uint64_t n, const SelectState* __restrict__ st,
                                                                   uint64_t* __restrict__ bitmap, uint32_t* __restrict__ counts) {
     constexpr int NV = KeyVec<K>::N;
     __shared__ uint64_t s_word[kResWords];
     uint8_t* s_byte = reinterpret_cast<uint8_t*>(s_word);   // kResRows == 8: one byte per lane
-    const int lane = lane_id(), wave = wave_id();
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    const uint64_t ntiles = tile_count(n);
     const uint64_t thr = st->prefix;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * kResTile + (uint64_t)threadIdx.x * kResRows;
@@ -213,39 +202,19 @@ __global__ __launch_bounds__(kMatThreads) void k_order_select_flag(const K* __re
                 if (base + (uint64_t)j < n) flags |= ((uint64_t)keys[base + (uint64_t)j] <= thr ? 1u : 0u) << j;
         }
         s_byte[threadIdx.x] = (uint8_t)flags;
-        __syncthreads();
-        if (wave == 0) {
-            const uint64_t word = lane < kResWords ? s_word[lane & (kResWords - 1)] : 0;
-            if (lane < kResWords) bitmap[tile * kResWords + lane] = word;
-            const uint32_t c = wave_sum((uint32_t)__popcll(word));
-            if (lane == 0) counts[tile] = c;
-        }
-        __syncthreads();
+        tile_store_words(s_word, tile, bitmap, counts);
     }
 }
 
 // offs[tile] = set bits in front of the tile; cand[rank] = the row of the rank-th set bit: the candidates in input order
 __global__ __launch_bounds__(kMatThreads) void k_order_select_emit(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ offs, uint64_t ntiles,
                                                                   uint64_t ncand, uint32_t* __restrict__ cand) {
-    const int lane = lane_id(), wave = wave_id();
-    constexpr int kWaveWords = kResWords / kResWaves;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t o0 = offs[tile], o1 = offs[tile + 1];
         if (o0 == o1) continue;   // uniform
-        const uint64_t word = lane < kResWords ? bitmap[tile * kResWords + lane] : 0;
-        const uint32_t pc = (uint32_t)__popcll(word);
-        const uint32_t before = wave_inclusive_sum(pc) - pc;
-#pragma unroll
-        for (int k = 0; k < kWaveWords; k++) {
-            const int w = wave * kWaveWords + k;
-            const uint32_t lo = __shfl((uint32_t)word, w, kWave), hi = __shfl((uint32_t)(word >> 32), w, kWave);
-            const uint32_t pre = __shfl(before, w, kWave);
-            const uint64_t bits = (uint64_t)lo | ((uint64_t)hi << 32);
-            if ((bits >> lane) & 1ull) {
-                const uint64_t rank = o0 + pre + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
-                if (rank < ncand) cand[rank] = (uint32_t)(tile * kResTile + (uint64_t)(w * 64 + lane));
-            }
-        }
+        tile_for_each_set(bitmap, tile, o0, [&](uint64_t rank, int r) {
+            if (rank < ncand) cand[rank] = (uint32_t)(tile * kResTile + (uint64_t)r);
+        });
     }
 }
 
@@ -327,25 +296,23 @@ Status key_pass_number(cph_ctx* ctx, const cph_order_key& key, int32_t k, uint64
 // A BYTES key: the dense rank of every row's run in the index.  One host read (the number of runs: the sort's bits).
 Status key_pass_bytes(cph_ctx* ctx, const cph_order_key& key, uint64_t n, DevKey* dk) {
     const cph_index* ix = key.index;
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
-    DevBuf bitmap, counts;
-    CPH_TRY(bitmap.alloc(&ctx->pool, ntiles * kResWords * sizeof(uint64_t)));
-    CPH_TRY(counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
-    agg_launch_heads(ctx, ix->sorted_codes.get(), ix->codec.key32, ix->total_words(), n, (double)index_code_bytes(ix), bitmap.as<uint64_t>(),
-                     counts.as<uint32_t>());
+    TileBitmap tb;
+    CPH_TRY(tb.alloc(ctx, n));
+    const uint64_t ntiles = tb.ntiles;
+    agg_launch_heads(ctx, ix->sorted_codes.get(), ix->codec.key32, ix->total_words(), n, (double)index_code_bytes(ix), tb.words(), tb.counts());
     CPH_HIP_TRY(hipGetLastError());
-    CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));
+    CPH_TRY(tb.scan(ctx));
     CPH_TRY(dk->buf.alloc(&ctx->pool, (size_t)n * 4));
     CPH_HIP_TRY(hipMemsetAsync(dk->buf.get(), 0, (size_t)n * 4, ctx->stream));   // a malformed perm leaves no row without a key
     {
         // byte model: 1 bit of bitmap, 4 B of perm, a 4-byte scattered store per row
         ProfScope ps(ctx, "k_order_key_rank", (double)n * (8.0 + 1.0 / 8.0) + 4.0 * (double)ntiles);
-        hipLaunchKernelGGL(k_order_key_rank, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap.as<uint64_t>(), counts.as<uint32_t>(),
-                           ix->perm.as<uint32_t>(), n, n, (uint32_t)(key.descending != 0), dk->buf.as<uint32_t>());
+        hipLaunchKernelGGL(k_order_key_rank, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, tb.words(), tb.counts(), ix->perm.as<uint32_t>(), n,
+                           n, (uint32_t)(key.descending != 0), dk->buf.as<uint32_t>());
     }
     CPH_HIP_TRY(hipGetLastError());
     uint32_t ng = 0;
-    CPH_TRY(read_device_value(ctx, counts.as<uint32_t>() + ntiles, &ng));
+    CPH_TRY(tb.read_total(ctx, &ng));
     if (ng == 0 || (uint64_t)ng > n) return {CPH_ERR_HIP, "cph_order_rows: the run count of an index is out of range"};
     dk->wide = false;
     dk->bits = bit_length((uint64_t)ng - 1);
@@ -426,25 +393,24 @@ Status select_candidates(cph_ctx* ctx, const DevKey& dk, uint64_t n, uint64_t wa
         hipLaunchKernelGGL(k_order_select_pick, dim3(1), dim3(kMatThreads), 0, ctx->stream, hist.as<uint32_t>() + (size_t)p * 256, shift, state.as<SelectState>());
         CPH_HIP_TRY(hipGetLastError());
     }
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
-    DevBuf bitmap, counts;
-    CPH_TRY(bitmap.alloc(&ctx->pool, ntiles * kResWords * sizeof(uint64_t)));
-    CPH_TRY(counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
+    TileBitmap tb;
+    CPH_TRY(tb.alloc(ctx, n));
+    const uint64_t ntiles = tb.ntiles;
     {
         ProfScope ps(ctx, sizeof(K) == 8 ? "k_order_select_flag_u64" : "k_order_select_flag_u32", (double)n * (sizeof(K) + 1.0 / 8.0) + 4.0 * (double)ntiles);
-        hipLaunchKernelGGL(k_order_select_flag<K>, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, keys, n, state.as<SelectState>(),
-                           bitmap.as<uint64_t>(), counts.as<uint32_t>());
+        hipLaunchKernelGGL(k_order_select_flag<K>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, keys, n, state.as<SelectState>(), tb.words(),
+                           tb.counts());
     }
     CPH_HIP_TRY(hipGetLastError());
-    CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));
+    CPH_TRY(tb.scan(ctx));
     uint32_t total = 0;
-    CPH_TRY(read_device_value(ctx, counts.as<uint32_t>() + ntiles, &total));   // the route's one host wait
+    CPH_TRY(tb.read_total(ctx, &total));   // the route's one host wait
     if ((uint64_t)total < want || (uint64_t)total > n) return {CPH_ERR_HIP, "cph_order_rows: the candidate count is out of range"};
     CPH_TRY(cand->alloc(&ctx->pool, (size_t)total * sizeof(uint32_t)));
     {
         ProfScope ps(ctx, "k_order_select_emit", (double)n / 8.0 + 8.0 * (double)ntiles + 4.0 * (double)total);
-        hipLaunchKernelGGL(k_order_select_emit, dim3(agg_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap.as<uint64_t>(), counts.as<uint32_t>(), ntiles,
-                           (uint64_t)total, cand->as<uint32_t>());
+        hipLaunchKernelGGL(k_order_select_emit, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, tb.words(), tb.counts(), ntiles, (uint64_t)total,
+                           cand->as<uint32_t>());
     }
     CPH_HIP_TRY(hipGetLastError());
     *ncand = total;

@@ -17,8 +17,8 @@
 //                     tiles in front, 64 at a time, to the tile where the run started (a run may span every tile), and sets
 //                     the winner's bit.
 //   k_resolve_finish  one lane: the reference's tail rule (it needs the GLOBAL group count) and perm[first error].
-//   exclusive scan of the tile counts (radix_sort.hip), then
-//   k_resolve_emit    bitmap words -> rank by popcount + mbcnt -> positions[rank], as k_pred_emit does.
+//   exclusive scan of the tile counts (TileBitmap::scan), then
+//   k_resolve_emit    the rank walker of tile_bitmap.hpp: positions[rank].
 //   index_select_device (index_ops.hip) gathers perm and the codes: the device half of cph_index_select.
 // The group count, the rows in groups, the error fields and the number of survivors come back in ONE small read.
 #include <algorithm>
@@ -29,7 +29,7 @@
 
 namespace cph {
 
-// kResRows / kResTile / kResWords / kResWaves and equal_flags: runs_device.hpp
+// kResRows / kResTile / kResWords / kResWaves and equal_flags: runs_device.hpp; the keep bitmap's layout: tile_bitmap.hpp
 constexpr uint32_t kNoPos = 0xFFFFFFFFu;
 
 enum : int { kOrdNone = 0, kOrdKey = 1, kOrdBytes = 2 };   // how k_resolve_tile orders the rows of a group
@@ -133,8 +133,8 @@ __device__ __forceinline__ Seg seg_shfl_up(const Seg& s, int d) {
     return r;
 }
 
-// bitmap[tile * 32 + w] bit b = sorted position tile * 2048 + 64 w + b survives (rows >= n: 0; the winners of runs that span
-// tiles are added by k_resolve_carry), counts[tile] = the tile's set bits, part[tile] = its open runs (ORD != kOrdNone).
+// bit = that sorted position survives (tile_bitmap.hpp; the winners of runs that span tiles are added by k_resolve_carry),
+// part[tile] = the tile's open runs (ORD != kOrdNone).
 // n >= 1; ORD == kOrdNone: rule is FIRST / LAST / DROP and nothing is scanned.
 template <bool KEY32, int ORD>
 __global__ __launch_bounds__(kMatThreads) void k_resolve_tile(const void* __restrict__ codes, uint64_t n, int nwords, int32_t rule, OrderArg ord,
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kMatThreads) void k_resolve_tile(const void* __rest
     __shared__ Seg s_wave[kResWaves];
     __shared__ TilePartial s_part;
     const int lane = lane_id(), wave = wave_id();
-    const uint64_t ntiles = (n + kResTile - 1) / kResTile;
+    const uint64_t ntiles = tile_count(n);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kResTile;
         const uint64_t tend = t0 + kResTile < n ? t0 + kResTile : n;   // one past the tile's last row
@@ -161,6 +161,7 @@ __global__ __launch_bounds__(kMatThreads) void k_resolve_tile(const void* __rest
         const uint32_t r0 = threadIdx.x * kResRows;   // the lane's first row inside the tile
         const uint64_t base = t0 + r0;
         const uint32_t e = base < n ? equal_flags<KEY32>(codes, n, nwords, base) : 0u;
+        // tile_live_rows(base, tend) spelled out: this kernel's register count moves with the shared function (profiles/tile_bitmap_refactor.txt)
         const uint32_t live = base >= tend ? 0u : (tend - base >= (uint64_t)kResRows ? (1u << kResRows) - 1 : (1u << (uint32_t)(tend - base)) - 1);
         const uint32_t eq_prev = e & live, eq_next = (e >> 1) & live;
         const uint32_t single = live & ~eq_prev & ~eq_next;
@@ -328,25 +329,10 @@ __global__ void k_resolve_finish(ResCounters* cnt, const uint32_t* __restrict__ 
 // offs[tile] = survivors in front of the tile; out[rank] = the sorted position
 __global__ __launch_bounds__(kMatThreads) void k_resolve_emit(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ offs,
                                                              uint64_t ntiles, uint64_t* __restrict__ out) {
-    const int lane = lane_id(), wave = wave_id();
-    constexpr int kWaveWords = kResWords / kResWaves;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t o0 = offs[tile], o1 = offs[tile + 1];
         if (o0 == o1) continue;   // uniform
-        const uint64_t word = lane < kResWords ? bitmap[tile * kResWords + lane] : 0;
-        const uint32_t pc = (uint32_t)__popcll(word);
-        const uint32_t before = wave_inclusive_sum(pc) - pc;
-#pragma unroll
-        for (int k = 0; k < kWaveWords; k++) {
-            const int w = wave * kWaveWords + k;
-            const uint32_t lo = __shfl((uint32_t)word, w, kWave), hi = __shfl((uint32_t)(word >> 32), w, kWave);
-            const uint32_t pre = __shfl(before, w, kWave);
-            const uint64_t bits = (uint64_t)lo | ((uint64_t)hi << 32);
-            if ((bits >> lane) & 1ull) {
-                const uint64_t rank = o0 + pre + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
-                out[rank] = tile * kResTile + (uint64_t)(w * 64 + lane);
-            }
-        }
+        tile_for_each_set(bitmap, tile, o0, [&](uint64_t rank, int r) { out[rank] = tile * kResTile + (uint64_t)r; });
     }
 }
 
@@ -363,16 +349,14 @@ struct cph_resolved_impl {
 
 namespace {
 
-unsigned resolve_grid(uint64_t ntiles) { return (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192); }
-
 template <int ORD>
 void launch_tile(cph_ctx* ctx, const cph_index* ix, int32_t rule, const OrderArg& ord, uint64_t ntiles, uint64_t* bitmap, uint32_t* counts,
                  TilePartial* part, ResCounters* cnt) {
     if (ix->codec.key32)
-        hipLaunchKernelGGL((k_resolve_tile<true, ORD>), dim3(resolve_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, ix->sorted_codes.get(),
+        hipLaunchKernelGGL((k_resolve_tile<true, ORD>), dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, ix->sorted_codes.get(),
                            ix->nrows, ix->total_words(), rule, ord, bitmap, counts, part, cnt);
     else
-        hipLaunchKernelGGL((k_resolve_tile<false, ORD>), dim3(resolve_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, ix->sorted_codes.get(),
+        hipLaunchKernelGGL((k_resolve_tile<false, ORD>), dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, ix->sorted_codes.get(),
                            ix->nrows, ix->total_words(), rule, ord, bitmap, counts, part, cnt);
 }
 
@@ -409,7 +393,6 @@ CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* ix, const cph_r
         const uint64_t n = ix->nrows;
         uint64_t kept = 0;
         if (n) {
-            const uint64_t ntiles = (n + kResTile - 1) / kResTile;
             const double cb = (double)index_code_bytes(ix);
             std::vector<DevBuf> staged;
             DevBuf values, status;
@@ -437,9 +420,10 @@ CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* ix, const cph_r
                     order_bytes = 9.0;
                 }
             }
-            DevBuf bitmap, counts, part, cnt;
-            CPH_TRY(bitmap.alloc(&ctx->pool, ntiles * kResWords * sizeof(uint64_t)));
-            CPH_TRY(counts.alloc(&ctx->pool, (ntiles + 1) * sizeof(uint32_t)));
+            TileBitmap tb;
+            CPH_TRY(tb.alloc(ctx, n));
+            const uint64_t ntiles = tb.ntiles;
+            DevBuf part, cnt;
             if (mode != kOrdNone) CPH_TRY(part.alloc(&ctx->pool, ntiles * sizeof(TilePartial)));
             CPH_TRY(cnt.alloc(&ctx->pool, sizeof(ResCounters)));
             {
@@ -454,9 +438,9 @@ CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* ix, const cph_r
             {
                 // byte model: the codes and the order values (or perm + offsets + ~8 string bytes) in, bitmap, counts and partials out
                 ProfScope ps(ctx, "k_resolve_tile", (double)n * (cb + order_bytes + 1.0 / 8.0) + (double)ntiles * (4.0 + (mode != kOrdNone ? (double)sizeof(TilePartial) : 0.0)));
-                if (mode == kOrdNone) launch_tile<kOrdNone>(ctx, ix, opts->rule, ord, ntiles, bitmap.as<uint64_t>(), counts.as<uint32_t>(), nullptr, cnt.as<ResCounters>());
-                else if (mode == kOrdKey) launch_tile<kOrdKey>(ctx, ix, opts->rule, ord, ntiles, bitmap.as<uint64_t>(), counts.as<uint32_t>(), part.as<TilePartial>(), cnt.as<ResCounters>());
-                else launch_tile<kOrdBytes>(ctx, ix, opts->rule, ord, ntiles, bitmap.as<uint64_t>(), counts.as<uint32_t>(), part.as<TilePartial>(), cnt.as<ResCounters>());
+                if (mode == kOrdNone) launch_tile<kOrdNone>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), nullptr, cnt.as<ResCounters>());
+                else if (mode == kOrdKey) launch_tile<kOrdKey>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), part.as<TilePartial>(), cnt.as<ResCounters>());
+                else launch_tile<kOrdBytes>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), part.as<TilePartial>(), cnt.as<ResCounters>());
             }
             CPH_HIP_TRY(hipGetLastError());
             if (mode != kOrdNone && ntiles > 1) {
@@ -464,17 +448,17 @@ CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* ix, const cph_r
                 const unsigned grid = (unsigned)std::min<uint64_t>((ntiles + kResWaves - 1) / kResWaves, 4096);
                 if (mode == kOrdKey)
                     hipLaunchKernelGGL(k_resolve_carry<kOrdKey>, dim3(grid), dim3(kMatThreads), 0, ctx->stream, part.as<TilePartial>(), ntiles, ord,
-                                       bitmap.as<unsigned long long>(), counts.as<uint32_t>());
+                                       tb.bitmap.as<unsigned long long>(), tb.counts());
                 else
                     hipLaunchKernelGGL(k_resolve_carry<kOrdBytes>, dim3(grid), dim3(kMatThreads), 0, ctx->stream, part.as<TilePartial>(), ntiles, ord,
-                                       bitmap.as<unsigned long long>(), counts.as<uint32_t>());
+                                       tb.bitmap.as<unsigned long long>(), tb.counts());
                 CPH_HIP_TRY(hipGetLastError());
             }
             hipLaunchKernelGGL(k_resolve_finish, dim3(1), dim3(kWave), 0, ctx->stream, cnt.as<ResCounters>(), ix->perm.as<uint32_t>(), n,
-                               opts->keep_last_row, bitmap.as<unsigned long long>(), counts.as<uint32_t>());
+                               opts->keep_last_row, tb.bitmap.as<unsigned long long>(), tb.counts());
             CPH_HIP_TRY(hipGetLastError());
-            CPH_TRY(exclusive_scan_u32_total(ctx, counts.as<uint32_t>(), ntiles, counts.as<uint32_t>() + ntiles));
-            CPH_HIP_TRY(hipMemcpyAsync(&cnt.as<ResCounters>()->total, counts.as<uint32_t>() + ntiles, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            CPH_TRY(tb.scan(ctx));
+            CPH_HIP_TRY(hipMemcpyAsync(&cnt.as<ResCounters>()->total, tb.total(), sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
             ResCounters got{};
             CPH_TRY(read_device_value(ctx, cnt.as<ResCounters>(), &got));   // the call's host wait
             r->pub.ngroups = got.ngroups;
@@ -490,8 +474,8 @@ CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* ix, const cph_r
             if (kept) {
                 CPH_TRY(r->d_pos.alloc(&ctx->pool, kept * sizeof(uint64_t)));
                 ProfScope ps(ctx, "k_resolve_emit", (double)n / 8.0 + 4.0 * (double)ntiles + 8.0 * (double)kept);
-                hipLaunchKernelGGL(k_resolve_emit, dim3(resolve_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, bitmap.as<uint64_t>(),
-                                   counts.as<uint32_t>(), ntiles, r->d_pos.as<uint64_t>());
+                hipLaunchKernelGGL(k_resolve_emit, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, tb.words(), tb.counts(), ntiles,
+                                   r->d_pos.as<uint64_t>());
                 CPH_HIP_TRY(hipGetLastError());
             }
         }

@@ -3,13 +3,16 @@
 #pragma once
 
 #include "numparse_device.hpp"
+#include "tile_bitmap.hpp"
 
 namespace cph {
 
-constexpr int kResRows  = 8;                          // consecutive rows per lane
-constexpr int kResTile  = kMatThreads * kResRows;     // 2048 rows = 32 bitmap words: tests/test_resolve.py and tests/test_totals.py call it T
-constexpr int kResWords = kResTile / 64;
-constexpr int kResWaves = kMatThreads / kWave;
+// the tile of tile_bitmap.hpp under the names of the run kernels
+constexpr int kResRows  = kTileLaneRows;              // consecutive rows per lane
+constexpr int kResTile  = kTileRows;                  // 2048 rows = 32 bitmap words: tests/test_resolve.py and tests/test_totals.py call it T
+constexpr int kResWords = kTileWords;
+constexpr int kResWaves = kTileWaves;
+static_assert(kMatThreads == kTileWaves * kWave, "one workgroup per tile");
 
 // e[j] (j = 0..kResRows) = sorted positions base + j - 1 and base + j exist and carry the same key
 template <bool KEY32>
