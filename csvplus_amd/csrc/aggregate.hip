@@ -361,6 +361,7 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* ix, const cph
         std::vector<DevBuf> staged;
         DevBuf values[CPH_AGG_MAX_SPECS], status[CPH_AGG_MAX_SPECS], uploaded[CPH_AGG_MAX_SPECS];
         const uint64_t* src[CPH_AGG_MAX_SPECS] = {nullptr};
+        NumColStats all;   // the col specs' reports, merged
         for (int32_t s = 0; s < nspecs; s++) {
             const cph_agg_spec& sp = specs[s];
             if (sp.col) {
@@ -371,23 +372,18 @@ CPH_API int32_t cph_index_aggregate(cph_ctx* ctx, const cph_index* ix, const cph
                 ids.bits = 32;
                 NumColStats st;
                 CPH_TRY(convert_rows(ctx, col, ids, 0, n, sp.kind, &values[s], &status[s], &st));
-                r->pub.host_rows += st.host_rows;
-                r->pub.nerrors += st.nerrors;
-                if (st.nerrors && st.first_error < r->pub.first_error_position) {   // ties: the lowest spec
-                    r->pub.first_error_position = st.first_error;
-                    r->pub.first_error_kind = st.first_kind;
-                    r->pub.first_error_spec = s;
-                }
+                all.merge(st, s);
                 src[s] = values[s].as<uint64_t>();
-            } else if (sp.numbers_mem == CPH_MEM_HOST) {
-                CPH_TRY(uploaded[s].alloc(&ctx->pool, (size_t)ix->table_rows * 8));
-                CPH_HIP_TRY(hipMemcpyAsync(uploaded[s].get(), sp.numbers, (size_t)ix->table_rows * 8, hipMemcpyHostToDevice, ctx->stream));
-                src[s] = uploaded[s].as<uint64_t>();
             } else {
-                src[s] = static_cast<const uint64_t*>(sp.numbers);
+                CPH_TRY(device_array(ctx, static_cast<const uint64_t*>(sp.numbers), sp.numbers_mem, (size_t)ix->table_rows, &uploaded[s], &src[s]));
             }
         }
-        if (r->pub.nerrors) {   // data, not a failure: no arrays
+        r->pub.host_rows = all.host_rows;
+        r->pub.nerrors = all.nerrors;
+        if (all.nerrors) {   // data, not a failure: no arrays
+            r->pub.first_error_position = all.first_error;
+            r->pub.first_error_kind = all.first_kind;
+            r->pub.first_error_spec = all.first_tag;
             uint32_t row = 0;
             CPH_TRY(read_device_value(ctx, perm + r->pub.first_error_position, &row));
             r->pub.first_error_row = row;

@@ -458,6 +458,25 @@ Status stage_cols(cph_ctx* ctx, const cph_strcol* cols, int32_t ncols, std::vect
     return {};
 }
 
+Status device_array(cph_ctx* ctx, const void* ptr, int32_t mem, size_t bytes, DevBuf* hold, const void** dev) {
+    *dev = ptr;
+    if (mem != CPH_MEM_HOST || !bytes) return {};
+    CPH_TRY(hold->alloc(&ctx->pool, bytes));
+    CPH_HIP_TRY(hipMemcpyAsync(hold->get(), ptr, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *dev = hold->get();
+    return {};
+}
+
+Status upload_block(cph_ctx* ctx, const void* src, size_t bytes, DevBuf* dst, size_t slack) {
+    CPH_TRY(dst->alloc(&ctx->pool, bytes + slack));
+    if (!bytes) return {};
+    void* slot = nullptr;
+    CPH_TRY(pinned_upload(ctx, bytes, &slot));   // ring slot: no synchronisation needed for the copy
+    memcpy(slot, src, bytes);
+    CPH_HIP_TRY(hipMemcpyAsync(dst->get(), slot, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return {};
+}
+
 Status check_row_sources(const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t first_row, uint64_t nrows, bool exact) {
     for (int c = 0; c < ncols; c++) {
         CPH_TRY(validate_cols(cols + c, 1));
@@ -937,13 +956,8 @@ CPH_API int32_t cph_join_probe(cph_ctx* ctx, const cph_index* ix, const cph_strc
         dsel.bits = sel_bits;
         dsel.base = sel_base;
         DevBuf selbuf;
-        const bool cols_on_host = probecols[0].mem == CPH_MEM_HOST;
-        if (row_sel && cols_on_host && nsel) {
-            const size_t sb = nsel * (size_t)(sel_bits / 8);
-            CPH_TRY(selbuf.alloc(&ctx->pool, sb));
-            CPH_HIP_TRY(hipMemcpyAsync(selbuf.get(), row_sel, sb, hipMemcpyHostToDevice, ctx->stream));
-            dsel.ptr = selbuf.get();
-        }
+        // the row ids live where the columns live
+        CPH_TRY(device_array(ctx, row_sel, probecols[0].mem, row_sel ? nsel * (size_t)(sel_bits / 8) : 0, &selbuf, &dsel.ptr));
         const uint64_t nprobe = row_sel ? nsel : probecols[0].nrows;
         ProbeOut po;
         CPH_TRY(probe_run(ctx, ix, dcols, nprobecols, dsel, nprobe, probe_base, want_pairs != 0, &po));

@@ -855,6 +855,23 @@ Status pinned_upload(cph_ctx* ctx, size_t bytes, void** out);   // staging slot 
 Status validate_cols(const cph_strcol* cols, int32_t ncols);
 // Makes columns device resident (host columns are copied into pool blocks kept alive by `storage`).
 Status stage_cols(cph_ctx* ctx, const cph_strcol* cols, int32_t ncols, std::vector<DevBuf>* storage, DevCol* out);
+// A caller's array in `mem` (CPH_MEM_HOST / CPH_MEM_DEVICE) for the kernels: *dev = ptr for device memory or no bytes (`hold` stays
+// empty); a host array is copied on ctx->stream into a pool block that `hold` keeps alive, and *dev points at it.
+Status device_array(cph_ctx* ctx, const void* ptr, int32_t mem, size_t bytes, DevBuf* hold, const void** dev);
+template <class T>
+Status device_array(cph_ctx* ctx, const T* ptr, int32_t mem, size_t count, DevBuf* hold, const T** dev) {
+    const void* d = nullptr;
+    CPH_TRY(device_array(ctx, static_cast<const void*>(ptr), mem, count * sizeof(T), hold, &d));
+    *dev = static_cast<const T*>(d);
+    return {};
+}
+// A small block the host has built, into a fresh pool block of bytes + slack: through a slot of the upload ring, on ctx->stream
+// (no wait).
+Status upload_block(cph_ctx* ctx, const void* src, size_t bytes, DevBuf* dst, size_t slack = 0);
+template <class T>
+Status upload_block(cph_ctx* ctx, const T& v, DevBuf* dst) {
+    return upload_block(ctx, &v, sizeof(T), dst);
+}
 // Row sources = columns read through optional row ids (cph_rowsel): what the gather, the writers and Filter take.
 // Per column: validate_cols | a column without ids has nrows rows (exact) or at least first_row + nrows | id bits 32 / 64.
 Status check_row_sources(const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t first_row, uint64_t nrows, bool exact);
@@ -977,6 +994,14 @@ struct NumColStats {
     uint64_t first_error = UINT64_MAX;   // relative to first_row; UINT64_MAX: no error
     int32_t first_kind = 0;
     uint64_t host_rows = 0;              // rows finished on the host
+    int32_t first_tag = 0;               // merge(): which of the merged reports holds the first error
+    // the report of several conversions over the same rows: the lowest row, ties to the lowest tag; the counts add up
+    void merge(const NumColStats& o, int32_t tag) {
+        if (o.nerrors && (!nerrors || o.first_error < first_error || (o.first_error == first_error && tag < first_tag)))
+            first_error = o.first_error, first_kind = o.first_kind, first_tag = tag;
+        nerrors += o.nerrors;
+        host_rows += o.host_rows;
+    }
 };
 Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t first_row, uint64_t n, int32_t kind, DevBuf* values,
                     DevBuf* status, NumColStats* st);

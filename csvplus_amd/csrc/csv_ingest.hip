@@ -1356,14 +1356,8 @@ static Status csv_fast_path(cph_ctx* ctx, cph_csv_table_impl* t, const uint8_t* 
     for (int c = 0; c < ncols; c++) fc.index[c] = col_index[c];
     DevBuf flags, ttot;
     const uint64_t narr = (uint64_t)ncols + 1;   // bytes per wanted column, newlines: per tile
-    CPH_TRY(flags.alloc(&ctx->pool, sizeof(FtFlags)));
+    CPH_TRY(upload_block(ctx, FtFlags{0u, 0xFFFFFFFFu, 0u, 0u}, &flags));
     CPH_TRY(ttot.alloc(&ctx->pool, (narr * ntiles + 1) * sizeof(uint64_t)));
-    {
-        void* up = nullptr;
-        CPH_TRY(pinned_upload(ctx, sizeof(FtFlags), &up));
-        *static_cast<FtFlags*>(up) = FtFlags{0u, 0xFFFFFFFFu, 0u, 0u};
-        CPH_HIP_TRY(hipMemcpyAsync(flags.get(), up, sizeof(FtFlags), hipMemcpyHostToDevice, ctx->stream));
-    }
     const size_t lds_count = (size_t)kFtStage + 16 + 3 * (size_t)(kFtStage / 16 + 8) * sizeof(uint16_t) + 16;
     const size_t lds_copy = lds_count + (size_t)kFtStage + 64;
     const uint64_t first_req = opt->skip_records;

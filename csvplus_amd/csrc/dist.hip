@@ -392,15 +392,9 @@ static Status exchange_counts(cph_dist* d, uint64_t count, uint64_t flag, uint64
     cph_ctx* ctx = d->ctx;
     const int n = d->t->size();
     DevBuf mine, all;
-    CPH_TRY(mine.alloc(&ctx->pool, 3 * sizeof(uint64_t)));
+    const uint64_t u[3] = {count, flag, base};
+    CPH_TRY(upload_block(ctx, u, sizeof u, &mine));
     CPH_TRY(all.alloc(&ctx->pool, 3 * sizeof(uint64_t) * (size_t)n));
-    void* up = nullptr;
-    CPH_TRY(pinned_upload(ctx, 3 * sizeof(uint64_t), &up));
-    uint64_t* u = static_cast<uint64_t*>(up);
-    u[0] = count;
-    u[1] = flag;
-    u[2] = base;
-    CPH_HIP_TRY(hipMemcpyAsync(mine.get(), up, 3 * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     CPH_TRY(d->t->allgather(mine.get(), all.get(), 3 * sizeof(uint64_t), ctx->stream));
     CPH_TRY(ensure_pinned_scratch(ctx, 3 * sizeof(uint64_t) * (size_t)n));
     CPH_HIP_TRY(hipMemcpyAsync(ctx->pinned_scratch, all.get(), 3 * sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1316,11 +1310,7 @@ CPH_API int32_t cph_dist_index_broadcast(cph_dist* d, const cph_index* root_inde
         std::vector<uint8_t> desc;
         if (is_root) index_desc_serialize(root_index, &desc);
         DevBuf dsz;
-        CPH_TRY(dsz.alloc(&ctx->pool, sizeof(uint64_t)));
-        void* up = nullptr;
-        CPH_TRY(pinned_upload(ctx, sizeof(uint64_t), &up));
-        *static_cast<uint64_t*>(up) = desc.size();
-        CPH_HIP_TRY(hipMemcpyAsync(dsz.get(), up, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        CPH_TRY(upload_block(ctx, (uint64_t)desc.size(), &dsz));
         CPH_TRY(d->t->broadcast(dsz.get(), sizeof(uint64_t), root, ctx->stream));
         uint64_t nbytes = 0;
         CPH_TRY(read_device_value(ctx, dsz.as<uint64_t>(), &nbytes));

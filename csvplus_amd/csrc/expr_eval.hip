@@ -9,8 +9,8 @@
 //                 string leaf is converted on the fly with numparse_device.hpp — span through the row ids, the value's first
 //                 16 bytes with two branch-free loads, the SWAR conversion — with its 4 rows' loads issued together; a
 //                 number leaf is a coalesced 8-byte load.  Values and status bytes leave as coalesced stores.  A wave that
-//                 saw an error adds its count and sends ONE 64-bit atomicMin of (row << 8 | op << 3 | kind); a wave that
-//                 deferred float rows adds their count.
+//                 saw an error adds its count and sends ONE 64-bit atomicMin (the report of num_report.hpp, tag = the op); a
+//                 wave that deferred float rows adds their count.
 //   The kernel is instantiated for stacks of 2, 4 and 8 values (the host knows the program's depth): the reference's own
 //   shape, COL_FLT COL_INT TO_FLT MUL, needs 2.
 //
@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "num_report.hpp"
 #include "numparse_device.hpp"
 
 #pragma clang fp contract(off)
@@ -34,8 +35,6 @@ namespace cph {
 constexpr int kExprRows  = 8;                           // rows per lane and tile
 constexpr int kExprPhase = 4;                           // ... of which this many are in flight at once
 constexpr int kExprTile  = kMatThreads * kExprRows;     // 2048 rows
-constexpr int kExprKeyShift = 8;                        // first_error = row << 8 | op << 3 | kind (op < 32, kind < 8)
-static_assert(CPH_EXPR_MAX_OPS <= 32 && CPH_NUM_ERR_CONVERT < 8, "the error key holds 5 op bits and 3 kind bits");
 
 struct ExprOp {          // one op as the kernel sees it
     int32_t op, arg;     // CPH_EXPR_*; COL_*: the column
@@ -46,8 +45,9 @@ struct ExprPlan {
     int32_t nops, pad_;
     ExprOp ops[CPH_EXPR_MAX_OPS];
 };
-struct ExprCounters {    // zeroed / preset by the host in front of k_expr_eval
-    unsigned long long nerrors, first_error, ndeferred;
+struct ExprCounters {    // preset by the host in front of k_expr_eval (ErrReport)
+    ErrWord err;         // first
+    unsigned long long ndeferred;
 };
 
 template <int D>
@@ -104,8 +104,8 @@ __global__ __launch_bounds__(kMatThreads) void k_expr_eval(ColsArg cols, ColIds 
     const uint64_t ntiles = (n + kExprTile - 1) / kExprTile;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kExprTile;
-        unsigned long long first = ~0ull;   // wave-uniform: the key of the wave's first error in this tile
-        uint32_t nerr = 0, ndef = 0;        // wave-uniform
+        WaveErr we;          // wave-uniform: the wave's errors in this tile
+        uint32_t ndef = 0;   // wave-uniform
 #pragma unroll 1
         for (int ph = 0; ph < kExprRows / kExprPhase; ph++) {
             uint64_t row[kExprPhase];       // rows past the end look at the last row; their result is dropped
@@ -215,25 +215,12 @@ __global__ __launch_bounds__(kMatThreads) void k_expr_eval(ColsArg cols, ColIds 
                     values[g0 + lane] = rst[k] == CPH_NUM_OK ? stk[0][k] : 0ull;
                     status[g0 + lane] = (uint8_t)rst[k];
                 }
-                const uint64_t bad = __ballot(live[k] && rst[k] != CPH_NUM_OK);
-                if (bad) {   // uniform
-                    const int fl = __builtin_ctzll(bad);
-                    const uint32_t tag = (rop[k] << 3) | rst[k];
-                    const unsigned long long key =
-                        ((unsigned long long)(g0 + (uint64_t)fl) << kExprKeyShift) | (unsigned long long)__shfl(tag, fl, kWave);
-                    if (key < first) first = key;
-                    nerr += (uint32_t)__popcll(bad);
-                }
+                we.note_ballot(__ballot(live[k] && rst[k] != CPH_NUM_OK), g0, err_tag_kind(rop[k], rst[k]));
                 ndef += (uint32_t)__popcll(__ballot(live[k] && deferred[k]));
             }
         }
-        if (lane == 0) {
-            if (nerr) {
-                atomicAdd(&cnt->nerrors, (unsigned long long)nerr);
-                atomicMin(&cnt->first_error, first);
-            }
-            if (ndef) atomicAdd(&cnt->ndeferred, (unsigned long long)ndef);
-        }
+        we.flush(&cnt->err);
+        if (lane == 0 && ndef) atomicAdd(&cnt->ndeferred, (unsigned long long)ndef);
     }
 }
 
@@ -299,31 +286,24 @@ Status check_program(const cph_expr_op* prog, int32_t nops, int32_t ncols, int32
 }
 
 Status launch_eval(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, const ExprPlan& plan, int depth, uint64_t n, double bytes, DevBuf* values,
-                   DevBuf* status, ExprCounters* got) {
-    DevBuf cnt;
-    CPH_TRY(cnt.alloc(&ctx->pool, sizeof(ExprCounters)));
-    {
-        void* slot = nullptr;
-        CPH_TRY(pinned_upload(ctx, sizeof(ExprCounters), &slot));
-        const ExprCounters zero{0ull, ~0ull, 0ull};
-        memcpy(slot, &zero, sizeof zero);
-        CPH_HIP_TRY(hipMemcpyAsync(cnt.get(), slot, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
-    }
+                   DevBuf* status, ErrFirst* err, ExprCounters* got) {
+    ErrReport<ExprCounters> cnt;
+    CPH_TRY(cnt.init(ctx));
     const dim3 grid(tile_grid((n + kExprTile - 1) / kExprTile));
     {
         ProfScope ps(ctx, "k_expr_eval", bytes);
         if (depth <= 2)
             hipLaunchKernelGGL(k_expr_eval<2>, grid, dim3(kMatThreads), 0, ctx->stream, arg, ids, plan, n, values->as<uint64_t>(),
-                               status->as<uint8_t>(), cnt.as<ExprCounters>());
+                               status->as<uint8_t>(), cnt.counters());
         else if (depth <= 4)
             hipLaunchKernelGGL(k_expr_eval<4>, grid, dim3(kMatThreads), 0, ctx->stream, arg, ids, plan, n, values->as<uint64_t>(),
-                               status->as<uint8_t>(), cnt.as<ExprCounters>());
+                               status->as<uint8_t>(), cnt.counters());
         else
             hipLaunchKernelGGL(k_expr_eval<CPH_EXPR_MAX_STACK>, grid, dim3(kMatThreads), 0, ctx->stream, arg, ids, plan, n,
-                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<ExprCounters>());
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.counters());
     }
     CPH_HIP_TRY(hipGetLastError());
-    return read_device_value(ctx, cnt.as<ExprCounters>(), got);   // the call's host wait
+    return cnt.read(ctx, err, got);   // the call's host wait
 }
 
 }  // namespace
@@ -380,12 +360,9 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
             dnums[k] = nums[k].ptr;
             bool used = false;
             for (int q = 0; q < nops; q++) used = used || ((prog[q].op == CPH_EXPR_NUM_INT || prog[q].op == CPH_EXPR_NUM_FLT) && prog[q].arg == k);
-            if (nums[k].mem == CPH_MEM_HOST && used) {   // staged like the row ids of a host column
-                staged.emplace_back();
-                CPH_TRY(staged.back().alloc(&ctx->pool, (size_t)n * 8));
-                CPH_HIP_TRY(hipMemcpyAsync(staged.back().get(), nums[k].ptr, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-                dnums[k] = staged.back().get();
-            }
+            if (!used) continue;
+            staged.emplace_back();   // staged like the row ids of a host column
+            CPH_TRY(device_array(ctx, nums[k].ptr, nums[k].mem, (size_t)n * 8, &staged.back(), &dnums[k]));
         }
         ExprPlan plan{};
         plan.nops = nops;
@@ -428,7 +405,8 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
         CPH_TRY(r->d_values.alloc(&ctx->pool, (size_t)n * 8));
         CPH_TRY(r->d_status.alloc(&ctx->pool, (size_t)n));
         ExprCounters got{};
-        CPH_TRY(launch_eval(ctx, arg, ids, plan, depth, n, (in_row + 9.0) * (double)n, &r->d_values, &r->d_status, &got));
+        ErrFirst err;
+        CPH_TRY(launch_eval(ctx, arg, ids, plan, depth, n, (in_row + 9.0) * (double)n, &r->d_values, &r->d_status, &err, &got));
         r->pub.host_rows = got.ndeferred;
         if (got.ndeferred && has_col) {
             // the plain route: every string leaf converted as cph_col_to_number converts it (one array per column and type),
@@ -457,14 +435,14 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
                 d.st = cs.as<uint8_t>();
                 row2 += 9.0;
             }
-            CPH_TRY(launch_eval(ctx, arg, ids, plan, depth, n, (row2 + 9.0) * (double)n, &r->d_values, &r->d_status, &got));
+            CPH_TRY(launch_eval(ctx, arg, ids, plan, depth, n, (row2 + 9.0) * (double)n, &r->d_values, &r->d_status, &err, &got));
             if (ctx->float_device) r->pub.host_rows = host_rows;
         }
-        r->pub.nerrors = got.nerrors;
-        if (got.nerrors) {
-            r->pub.first_error_row = got.first_error >> kExprKeyShift;
-            r->pub.first_error_kind = (int32_t)(got.first_error & 7ull);
-            if (first_error_op) *first_error_op = (int32_t)((got.first_error >> 3) & 31ull);
+        r->pub.nerrors = err.nerrors;
+        if (err.nerrors) {
+            r->pub.first_error_row = err.row;
+            r->pub.first_error_kind = err.kind;
+            if (first_error_op) *first_error_op = err.tag;
         }
         // the kernels read the staged arrays: they go back to the pool behind deliver's wait
         const ResultPart parts[2] = {{&r->d_values, (size_t)n * 8, &r->pub.values}, {&r->d_status, (size_t)n, &r->pub.status}};

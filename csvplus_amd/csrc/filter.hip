@@ -551,11 +551,7 @@ Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, cons
     if (!lits.empty()) {
         if (lits.size() > 0xFFFFFFFFull / 8) return {CPH_ERR_INVALID, "cph_filter_rows: literals beyond 4 GiB"};
         const size_t lb = lits.size() * sizeof(uint64_t);
-        CPH_TRY(bp->litbuf.alloc(&ctx->pool, lb));
-        void* slot = nullptr;
-        CPH_TRY(pinned_upload(ctx, lb, &slot));
-        memcpy(slot, lits.data(), lb);
-        CPH_HIP_TRY(hipMemcpyAsync(bp->litbuf.get(), slot, lb, hipMemcpyHostToDevice, ctx->stream));
+        CPH_TRY(upload_block(ctx, lits.data(), lb, &bp->litbuf));
         pp.lits = bp->litbuf.as<uint64_t>();
         pp.lit_words = (uint32_t)lits.size();
         pp.lits_in_lds = lb <= (size_t)kLitLds;
@@ -652,12 +648,8 @@ CPH_API int32_t cph_filter_rows(cph_ctx* ctx, const cph_strcol* cols, const cph_
         if (opts->mode != CPH_FILTER_WHERE) {
             BuiltProg bp;
             CPH_TRY(build_pred_prog(ctx, arg, ids, prog, nops, first_row, n, &fcols, &bp));
-            DevBuf ff;
-            CPH_TRY(ff.alloc(&ctx->pool, sizeof(uint64_t)));
-            void* slot = nullptr;
-            CPH_TRY(pinned_upload(ctx, sizeof(uint64_t), &slot));
-            memcpy(slot, &n, sizeof n);
-            CPH_HIP_TRY(hipMemcpyAsync(ff.get(), slot, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+            DevBuf ff;   // rows in front of the first failing one; n: none fails
+            CPH_TRY(upload_block(ctx, n, &ff));
             {
                 ProfScope ps(ctx, bp.strings ? "k_pred_eval_str" : "k_pred_eval", bp.col_bytes);
                 launch_pred_eval<false>(ctx, bp, arg, ids, first_row, n, ntiles, nullptr, nullptr, ff.as<unsigned long long>());
@@ -728,13 +720,7 @@ CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel
         const size_t lw = (size_t)(list->bits / 8);
         if (list->ids) {
             lst.bits = list->bits;
-            if (list->mem == CPH_MEM_HOST) {
-                CPH_TRY(lbuf.alloc(&ctx->pool, n * lw));
-                CPH_HIP_TRY(hipMemcpyAsync(lbuf.get(), list->ids, n * lw, hipMemcpyHostToDevice, ctx->stream));
-                lst.ptr = lbuf.get();
-            } else {
-                lst.ptr = list->ids;
-            }
+            CPH_TRY(device_array(ctx, list->ids, list->mem, n * lw, &lbuf, &lst.ptr));
         }
         if (ident) {   // a copy of the list in out_mem
             DevBuf copy;
@@ -764,10 +750,7 @@ CPH_API int32_t cph_rowsel_take(cph_ctx* ctx, const cph_rowsel* sel, int32_t sel
             } else {
                 CPH_TRY(read_device_value(ctx, static_cast<const uint64_t*>(list->ids) + (n - 1), &last));
             }
-            const size_t sb = (size_t)(last + 1) * (size_t)(sel->bits / 8);
-            CPH_TRY(sbuf.alloc(&ctx->pool, sb));
-            CPH_HIP_TRY(hipMemcpyAsync(sbuf.get(), sel->ids, sb, hipMemcpyHostToDevice, ctx->stream));
-            s.ptr = sbuf.get();
+            CPH_TRY(device_array(ctx, sel->ids, sel_mem, (size_t)(last + 1) * (size_t)(sel->bits / 8), &sbuf, &s.ptr));
         }
         DevBuf outb;
         CPH_TRY(outb.alloc(&ctx->pool, n * (size_t)(sel->bits / 8)));

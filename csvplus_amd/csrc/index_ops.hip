@@ -565,15 +565,15 @@ CPH_API int32_t cph_index_select(cph_ctx* ctx, const cph_index* ix, const uint64
     if (!nx) return fail_with(ctx, {CPH_ERR_NOMEM, "out of host memory"});
     auto run = [&]() -> Status {
         DevBuf pos, bad;
-        CPH_TRY(pos.alloc(&ctx->pool, n * sizeof(uint64_t)));
+        const uint64_t* dpos = nullptr;
+        CPH_TRY(device_array(ctx, positions, CPH_MEM_HOST, (size_t)n, &pos, &dpos));
         CPH_TRY(bad.alloc(&ctx->pool, sizeof(uint32_t)));
         CPH_HIP_TRY(hipMemsetAsync(bad.get(), 0, sizeof(uint32_t), ctx->stream));
-        if (n) CPH_HIP_TRY(hipMemcpyAsync(pos.get(), positions, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_select_check, dim3(grid_for_items(n)), dim3(256), 0, ctx->stream, pos.as<uint64_t>(), n, ix->nrows, bad.as<uint32_t>());
+        hipLaunchKernelGGL(k_select_check, dim3(grid_for_items(n)), dim3(256), 0, ctx->stream, dpos, n, ix->nrows, bad.as<uint32_t>());
         uint32_t isbad = 0;
         CPH_TRY(read_device_value(ctx, bad.as<uint32_t>(), &isbad));
         if (isbad) return {CPH_ERR_INVALID, "positions must be strictly ascending sorted positions of the index"};
-        return index_select_device(ctx, ix, pos.as<uint64_t>(), n, nx);
+        return index_select_device(ctx, ix, dpos, n, nx);
     };
     Status s = run();
     if (!s.ok()) {

@@ -26,13 +26,14 @@
 //                  column of such a table rides the sorted runs: Count = the run lengths, int Sum / Min / Max and float Min / Max
 //                  by the same segmented reduce (aggregate.hip's agg_join: the same results as the direct route, bit for bit).
 //                  Smaller calls keep the global atomics: two launches per column instead of a dozen.
-//   k_jt_errors    a non-zero status byte is DATA: counted, and the lowest (row, spec) kept with one 64-bit atomicMin.
+//   k_jt_errors    a non-zero status byte is DATA: counted, and the lowest (row, spec) kept (the report of num_report.hpp, tag = the spec).
 // Every launch goes on the ctx stream, scratch comes from the ctx pool; the call waits once for the error words and the
 // out-of-range flag, then hands the arrays over.
 #include <algorithm>
 #include <cstring>
 #include <new>
 
+#include "num_report.hpp"
 #include "runs_device.hpp"
 
 namespace cph {
@@ -47,6 +48,12 @@ enum { kJtOne = 0, kJtRaw = 1, kJtIntKey = 2, kJtFltKey = 3 };   // what a row c
 
 constexpr uint64_t kSign = 0x8000000000000000ull;
 constexpr uint64_t kGoNaN = 0x7FF8000000000001ull;
+
+struct JtFlags {     // what the call waits for once (ErrReport)
+    ErrWord err;     // first
+    uint32_t bad;    // a build_row outside the index
+    uint32_t pad_;
+};
 
 template <int OP>
 __host__ __device__ constexpr uint64_t jt_identity() { return OP == kJtMin ? ~0ull : 0ull; }
@@ -149,30 +156,19 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_decode(uint64_t* __restrict__
     }
 }
 
-// err[0] += status bytes != 0; err[1] = min over them of (m << 32 | spec << 8 | status): the lowest row, there the lowest spec
-// (the specs run one after the other, all through this word), and its kind.  n < 2^32.
-__global__ __launch_bounds__(kJtThreads) void k_jt_errors(const uint8_t* __restrict__ status, uint64_t n, uint32_t spec, uint64_t* __restrict__ err) {
+// The status bytes != 0 into *err: their number, and the lowest row, there the lowest spec (the specs run one after the other, all
+// through this word), and its kind.
+__global__ __launch_bounds__(kJtThreads) void k_jt_errors(const uint8_t* __restrict__ status, uint64_t n, uint32_t spec, ErrWord* __restrict__ err) {
     const uint64_t stride = (uint64_t)gridDim.x * kJtThreads;
     const uint64_t rounds = (n + stride - 1) / stride;
-    uint64_t first = ~0ull;
-    uint32_t mine = 0;
+    WaveErr we;
     for (uint64_t r = 0; r < rounds; r++) {
         const uint64_t m = r * stride + (uint64_t)blockIdx.x * kJtThreads + threadIdx.x;
         const uint32_t s = m < n ? status[m] : 0u;
-        if (s) {
-            mine++;
-            const uint64_t key = (m << 32) | ((uint64_t)spec << 8) | s;
-            first = key < first ? key : first;
-        }
+        if (s) we.note_lane(m, spec, s);
     }
-    const uint32_t total = wave_sum(mine);
-    if (total) {   // uniform
-        const uint64_t lo = wave_min(first);
-        if (lane_id() == 0) {
-            (void)atomicAdd(reinterpret_cast<unsigned long long*>(err), (unsigned long long)total);
-            (void)atomicMin(reinterpret_cast<unsigned long long*>(err + 1), (unsigned long long)lo);
-        }
-    }
+    we.reduce();
+    we.flush(err);
 }
 
 // keys[m] = rows[m] clamped below ngroups (a row outside raises *bad): what the sort route sorts, so that its runs stay <= ngroups
@@ -374,36 +370,19 @@ CPH_API int32_t cph_chain_aggregate(cph_ctx* ctx, const cph_chain* chain, int32_
         const uint32_t* rows = chain->build_row[step];
         const uint64_t* vals[CPH_AGG_MAX_SPECS] = {nullptr};
         const uint8_t* status[CPH_AGG_MAX_SPECS] = {nullptr};
-        if (n && chain->mem == CPH_MEM_HOST) {
-            CPH_TRY(up_rows.alloc(&ctx->pool, n * sizeof(uint32_t)));
-            CPH_HIP_TRY(hipMemcpyAsync(up_rows.get(), rows, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            rows = up_rows.as<uint32_t>();
-        }
-        for (int32_t s = 0; s < nspecs; s++) {
+        CPH_TRY(device_array(ctx, chain->build_row[step], chain->mem, (size_t)n, &up_rows, &rows));
+        for (int32_t s = 0; s < nspecs; s++) {   // a spec's status bytes lie where its numbers lie
             const cph_chain_agg_spec& sp = specs[s];
-            vals[s] = static_cast<const uint64_t*>(sp.numbers);
-            status[s] = sp.status;
-            if (!n || sp.numbers_mem != CPH_MEM_HOST) continue;
-            CPH_TRY(up_vals[s].alloc(&ctx->pool, n * 8));
-            CPH_HIP_TRY(hipMemcpyAsync(up_vals[s].get(), sp.numbers, n * 8, hipMemcpyHostToDevice, ctx->stream));
-            vals[s] = up_vals[s].as<uint64_t>();
-            if (sp.status) {
-                CPH_TRY(up_status[s].alloc(&ctx->pool, n));
-                CPH_HIP_TRY(hipMemcpyAsync(up_status[s].get(), sp.status, n, hipMemcpyHostToDevice, ctx->stream));
-                status[s] = up_status[s].as<uint8_t>();
-            }
+            CPH_TRY(device_array(ctx, static_cast<const uint64_t*>(sp.numbers), sp.numbers_mem, (size_t)n, &up_vals[s], &vals[s]));
+            CPH_TRY(device_array(ctx, sp.status, sp.numbers_mem, sp.status ? (size_t)n : 0, &up_status[s], &status[s]));
         }
-        // flags[0] = error count, flags[1] = lowest (row, spec, kind), flags[2] (low half) = a build_row outside the index
-        DevBuf flags;
-        CPH_TRY(flags.alloc(&ctx->pool, 3 * sizeof(uint64_t)));
-        uint64_t* d_flags = flags.as<uint64_t>();
-        uint32_t* d_bad = reinterpret_cast<uint32_t*>(d_flags + 2);
-        CPH_HIP_TRY(hipMemsetAsync(d_flags, 0, 3 * sizeof(uint64_t), ctx->stream));
-        CPH_HIP_TRY(hipMemsetAsync(d_flags + 1, 0xFF, sizeof(uint64_t), ctx->stream));
+        ErrReport<JtFlags> flags;
+        CPH_TRY(flags.init(ctx));
+        uint32_t* d_bad = &flags.counters()->bad;
         for (int32_t s = 0; s < nspecs && n; s++) {
             if (!status[s]) continue;
             ProfScope ps(ctx, "k_jt_errors", (double)n);
-            hipLaunchKernelGGL(k_jt_errors, dim3(grid_for_items(n, 2048)), dim3(kJtThreads), 0, ctx->stream, status[s], n, (uint32_t)s, d_flags);
+            hipLaunchKernelGGL(k_jt_errors, dim3(grid_for_items(n, 2048)), dim3(kJtThreads), 0, ctx->stream, status[s], n, (uint32_t)s, flags.word());
             CPH_HIP_TRY(hipGetLastError());
         }
         bool has_fsum = false;
@@ -464,18 +443,16 @@ CPH_API int32_t cph_chain_aggregate(cph_ctx* ctx, const cph_chain* chain, int32_
             CPH_TRY(reduce_runs(specs[s].op, flt, vals[s], table));
         }
         // the call's host wait
-        CPH_TRY(ensure_pinned_scratch(ctx, 3 * sizeof(uint64_t)));
-        CPH_HIP_TRY(hipMemcpyAsync(ctx->pinned_scratch, d_flags, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        CPH_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        uint64_t h[3];
-        memcpy(h, ctx->pinned_scratch, sizeof h);
-        if ((uint32_t)h[2])
+        JtFlags got{};
+        ErrFirst e;
+        CPH_TRY(flags.read(ctx, &e, &got));
+        if (got.bad)
             return {CPH_ERR_INVALID, "cph_chain_aggregate: a build_row of the chain is not below the index's row count (not the chain step's index?)"};
-        if (h[0]) {   // data, not a failure: no arrays
-            r->pub.nerrors = h[0];
-            r->pub.first_error_row = h[1] >> 32;
-            r->pub.first_error_spec = (int32_t)((h[1] >> 8) & 0xFFFFFFu);
-            r->pub.first_error_kind = (int32_t)(h[1] & 0xFFu);
+        if (e.nerrors) {   // data, not a failure: no arrays
+            r->pub.nerrors = e.nerrors;
+            r->pub.first_error_row = e.row;
+            r->pub.first_error_spec = e.tag;
+            r->pub.first_error_kind = e.kind;
             r->d_cnt.reset();
             for (int32_t s = 0; s < nspecs; s++) r->d_val[s].reset();
             return {};

@@ -377,11 +377,7 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
         uint64_t total = 0;
         if (n) {
             DevBuf kbuf, offs, eflags;
-            CPH_TRY(kbuf.alloc(&ctx->pool, frags.size() + 16));
-            void* slot = nullptr;
-            CPH_TRY(pinned_upload(ctx, frags.size(), &slot));
-            memcpy(slot, frags.data(), frags.size());
-            CPH_HIP_TRY(hipMemcpyAsync(kbuf.get(), slot, frags.size(), hipMemcpyHostToDevice, ctx->stream));
+            CPH_TRY(upload_block(ctx, frags.data(), frags.size(), &kbuf, 16));
             keys.bytes = kbuf.as<uint8_t>();
             CPH_TRY(offs.alloc(&ctx->pool, (n + 1) * sizeof(uint64_t)));
             CPH_TRY(eflags.alloc(&ctx->pool, (n + 1) * sizeof(uint16_t)));
@@ -400,11 +396,7 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
             }
             CPH_HIP_TRY(hipGetLastError());
         } else {   // no rows: "[]"
-            CPH_TRY(r->d_data.alloc(&ctx->pool, 2 + 16));
-            void* slot = nullptr;
-            CPH_TRY(pinned_upload(ctx, 2, &slot));
-            memcpy(slot, "[]", 2);
-            CPH_HIP_TRY(hipMemcpyAsync(r->d_data.get(), slot, 2, hipMemcpyHostToDevice, ctx->stream));
+            CPH_TRY(upload_block(ctx, "[]", 2, &r->d_data, 16));
         }
         r->pub.size = total + 2;
         r->pub.mem = out_mem;

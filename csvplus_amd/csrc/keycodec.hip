@@ -639,11 +639,7 @@ Status codec_try_groups(cph_ctx* ctx, const DevCol* cols, int32_t ncols, uint64_
     CPH_TRY(slots.alloc(&ctx->pool, (size_t)nt * kGroupSlots * sizeof(uint64_t)));
     CPH_TRY(counts.alloc(&ctx->pool, (size_t)nt * sizeof(uint32_t)));
     CPH_TRY(singles.alloc(&ctx->pool, (size_t)nt * sizeof(uint32_t)));
-    CPH_TRY(tabs_dev.alloc(&ctx->pool, (size_t)nt * sizeof(uint32_t)));
-    void* up = nullptr;
-    CPH_TRY(pinned_upload(ctx, (size_t)nt * sizeof(uint32_t), &up));
-    memcpy(up, tabs.data(), (size_t)nt * sizeof(uint32_t));
-    CPH_HIP_TRY(hipMemcpyAsync(tabs_dev.get(), up, (size_t)nt * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    CPH_TRY(upload_block(ctx, tabs.data(), (size_t)nt * sizeof(uint32_t), &tabs_dev));
     const uint64_t nsel = (n + step - 1) / step;
     StageArg st{};
     st.ncols = cd.ncols;
@@ -2035,12 +2031,7 @@ Status codec_upload(cph_ctx* ctx, const CodecHost& cd, DevBuf* dev) {
             memcpy(blob.data() + h.lut_off, cd.lut.data(), sizeof(uint16_t) * (size_t)cd.npos * kLutStride);
         }
     }
-    CPH_TRY(dev->alloc(&ctx->pool, off));
-    void* slot = nullptr;
-    CPH_TRY(pinned_upload(ctx, off, &slot));   // ring slot: no synchronisation needed for the copy
-    memcpy(slot, blob.data(), off);
-    CPH_HIP_TRY(hipMemcpyAsync(dev->get(), slot, off, hipMemcpyHostToDevice, ctx->stream));
-    return {};
+    return upload_block(ctx, blob.data(), off, dev);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -97,12 +97,8 @@ inline Status append_map_pieces(cph_ctx* ctx, const cph_map_piece* pieces, int32
         } else {   // INT64 / FLOAT64 / TIME: 8 bytes per row
             const void* vals = p.kind == CPH_MAP_FLOAT64 ? static_cast<const void*>(p.floats) : static_cast<const void*>(p.ints);
             b->in_bytes += 8.0;
-            if (p.arg == CPH_MEM_HOST) {
-                staged->emplace_back();
-                CPH_TRY(staged->back().alloc(&ctx->pool, n * sizeof(int64_t)));
-                CPH_HIP_TRY(hipMemcpyAsync(staged->back().get(), vals, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-                vals = staged->back().get();
-            }
+            staged->emplace_back();
+            CPH_TRY(device_array(ctx, vals, p.arg, n * sizeof(int64_t), &staged->back(), &vals));
             if (p.kind == CPH_MAP_FLOAT64) d.floats = static_cast<const double*>(vals);
             else d.ints = static_cast<const int64_t*>(vals);
             if (p.kind != CPH_MAP_INT64) d.col = p.prec;   // FLOAT64: prec; TIME: the zone
@@ -114,14 +110,7 @@ inline Status append_map_pieces(cph_ctx* ctx, const cph_map_piece* pieces, int32
 
 // The literal block on the device (16 bytes of slack: the kernels read it 8 bytes at a time).
 inline Status upload_map_literals(cph_ctx* ctx, const std::string& lits, DevBuf* litbuf) {
-    CPH_TRY(litbuf->alloc(&ctx->pool, lits.size() + 16));
-    if (!lits.empty()) {
-        void* slot = nullptr;
-        CPH_TRY(pinned_upload(ctx, lits.size(), &slot));
-        memcpy(slot, lits.data(), lits.size());
-        CPH_HIP_TRY(hipMemcpyAsync(litbuf->get(), slot, lits.size(), hipMemcpyHostToDevice, ctx->stream));
-    }
-    return {};
+    return upload_block(ctx, lits.data(), lits.size(), litbuf, 16);
 }
 
 // The row's value of an INT64 / FLOAT64 / TIME piece, from whichever memory space holds it.

@@ -8,8 +8,8 @@
 //   k_num_parse    rows on lanes (row = tile + 64 k + lane, 8 rows per lane and tile, 4 in flight, the geometry of
 //                  k_pred_eval): span -> the value's first 16 bytes with two branch-free loads -> the SWAR conversion of
 //                  numparse_device.hpp.  Values and status bytes leave as coalesced stores.  A wave that saw an error
-//                  adds its count and sends ONE 64-bit atomicMin of (row << 2 | kind), so the first error row and its
-//                  kind arrive together; a wave that deferred float rows adds their count.
+//                  adds its count and sends ONE 64-bit atomicMin (the report of num_report.hpp, tag = 0), so the first
+//                  error row and its kind arrive together; a wave that deferred float rows adds their count.
 //                  The time instantiation (CPH_NUM_TIME_UNIX / CPH_NUM_TIME_UNIXNANO: RFC 3339 text -> t.Unix() / t.UnixNano(),
 //                  timeparse_device.hpp) loads bytes 16..31 with two more unbranched loads per row, issued for the phase's rows
 //                  together; it defers nothing.
@@ -34,6 +34,7 @@
 #include <locale.h>
 
 #include "floatparse_device.hpp"
+#include "num_report.hpp"
 #include "numparse_device.hpp"
 #include "timeparse_device.hpp"
 
@@ -70,8 +71,9 @@ constexpr int kNumTile  = kMatThreads * kNumRows;     // 2048 rows
 constexpr int kNumWaveRows = kNumRows;                // 64-row groups per wave and tile
 constexpr uint32_t kSlotBytes = 104;                  // value bytes a deferred row's slot holds
 
-struct NumCounters {   // zeroed / preset by the host in front of k_num_parse
-    unsigned long long nerrors, first_error, ndeferred, collected;
+struct NumCounters {   // preset by the host in front of k_num_parse (ErrReport)
+    ErrWord err;       // first
+    unsigned long long ndeferred, collected;
 };
 struct NumSlot {       // one deferred row on its way to the host
     uint64_t pos, begin, len;
@@ -111,8 +113,8 @@ __global__ __launch_bounds__(kMatThreads) void k_num_parse(DevCol col, RowIds ri
     const uint64_t ntiles = (n + kNumTile - 1) / kNumTile;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kNumTile;
-        unsigned long long first = ~0ull;   // wave-uniform: (row << 2 | kind) of the wave's first error in this tile
-        uint32_t nerr = 0, ndef = 0;        // wave-uniform
+        WaveErr we;          // wave-uniform: the wave's errors in this tile
+        uint32_t ndef = 0;   // wave-uniform
 #pragma unroll
         for (int ph = 0; ph < kNumRows / kNumPhase; ph++) {
             uint64_t b[kNumPhase], l[kNumPhase], c0[kNumPhase], c1[kNumPhase];
@@ -153,23 +155,12 @@ __global__ __launch_bounds__(kMatThreads) void k_num_parse(DevCol col, RowIds ri
                     values[g0 + lane] = bits;
                     status[g0 + lane] = (uint8_t)st;
                 }
-                const uint64_t bad = __ballot(live[k] && st != CPH_NUM_OK && st != kNumDeferred);
-                if (bad) {   // uniform
-                    const int fl = __builtin_ctzll(bad);
-                    const unsigned long long key = ((unsigned long long)(g0 + (uint64_t)fl) << 2) | (unsigned long long)__shfl(st, fl, kWave);
-                    if (key < first) first = key;
-                    nerr += (uint32_t)__popcll(bad);
-                }
+                we.note_ballot(__ballot(live[k] && st != CPH_NUM_OK && st != kNumDeferred), g0, err_tag_kind(0u, st));
                 if constexpr (FLT) ndef += (uint32_t)__popcll(__ballot(live[k] && st == kNumDeferred));
             }
         }
-        if (lane == 0) {
-            if (nerr) {
-                atomicAdd(&cnt->nerrors, (unsigned long long)nerr);
-                atomicMin(&cnt->first_error, first);
-            }
-            if (ndef) atomicAdd(&cnt->ndeferred, (unsigned long long)ndef);
-        }
+        we.flush(&cnt->err);
+        if (lane == 0 && ndef) atomicAdd(&cnt->ndeferred, (unsigned long long)ndef);
     }
 }
 
@@ -244,15 +235,8 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
     const bool tim = kind == CPH_NUM_TIME_UNIX || kind == CPH_NUM_TIME_UNIXNANO;
     CPH_TRY(values->alloc(&ctx->pool, (size_t)n * 8));
     CPH_TRY(status->alloc(&ctx->pool, (size_t)n));
-    DevBuf cnt;
-    CPH_TRY(cnt.alloc(&ctx->pool, sizeof(NumCounters)));
-    {
-        void* slot = nullptr;
-        CPH_TRY(pinned_upload(ctx, sizeof(NumCounters), &slot));
-        const NumCounters zero{0ull, ~0ull, 0ull, 0ull};
-        memcpy(slot, &zero, sizeof zero);
-        CPH_HIP_TRY(hipMemcpyAsync(cnt.get(), slot, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
-    }
+    ErrReport<NumCounters> cnt;
+    CPH_TRY(cnt.init(ctx));
     const uint64_t ntiles = (n + kNumTile - 1) / kNumTile;
     {
         // byte model: offsets (or nothing for a fixed width) + row ids + ~8 value bytes in, 9 bytes out per row
@@ -264,25 +248,24 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
                      (in_row + in_time + 9.0) * (double)n);
         if (tim)
             hipLaunchKernelGGL(k_num_parse<kParseTime>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
-                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), kind == CPH_NUM_TIME_UNIXNANO ? 1u : 0u);
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.counters(), kind == CPH_NUM_TIME_UNIXNANO ? 1u : 0u);
         else if (full)
             hipLaunchKernelGGL(k_num_parse<kParseFloatFull>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
-                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.counters(), 0u);
         else if (flt)
             hipLaunchKernelGGL(k_num_parse<kParseFloat>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
-                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.counters(), 0u);
         else
             hipLaunchKernelGGL(k_num_parse<kParseInt>, dim3(tile_grid(ntiles)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n,
-                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.as<NumCounters>(), 0u);
+                               values->as<uint64_t>(), status->as<uint8_t>(), cnt.counters(), 0u);
     }
     CPH_HIP_TRY(hipGetLastError());
     NumCounters got{};
-    CPH_TRY(read_device_value(ctx, cnt.as<NumCounters>(), &got));   // the call's host wait
-    st->nerrors = got.nerrors;
-    if (got.nerrors) {
-        st->first_error = got.first_error >> 2;
-        st->first_kind = (int32_t)(got.first_error & 3ull);
-    }
+    ErrFirst e;
+    CPH_TRY(cnt.read(ctx, &e, &got));   // the call's host wait
+    st->nerrors = e.nerrors;
+    st->first_error = e.row;
+    st->first_kind = e.kind;
     st->host_rows = got.ndeferred;
     if (!got.ndeferred) return {};
 
@@ -291,7 +274,7 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
     DevBuf slots;
     CPH_TRY(slots.alloc(&ctx->pool, (size_t)nd * sizeof(NumSlot)));
     hipLaunchKernelGGL(k_num_collect, dim3(grid_rows(n)), dim3(kMatThreads), 0, ctx->stream, col, ids, first_row, n, status->as<uint8_t>(),
-                       cnt.as<NumCounters>(), slots.as<NumSlot>(), nd);
+                       cnt.counters(), slots.as<NumSlot>(), nd);
     CPH_HIP_TRY(hipGetLastError());
     std::vector<NumSlot> hs((size_t)nd);
     CPH_HIP_TRY(hipMemcpyAsync(hs.data(), slots.get(), (size_t)nd * sizeof(NumSlot), hipMemcpyDeviceToHost, ctx->stream));

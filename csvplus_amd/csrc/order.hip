@@ -3,8 +3,8 @@
 // integer of the same order, and the stable LSD radix sort of the index build (radix_sort.hip) does the rest:
 //
 //   k_order_key_i64 / _f64   one pass per number key: value -> order_key64 (order_device.hpp) by selection position; the rows
-//                            whose status byte is not OK are counted and the lowest (row, key) is kept (integer atomics, one
-//                            pair per wave).
+//                            whose status byte is not OK are counted and the lowest (row, key) is kept (the report of
+//                            num_report.hpp, tag = the key).
 //   k_order_key_rank         a BYTES key: the index's run starts (k_agg_heads, aggregate.hip) and their scan give every sorted
 //                            position the DENSE RANK of its run (the reverse lookup of tile_bitmap.hpp); key[perm[p]] = rank
 //                            (ngroups - 1 - rank when descending):
@@ -27,6 +27,7 @@
 #include <cstring>
 #include <new>
 
+#include "num_report.hpp"
 #include "order_device.hpp"
 #include "runs_device.hpp"
 
@@ -38,10 +39,6 @@ namespace cph {
 // the candidates' side (one gather per key), which was not recorded.
 constexpr uint64_t kSelectGate = 4;
 
-struct OrderErr {                 // device accumulator of the key passes
-    unsigned long long nerrors;
-    unsigned long long first;     // row << 11 | key << 8 | status byte; ~0: none
-};
 struct SelectState {              // device: what one select pass leaves for the next
     unsigned long long prefix;    // the threshold's digits chosen so far (lower bits 0)
     unsigned long long rank;      // wanted ascending rank among the rows that match the prefix
@@ -50,27 +47,19 @@ struct SelectState {              // device: what one select pass leaves for the
 template <bool FLT>
 __global__ __launch_bounds__(kMatThreads) void k_order_key_num(const uint64_t* __restrict__ values, const uint8_t* __restrict__ status, uint64_t n,
                                                               uint32_t descending, uint32_t key_index, uint64_t* __restrict__ out,
-                                                              OrderErr* __restrict__ err) {
+                                                              ErrWord* __restrict__ err) {
     const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;
-    unsigned long long nerr = 0, first = ~0ull;
+    WaveErr we;
     for (uint64_t i = (uint64_t)blockIdx.x * kMatThreads + threadIdx.x; i < n; i += stride) {
         out[i] = order_key64(values[i], FLT, descending != 0);
         if (status) {
             const uint32_t st = status[i];
-            if (st != CPH_NUM_OK) {
-                nerr++;
-                const unsigned long long e = ((unsigned long long)i << 11) | ((unsigned long long)key_index << 8) | st;
-                first = e < first ? e : first;
-            }
+            if (st != CPH_NUM_OK) we.note_lane(i, key_index, st);
         }
     }
     if (status) {   // uniform
-        nerr = wave_sum(nerr);
-        first = wave_min(first);
-        if (lane_id() == 0 && nerr) {
-            atomicAdd(&err->nerrors, nerr);
-            atomicMin(&err->first, first);
-        }
+        we.reduce();
+        we.flush(err);
     }
 }
 
@@ -263,20 +252,12 @@ Status check_keys(const cph_order_key* keys, int32_t nkeys, uint64_t nrows) {
 }
 
 // A number key: values (and status) made device resident, mapped into dk->buf.
-Status key_pass_number(cph_ctx* ctx, const cph_order_key& key, int32_t k, uint64_t n, DevKey* dk, OrderErr* d_err) {
+Status key_pass_number(cph_ctx* ctx, const cph_order_key& key, int32_t k, uint64_t n, DevKey* dk, ErrWord* d_err) {
     DevBuf up_values, up_status;
-    const uint64_t* values = static_cast<const uint64_t*>(key.values);
-    const uint8_t* status = key.status;
-    if (key.values_mem == CPH_MEM_HOST) {
-        CPH_TRY(up_values.alloc(&ctx->pool, (size_t)n * 8));
-        CPH_HIP_TRY(hipMemcpyAsync(up_values.get(), key.values, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        values = up_values.as<uint64_t>();
-        if (key.status) {
-            CPH_TRY(up_status.alloc(&ctx->pool, (size_t)n));
-            CPH_HIP_TRY(hipMemcpyAsync(up_status.get(), key.status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            status = up_status.as<uint8_t>();
-        }
-    }
+    const uint64_t* values = nullptr;
+    const uint8_t* status = nullptr;   // lies where the values lie
+    CPH_TRY(device_array(ctx, static_cast<const uint64_t*>(key.values), key.values_mem, (size_t)n, &up_values, &values));
+    CPH_TRY(device_array(ctx, key.status, key.values_mem, key.status ? (size_t)n : 0, &up_status, &status));
     CPH_TRY(dk->buf.alloc(&ctx->pool, (size_t)n * 8));
     dk->wide = true;
     dk->bits = 64;
@@ -372,14 +353,9 @@ Status select_candidates(cph_ctx* ctx, const DevKey& dk, uint64_t n, uint64_t wa
     const K* keys = dk.buf.as<K>();
     const int npass = (dk.bits + 7) / 8;   // >= 1: the caller skips a key of 0 bits
     DevBuf state, hist;
-    CPH_TRY(state.alloc(&ctx->pool, sizeof(SelectState)));
+    CPH_TRY(upload_block(ctx, SelectState{0ull, (unsigned long long)(want - 1)}, &state));
     CPH_TRY(hist.alloc(&ctx->pool, (size_t)npass * 256 * sizeof(uint32_t)));
     CPH_HIP_TRY(hipMemsetAsync(hist.get(), 0, (size_t)npass * 256 * sizeof(uint32_t), ctx->stream));
-    void* up = nullptr;
-    CPH_TRY(pinned_upload(ctx, sizeof(SelectState), &up));
-    const SelectState init{0ull, (unsigned long long)(want - 1)};
-    memcpy(up, &init, sizeof init);
-    CPH_HIP_TRY(hipMemcpyAsync(state.get(), up, sizeof init, hipMemcpyHostToDevice, ctx->stream));
     constexpr int NV = sizeof(K) == 8 ? 2 : 4;
     for (int p = 0; p < npass; p++) {
         const int shift = 8 * (npass - 1 - p);
@@ -442,26 +418,22 @@ CPH_API int32_t cph_order_rows(cph_ctx* ctx, const cph_order_key* keys, int32_t 
         if (!n) return {};
         // ---- key pass ----
         DevKey dkeys[CPH_ORDER_MAX_KEYS];
-        DevBuf err;
+        ErrReport<> err;
         bool any_status = false;
         for (int32_t k = 0; k < nkeys; k++) any_status = any_status || (keys[k].kind != CPH_ORDER_BYTES && keys[k].status);
-        if (any_status) {
-            CPH_TRY(err.alloc(&ctx->pool, sizeof(OrderErr)));
-            CPH_HIP_TRY(hipMemsetAsync(err.get(), 0, 8, ctx->stream));
-            CPH_HIP_TRY(hipMemsetAsync(err.as<uint8_t>() + 8, 0xFF, 8, ctx->stream));
-        }
+        if (any_status) CPH_TRY(err.init(ctx));
         for (int32_t k = 0; k < nkeys; k++) {
             if (keys[k].kind == CPH_ORDER_BYTES) CPH_TRY(key_pass_bytes(ctx, keys[k], n, &dkeys[k]));
-            else CPH_TRY(key_pass_number(ctx, keys[k], k, n, &dkeys[k], err.as<OrderErr>()));
+            else CPH_TRY(key_pass_number(ctx, keys[k], k, n, &dkeys[k], err.word()));
         }
         if (any_status) {
-            OrderErr e{};
-            CPH_TRY(read_device_value(ctx, err.as<OrderErr>(), &e));
+            ErrFirst e;
+            CPH_TRY(err.read(ctx, &e));
             if (e.nerrors) {   // data, not a failure: no ids
                 r->pub.nerrors = e.nerrors;
-                r->pub.first_error_row = e.first >> 11;
-                r->pub.first_error_key = (int32_t)((e.first >> 8) & 7u);
-                r->pub.first_error_kind = (int32_t)(e.first & 0xFFu);
+                r->pub.first_error_row = e.row;
+                r->pub.first_error_key = e.tag;
+                r->pub.first_error_kind = e.kind;
                 return {};
             }
         }

@@ -25,6 +25,7 @@
 #include <cstring>
 #include <new>
 
+#include "num_report.hpp"
 #include "runs_device.hpp"
 
 namespace cph {
@@ -40,9 +41,10 @@ struct Best {
     uint64_t key;
     uint32_t pos;
 };
-struct ResCounters {   // zeroed / preset by the host in front of k_resolve_tile
-    unsigned long long ngroups, group_rows, nerrors, first_error;   // first_error = (position << 2 | kind), ~0: none
-    unsigned long long first_error_row;
+struct ResCounters {   // preset by the host in front of k_resolve_tile (ErrReport)
+    ErrWord err;           // first; its row = the sorted position, tag = 0
+    unsigned long long ngroups, group_rows;
+    unsigned long long first_error_row;   // k_resolve_finish: perm[that position], ~0: none
     uint32_t last_single;   // the final sorted row is not inside a group
     uint32_t total;         // surviving rows (copied in behind the scan)
 };
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(kMatThreads) void k_resolve_tile(const void* __rest
                         self.key = order_key(ord.values[base + (uint64_t)k], st, ord);
                         if (st != CPH_NUM_OK && (((eq_prev | eq_next) >> k) & 1u)) {
                             nerr++;
-                            const unsigned long long key = ((unsigned long long)(base + (uint64_t)k) << 2) | (unsigned long long)(st & 3u);
+                            const unsigned long long key = err_pack(base + (uint64_t)k, 0u, st);
                             if (key < first_err) first_err = key;
                         }
                     }
@@ -256,7 +258,7 @@ __global__ __launch_bounds__(kMatThreads) void k_resolve_tile(const void* __rest
             if (grows) atomicAdd(&s_cnt[1], grows);
             if (nerr) {
                 atomicAdd(&s_cnt[2], nerr);
-                atomicMin(&cnt->first_error, first_err);
+                atomicMin(&cnt->err.first, first_err);
             }
         }
         if (base + kResRows >= n && base < n) cnt->last_single = (single >> (uint32_t)(n - 1 - base)) & 1u;   // the lane of row n-1
@@ -270,7 +272,7 @@ __global__ __launch_bounds__(kMatThreads) void k_resolve_tile(const void* __rest
                 counts[tile] = c;
                 if (s_cnt[0]) atomicAdd(&cnt->ngroups, (unsigned long long)s_cnt[0]);
                 if (s_cnt[1]) atomicAdd(&cnt->group_rows, (unsigned long long)s_cnt[1]);
-                if (s_cnt[2]) atomicAdd(&cnt->nerrors, (unsigned long long)s_cnt[2]);
+                if (s_cnt[2]) atomicAdd(&cnt->err.nerrors, (unsigned long long)s_cnt[2]);
                 if constexpr (ORD != kOrdNone) part[tile] = s_part;
             }
         }
@@ -323,7 +325,7 @@ __global__ void k_resolve_finish(ResCounters* cnt, const uint32_t* __restrict__ 
         const unsigned long long bit = 1ull << (p & 63u);
         if (atomicAnd(&bitmap[p >> 6], ~bit) & bit) atomicSub(&counts[p / kResTile], 1u);
     }
-    cnt->first_error_row = cnt->first_error == ~0ull ? ~0ull : (unsigned long long)perm[cnt->first_error >> 2];
+    cnt->first_error_row = cnt->err.first == kErrNone ? ~0ull : (unsigned long long)perm[err_row(cnt->err.first)];
 }
 
 // offs[tile] = survivors in front of the tile; out[rank] = the sorted position
@@ -423,24 +425,16 @@ CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* ix, const cph_r
             TileBitmap tb;
             CPH_TRY(tb.alloc(ctx, n));
             const uint64_t ntiles = tb.ntiles;
-            DevBuf part, cnt;
+            DevBuf part;
+            ErrReport<ResCounters> cnt;
             if (mode != kOrdNone) CPH_TRY(part.alloc(&ctx->pool, ntiles * sizeof(TilePartial)));
-            CPH_TRY(cnt.alloc(&ctx->pool, sizeof(ResCounters)));
-            {
-                void* slot = nullptr;
-                CPH_TRY(pinned_upload(ctx, sizeof(ResCounters), &slot));
-                ResCounters zero{};
-                zero.first_error = ~0ull;
-                zero.first_error_row = ~0ull;
-                memcpy(slot, &zero, sizeof zero);
-                CPH_HIP_TRY(hipMemcpyAsync(cnt.get(), slot, sizeof zero, hipMemcpyHostToDevice, ctx->stream));
-            }
+            CPH_TRY(cnt.init(ctx));   // first_error_row is k_resolve_finish's to write
             {
                 // byte model: the codes and the order values (or perm + offsets + ~8 string bytes) in, bitmap, counts and partials out
                 ProfScope ps(ctx, "k_resolve_tile", (double)n * (cb + order_bytes + 1.0 / 8.0) + (double)ntiles * (4.0 + (mode != kOrdNone ? (double)sizeof(TilePartial) : 0.0)));
-                if (mode == kOrdNone) launch_tile<kOrdNone>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), nullptr, cnt.as<ResCounters>());
-                else if (mode == kOrdKey) launch_tile<kOrdKey>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), part.as<TilePartial>(), cnt.as<ResCounters>());
-                else launch_tile<kOrdBytes>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), part.as<TilePartial>(), cnt.as<ResCounters>());
+                if (mode == kOrdNone) launch_tile<kOrdNone>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), nullptr, cnt.counters());
+                else if (mode == kOrdKey) launch_tile<kOrdKey>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), part.as<TilePartial>(), cnt.counters());
+                else launch_tile<kOrdBytes>(ctx, ix, opts->rule, ord, ntiles, tb.words(), tb.counts(), part.as<TilePartial>(), cnt.counters());
             }
             CPH_HIP_TRY(hipGetLastError());
             if (mode != kOrdNone && ntiles > 1) {
@@ -454,20 +448,21 @@ CPH_API int32_t cph_index_resolve(cph_ctx* ctx, const cph_index* ix, const cph_r
                                        tb.bitmap.as<unsigned long long>(), tb.counts());
                 CPH_HIP_TRY(hipGetLastError());
             }
-            hipLaunchKernelGGL(k_resolve_finish, dim3(1), dim3(kWave), 0, ctx->stream, cnt.as<ResCounters>(), ix->perm.as<uint32_t>(), n,
+            hipLaunchKernelGGL(k_resolve_finish, dim3(1), dim3(kWave), 0, ctx->stream, cnt.counters(), ix->perm.as<uint32_t>(), n,
                                opts->keep_last_row, tb.bitmap.as<unsigned long long>(), tb.counts());
             CPH_HIP_TRY(hipGetLastError());
             CPH_TRY(tb.scan(ctx));
-            CPH_HIP_TRY(hipMemcpyAsync(&cnt.as<ResCounters>()->total, tb.total(), sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            CPH_HIP_TRY(hipMemcpyAsync(&cnt.counters()->total, tb.total(), sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
             ResCounters got{};
-            CPH_TRY(read_device_value(ctx, cnt.as<ResCounters>(), &got));   // the call's host wait
+            ErrFirst e;
+            CPH_TRY(cnt.read(ctx, &e, &got));   // the call's host wait
             r->pub.ngroups = got.ngroups;
             r->pub.group_rows = got.group_rows;
-            r->pub.nerrors = got.nerrors;
-            if (got.nerrors) {   // data, not a failure: no positions, no index
-                r->pub.first_error_position = got.first_error >> 2;
+            r->pub.nerrors = e.nerrors;
+            if (e.nerrors) {   // data, not a failure: no positions, no index
+                r->pub.first_error_position = e.row;
                 r->pub.first_error_row = got.first_error_row;
-                r->pub.first_error_kind = (int32_t)(got.first_error & 3ull);
+                r->pub.first_error_kind = e.kind;
                 return {};
             }
             kept = got.total;

@@ -362,9 +362,7 @@ static int32_t submit_impl(cph_stream_join* sj, const cph_strcol* step_cols, con
         for (int s = 0; s < sj->nsteps; s++) {
             if (step_codes) {   // 4 bytes per row of this step
                 DevBuf b;
-                CPH_TRY(b.alloc(&ctx->pool, n * sizeof(uint32_t)));
-                CPH_HIP_TRY(hipMemcpyAsync(b.get(), step_codes[s], n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-                d_codes[s] = b.as<uint32_t>();
+                CPH_TRY(device_array(ctx, step_codes[s], CPH_MEM_HOST, (size_t)n, &b, &d_codes[s]));
                 sl.d_in.push_back(std::move(b));
                 continue;
             }
