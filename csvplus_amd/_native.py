@@ -204,6 +204,7 @@ class cph_expr_nums(C.Structure):
 CPH_MAP_LITERAL, CPH_MAP_COLUMN, CPH_MAP_INT64, CPH_MAP_FLOAT64 = 1, 2, 3, 4
 CPH_MAP_SLICE = 8
 CPH_MAP_TIME = 10   # Unix seconds written as RFC 3339; prec = the zone in minutes east of UTC
+CPH_MAP_FLOAT64_SHORTEST = 12   # a float64's shortest round-trip digits; prec = the format byte: 'e' 'E' 'f' 'g' 'G'
 
 
 class cph_map_slice(C.Structure):

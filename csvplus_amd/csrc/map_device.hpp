@@ -7,6 +7,7 @@
 
 #include "materialize_device.hpp"
 #include "numformat_device.hpp"
+#include "shortfmt_device.hpp"
 #include "strpred_device.hpp"
 #include "timeparse_device.hpp"
 
@@ -14,7 +15,7 @@ namespace cph {
 
 struct MapPiece {
     int32_t kind;          // CPH_MAP_*
-    int32_t col;           // COLUMN / SLICE: the column; FLOAT64: prec; TIME: the zone, minutes east of UTC
+    int32_t col;           // COLUMN / SLICE: the column; FLOAT64: prec; TIME: the zone, minutes east of UTC; FLOAT64_SHORTEST: the format byte
     union {
         struct {
             uint32_t off, len;   // LITERAL: its bytes in the plan's literal block
@@ -23,7 +24,7 @@ struct MapPiece {
     };
     union {
         const int64_t* ints;    // INT64 / TIME: one value per output row, on the device
-        const double* floats;   // FLOAT64: likewise
+        const double* floats;   // FLOAT64 / FLOAT64_SHORTEST: likewise
         int64_t to;             // SLICE
     };
 };
@@ -32,8 +33,11 @@ struct MapPiece {
 // its pieces, so one of LITERAL / COLUMN / INT64 pieces alone launches the kernels it always launched.
 enum : int { kPiecesBase = 0,     // LITERAL, COLUMN, INT64
              kPiecesSlice = 1,    // + SLICE
-             kPiecesFloat = 2 };  // + SLICE, FLOAT64 (the formatter's registers) and TIME: the pieces whose values can be refused
-__host__ __device__ constexpr int pieces_set(bool has_float, bool has_slice) { return has_float ? kPiecesFloat : has_slice ? kPiecesSlice : kPiecesBase; }
+             kPiecesFloat = 2,    // + SLICE, FLOAT64 (the formatter's registers) and TIME: the pieces whose values can be refused
+             kPiecesShortest = 3 };  // + all of those and FLOAT64_SHORTEST (shortfmt_device.hpp: the digit generator's registers)
+__host__ __device__ constexpr int pieces_set(bool has_shortest, bool has_float, bool has_slice) {
+    return has_shortest ? kPiecesShortest : has_float ? kPiecesFloat : has_slice ? kPiecesSlice : kPiecesBase;
+}
 
 __device__ __forceinline__ uint64_t int_magnitude(int64_t v) { return v < 0 ? 0ull - (uint64_t)v : (uint64_t)v; }
 
@@ -108,7 +112,7 @@ __device__ __forceinline__ uint64_t map_field_bytes(const ColsArg& cols, const C
 }
 
 // The length pass of one piece: the bytes piece p adds to output row i besides its literal (digit counts by compares, spans
-// from offsets alone).  PK == kPiecesFloat: *refused, preset to UINT64_MAX, takes the lowest row with a value the FLOAT64 or
+// from offsets alone).  PK >= kPiecesFloat: *refused, preset to UINT64_MAX, takes the lowest row with a value the FLOAT64 or
 // TIME formatter refuses.
 template <int NC, int PK>
 __device__ __forceinline__ uint64_t map_piece_bytes(const ColsArg& cols, const ColIds& ids, const MapPiece& p, const RecordFields<NC>& f, uint64_t i,
@@ -116,11 +120,13 @@ __device__ __forceinline__ uint64_t map_piece_bytes(const ColsArg& cols, const C
     uint64_t bytes = 0;
     if (p.kind == CPH_MAP_INT64) {
         bytes = int_chars(p.ints[i]);
-    } else if (PK == kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
+    } else if (PK >= kPiecesShortest && p.kind == CPH_MAP_FLOAT64_SHORTEST) {   // no value is refused
+        bytes = short_chars(short_split(p.floats[i]), p.col);
+    } else if (PK >= kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
         const FixedParts r = fixed_split(p.floats[i], p.col);
         bytes = fixed_chars(r, p.col);
         if (r.kind == FIXED_RANGE) atomicMin(reinterpret_cast<unsigned long long*>(refused), (unsigned long long)i);
-    } else if (PK == kPiecesFloat && p.kind == CPH_MAP_TIME) {   // the length needs no look at the value; the refusal does
+    } else if (PK >= kPiecesFloat && p.kind == CPH_MAP_TIME) {   // the length needs no look at the value; the refusal does
         bytes = rfc3339_chars(p.col);
         if (!rfc3339_in_range(p.ints[i], p.col)) atomicMin(reinterpret_cast<unsigned long long*>(refused), (unsigned long long)i);
     } else if (p.kind == CPH_MAP_COLUMN || (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE)) {
@@ -141,9 +147,11 @@ __device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, con
                 s.put8(load_value_chunk(lits, p.off, p.len, (int)(q >> 3)), p.len - q < 8u ? p.len - q : 8u);
         } else if (p.kind == CPH_MAP_INT64) {
             put_int(s, p.ints[i]);
-        } else if (PK == kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
+        } else if (PK >= kPiecesShortest && p.kind == CPH_MAP_FLOAT64_SHORTEST) {
+            short_put(s, short_split(p.floats[i]), p.col);
+        } else if (PK >= kPiecesFloat && p.kind == CPH_MAP_FLOAT64) {
             fixed_put(s, fixed_split(p.floats[i], p.col), p.col);
-        } else if (PK == kPiecesFloat && p.kind == CPH_MAP_TIME) {
+        } else if (PK >= kPiecesFloat && p.kind == CPH_MAP_TIME) {
             put_time(s, p.ints[i], p.col);
         } else if (PK >= kPiecesSlice && p.kind == CPH_MAP_SLICE) {   // the record's preloaded first chunk is the whole field's: a slice loads its own
             const uint8_t* data = cols.c[p.col].data;

@@ -3,7 +3,8 @@
 //   cph_map_format  value i of the new column = the template's pieces in order: literal bytes, the value of a column in
 //                   row i (read through that column's row ids, as the writers read a joined row), an int64 written as
 //                   strconv.FormatInt(v, 10), a float64 written as strconv.FormatFloat(v, 'f', prec, 64) (numformat_device.hpp),
-//                   a slice [from, to) of a column's value in row i, Unix seconds written as RFC 3339 (timeparse_device.hpp).
+//                   a slice [from, to) of a column's value in row i, Unix seconds written as RFC 3339 (timeparse_device.hpp),
+//                   a float64 written with its shortest round-trip digits, FormatFloat(v, 'e' / 'f' / 'g', -1, 64) (shortfmt_device.hpp).
 //                   Bytes are copied verbatim; nothing is escaped.
 //
 // The pipeline of the gather and of the two-pass CSV writer (materialize.hip): k_map_lens (bytes per row: offsets only, the
@@ -11,11 +12,13 @@
 // k_map_copy (a tile's rows assembled in the LDS stage 8 value bytes at a time, streamed out with 16-byte stores; a tile
 // beyond the stage writes its rows to global memory itself).  Two passes, no look-back and no waiting between workgroups.
 // The literals are packed into one small device block that every row reads 8 bytes at a time.
-// Both kernels come in three piece sets (map_device.hpp: pieces_set), and a template launches the smallest that holds its
+// Both kernels come in four piece sets (map_device.hpp: pieces_set), and a template launches the smallest that holds its
 // pieces: the base pair carries no SLICE code (strpred_device.hpp: slice_span) and no float code; the slice pair
 // (k_map_lens_sl / k_map_copy_sl) adds SLICE; the float pair (k_map_lens_f64 / k_map_copy_f64) adds SLICE, FLOAT64 and TIME,
 // the pieces whose values can be refused (beyond the formatter's range; a local year outside 0000..9999).  Its length pass
-// also finds the lowest refused row, which comes back in the same copy as the scan's total.
+// also finds the lowest refused row, which comes back in the same copy as the scan's total.  The shortest pair (k_map_lens_g64 /
+// k_map_copy_g64) adds FLOAT64_SHORTEST (shortfmt_device.hpp) to all of those: the digit generator's registers stay out of the
+// float pair, which compiles to what it was.  Both passes run the digit generator; nothing is cached between them.
 // Where things live: this file has the plan (a kernel argument), the two kernels' row loops and the entry point's own
 // arguments.  map_device.hpp has what a row does in either pass; map_plan.hpp has the piece rules, the plan's pieces and
 // literals, the scan with the refused-row report, the result column and the launch by piece set.  map_switch.hip shares both.
@@ -33,7 +36,7 @@ struct MapPlan {
     MapPiece p[CPH_MAP_MAX_PIECES];
 };
 
-// lens[i] = bytes of value i.  PK == kPiecesFloat (the plan has a FLOAT64 or TIME piece): lens[n + 1], preset to UINT64_MAX, = the lowest
+// lens[i] = bytes of value i.  PK >= kPiecesFloat (the plan has a FLOAT64 or TIME piece): lens[n + 1], preset to UINT64_MAX, = the lowest
 // row with a value the formatter refuses.
 template <int NC, int PK = kPiecesBase>
 __global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, uint64_t* __restrict__ lens) {
@@ -52,6 +55,8 @@ template <int NC>
 constexpr auto k_map_lens_f64 = k_map_lens<NC, kPiecesFloat>;
 template <int NC>
 constexpr auto k_map_lens_sl = k_map_lens<NC, kPiecesSlice>;
+template <int NC>
+constexpr auto k_map_lens_g64 = k_map_lens<NC, kPiecesShortest>;
 
 // value i at out + offs[i]
 template <int NC, int PK = kPiecesBase>
@@ -93,6 +98,8 @@ template <int NC>
 constexpr auto k_map_copy_f64 = k_map_copy<NC, kPiecesFloat>;
 template <int NC>
 constexpr auto k_map_copy_sl = k_map_copy<NC, kPiecesSlice>;
+template <int NC>
+constexpr auto k_map_copy_g64 = k_map_copy<NC, kPiecesShortest>;
 
 }  // namespace cph
 
@@ -114,9 +121,9 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
     const uint64_t n = nrows;
     const std::string who = "cph_map_format: ";
     uint64_t lit_bytes = 0;
-    bool has_float = false, has_slice = false;
+    bool has_shortest = false, has_float = false, has_slice = false;
     {
-        Status s = check_map_pieces(pieces, npieces, ncols, n, [&](int) { return who; }, &lit_bytes, &has_float, &has_slice);
+        Status s = check_map_pieces(pieces, npieces, ncols, n, [&](int) { return who; }, &lit_bytes, &has_shortest, &has_float, &has_slice);
         if (s.ok()) s = check_row_sources(cols, sel, ncols, 0, n, true);
         if (!s.ok()) return fail_with(ctx, s);
     }
@@ -140,7 +147,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         CPH_TRY(r->d_offs.alloc(&ctx->pool, (n + (has_float ? 2 : 1)) * sizeof(uint64_t)));   // a float plan: + the refused row
         uint64_t* offs = r->d_offs.as<uint64_t>();
         if (has_float) CPH_HIP_TRY(hipMemsetAsync(offs + n + 1, 0xFF, sizeof(uint64_t), ctx->stream));
-        const int pk = pieces_set(has_float, has_slice);
+        const int pk = pieces_set(has_shortest, has_float, has_slice);
         CPH_MAP_DISPATCH(ctx, k_map_lens, pk, 0, ncols, n, 0, arg, ids, plan, n, offs);
         uint64_t total = 0;
         CPH_TRY(scan_with_refusal(ctx, offs, n, has_float,

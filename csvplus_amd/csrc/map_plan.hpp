@@ -1,7 +1,7 @@
 // map_plan.hpp — the host side the two Map entry points share (map_format.hip: one template; map_switch.hip: one per
 // alternative): the rules for a template's pieces, the pieces as the kernels see them (map_device.hpp: MapPiece) with their
 // literal block and staged number arrays, the scan with the refused-row report, the result column, and the choice among a
-// kernel's three piece sets.  Host only; the kernels and their plans (kernel arguments) stay with each entry point.
+// kernel's four piece sets.  Host only; the kernels and their plans (kernel arguments) stay with each entry point.
 #pragma once
 
 #include <string>
@@ -14,7 +14,7 @@ namespace cph {
 // bytes to *lit_bytes (all templates of a call together stay below 4 GiB) and notes which piece set the call needs.
 template <class Prefix>
 Status check_map_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t ncols, uint64_t n, Prefix prefix, uint64_t* lit_bytes,
-                        bool* has_float, bool* has_slice) {
+                        bool* has_shortest, bool* has_float, bool* has_slice) {
     for (int k = 0; k < npieces; k++) {
         const cph_map_piece& p = pieces[k];
         auto fail = [&](const char* words) { return Status{CPH_ERR_INVALID, prefix(k) + words}; };
@@ -38,6 +38,12 @@ Status check_map_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t nc
                 if (p.prec < 0 || p.prec > kFixedMaxPrec) return fail("prec of a FLOAT64 piece outside 0..22");
                 *has_float = true;
                 break;
+            case CPH_MAP_FLOAT64_SHORTEST:
+                if (!mem_ok) return fail("bad memory space of a FLOAT64_SHORTEST piece");
+                if (!p.floats && n) return fail("a FLOAT64_SHORTEST piece without values");
+                if (!short_fmt_ok(p.prec)) return fail("prec of a FLOAT64_SHORTEST piece (the format byte) is none of 'e' 'E' 'f' 'g' 'G'");
+                *has_shortest = true;
+                break;
             case CPH_MAP_TIME:
                 if (!mem_ok) return fail("bad memory space of a TIME piece");
                 if (!p.ints && n) return fail("a TIME piece without values");
@@ -52,7 +58,7 @@ Status check_map_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t nc
                 *has_slice = true;
                 break;
             default:
-                return fail("unknown piece kind (1..4, 8, 10)");
+                return fail("unknown piece kind (1..4, 8, 10)");   // the words are pinned by the message tests; 12 is a kind too
         }
     }
     return {};
@@ -94,14 +100,15 @@ inline Status append_map_pieces(cph_ctx* ctx, const cph_map_piece* pieces, int32
             d.to = sl.to;
             if (!(((b->slice_cols | b->col_mask) >> p.arg) & 1u)) b->in_bytes += offsets_and_ids(p.arg);
             b->slice_cols |= 1u << p.arg;
-        } else {   // INT64 / FLOAT64 / TIME: 8 bytes per row
-            const void* vals = p.kind == CPH_MAP_FLOAT64 ? static_cast<const void*>(p.floats) : static_cast<const void*>(p.ints);
+        } else {   // INT64 / FLOAT64 / FLOAT64_SHORTEST / TIME: 8 bytes per row
+            const bool is_float = p.kind == CPH_MAP_FLOAT64 || p.kind == CPH_MAP_FLOAT64_SHORTEST;
+            const void* vals = is_float ? static_cast<const void*>(p.floats) : static_cast<const void*>(p.ints);
             b->in_bytes += 8.0;
             staged->emplace_back();
             CPH_TRY(device_array(ctx, vals, p.arg, n * sizeof(int64_t), &staged->back(), &vals));
-            if (p.kind == CPH_MAP_FLOAT64) d.floats = static_cast<const double*>(vals);
+            if (is_float) d.floats = static_cast<const double*>(vals);
             else d.ints = static_cast<const int64_t*>(vals);
-            if (p.kind != CPH_MAP_INT64) d.col = p.prec;   // FLOAT64: prec; TIME: the zone
+            if (p.kind != CPH_MAP_INT64) d.col = p.prec;   // FLOAT64: prec; TIME: the zone; FLOAT64_SHORTEST: the format byte
         }
     }
     *lit_bytes = b->lits.size() - lit0;
@@ -174,14 +181,16 @@ inline Status deliver_map_column(cph_ctx* ctx, cph_colbuf_impl* r, uint64_t n, u
     return deliver(ctx, &r->own, parts, 2, out_mem);
 }
 
-// Launches KERNEL, KERNEL_sl or KERNEL_f64 for the piece set PK (map_device.hpp: pieces_set) over NROWS rows of NCOLS columns,
-// inside a function that returns Status.  The slice kernels have a profile name of their own; the float ones report under the
-// base name.
+// Launches KERNEL, KERNEL_sl, KERNEL_f64 or KERNEL_g64 for the piece set PK (map_device.hpp: pieces_set) over NROWS rows of NCOLS columns,
+// inside a function that returns Status.  The slice kernels have a profile name of their own; the float and shortest
+// ones report under the base name.
 #define CPH_MAP_DISPATCH(CTX, KERNEL, PK, BYTES, NCOLS, NROWS, SMEM, ...)                                                  \
     do {                                                                                                                   \
         {                                                                                                                  \
             ProfScope ps_(CTX, (PK) == kPiecesSlice ? #KERNEL "_sl" : #KERNEL, BYTES);                                     \
-            if ((PK) == kPiecesFloat) {                                                                                    \
+            if ((PK) == kPiecesShortest) {                                                                                 \
+                CPH_CSV_DISPATCH(KERNEL##_g64, NCOLS, dim3(grid_rows(NROWS)), SMEM, (CTX)->stream, __VA_ARGS__);           \
+            } else if ((PK) == kPiecesFloat) {                                                                             \
                 CPH_CSV_DISPATCH(KERNEL##_f64, NCOLS, dim3(grid_rows(NROWS)), SMEM, (CTX)->stream, __VA_ARGS__);           \
             } else if ((PK) == kPiecesSlice) {                                                                             \
                 CPH_CSV_DISPATCH(KERNEL##_sl, NCOLS, dim3(grid_rows(NROWS)), SMEM, (CTX)->stream, __VA_ARGS__);            \

@@ -12,7 +12,7 @@
 // may take different alternatives: every lane walks its own run [first[a], first[a + 1]) of the one flat piece array, so the
 // k-th pieces of two alternatives run together where they are of one kind and one after the other where they are not; the
 // stage sink ORs words into LDS, so no lane depends on another's progress and rows are not sorted by alternative.
-// The kernels come in map_format.hip's three piece sets, chosen over the pieces of all alternatives together.
+// The kernels come in map_format.hip's four piece sets, chosen over the pieces of all alternatives together.
 // Where things live: this file has what Switch adds to map_format.hip — the bitmaps, the byte per row, the plan with one run
 // of pieces per alternative, and the alternative in the messages.  What a row does in either pass is map_device.hpp's; the
 // piece rules, the plan's pieces and literals, the scan with the refused-row report, the result column and the launch by
@@ -35,7 +35,7 @@ struct SwitchPlan {   // travels in the kernel arguments (~1 KB beside ColsArg a
     MapPiece p[CPH_MAP_SWITCH_MAX_PIECES];
 };
 
-// which[i] = the alternative of row i, lens[i] = bytes of its value.  PK == kPiecesFloat: lens[n + 1], preset to UINT64_MAX, = the lowest row
+// which[i] = the alternative of row i, lens[i] = bytes of its value.  PK >= kPiecesFloat: lens[n + 1], preset to UINT64_MAX, = the lowest row
 // whose OWN alternative holds a value the float formatter refuses.
 template <int NC, int PK = kPiecesBase>
 __global__ __launch_bounds__(kMatThreads) void k_switch_lens(ColsArg cols, ColIds ids, SwitchPlan plan, uint64_t n, uint8_t* __restrict__ which,
@@ -60,6 +60,8 @@ template <int NC>
 constexpr auto k_switch_lens_f64 = k_switch_lens<NC, kPiecesFloat>;
 template <int NC>
 constexpr auto k_switch_lens_sl = k_switch_lens<NC, kPiecesSlice>;
+template <int NC>
+constexpr auto k_switch_lens_g64 = k_switch_lens<NC, kPiecesShortest>;
 
 // row i's own run of pieces [first[a], first[a + 1]): the bounds and the piece index differ from lane to lane
 template <int NC, int PK, class Sink>
@@ -111,6 +113,8 @@ template <int NC>
 constexpr auto k_switch_copy_f64 = k_switch_copy<NC, kPiecesFloat>;
 template <int NC>
 constexpr auto k_switch_copy_sl = k_switch_copy<NC, kPiecesSlice>;
+template <int NC>
+constexpr auto k_switch_copy_g64 = k_switch_copy<NC, kPiecesShortest>;
 
 }  // namespace cph
 
@@ -149,14 +153,14 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
     auto alt_npieces = [&](int a) { return a < ncases ? cases[a].npieces : notherwise; };
     auto alt_name = [&](int a) { return "cph_map_switch: " + (a < ncases ? "case " + std::to_string(a) : std::string("otherwise")) + ", "; };
     uint64_t lit_bytes = 0;
-    bool has_float = false, has_slice = false;
+    bool has_shortest = false, has_float = false, has_slice = false;
     for (int a = 0; a <= ncases; a++) {
         if (a < ncases) {
             Status s = check_pred_program(cases[a].prog, cases[a].nops, ncols);
             if (!s.ok()) return fail_with(ctx, {s.code, "cph_map_switch: case " + std::to_string(a) + ": " + s.msg});
         }
         Status s = check_map_pieces(alt_pieces(a), alt_npieces(a), ncols, n, [&](int k) { return alt_name(a) + "piece " + std::to_string(k) + ": "; },
-                                    &lit_bytes, &has_float, &has_slice);
+                                    &lit_bytes, &has_shortest, &has_float, &has_slice);
         if (!s.ok()) return fail_with(ctx, s);
     }
     {
@@ -197,7 +201,7 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         CPH_TRY(r->d_offs.alloc(&ctx->pool, (n + (has_float ? 2 : 1)) * sizeof(uint64_t)));   // a float plan: + the refused row
         uint64_t* offs = r->d_offs.as<uint64_t>();
         if (has_float) CPH_HIP_TRY(hipMemsetAsync(offs + n + 1, 0xFF, sizeof(uint64_t), ctx->stream));
-        const int pk = pieces_set(has_float, has_slice);
+        const int pk = pieces_set(has_shortest, has_float, has_slice);
         // besides the value bytes, both passes read or write the alternative's byte
         CPH_MAP_DISPATCH(ctx, k_switch_lens, pk, (8.0 + 1.0 + (double)ncases / 8.0 + build.in_bytes) * (double)n, ncols, n, 0, arg, ids, plan, n, which_dev,
                          offs);

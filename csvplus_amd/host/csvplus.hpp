@@ -16,7 +16,8 @@
 //   Like / All / Any / Not           :1243-1293  csvplus::Like / All / Any / Not (plain data, also callable on a Row)
 //   DataSource.Map                     :290-296  DataSource::Map over csvplus::Set(name, literal or Format{...}): a row
 //                                                template instead of a closure, rendered on the GPU (cph_map_format);
-//                                                Fixed(expr, prec) / Itoa(expr): an Expr's value (cph_num_eval);
+//                                                Fixed(expr, prec) / Shortest(expr, fmt) / Itoa(expr): an Expr's value
+//                                                (cph_num_eval);
 //                                                Set(name, Switch({Case(pred, Format)...}, otherwise)) / When(pred, then,
 //                                                otherwise): the `if` inside the closure — the template of the first case
 //                                                whose Pred holds (cph_map_switch)
@@ -58,6 +59,7 @@
 #pragma once
 
 #include <algorithm>
+#include <charconv>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -310,6 +312,28 @@ inline int32_t ParseRfc3339(const std::string& s, bool nano, int64_t* out) {
     *out = (int64_t)ns;
     return CPH_NUM_OK;
 }
+// strconv.FormatFloat(v, fmt, -1, 64) on the host for fmt 'e' 'E' 'f' 'g' 'G': the shortest round-trip digits from std::to_chars,
+// laid out by Go's rules (strconv/ftoa.go: %e, %f, and 'g' choosing %e when the exponent is below -4 or at least 6)
+inline std::string FormatShortest(double v, char fmt) {
+    if (std::isnan(v)) return "NaN";
+    if (std::isinf(v)) return v < 0 ? "-Inf" : "+Inf";
+    char buf[40];
+    const auto res = std::to_chars(buf, buf + sizeof buf, std::fabs(v), std::chars_format::scientific);   // d[.ddd]e±XX[X]
+    std::string sci(buf, res.ptr), digits;
+    const size_t epos = sci.find('e');
+    for (size_t i = 0; i < epos; i++)
+        if (sci[i] != '.') digits.push_back(sci[i]);
+    const int exp = atoi(sci.c_str() + epos + 1), nd = (int)digits.size(), dp = exp + 1;
+    const std::string sign = std::signbit(v) ? "-" : "";
+    if (fmt == 'e' || fmt == 'E' || (fmt != 'f' && (exp < -4 || exp >= 6))) {
+        if (fmt == 'E' || fmt == 'G') sci[epos] = 'E';
+        return sign + sci;
+    }
+    if (dp <= 0) return sign + "0." + std::string((size_t)-dp, '0') + digits;
+    if (dp < nd) return sign + digits.substr(0, (size_t)dp) + "." + digits.substr((size_t)dp);
+    return sign + digits + std::string((size_t)(dp - nd), '0');
+}
+
 // time.Unix(v, 0).In(time.FixedZone("", 60 * zone)).Format(time.RFC3339) on the host; false where the local year leaves 0000..9999
 inline bool FormatRfc3339(int64_t v, int zone, std::string* out) {
     if (v < -62167219200ll - 86400 || v > 253402300799ll + 86400) return false;
@@ -698,6 +722,22 @@ struct Fixed {
         if (expr->kind != CPH_NUM_FLOAT64) throw Panic("Fixed() of an int64 expression (use Itoa, or Float64)");
     }
 };
+// Shortest(Col("price"), 'g') is the column's value read as Row.ValueAsFloat64 reads it and written back as
+// strconv.FormatFloat(v, fmt, -1, 64) writes it: the shortest digits that read back to the same float64, as 'e' / 'E', 'f' or
+// 'g' / 'G' (a CPH_MAP_FLOAT64_SHORTEST piece).  Shortest(expression, fmt) writes a float64 expression's value.  No value is refused.
+struct Shortest {
+    Col col;
+    char fmt;
+    std::shared_ptr<const Expr> expr;
+    static void check(char f) {
+        if (f != 'e' && f != 'E' && f != 'f' && f != 'g' && f != 'G') throw Panic("Shortest(): fmt is none of 'e' 'E' 'f' 'g' 'G'");
+    }
+    Shortest(Col c, char f = 'g') : col(std::move(c)), fmt(f) { check(f); }
+    Shortest(Expr e, char f = 'g') : col(""), fmt(f), expr(std::make_shared<const Expr>(std::move(e))) {
+        check(f);
+        if (expr->kind != CPH_NUM_FLOAT64) throw Panic("Shortest() of an int64 expression (use Itoa, or Float64)");
+    }
+};
 struct Itoa {   // an int64 expression written as strconv.Itoa writes it
     std::shared_ptr<const Expr> expr;
     explicit Itoa(Expr e) : expr(std::make_shared<const Expr>(std::move(e))) {
@@ -737,7 +777,8 @@ struct Part {   // a literal, a column, a slice of a column, a column as a fixed
     cph_map_slice slice{0, 0};
     std::string text;   // the literal's bytes
     Col col{""};
-    int prec = -1;      // >= 0: Fixed
+    int prec = -1;      // >= 0: Fixed, or Shortest (0)
+    char shortest = 0;  // Shortest: the format byte; the float64 value is written with its shortest round-trip digits
     std::shared_ptr<const Expr> expr;   // Fixed(expr, prec) (prec >= 0), Itoa(expr) or Rfc3339(expr, zone) (prec < 0)
     bool is_time = false;               // Rfc3339: the int64 value is Unix seconds, written in the zone `zone`
     int zone = 0;
@@ -746,7 +787,9 @@ struct Part {   // a literal, a column, a slice of a column, a column as a fixed
     Part(std::string lit) : text(std::move(lit)) {}      // NOLINT
     Part(Col c) : is_col(true), col(std::move(c)) {}     // NOLINT
     Part(Fixed f) : is_col(!f.expr), col(std::move(f.col)), prec(f.prec), expr(std::move(f.expr)) {}   // NOLINT
+    Part(Shortest f) : is_col(!f.expr), col(std::move(f.col)), prec(0), shortest(f.fmt), expr(std::move(f.expr)) {}   // NOLINT
     Part(Itoa i) : expr(std::move(i.expr)) {}            // NOLINT
+    std::string floatText(double v) const { return shortest ? FormatShortest(v, shortest) : FormatFixed(v, prec); }
     Part(Substr s) : is_col(true), is_slice(true), slice{s.from, s.to}, col(std::move(s.col)) {}   // NOLINT
 };
 struct Format {
@@ -777,7 +820,7 @@ struct Format {
                     *out += t;
                     continue;
                 }
-                *out += p.prec >= 0 ? FormatFixed(fv, p.prec) : std::to_string(iv);
+                *out += p.prec >= 0 ? p.floatText(fv) : std::to_string(iv);
                 continue;
             }
             if (!p.is_col) {
@@ -804,7 +847,7 @@ struct Format {
                 if (invalid) *invalid = conversionError(p.col.name, *v, CPH_NUM_FLOAT64, rc);
                 return false;
             }
-            *out += FormatFixed(d, p.prec);
+            *out += p.floatText(d);
         }
         return true;
     }
@@ -842,6 +885,7 @@ inline Assign Set(std::string name, std::string literal) { return Assign{std::mo
 inline Assign Set(std::string name, const char* literal) { return Set(std::move(name), std::string(literal)); }
 inline Assign Set(std::string name, Format value) { return Assign{std::move(name), std::move(value)}; }
 inline Assign Set(std::string name, Fixed value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
+inline Assign Set(std::string name, Shortest value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
 inline Assign Set(std::string name, Itoa value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
 inline Assign Set(std::string name, Rfc3339 value) { return Assign{std::move(name), Format({Part(std::move(value))})}; }
 inline Assign Set(std::string name, Switch value) { return Assign{std::move(name), std::move(value.otherwise), std::move(value.cases)}; }
@@ -1963,7 +2007,9 @@ private:
         if (p.expr && p.prec < 0)
             return cph_map_piece{p.is_time ? CPH_MAP_TIME : CPH_MAP_INT64, CPH_MEM_HOST, {nullptr, 0}, static_cast<const int64_t*>(num->values), nullptr,
                                  p.is_time ? p.zone : 0, 0};
-        if (p.expr || p.prec >= 0) return cph_map_piece{CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr, static_cast<const double*>(num->values), p.prec, 0};
+        if (p.expr || p.prec >= 0)
+            return cph_map_piece{p.shortest ? CPH_MAP_FLOAT64_SHORTEST : CPH_MAP_FLOAT64, CPH_MEM_HOST, {nullptr, 0}, nullptr, static_cast<const double*>(num->values),
+                                 p.shortest ? (int32_t)p.shortest : p.prec, 0};
         if (!p.is_col) return cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr};
         if (p.is_slice) return cph_map_piece{CPH_MAP_SLICE, (int32_t)col, {reinterpret_cast<const uint8_t*>(&p.slice), sizeof p.slice}, nullptr};
         return cph_map_piece{CPH_MAP_COLUMN, (int32_t)col, {nullptr, 0}, nullptr};

@@ -18,6 +18,12 @@ the new column in row i is the concatenation of the template's parts —
                          `strconv.FormatFloat(price*float64(qty), 'f', 2, 64)` (csvplus_test.go:1391-1421).  prec is 0..22 and
                          finite values of 2^128 or more are refused, on the device and by the host model alike; host or
                          device array as for Int: Float.on_device(device_ptr, count, prec).
+    Float.shortest(array, fmt="g")
+                         array[i] written as strconv.FormatFloat(v, fmt, -1, 64) writes it: the SHORTEST digits that read back to
+                         the same float64 (Python's repr digits), laid out by fmt = 'e' / 'E' (d.ddde±XX), 'f' (no exponent) or
+                         'g' / 'G' ('e' when the exponent is below -4 or at least 6, else 'f').  No value is refused and the
+                         text converts back to the same bits.  Float.shortest_on_device(device_ptr, count, fmt) and
+                         Float.shortest_of(expr, fmt) as for Float; ftoa_shortest is the host model.
     Time(array, zone)    array[i] = Unix seconds, written as RFC 3339 in the fixed zone `zone_minutes` east of UTC:
                          `time.Unix(v, 0).In(time.FixedZone("", 60*zone)).Format(time.RFC3339)` — "YYYY-MM-DDTHH:MM:SSZ" for
                          zone 0, "...+HH:MM" / "...-HH:MM" otherwise (timeconv.format_model).  The zone is within -1439..1439
@@ -33,7 +39,7 @@ the new column in row i is the concatenation of the template's parts —
 
 `compile` turns a template into the piece list cph_map_format takes (include/csvplus_hip.h), `render` evaluates it on one
 row held as a dict — the host model, for callers without a GPU and as the cross-check of the device.  Nothing here
-touches the GPU.  Out of scope: FormatFloat's other forms (shortest round-trip digits, 'e' and 'g'); case mapping and
+touches the GPU.  Out of scope: FormatFloat's remaining forms ('e' / 'g' with an explicit precision, 'b' / 'x', 32-bit floats); case mapping and
 TrimSpace (Go's are Unicode-aware); splitting a value on a delimiter; regular expressions; time layouts other than
 RFC 3339, named zones and DST rules.
 
@@ -60,6 +66,8 @@ from . import timeconv as _T
 from .predicates import INT64_MAX, INT64_MIN, _bytes, _go_quote
 
 LITERAL, COLUMN, INT64, FLOAT64, SLICE, TIME = 1, 2, 3, 4, 8, 10   # CPH_MAP_*
+FLOAT64_SHORTEST = 12              # CPH_MAP_FLOAT64_SHORTEST: prec carries the format byte
+SHORTEST_FORMATS = "eEfgG"
 MAX_PIECES = 16                    # CPH_MAP_MAX_PIECES
 MAX_CASES = 8                      # CPH_MAP_MAX_CASES
 SWITCH_MAX_PIECES = 32             # CPH_MAP_SWITCH_MAX_PIECES: the pieces of all alternatives together
@@ -197,13 +205,24 @@ def _check_prec(prec, who) -> int:
     return int(prec)
 
 
+def _check_fmt(fmt, who) -> str:
+    if isinstance(fmt, (bytes, bytearray)):
+        fmt = bytes(fmt).decode("latin-1")
+    if not isinstance(fmt, str) or len(fmt) != 1 or fmt not in SHORTEST_FORMATS:
+        raise ValueError(f"{who}: fmt must be one of 'e' 'E' 'f' 'g' 'G', not {fmt!r}")
+    return fmt
+
+
 class Float:
     """One float64 per OUTPUT row, formatted as strconv.FormatFloat(v, 'f', prec, 64) does.  Float(values, prec): anything
     numpy turns into a float64 array (an integer array is converted, as Go's float64(qty) would), in host memory;
     Float.on_device(device_ptr, count, prec): a float64 array on the device, e.g. NumCol.values of
     materialize.to_float / eval_number(..., out_mem=DEVICE); Float.of(expr, prec): a float64 expression of csvplus_amd.expr,
-    evaluated over the template's rows.  prec: 0..22."""
+    evaluated over the template's rows.  prec: 0..22.
+    Float.shortest(values, fmt), Float.shortest_on_device(device_ptr, count, fmt), Float.shortest_of(expr, fmt): the same three
+    sources, formatted as strconv.FormatFloat(v, fmt, -1, 64) does (ftoa_shortest); such a part has `fmt` set and prec None."""
     expr = None
+    fmt = None
 
     def __init__(self, values, prec):
         self.prec = _check_prec(prec, "Float")
@@ -230,7 +249,39 @@ class Float:
         self.device, self.values, self.count, self.expr = False, None, None, expr
         return self
 
+    @classmethod
+    def shortest(cls, values, fmt="g") -> "Float":
+        fmt = _check_fmt(fmt, "Float.shortest")
+        self = cls(values, 0)
+        self.prec, self.fmt = None, fmt
+        return self
+
+    @classmethod
+    def shortest_on_device(cls, device_ptr: int, count: int, fmt="g") -> "Float":
+        fmt = _check_fmt(fmt, "Float.shortest_on_device")
+        self = cls.on_device(device_ptr, count, 0)
+        self.prec, self.fmt = None, fmt
+        return self
+
+    @classmethod
+    def shortest_of(cls, expr, fmt="g") -> "Float":
+        fmt = _check_fmt(fmt, "Float.shortest_of")
+        from . import expr as E
+        if E.kind_of(expr) != E.FLOAT:
+            raise TypeError("Float.shortest_of: the expression is an int64 (use Int.of, or ToFloat)")
+        self = cls.of(expr, 0)
+        self.prec, self.fmt = None, fmt
+        return self
+
+    def text(self, v) -> bytes:
+        """What the part writes for the value v: the host model."""
+        return ftoa(v, self.prec) if self.fmt is None else ftoa_shortest(v, self.fmt)
+
     def __repr__(self):
+        if self.fmt is not None:
+            if self.expr is not None:
+                return f"Float.shortest_of({self.expr!r}, {self.fmt!r})"
+            return f"Float.shortest(<{self.count} values{' on the device' if self.device else ''}>, {self.fmt!r})"
         if self.expr is not None:
             return f"Float.of({self.expr!r}, {self.prec})"
         return f"Float(<{self.count} values{' on the device' if self.device else ''}>, {self.prec})"
@@ -338,7 +389,7 @@ def columns(template) -> list:
 
 def compile(template, column_names):   # noqa: A001 (the name predicates.compile uses)
     """(names of the columns used, pieces).  A piece is (LITERAL, 0, bytes), (COLUMN, k, None) with k indexing the returned
-    name list, (SLICE, k, (from, to)), (INT64, 0, Int), (FLOAT64, 0, Float) or (TIME, 0, Time).  A Col (or the Col of a Slice) whose name is not among `column_names` becomes its default as a literal — in
+    name list, (SLICE, k, (from, to)), (INT64, 0, Int), (FLOAT64, 0, Float), (FLOAT64_SHORTEST, 0, Float) or (TIME, 0, Time).  A Col (or the Col of a Slice) whose name is not among `column_names` becomes its default as a literal — in
     structure-of-arrays a column is present for all rows or for none — and without a default raises MissingColumn.
     Neighbouring literals are joined.  Raises ValueError beyond the ABI's limits (16 pieces, 16 columns)."""
     known = [str(c) for c in column_names]
@@ -359,7 +410,7 @@ def compile(template, column_names):   # noqa: A001 (the name predicates.compile
         elif isinstance(p, Int):
             pieces.append((INT64, 0, p))
         elif isinstance(p, Float):
-            pieces.append((FLOAT64, 0, p))
+            pieces.append((FLOAT64 if p.fmt is None else FLOAT64_SHORTEST, 0, p))
         elif p.name in known:
             if p.name not in used:
                 used.append(p.name)
@@ -447,6 +498,37 @@ def ftoa(v, prec) -> bytes:
     return b"%.*f" % (prec, v)
 
 
+def ftoa_shortest(v, fmt="g") -> bytes:
+    """strconv.FormatFloat(v, fmt, -1, 64) of a float64 for fmt 'e' 'E' 'f' 'g' 'G'.  The digits are repr's — the shortest that
+    read back to the same float64, the closest such — taken through decimal.Decimal(repr(v)).as_tuple(); the layouts are
+    Go's (strconv/ftoa.go, %e / %f, and for 'g' the exponent test with precision 6).  No value is refused."""
+    import decimal
+    fmt = _check_fmt(fmt, "ftoa_shortest")
+    v = float(v)
+    if math.isnan(v):
+        return b"NaN"
+    if math.isinf(v):
+        return b"-Inf" if v < 0 else b"+Inf"
+    sign, digits, exponent = decimal.Decimal(repr(v)).as_tuple()
+    d = "".join(map(str, digits)).lstrip("0")
+    exponent += len(d) - len(d.rstrip("0"))
+    d = d.rstrip("0") or "0"
+    nd = len(d)
+    dp = nd + exponent if d != "0" else 1       # the value is 0.d * 10^dp; zero is the digit 0 with dp 1
+    exp = dp - 1
+    neg = "-" if sign else ""
+    if fmt in "eE" or (fmt in "gG" and (exp < -4 or exp >= 6)):
+        e = "E" if fmt in "EG" else "e"
+        text = f"{neg}{d[0]}{'.' + d[1:] if nd > 1 else ''}{e}{'-' if exp < 0 else '+'}{abs(exp):02d}"
+    elif dp <= 0:
+        text = f"{neg}0.{'0' * -dp}{d}"
+    elif dp < nd:
+        text = f"{neg}{d[:dp]}.{d[dp:]}"
+    else:
+        text = f"{neg}{d}{'0' * (dp - nd)}"
+    return text.encode("ascii")
+
+
 def _expr_value(p, row, i):
     from . import expr as E
     v, status, op = E.evaluate(p.expr, row, i)
@@ -470,7 +552,7 @@ def render(template, row, i: int = 0) -> bytes:
             out.append(p)
         elif isinstance(p, (Int, Float)) and p.expr is not None:
             v = _expr_value(p, row, i)
-            out.append(_T.format_model(v, p.zone) if isinstance(p, Time) else itoa(v) if isinstance(p, Int) else ftoa(v, p.prec))
+            out.append(_T.format_model(v, p.zone) if isinstance(p, Time) else itoa(v) if isinstance(p, Int) else p.text(v))
         elif isinstance(p, Time):
             if p.device:
                 raise ValueError("render: a Time part on the device has no host values")
@@ -482,7 +564,7 @@ def render(template, row, i: int = 0) -> bytes:
         elif isinstance(p, Float):
             if p.device:
                 raise ValueError("render: a Float part on the device has no host values")
-            out.append(ftoa(p.values[i], p.prec))
+            out.append(p.text(p.values[i]))
         else:
             col = p.col if isinstance(p, Slice) else p
             v = row.get(col.name)

@@ -553,8 +553,8 @@ def _map_rows(cols_by_name, row_ids, nrows, names, pieces, keep, who):
     ids = None if row_ids is None else [row_ids.get(nm) for nm in names]
     if cols:
         return _rowsel(cols, ids, nrows, keep)
-    exprs = [p[2].expr for p in pieces if p[0] in (M.INT64, M.FLOAT64, M.TIME) and p[2].expr is not None]
-    counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64, M.TIME) and p[2].expr is None]
+    exprs = [p[2].expr for p in pieces if p[0] in (M.INT64, M.FLOAT64, M.FLOAT64_SHORTEST, M.TIME) and p[2].expr is not None]
+    counts = [p[2].count for p in pieces if p[0] in (M.INT64, M.FLOAT64, M.FLOAT64_SHORTEST, M.TIME) and p[2].expr is None]
     from . import expr as E
     ecols = [nm for e in exprs for nm in E.columns(e) if nm in cols_by_name]
     if nrows is not None:
@@ -619,7 +619,7 @@ def _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending=
             elif kind == M.TIME:
                 parr[k].ints, parr[k].prec = ptr, value.zone
             else:
-                parr[k].floats, parr[k].prec = ptr, value.prec
+                parr[k].floats, parr[k].prec = ptr, ord(value.fmt) if kind == M.FLOAT64_SHORTEST else value.prec
     return parr
 
 

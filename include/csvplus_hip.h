@@ -1000,6 +1000,25 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  *                    prec == 0, otherwise "YYYY-MM-DDTHH:MM:SS+HH:MM" / "-HH:MM" (25 bytes).  A value whose LOCAL year falls
  *                    outside 0000..9999 is not formatted: the call fails with CPH_ERR_INVALID, the message names the piece and
  *                    the LOWEST such output row, *out stays NULL — exactly as for the FLOAT64 limit.
+ *   CPH_MAP_FLOAT64_SHORTEST  floats[i] written as strconv.FormatFloat(v, fmt, -1, 64) does, with the format byte fmt in `prec`:
+ *                    one of 'e' 'E' 'f' 'g' 'G'.  `floats` and `arg` follow the rules of FLOAT64 (nrows entries, entry i belongs
+ *                    to OUTPUT row i, a host array is staged).  The digits d1...dn (1..17 of them) are the SHORTEST that
+ *                    strconv.ParseFloat maps back to the same double and, among strings of that length, the one closest
+ *                    to the exact binary value (what fmt.Sprint, encoding/json, Python's repr and std::to_chars print).
+ *                    With exp = the decimal exponent of d1:
+ *                      'e' / 'E'  d1[.d2...dn]e±XX: no point when n = 1, at least two exponent digits, three when |exp| >= 100;
+ *                                 at most 24 bytes ("-2.2250738585072014e-308").
+ *                      'f'        no exponent.  |v| < 1: "0." , the zeros up to d1, the digits; otherwise the digits with the
+ *                                 point inside them, or the digits and then zeros up to the units with no point.  At most 327
+ *                                 bytes (the same value: '-', "0.", 307 zeros, 17 digits; 5e-324 is "0.", 323 zeros, "5");
+ *                                 at most 310 for |v| >= 1.
+ *                      'g' / 'G'  the 'e' / 'E' form when exp < -4 || exp >= 6, otherwise the 'f' form (Go decides with
+ *                                 precision 6 for the shortest digits; 21 is %v's and JSON's threshold, not 'g''s); at most
+ *                                 24 bytes.
+ *                    Zero gives "0e+00", "0", "0" and -0 keeps its sign ("-0e+00", "-0", "-0"); NaN of any sign or payload gives
+ *                    "NaN", the infinities "+Inf" and "-Inf".  Exact for every double (Schubfach, one 128-bit table entry per
+ *                    value), and NO value is refused: 2^128 and 1e300 are formatted like any other.  The text reads back to
+ *                    the same bits through cph_col_to_number.
  * All bytes are copied verbatim (NUL and bytes >= 0x80 included); nothing is escaped.
  *
  * cols / sel / nrows mean exactly what they mean for cph_csv_write_rows (host or device columns, fixed-width or 32 / 64-bit
@@ -1012,31 +1031,34 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  * legal and yields an empty column.
  *
  * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / pieces / out, npieces outside 1..CPH_MAP_MAX_PIECES, an
- * unknown kind (5..7 and 9 included), a COLUMN or SLICE index outside 0..ncols-1 (a column the rows lack is the host's business:
+ * unknown kind (5..7, 9, 11 and 13 included), a COLUMN or SLICE index outside 0..ncols-1 (a column the rows lack is the host's business:
  * it substitutes a literal or reports the reference's missing-column error), a SLICE whose value is not exactly 16 bytes
  * behind a non-NULL pointer, a literal with a length but no pointer, an INT64 piece with ints ==
  * NULL while nrows > 0 or with an unknown memory space, a FLOAT64 piece with floats == NULL while nrows > 0, with an unknown
  * memory space or with prec outside 0..22, a FLOAT64 value beyond the range above (found while the call runs), a TIME piece with
  * ints == NULL while nrows > 0, with an unknown memory space or with prec outside -1439..1439, a TIME value whose local year is
- * outside 0000..9999 (found while the call runs), ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
+ * outside 0000..9999 (found while the call runs), a FLOAT64_SHORTEST piece with floats == NULL while nrows > 0, with an unknown
+ * memory space or with a prec that is none of 'e' 'E' 'f' 'g' 'G' (FLOAT64 with prec -1 stays refused: the shortest digits are
+ * the other kind), ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
  * than 32 / 64, an identity column whose row count is not nrows, an unknown out_mem.
  *
- * Out of scope: the other forms of FormatFloat — the shortest round-trip digits (prec -1) and the 'e' / 'g' formats, a
- * project of their own —; case mapping and TrimSpace (Go's are Unicode-aware: a project of their own); splitting a value
+ * Out of scope: the remaining forms of FormatFloat — 'e' / 'g' with an explicit precision, 'b' / 'x', and 32-bit floats
+ * (bitSize 32) —; case mapping and TrimSpace (Go's are Unicode-aware: a project of their own); splitting a value
  * on a delimiter; regular expressions; a slice whose ends come from another column; time layouts other than RFC 3339, named
  * zones and DST rules.  A value that
  * depends on a condition is cph_map_switch's.
  */
-enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4, CPH_MAP_SLICE = 8, CPH_MAP_TIME = 10 };   /* 5..7, 9: invalid */
+enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4, CPH_MAP_SLICE = 8, CPH_MAP_TIME = 10,
+       CPH_MAP_FLOAT64_SHORTEST = 12 };   /* 5..7, 9, 11: invalid */
 #define CPH_MAP_MAX_PIECES 16
 typedef struct { int64_t from, to; } cph_map_slice;   /* what a SLICE piece's `value` points at: 16 bytes */
 typedef struct {
     int32_t        kind;    /* CPH_MAP_* */
-    int32_t        arg;     /* COLUMN / SLICE: index into cols; INT64 / FLOAT64 / TIME: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
+    int32_t        arg;     /* COLUMN / SLICE: index into cols; INT64 / FLOAT64 / FLOAT64_SHORTEST / TIME: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
     cph_strval     value;   /* LITERAL: its bytes (host memory, any length, any byte values); SLICE: a cph_map_slice, len == 16 */
     const int64_t* ints;    /* INT64 / TIME: nrows values, entry i belongs to OUTPUT row i (no row ids) */
-    const double*  floats;  /* FLOAT64: likewise */
-    int32_t        prec;    /* FLOAT64: digits behind the point, 0..22; TIME: the zone, minutes east of UTC, -1439..1439 */
+    const double*  floats;  /* FLOAT64 / FLOAT64_SHORTEST: likewise */
+    int32_t        prec;    /* FLOAT64: digits behind the point, 0..22; TIME: the zone, minutes east of UTC, -1439..1439; FLOAT64_SHORTEST: the format byte */
     int32_t        reserved_;
 } cph_map_piece;
 
@@ -1060,14 +1082,14 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  *
  * Selection.  Row i takes the alternative a = the lowest case index whose program holds, or ncases (`otherwise`) if none
  * does.  Its value is that alternative's pieces rendered exactly as cph_map_format renders them (LITERAL / COLUMN / INT64 /
- * FLOAT64 / SLICE / TIME; verbatim bytes; FormatInt, FormatFloat 'f' and RFC 3339 rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
+ * FLOAT64 / FLOAT64_SHORTEST / SLICE / TIME; verbatim bytes; FormatInt, FormatFloat and RFC 3339 rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
  * memory, written when the call succeeds).
  *
- * Number pieces.  INT64 / FLOAT64 / TIME arrays have nrows entries indexed by OUTPUT row.  Entries of rows that select ANOTHER
+ * Number pieces.  INT64 / FLOAT64 / FLOAT64_SHORTEST / TIME arrays have nrows entries indexed by OUTPUT row.  Entries of rows that select ANOTHER
  * alternative are never interpreted and may hold anything; in particular the FLOAT64 refusal (a finite |v| >= 2^128) and the
  * TIME refusal (a local year outside 0000..9999) fail
  * the call only for a row that selects the alternative holding that piece.  The message then names the alternative, the
- * piece and the lowest such row, and *out stays NULL.
+ * piece and the lowest such row, and *out stays NULL.  A FLOAT64_SHORTEST piece refuses no value, so it can never fail a row.
  *
  * Result.  An ordinary library-owned cph_colbuf: 64-bit offsets, exact nbytes, in out_mem.  nrows == 0 is legal, and so is a
  * call in which every row selects an empty value (nbytes == 0).
