@@ -69,9 +69,10 @@ namespace cph {
 constexpr int kCsvThreads = 256;
 constexpr int kCsvWaves = kCsvThreads / kWave;
 constexpr int kCsvChunks = 4;                                  // 16-byte chunks per thread per tile
-constexpr int kCsvTile = kCsvThreads * 16 * kCsvChunks;       // 16 KiB per workgroup
+constexpr int kCsvTile = kCsvThreads * 16 * kCsvChunks;       // 16 KiB per workgroup (tests/test_gpu_csv_strict_edges.py: TILE)
 constexpr int kCsvStageMax = 32 * 1024;                       // LDS bytes for one 256-record tile (in, and out): the host picks
 constexpr int kCsvStageMin = 8 * 1024;                        // the smallest power of two that holds 1.5x an average tile
+                                                              // (tests/test_gpu_csv_strict_edges.py: STAGE_MIN, STAGE_MAX)
 
 struct CsvOpts {
     uint8_t comma, comment;   // comment 0 = none
@@ -822,7 +823,7 @@ __global__ __launch_bounds__(kCsvThreads) void k_csv_copy_fields(const uint8_t* 
     __shared__ uint64_t s_obase[kMaxKeyCols];
     __shared__ uint64_t s_range[2];
     __shared__ uint32_t s_scan[kCsvWaves + 1];
-    const uint32_t kOutCap = (uint32_t)stage_bytes + 32 * kMaxKeyCols;
+    const uint32_t kOutCap = (uint32_t)stage_bytes + 32 * kMaxKeyCols;   // tests/test_gpu_csv_strict_edges.py: out_cap(), copy_fits()
     CPH_LDS uint8_t* stage = (CPH_LDS uint8_t*)smem;
     CPH_LDS uint8_t* ostage = stage + (stage_bytes + 16);
     CPH_LDS uint16_t* cmask = (CPH_LDS uint16_t*)(ostage + kOutCap);
@@ -830,7 +831,7 @@ __global__ __launch_bounds__(kCsvThreads) void k_csv_copy_fields(const uint8_t* 
     CPH_LDS uint32_t* off32 = (CPH_LDS uint32_t*)(qmask + csv_mask_halves(stage_bytes));
     // record bounds, lengths and tile bases are loaded one tile AHEAD (k_csv_fields does the same): they are in flight while the
     // tile before is staged, parsed and flushed
-    constexpr int kPre = 4;   // columns whose lengths and bases are prefetched (registers); any further column is loaded in its tile
+    constexpr int kPre = 4;   // (tests/test_gpu_csv_strict_edges.py: K_PRE) columns whose lengths and bases are prefetched (registers); any further column is loaded in its tile
     uint32_t nlen[kPre];
     uint64_t nbase[kPre], nb = 0, ne = 0;
     auto prefetch = [&](uint64_t r0) {
@@ -950,7 +951,7 @@ __global__ __launch_bounds__(kCsvThreads) void k_csv_copy_fields(const uint8_t* 
 // ================================================================================================================
 constexpr int kFtThreads = 320;
 constexpr int kFtWaves = kFtThreads / kWave;
-constexpr int kFtStage = kFtThreads * 64;   // 20 KiB staged per 16 KiB tile: a record may run 4 KiB past its tile
+constexpr int kFtStage = kFtThreads * 64;   // 20 KiB staged per 16 KiB tile: a record may run 4 KiB past its tile (tests/test_gpu_csv_strict_edges.py: FT_STAGE)
 constexpr int kFtOwn = kCsvTile / 64;       // the chunks (threads) of the tile's own 16 KiB
 constexpr int kFtMaxCols = 8;
 static_assert(kFtStage > kCsvTile && kFtStage % 64 == 0, "a tile's stage must reach past its end");
@@ -1601,10 +1602,10 @@ static int32_t csv_parse_any(cph_ctx* ctx, const uint8_t* data, uint64_t size, i
         // (small stages leave room for more workgroups per CU; tiles that do not fit are parsed from global memory)
         int stage_bytes = kCsvStageMin;
         if (nrec)
-            while (stage_bytes < kCsvStageMax && (double)stage_bytes < 1.5 * 256.0 * (double)size / (double)nrec) stage_bytes *= 2;
+            while (stage_bytes < kCsvStageMax && (double)stage_bytes < 1.5 * 256.0 * (double)size / (double)nrec) stage_bytes *= 2;   // tests/test_gpu_csv_strict_edges.py: stage_bytes()
         // tiles of 256 records, aligned so that the first returned record starts one (k_csv_fields); their per-column byte totals
         const uint64_t skip_eff = std::min<uint64_t>(opt->skip_records, nrec);
-        const uint32_t pad = (uint32_t)((kCsvThreads - skip_eff % kCsvThreads) % kCsvThreads);
+        const uint32_t pad = (uint32_t)((kCsvThreads - skip_eff % kCsvThreads) % kCsvThreads);   // tests/test_gpu_csv_strict_edges.py: pad_of()
         const uint64_t ntile = (nrec + pad + kCsvThreads - 1) / kCsvThreads;
         const uint64_t T0 = (skip_eff + pad) / kCsvThreads;
         DevBuf tile_tot;

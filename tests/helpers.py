@@ -60,6 +60,18 @@ def random_keys(rng, n, min_len=0, max_len=12, alphabet=None, distinct=None):
     return pool
 
 
+def spliced(pre, post, boundary, total=40 * 1024):
+    """~40 KiB of short plain records with pre + post spliced in at a record start so that post begins at `boundary`."""
+    p0 = boundary - len(pre)
+    assert p0 >= 2
+    k = (p0 - 2) // 15                     # records of 15 bytes, then one padded to the byte
+    head = b"".join(b"r%05d,abc,xyz\n" % i for i in range(k))
+    head += b"x" * (p0 - len(head) - 1) + b"\n"
+    assert len(head) == p0
+    tail = b"".join(b"t%05d,abc,xyz\n" % i for i in range(max(0, total - boundary) // 15 + 1))
+    return head + pre + post + tail
+
+
 def assert_join_equal(gpu_matches, oracle_join, check_lo=True):
     """Bit-exact comparison of a cph_matches (host) with the oracle's join output."""
     cnt = gpu_matches.cnt

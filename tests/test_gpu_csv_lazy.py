@@ -13,6 +13,7 @@ from oracle import orc
 from tests import lazy_csv_model as M
 from tests.golden.go_csv_lazy_cases import LAZY_CASES
 from tests.golden.go_csv_reader_cases import CASES
+from tests.helpers import spliced as _spliced
 
 pytestmark = pytest.mark.gpu
 
@@ -117,18 +118,6 @@ _HAZARDS = {
     "CM_quote_in_comment": (b'#c "', b'd" e\nq,r\n', M.CM),
 }
 _BOUNDARIES = [b + d for b in (16, 1024, 4096, TILE, 2 * TILE) for d in (0, 1)]
-
-
-def _spliced(pre, post, boundary, total=40 * 1024):
-    """~40 KiB of short plain records with pre + post spliced in at a record start so that post begins at `boundary`."""
-    p0 = boundary - len(pre)
-    assert p0 >= 2
-    k = (p0 - 2) // 15                     # records of 15 bytes, then one padded to the byte
-    head = b"".join(b"r%05d,abc,xyz\n" % i for i in range(k))
-    head += b"x" * (p0 - len(head) - 1) + b"\n"
-    assert len(head) == p0
-    tail = b"".join(b"t%05d,abc,xyz\n" % i for i in range(max(0, total - boundary) // 15 + 1))
-    return head + pre + post + tail
 
 
 @pytest.mark.parametrize("name", list(_HAZARDS))
