@@ -20,7 +20,7 @@ all: hip datagen oracle host
 hip: $(LIBDIR)/libcsvplus_hip.so
 datagen: $(LIBDIR)/libcph_datagen.so
 oracle: oracle/_build/liboracle.so oracle/_build/libfaithful.so
-host: tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_host_encode tests/cpp/test_numformat tests/cpp/test_strpred tests/cpp/test_strpred_facade tests/cpp/test_hash_model tests/cpp/test_orderkey tests/cpp/test_order tests/cpp/test_csv_lazy tests/cpp/test_timeparse tests/cpp/test_time tests/cpp/test_floatparse tests/cpp/test_shortfmt tests/cpp/test_map_shortest tests/cpp/test_num_report tests/c/abi_demo tests/c/libnccl_standin.so
+host: tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_expr_cond tests/cpp/test_host_encode tests/cpp/test_numformat tests/cpp/test_strpred tests/cpp/test_strpred_facade tests/cpp/test_hash_model tests/cpp/test_orderkey tests/cpp/test_order tests/cpp/test_csv_lazy tests/cpp/test_timeparse tests/cpp/test_time tests/cpp/test_floatparse tests/cpp/test_shortfmt tests/cpp/test_map_shortest tests/cpp/test_num_report tests/c/abi_demo tests/c/libnccl_standin.so
 
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(LIBDIR)/obj
@@ -72,6 +72,9 @@ tests/cpp/test_map_float: tests/cpp/test_map_float.cpp csvplus_amd/host/csvplus.
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -Icsvplus_amd/host $< -L$(LIBDIR) -lcsvplus_hip -Wl,-rpath,'$$ORIGIN/../../csvplus_amd/lib' -o $@
 
 tests/cpp/test_expr: tests/cpp/test_expr.cpp csvplus_amd/host/csvplus.hpp include/csvplus_hip.h $(LIBDIR)/libcsvplus_hip.so
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -Icsvplus_amd/host $< -L$(LIBDIR) -lcsvplus_hip -Wl,-rpath,'$$ORIGIN/../../csvplus_amd/lib' -o $@
+
+tests/cpp/test_expr_cond: tests/cpp/test_expr_cond.cpp csvplus_amd/host/csvplus.hpp include/csvplus_hip.h $(LIBDIR)/libcsvplus_hip.so
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -Icsvplus_amd/host $< -L$(LIBDIR) -lcsvplus_hip -Wl,-rpath,'$$ORIGIN/../../csvplus_amd/lib' -o $@
 
 # the Map kernels' float formatter compiled for the host, against glibc's exact "%.*f" (CPU only)
@@ -166,6 +169,6 @@ oracle/_build/datagen_asan: tests/c/datagen_check.c $(CSRC)/datagen.c
 	$(CC) $(SAN) -fopenmp -Wall tests/c/datagen_check.c -o $@
 
 clean:
-	rm -rf $(LIBDIR) oracle/_build tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_numformat tests/cpp/test_strpred tests/cpp/test_strpred_facade tests/cpp/test_host_encode tests/cpp/test_hash_model tests/cpp/test_orderkey tests/cpp/test_order tests/cpp/test_csv_lazy tests/cpp/test_timeparse tests/cpp/test_time tests/cpp/test_floatparse tests/cpp/test_shortfmt tests/cpp/test_map_shortest tests/cpp/test_num_report tests/c/abi_demo tests/c/libnccl_standin.so
+	rm -rf $(LIBDIR) oracle/_build tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_expr_cond tests/cpp/test_numformat tests/cpp/test_strpred tests/cpp/test_strpred_facade tests/cpp/test_host_encode tests/cpp/test_hash_model tests/cpp/test_orderkey tests/cpp/test_order tests/cpp/test_csv_lazy tests/cpp/test_timeparse tests/cpp/test_time tests/cpp/test_floatparse tests/cpp/test_shortfmt tests/cpp/test_map_shortest tests/cpp/test_num_report tests/c/abi_demo tests/c/libnccl_standin.so
 
 .PHONY: all hip datagen oracle host asan clean

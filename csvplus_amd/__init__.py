@@ -22,7 +22,7 @@ materialize.order_rows; the contract in pure Python: order_model),
 from . import _native as native  # noqa: F401
 from ._native import CphError, NativeLibraryMissing, Context, DeviceIndex, Matches, Chain, join_chain  # noqa: F401
 from .columns import StrCol  # noqa: F401
-from .predicates import Like, All, Any, Not, IntCmp, FloatCmp, TimeCmp  # noqa: F401
+from .predicates import Like, All, Any, Not, IntCmp, FloatCmp, TimeCmp, ExprCmp, ColCmp  # noqa: F401
 
 __all__ = ["native", "CphError", "NativeLibraryMissing", "Context", "DeviceIndex", "Matches", "Chain", "join_chain", "StrCol",
-           "Like", "All", "Any", "Not", "IntCmp", "FloatCmp", "TimeCmp"]
+           "Like", "All", "Any", "Not", "IntCmp", "FloatCmp", "TimeCmp", "ExprCmp", "ColCmp"]

@@ -153,6 +153,8 @@ CPH_PRED_FLT_LT, CPH_PRED_FLT_LE, CPH_PRED_FLT_EQ, CPH_PRED_FLT_NE, CPH_PRED_FLT
 CPH_PRED_STR_LT, CPH_PRED_STR_LE, CPH_PRED_STR_EQ, CPH_PRED_STR_NE, CPH_PRED_STR_GE, CPH_PRED_STR_GT = 32, 33, 34, 35, 36, 37
 CPH_PRED_HAS_PREFIX, CPH_PRED_HAS_SUFFIX, CPH_PRED_CONTAINS = 40, 41, 42
 CPH_PRED_TIME_LT, CPH_PRED_TIME_LE, CPH_PRED_TIME_EQ, CPH_PRED_TIME_NE, CPH_PRED_TIME_GE, CPH_PRED_TIME_GT = 48, 49, 50, 51, 52, 53
+CPH_PRED_EXPR_LT, CPH_PRED_EXPR_LE, CPH_PRED_EXPR_EQ, CPH_PRED_EXPR_NE, CPH_PRED_EXPR_GE, CPH_PRED_EXPR_GT = 56, 57, 58, 59, 60, 61
+CPH_PRED_COLS_LT, CPH_PRED_COLS_LE, CPH_PRED_COLS_EQ, CPH_PRED_COLS_NE, CPH_PRED_COLS_GE, CPH_PRED_COLS_GT = 72, 73, 74, 75, 76, 77
 CPH_PRED_MAX_OPS, CPH_PRED_MAX_LIKE, CPH_PRED_MAX_STACK = 64, 32, 32
 CPH_FILTER_WHERE, CPH_FILTER_TAKE_WHILE, CPH_FILTER_DROP_WHILE = 0, 1, 2
 CPH_NO_LIMIT = 0xFFFFFFFFFFFFFFFF
@@ -199,6 +201,10 @@ class cph_expr_op(C.Structure):
 
 class cph_expr_nums(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("mem", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class cph_pred_expr(C.Structure):   # the value of a CPH_PRED_EXPR_* term
+    _fields_ = [("prog", C.POINTER(cph_expr_op)), ("nops", C.c_int32), ("nnums", C.c_int32), ("nums", C.POINTER(cph_expr_nums))]
 
 
 CPH_MAP_LITERAL, CPH_MAP_COLUMN, CPH_MAP_INT64, CPH_MAP_FLOAT64 = 1, 2, 3, 4

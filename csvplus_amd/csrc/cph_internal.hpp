@@ -1007,10 +1007,16 @@ Status convert_rows(cph_ctx* ctx, const DevCol& col, const RowIds& ids, uint64_t
                     DevBuf* status, NumColStats* st);
 
 // filter.hip: a cph_pred_op program evaluated into one bit per row — what cph_filter_rows (WHERE) and cph_map_switch share.
+// which outcomes of (a ? b) make a relation hold: bits 8..11 of a comparing term's kind (filter.hip), k_expr_cmp's `rel` (expr_eval.hip)
+enum : uint32_t { kCmpLess = 1, kCmpEqual = 2, kCmpGreater = 4, kCmpUnordered = 8 };
 struct PredFloatCol {   // a column converted for the float or time terms of a call: one conversion, whichever program asks first
     int col;
     int32_t kind = CPH_NUM_FLOAT64;   // ... or CPH_NUM_TIME_UNIX: the same column may be converted once as each
     DevBuf values, status;
+    // kind == 0, col == -1: no column but ONE expression term's bits (k_expr_cmp) and the arrays its kernel read.  Never looked up,
+    // so no program reuses another's: it only lives here as long as the call.
+    TileBitmap bits;
+    std::vector<DevBuf> hold;
 };
 struct PredBitmap {
     TileBitmap rows;   // bit = the program holds for that row of the call
@@ -1019,9 +1025,18 @@ struct PredBitmap {
 // every rule of cph_filter_rows' comment about the program that does not need the columns
 Status check_pred_program(const cph_pred_op* prog, int32_t nops, int32_t ncols);
 // Terms, literal block and float-column conversion (into *fcols, reused from it), then k_pred_eval<true, NUM> over rows
-// [first_row, first_row + n) of the staged row sources; n > 0 and the program has passed check_pred_program.
+// [first_row, first_row + n) of the staged row sources; n > 0 and the program has passed check_pred_program.  An expression term is
+// evaluated first (expr_cmp_bitmap, its bitmap appended to *fcols); a program of exactly one such op returns that bitmap as the
+// result and launches no k_pred_eval.
 Status pred_eval_bitmap(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, const cph_pred_op* prog, int32_t nops, uint64_t first_row,
                         uint64_t n, std::vector<PredFloatCol>* fcols, PredBitmap* out);
+// expr_eval.hip: an expression term (CPH_PRED_EXPR_*).  check_pred_expr: every rule of the term's value (one cph_pred_expr) that does
+// not need the columns' data.  expr_cmp_bitmap: k_expr_cmp over rows [first_row, first_row + n) into *out, a complete TileBitmap
+// (words and counts; n > 0); rel = the kCmp* outcomes under which the relation holds; *hold keeps what the kernel reads.  Waits for
+// the stream only when the program has a COL_FLT leaf (the deferred rows' count).
+Status check_pred_expr(const cph_strval& value, int32_t ncols);
+Status expr_cmp_bitmap(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, const cph_strval& value, uint32_t rel, uint64_t first_row, uint64_t n,
+                       TileBitmap* out, std::vector<DevBuf>* hold);
 
 }  // namespace cph
 

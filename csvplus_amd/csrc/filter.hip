@@ -35,6 +35,17 @@
 // (CPH_NUM_TIME_UNIX, once per column and call) and k_pred_eval compares the int64 seconds with their status; the literal is RFC
 // 3339 text the host converts with the same routine (timeparse_device.hpp).  A program with such a term launches the TIM = true
 // instantiations (which carry the numeric code too); every other program launches exactly what it launched before.
+//
+// Two more term kinds, behind template flags of their own (BITS, COLS) so that the twelve instantiations above stay the kernels they
+// are (profiles/expr_conditions.txt):
+//   CPH_PRED_EXPR_*  two numeric expressions compared.  k_expr_cmp (expr_eval.hip) evaluates the term FIRST into a TileBitmap of its
+//                    own, kept beside the converted float columns for the call; here the term is kTermBits: row i of the call is bit
+//                    i & 63 of word i >> 6, one wave-uniform 8-byte load per 64 rows.  A WHERE (or Switch-case) program that consists
+//                    of exactly one such op is answered with that bitmap: no k_pred_eval is launched.
+//   CPH_PRED_COLS_*  two columns of the row compared as strings: str_compare with the second column's value (its own value_span and
+//                    source_row: another layout, other row ids) in the literal's place, kTermColCmp.
+// A program with either launches one of five further instantiations: the lean ones of a program without numeric and time terms, or
+// the one that carries every term kind.
 // The way from a cph_pred_op program to the bitmap (terms, literal block, float columns, the k_pred_eval<true, NUM> launch) is
 // pred_eval_bitmap (cph_internal.hpp): the WHERE mode calls it, and so does cph_map_switch (map_switch.hip), once per case.
 #include <algorithm>
@@ -56,9 +67,11 @@ constexpr int kLitLds    = 4096;                       // literal bytes kept in 
 
 enum : uint32_t { kTermBytes = 0, kTermFix8 = 1, kTermInt = 2, kTermF64 = 3,     // low byte of PredTerm::kind
                   kTermStrCmp = 4, kTermPrefix = 5, kTermSuffix = 6, kTermContains = 7,    // STR instantiations only
-                  kTermTime = 8 };                                                          // TIM instantiations only
-// bits 8..11 of a numeric or kTermStrCmp term's kind: which outcomes of (value ? literal) make the relation hold
-enum : uint32_t { kCmpLess = 1, kCmpEqual = 2, kCmpGreater = 4, kCmpUnordered = 8 };
+                  kTermTime = 8,                                                            // TIM instantiations only
+                  kTermBits = 9,                                                            // BITS instantiations only
+                  kTermColCmp = 10 };                                                       // COLS instantiations only
+// bits 8..11 of a numeric, kTermStrCmp or kTermColCmp term's kind: which outcomes of (value ? literal) make the relation hold (kCmp*,
+// cph_internal.hpp)
 constexpr uint8_t kTermNever = 0xFF;                   // a LIKE decided on the host: no such column, or a fixed width other than the literal's
 
 // One LIKE over a real column.  A literal of at most 8 bytes is lit8 (zero padded); a longer one lies in the literal
@@ -70,6 +83,8 @@ struct PredTerm {
     uint32_t kind;   // kTermFix8: a fixed-width column of 8 bytes on an 8-byte aligned base — one aligned load and one compare
                      // kTermInt / kTermF64 / kTermTime: lit8 = the literal's bits (kTermTime: its Unix seconds), the relation in bits 8..11
                      // kTermStrCmp .. kTermContains: the literal as a LIKE's (lit8 / lit_off, len); kTermStrCmp: the relation in bits 8..11
+                     // kTermBits: an expression term k_expr_cmp has evaluated: fval = the bitmap's words, row i of the call = word i >> 6, bit i & 63
+                     // kTermColCmp: col REL the column lit_off (both >= 0), the relation in bits 8..11
     const double*  fval;   // kTermF64 / kTermTime: the converted column (kTermTime: int64 seconds), entry i = row first_row + i of the selection ...
     const uint8_t* fstat;  // ... and its CPH_NUM_* status bytes
 };
@@ -102,6 +117,11 @@ struct ValueChunks {
     uint64_t begin;
     __device__ __forceinline__ uint64_t operator()(uint64_t off, uint64_t len, int j) const { return load_value_chunk(data, begin + off, len, j); }
 };
+struct ValueWords {   // a second column's value in the literal's place (kTermColCmp): word j of its len bytes
+    const uint8_t* data;
+    uint64_t begin, len;
+    __device__ __forceinline__ uint64_t operator()(uint64_t j) const { return load_value_chunk(data, begin, len, (int)j); }
+};
 struct LiteralWords {
     const PredTerm& t;
     const uint64_t* glits;
@@ -126,8 +146,9 @@ __device__ __forceinline__ bool str_term(uint32_t what, uint32_t rel, const DevC
 
 // BITMAP: bit = the predicate holds for that row of the call, in the layout of tile_bitmap.hpp.
 // else:   *first_fail = min(*first_fail, the first row where it does not hold); the host presets it to n.
-// STR: the program has a term of strpred_device.hpp; NUM: a numeric one; TIM (with NUM): a time term
-template <bool BITMAP, bool NUM, bool STR = false, bool TIM = false>
+// STR: the program has a term of strpred_device.hpp; NUM: a numeric one; TIM (with NUM): a time term; BITS: an expression term's
+// bits; COLS (with STR): a column-against-column term.  The instantiations without BITS and COLS are the kernels they were.
+template <bool BITMAP, bool NUM, bool STR = false, bool TIM = false, bool BITS = false, bool COLS = false>
 __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds ids, PredProg prog, uint64_t first_row, uint64_t n,
                                                           uint64_t* __restrict__ bitmap, uint32_t* __restrict__ counts,
                                                           unsigned long long* first_fail) {
@@ -215,6 +236,28 @@ __global__ __launch_bounds__(kMatThreads) void k_pred_eval(ColsArg cols, ColIds 
                     for (int k = 0; k < kFiltPhase; k++) {
                         const uint32_t cls = v[k] < lit ? kCmpLess : v[k] == lit ? kCmpEqual : kCmpGreater;
                         mask[k] |= (uint32_t)(st[k] == CPH_NUM_OK && (rel & cls) != 0) << t;   // a row that does not convert: false
+                    }
+                } else if (BITS && (tm.kind & 0xFFu) == kTermBits) {
+                    const uint64_t* words = reinterpret_cast<const uint64_t*>(tm.fval);
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {   // wave-uniform: one 8-byte load per 64 rows (a tile's 32 words are all written)
+                        const uint64_t w = words[tile * kTileWords + (uint64_t)(wave * kTileWaveWords + ph * kFiltPhase + k)];
+                        mask[k] |= (uint32_t)((w >> lane) & 1ull) << t;
+                    }
+                } else if (COLS && (tm.kind & 0xFFu) == kTermColCmp) {
+                    const uint32_t rel = tm.kind >> 8;
+                    const DevCol& colb = cols.c[tm.lit_off];
+                    const RowIds& ridb = ids.ids[tm.lit_off];
+                    uint64_t b[kFiltPhase], l[kFiltPhase], b2[kFiltPhase], l2[kFiltPhase];
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {
+                        value_span(col, source_row(rid, pos[k]), &b[k], &l[k]);
+                        value_span(colb, source_row(ridb, pos[k]), &b2[k], &l2[k]);
+                    }
+#pragma unroll
+                    for (int k = 0; k < kFiltPhase; k++) {
+                        const int c = str_compare(ValueChunks{col.data, b[k]}, l[k], ValueWords{colb.data, b2[k], l2[k]}, l2[k]);
+                        mask[k] |= (uint32_t)((rel & (c < 0 ? kCmpLess : c == 0 ? kCmpEqual : kCmpGreater)) != 0) << t;
                     }
                 } else if (STR && (tm.kind & 0xFFu) >= kTermStrCmp) {
                     const uint32_t what = tm.kind & 0xFFu, rel = tm.kind >> 8;   // uniform: the wave diverges on the values' lengths alone
@@ -401,6 +444,27 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
                 depth++;
                 break;
             }
+            case CPH_PRED_EXPR_LT: case CPH_PRED_EXPR_LE: case CPH_PRED_EXPR_EQ: case CPH_PRED_EXPR_NE: case CPH_PRED_EXPR_GE: case CPH_PRED_EXPR_GT: {
+                if (o.arg != 0 && o.arg != -1) return {CPH_ERR_INVALID, "cph_filter_rows: expression term: arg is 0, or -1 for a column the rows lack"};
+                if (o.arg == 0) {   // arg == -1: the value is ignored
+                    Status s = check_pred_expr(o.value, ncols);
+                    if (!s.ok()) return s;
+                }
+                if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE, numeric, string, time, expression and column terms"};
+                depth++;
+                break;
+            }
+            case CPH_PRED_COLS_LT: case CPH_PRED_COLS_LE: case CPH_PRED_COLS_EQ: case CPH_PRED_COLS_NE: case CPH_PRED_COLS_GE: case CPH_PRED_COLS_GT: {
+                if (o.arg < -1 || o.arg >= ncols) return {CPH_ERR_INVALID, "cph_filter_rows: column-against-column term: column outside -1..ncols-1"};
+                if (!o.value.data || o.value.len != 4)
+                    return {CPH_ERR_INVALID, "cph_filter_rows: column-against-column term: value is exactly 4 bytes (the int32_t second column) behind a non-NULL pointer"};
+                int32_t b = 0;
+                memcpy(&b, o.value.data, 4);
+                if (b < -1 || b >= ncols) return {CPH_ERR_INVALID, "cph_filter_rows: column-against-column term: second column outside -1..ncols-1"};
+                if (++likes > CPH_PRED_MAX_LIKE) return {CPH_ERR_INVALID, "cph_filter_rows: more than 32 LIKE, numeric, string, time, expression and column terms"};
+                depth++;
+                break;
+            }
             case CPH_PRED_NOT:
                 if (depth < 1) return {CPH_ERR_INVALID, "cph_filter_rows: stack underflow (NOT on an empty stack)"};
                 break;
@@ -410,7 +474,7 @@ Status check_program(const cph_pred_op* prog, int32_t nops, int32_t ncols) {
                 depth += 1 - o.arg;
                 break;
             default:
-                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4, 16..21, 24..29, 32..37, 40..42, 48..53)"};
+                return {CPH_ERR_INVALID, "cph_filter_rows: unknown op (1..4, 16..21, 24..29, 32..37, 40..42, 48..53, 56..61, 72..77)"};
         }
         if (depth > CPH_PRED_MAX_STACK) return {CPH_ERR_INVALID, "cph_filter_rows: stack deeper than 32"};
     }
@@ -422,6 +486,8 @@ bool is_int_cmp(int32_t op) { return op >= CPH_PRED_INT_LT && op <= CPH_PRED_INT
 bool is_flt_cmp(int32_t op) { return op >= CPH_PRED_FLT_LT && op <= CPH_PRED_FLT_GT; }
 bool is_str_cmp(int32_t op) { return op >= CPH_PRED_STR_LT && op <= CPH_PRED_STR_GT; }
 bool is_time_cmp(int32_t op) { return op >= CPH_PRED_TIME_LT && op <= CPH_PRED_TIME_GT; }
+bool is_expr_cmp(int32_t op) { return op >= CPH_PRED_EXPR_LT && op <= CPH_PRED_EXPR_GT; }
+bool is_cols_cmp(int32_t op) { return op >= CPH_PRED_COLS_LT && op <= CPH_PRED_COLS_GT; }
 bool is_str_term(int32_t op) { return is_str_cmp(op) || (op >= CPH_PRED_HAS_PREFIX && op <= CPH_PRED_CONTAINS); }
 // LT LE EQ NE GE GT -> the outcomes under which the relation holds (IEEE: unordered satisfies NE alone)
 uint32_t rel_outcomes(int32_t rel) {
@@ -436,6 +502,9 @@ struct BuiltProg {   // a program as k_pred_eval takes it
     bool numeric = false;   // the NUM instantiations
     bool strings = false;   // the STR instantiations
     bool times = false;     // the TIM instantiations
+    bool bits = false;      // the BITS instantiations: an expression term
+    bool colcmp = false;    // the COLS instantiations: a column-against-column term
+    size_t expr_term = 0;   // bits: the last expression term's entry of the call's PredFloatCol vector
 };
 
 // fcols: the float columns converted so far in this call (reused, appended to)
@@ -475,6 +544,49 @@ Status build_pred_prog(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, cons
             }
             t.fval = (*fcols)[f].values.as<double>();
             t.fstat = (*fcols)[f].status.as<uint8_t>();
+            continue;
+        }
+        if (is_expr_cmp(prog[q].op)) {   // a term bit k_expr_cmp evaluates first: a bitmap of its own, kept beside the float columns
+            pp.op[q] = (uint8_t)CPH_PRED_LIKE;
+            if (prog[q].arg < 0) {
+                pp.arg[q] = kTermNever;
+                continue;
+            }
+            bp->bits = true;
+            fcols->emplace_back();
+            PredFloatCol& e = fcols->back();
+            e.col = -1, e.kind = 0;
+            CPH_TRY(expr_cmp_bitmap(ctx, arg, ids, prog[q].value, rel_outcomes(prog[q].op - CPH_PRED_EXPR_LT), first_row, n, &e.bits, &e.hold));
+            bp->expr_term = fcols->size() - 1;
+            PredTerm& t = pp.term[pp.nterms];
+            pp.arg[q] = (uint8_t)pp.nterms++;
+            t.col = 0;
+            t.kind = kTermBits;
+            t.fval = reinterpret_cast<const double*>(e.bits.words());
+            bp->col_bytes += (double)n / 8.0;
+            continue;
+        }
+        if (is_cols_cmp(prog[q].op)) {
+            int32_t c2 = 0;
+            memcpy(&c2, prog[q].value.data, 4);
+            const int c = prog[q].arg;
+            pp.op[q] = (uint8_t)CPH_PRED_LIKE;
+            if (c < 0 || c2 < 0) {
+                pp.arg[q] = kTermNever;
+                continue;
+            }
+            bp->strings = bp->colcmp = true;
+            PredTerm& t = pp.term[pp.nterms];
+            pp.arg[q] = (uint8_t)pp.nterms++;
+            t.col = c;
+            t.lit_off = (uint32_t)c2;
+            t.kind = kTermColCmp | (rel_outcomes(prog[q].op - CPH_PRED_COLS_LT) << 8);
+            for (const int k : {c, (int)c2}) {   // byte model: offsets (or nothing) + ~8 value bytes, once per column
+                if ((seen_cols >> k) & 1u) continue;
+                seen_cols |= 1u << k;
+                bp->col_bytes += arg.c[k].fixed_width ? (double)arg.c[k].fixed_width * (double)n : ((double)(arg.c[k].offset_bits / 8) + 8.0) * (double)n;
+                if (ids.ids[k].ptr) bp->col_bytes += (double)(ids.ids[k].bits / 8) * (double)n;
+            }
             continue;
         }
         if (is_int_cmp(prog[q].op) || is_flt_cmp(prog[q].op)) {   // a term bit like a LIKE: the kernel's program sees a LIKE
@@ -564,7 +676,19 @@ template <bool BITMAP>
 void launch_pred_eval(cph_ctx* ctx, const BuiltProg& bp, const ColsArg& arg, const ColIds& ids, uint64_t first_row, uint64_t n, uint64_t ntiles,
                       uint64_t* bitmap, uint32_t* counts, unsigned long long* first_fail) {
     const dim3 grid(tile_grid(ntiles)), block(kMatThreads);
-    if (bp.times && bp.strings)
+    if (bp.bits || bp.colcmp) {   // the new terms: the lean kernel of a program without numeric and time terms, else the one with every kind
+        const bool lean = !bp.numeric && !bp.times;
+        if (!lean)
+            hipLaunchKernelGGL((k_pred_eval<BITMAP, true, true, true, true, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+        else if (bp.colcmp && bp.bits)
+            hipLaunchKernelGGL((k_pred_eval<BITMAP, false, true, false, true, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+        else if (bp.colcmp)
+            hipLaunchKernelGGL((k_pred_eval<BITMAP, false, true, false, false, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+        else if (bp.strings)
+            hipLaunchKernelGGL((k_pred_eval<BITMAP, false, true, false, true, false>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+        else
+            hipLaunchKernelGGL((k_pred_eval<BITMAP, false, false, false, true, false>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
+    } else if (bp.times && bp.strings)
         hipLaunchKernelGGL((k_pred_eval<BITMAP, true, true, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
     else if (bp.times)
         hipLaunchKernelGGL((k_pred_eval<BITMAP, true, false, true>), grid, block, 0, ctx->stream, arg, ids, bp.pp, first_row, n, bitmap, counts, first_fail);
@@ -589,6 +713,13 @@ Status pred_eval_bitmap(cph_ctx* ctx, const ColsArg& arg, const ColIds& ids, con
     BuiltProg bp;
     CPH_TRY(build_pred_prog(ctx, arg, ids, prog, nops, first_row, n, fcols, &bp));
     TileBitmap& tb = out->rows;
+    if (nops == 1 && bp.bits) {   // the program IS one expression term: k_expr_cmp's bitmap is the answer, no k_pred_eval
+        PredFloatCol& e = (*fcols)[bp.expr_term];
+        tb.bitmap = std::move(e.bits.bitmap);
+        tb.tile_counts = std::move(e.bits.tile_counts);
+        tb.ntiles = e.bits.ntiles;
+        return {};
+    }
     CPH_TRY(tb.alloc(ctx, n));
     {
         ProfScope ps(ctx, bp.strings ? "k_pred_eval_str" : "k_pred_eval", bp.col_bytes + (double)n / 8.0 + 4.0 * (double)tb.ntiles);

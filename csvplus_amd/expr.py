@@ -22,8 +22,8 @@ guess).  Within one row the first failing op in program order decides the row's 
 
 `compile` turns a tree into the postfix program cph_num_eval takes, `check_ops` states the ABI's typing rules and limits
 over a raw program, `evaluate` runs the tree on one row held as a dict — the host model, for callers without a GPU and as
-the cross-check of the device.  Nothing here touches the GPU.  Comparisons, math functions, rounding helpers and string
-operands are out of scope.
+the cross-check of the device.  Nothing here touches the GPU.  Comparing two expressions is a predicate (predicates.ExprCmp,
+over compile_pair); boolean-valued ops, math functions, rounding helpers and string operands are out of scope.
 """
 from __future__ import annotations
 
@@ -194,13 +194,14 @@ def columns(expr) -> list:
     return names
 
 
-def check_ops(ops, ncols: int, nnums: int) -> tuple:
+def check_ops(ops, ncols: int, nnums: int, want: int = 1) -> tuple:
     """The ABI's rules over a raw program of (op, arg, ...) tuples: (result type, deepest stack, [type each op pushes]).
     Raises TypeError for what cph_num_eval refuses with CPH_ERR_INVALID: an unknown op, an arg outside its table, mixed or
     wrong operand types, a missing operand, more than MAX_OPS ops, a stack deeper than MAX_STACK, more than MAX_NUMS arrays
-    or MAX_COLUMNS columns, a program that does not leave exactly one value."""
-    if not 1 <= len(ops) <= MAX_OPS:
-        raise TypeError(f"a program has 1..{MAX_OPS} ops, not {len(ops)}")
+    or MAX_COLUMNS columns, a program that does not leave exactly one value.  want=2: the program of an expression term of
+    cph_filter_rows (predicates.ExprCmp), which leaves exactly two values of one type, lhs below rhs."""
+    if not want <= len(ops) <= MAX_OPS:
+        raise TypeError(f"a program has {want}..{MAX_OPS} ops, not {len(ops)}")
     if nnums > MAX_NUMS:
         raise TypeError(f"{nnums} number arrays, more than {MAX_NUMS}")
     if ncols > MAX_COLUMNS:
@@ -243,13 +244,16 @@ def check_ops(ops, ncols: int, nnums: int) -> tuple:
         stack.append(t)
         pushed.append(t)
         depth = max(depth, len(stack))
-    if len(stack) != 1:
-        raise TypeError(f"the program leaves {len(stack)} values, not exactly one")
+    if len(stack) != want:
+        raise TypeError(f"the program leaves {len(stack)} values, not exactly {'one' if want == 1 else 'two'}")
+    if want == 2 and stack[0] != stack[1]:
+        raise TypeError("int64 REL float64 mixes types (Go has no implicit conversions: use ToFloat / ToInt)")
     return stack[0], depth, pushed
 
 
-def compile(expr, column_names):   # noqa: A001 (the name predicates.compile and mapping.compile use)
-    """(names of the columns used, ops).  An op is (opcode, arg, value): COL_* — arg indexes the returned name list; NUM_* —
+def compile(expr, column_names, also=None):   # noqa: A001 (the name predicates.compile and mapping.compile use)
+    """(names of the columns used, ops).  also: a second expression whose ops follow in the same program, which then leaves
+    two values of one type (compile_pair).  An op is (opcode, arg, value): COL_* — arg indexes the returned name list; NUM_* —
     arg indexes `arrays(ops)` and value is the IntArr / FloatArr; LIT_* — value is the int / float; others — (op, 0, None).
     A column the rows lack raises mapping.MissingColumn; what the ABI would refuse raises TypeError (see check_ops)."""
     known = [str(c) for c in column_names]
@@ -285,8 +289,19 @@ def compile(expr, column_names):   # noqa: A001 (the name predicates.compile and
             raise TypeError(f"the expression compiles to more than {MAX_OPS} ops")
 
     walk(_node(expr))
-    check_ops(ops, len(used), len(arrs))
+    if also is not None:
+        walk(_node(also))
+    check_ops(ops, len(used), len(arrs), want=1 if also is None else 2)
     return used, ops
+
+
+def compile_pair(lhs, rhs, column_names):
+    """(names of the columns used, ops) of two expressions as ONE program that leaves lhs below rhs, both of one type: what an
+    expression term of cph_filter_rows takes (predicates.ExprCmp).  Each side is checked on its own first, so a typing error
+    names the side's own op."""
+    compile(lhs, column_names)
+    compile(rhs, column_names)
+    return compile(lhs, column_names, also=rhs)
 
 
 def arrays(ops) -> list:
@@ -333,9 +348,10 @@ def _float_binary(op, a, b):
     return a + b if op == ADD else a - b if op == SUB else a * b   # Python floats: IEEE doubles, one rounding each, never fused
 
 
-def run_ops(ops, leaf) -> tuple:
+def run_ops(ops, leaf, want: int = 1) -> tuple:
     """(value, status, op) of a compiled program on one row: leaf(q, op) -> (value, status) of leaf op q.  status is NUM_* /
-    NUM_ERR_DIV_ZERO / NUM_ERR_CONVERT, `op` the index of the first failing op (-1 without an error); an error gives value 0."""
+    NUM_ERR_DIV_ZERO / NUM_ERR_CONVERT, `op` the index of the first failing op (-1 without an error); an error gives value 0.
+    want=2 (a two-value program, check_ops): `value` is the pair (lhs, rhs)."""
     stack: list = []
     status, bad = NUM_OK, -1
     for q, o in enumerate(ops):
@@ -362,6 +378,8 @@ def run_ops(ops, leaf) -> tuple:
         if st != NUM_OK and status == NUM_OK:
             status, bad = st, q
         stack.append(v)
+    if want == 2:
+        return (stack[0], stack[1]), status, bad
     if status != NUM_OK:
         return (0 if isinstance(stack[0], int) else 0.0), status, bad
     return stack[0], NUM_OK, -1

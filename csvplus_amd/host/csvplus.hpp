@@ -26,7 +26,10 @@
 //   Row.ValueAsInt / ValueAsFloat64  :165-205    csvplus::ValueAsInt / ValueAsFloat64 (one row, on the host);
 //                                                DataSource::ColumnAsInt / ColumnAsFloat64 (a whole column, on the GPU);
 //                                                csvplus::IntCmp / FloatCmp: `v, err := row.ValueAsInt(c); err == nil && v REL k`
-//                                                as a predicate that composes with Like / All / Any / Not
+//                                                as a predicate that composes with Like / All / Any / Not;
+//                                                csvplus::ExprCmp(lhs, REL, rhs): two numeric expressions compared (`price(r) *
+//                                                float64(qty(r)) >= 100`, `died(r) > born(r)`); csvplus::ColCmp(a, REL, b): two
+//                                                columns of a row compared as strings (`r["ship"] != r["bill"]`)
 //   time.Parse(time.RFC3339, row[c])   (closures) DataSource::ColumnAsTime / ColumnAsTimeNano (t.Unix() / t.UnixNano() of a whole
 //                                                column, on the GPU); csvplus::TimeCmp(c, REL, "2016-09-14T00:00:00Z"): instants, not
 //                                                bytes; Rfc3339(expr or Col, zone_minutes) as a Format part: Unix seconds written
@@ -66,6 +69,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <deque>
 #include <functional>
 #include <map>
 #include <memory>
@@ -353,11 +357,17 @@ inline bool FormatRfc3339(int64_t v, int zone, std::string* out) {
     return true;
 }
 
+class Expr;
 class Pred {
 public:
-    enum Kind { kLike, kNot, kAll, kAny, kIntCmp, kFloatCmp, kStrCmp, kHasPrefix, kHasSuffix, kContains, kTimeCmp };
+    enum Kind { kLike, kNot, kAll, kAny, kIntCmp, kFloatCmp, kStrCmp, kHasPrefix, kHasSuffix, kContains, kTimeCmp, kExprCmp, kColCmp };
     bool operator()(const Row& row) const {
         switch (kind_) {
+            case kExprCmp: return exprHolds(row);   // a row that lacks a column, or in which an op fails, is false under every relation
+            case kColCmp: {                         // bytes, as kStrCmp; a row without either column is false under every relation
+                auto a = row.find(column_), b = row.find(slit_);
+                return a != row.end() && b != row.end() && holds(a->second.compare(b->second), 0);
+            }
             case kTimeCmp: {   // a row without the column, or whose stamp does not convert, is false under every relation
                 auto it = row.find(column_);
                 int64_t v;
@@ -410,7 +420,9 @@ public:
     const std::string& column() const { return column_; }
     Rel rel() const { return rel_; }
     const void* literal() const { return kind_ == kIntCmp ? (const void*)&ilit_ : (const void*)&flit_; }   // 8 bytes
-    const std::string& text() const { return slit_; }   // kStrCmp .. kContains: the literal's bytes
+    const std::string& text() const { return slit_; }   // kStrCmp .. kContains: the literal's bytes; kColCmp: the second column's name
+    const Expr& lhs() const { return *lhs_; }           // kExprCmp
+    const Expr& rhs() const { return *rhs_; }
 
 private:
     template <class T>
@@ -429,6 +441,10 @@ private:
     friend Pred StrCmp(std::string column, Rel rel, std::string literal);
     friend Pred StrTest(Pred::Kind kind, std::string column, std::string literal);
     friend Pred TimeCmp(std::string column, Rel rel, std::string literal);
+    friend Pred ExprCmp(Expr lhs, Rel rel, Expr rhs);
+    friend Pred ColCmp(std::string a, Rel rel, std::string b);
+    bool exprHolds(const Row& row) const;   // defined behind Expr
+    std::shared_ptr<const Expr> lhs_, rhs_;
     std::string column_, slit_;
     Rel rel_ = EQ;
     int64_t ilit_ = 0;
@@ -493,6 +509,16 @@ inline Pred TimeCmp(std::string column, Rel rel, std::string literal) {
     if (ParseRfc3339(literal, false, &p.ilit_) != CPH_NUM_OK) throw Panic("TimeCmp(): the literal is no RFC 3339 timestamp this library converts");
     if (literal.find('.') != std::string::npos) throw Panic("TimeCmp(): the literal has a fraction (the term compares whole seconds)");
     p.slit_ = std::move(literal);
+    return p;
+}
+// ColCmp("ship_city", NE, "bill_city") is `row["ship_city"] != row["bill_city"]`: StrCmp's byte comparison with the second column's
+// value in the literal's place.  On the device it is AND-ed with the presence flags of both columns (see StrCmp): three terms.
+inline Pred ColCmp(std::string a, Rel rel, std::string b) {
+    Pred p;
+    p.kind_ = Pred::kColCmp;
+    p.column_ = std::move(a);
+    p.rel_ = rel;
+    p.slit_ = std::move(b);
     return p;
 }
 inline Pred HasPrefix(std::string column, std::string literal) { return StrTest(Pred::kHasPrefix, std::move(column), std::move(literal)); }
@@ -709,6 +735,29 @@ inline Expr operator-(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_SUB,
 inline Expr operator*(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_MUL, std::move(a), b); }
 inline Expr operator/(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_DIV, std::move(a), b); }
 inline Expr operator%(Expr a, const Expr& b) { return Expr::binary(CPH_EXPR_MOD, std::move(a), b); }
+
+// ExprCmp(AsFloat64(Col("price")) * Float64(AsInt(Col("qty"))), GE, 100.0) is `price(r) * float64(qty(r)) >= 100`, and
+// ExprCmp(AsInt(Col("died")), GT, AsInt(Col("born"))) a column against a column as numbers: both sides of one type (mixing them is a
+// Panic here, there are no implicit conversions), int64 compared signed, float64 as IEEE (with a NaN only NE holds).  A row in which
+// any op fails — a value that does not convert, a zero divisor, an Int() out of range — or that lacks a column without default is
+// false under every relation, NE included.  One term on the device (cph_filter_rows: CPH_PRED_EXPR_*), whatever the expressions.
+inline Pred ExprCmp(Expr lhs, Rel rel, Expr rhs) {
+    if (lhs.kind != rhs.kind) throw Panic("mismatched types int64 and float64 in ExprCmp() (there are no implicit conversions)");
+    if (lhs.ops.size() + rhs.ops.size() > (size_t)CPH_EXPR_MAX_OPS) throw Panic("ExprCmp(): more than 32 ops on both sides together");
+    Expr::binary(CPH_EXPR_SUB, lhs, rhs);   // the stack of rhs on top of lhs, and the columns of both: Panics beyond the ABI's limits
+    Pred p;
+    p.kind_ = Pred::kExprCmp;
+    p.rel_ = rel;
+    p.lhs_ = std::make_shared<const Expr>(std::move(lhs));
+    p.rhs_ = std::make_shared<const Expr>(std::move(rhs));
+    return p;
+}
+inline bool Pred::exprHolds(const Row& row) const {
+    int64_t ai = 0, bi = 0;
+    double af = 0, bf = 0;
+    if (lhs_->eval(row, &ai, &af, nullptr, nullptr) != CPH_NUM_OK || rhs_->eval(row, &bi, &bf, nullptr, nullptr) != CPH_NUM_OK) return false;
+    return lhs_->kind == CPH_NUM_INT64 ? holds(ai, bi) : holds(af, bf);
+}
 
 struct Fixed {
     Col col;
@@ -1012,6 +1061,9 @@ struct PredProgram {
     std::vector<int> flag_of;           // per column: -1, or this staged column is the PRESENCE FLAG of that column ("1" / "")
     std::vector<cph_pred_op> ops;       // literal pointers point into `pred`
     std::shared_ptr<const Pred> pred;
+    std::deque<std::vector<cph_expr_op>> expr_progs;   // an ExprCmp's two sides as one program ...
+    std::deque<cph_pred_expr> exprs;                   // ... and the struct its op's value points at (a deque: addresses stay)
+    std::deque<int32_t> second_cols;                   // a ColCmp's second column, its op's value
     // what column c holds for `row` on the device
     const std::string* value(size_t c, const Row& row) const {
         static const std::string one("1"), none;
@@ -1046,6 +1098,44 @@ struct PredProgram {
                 ops.push_back(cph_pred_op{op, (int32_t)c, {reinterpret_cast<const uint8_t*>(p.text().data()), p.text().size()}});
                 ops.push_back(cph_pred_op{CPH_PRED_LIKE, (int32_t)f, {reinterpret_cast<const uint8_t*>("1"), 1}});
                 ops.push_back(cph_pred_op{CPH_PRED_ALL, 2, {nullptr, 0}});
+                break;
+            }
+            case Pred::kExprCmp: {
+                // one program, lhs below rhs, over this program's columns.  A row that lacks a column reads the Col's default, or
+                // a NUL, which converts to no number: the row is false under every relation, as on the host.
+                expr_progs.emplace_back();
+                std::vector<cph_expr_op>& prog = expr_progs.back();
+                for (const Expr* e : {&p.lhs(), &p.rhs()})
+                    for (const Expr::Op& o : e->ops) {
+                        cph_expr_op d{};
+                        d.op = o.op;
+                        if (o.op == CPH_EXPR_COL_INT || o.op == CPH_EXPR_COL_FLT) {
+                            const Col& col = e->cols[(size_t)o.arg];
+                            const size_t c = column(col.name);
+                            if (col.has_default) absent[c] = col.fallback;
+                            else if (absent[c].empty()) absent[c].assign(1, '\0');
+                            d.arg = (int32_t)c;
+                        }
+                        if (o.op == CPH_EXPR_LIT_FLT) d.lit.f = o.f;
+                        else d.lit.i = o.i;
+                        prog.push_back(d);
+                    }
+                exprs.push_back(cph_pred_expr{prog.data(), (int32_t)prog.size(), 0, nullptr});
+                ops.push_back(cph_pred_op{(int32_t)CPH_PRED_EXPR_LT + (int32_t)p.rel(), 0,
+                                          {reinterpret_cast<const uint8_t*>(&exprs.back()), sizeof(cph_pred_expr)}});
+                break;
+            }
+            case Pred::kColCmp: {   // like kStrCmp: AND-ed with the presence flags of both columns
+                const size_t a = column(p.column()), b = column(p.text());
+                const size_t fa = column(std::string("\0present\0", 9) + p.column()), fb = column(std::string("\0present\0", 9) + p.text());
+                flag_of[fa] = (int)a;
+                flag_of[fb] = (int)b;
+                second_cols.push_back((int32_t)b);
+                ops.push_back(cph_pred_op{(int32_t)CPH_PRED_COLS_LT + (int32_t)p.rel(), (int32_t)a,
+                                          {reinterpret_cast<const uint8_t*>(&second_cols.back()), 4}});
+                ops.push_back(cph_pred_op{CPH_PRED_LIKE, (int32_t)fa, {reinterpret_cast<const uint8_t*>("1"), 1}});
+                ops.push_back(cph_pred_op{CPH_PRED_LIKE, (int32_t)fb, {reinterpret_cast<const uint8_t*>("1"), 1}});
+                ops.push_back(cph_pred_op{CPH_PRED_ALL, 3, {nullptr, 0}});
                 break;
             }
             case Pred::kLike:

@@ -356,6 +356,10 @@ def _pred_columns(pred) -> list:
         return [name for name, _ in pred.items]
     if isinstance(pred, (_P._NumCmp, _P.StrCmp, _P._StrTest, _P.TimeCmp)):
         return [pred.column]
+    if isinstance(pred, _P.ExprCmp):
+        return list(pred.names)
+    if isinstance(pred, _P.ColCmp):
+        return [pred.a, pred.b]
     if isinstance(pred, _P.Not):
         return _pred_columns(pred.pred)
     if isinstance(pred, (_P.All, _P.Any)):
@@ -456,7 +460,7 @@ def compile_switch(switch, column_names):
     cases = []
     for pred, tmpl in switch.cases:
         used, ops = _P.compile(pred, known)
-        ops = [(op, index_of(used[arg]), v) if v is not None and arg >= 0 else (op, arg, v) for op, arg, v in ops]
+        ops = _P.remap_columns(ops, lambda k: index_of(used[k]))
         cases.append((ops, alternative(tmpl)))
     otherwise = alternative(switch.otherwise)
     total = sum(len(pc) for _, pc in cases) + len(otherwise)
@@ -467,10 +471,11 @@ def compile_switch(switch, column_names):
     return shared, cases, otherwise
 
 
-def which_of(switch, row) -> int:
-    """The alternative a row selects: the index of the first case whose predicate holds, or the number of cases (`otherwise`)."""
+def which_of(switch, row, i: int = 0) -> int:
+    """The alternative a row selects: the index of the first case whose predicate holds, or the number of cases (`otherwise`);
+    i = the row's number (the array leaves of an ExprCmp)."""
     for k, (pred, _) in enumerate(switch.cases):
-        if _P.matches(pred, row):
+        if _P.matches(pred, row, i):
             return k
     return len(switch.cases)
 
@@ -545,7 +550,7 @@ def render(template, row, i: int = 0) -> bytes:
     where it fails raises expr.ExprError.  A Switch renders the alternative the row selects (which_of): parts of the
     other alternatives are not evaluated."""
     if isinstance(template, Switch):
-        return render(template.alternatives()[which_of(template, row)], row, i)
+        return render(template.alternatives()[which_of(template, row, i)], row, i)
     out = []
     for p in _template(template).parts:
         if isinstance(p, bytes):

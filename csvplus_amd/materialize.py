@@ -247,11 +247,54 @@ class RowList:
             pass
 
 
-def _pred_program(ops, keep):
+def _expr_program(ops, keep):
+    """The cph_expr_op array of expr.compile's ops."""
+    from . import expr as E
+
+    prog = (N.cph_expr_op * max(len(ops), 1))()
+    for k, (op, arg, value) in enumerate(ops):
+        prog[k].op, prog[k].arg = op, arg
+        if op == E.LIT_INT:
+            prog[k].lit.i = value
+        elif op == E.LIT_FLT:
+            prog[k].lit.f = value
+    keep.append(prog)
+    return prog
+
+
+def _pred_expr(eops, arrs, need, keep):
+    """One cph_pred_expr for an expression term: host arrays are passed as they are, device arrays by pointer; every array
+    has an entry for each of the `need` positions of the selection the call can look at."""
+    nums = (N.cph_expr_nums * max(len(arrs), 1))()
+    for k, a in enumerate(arrs):
+        if a.count < need:
+            raise ValueError(f"filter_rows: {a!r} has {a.count} values for positions 0..{need - 1} of the selection")
+        if a.device:
+            nums[k].ptr, nums[k].mem = a.values or None, N.CPH_MEM_DEVICE
+        else:
+            keep.append(a.values)
+            nums[k].ptr, nums[k].mem = (a.values.ctypes.data if a.count else None), N.CPH_MEM_HOST
+    pe = N.cph_pred_expr(_expr_program(eops, keep), len(eops), len(arrs), nums if arrs else None)
+    keep += [nums, pe]
+    return pe
+
+
+def _pred_program(ops, keep, need=0):
+    """The cph_pred_op array of predicates.compile's ops; need = first_row + nrows of the call (an expression term's arrays)."""
+    from . import predicates as P
+
     arr = (N.cph_pred_op * max(len(ops), 1))()
     for i, (op, arg, value) in enumerate(ops):
         arr[i].op, arr[i].arg = int(op), int(arg)
-        if value is not None:
+        if P._is_expr_op(op):
+            if arg >= 0:
+                pe = _pred_expr(value[0], value[1], need, keep)
+                arr[i].value.data, arr[i].value.len = C.addressof(pe), C.sizeof(pe)
+        elif P._is_cols_op(op):
+            b = np.array([value], dtype=np.int32)
+            keep.append(b)
+            arr[i].value.data, arr[i].value.len = b.ctypes.data, 4
+        elif value is not None:
             b = np.frombuffer(bytes(value), dtype=np.uint8)
             keep.append(b)
             arr[i].value.data = b.ctypes.data if len(b) else None
@@ -287,7 +330,7 @@ def filter_rows(ctx: N.Context, cols_by_name, pred, row_ids=None, nrows=None, mo
     if out_bits is None:
         out_bits = 32 if first_row + n <= 0xFFFFFFFF else 64
     opts = N.cph_filter_opts(_MODES[mode], int(out_bits), int(first_row), int(skip), N.CPH_NO_LIMIT if limit is None else int(limit))
-    prog = _pred_program(ops, keep)
+    prog = _pred_program(ops, keep, first_row + n)
     out = C.POINTER(N.cph_rowlist)()
     ctx._check(ctx.lib.cph_filter_rows(ctx.handle, arr, sel, len(cols), n, prog, len(ops), C.byref(opts), out_mem, C.byref(out)))
     del keep
@@ -464,13 +507,7 @@ def eval_number(ctx: N.Context, cols_by_name, expr, row_ids=None, nrows=None, ou
         else:
             keep.append(a.values)
             nums[k].ptr, nums[k].mem = (a.values.ctypes.data if a.count else None), N.CPH_MEM_HOST
-    prog = (N.cph_expr_op * len(ops))()
-    for k, (op, arg, value) in enumerate(ops):
-        prog[k].op, prog[k].arg = op, arg
-        if op == E.LIT_INT:
-            prog[k].lit.i = value
-        elif op == E.LIT_FLT:
-            prog[k].lit.f = value
+    prog = _expr_program(ops, keep)
     out = C.POINTER(N.cph_numcol)()
     eop = C.c_int32(-1)
     ctx._check(ctx.lib.cph_num_eval(ctx.handle, arr, sel, len(cols), n, nums if arrs else None, len(arrs), prog, len(ops), out_mem,
@@ -643,7 +680,7 @@ def map_switch(ctx: N.Context, cols_by_name, switch, row_ids=None, nrows=None, o
     try:
         carr = (N.cph_map_case * len(cases))()
         for a, (ops, pieces) in enumerate(cases):
-            prog = _pred_program(ops, keep)
+            prog = _pred_program(ops, keep, n)
             parr = _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending, a)
             keep += [prog, parr]
             carr[a].prog, carr[a].nops = prog, len(ops)

@@ -65,7 +65,7 @@ def join_to_csv(ctx: N.Context, stream: Table, steps, out_columns, timings: dict
     order costs ~0.3 ms per 1e7 table rows, reporting positions saves ~1.0 ms per 1e8 stream rows, so a one-shot pipeline
     whose stream is only a few times longer than its build tables keeps row ids.
     where / skip / limit: Join(...).Filter(where).Drop(skip).Top(limit) in front of the writer — `where` is a predicate of
-    csvplus_amd.predicates (Like, All, Any, Not, IntCmp, FloatCmp, StrCmp, HasPrefix, HasSuffix, Contains, TimeCmp) over the JOINED row: a name is looked up in the stream first, then in
+    csvplus_amd.predicates (Like, All, Any, Not, IntCmp, FloatCmp, StrCmp, HasPrefix, HasSuffix, Contains, TimeCmp, ExprCmp, ColCmp) over the JOINED row: a name is looked up in the stream first, then in
     steps[0]'s table, steps[1]'s, ... (mergeRows: the stream's value wins); a name none of them has makes its Like false.
     computed: {name: template} — ...Map(row[name] = template(row)) behind the filter, one template of csvplus_amd.mapping
     (Format, Const, Switch; parts may be slices, Col("ts")[0:10]) per new column, applied in dict order over the joined rows that are left: a Col is looked up among the

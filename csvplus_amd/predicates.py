@@ -4,7 +4,9 @@ IntCmp, FloatCmp — and the conditions that look inside a string (`row["ts"] >=
 Contains): StrCmp, HasPrefix, HasSuffix, Contains.  Those are byte operations in Go; Python's bytes comparison, startswith,
 endswith and `in` are their exact host model.  TimeCmp compares a column of RFC 3339 timestamps as INSTANTS
 (`t, err := time.Parse(time.RFC3339, row["ts"]); return err == nil && t.Unix() REL u.Unix()`): two stamps of one instant in
-different zones are equal, which their bytes are not; csvplus_amd.timeconv is its host model.
+different zones are equal, which their bytes are not; csvplus_amd.timeconv is its host model.  ExprCmp compares two numeric
+expressions of csvplus_amd.expr (`price(r) * float64(qty(r)) >= 100`, `died(r) > born(r)`) and ColCmp two columns of one row as
+strings (`r["ship_city"] != r["bill_city"]`); expr.run_ops and Python's bytes comparison are their host models.
 
 A Go closure cannot run on a GPU; these are declarative and can.  `compile` flattens any nesting of them into the
 postfix program cph_filter_rows takes (include/csvplus_hip.h), `matches` evaluates a predicate on one row held as a dict —
@@ -23,6 +25,8 @@ INT_LT, FLT_LT = 16, 24            # CPH_PRED_INT_LT / CPH_PRED_FLT_LT; + the re
 STR_LT = 32                        # CPH_PRED_STR_LT; + the relation's index in RELS
 HAS_PREFIX, HAS_SUFFIX, CONTAINS = 40, 41, 42   # CPH_PRED_*
 TIME_LT = 48                       # CPH_PRED_TIME_LT; + the relation's index in RELS
+EXPR_LT = 56                       # CPH_PRED_EXPR_LT; + the relation's index in RELS
+COLS_LT = 72                       # CPH_PRED_COLS_LT; + the relation's index in RELS
 RELS = ("<", "<=", "==", "!=", ">=", ">")
 MAX_OPS, MAX_LIKE, MAX_STACK = 64, 32, 32
 NUM_OK, NUM_ERR_SYNTAX, NUM_ERR_RANGE, NUM_ERR_UNSUPPORTED = 0, 1, 2, 3   # CPH_NUM_*
@@ -150,6 +154,44 @@ class TimeCmp(Pred):
         return f"TimeCmp({self.column!r}, {self.rel!r}, {self.literal!r})"
 
 
+class ExprCmp(Pred):
+    """ExprCmp(FloatCol("price") * ToFloat(IntCol("qty")), ">=", 100.0): `lhs REL rhs` over two expressions of csvplus_amd.expr
+    (a Python int is an int64 literal, a float a float64 literal; IntArr / FloatArr leaves are indexed by the row's POSITION in
+    the selection).  Both sides have ONE type — Go has no implicit conversions — else TypeError here.  int64 compares signed,
+    float64 IEEE (with a NaN on either side only "!=" holds; -0.0 == 0.0).  A row in which any op fails (a leaf that does not
+    convert, a zero divisor, a ToInt out of range) or that lacks a column is false under every relation, "!=" included."""
+
+    def __init__(self, lhs, rel, rhs):
+        from . import expr as E
+        if rel not in RELS:
+            raise ValueError(f"unknown relation {rel!r}: one of {' '.join(RELS)}")
+        self.lhs, self.rel, self.rhs = E._node(lhs), rel, E._node(rhs)
+        self.names = E.columns(self.lhs)
+        self.names += [nm for nm in E.columns(self.rhs) if nm not in self.names]
+        self.ops = self._compile(self.names)[1]   # typing (both sides, then across the relation) and the limits: TypeError
+
+    def _compile(self, known):
+        """(names used, ops) of both sides as ONE program that leaves lhs below rhs; column indices into the names used."""
+        from . import expr as E
+        return E.compile_pair(self.lhs, self.rhs, known)
+
+    def __repr__(self):
+        return f"ExprCmp({self.lhs!r}, {self.rel!r}, {self.rhs!r})"
+
+
+class ColCmp(Pred):
+    """ColCmp("ship_city", "!=", "bill_city"): `row[a] REL row[b]`, Go's string comparison (StrCmp's rules with the second
+    column's value in the literal's place).  A row that lacks either column is false under every relation, "!=" included."""
+
+    def __init__(self, a, rel, b):
+        if rel not in RELS:
+            raise ValueError(f"unknown relation {rel!r}: one of {' '.join(RELS)}")
+        self.a, self.rel, self.b = str(a), rel, str(b)
+
+    def __repr__(self):
+        return f"ColCmp({self.a!r}, {self.rel!r}, {self.b!r})"
+
+
 class _StrTest(Pred):
     op = None
 
@@ -179,7 +221,7 @@ class Contains(_StrTest):
 def _operands(preds):
     for p in preds:
         if not isinstance(p, Pred):
-            raise TypeError(f"not a predicate: {p!r} (closures cannot run on the device; use Like / All / Any / Not / IntCmp / FloatCmp / StrCmp / HasPrefix / HasSuffix / Contains / TimeCmp)")
+            raise TypeError(f"not a predicate: {p!r} (closures cannot run on the device; use Like / All / Any / Not / IntCmp / FloatCmp / StrCmp / HasPrefix / HasSuffix / Contains / TimeCmp / ExprCmp / ColCmp)")
     return list(preds)
 
 
@@ -328,6 +370,51 @@ def _time_holds(rel, value, literal) -> bool:
     return status == NUM_OK and _cmp(rel, v, T.parse_model(literal, "s")[1])
 
 
+def _is_expr_op(op) -> bool:
+    return EXPR_LT <= op < EXPR_LT + len(RELS)
+
+
+def _is_cols_op(op) -> bool:
+    return COLS_LT <= op < COLS_LT + len(RELS)
+
+
+def _expr_holds(rel, ops, values, i) -> bool:
+    """One expression term: `ops` (two values left, lhs below rhs) on the row whose column values are values[k]; i = the
+    row's position, which indexes the array leaves.  A failing op makes it false."""
+    from . import expr as E
+
+    def leaf(q, o):
+        op, arg, value = o
+        if op == E.COL_INT:
+            return atoi(values[arg])
+        if op == E.COL_FLT:
+            return parse_float(values[arg])
+        if value.device:
+            raise ValueError("an array on the device has no host values")
+        return (int(value.values[i]) if op == E.NUM_INT else float(value.values[i])), NUM_OK
+
+    (a, b), status, _ = E.run_ops(ops, leaf, want=2)
+    return status == NUM_OK and _cmp(rel, a, b)
+
+
+def remap_columns(ops, index):
+    """The ops of `compile` with every column k — a term's own, a ColCmp's second, an expression's COL leaves — replaced by
+    index(k): what a caller needs that shares one column list among several programs (mapping.compile_switch)."""
+    from . import expr as E
+    out = []
+    for op, arg, v in ops:
+        if _is_expr_op(op):
+            if arg >= 0:
+                eops, arrs = v
+                v = ([(o, index(a), x) if o in (E.COL_INT, E.COL_FLT) else (o, a, x) for o, a, x in eops], arrs)
+        elif _is_cols_op(op):
+            arg, v = (index(arg) if arg >= 0 else arg), (index(v) if v >= 0 else v)
+        elif v is not None and arg >= 0:
+            arg = index(arg)
+        out.append((op, arg, v))
+    return out
+
+
 def _is_str_op(op) -> bool:
     return STR_LT <= op < STR_LT + len(RELS) or op in (HAS_PREFIX, HAS_SUFFIX, CONTAINS)
 
@@ -341,7 +428,10 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
     """(names of the columns used, postfix ops).  An op is (LIKE, column, value bytes) with `column` indexing the returned
     name list, or -1 for a name that is not among `column_names` (the row has no such column: false, :1286); a numeric term
     (INT_LT / FLT_LT + relation, column, 8 literal bytes); a string term (STR_LT + relation / HAS_PREFIX / HAS_SUFFIX /
-    CONTAINS, column, literal bytes); a time term (TIME_LT + relation, column, the literal's RFC 3339 text); (NOT, 0, None);
+    CONTAINS, column, literal bytes); a time term (TIME_LT + relation, column, the literal's RFC 3339 text); an expression term
+    (EXPR_LT + relation, 0, (expr ops, arrays)) whose expr ops are expr.compile's for both sides in one program (lhs below rhs)
+    with COL leaves indexing the returned name list, or (EXPR_LT + relation, -1, None) when a column is missing; a
+    column-against-column term (COLS_LT + relation, column a, column b), either -1 when missing; (NOT, 0, None);
     (ALL, k, None); (ANY, k, None).  Raises ValueError beyond the ABI's limits (64 ops, 32 LIKE terms, stack of 32)."""
     known = [str(c) for c in column_names]
     used: list[str] = []
@@ -376,6 +466,23 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
                 if p.column not in used:
                     used.append(p.column)
                 ops.append((op, used.index(p.column), p.literal))
+        elif isinstance(p, ExprCmp):
+            from . import expr as E
+            op = EXPR_LT + RELS.index(p.rel)
+            if any(nm not in known for nm in p.names):
+                ops.append((op, -1, None))
+            else:
+                for nm in p.names:
+                    if nm not in used:
+                        used.append(nm)
+                own, eops = p._compile(known)
+                eops = [(o, used.index(own[a]), x) if o in (E.COL_INT, E.COL_FLT) else (o, a, x) for o, a, x in eops]
+                ops.append((op, 0, (eops, E.arrays(eops))))
+        elif isinstance(p, ColCmp):
+            for nm in (p.a, p.b):
+                if nm in known and nm not in used:
+                    used.append(nm)
+            ops.append((COLS_LT + RELS.index(p.rel), used.index(p.a) if p.a in known else -1, used.index(p.b) if p.b in known else -1))
         elif isinstance(p, Not):
             emit(p.pred)
             ops.append((NOT, 0, None))
@@ -403,8 +510,20 @@ def compile(pred: Pred, column_names):   # noqa: A001 (the name the issue of rec
     return used, ops
 
 
-def matches(pred: Pred, row) -> bool:
-    """The predicate on one row (a dict; str and bytes compare by their UTF-8 bytes)."""
+def _row_get(row, name):
+    v = row.get(name)
+    return row.get(name.encode("utf-8")) if v is None else v
+
+
+def matches(pred: Pred, row, i: int = 0) -> bool:
+    """The predicate on one row (a dict; str and bytes compare by their UTF-8 bytes); i = the row's position in the
+    selection, which is what an ExprCmp's IntArr / FloatArr leaves are indexed with."""
+    if isinstance(pred, ExprCmp):
+        values = [_row_get(row, nm) for nm in pred.names]
+        return all(v is not None for v in values) and _expr_holds(pred.rel, pred.ops, values, i)
+    if isinstance(pred, ColCmp):
+        a, b = _row_get(row, pred.a), _row_get(row, pred.b)
+        return a is not None and b is not None and _cmp(pred.rel, _bytes(a), _bytes(b))
     if isinstance(pred, Like):
         for name, value in pred.items:
             v = row.get(name)
@@ -430,19 +549,24 @@ def matches(pred: Pred, row) -> bool:
             v = row.get(pred.column.encode("utf-8"))
         return v is not None and _time_holds(pred.rel, v, pred.literal)
     if isinstance(pred, Not):
-        return not matches(pred.pred, row)
+        return not matches(pred.pred, row, i)
     if isinstance(pred, All):
-        return all(matches(p, row) for p in pred.preds)
+        return all(matches(p, row, i) for p in pred.preds)
     if isinstance(pred, Any):
-        return any(matches(p, row) for p in pred.preds)
+        return any(matches(p, row, i) for p in pred.preds)
     raise TypeError(f"not a predicate: {pred!r}")
 
 
-def run_ops(ops, values) -> bool:
-    """The postfix program on one row given as the list of its column values (indexed like compile's name list)."""
+def run_ops(ops, values, i: int = 0) -> bool:
+    """The postfix program on one row given as the list of its column values (indexed like compile's name list); i = the
+    row's position in the selection (an expression term's array leaves)."""
     st: list[bool] = []
     for op, arg, value in ops:
-        if op == LIKE:
+        if _is_expr_op(op):
+            st.append(arg >= 0 and _expr_holds(RELS[op - EXPR_LT], value[0], values, i))
+        elif _is_cols_op(op):
+            st.append(arg >= 0 and value >= 0 and _cmp(RELS[op - COLS_LT], _bytes(values[arg]), _bytes(values[value])))
+        elif op == LIKE:
             st.append(arg >= 0 and _bytes(values[arg]) == value)
         elif _is_str_op(op):
             st.append(arg >= 0 and _str_holds(op, values[arg], value))

@@ -748,12 +748,34 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
  * included, and arg = -1 pushes false.  Two stamps of the same instant in different zones are equal here, which their bytes
  * (CPH_PRED_STR_*) are not.
  *
- * Every LIKE, numeric, string and time term counts against CPH_PRED_MAX_LIKE (32 terms in all).  The valid ops are 1..4, 16..21,
- * 24..29, 32..37, 40..42 and 48..53; every other op (0, 5..15, 22, 23, 30, 31, 38, 39, 43..47, 54..) is invalid.
+ * Expression terms — `price(r) * float64(qty(r)) >= 100`, `died(r) > born(r)` as data: two cph_num_eval expressions compared:
+ *   CPH_PRED_EXPR_LT .. CPH_PRED_EXPR_GT (56..61, in the order LT LE EQ NE GE GT)   push (lhs of this row) REL (rhs of this row)
+ * `value.data` points at ONE cph_pred_expr in host memory (declared behind cph_expr_nums below) and value.len ==
+ * sizeof(cph_pred_expr).  Its program is a cph_num_eval program that leaves exactly TWO values of ONE type, lhs below rhs; COL_*
+ * leaves index this call's cols, and entry p of a number array belongs to POSITION p of the selection (first_row included), so
+ * an array has at least first_row + nrows entries.  Typing is checked on the host with cph_num_eval's rules; int64 and float64
+ * do not mix across the relation either (no implicit conversions).  int64 compares signed; float64 compares IEEE: with a NaN
+ * on either side only NE holds, and -0 == +0.  A row in which ANY op fails — a leaf that does not convert, a zero divisor, a
+ * TO_INT out of range — pushes FALSE under every relation, NE included (what the reference's closure does with err: the rule
+ * of INT_* / FLT_*).  `arg` is 0; arg = -1 means "a column of the expression is not in the rows": the term is false and `value`
+ * is ignored.  One kernel (k_expr_cmp) reads the leaves once and writes one BIT per row; a program that consists of a single
+ * expression term runs nothing else in the WHERE mode.  Deferred float leaves take cph_num_eval's two routes, with the same bits.
  *
- * Out of scope for a condition: comparing a column against ANOTHER COLUMN; case mapping and TrimSpace (Go's are
- * Unicode-aware: a project of their own); splitting on a delimiter; regular expressions; time layouts other than RFC 3339,
- * named zones, and comparing below the second.
+ * Column-against-column terms — `r["ship_city"] != r["bill_city"]` as data:
+ *   CPH_PRED_COLS_LT .. CPH_PRED_COLS_GT (72..77, same order)   push strings.Compare(value of column `arg`, value of column b) REL 0
+ * `value.data` points at 4 host bytes holding the int32_t column b and value.len == 4.  These are exactly CPH_PRED_STR_*'s rules
+ * with the second value in the literal's place: bytewise, unsigned, the shorter of two values that agree on the common prefix
+ * the smaller.  Either column -1 pushes FALSE under all six relations.  The two columns may have different layouts (fixed width,
+ * 32- / 64-bit offsets) and different row ids: that is how a joined row compares a stream column with a build column.
+ *
+ * Every LIKE, numeric, string, time, expression and column-against-column term counts against CPH_PRED_MAX_LIKE (32 terms in
+ * all).  The valid ops are 1..4, 16..21, 24..29, 32..37, 40..42, 48..53, 56..61 and 72..77; every other op (0, 5..15, 22, 23, 30,
+ * 31, 38, 39, 43..47, 54, 55, 62..71, 78..) is invalid.
+ *
+ * Out of scope for a condition: boolean-valued ops and math functions inside an expression, string operands inside an
+ * expression, prefix / suffix / contains against another column; case mapping and TrimSpace (Go's are Unicode-aware: a project
+ * of their own); splitting on a delimiter; regular expressions; time layouts other than RFC 3339, named zones, and comparing
+ * below the second.
  */
 enum { CPH_PRED_LIKE = 1, CPH_PRED_NOT = 2, CPH_PRED_ALL = 3, CPH_PRED_ANY = 4 };
 enum { CPH_PRED_INT_LT = 16, CPH_PRED_INT_LE = 17, CPH_PRED_INT_EQ = 18, CPH_PRED_INT_NE = 19, CPH_PRED_INT_GE = 20, CPH_PRED_INT_GT = 21 };
@@ -761,13 +783,17 @@ enum { CPH_PRED_FLT_LT = 24, CPH_PRED_FLT_LE = 25, CPH_PRED_FLT_EQ = 26, CPH_PRE
 enum { CPH_PRED_STR_LT = 32, CPH_PRED_STR_LE = 33, CPH_PRED_STR_EQ = 34, CPH_PRED_STR_NE = 35, CPH_PRED_STR_GE = 36, CPH_PRED_STR_GT = 37 };
 enum { CPH_PRED_HAS_PREFIX = 40, CPH_PRED_HAS_SUFFIX = 41, CPH_PRED_CONTAINS = 42 };
 enum { CPH_PRED_TIME_LT = 48, CPH_PRED_TIME_LE = 49, CPH_PRED_TIME_EQ = 50, CPH_PRED_TIME_NE = 51, CPH_PRED_TIME_GE = 52, CPH_PRED_TIME_GT = 53 };
+enum { CPH_PRED_EXPR_LT = 56, CPH_PRED_EXPR_LE = 57, CPH_PRED_EXPR_EQ = 58, CPH_PRED_EXPR_NE = 59, CPH_PRED_EXPR_GE = 60, CPH_PRED_EXPR_GT = 61 };
+enum { CPH_PRED_COLS_LT = 72, CPH_PRED_COLS_LE = 73, CPH_PRED_COLS_EQ = 74, CPH_PRED_COLS_NE = 75, CPH_PRED_COLS_GE = 76, CPH_PRED_COLS_GT = 77 };
 #define CPH_PRED_MAX_OPS   64
 #define CPH_PRED_MAX_LIKE  32
 #define CPH_PRED_MAX_STACK 32
 typedef struct {
     int32_t    op;      /* CPH_PRED_* */
-    int32_t    arg;     /* LIKE / INT_* / FLT_* / STR_* / HAS_* / CONTAINS / TIME_*: column (index into cols) or -1; ALL / ANY: operand count; NOT: ignored */
-    cph_strval value;   /* LIKE / STR_* / HAS_* / CONTAINS: the literal's bytes; INT_* / FLT_*: 8 bytes, an int64_t / a double; TIME_*: RFC 3339 text; host memory */
+    int32_t    arg;     /* LIKE / INT_* / FLT_* / STR_* / HAS_* / CONTAINS / TIME_* / COLS_*: column (index into cols) or -1; EXPR_*: 0 or -1;
+                           ALL / ANY: operand count; NOT: ignored */
+    cph_strval value;   /* LIKE / STR_* / HAS_* / CONTAINS: the literal's bytes; INT_* / FLT_*: 8 bytes, an int64_t / a double; TIME_*: RFC 3339 text;
+                           EXPR_*: one cph_pred_expr; COLS_*: 4 bytes, the int32_t second column; host memory */
 } cph_pred_op;
 
 enum { CPH_FILTER_WHERE = 0, CPH_FILTER_TAKE_WHILE = 1, CPH_FILTER_DROP_WHILE = 2 };
@@ -806,6 +832,11 @@ typedef struct {
  * 1..CPH_PRED_MAX_OPS, an unknown op, a LIKE / numeric / string-term column outside -1..ncols-1, a LIKE or string-term value
  * with a length but no pointer, a string-term literal of 4 GiB or more,
  * a numeric literal that is not exactly 8 bytes behind a non-NULL pointer, a time literal that is no whole-second RFC 3339 stamp,
+ * an expression term whose value is not exactly one cph_pred_expr, whose prog is NULL, whose nops is outside
+ * 2..CPH_EXPR_MAX_OPS, whose nnums is outside 0..CPH_EXPR_MAX_NUMS (or nums NULL with nnums > 0, a number array without values
+ * or with an unknown memory space), whose program breaks a rule of cph_num_eval or does not leave exactly two values of one
+ * type, or whose arg is neither 0 nor -1; a column-against-column term whose value is not exactly 4 bytes or whose either
+ * column is outside -1..ncols-1,
  * a negative or too large ALL / ANY count (stack underflow), a NOT on an empty stack, a program that does not leave
  * exactly one value, the limits above, out_bits or row-id bits other than 32 / 64, an unknown mode or out_mem, a short
  * identity column.  CPH_ERR_TOO_MANY_ROWS when out_bits == 32 and first_row + nrows > 2^32 - 1, and when nrows alone is
@@ -942,8 +973,8 @@ CPH_API void    cph_numcol_release(cph_numcol* col);
  * not leave exactly one value, an unknown out_mem, row-id bits other than 32 / 64, an identity column whose row count is
  * not nrows.  nrows == 0 is legal (values and status are NULL).
  *
- * Out of scope: comparisons and boolean results (cph_filter_rows has INT_* / FLT_* terms), math functions and rounding
- * helpers, string operands, more than one result per call.
+ * Out of scope: boolean results (comparing two expressions is a term of cph_filter_rows: CPH_PRED_EXPR_*, over the
+ * cph_pred_expr below), math functions and rounding helpers, string operands, more than one result per call.
  */
 enum { CPH_NUM_ERR_DIV_ZERO = 4, CPH_NUM_ERR_CONVERT = 5 };   /* beside CPH_NUM_OK .. CPH_NUM_ERR_UNSUPPORTED = 0..3 */
 enum { CPH_EXPR_COL_INT = 1, CPH_EXPR_COL_FLT = 2, CPH_EXPR_NUM_INT = 3, CPH_EXPR_NUM_FLT = 4, CPH_EXPR_LIT_INT = 5,
@@ -962,6 +993,13 @@ typedef struct {
     int32_t     mem;   /* CPH_MEM_HOST / CPH_MEM_DEVICE */
     int32_t     reserved_;
 } cph_expr_nums;
+/* The value of a CPH_PRED_EXPR_* term of cph_filter_rows / cph_map_switch (see there): two expressions in one program. */
+typedef struct {
+    const cph_expr_op*   prog;   /* a cph_num_eval program that leaves exactly TWO values of ONE type: lhs below rhs */
+    int32_t              nops;   /* 2..CPH_EXPR_MAX_OPS for both sides together; stack <= CPH_EXPR_MAX_STACK */
+    int32_t              nnums;
+    const cph_expr_nums* nums;   /* entry p belongs to POSITION p of the selection: at least first_row + nrows entries */
+} cph_pred_expr;
 
 CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_rowsel* sel, int32_t ncols, uint64_t nrows,
                              const cph_expr_nums* nums, int32_t nnums, const cph_expr_op* prog, int32_t nops,
@@ -1100,8 +1138,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  * cph_map_format rejects in a piece or in the row sources.  CPH_ERR_TOO_MANY_ROWS for nrows > 2^32 - 1 (the predicate
  * evaluator's limit).
  *
- * Out of scope: nested switches; a conditional part inside a template (use one Switch over whole templates); a condition
- * that compares a column against another column; case mapping and TrimSpace; splitting on a delimiter; regular expressions;
+ * Out of scope: nested switches; a conditional part inside a template (use one Switch over whole templates); case mapping and TrimSpace; splitting on a delimiter; regular expressions;
  * the other forms of FormatFloat; time layouts other than RFC 3339.
  */
 #define CPH_MAP_MAX_CASES         8
