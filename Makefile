@@ -13,14 +13,14 @@ LIBDIR  = csvplus_amd/lib
 CSRC    = csvplus_amd/csrc
 HIP_SRCS = $(CSRC)/capi.hip $(CSRC)/index_build.hip $(CSRC)/keycodec.hip $(CSRC)/radix_sort.hip $(CSRC)/probe.hip $(CSRC)/chain.hip $(CSRC)/stream_join.hip $(CSRC)/materialize.hip $(CSRC)/json_write.hip $(CSRC)/map_format.hip $(CSRC)/map_switch.hip $(CSRC)/filter.hip $(CSRC)/numparse.hip $(CSRC)/expr_eval.hip $(CSRC)/csv_ingest.hip $(CSRC)/index_ops.hip $(CSRC)/resolve.hip $(CSRC)/aggregate.hip $(CSRC)/join_totals.hip $(CSRC)/order.hip $(CSRC)/dist.hip $(CSRC)/calibrate.hip $(CSRC)/small_build.hip $(CSRC)/host_encode.hip $(CSRC)/window_sort.hip $(CSRC)/counted_sort.hip
 HIP_OBJS = $(patsubst $(CSRC)/%.hip,$(LIBDIR)/obj/%.o,$(HIP_SRCS))
-HIP_HDRS = $(CSRC)/cph_internal.hpp $(CSRC)/device_utils.hpp $(CSRC)/codec_device.hpp $(CSRC)/probe_device.hpp $(CSRC)/hash_device.hpp $(CSRC)/lds_stage.hpp $(CSRC)/materialize_device.hpp $(CSRC)/map_device.hpp $(CSRC)/map_plan.hpp $(CSRC)/numparse_device.hpp $(CSRC)/floatparse_device.hpp $(CSRC)/pow5_table.inc $(CSRC)/numformat_device.hpp $(CSRC)/shortfmt_device.hpp $(CSRC)/pow10_table.inc $(CSRC)/strpred_device.hpp $(CSRC)/timeparse_device.hpp $(CSRC)/runs_device.hpp $(CSRC)/tile_bitmap.hpp $(CSRC)/num_report.hpp $(CSRC)/order_device.hpp $(CSRC)/csv_lazy_device.hpp $(CSRC)/host_encode_kernels.hpp include/csvplus_hip.h
+HIP_HDRS = $(CSRC)/cph_internal.hpp $(CSRC)/device_utils.hpp $(CSRC)/codec_device.hpp $(CSRC)/probe_device.hpp $(CSRC)/hash_device.hpp $(CSRC)/lds_stage.hpp $(CSRC)/materialize_device.hpp $(CSRC)/map_device.hpp $(CSRC)/map_plan.hpp $(CSRC)/numparse_device.hpp $(CSRC)/floatparse_device.hpp $(CSRC)/pow5_table.inc $(CSRC)/numformat_device.hpp $(CSRC)/shortfmt_device.hpp $(CSRC)/pow10_table.inc $(CSRC)/strpred_device.hpp $(CSRC)/span_device.hpp $(CSRC)/timeparse_device.hpp $(CSRC)/runs_device.hpp $(CSRC)/tile_bitmap.hpp $(CSRC)/num_report.hpp $(CSRC)/order_device.hpp $(CSRC)/csv_lazy_device.hpp $(CSRC)/host_encode_kernels.hpp include/csvplus_hip.h
 
 all: hip datagen oracle host
 
 hip: $(LIBDIR)/libcsvplus_hip.so
 datagen: $(LIBDIR)/libcph_datagen.so
 oracle: oracle/_build/liboracle.so oracle/_build/libfaithful.so
-host: tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_expr_cond tests/cpp/test_host_encode tests/cpp/test_numformat tests/cpp/test_strpred tests/cpp/test_strpred_facade tests/cpp/test_hash_model tests/cpp/test_orderkey tests/cpp/test_order tests/cpp/test_csv_lazy tests/cpp/test_timeparse tests/cpp/test_time tests/cpp/test_floatparse tests/cpp/test_shortfmt tests/cpp/test_map_shortest tests/cpp/test_num_report tests/c/abi_demo tests/c/libnccl_standin.so
+host: tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_expr_cond tests/cpp/test_host_encode tests/cpp/test_numformat tests/cpp/test_strpred tests/cpp/test_strpred_facade tests/cpp/test_span tests/cpp/test_span_facade tests/cpp/test_hash_model tests/cpp/test_orderkey tests/cpp/test_order tests/cpp/test_csv_lazy tests/cpp/test_timeparse tests/cpp/test_time tests/cpp/test_floatparse tests/cpp/test_shortfmt tests/cpp/test_map_shortest tests/cpp/test_num_report tests/c/abi_demo tests/c/libnccl_standin.so
 
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(LIBDIR)/obj
@@ -88,6 +88,14 @@ tests/cpp/test_strpred: tests/cpp/test_strpred.cpp $(CSRC)/strpred_device.hpp
 tests/cpp/test_strpred_facade: tests/cpp/test_strpred_facade.cpp csvplus_amd/host/csvplus.hpp include/csvplus_hip.h $(LIBDIR)/libcsvplus_hip.so
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -Icsvplus_amd/host $< -L$(LIBDIR) -lcsvplus_hip -Wl,-rpath,'$$ORIGIN/../../csvplus_amd/lib' -o $@
 
+# the SPAN piece's operations (the code the Map kernels run per value: trims, affixes, the field search) compiled for the host, against
+# Go's definitions restated a byte at a time (CPU only)
+tests/cpp/test_span: tests/cpp/test_span.cpp $(CSRC)/span_device.hpp $(CSRC)/strpred_device.hpp
+	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) $< -o $@
+
+tests/cpp/test_span_facade: tests/cpp/test_span_facade.cpp csvplus_amd/host/csvplus.hpp $(CSRC)/span_device.hpp $(CSRC)/strpred_device.hpp include/csvplus_hip.h $(LIBDIR)/libcsvplus_hip.so
+	$(CXX) -O2 -std=c++17 -Wall -Iinclude -Icsvplus_amd/host $< -L$(LIBDIR) -lcsvplus_hip -Wl,-rpath,'$$ORIGIN/../../csvplus_amd/lib' -o $@
+
 # the LazyQuotes separator automaton (the code k_csv_lazy_tile_maps / k_csv_lazy_marks run per chunk) compiled for the host (CPU only)
 tests/cpp/test_csv_lazy: tests/cpp/test_csv_lazy.cpp $(CSRC)/csv_lazy_device.hpp
 	$(CXX) -O2 -std=c++17 -Wall -I$(CSRC) $< -o $@
@@ -143,7 +151,7 @@ tests/c/libnccl_standin.so: tests/c/nccl_standin.cpp
 # tests/test_asan.py runs them; findings abort the run.  The device side has its own canaries: cph_ctx_set_option
 # "pool_guard" (tools/gpu_guard.sh runs the whole GPU suite under it).
 SAN = -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1
-asan: oracle/_build/oracle_fuzz_asan oracle/_build/datagen_asan oracle/_build/timeparse_asan oracle/_build/floatparse_asan oracle/_build/shortfmt_asan
+asan: oracle/_build/oracle_fuzz_asan oracle/_build/datagen_asan oracle/_build/timeparse_asan oracle/_build/floatparse_asan oracle/_build/shortfmt_asan oracle/_build/span_asan
 
 # the same stand-alone program as tests/cpp/test_timeparse, under the sanitizers (run it on a CPU machine)
 oracle/_build/timeparse_asan: tests/cpp/test_timeparse.cpp $(CSRC)/timeparse_device.hpp
@@ -160,6 +168,11 @@ oracle/_build/shortfmt_asan: tests/cpp/test_shortfmt.cpp $(CSRC)/shortfmt_device
 	@mkdir -p oracle/_build
 	$(CXX) $(SAN) -std=c++17 -Wall -I$(CSRC) tests/cpp/test_shortfmt.cpp -o $@
 
+# the same stand-alone program as tests/cpp/test_span, under the sanitizers (run it on a CPU machine)
+oracle/_build/span_asan: tests/cpp/test_span.cpp $(CSRC)/span_device.hpp $(CSRC)/strpred_device.hpp
+	@mkdir -p oracle/_build
+	$(CXX) $(SAN) -std=c++17 -Wall -I$(CSRC) tests/cpp/test_span.cpp -o $@
+
 oracle/_build/oracle_fuzz_asan: tests/c/oracle_fuzz.c oracle/csvplus_oracle.c
 	@mkdir -p oracle/_build
 	$(CC) $(SAN) -Wall tests/c/oracle_fuzz.c -o $@
@@ -169,6 +182,6 @@ oracle/_build/datagen_asan: tests/c/datagen_check.c $(CSRC)/datagen.c
 	$(CC) $(SAN) -fopenmp -Wall tests/c/datagen_check.c -o $@
 
 clean:
-	rm -rf $(LIBDIR) oracle/_build tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_expr_cond tests/cpp/test_numformat tests/cpp/test_strpred tests/cpp/test_strpred_facade tests/cpp/test_host_encode tests/cpp/test_hash_model tests/cpp/test_orderkey tests/cpp/test_order tests/cpp/test_csv_lazy tests/cpp/test_timeparse tests/cpp/test_time tests/cpp/test_floatparse tests/cpp/test_shortfmt tests/cpp/test_map_shortest tests/cpp/test_num_report tests/c/abi_demo tests/c/libnccl_standin.so
+	rm -rf $(LIBDIR) oracle/_build tests/cpp/test_host tests/cpp/test_filter tests/cpp/test_numeric tests/cpp/test_resolve tests/cpp/test_map tests/cpp/test_map_switch tests/cpp/test_totals tests/cpp/test_join_totals tests/cpp/test_map_float tests/cpp/test_expr tests/cpp/test_expr_cond tests/cpp/test_numformat tests/cpp/test_strpred tests/cpp/test_strpred_facade tests/cpp/test_span tests/cpp/test_span_facade tests/cpp/test_host_encode tests/cpp/test_hash_model tests/cpp/test_orderkey tests/cpp/test_order tests/cpp/test_csv_lazy tests/cpp/test_timeparse tests/cpp/test_time tests/cpp/test_floatparse tests/cpp/test_shortfmt tests/cpp/test_map_shortest tests/cpp/test_num_report tests/c/abi_demo tests/c/libnccl_standin.so
 
 .PHONY: all hip datagen oracle host asan clean

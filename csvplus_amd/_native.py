@@ -213,8 +213,19 @@ CPH_MAP_TIME = 10   # Unix seconds written as RFC 3339; prec = the zone in minut
 CPH_MAP_FLOAT64_SHORTEST = 12   # a float64's shortest round-trip digits; prec = the format byte: 'e' 'E' 'f' 'g' 'G'
 
 
+CPH_MAP_SPAN = 14   # a column value narrowed by 1..4 span operations; value = a cph_span_op array
+
+
 class cph_map_slice(C.Structure):
     _fields_ = [("from_", C.c_int64), ("to", C.c_int64)]
+
+
+CPH_SPAN_TRIM_SPACE, CPH_SPAN_TRIM_CUTSET, CPH_SPAN_TRIM_PREFIX, CPH_SPAN_TRIM_SUFFIX, CPH_SPAN_FIELD, CPH_SPAN_SLICE = 1, 2, 3, 4, 5, 6
+CPH_SPAN_MAX_OPS, CPH_SPAN_MAX_TOTAL = 4, 16
+
+
+class cph_span_op(C.Structure):   # one operation of a SPAN piece: 40 bytes
+    _fields_ = [("op", C.c_int32), ("mode", C.c_int32), ("a", C.c_int64), ("b", C.c_int64), ("lit", cph_strval)]
 
 
 CPH_MAP_MAX_PIECES = 16

@@ -2,12 +2,14 @@
 // map_switch.hip: the template of the first case that holds): a template piece as the kernels see it, FormatInt's digit
 // count and characters, the field of a loaded record, the bytes one piece adds to a row (map_piece_bytes: the length pass)
 // and the loop that puts a run of pieces into a byte sink (map_put_record: the copy pass).  The kernels keep their row and
-// tile loops and what tells a row its run of pieces; what the entry points share on the host is in map_plan.hpp.
+// tile loops and what tells a row its run of pieces; what the entry points share on the host is in map_plan.hpp.  A SPAN piece
+// (span_device.hpp: a column's value narrowed by a program of span operations) computes its span in both passes (map_span_of).
 #pragma once
 
 #include "materialize_device.hpp"
 #include "numformat_device.hpp"
 #include "shortfmt_device.hpp"
+#include "span_device.hpp"
 #include "strpred_device.hpp"
 #include "timeparse_device.hpp"
 
@@ -15,10 +17,10 @@ namespace cph {
 
 struct MapPiece {
     int32_t kind;          // CPH_MAP_*
-    int32_t col;           // COLUMN / SLICE: the column; FLOAT64: prec; TIME: the zone, minutes east of UTC; FLOAT64_SHORTEST: the format byte
+    int32_t col;           // COLUMN / SLICE / SPAN: the column; FLOAT64: prec; TIME: the zone, minutes east of UTC; FLOAT64_SHORTEST: the format byte
     union {
         struct {
-            uint32_t off, len;   // LITERAL: its bytes in the plan's literal block
+            uint32_t off, len;   // LITERAL: its bytes in the plan's literal block; SPAN: its operations [off, off + len) of the plan's
         };
         int64_t from;            // SLICE: bytes [from, to) of the value, Python's slice rules (strpred_device.hpp: slice_span)
     };
@@ -38,6 +40,27 @@ enum : int { kPiecesBase = 0,     // LITERAL, COLUMN, INT64
 __host__ __device__ constexpr int pieces_set(bool has_shortest, bool has_float, bool has_slice) {
     return has_shortest ? kPiecesShortest : has_float ? kPiecesFloat : has_slice ? kPiecesSlice : kPiecesBase;
 }
+
+// A SPAN piece (span_device.hpp) is no member of those sets: an instantiation carries its code where the second template
+// parameter SP is set, and the entry points instantiate SP only over kPiecesSlice (a span-only template does not pay the
+// float formatters' registers) and over kPiecesShortest (SPAN beside any other piece).  Without SP nothing changes.
+__host__ __device__ constexpr int span_pieces_set(int pk) { return pk >= kPiecesFloat ? kPiecesShortest : kPiecesSlice; }
+
+// a column's value and the plan's literal block as span_device.hpp reads them
+struct SpanValue {
+    const uint8_t* data;
+    uint64_t begin;
+    __device__ __forceinline__ uint64_t operator()(uint64_t off, uint64_t len, int j) const { return load_value_chunk(data, begin + off, len, j); }
+};
+struct SpanLiteral {
+    const uint8_t* lits;
+    uint32_t off, len;
+    __device__ __forceinline__ uint64_t operator()(uint64_t j) const { return load_value_chunk(lits, off, len, (int)j); }
+};
+struct SpanLiterals {
+    const uint8_t* lits;
+    __device__ __forceinline__ SpanLiteral operator()(uint32_t off, uint32_t len) const { return SpanLiteral{lits, off, len}; }
+};
 
 __device__ __forceinline__ uint64_t int_magnitude(int64_t v) { return v < 0 ? 0ull - (uint64_t)v : (uint64_t)v; }
 
@@ -97,6 +120,17 @@ __device__ __forceinline__ void pick_field(const RecordFields<NC>& f, int c, uin
         if (k == c) *b = f.b[k], *l = f.l[k], *c0 = f.c0[k];
 }
 
+// the span (begin in the column's bytes, length) a SPAN piece leaves of its column's value in row i: both passes compute it
+template <int NC>
+__device__ __forceinline__ void map_span_of(const ColsArg& cols, const ColIds& ids, const uint8_t* lits, const SpanOp* ops, const MapPiece& p,
+                                            const RecordFields<NC>& f, uint64_t i, uint64_t* begin, uint64_t* len) {
+    uint64_t b, l, c0, so, sn;
+    if constexpr (NC > 0) pick_field(f, p.col, &b, &l, &c0);
+    else value_span(cols.c[p.col], source_row(ids.ids[p.col], i), &b, &l);
+    span_run(ops + p.off, (int)p.len, SpanValue{cols.c[p.col].data, b}, l, SpanLiterals{lits}, &so, &sn);
+    *begin = b + so, *len = sn;
+}
+
 // bytes a COLUMN or SLICE piece adds to row i: from the value's span alone, no data read
 template <int NC, int PK>
 __device__ __forceinline__ uint64_t map_field_bytes(const ColsArg& cols, const ColIds& ids, const MapPiece& p, const RecordFields<NC>& f, uint64_t i) {
@@ -114,11 +148,15 @@ __device__ __forceinline__ uint64_t map_field_bytes(const ColsArg& cols, const C
 // The length pass of one piece: the bytes piece p adds to output row i besides its literal (digit counts by compares, spans
 // from offsets alone).  PK >= kPiecesFloat: *refused, preset to UINT64_MAX, takes the lowest row with a value the FLOAT64 or
 // TIME formatter refuses.
-template <int NC, int PK>
+// SP: the plan may hold SPAN pieces, whose length is the span their program leaves: the one piece whose length reads value bytes.
+template <int NC, int PK, bool SP = false>
 __device__ __forceinline__ uint64_t map_piece_bytes(const ColsArg& cols, const ColIds& ids, const MapPiece& p, const RecordFields<NC>& f, uint64_t i,
-                                                    uint64_t* refused) {
+                                                    uint64_t* refused, const uint8_t* lits = nullptr, const SpanOp* ops = nullptr) {
     uint64_t bytes = 0;
-    if (p.kind == CPH_MAP_INT64) {
+    if (SP && p.kind == CPH_MAP_SPAN) {
+        uint64_t b;
+        map_span_of<NC>(cols, ids, lits, ops, p, f, i, &b, &bytes);
+    } else if (p.kind == CPH_MAP_INT64) {
         bytes = int_chars(p.ints[i]);
     } else if (PK >= kPiecesShortest && p.kind == CPH_MAP_FLOAT64_SHORTEST) {   // no value is refused
         bytes = short_chars(short_split(p.floats[i]), p.col);
@@ -137,12 +175,17 @@ __device__ __forceinline__ uint64_t map_piece_bytes(const ColsArg& cols, const C
 
 // pieces [k0, k1) of `pieces` for output row i, in order, into the sink; literals lie in `lits` (k0 and k1 may differ from lane
 // to lane)
-template <int NC, int PK, class Sink>
+template <int NC, int PK, bool SP = false, class Sink>
 __device__ __forceinline__ void map_put_record(Sink& s, const ColsArg& cols, const ColIds& ids, const uint8_t* lits, const MapPiece* pieces,
-                                               int k0, int k1, const RecordFields<NC>& f, uint64_t i) {
+                                               int k0, int k1, const RecordFields<NC>& f, uint64_t i, const SpanOp* ops = nullptr) {
     for (int k = k0; k < k1; k++) {
         const MapPiece& p = pieces[k];
-        if (p.kind == CPH_MAP_LITERAL) {
+        if (SP && p.kind == CPH_MAP_SPAN) {   // the span again, then a slice's copy
+            const uint8_t* data = cols.c[p.col].data;
+            uint64_t sb, sn;
+            map_span_of<NC>(cols, ids, lits, ops, p, f, i, &sb, &sn);
+            for (uint64_t q = 0; q < sn; q += 8) s.put8(load_value_chunk(data, sb, sn, (int)(q >> 3)), (uint32_t)(sn - q < 8 ? sn - q : 8));
+        } else if (p.kind == CPH_MAP_LITERAL) {
             for (uint32_t q = 0; q < p.len; q += 8)
                 s.put8(load_value_chunk(lits, p.off, p.len, (int)(q >> 3)), p.len - q < 8u ? p.len - q : 8u);
         } else if (p.kind == CPH_MAP_INT64) {

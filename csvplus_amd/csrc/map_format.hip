@@ -4,7 +4,9 @@
 //                   row i (read through that column's row ids, as the writers read a joined row), an int64 written as
 //                   strconv.FormatInt(v, 10), a float64 written as strconv.FormatFloat(v, 'f', prec, 64) (numformat_device.hpp),
 //                   a slice [from, to) of a column's value in row i, Unix seconds written as RFC 3339 (timeparse_device.hpp),
-//                   a float64 written with its shortest round-trip digits, FormatFloat(v, 'e' / 'f' / 'g', -1, 64) (shortfmt_device.hpp).
+//                   a float64 written with its shortest round-trip digits, FormatFloat(v, 'e' / 'f' / 'g', -1, 64) (shortfmt_device.hpp),
+//                   a column's value in row i narrowed by a short program of span operations — TrimSpace, Trim*, TrimPrefix /
+//                   TrimSuffix, one field of Split / SplitN, a slice of what is left (CPH_MAP_SPAN, span_device.hpp).
 //                   Bytes are copied verbatim; nothing is escaped.
 //
 // The pipeline of the gather and of the two-pass CSV writer (materialize.hip): k_map_lens (bytes per row: offsets only, the
@@ -19,10 +21,17 @@
 // also finds the lowest refused row, which comes back in the same copy as the scan's total.  The shortest pair (k_map_lens_g64 /
 // k_map_copy_g64) adds FLOAT64_SHORTEST (shortfmt_device.hpp) to all of those: the digit generator's registers stay out of the
 // float pair, which compiles to what it was.  Both passes run the digit generator; nothing is cached between them.
+// A SPAN piece is a boolean beside the piece set (SP): k_map_lens_sp / k_map_copy_sp carry SPAN over the slice set, so a template
+// of spans, slices, columns, literals and ints pays no formatter's registers, and k_map_*_spg over the shortest set, for SPAN
+// beside any other piece; both report as k_map_*_sp.  Their plan (MapPlanSp) carries the operations, at most 16 of 24 bytes,
+// behind MapPlan; every launch without a SPAN piece takes MapPlan and the instantiation it took before.  For a SPAN piece the
+// length pass reads value bytes (the span has to be found), and the copy pass finds the span again: nothing is cached between
+// them either.  One lane runs one row's program: correct for any value length, tuned for CSV-sized values.
 // Where things live: this file has the plan (a kernel argument), the two kernels' row loops and the entry point's own
 // arguments.  map_device.hpp has what a row does in either pass; map_plan.hpp has the piece rules, the plan's pieces and
 // literals, the scan with the refused-row report, the result column and the launch by piece set.  map_switch.hip shares both.
 #include <new>
+#include <type_traits>
 
 #include "map_plan.hpp"
 
@@ -35,18 +44,26 @@ struct MapPlan {
     uint64_t fixed;        // bytes of the literals together
     MapPiece p[CPH_MAP_MAX_PIECES];
 };
+// the plan of a template with SPAN pieces: their operations ride behind it, and only the _sp kernels take them
+struct MapPlanSp : MapPlan {
+    SpanOp ops[CPH_SPAN_MAX_TOTAL];
+};
+template <bool SP>
+using MapPlanOf = std::conditional_t<SP, MapPlanSp, MapPlan>;
+__device__ __forceinline__ const SpanOp* plan_ops(const MapPlan&) { return nullptr; }
+__device__ __forceinline__ const SpanOp* plan_ops(const MapPlanSp& plan) { return plan.ops; }
 
 // lens[i] = bytes of value i.  PK >= kPiecesFloat (the plan has a FLOAT64 or TIME piece): lens[n + 1], preset to UINT64_MAX, = the lowest
 // row with a value the formatter refuses.
-template <int NC, int PK = kPiecesBase>
-__global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, uint64_t* __restrict__ lens) {
+template <int NC, int PK = kPiecesBase, bool SP = false>
+__global__ __launch_bounds__(kMatThreads) void k_map_lens(ColsArg cols, ColIds ids, MapPlanOf<SP> plan, uint64_t n, uint64_t* __restrict__ lens) {
     const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;
     uint64_t* const refused = lens + n + 1;
     for (uint64_t i = (uint64_t)blockIdx.x * kMatThreads + threadIdx.x; i < n; i += stride) {
         uint64_t total = plan.fixed;
         RecordFields<NC> f;
         if constexpr (NC > 0) f.load(cols, ids, i, 0);   // offsets only
-        for (int k = 0; k < plan.npieces; k++) total += map_piece_bytes<NC, PK>(cols, ids, plan.p[k], f, i, refused);
+        for (int k = 0; k < plan.npieces; k++) total += map_piece_bytes<NC, PK, SP>(cols, ids, plan.p[k], f, i, refused, plan.lits, plan_ops(plan));
         lens[i] = total;
     }
 }
@@ -57,10 +74,14 @@ template <int NC>
 constexpr auto k_map_lens_sl = k_map_lens<NC, kPiecesSlice>;
 template <int NC>
 constexpr auto k_map_lens_g64 = k_map_lens<NC, kPiecesShortest>;
+template <int NC>
+constexpr auto k_map_lens_sp = k_map_lens<NC, kPiecesSlice, true>;
+template <int NC>
+constexpr auto k_map_lens_spg = k_map_lens<NC, kPiecesShortest, true>;
 
 // value i at out + offs[i]
-template <int NC, int PK = kPiecesBase>
-__global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds ids, MapPlan plan, uint64_t n, const uint64_t* __restrict__ offs,
+template <int NC, int PK = kPiecesBase, bool SP = false>
+__global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds ids, MapPlanOf<SP> plan, uint64_t n, const uint64_t* __restrict__ offs,
                                                          uint8_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     CPH_LDS uint8_t* stage = (CPH_LDS uint8_t*)smem;
@@ -80,11 +101,11 @@ __global__ __launch_bounds__(kMatThreads) void k_map_copy(ColsArg cols, ColIds i
         if (i < tend) {
             if (staged) {
                 WordSink s(reinterpret_cast<uint32_t*>(smem), (uint32_t)((offs[i] - obase) + (obase & 15)));
-                map_put_record<NC, PK>(s, cols, ids, plan.lits, plan.p, 0, plan.npieces, f, i);
+                map_put_record<NC, PK, SP>(s, cols, ids, plan.lits, plan.p, 0, plan.npieces, f, i, plan_ops(plan));
                 s.finish();
             } else {
                 GlobalSink s{out + offs[i]};
-                map_put_record<NC, PK>(s, cols, ids, plan.lits, plan.p, 0, plan.npieces, f, i);
+                map_put_record<NC, PK, SP>(s, cols, ids, plan.lits, plan.p, 0, plan.npieces, f, i, plan_ops(plan));
             }
         }
         if (staged) {
@@ -100,6 +121,10 @@ template <int NC>
 constexpr auto k_map_copy_sl = k_map_copy<NC, kPiecesSlice>;
 template <int NC>
 constexpr auto k_map_copy_g64 = k_map_copy<NC, kPiecesShortest>;
+template <int NC>
+constexpr auto k_map_copy_sp = k_map_copy<NC, kPiecesSlice, true>;
+template <int NC>
+constexpr auto k_map_copy_spg = k_map_copy<NC, kPiecesShortest, true>;
 
 }  // namespace cph
 
@@ -121,9 +146,11 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
     const uint64_t n = nrows;
     const std::string who = "cph_map_format: ";
     uint64_t lit_bytes = 0;
-    bool has_shortest = false, has_float = false, has_slice = false;
+    bool has_shortest = false, has_float = false, has_slice = false, has_span = false;
+    int span_ops = 0;
     {
-        Status s = check_map_pieces(pieces, npieces, ncols, n, [&](int) { return who; }, &lit_bytes, &has_shortest, &has_float, &has_slice);
+        Status s = check_map_pieces(pieces, npieces, ncols, n, [&](int) { return who; }, &lit_bytes, &has_shortest, &has_float, &has_slice, &has_span,
+                                    &span_ops);
         if (s.ok()) s = check_row_sources(cols, sel, ncols, 0, n, true);
         if (!s.ok()) return fail_with(ctx, s);
     }
@@ -136,8 +163,9 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         ColsArg arg{};
         ColIds ids{};
         CPH_TRY(stage_row_sources(ctx, cols, sel, nullptr, ncols, 0, n, &staged, &arg, &ids));
-        MapPlan plan{};
+        MapPlanSp plan{};   // a launch without SPAN pieces takes its MapPlan part
         MapPlanBuild build;
+        build.ops = plan.ops;
         plan.npieces = npieces;
         CPH_TRY(append_map_pieces(ctx, pieces, npieces, n, arg, ids, &build, plan.p, &staged, &plan.fixed));
         plan.col_mask = build.col_mask;
@@ -148,7 +176,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         uint64_t* offs = r->d_offs.as<uint64_t>();
         if (has_float) CPH_HIP_TRY(hipMemsetAsync(offs + n + 1, 0xFF, sizeof(uint64_t), ctx->stream));
         const int pk = pieces_set(has_shortest, has_float, has_slice);
-        CPH_MAP_DISPATCH(ctx, k_map_lens, pk, 0, ncols, n, 0, arg, ids, plan, n, offs);
+        CPH_MAP_DISPATCH(ctx, k_map_lens, pk, has_span, 0, ncols, n, 0, arg, ids, plan, n, offs);
         uint64_t total = 0;
         CPH_TRY(scan_with_refusal(ctx, offs, n, has_float,
                                   [&](uint64_t, const cph_map_piece** ps, int32_t* nps, std::string* prefix) {
@@ -158,7 +186,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                                   &total));
         CPH_TRY(r->d_data.alloc(&ctx->pool, total + 16));
         if (total) {
-            CPH_MAP_DISPATCH(ctx, k_map_copy, pk, 2.0 * (double)total + (8.0 + build.in_bytes) * (double)n, ncols, n, kMatStage, arg, ids, plan, n, offs,
+            CPH_MAP_DISPATCH(ctx, k_map_copy, pk, has_span, 2.0 * (double)total + (8.0 + build.in_bytes) * (double)n, ncols, n, kMatStage, arg, ids, plan, n, offs,
                              r->d_data.as<uint8_t>());
         }
         return deliver_map_column(ctx, r, n, total, out_mem);

@@ -1,7 +1,7 @@
 // map_plan.hpp — the host side the two Map entry points share (map_format.hip: one template; map_switch.hip: one per
 // alternative): the rules for a template's pieces, the pieces as the kernels see them (map_device.hpp: MapPiece) with their
 // literal block and staged number arrays, the scan with the refused-row report, the result column, and the choice among a
-// kernel's four piece sets.  Host only; the kernels and their plans (kernel arguments) stay with each entry point.
+// kernel's piece sets.  Host only; the kernels and their plans (kernel arguments) stay with each entry point.
 #pragma once
 
 #include <string>
@@ -10,11 +10,55 @@
 
 namespace cph {
 
+// The rules for the operations of one SPAN piece (include/csvplus_hip.h: cph_span_op).  fail(words) = the Status with the
+// piece's prefix in front; the operations' literal bytes count into *lit_bytes, their number into *span_ops (the call's).
+template <class Fail>
+Status check_span_piece(const cph_map_piece& p, int32_t ncols, Fail fail, uint64_t* lit_bytes, int* span_ops) {
+    if (p.arg < 0 || p.arg >= ncols) return fail("a SPAN piece's column outside 0..ncols-1");
+    if (!p.value.data || p.value.len % sizeof(cph_span_op))
+        return fail("a SPAN piece's value is a whole number of cph_span_op (40 bytes each) behind a non-NULL pointer");
+    const uint64_t nops = p.value.len / sizeof(cph_span_op);
+    if (nops < 1 || nops > CPH_SPAN_MAX_OPS) return fail("a SPAN piece holds 1..4 operations");
+    *span_ops += (int)nops;
+    if (*span_ops > CPH_SPAN_MAX_TOTAL) return fail("more than 16 SPAN operations in the pieces of one call together");
+    for (uint64_t q = 0; q < nops; q++) {
+        cph_span_op op;
+        memcpy(&op, p.value.data + q * sizeof op, sizeof op);
+        auto bad = [&](const char* name, const char* words) { return fail((std::string("SPAN operation ") + std::to_string(q) + " (" + name + "): " + words).c_str()); };
+        const char* name = op.op == CPH_SPAN_TRIM_SPACE    ? "TRIM_SPACE"
+                           : op.op == CPH_SPAN_TRIM_CUTSET ? "TRIM_CUTSET"
+                           : op.op == CPH_SPAN_TRIM_PREFIX ? "TRIM_PREFIX"
+                           : op.op == CPH_SPAN_TRIM_SUFFIX ? "TRIM_SUFFIX"
+                           : op.op == CPH_SPAN_FIELD       ? "FIELD"
+                           : op.op == CPH_SPAN_SLICE       ? "SLICE"
+                                                           : nullptr;
+        if (!name) return bad(std::to_string(op.op).c_str(), "unknown span op (1..6)");
+        const bool trim = op.op == CPH_SPAN_TRIM_SPACE || op.op == CPH_SPAN_TRIM_CUTSET;
+        if (trim && (op.mode < CPH_SPAN_LEFT || op.mode > CPH_SPAN_BOTH)) return bad(name, "unknown mode: 1 (left), 2 (right) or 3 (both)");
+        if (op.op == CPH_SPAN_FIELD && (op.mode == 0 || op.mode < -1)) return bad(name, "the limit (mode) is -1 or at least 1");
+        if (!trim && op.op != CPH_SPAN_FIELD && op.mode != 0) return bad(name, "unknown mode: 0 for this op");
+        if (op.op == CPH_SPAN_TRIM_SPACE || op.op == CPH_SPAN_SLICE) continue;   // no literal
+        if (!op.lit.data && op.lit.len) return bad(name, "a literal with bytes but no data pointer");
+        if (op.op == CPH_SPAN_TRIM_CUTSET) {
+            if (op.lit.len > CPH_SPAN_MAX_CUTSET) return bad(name, "a cutset of more than 32 bytes");
+            for (uint64_t c = 0; c < op.lit.len; c++)
+                if (op.lit.data[c] >= 0x80) return bad(name, "a cutset byte of 0x80 or above (only an ASCII cutset trims bytewise as Go trims runes)");
+            continue;   // travels as a bitmap
+        }
+        if (op.op == CPH_SPAN_FIELD && op.lit.len == 0) return bad(name, "an empty separator");
+        if (op.lit.len > CPH_SPAN_MAX_LITERAL) return bad(name, op.op == CPH_SPAN_FIELD ? "a separator of more than 255 bytes" : "a literal of more than 255 bytes");
+        *lit_bytes += op.lit.len;
+        if (*lit_bytes > 0xFFFFFFFFull) return bad(name, "literals beyond 4 GiB");
+    }
+    return {};
+}
+
 // The rules for the pieces of one template.  prefix(k) = the text in front of a rule's words for piece k.  Adds the literals'
-// bytes to *lit_bytes (all templates of a call together stay below 4 GiB) and notes which piece set the call needs.
+// bytes to *lit_bytes (all templates of a call together stay below 4 GiB) and notes which piece set the call needs, whether
+// it holds a SPAN piece, and in *span_ops the operations of the call's SPAN pieces together.
 template <class Prefix>
 Status check_map_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t ncols, uint64_t n, Prefix prefix, uint64_t* lit_bytes,
-                        bool* has_shortest, bool* has_float, bool* has_slice) {
+                        bool* has_shortest, bool* has_float, bool* has_slice, bool* has_span, int* span_ops) {
     for (int k = 0; k < npieces; k++) {
         const cph_map_piece& p = pieces[k];
         auto fail = [&](const char* words) { return Status{CPH_ERR_INVALID, prefix(k) + words}; };
@@ -57,6 +101,10 @@ Status check_map_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t nc
                     return fail("a SLICE piece's value is exactly 16 bytes (a cph_map_slice) behind a non-NULL pointer");
                 *has_slice = true;
                 break;
+            case CPH_MAP_SPAN:
+                CPH_TRY(check_span_piece(p, ncols, fail, lit_bytes, span_ops));
+                *has_span = true;
+                break;
             default:
                 return fail("unknown piece kind (1..4, 8, 10)");   // the words are pinned by the message tests; 12 is a kind too
         }
@@ -68,7 +116,9 @@ Status check_map_pieces(const cph_map_piece* pieces, int32_t npieces, int32_t nc
 struct MapPlanBuild {
     std::string lits;          // the literals of all templates, in piece order: one device block
     uint32_t col_mask = 0;     // bit c: some COLUMN piece reads column c (the copy pass preloads those)
-    uint32_t slice_cols = 0;   // bit c: some SLICE piece reads column c
+    uint32_t slice_cols = 0;   // bit c: some SLICE or SPAN piece reads column c
+    SpanOp* ops = nullptr;     // the plan's CPH_SPAN_MAX_TOTAL operations, for the SPAN pieces
+    int nops = 0;              // ... and how many are taken
     double in_bytes = 0;       // what the copy pass reads per row besides the value bytes
 };
 
@@ -76,7 +126,7 @@ struct MapPlanBuild {
 // `staged`, like the row ids of a host column.  *lit_bytes = the bytes of this template's literals together.
 inline Status append_map_pieces(cph_ctx* ctx, const cph_map_piece* pieces, int32_t npieces, uint64_t n, const ColsArg& arg, const ColIds& ids,
                                 MapPlanBuild* b, MapPiece* dst, std::vector<DevBuf>* staged, uint64_t* lit_bytes) {
-    const size_t lit0 = b->lits.size();
+    uint64_t fixed = 0;   // what the LITERAL pieces give every row (a SPAN operation's literal lies in the block too, and gives nothing)
     auto offsets_and_ids = [&](int c) {   // what reading column c's spans costs per row
         return (arg.c[c].fixed_width ? 0.0 : (double)(arg.c[c].offset_bits / 8)) + (ids.ids[c].ptr ? (double)(ids.ids[c].bits / 8) : 0.0);
     };
@@ -88,6 +138,7 @@ inline Status append_map_pieces(cph_ctx* ctx, const cph_map_piece* pieces, int32
             d.off = (uint32_t)b->lits.size();
             d.len = (uint32_t)p.value.len;
             if (d.len) b->lits.append(reinterpret_cast<const char*>(p.value.data), d.len);
+            fixed += d.len;
         } else if (p.kind == CPH_MAP_COLUMN) {
             d.col = p.arg;
             if (!((b->col_mask >> p.arg) & 1u)) b->in_bytes += offsets_and_ids(p.arg);
@@ -98,6 +149,30 @@ inline Status append_map_pieces(cph_ctx* ctx, const cph_map_piece* pieces, int32
             d.col = p.arg;
             d.from = sl.from;
             d.to = sl.to;
+            if (!(((b->slice_cols | b->col_mask) >> p.arg) & 1u)) b->in_bytes += offsets_and_ids(p.arg);
+            b->slice_cols |= 1u << p.arg;
+        } else if (p.kind == CPH_MAP_SPAN) {   // its operations behind the plan's, their literals behind the block's; not in col_mask
+            d.col = p.arg;
+            d.off = (uint32_t)b->nops;
+            d.len = (uint32_t)(p.value.len / sizeof(cph_span_op));
+            for (uint32_t q = 0; q < d.len; q++) {
+                cph_span_op op;
+                memcpy(&op, p.value.data + q * sizeof op, sizeof op);
+                SpanOp& o = b->ops[b->nops++];
+                o = SpanOp{};
+                o.op = op.op, o.mode = op.mode, o.a = op.a;
+                if (op.op == CPH_SPAN_SLICE) {
+                    o.b = op.b;
+                } else if (op.op == CPH_SPAN_TRIM_CUTSET) {   // the set as a 128-bit bitmap
+                    uint64_t set[2] = {0, 0};
+                    for (uint64_t c = 0; c < op.lit.len; c++) set[op.lit.data[c] >> 6] |= 1ull << (op.lit.data[c] & 63);
+                    o.a = (int64_t)set[0], o.b = (int64_t)set[1];
+                } else if (op.op != CPH_SPAN_TRIM_SPACE) {
+                    o.lit_off = (uint32_t)b->lits.size();
+                    o.lit_len = (uint32_t)op.lit.len;
+                    if (o.lit_len) b->lits.append(reinterpret_cast<const char*>(op.lit.data), o.lit_len);
+                }
+            }
             if (!(((b->slice_cols | b->col_mask) >> p.arg) & 1u)) b->in_bytes += offsets_and_ids(p.arg);
             b->slice_cols |= 1u << p.arg;
         } else {   // INT64 / FLOAT64 / FLOAT64_SHORTEST / TIME: 8 bytes per row
@@ -111,7 +186,7 @@ inline Status append_map_pieces(cph_ctx* ctx, const cph_map_piece* pieces, int32
             if (p.kind != CPH_MAP_INT64) d.col = p.prec;   // FLOAT64: prec; TIME: the zone; FLOAT64_SHORTEST: the format byte
         }
     }
-    *lit_bytes = b->lits.size() - lit0;
+    *lit_bytes = fixed;
     return {};
 }
 
@@ -183,12 +258,17 @@ inline Status deliver_map_column(cph_ctx* ctx, cph_colbuf_impl* r, uint64_t n, u
 
 // Launches KERNEL, KERNEL_sl, KERNEL_f64 or KERNEL_g64 for the piece set PK (map_device.hpp: pieces_set) over NROWS rows of NCOLS columns,
 // inside a function that returns Status.  The slice kernels have a profile name of their own; the float and shortest
-// ones report under the base name.
-#define CPH_MAP_DISPATCH(CTX, KERNEL, PK, BYTES, NCOLS, NROWS, SMEM, ...)                                                  \
+// ones report under the base name.  SP (the plan holds a SPAN piece): KERNEL_sp for a set up to kPiecesSlice, KERNEL_spg
+// (every piece kind) above it, both under the profile name KERNEL_sp; without SP the launches are what they were.
+#define CPH_MAP_DISPATCH(CTX, KERNEL, PK, SP, BYTES, NCOLS, NROWS, SMEM, ...)                                              \
     do {                                                                                                                   \
         {                                                                                                                  \
-            ProfScope ps_(CTX, (PK) == kPiecesSlice ? #KERNEL "_sl" : #KERNEL, BYTES);                                     \
-            if ((PK) == kPiecesShortest) {                                                                                 \
+            ProfScope ps_(CTX, (SP) ? #KERNEL "_sp" : (PK) == kPiecesSlice ? #KERNEL "_sl" : #KERNEL, BYTES);              \
+            if ((SP) && span_pieces_set(PK) == kPiecesShortest) {                                                          \
+                CPH_CSV_DISPATCH(KERNEL##_spg, NCOLS, dim3(grid_rows(NROWS)), SMEM, (CTX)->stream, __VA_ARGS__);           \
+            } else if (SP) {                                                                                               \
+                CPH_CSV_DISPATCH(KERNEL##_sp, NCOLS, dim3(grid_rows(NROWS)), SMEM, (CTX)->stream, __VA_ARGS__);            \
+            } else if ((PK) == kPiecesShortest) {                                                                                 \
                 CPH_CSV_DISPATCH(KERNEL##_g64, NCOLS, dim3(grid_rows(NROWS)), SMEM, (CTX)->stream, __VA_ARGS__);           \
             } else if ((PK) == kPiecesFloat) {                                                                             \
                 CPH_CSV_DISPATCH(KERNEL##_f64, NCOLS, dim3(grid_rows(NROWS)), SMEM, (CTX)->stream, __VA_ARGS__);           \

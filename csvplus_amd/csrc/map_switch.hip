@@ -12,12 +12,15 @@
 // may take different alternatives: every lane walks its own run [first[a], first[a + 1]) of the one flat piece array, so the
 // k-th pieces of two alternatives run together where they are of one kind and one after the other where they are not; the
 // stage sink ORs words into LDS, so no lane depends on another's progress and rows are not sorted by alternative.
-// The kernels come in map_format.hip's four piece sets, chosen over the pieces of all alternatives together.
+// The kernels come in map_format.hip's four piece sets, chosen over the pieces of all alternatives together, and in its two
+// SPAN instantiations (k_switch_*_sp / k_switch_*_spg) where any alternative holds a SPAN piece; the operations of all
+// alternatives together, at most 16, ride behind the plan (SwitchPlanSp).
 // Where things live: this file has what Switch adds to map_format.hip — the bitmaps, the byte per row, the plan with one run
 // of pieces per alternative, and the alternative in the messages.  What a row does in either pass is map_device.hpp's; the
 // piece rules, the plan's pieces and literals, the scan with the refused-row report, the result column and the launch by
 // piece set are map_plan.hpp's.
 #include <new>
+#include <type_traits>
 
 #include "map_plan.hpp"
 
@@ -34,11 +37,19 @@ struct SwitchPlan {   // travels in the kernel arguments (~1 KB beside ColsArg a
     uint64_t fixed[kSwitchAlts];               // ... and the bytes of its literals together
     MapPiece p[CPH_MAP_SWITCH_MAX_PIECES];
 };
+// the plan of a switch with SPAN pieces: their operations (of all alternatives together) ride behind it, +384 bytes
+struct SwitchPlanSp : SwitchPlan {
+    SpanOp ops[CPH_SPAN_MAX_TOTAL];
+};
+template <bool SP>
+using SwitchPlanOf = std::conditional_t<SP, SwitchPlanSp, SwitchPlan>;
+__device__ __forceinline__ const SpanOp* plan_ops(const SwitchPlan&) { return nullptr; }
+__device__ __forceinline__ const SpanOp* plan_ops(const SwitchPlanSp& plan) { return plan.ops; }
 
 // which[i] = the alternative of row i, lens[i] = bytes of its value.  PK >= kPiecesFloat: lens[n + 1], preset to UINT64_MAX, = the lowest row
 // whose OWN alternative holds a value the float formatter refuses.
-template <int NC, int PK = kPiecesBase>
-__global__ __launch_bounds__(kMatThreads) void k_switch_lens(ColsArg cols, ColIds ids, SwitchPlan plan, uint64_t n, uint8_t* __restrict__ which,
+template <int NC, int PK = kPiecesBase, bool SP = false>
+__global__ __launch_bounds__(kMatThreads) void k_switch_lens(ColsArg cols, ColIds ids, SwitchPlanOf<SP> plan, uint64_t n, uint8_t* __restrict__ which,
                                                             uint64_t* __restrict__ lens) {
     const uint64_t stride = (uint64_t)gridDim.x * kMatThreads;   // a multiple of 64: a wave's rows share their bitmap words
     const uint32_t lane = threadIdx.x & 63u;
@@ -52,7 +63,7 @@ __global__ __launch_bounds__(kMatThreads) void k_switch_lens(ColsArg cols, ColId
         if constexpr (NC > 0) f.load(cols, ids, i, 0);   // offsets only
         // the lane's own run of pieces: the k-th pieces of two alternatives that are of one kind run together
         uint64_t total = plan.fixed[a];
-        for (int k = plan.first[a]; k < plan.first[a + 1]; k++) total += map_piece_bytes<NC, PK>(cols, ids, plan.p[k], f, i, lens + n + 1);
+        for (int k = plan.first[a]; k < plan.first[a + 1]; k++) total += map_piece_bytes<NC, PK, SP>(cols, ids, plan.p[k], f, i, lens + n + 1, plan.lits, plan_ops(plan));
         lens[i] = total;
     }
 }
@@ -62,17 +73,21 @@ template <int NC>
 constexpr auto k_switch_lens_sl = k_switch_lens<NC, kPiecesSlice>;
 template <int NC>
 constexpr auto k_switch_lens_g64 = k_switch_lens<NC, kPiecesShortest>;
+template <int NC>
+constexpr auto k_switch_lens_sp = k_switch_lens<NC, kPiecesSlice, true>;
+template <int NC>
+constexpr auto k_switch_lens_spg = k_switch_lens<NC, kPiecesShortest, true>;
 
 // row i's own run of pieces [first[a], first[a + 1]): the bounds and the piece index differ from lane to lane
-template <int NC, int PK, class Sink>
-__device__ __forceinline__ void switch_put_record(Sink& s, const ColsArg& cols, const ColIds& ids, const SwitchPlan& plan, int a,
+template <int NC, int PK, bool SP, class Sink>
+__device__ __forceinline__ void switch_put_record(Sink& s, const ColsArg& cols, const ColIds& ids, const SwitchPlanOf<SP>& plan, int a,
                                                   const RecordFields<NC>& f, uint64_t i) {
-    map_put_record<NC, PK>(s, cols, ids, plan.lits, plan.p, plan.first[a], plan.first[a + 1], f, i);
+    map_put_record<NC, PK, SP>(s, cols, ids, plan.lits, plan.p, plan.first[a], plan.first[a + 1], f, i, plan_ops(plan));
 }
 
 // value i at out + offs[i]
-template <int NC, int PK = kPiecesBase>
-__global__ __launch_bounds__(kMatThreads) void k_switch_copy(ColsArg cols, ColIds ids, SwitchPlan plan, uint64_t n, const uint8_t* __restrict__ which,
+template <int NC, int PK = kPiecesBase, bool SP = false>
+__global__ __launch_bounds__(kMatThreads) void k_switch_copy(ColsArg cols, ColIds ids, SwitchPlanOf<SP> plan, uint64_t n, const uint8_t* __restrict__ which,
                                                             const uint64_t* __restrict__ offs, uint8_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     CPH_LDS uint8_t* stage = (CPH_LDS uint8_t*)smem;
@@ -95,11 +110,11 @@ __global__ __launch_bounds__(kMatThreads) void k_switch_copy(ColsArg cols, ColId
             const int a = which[i];
             if (staged) {
                 WordSink s(reinterpret_cast<uint32_t*>(smem), (uint32_t)((offs[i] - obase) + (obase & 15)));
-                switch_put_record<NC, PK>(s, cols, ids, plan, a, f, i);
+                switch_put_record<NC, PK, SP>(s, cols, ids, plan, a, f, i);
                 s.finish();
             } else {
                 GlobalSink s{out + offs[i]};
-                switch_put_record<NC, PK>(s, cols, ids, plan, a, f, i);
+                switch_put_record<NC, PK, SP>(s, cols, ids, plan, a, f, i);
             }
         }
         if (staged) {
@@ -115,6 +130,10 @@ template <int NC>
 constexpr auto k_switch_copy_sl = k_switch_copy<NC, kPiecesSlice>;
 template <int NC>
 constexpr auto k_switch_copy_g64 = k_switch_copy<NC, kPiecesShortest>;
+template <int NC>
+constexpr auto k_switch_copy_sp = k_switch_copy<NC, kPiecesSlice, true>;
+template <int NC>
+constexpr auto k_switch_copy_spg = k_switch_copy<NC, kPiecesShortest, true>;
 
 }  // namespace cph
 
@@ -153,14 +172,15 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
     auto alt_npieces = [&](int a) { return a < ncases ? cases[a].npieces : notherwise; };
     auto alt_name = [&](int a) { return "cph_map_switch: " + (a < ncases ? "case " + std::to_string(a) : std::string("otherwise")) + ", "; };
     uint64_t lit_bytes = 0;
-    bool has_shortest = false, has_float = false, has_slice = false;
+    bool has_shortest = false, has_float = false, has_slice = false, has_span = false;
+    int span_ops = 0;   // of all alternatives together
     for (int a = 0; a <= ncases; a++) {
         if (a < ncases) {
             Status s = check_pred_program(cases[a].prog, cases[a].nops, ncols);
             if (!s.ok()) return fail_with(ctx, {s.code, "cph_map_switch: case " + std::to_string(a) + ": " + s.msg});
         }
         Status s = check_map_pieces(alt_pieces(a), alt_npieces(a), ncols, n, [&](int k) { return alt_name(a) + "piece " + std::to_string(k) + ": "; },
-                                    &lit_bytes, &has_shortest, &has_float, &has_slice);
+                                    &lit_bytes, &has_shortest, &has_float, &has_slice, &has_span, &span_ops);
         if (!s.ok()) return fail_with(ctx, s);
     }
     {
@@ -179,7 +199,7 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         // one bitmap per case; a float column several cases compare is converted once
         std::vector<PredFloatCol> fcols;
         PredBitmap maps[CPH_MAP_MAX_CASES];
-        SwitchPlan plan{};
+        SwitchPlanSp plan{};   // a launch without SPAN pieces takes its SwitchPlan part
         plan.ncases = ncases;
         for (int c = 0; c < ncases; c++) {
             CPH_TRY(pred_eval_bitmap(ctx, arg, ids, cases[c].prog, cases[c].nops, 0, n, &fcols, &maps[c]));
@@ -187,6 +207,7 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         }
         // the alternatives' pieces in one flat array, their literals in one block
         MapPlanBuild build;
+        build.ops = plan.ops;
         for (int a = 0; a <= ncases; a++) {
             CPH_TRY(append_map_pieces(ctx, alt_pieces(a), alt_npieces(a), n, arg, ids, &build, plan.p + plan.first[a], &staged, &plan.fixed[a]));
             plan.first[a + 1] = plan.first[a] + alt_npieces(a);
@@ -203,7 +224,7 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
         if (has_float) CPH_HIP_TRY(hipMemsetAsync(offs + n + 1, 0xFF, sizeof(uint64_t), ctx->stream));
         const int pk = pieces_set(has_shortest, has_float, has_slice);
         // besides the value bytes, both passes read or write the alternative's byte
-        CPH_MAP_DISPATCH(ctx, k_switch_lens, pk, (8.0 + 1.0 + (double)ncases / 8.0 + build.in_bytes) * (double)n, ncols, n, 0, arg, ids, plan, n, which_dev,
+        CPH_MAP_DISPATCH(ctx, k_switch_lens, pk, has_span, (8.0 + 1.0 + (double)ncases / 8.0 + build.in_bytes) * (double)n, ncols, n, 0, arg, ids, plan, n, which_dev,
                          offs);
         uint64_t total = 0;
         CPH_TRY(scan_with_refusal(ctx, offs, n, has_float,
@@ -216,7 +237,7 @@ CPH_API int32_t cph_map_switch(cph_ctx* ctx, const cph_strcol* cols, const cph_r
                                   &total));
         CPH_TRY(r->d_data.alloc(&ctx->pool, total + 16));
         if (total) {
-            CPH_MAP_DISPATCH(ctx, k_switch_copy, pk, 2.0 * (double)total + (8.0 + 1.0 + build.in_bytes) * (double)n, ncols, n, kMatStage, arg, ids, plan, n,
+            CPH_MAP_DISPATCH(ctx, k_switch_copy, pk, has_span, 2.0 * (double)total + (8.0 + 1.0 + build.in_bytes) * (double)n, ncols, n, kMatStage, arg, ids, plan, n,
                              which_dev, offs, r->d_data.as<uint8_t>());
         }
         if (which) CPH_HIP_TRY(hipMemcpyAsync(which, which_dev, n, hipMemcpyDeviceToHost, ctx->stream));

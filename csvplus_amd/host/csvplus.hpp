@@ -82,6 +82,7 @@
 #include <locale.h>
 
 #include "csvplus_hip.h"
+#include "../csrc/span_device.hpp"   // the SPAN piece's routines: the host row model runs the code the kernels run
 
 namespace csvplus {
 
@@ -809,10 +810,18 @@ struct Rfc3339 {
 // Substr(Col("ts"), 0, 10) is Go's `row["ts"][0:10]`: the bytes [from, to) of the column's value (of its default where the row
 // lacks the column).  Python's slice rules: a negative index counts from the end, both ends are clamped into the value, from >=
 // to gives "", to == INT64_MAX (the default) means "to the end".  One deviation from Go: an index out of range clamps, no panic.
+struct SpanStep {   // one cph_span_op with its literal owned
+    int32_t op, mode;
+    int64_t a, b;
+    std::string lit;
+};
+struct Span;
 struct Substr {
     Col col;
     int64_t from, to;
+    std::vector<SpanStep> pre;   // Substr(TrimSpace(col), 0, 10): the operations in front of the slice
     Substr(Col c, int64_t f, int64_t t = INT64_MAX) : col(std::move(c)), from(f), to(t) {}
+    inline Substr(Span s, int64_t f, int64_t t = INT64_MAX);
     static std::string of(const std::string& v, int64_t from, int64_t to) {
         const int64_t l = (int64_t)v.size();
         const int64_t f = from < 0 ? (from + l < 0 ? 0 : from + l) : (from < l ? from : l);
@@ -820,12 +829,105 @@ struct Substr {
         return t > f ? v.substr((size_t)f, (size_t)(t - f)) : std::string();
     }
 };
-struct Part {   // a literal, a column, a slice of a column, a column as a fixed-precision number, or an expression's value
+// A column's value NARROWED by a short program of span operations (CPH_MAP_SPAN): TrimSpace(Col("id")) is strings.TrimSpace,
+// TrimLeft / TrimRight / Trim(col, cutset) strings.TrimLeft / TrimRight / Trim with an ASCII cutset of at most 32 bytes,
+// TrimPrefix / TrimSuffix(col, lit) once and only if the literal is there, Field(col, sep, k, limit) is strings.Split(s, sep)[k]
+// (limit -1) or strings.SplitN(s, sep, limit)[k] — k < 0 counts from the last part, an index outside the parts gives "" where
+// Go panics — and Before / After(col, sep) are strings.Cut's two halves.  They nest, Substr included:
+// Substr(TrimSpace(Col("ts")), 0, 10); at most 4 operations per part.  Accepted wherever a Part is.
+struct Span {
+    Col col;
+    std::vector<SpanStep> ops;
+    Span(Col c) : col(std::move(c)) {}   // NOLINT: implicit, so that the functions take a Col, a Substr or another Span
+    Span(Substr s) : col(std::move(s.col)), ops(std::move(s.pre)) { ops.push_back(SpanStep{CPH_SPAN_SLICE, 0, s.from, s.to, ""}); }   // NOLINT
+    Span then(SpanStep step) && {
+        if (ops.size() >= (size_t)CPH_SPAN_MAX_OPS) throw Panic("more than 4 span operations on one column value");
+        ops.push_back(std::move(step));
+        return std::move(*this);
+    }
+    // the program on one value, on the host: span_device.hpp's routines over the value's bytes
+    static std::string of(const std::vector<SpanStep>& steps, const std::string& v) {
+        struct Value {
+            const std::string& s;
+            uint64_t operator()(uint64_t off, uint64_t len, int j) const {
+                uint64_t w = 0;
+                for (uint64_t k = 0; k < 8 && 8 * (uint64_t)j + k < len; k++) w |= (uint64_t)(uint8_t)s[(size_t)(off + 8 * (uint64_t)j + k)] << (8 * k);
+                return w;
+            }
+        };
+        struct Literal {
+            const std::string& block;
+            uint32_t off, len;
+            uint64_t operator()(uint64_t j) const {
+                uint64_t w = 0;
+                for (uint64_t k = 0; k < 8 && 8 * j + k < len; k++) w |= (uint64_t)(uint8_t)block[(size_t)(off + 8 * j + k)] << (8 * k);
+                return w;
+            }
+        };
+        struct Literals {
+            const std::string& block;
+            Literal operator()(uint32_t off, uint32_t len) const { return Literal{block, off, len}; }
+        };
+        std::string block;
+        std::vector<cph::SpanOp> ops;
+        for (const SpanStep& st : steps) {
+            cph::SpanOp o{};
+            o.op = st.op, o.mode = st.mode, o.a = st.a;
+            if (st.op == CPH_SPAN_SLICE) {
+                o.b = st.b;
+            } else if (st.op == CPH_SPAN_TRIM_CUTSET) {
+                uint64_t set[2] = {0, 0};
+                for (unsigned char c : st.lit) set[c >> 6] |= 1ull << (c & 63);
+                o.a = (int64_t)set[0], o.b = (int64_t)set[1];
+            } else if (st.op != CPH_SPAN_TRIM_SPACE) {
+                o.lit_off = (uint32_t)block.size(), o.lit_len = (uint32_t)st.lit.size();
+                block += st.lit;
+            }
+            ops.push_back(o);
+        }
+        uint64_t off = 0, len = 0;
+        cph::span_run(ops.data(), (int)ops.size(), Value{v}, v.size(), Literals{block}, &off, &len);
+        return v.substr((size_t)off, (size_t)len);
+    }
+};
+inline Substr::Substr(Span s, int64_t f, int64_t t) : col(std::move(s.col)), from(f), to(t), pre(std::move(s.ops)) {
+    if (pre.size() >= (size_t)CPH_SPAN_MAX_OPS) throw Panic("more than 4 span operations on one column value");
+}
+namespace detail {
+inline std::string spanCutset(std::string cutset) {
+    if (cutset.size() > (size_t)CPH_SPAN_MAX_CUTSET) throw Panic("a trim cutset of more than 32 bytes");
+    for (unsigned char c : cutset)
+        if (c >= 0x80) throw Panic("a trim cutset byte of 0x80 or above (only an ASCII cutset trims bytewise as Go trims runes)");
+    return cutset;
+}
+inline std::string spanLiteral(std::string lit, size_t least) {
+    if (lit.size() < least) throw Panic("an empty separator in Field()");
+    if (lit.size() > (size_t)CPH_SPAN_MAX_LITERAL) throw Panic("a span literal of more than 255 bytes");
+    return lit;
+}
+}  // namespace detail
+inline Span TrimSpace(Span s) { return std::move(s).then(SpanStep{CPH_SPAN_TRIM_SPACE, CPH_SPAN_BOTH, 0, 0, ""}); }
+inline Span TrimLeftSpace(Span s) { return std::move(s).then(SpanStep{CPH_SPAN_TRIM_SPACE, CPH_SPAN_LEFT, 0, 0, ""}); }
+inline Span TrimRightSpace(Span s) { return std::move(s).then(SpanStep{CPH_SPAN_TRIM_SPACE, CPH_SPAN_RIGHT, 0, 0, ""}); }
+inline Span Trim(Span s, std::string cutset) { return std::move(s).then(SpanStep{CPH_SPAN_TRIM_CUTSET, CPH_SPAN_BOTH, 0, 0, detail::spanCutset(std::move(cutset))}); }
+inline Span TrimLeft(Span s, std::string cutset) { return std::move(s).then(SpanStep{CPH_SPAN_TRIM_CUTSET, CPH_SPAN_LEFT, 0, 0, detail::spanCutset(std::move(cutset))}); }
+inline Span TrimRight(Span s, std::string cutset) { return std::move(s).then(SpanStep{CPH_SPAN_TRIM_CUTSET, CPH_SPAN_RIGHT, 0, 0, detail::spanCutset(std::move(cutset))}); }
+inline Span TrimPrefix(Span s, std::string lit) { return std::move(s).then(SpanStep{CPH_SPAN_TRIM_PREFIX, 0, 0, 0, detail::spanLiteral(std::move(lit), 0)}); }
+inline Span TrimSuffix(Span s, std::string lit) { return std::move(s).then(SpanStep{CPH_SPAN_TRIM_SUFFIX, 0, 0, 0, detail::spanLiteral(std::move(lit), 0)}); }
+inline Span Field(Span s, std::string sep, int64_t k, int32_t limit = -1) {
+    if (limit == 0 || limit < -1) throw Panic("Field(): limit is -1 (all parts) or at least 1");
+    return std::move(s).then(SpanStep{CPH_SPAN_FIELD, limit, k, 0, detail::spanLiteral(std::move(sep), 1)});
+}
+inline Span Before(Span s, std::string sep) { return Field(std::move(s), std::move(sep), 0, 2); }
+inline Span After(Span s, std::string sep) { return Field(std::move(s), std::move(sep), 1, 2); }
+struct Part {   // a literal, a column, a slice of a column, a narrowed column, a column as a fixed-precision number, or an expression's value
     bool is_col = false;
     bool is_slice = false;        // Substr: bytes [slice.from, slice.to) of the column
     cph_map_slice slice{0, 0};
     std::string text;   // the literal's bytes
     Col col{""};
+    std::vector<SpanStep> span;   // TrimSpace(col) and its kin: the column's value narrowed by these operations
+    mutable std::vector<cph_span_op> span_abi;   // ... as the C ABI takes them, filled while a batch is mapped (the literals stay in `span`)
     int prec = -1;      // >= 0: Fixed, or Shortest (0)
     char shortest = 0;  // Shortest: the format byte; the float64 value is written with its shortest round-trip digits
     std::shared_ptr<const Expr> expr;   // Fixed(expr, prec) (prec >= 0), Itoa(expr) or Rfc3339(expr, zone) (prec < 0)
@@ -839,7 +941,10 @@ struct Part {   // a literal, a column, a slice of a column, a column as a fixed
     Part(Shortest f) : is_col(!f.expr), col(std::move(f.col)), prec(0), shortest(f.fmt), expr(std::move(f.expr)) {}   // NOLINT
     Part(Itoa i) : expr(std::move(i.expr)) {}            // NOLINT
     std::string floatText(double v) const { return shortest ? FormatShortest(v, shortest) : FormatFixed(v, prec); }
-    Part(Substr s) : is_col(true), is_slice(true), slice{s.from, s.to}, col(std::move(s.col)) {}   // NOLINT
+    Part(Substr s) : is_col(true), is_slice(s.pre.empty()), slice{s.from, s.to}, col(s.col) {   // NOLINT
+        if (!s.pre.empty()) span = Span(std::move(s)).ops;
+    }
+    Part(Span s) : is_col(true), col(std::move(s.col)), span(std::move(s.ops)) {}   // NOLINT
 };
 struct Format {
     std::vector<Part> parts;
@@ -884,6 +989,10 @@ struct Format {
             }
             if (p.is_slice) {
                 *out += Substr::of(*v, p.slice.from, p.slice.to);
+                continue;
+            }
+            if (!p.span.empty()) {
+                *out += Span::of(p.span, *v);
                 continue;
             }
             if (p.prec < 0) {
@@ -2102,6 +2211,12 @@ private:
                                  p.shortest ? (int32_t)p.shortest : p.prec, 0};
         if (!p.is_col) return cph_map_piece{CPH_MAP_LITERAL, 0, {reinterpret_cast<const uint8_t*>(p.text.data()), p.text.size()}, nullptr};
         if (p.is_slice) return cph_map_piece{CPH_MAP_SLICE, (int32_t)col, {reinterpret_cast<const uint8_t*>(&p.slice), sizeof p.slice}, nullptr};
+        if (!p.span.empty()) {
+            p.span_abi.clear();
+            for (const SpanStep& st : p.span)
+                p.span_abi.push_back(cph_span_op{st.op, st.mode, st.a, st.b, {st.lit.empty() ? nullptr : reinterpret_cast<const uint8_t*>(st.lit.data()), st.lit.size()}});
+            return cph_map_piece{CPH_MAP_SPAN, (int32_t)col, {reinterpret_cast<const uint8_t*>(p.span_abi.data()), p.span_abi.size() * sizeof(cph_span_op)}, nullptr};
+        }
         return cph_map_piece{CPH_MAP_COLUMN, (int32_t)col, {nullptr, 0}, nullptr};
     }
     // the columns a number part converts

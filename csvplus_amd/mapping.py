@@ -11,6 +11,20 @@ the new column in row i is the concatenation of the template's parts —
                          Python's slice rules (negative counts from the end, open ends, both clamped into the value, crossing
                          ends give the empty string); one deviation from Go: an index out of range clamps instead of panicking.
                          No step.  A Col with a default over a missing column slices the default;
+    Col("id").trim_space()   a Span: the column's value NARROWED by a short program of span operations — the result is a
+                         sub-span of the value, no byte changes.  The methods chain (each returns a new Span, which has the same
+                         methods), at most 4 operations per part and 16 per template or Switch:
+                           trim_space() / trim_left_space() / trim_right_space()   strings.TrimSpace / TrimLeftFunc / TrimRightFunc(s,
+                                                 unicode.IsSpace): Go's 25 space sequences, exact for every byte string;
+                           trim(cutset) / trim_left(cutset) / trim_right(cutset)   strings.Trim / TrimLeft / TrimRight with an ASCII
+                                                 cutset of at most 32 bytes (a byte of 0x80 or above is refused);
+                           trim_prefix(lit) / trim_suffix(lit)                     strings.TrimPrefix / TrimSuffix, at most 255 bytes;
+                           field(sep, k, limit=-1)   strings.Split(s, sep)[k] (limit -1) or strings.SplitN(s, sep, limit)[k]; k < 0
+                                                 counts from the last part; an index outside the parts gives b"" where Go panics;
+                           before(sep) / after(sep)  strings.Cut: field 0 / field 1 of limit 2 (after: b"" without the separator);
+                           span[a:b]             a slice of what is left: Col("ts").trim_space()[:10] is one part.
+                         Span.apply(value) is the host model.  A Col with a default over a missing column runs the program on
+                         the default.  Col("ts")[0:10] stays a Slice;
     Int(array)           array[i] written as strconv.Itoa writes it ('-' for negatives, no '+', no leading zeros); the array
                          lives on the host, or on the device: Int.on_device(device_ptr, count);
     Float(array, prec)   array[i] written as strconv.FormatFloat(v, 'f', prec, 64) writes it: prec digits behind the point,
@@ -39,9 +53,9 @@ the new column in row i is the concatenation of the template's parts —
 
 `compile` turns a template into the piece list cph_map_format takes (include/csvplus_hip.h), `render` evaluates it on one
 row held as a dict — the host model, for callers without a GPU and as the cross-check of the device.  Nothing here
-touches the GPU.  Out of scope: FormatFloat's remaining forms ('e' / 'g' with an explicit precision, 'b' / 'x', 32-bit floats); case mapping and
-TrimSpace (Go's are Unicode-aware); splitting a value on a delimiter; regular expressions; time layouts other than
-RFC 3339, named zones and DST rules.
+touches the GPU.  Out of scope: FormatFloat's remaining forms ('e' / 'g' with an explicit precision, 'b' / 'x', 32-bit floats); case mapping
+(it changes bytes and needs Go's Unicode tables); a cutset with a byte of 0x80 or above; splitting on the empty separator;
+regular expressions; time layouts other than RFC 3339, named zones and DST rules.
 
 A value that depends on a condition is a Switch — Go's `if / else if / else` inside the closure, as data:
 
@@ -67,6 +81,13 @@ from .predicates import INT64_MAX, INT64_MIN, _bytes, _go_quote
 
 LITERAL, COLUMN, INT64, FLOAT64, SLICE, TIME = 1, 2, 3, 4, 8, 10   # CPH_MAP_*
 FLOAT64_SHORTEST = 12              # CPH_MAP_FLOAT64_SHORTEST: prec carries the format byte
+SPAN = 14                          # CPH_MAP_SPAN: value carries the operations
+SPAN_TRIM_SPACE, SPAN_TRIM_CUTSET, SPAN_TRIM_PREFIX, SPAN_TRIM_SUFFIX, SPAN_FIELD, SPAN_SLICE = 1, 2, 3, 4, 5, 6   # CPH_SPAN_*
+SPAN_LEFT, SPAN_RIGHT, SPAN_BOTH = 1, 2, 3
+SPAN_MAX_OPS, SPAN_MAX_TOTAL, SPAN_MAX_CUTSET, SPAN_MAX_LITERAL = 4, 16, 32, 255
+# unicode.IsSpace as bytes: the UTF-8 encodings of Go's 25 spaces
+SPACE_SEQUENCES = (b"\t", b"\n", b"\v", b"\f", b"\r", b" ", b"\xc2\x85", b"\xc2\xa0", b"\xe1\x9a\x80") + tuple(
+    bytes([0xE2, 0x80, c]) for c in range(0x80, 0x8B)) + (b"\xe2\x80\xa8", b"\xe2\x80\xa9", b"\xe2\x80\xaf", b"\xe2\x81\x9f", b"\xe3\x80\x80")
 SHORTEST_FORMATS = "eEfgG"
 MAX_PIECES = 16                    # CPH_MAP_MAX_PIECES
 MAX_CASES = 8                      # CPH_MAP_MAX_CASES
@@ -84,8 +105,76 @@ class MissingColumn(LookupError):
         self.column = name
 
 
-class Col:
+class _SpanMethods:
+    """The chainable span operations of Col and Span; each returns a new Span."""
+
+    def _with(self, op):
+        raise NotImplementedError
+
+    def trim_space(self) -> "Span":
+        return self._with((SPAN_TRIM_SPACE, SPAN_BOTH, 0, 0, b""))
+
+    def trim_left_space(self) -> "Span":
+        return self._with((SPAN_TRIM_SPACE, SPAN_LEFT, 0, 0, b""))
+
+    def trim_right_space(self) -> "Span":
+        return self._with((SPAN_TRIM_SPACE, SPAN_RIGHT, 0, 0, b""))
+
+    def trim(self, cutset) -> "Span":
+        return self._with((SPAN_TRIM_CUTSET, SPAN_BOTH, 0, 0, _cutset(cutset)))
+
+    def trim_left(self, cutset) -> "Span":
+        return self._with((SPAN_TRIM_CUTSET, SPAN_LEFT, 0, 0, _cutset(cutset)))
+
+    def trim_right(self, cutset) -> "Span":
+        return self._with((SPAN_TRIM_CUTSET, SPAN_RIGHT, 0, 0, _cutset(cutset)))
+
+    def trim_prefix(self, lit) -> "Span":
+        return self._with((SPAN_TRIM_PREFIX, 0, 0, 0, _span_literal(lit, "trim_prefix", 0)))
+
+    def trim_suffix(self, lit) -> "Span":
+        return self._with((SPAN_TRIM_SUFFIX, 0, 0, 0, _span_literal(lit, "trim_suffix", 0)))
+
+    def field(self, sep, k, limit=-1) -> "Span":
+        for v, what in ((k, "k"), (limit, "limit")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"field: {what} is an int, not {v!r}")
+        if not INT64_MIN <= int(k) <= INT64_MAX:
+            raise ValueError("field: k is not an int64")
+        if int(limit) == 0 or not -1 <= int(limit) <= 0x7FFFFFFF:
+            raise ValueError(f"field: limit is -1 (all parts) or at least 1, not {limit!r}")
+        return self._with((SPAN_FIELD, int(limit), int(k), 0, _span_literal(sep, "field", 1)))
+
+    def before(self, sep) -> "Span":
+        return self.field(sep, 0, 2)
+
+    def after(self, sep) -> "Span":
+        return self.field(sep, 1, 2)
+
+
+def _span_literal(lit, who, least) -> bytes:
+    b = _bytes(lit)
+    if len(b) < least:
+        raise ValueError(f"{who}: an empty separator is not supported")
+    if len(b) > SPAN_MAX_LITERAL:
+        raise ValueError(f"{who}: a literal of {len(b)} bytes, more than {SPAN_MAX_LITERAL}")
+    return b
+
+
+def _cutset(cutset) -> bytes:
+    b = _bytes(cutset)
+    if len(b) > SPAN_MAX_CUTSET:
+        raise ValueError(f"trim: a cutset of {len(b)} bytes, more than {SPAN_MAX_CUTSET}")
+    if any(c >= 0x80 for c in b):
+        raise ValueError("trim: a cutset byte of 0x80 or above (only an ASCII cutset trims bytewise as Go trims runes)")
+    return b
+
+
+class Col(_SpanMethods):
     """The row's value of column `name`; with `default`, that literal where the rows lack the column (SafeGetValue)."""
+
+    def _with(self, op):
+        return Span(self, (op,))
 
     def __init__(self, name, default=None):
         self.name = str(name)
@@ -123,6 +212,113 @@ class Slice:
 
     def __repr__(self):
         return f"{self.col!r}[{self.start or ''}:{'' if self.stop == INT64_MAX else self.stop}]"
+
+
+def _space_at_head(v: bytes, at: int, end: int) -> int:
+    """Bytes of the space sequence that starts at v[at] inside v[:end]: 0, 1, 2 or 3."""
+    for seq in SPACE_SEQUENCES:
+        if at + len(seq) <= end and v[at:at + len(seq)] == seq:
+            return len(seq)
+    return 0
+
+
+def _space_at_tail(v: bytes, at: int, end: int) -> int:
+    """Bytes of the space sequence that ends at v[end - 1] inside v[at:end], start byte included: utf8.DecodeLastRune's decision."""
+    for seq in SPACE_SEQUENCES:
+        if end - len(seq) >= at and v[end - len(seq):end] == seq:
+            return len(seq)
+    return 0
+
+
+class Span(_SpanMethods):
+    """Span(col, ops): the value of `col` narrowed by the operations, left to right.  An operation is the tuple
+    (op, mode, a, b, literal) of a cph_span_op.  Made by the methods of Col and Span, and by Span[a:b]."""
+
+    def __init__(self, col, ops):
+        if not isinstance(col, Col):
+            raise TypeError(f"Span: not a Col: {col!r}")
+        self.col = col
+        self.ops = tuple(ops)
+        if not 1 <= len(self.ops) <= SPAN_MAX_OPS:
+            raise ValueError(f"a Span holds 1..{SPAN_MAX_OPS} operations, not {len(self.ops)}")
+
+    def _with(self, op):
+        return Span(self.col, self.ops + (op,))
+
+    def __getitem__(self, key) -> "Span":
+        if not isinstance(key, slice) or key.step is not None:
+            raise TypeError(f"Span[...]: only a slice without a step, not {key!r}")
+        sl = Slice(self.col, key.start, key.stop)   # its checks and its open ends
+        return self._with((SPAN_SLICE, 0, sl.start, sl.stop, b""))
+
+    @property
+    def name(self):
+        return self.col.name
+
+    def apply(self, value: bytes) -> bytes:
+        """The host model: the program on one value."""
+        v = bytes(value)
+        a, e = 0, len(v)
+        for op, mode, x, y, lit in self.ops:
+            if op == SPAN_TRIM_SPACE:
+                if mode & SPAN_LEFT:
+                    while True:
+                        n = _space_at_head(v, a, e)
+                        if not n:
+                            break
+                        a += n
+                if mode & SPAN_RIGHT:
+                    while True:
+                        n = _space_at_tail(v, a, e)
+                        if not n:
+                            break
+                        e -= n
+            elif op == SPAN_TRIM_CUTSET:
+                if mode & SPAN_LEFT:
+                    while a < e and v[a] in lit:
+                        a += 1
+                if mode & SPAN_RIGHT:
+                    while e > a and v[e - 1] in lit:
+                        e -= 1
+            elif op == SPAN_TRIM_PREFIX:
+                if len(lit) <= e - a and v[a:a + len(lit)] == lit:
+                    a += len(lit)
+            elif op == SPAN_TRIM_SUFFIX:
+                if len(lit) <= e - a and v[e - len(lit):e] == lit:
+                    e -= len(lit)
+            elif op == SPAN_FIELD:
+                starts, ends, at = [], [], a   # strings.SplitN(v[a:e], lit, mode): left to right, no overlap
+                while mode < 0 or len(starts) < mode - 1:
+                    m = v.find(lit, at, e)
+                    if m < 0:
+                        break
+                    starts.append(at)
+                    ends.append(m)
+                    at = m + len(lit)
+                starts.append(at)
+                ends.append(e)
+                k = x + len(starts) if x < 0 else x
+                a, e = (starts[k], ends[k]) if 0 <= k < len(starts) else (a, a)
+            else:   # SPAN_SLICE
+                lo, hi, _ = slice(x, None if y == INT64_MAX else y).indices(e - a)
+                a, e = (a + lo, a + max(hi, lo))
+        return v[a:e]
+
+    def __repr__(self):
+        names = {(SPAN_TRIM_SPACE, 3): "trim_space()", (SPAN_TRIM_SPACE, 1): "trim_left_space()", (SPAN_TRIM_SPACE, 2): "trim_right_space()"}
+        out = repr(self.col)
+        for op, mode, x, y, lit in self.ops:
+            if op == SPAN_TRIM_SPACE:
+                out += "." + names[(op, mode)]
+            elif op == SPAN_TRIM_CUTSET:
+                out += f".{('trim_left', 'trim_right', 'trim')[mode - 1]}({lit!r})"
+            elif op in (SPAN_TRIM_PREFIX, SPAN_TRIM_SUFFIX):
+                out += f".{'trim_prefix' if op == SPAN_TRIM_PREFIX else 'trim_suffix'}({lit!r})"
+            elif op == SPAN_FIELD:
+                out += f".field({lit!r}, {x}, {mode})"
+            else:
+                out += f"[{x or ''}:{'' if y == INT64_MAX else y}]"
+        return out
 
 
 class Int:
@@ -295,12 +491,12 @@ class Format:
             raise ValueError("Format: no parts")
         self.parts = []
         for p in parts:
-            if isinstance(p, (Col, Slice, Int, Float)):
+            if isinstance(p, (Col, Slice, Span, Int, Float)):
                 self.parts.append(p)
             elif isinstance(p, (bytes, bytearray, memoryview, str)):
                 self.parts.append(_bytes(p))
             else:
-                raise TypeError(f"not a template part: {p!r} (closures cannot run on the device; use bytes / str, Col, Col[a:b], Int, Float, Time)")
+                raise TypeError(f"not a template part: {p!r} (closures cannot run on the device; use bytes / str, Col, Col[a:b], Col.trim_space() and its kin, Int, Float, Time)")
 
     def __repr__(self):
         return f"Format{tuple(self.parts)!r}"
@@ -346,7 +542,7 @@ def _template(t) -> Format:
         return t
     if isinstance(t, Switch):
         raise TypeError("a Switch stands where a whole template stands: it is no part of a Format and does not nest")
-    if isinstance(t, (Col, Slice, Int, Float, bytes, bytearray, memoryview, str)):
+    if isinstance(t, (Col, Slice, Span, Int, Float, bytes, bytearray, memoryview, str)):
         return Format(t)
     raise TypeError(f"not a template: {t!r}")
 
@@ -378,7 +574,7 @@ def columns(template) -> list:
                     names.append(name)
         return names
     for p in _template(template).parts:
-        if isinstance(p, (Col, Slice)):
+        if isinstance(p, (Col, Slice, Span)):
             found = [p.name]
         elif isinstance(p, (Int, Float)) and p.expr is not None:
             from . import expr as E
@@ -393,9 +589,10 @@ def columns(template) -> list:
 
 def compile(template, column_names):   # noqa: A001 (the name predicates.compile uses)
     """(names of the columns used, pieces).  A piece is (LITERAL, 0, bytes), (COLUMN, k, None) with k indexing the returned
-    name list, (SLICE, k, (from, to)), (INT64, 0, Int), (FLOAT64, 0, Float), (FLOAT64_SHORTEST, 0, Float) or (TIME, 0, Time).  A Col (or the Col of a Slice) whose name is not among `column_names` becomes its default as a literal — in
+    name list, (SLICE, k, (from, to)), (SPAN, k, ((op, mode, a, b, literal), ...)), (INT64, 0, Int), (FLOAT64, 0, Float), (FLOAT64_SHORTEST, 0, Float) or (TIME, 0, Time).  A Col (or the Col of a Slice) whose name is not among `column_names` becomes its default as a literal — in
     structure-of-arrays a column is present for all rows or for none — and without a default raises MissingColumn.
-    Neighbouring literals are joined.  Raises ValueError beyond the ABI's limits (16 pieces, 16 columns)."""
+    A Span over such a column runs its program on the default, likewise.
+    Neighbouring literals are joined.  Raises ValueError beyond the ABI's limits (16 pieces, 16 columns, 16 span operations)."""
     known = [str(c) for c in column_names]
     used: list[str] = []
     pieces: list[tuple] = []
@@ -420,9 +617,11 @@ def compile(template, column_names):   # noqa: A001 (the name predicates.compile
                 used.append(p.name)
             if isinstance(p, Slice):
                 pieces.append((SLICE, used.index(p.name), (p.start, p.stop)))
+            elif isinstance(p, Span):
+                pieces.append((SPAN, used.index(p.name), p.ops))
             else:
                 pieces.append((COLUMN, used.index(p.name), None))
-        elif isinstance(p, Slice) and p.col.default is not None:   # the default, sliced on the host
+        elif isinstance(p, (Slice, Span)) and p.col.default is not None:   # the default, sliced or narrowed on the host
             literal(p.apply(p.col.default))
         elif isinstance(p, Col) and p.default is not None:
             literal(p.default)
@@ -432,6 +631,9 @@ def compile(template, column_names):   # noqa: A001 (the name predicates.compile
         raise ValueError(f"template compiles to {len(pieces)} pieces, more than {MAX_PIECES}")
     if len(used) > MAX_COLUMNS:
         raise ValueError(f"template reads {len(used)} columns, more than {MAX_COLUMNS}")
+    nops = sum(len(v) for kind, _, v in pieces if kind == SPAN)
+    if nops > SPAN_MAX_TOTAL:
+        raise ValueError(f"template holds {nops} span operations, more than {SPAN_MAX_TOTAL}")
     return used, pieces
 
 
@@ -455,7 +657,7 @@ def compile_switch(switch, column_names):
 
     def alternative(tmpl):
         used, pieces = compile(tmpl, known)
-        return [(kind, index_of(used[arg]), v) if kind in (COLUMN, SLICE) else (kind, arg, v) for kind, arg, v in pieces]
+        return [(kind, index_of(used[arg]), v) if kind in (COLUMN, SLICE, SPAN) else (kind, arg, v) for kind, arg, v in pieces]
 
     cases = []
     for pred, tmpl in switch.cases:
@@ -468,6 +670,9 @@ def compile_switch(switch, column_names):
         raise ValueError(f"Switch compiles to {total} pieces in all, more than {SWITCH_MAX_PIECES}")
     if len(shared) > MAX_COLUMNS:
         raise ValueError(f"Switch reads {len(shared)} columns, more than {MAX_COLUMNS}")
+    nops = sum(len(v) for pc in [pc for _, pc in cases] + [otherwise] for kind, _, v in pc if kind == SPAN)
+    if nops > SPAN_MAX_TOTAL:
+        raise ValueError(f"Switch holds {nops} span operations in all, more than {SPAN_MAX_TOTAL}")
     return shared, cases, otherwise
 
 
@@ -571,7 +776,7 @@ def render(template, row, i: int = 0) -> bytes:
                 raise ValueError("render: a Float part on the device has no host values")
             out.append(p.text(p.values[i]))
         else:
-            col = p.col if isinstance(p, Slice) else p
+            col = p.col if isinstance(p, (Slice, Span)) else p
             v = row.get(col.name)
             if v is None:
                 v = row.get(col.name.encode("utf-8"))
@@ -579,5 +784,5 @@ def render(template, row, i: int = 0) -> bytes:
                 if col.default is None:
                     raise MissingColumn(col.name)
                 v = col.default
-            out.append(p.apply(_bytes(v)) if isinstance(p, Slice) else _bytes(v))
+            out.append(p.apply(_bytes(v)) if isinstance(p, (Slice, Span)) else _bytes(v))
     return b"".join(out)

@@ -608,7 +608,7 @@ def _map_rows(cols_by_name, row_ids, nrows, names, pieces, keep, who):
 
 
 def _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending=None, tag=None):
-    """The cph_map_piece array of `pieces` (mapping.compile).  An Int.of / Float.of part is evaluated over the n rows into a
+    """The cph_map_piece array of `pieces` (mapping.compile); a SPAN piece's operations become a cph_span_op array.  An Int.of / Float.of part is evaluated over the n rows into a
     device array (cph_num_eval, appended to `computed`).  A failing row raises expr.ExprError at once — or, with a `pending`
     list, the part is evaluated again into host memory and (tag, expression, NumCol with host status) is appended, for a
     caller that decides per row whether the failure counts."""
@@ -630,6 +630,18 @@ def _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending=
             parr[k].arg = arg
             parr[k].value.data = b.ctypes.data
             parr[k].value.len = 16
+        elif kind == M.SPAN:   # value: the operations, one cph_span_op each
+            ops = (N.cph_span_op * len(value))()
+            for q, (op, mode, a, b, lit) in enumerate(value):
+                ops[q].op, ops[q].mode, ops[q].a, ops[q].b = op, mode, a, b
+                lb = np.frombuffer(lit, dtype=np.uint8)
+                keep.append(lb)
+                ops[q].lit.data = lb.ctypes.data if len(lb) else None
+                ops[q].lit.len = len(lb)
+            keep.append(ops)
+            parr[k].arg = arg
+            parr[k].value.data = C.addressof(ops)
+            parr[k].value.len = C.sizeof(ops)
         else:
             if value.expr is not None:   # evaluated over the same rows into a device array: cph_num_eval
                 nc = eval_number(ctx, cols_by_name, value.expr, row_ids=row_ids, nrows=n, out_mem=N.CPH_MEM_DEVICE)

@@ -773,9 +773,9 @@ CPH_API int32_t cph_json_write_rows(cph_ctx* ctx, const cph_strcol* cols, const 
  * 31, 38, 39, 43..47, 54, 55, 62..71, 78..) is invalid.
  *
  * Out of scope for a condition: boolean-valued ops and math functions inside an expression, string operands inside an
- * expression, prefix / suffix / contains against another column; case mapping and TrimSpace (Go's are Unicode-aware: a project
- * of their own); splitting on a delimiter; regular expressions; time layouts other than RFC 3339, named zones, and comparing
- * below the second.
+ * expression, prefix / suffix / contains against another column; case mapping (it needs Go's Unicode tables: a project of
+ * its own); a condition on a trimmed or split value directly (map it first: a CPH_MAP_SPAN piece of cph_map_format gives an
+ * ordinary column); regular expressions; time layouts other than RFC 3339, named zones, and comparing below the second.
  */
 enum { CPH_PRED_LIKE = 1, CPH_PRED_NOT = 2, CPH_PRED_ALL = 3, CPH_PRED_ANY = 4 };
 enum { CPH_PRED_INT_LT = 16, CPH_PRED_INT_LE = 17, CPH_PRED_INT_EQ = 18, CPH_PRED_INT_NE = 19, CPH_PRED_INT_GE = 20, CPH_PRED_INT_GT = 21 };
@@ -1057,6 +1057,32 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  *                    "NaN", the infinities "+Inf" and "-Inf".  Exact for every double (Schubfach, one 128-bit table entry per
  *                    value), and NO value is refused: 2^128 and 1e300 are formatted like any other.  The text reads back to
  *                    the same bits through cph_col_to_number.
+ *   CPH_MAP_SPAN     the value of column `arg` in row i (read through its own row ids, like COLUMN and SLICE) NARROWED by a short
+ *                    program of span operations: the result is a sub-span of the source value, no byte changes.  `value` points
+ *                    at 1..CPH_SPAN_MAX_OPS cph_span_op in host memory; they are applied left to right, each to the span the
+ *                    previous one left.  Each stands for a Go call, over bytes:
+ *                      TRIM_SPACE    mode BOTH: strings.TrimSpace; LEFT / RIGHT: strings.TrimLeftFunc / TrimRightFunc(s,
+ *                                    unicode.IsSpace).  Exact for every byte string, invalid UTF-8 included: a space is one of 25
+ *                                    byte sequences — \t \n \v \f \r ' '; C2 85, C2 A0; E1 9A 80; E2 80 80 .. E2 80 8A; E2 80 A8,
+ *                                    E2 80 A9, E2 80 AF; E2 81 9F; E3 80 80 — and from each end the longest run of them goes.  At
+ *                                    the tail a sequence matches only together with its start byte (utf8.DecodeLastRune's
+ *                                    decision): a lone 85 or 80 stops the trim, "E2 80 80 80" keeps its four bytes, "E2 C2 85"
+ *                                    loses its last two.
+ *                      TRIM_CUTSET   strings.Trim / TrimLeft / TrimRight(s, cutset) by mode.  The cutset is 0..32 bytes, all below
+ *                                    0x80 (bytewise trimming is then Go's result for every byte string); the empty set changes
+ *                                    nothing; a set byte of 0x80 or above is refused, never guessed.
+ *                      TRIM_PREFIX / TRIM_SUFFIX   strings.TrimPrefix / TrimSuffix: once, and only if the literal (any bytes,
+ *                                    0..255 of them) is there.
+ *                      FIELD         parts = strings.Split(s, sep) for mode -1, strings.SplitN(s, sep, mode) for mode >= 1; the
+ *                                    result is parts[a] for a >= 0 and parts[len(parts) + a] for a < 0.  One deviation, SLICE's
+ *                                    kind: an index outside parts gives the empty span where Go panics.  strings.Cut falls out of
+ *                                    it: `before` is field 0 of limit 2, `after` field 1 of limit 2 (empty when the separator is
+ *                                    absent).  The separator is 1..255 bytes of any value, matched left to right without
+ *                                    overlap ("aaa" on "aa": "", "a"); the empty value gives one empty field.
+ *                      SLICE         bytes [a, b) of the current span under cph_map_slice's rules: TrimSpace(ts)[:10] is one piece.
+ *                    The SPAN pieces of one call hold at most CPH_SPAN_MAX_TOTAL operations together; their literal bytes go
+ *                    into the plan's literal block and count against its 4 GiB.  One lane runs one row's program: correct for
+ *                    any value length, tuned for CSV-sized values.  Both passes compute the span; nothing is cached between them.
  * All bytes are copied verbatim (NUL and bytes >= 0x80 included); nothing is escaped.
  *
  * cols / sel / nrows mean exactly what they mean for cph_csv_write_rows (host or device columns, fixed-width or 32 / 64-bit
@@ -1069,7 +1095,7 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  * legal and yields an empty column.
  *
  * CPH_ERR_INVALID (with a message in cph_last_error): NULL ctx / pieces / out, npieces outside 1..CPH_MAP_MAX_PIECES, an
- * unknown kind (5..7, 9, 11 and 13 included), a COLUMN or SLICE index outside 0..ncols-1 (a column the rows lack is the host's business:
+ * unknown kind (5..7, 9, 11, 13 and 15 included), a COLUMN, SLICE or SPAN index outside 0..ncols-1 (a column the rows lack is the host's business:
  * it substitutes a literal or reports the reference's missing-column error), a SLICE whose value is not exactly 16 bytes
  * behind a non-NULL pointer, a literal with a length but no pointer, an INT64 piece with ints ==
  * NULL while nrows > 0 or with an unknown memory space, a FLOAT64 piece with floats == NULL while nrows > 0, with an unknown
@@ -1077,23 +1103,41 @@ CPH_API int32_t cph_num_eval(cph_ctx* ctx, const cph_strcol* cols, const cph_row
  * ints == NULL while nrows > 0, with an unknown memory space or with prec outside -1439..1439, a TIME value whose local year is
  * outside 0000..9999 (found while the call runs), a FLOAT64_SHORTEST piece with floats == NULL while nrows > 0, with an unknown
  * memory space or with a prec that is none of 'e' 'E' 'f' 'g' 'G' (FLOAT64 with prec -1 stays refused: the shortest digits are
- * the other kind), ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
+ * the other kind), a SPAN piece whose value is NULL or no whole number of cph_span_op, with 0 or more than CPH_SPAN_MAX_OPS
+ * operations, or that brings the call beyond CPH_SPAN_MAX_TOTAL, a span operation with an unknown op or mode, with a literal
+ * that has a length but no pointer or is over its limit (32 / 255 bytes), a cutset byte of 0x80 or above, an empty separator,
+ * a FIELD limit of 0 or below -1, ncols outside 0..16 or cols NULL with ncols > 0, row-id bits other
  * than 32 / 64, an identity column whose row count is not nrows, an unknown out_mem.
  *
  * Out of scope: the remaining forms of FormatFloat — 'e' / 'g' with an explicit precision, 'b' / 'x', and 32-bit floats
- * (bitSize 32) —; case mapping and TrimSpace (Go's are Unicode-aware: a project of their own); splitting a value
- * on a delimiter; regular expressions; a slice whose ends come from another column; time layouts other than RFC 3339, named
+ * (bitSize 32) —; case mapping (it changes bytes and needs Go's Unicode tables: a project of its own); a cutset with
+ * a byte of 0x80 or above; splitting on the empty separator; regular expressions; a slice whose ends come from another column; time layouts other than RFC 3339, named
  * zones and DST rules.  A value that
  * depends on a condition is cph_map_switch's.
  */
 enum { CPH_MAP_LITERAL = 1, CPH_MAP_COLUMN = 2, CPH_MAP_INT64 = 3, CPH_MAP_FLOAT64 = 4, CPH_MAP_SLICE = 8, CPH_MAP_TIME = 10,
-       CPH_MAP_FLOAT64_SHORTEST = 12 };   /* 5..7, 9, 11: invalid */
+       CPH_MAP_FLOAT64_SHORTEST = 12, CPH_MAP_SPAN = 14 };   /* 5..7, 9, 11, 13: invalid */
 #define CPH_MAP_MAX_PIECES 16
 typedef struct { int64_t from, to; } cph_map_slice;   /* what a SLICE piece's `value` points at: 16 bytes */
+/* One operation of a SPAN piece (see CPH_MAP_SPAN above); a piece's `value` points at 1..CPH_SPAN_MAX_OPS of them. */
+enum { CPH_SPAN_TRIM_SPACE = 1, CPH_SPAN_TRIM_CUTSET = 2, CPH_SPAN_TRIM_PREFIX = 3, CPH_SPAN_TRIM_SUFFIX = 4, CPH_SPAN_FIELD = 5,
+       CPH_SPAN_SLICE = 6 };
+enum { CPH_SPAN_LEFT = 1, CPH_SPAN_RIGHT = 2, CPH_SPAN_BOTH = 3 };   /* the mode of TRIM_SPACE / TRIM_CUTSET */
+#define CPH_SPAN_MAX_OPS      4     /* operations in one SPAN piece */
+#define CPH_SPAN_MAX_TOTAL    16    /* operations in the SPAN pieces of one call together (all alternatives of a switch) */
+#define CPH_SPAN_MAX_CUTSET   32    /* bytes of a TRIM_CUTSET set, each below 0x80 */
+#define CPH_SPAN_MAX_LITERAL  255   /* bytes of a TRIM_PREFIX / TRIM_SUFFIX literal (0..255) or of a FIELD separator (1..255) */
+typedef struct {
+    int32_t    op;    /* CPH_SPAN_* */
+    int32_t    mode;  /* TRIM_SPACE / TRIM_CUTSET: CPH_SPAN_LEFT / RIGHT / BOTH; FIELD: SplitN's n, -1 (all) or >= 1; otherwise 0 */
+    int64_t    a, b;  /* SLICE: from, to (cph_map_slice's rules); FIELD: a = the index k, b = 0; otherwise 0 */
+    cph_strval lit;   /* TRIM_CUTSET: the set; TRIM_PREFIX / TRIM_SUFFIX: the literal; FIELD: the separator; host memory */
+} cph_span_op;
 typedef struct {
     int32_t        kind;    /* CPH_MAP_* */
-    int32_t        arg;     /* COLUMN / SLICE: index into cols; INT64 / FLOAT64 / FLOAT64_SHORTEST / TIME: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
-    cph_strval     value;   /* LITERAL: its bytes (host memory, any length, any byte values); SLICE: a cph_map_slice, len == 16 */
+    int32_t        arg;     /* COLUMN / SLICE / SPAN: index into cols; INT64 / FLOAT64 / FLOAT64_SHORTEST / TIME: memory space of `ints` / `floats` (CPH_MEM_*); LITERAL: ignored */
+    cph_strval     value;   /* LITERAL: its bytes (host memory, any length, any byte values); SLICE: a cph_map_slice, len == 16;
+                               SPAN: 1..CPH_SPAN_MAX_OPS cph_span_op, len == their number * sizeof(cph_span_op) */
     const int64_t* ints;    /* INT64 / TIME: nrows values, entry i belongs to OUTPUT row i (no row ids) */
     const double*  floats;  /* FLOAT64 / FLOAT64_SHORTEST: likewise */
     int32_t        prec;    /* FLOAT64: digits behind the point, 0..22; TIME: the zone, minutes east of UTC, -1439..1439; FLOAT64_SHORTEST: the format byte */
@@ -1120,7 +1164,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  *
  * Selection.  Row i takes the alternative a = the lowest case index whose program holds, or ncases (`otherwise`) if none
  * does.  Its value is that alternative's pieces rendered exactly as cph_map_format renders them (LITERAL / COLUMN / INT64 /
- * FLOAT64 / FLOAT64_SHORTEST / SLICE / TIME; verbatim bytes; FormatInt, FormatFloat and RFC 3339 rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
+ * FLOAT64 / FLOAT64_SHORTEST / SLICE / TIME / SPAN; verbatim bytes; FormatInt, FormatFloat and RFC 3339 rules).  which[i] = a when `which` is not NULL (nrows bytes of HOST
  * memory, written when the call succeeds).
  *
  * Number pieces.  INT64 / FLOAT64 / FLOAT64_SHORTEST / TIME arrays have nrows entries indexed by OUTPUT row.  Entries of rows that select ANOTHER
@@ -1138,7 +1182,7 @@ CPH_API int32_t cph_map_format(cph_ctx* ctx, const cph_strcol* cols, const cph_r
  * cph_map_format rejects in a piece or in the row sources.  CPH_ERR_TOO_MANY_ROWS for nrows > 2^32 - 1 (the predicate
  * evaluator's limit).
  *
- * Out of scope: nested switches; a conditional part inside a template (use one Switch over whole templates); case mapping and TrimSpace; splitting on a delimiter; regular expressions;
+ * Out of scope: nested switches; a conditional part inside a template (use one Switch over whole templates); case mapping; a non-ASCII cutset and an empty separator (SPAN pieces); regular expressions;
  * the other forms of FormatFloat; time layouts other than RFC 3339.
  */
 #define CPH_MAP_MAX_CASES         8
