@@ -570,14 +570,120 @@ class Context:
                                        "algo_bytes": float(arr[i].algo_bytes)} for i in range(min(cap, n.value))}
 
 
-def _cols_array(cols):
+class Owned:
+    """Owner of one library result: `ptr` is given back once, by the subclass's release function, at release() / close(),
+    when the owner dies, or when its ctx closes (the library wants its results released before the ctx).  A subclass
+    names the function and reads what it shows out of ptr.contents."""
+    _release_fn = None
+
+    def __init__(self, ctx, ptr, lib=None):
+        self.ctx, self.ptr, self.lib = ctx, ptr, lib or ctx.lib
+        if ctx is not None:
+            ctx._children.add(self)
+
+    def release(self):
+        ptr, self.ptr = getattr(self, "ptr", None), None
+        if ptr:
+            getattr(self.lib, self._release_fn)(ptr)
+
+    close = release
+
+    def taken(self, copy):
+        """copy(self), then release: the tail of a call whose result goes to the host."""
+        try:
+            return copy(self)
+        finally:
+            self.release()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def result_array(ptr, n: int, dtype, mem: int):
+    """An array of a result as its owner shows it: a numpy copy (HOST) or a (device pointer, count) pair (DEVICE)."""
+    return _ptr_array(ptr, n, dtype).copy() if mem == CPH_MEM_HOST else (int(ptr or 0), n)
+
+
+class _Raw:   # minimal object with data_ptr(): a library-owned device buffer as a StrCol's data / offsets
+    def __init__(self, p):
+        self._p = int(p or 0)
+
+    def data_ptr(self):
+        return self._p
+
+
+# ---- marshallers: Python values -> the structures of the C ABI; what a pointer points into is appended to `keep` ---------
+
+def cols_array(cols, keep):
+    """The cph_strcol array of `cols` (StrCols)."""
     arr = (cph_strcol * len(cols))()
-    keep = []
     for i, c in enumerate(cols):
-        sc, k = c.as_c()
-        arr[i] = sc
+        arr[i], k = c.as_c()
         keep.append(k)
-    return arr, keep
+    keep.append(arr)
+    return arr
+
+
+def _cols_array(cols):
+    """(cols_array(cols, keep), keep) with a keep list of its own: for a call that marshals nothing else."""
+    keep = []
+    return cols_array(cols, keep), keep
+
+
+def fill_rowsel(sel, ids, keep) -> int:
+    """Fills the cph_rowsel `sel` from row ids in one of three forms and returns their count: a numpy array (uint64 stays,
+    every other dtype becomes uint32), (numpy ids, base), or (device_ptr, bits, count[, base]).  Only a host form appends
+    to `keep`."""
+    base = 0
+    if isinstance(ids, tuple) and isinstance(ids[0], np.ndarray):
+        ids, base = ids
+    if isinstance(ids, np.ndarray):
+        if ids.dtype != np.uint64:
+            ids = ids.astype(np.uint32)
+        ids = np.ascontiguousarray(ids)
+        keep.append(ids)
+        sel.ids, sel.bits, count = ids.ctypes.data if len(ids) else None, ids.dtype.itemsize * 8, len(ids)
+    else:
+        sel.ids, sel.bits, count = int(ids[0]) or None, int(ids[1]), int(ids[2])
+        base = ids[3] if len(ids) > 3 else 0
+    sel.base = int(base)
+    return count
+
+
+def number_source(src, kind, need, who, keep, stand_in=False):
+    """(pointer or None, CPH_MEM_*) of a source of at least `need` int64 (kind CPH_NUM_INT64) or float64 values: anything
+    numpy turns into such an array (host), a (device_ptr, count) pair, a device tensor (an object with data_ptr()), or an
+    IntArr / FloatArr / Int / Float object, which stands for its host array or its device pair.  who: the message for a
+    source that is too short, with {src}, {count}, {need} and {last} (need - 1) to fill in; what stands in front of its
+    colon names the caller in the tensor messages.  stand_in: an empty host array is passed as one zero, for a call that
+    wants a pointer even then."""
+    want = "int64" if kind == CPH_NUM_INT64 else "float64"
+    given = src
+    if isinstance(getattr(src, "device", None), bool):   # IntArr / FloatArr / Int / Float
+        src = (src.values, src.count) if src.device else src.values
+    if isinstance(src, tuple):
+        ptr, count, mem = int(src[0]) or None, int(src[1]), CPH_MEM_DEVICE
+    elif hasattr(src, "data_ptr"):
+        name = who.partition(":")[0]
+        if not str(getattr(src, "dtype", want)).endswith(want):
+            raise ValueError(f"{name}: the tensor's dtype is {src.dtype}, the kind wants {want}")
+        if not getattr(src, "is_cuda", True):
+            raise ValueError(f"{name}: a tensor source must live on the device (pass .numpy() for host values)")
+        keep.append(src)
+        ptr, count, mem = int(src.data_ptr()) or None, int(src.numel()), CPH_MEM_DEVICE
+    else:
+        v = np.ascontiguousarray(np.asarray(src, dtype=want).reshape(-1))
+        count = len(v)
+        if stand_in and not count:
+            v = np.zeros(1, v.dtype)
+        keep.append(v)
+        ptr, mem = (v.ctypes.data if len(v) else None), CPH_MEM_HOST
+    if count < need:
+        raise ValueError(who.format(src=given, count=count, need=need, last=need - 1))
+    return ptr, mem
 
 
 class DeviceIndex:
@@ -607,9 +713,7 @@ class DeviceIndex:
         arr = (cph_index_spec * k)()
         keep = []
         for i, (cols, unique) in enumerate(specs):
-            ca, kp = _cols_array(cols)
-            keep.append((ca, kp))
-            arr[i].keycols = ca
+            arr[i].keycols = cols_array(cols, keep)
             arr[i].nkeycols = len(cols)
             arr[i].unique = 1 if unique else 0
         outs = (_P * k)()
@@ -784,10 +888,9 @@ def join_chain(ctx: Context, steps, probe_base: int = 0, out_mem: int = CPH_MEM_
     keep = []
     for i, step in enumerate(steps):
         index, cols = step[0], step[1]
-        carr, k = _cols_array(cols)
-        keep.append((carr, k, index))
+        keep.append(index)
         arr[i].index = index.handle
-        arr[i].cols = carr
+        arr[i].cols = cols_array(cols, keep)
         arr[i].ncols = len(cols)
         arr[i].source = int(step[2]) if len(step) > 2 else 0
     out = C.POINTER(cph_chain)()
@@ -800,21 +903,19 @@ def join_chain(ctx: Context, steps, probe_base: int = 0, out_mem: int = CPH_MEM_
     return Chain(ctx, out, [s[0] for s in steps], probe_base)
 
 
-class Chain:
+class Chain(Owned):
     """Result of a chained join (cph_chain): row-id tuples in emission order."""
+    _release_fn = "cph_chain_release"
 
     def __init__(self, ctx: Context, ptr, owners, probe_base: int = 0):
+        super().__init__(ctx, ptr)
         self.probe_base = probe_base
-        self.ctx = ctx
-        self.lib = ctx.lib
-        self.ptr = ptr
         self.owners = owners
         c = ptr.contents
         self.nrows = int(c.nrows)
         self.nsteps = int(c.nsteps)
         self.mem = int(c.mem)
         self.positions = bool(c.positions)
-        ctx._children.add(self)
 
     @property
     def identity(self) -> bool:
@@ -836,25 +937,13 @@ class Chain:
         c = self.ptr.contents
         return {"stream_row": int(c.stream_row or 0), "build_row": [int(c.build_row[k] or 0) for k in range(self.nsteps)]}
 
-    def release(self):
-        if self.ptr:
-            self.lib.cph_chain_release(self.ptr)
-            self.ptr = None
 
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-
-class Gathered:
+class Gathered(Owned):
     """Result of an exchange (cph_gathered): device arrays of this rank's ctx + host counts / displacements."""
+    _release_fn = "cph_gathered_release"
 
     def __init__(self, ctx: Context, ptr, identity=None, stream_base: int = 0):
-        self.ctx, self.lib, self.ptr = ctx, ctx.lib, ptr
+        super().__init__(ctx, ptr)
         g = ptr.contents
         self.total = int(g.total)
         self.narrays = int(g.narrays)
@@ -865,20 +954,6 @@ class Gathered:
         self.stats = None
         self.identity = identity
         self.stream_base = stream_base
-        ctx._children.add(self)
-
-    def release(self):
-        if self.ptr:
-            self.lib.cph_gathered_release(self.ptr)
-            self.ptr = None
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
 
 class Dist:
@@ -938,10 +1013,9 @@ class Dist:
         arr = (cph_chain_step * len(steps))()
         keep = []
         for i, (index, cols) in enumerate(steps):
-            carr, k = _cols_array(cols)
-            keep.append((carr, k, index))
+            keep.append(index)
             arr[i].index = index.handle
-            arr[i].cols = carr
+            arr[i].cols = cols_array(cols, keep)
             arr[i].ncols = len(cols)
         sr = (C.c_uint64 * self.size)(*shard_rows) if shard_rows is not None else None
         flags = (CPH_CHAIN_POSITIONS if positions else 0) | (CPH_DIST_HOST_GATHER if host else 0) | (CPH_DIST_PACKED if packed else 0)
@@ -976,15 +1050,13 @@ class Dist:
             pass
 
 
-class Matches:
+class Matches(Owned):
     """Result of one probe (cph_matches).  Host results are exposed as numpy copies."""
+    _release_fn = "cph_matches_release"
 
     def __init__(self, lib, ptr, owner=None):
-        self.lib = lib
-        self.ptr = ptr
+        super().__init__(owner.ctx if owner is not None else None, ptr, lib)
         self.owner = owner  # keeps the index (and its ctx) alive: the arrays come from the ctx's pool
-        if owner is not None:
-            owner.ctx._children.add(self)
         m = ptr.contents
         self.nprobe = int(m.nprobe)
         self.nmatches = int(m.nmatches)
@@ -1013,16 +1085,3 @@ class Matches:
     def device_ptrs(self) -> dict:
         m = self.ptr.contents
         return {k: int(getattr(m, k) or 0) for k in ("lo", "cnt", "probe_idx", "build_row")}
-
-    def release(self):
-        if self.ptr:
-            self.lib.cph_matches_release(self.ptr)
-            self.ptr = None
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass

@@ -82,53 +82,32 @@ class TotalsError(ValueError):
         self.position, self.row, self.kind, self.nerrors, self.spec = position, row, kind, nerrors, spec
 
 
-class Totals:
+class Totals(N.Owned):
     """What `totals` returns.  out_mem = HOST: first_position (uint64), first_row (uint32), count (uint64) and values[i] (int64 /
     float64) are numpy arrays; DEVICE: (device pointer, count) pairs, valid until release()."""
+    _release_fn = "cph_aggregated_release"
 
-    def __init__(self, ngroups, first_position, first_row, count, values, host_rows, _release=None):
-        self.ngroups, self.first_position, self.first_row, self.count = ngroups, first_position, first_row, count
-        self.values, self.host_rows = values, host_rows
-        self._release = _release
-
-    def release(self):
-        """Gives the device blocks back (out_mem = DEVICE only)."""
-        if self._release:
-            self._release()
-            self._release = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+    def __init__(self, ctx, ptr, specs, out_mem):
+        super().__init__(ctx, ptr)
+        r = ptr.contents
+        self.ngroups, self.host_rows = int(r.ngroups), int(r.host_rows)
+        self.first_position = N.result_array(r.first_position, self.ngroups, np.uint64, out_mem)
+        self.first_row = N.result_array(r.first_row, self.ngroups, np.uint32, out_mem)
+        self.count = N.result_array(r.count, self.ngroups, np.uint64, out_mem)
+        self.values = _spec_values(r, self.ngroups, specs, out_mem)
+        if out_mem == N.CPH_MEM_HOST:
+            self.release()   # the arrays are copies
 
 
-def _fill_spec(cs, spec, keep):
-    if not isinstance(spec, Spec):
-        raise TypeError(f"not an aggregate: {spec!r} (closures cannot run on the device; use Sum, Min, Max)")
-    cs.op, cs.kind = spec.op, spec.kind
-    src = spec.source
-    if isinstance(src, StrCol):
-        sc, k = src.as_c()
-        keep.append((sc, k))
-        cs.col = C.pointer(sc)
-    elif isinstance(src, tuple):   # (device pointer, count)
-        cs.numbers, cs.numbers_mem = int(src[0]) or None, N.CPH_MEM_DEVICE
-    elif hasattr(src, "data_ptr"):   # a device tensor
-        want = "int64" if spec.kind == N.CPH_NUM_INT64 else "float64"
-        if not str(getattr(src, "dtype", want)).endswith(want):
-            raise ValueError(f"{type(spec).__name__}: the tensor's dtype is {src.dtype}, the kind wants {want}")
-        if not getattr(src, "is_cuda", True):
-            raise ValueError(f"{type(spec).__name__}: a tensor source must live on the device (pass .numpy() for host values)")
-        keep.append(src)
-        cs.numbers, cs.numbers_mem = int(src.data_ptr()) or None, N.CPH_MEM_DEVICE
-    else:
-        arr = np.ascontiguousarray(np.asarray(src, dtype=np.int64 if spec.kind == N.CPH_NUM_INT64 else np.float64).reshape(-1))
-        if len(arr) == 0:
-            arr = np.zeros(1, arr.dtype)   # a pointer for an empty table
-        keep.append(arr)
-        cs.numbers, cs.numbers_mem = arr.ctypes.data, N.CPH_MEM_HOST
+def _spec_values(r, ngroups, specs, out_mem):
+    return [N.result_array(r.values[i], ngroups, np.int64 if sp.kind == N.CPH_NUM_INT64 else np.float64, out_mem)
+            for i, sp in enumerate(specs)]
+
+
+def _numbers(spec, need, rows, keep):
+    """(pointer, CPH_MEM_*) of a spec's numbers, one per row of the build table / per joined row (`rows` words the
+    message); an empty host array is passed as one zero: the library wants a pointer."""
+    return N.number_source(spec.source, spec.kind, need, f"{type(spec).__name__}: {{count}} values for {{need}} {rows}", keep, stand_in=True)
 
 
 def totals(index: N.DeviceIndex, specs=(), out_mem: int = N.CPH_MEM_HOST, columns=None) -> Totals:
@@ -144,16 +123,20 @@ def totals(index: N.DeviceIndex, specs=(), out_mem: int = N.CPH_MEM_HOST, column
     keep, evaluated = [], []
     try:
         for i, sp in enumerate(specs):
-            if isinstance(sp, Spec) and isinstance(sp.source, E.Expr):
+            if not isinstance(sp, Spec):
+                raise TypeError(f"not an aggregate: {sp!r} (closures cannot run on the device; use Sum, Min, Max)")
+            arr[i].op, arr[i].kind = sp.op, sp.kind
+            if isinstance(sp.source, E.Expr):
                 from .materialize import eval_number, raise_expr_error
                 nc = eval_number(ctx, columns or {}, sp.source, out_mem=N.CPH_MEM_DEVICE)   # the identity selection
                 evaluated.append(nc)
                 if nc.nerrors:
                     raise_expr_error(ctx, columns or {}, sp.source, nc)
-                arr[i].op, arr[i].kind = sp.op, sp.kind
                 arr[i].numbers, arr[i].numbers_mem = nc.values[0] or None, N.CPH_MEM_DEVICE
+            elif isinstance(sp.source, StrCol):
+                arr[i].col = N.cols_array([sp.source], keep)
             else:
-                _fill_spec(arr[i], sp, keep)
+                arr[i].numbers, arr[i].numbers_mem = _numbers(sp, 0, "rows", keep)
         out = C.POINTER(N.cph_aggregated)()
         rc = ctx.lib.cph_index_aggregate(ctx.handle, index.handle, arr if specs else None, len(specs), out_mem, C.byref(out))
     finally:
@@ -166,17 +149,7 @@ def totals(index: N.DeviceIndex, specs=(), out_mem: int = N.CPH_MEM_HOST, column
         err = TotalsError(int(r.first_error_position), int(r.first_error_row), int(r.first_error_kind), int(r.nerrors), int(r.first_error_spec))
         ctx.lib.cph_aggregated_release(out)
         raise err
-    ng = int(r.ngroups)
-    dts = [np.int64 if sp.kind == N.CPH_NUM_INT64 else np.float64 for sp in specs]
-    if out_mem == N.CPH_MEM_HOST:
-        res = Totals(ng, N._ptr_array(r.first_position, ng, np.uint64).copy(), N._ptr_array(r.first_row, ng, np.uint32).copy(),
-                     N._ptr_array(r.count, ng, np.uint64).copy(), [N._ptr_array(r.values[i], ng, dt).copy() for i, dt in enumerate(dts)],
-                     int(r.host_rows))
-        ctx.lib.cph_aggregated_release(out)
-        return res
-    return Totals(ng, (int(r.first_position or 0), ng), (int(r.first_row or 0), ng), (int(r.count or 0), ng),
-                  [(int(r.values[i] or 0), ng) for i in range(len(specs))], int(r.host_rows),
-                  _release=lambda: ctx.lib.cph_aggregated_release(out))
+    return Totals(ctx, out, specs, out_mem)
 
 
 # ---- the contract in pure Python ----------------------------------------------------------------------------------------
@@ -239,27 +212,21 @@ def totals_model(keys_in_sorted_order, values_by_sorted_position=(), specs=()):
 
 
 # ---- Totals over a Join: Count and Sum / Min / Max per BUILD ROW of a chain step (cph_chain_aggregate) --------------------
-class JoinTotals:
+class JoinTotals(N.Owned):
     """What `join_totals` returns: one group per build row of the step's index (ngroups == index.nrows), empty groups
     included.  `positions`: group g is a sorted position of the index (True) or an original row id of its table (False), as
     in the chain.  out_mem = HOST: count (uint64) and values[i] (int64 / float64) are numpy arrays; DEVICE: (device pointer,
     count) pairs, valid until release()."""
+    _release_fn = "cph_chain_aggregated_release"
 
-    def __init__(self, ngroups, count, values, positions, _release=None):
-        self.ngroups, self.count, self.values, self.positions = ngroups, count, values, positions
-        self._release = _release
-
-    def release(self):
-        """Gives the device blocks back (out_mem = DEVICE only)."""
-        if self._release:
-            self._release()
-            self._release = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+    def __init__(self, ctx, ptr, specs, out_mem):
+        super().__init__(ctx, ptr)
+        r = ptr.contents
+        self.ngroups, self.positions = int(r.ngroups), bool(r.positions)
+        self.count = N.result_array(r.count, self.ngroups, np.uint64, out_mem)
+        self.values = _spec_values(r, self.ngroups, specs, out_mem)
+        if out_mem == N.CPH_MEM_HOST:
+            self.release()   # the arrays are copies
 
 
 def _chain_row_ids(chain, which):
@@ -334,11 +301,7 @@ def join_totals(chain: N.Chain, step: int, index: N.DeviceIndex, specs=(), out_m
                     arr[i].numbers, arr[i].status, arr[i].numbers_mem = v.ctypes.data, st.ctypes.data, N.CPH_MEM_HOST
                 keep.append(src)
                 continue
-            cs = N.cph_agg_spec()
-            _fill_spec(cs, sp, keep)
-            if cs.numbers_mem == N.CPH_MEM_HOST and len(keep[-1]) < n:
-                raise ValueError(f"{type(sp).__name__}: {len(keep[-1])} values for {n} joined rows")
-            arr[i].numbers, arr[i].numbers_mem = cs.numbers, cs.numbers_mem
+            arr[i].numbers, arr[i].numbers_mem = _numbers(sp, n, "joined rows", keep)
         out = C.POINTER(N.cph_chain_aggregated)()
         rc = ctx.lib.cph_chain_aggregate(ctx.handle, chain.ptr, int(step), index.handle if index is not None else None,
                                          arr if specs else None, len(specs), out_mem, C.byref(out))
@@ -353,15 +316,7 @@ def join_totals(chain: N.Chain, step: int, index: N.DeviceIndex, specs=(), out_m
         err = TotalsError(row, row, int(r.first_error_kind), int(r.nerrors), int(r.first_error_spec))
         ctx.lib.cph_chain_aggregated_release(out)
         raise err
-    ng = int(r.ngroups)
-    dts = [np.int64 if sp.kind == N.CPH_NUM_INT64 else np.float64 for sp in specs]
-    if out_mem == N.CPH_MEM_HOST:
-        res = JoinTotals(ng, N._ptr_array(r.count, ng, np.uint64).copy(), [N._ptr_array(r.values[i], ng, dt).copy() for i, dt in enumerate(dts)],
-                         bool(r.positions))
-        ctx.lib.cph_chain_aggregated_release(out)
-        return res
-    return JoinTotals(ng, (int(r.count or 0), ng), [(int(r.values[i] or 0), ng) for i in range(len(specs))], bool(r.positions),
-                      _release=lambda: ctx.lib.cph_chain_aggregated_release(out))
+    return JoinTotals(ctx, out, specs, out_mem)
 
 
 def join_totals_model(build_rows, ngroups, values=(), specs=()):

@@ -101,26 +101,19 @@ class ResolveError(ValueError):
         self.position, self.row, self.kind, self.nerrors = position, row, kind, nerrors
 
 
-class Resolved:
+class Resolved(N.Owned):
     """What resolve_duplicates_device returns: the compacted `index`, the surviving sorted `positions` of the input index
-    (a numpy uint64 array, or (device pointer, count) for out_mem = DEVICE), and the call's statistics."""
+    (a numpy uint64 array, or (device pointer, count) for out_mem = DEVICE, valid until release(); the index lives on),
+    and the call's statistics."""
+    _release_fn = "cph_resolved_release"
 
-    def __init__(self, index, positions, ngroups, group_rows, host_rows, _release=None):
-        self.index, self.positions = index, positions
-        self.ngroups, self.group_rows, self.host_rows = ngroups, group_rows, host_rows
-        self._release = _release
-
-    def release(self):
-        """Gives the device block of `positions` back (out_mem = DEVICE only; the index lives on)."""
-        if self._release:
-            self._release()
-            self._release = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+    def __init__(self, ctx, ptr, index, out_mem):
+        super().__init__(ctx, ptr)
+        r = ptr.contents
+        self.index, self.positions = index, N.result_array(r.positions, int(r.nrows), np.uint64, out_mem)
+        self.ngroups, self.group_rows, self.host_rows = int(r.ngroups), int(r.group_rows), int(r.host_rows)
+        if out_mem == N.CPH_MEM_HOST:
+            self.release()   # the array is a copy
 
 
 def rule_pick(rule: Rule, values_by_sorted_position=None):
@@ -166,13 +159,12 @@ def resolve_duplicates_device(index: N.DeviceIndex, rule: Rule, order=None, kind
     if not isinstance(rule, Rule):
         raise TypeError(f"not a resolve rule: {rule!r}")
     opts = N.cph_resolve_opts(rule.code, 0, 1 if keep_last_row else 0, 0)
-    col, keep = None, None
+    col, keep = None, []
     if rule.ordered:
         if order is None or kind not in _KINDS:
             raise ValueError('MinBy / MaxBy need an order column and kind = "int", "float" or "bytes"')
         opts.order_kind = _KINDS[kind]
-        sc, keep = order.as_c()
-        col = C.pointer(sc)
+        col = N.cols_array([order], keep)
     ctx = index.ctx
     h = N._P()
     out = C.POINTER(N.cph_resolved)()
@@ -184,10 +176,4 @@ def resolve_duplicates_device(index: N.DeviceIndex, rule: Rule, order=None, kind
         err = ResolveError(int(r.first_error_position), int(r.first_error_row), int(r.first_error_kind), int(r.nerrors))
         ctx.lib.cph_resolved_release(out)
         raise err
-    nx = N.DeviceIndex._from_handle(ctx, h)
-    stats = (int(r.ngroups), int(r.group_rows), int(r.host_rows))
-    if out_mem == N.CPH_MEM_HOST:
-        pos = N._ptr_array(r.positions, int(r.nrows), np.uint64).copy()
-        ctx.lib.cph_resolved_release(out)
-        return Resolved(nx, pos, *stats)
-    return Resolved(nx, (int(r.positions or 0), int(r.nrows)), *stats, _release=lambda: ctx.lib.cph_resolved_release(out))
+    return Resolved(ctx, out, N.DeviceIndex._from_handle(ctx, h), out_mem)

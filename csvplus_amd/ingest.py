@@ -15,20 +15,22 @@ ERR_NAMES = {0: None, N.CPH_CSV_ERR_BARE_QUOTE: "bare \" in non-quoted field",
              N.CPH_CSV_ERR_FIELD_COUNT: "wrong number of fields"}
 
 
-class CsvError(Exception):
-    """Mirrors csv.ParseError as csvplus reports it: kind + the record it happened in."""
+class CsvParseError(Exception):
+    """A parse error of the device reader (cph_csv_parse), as csvplus reports a csv.ParseError: `kind` = CPH_CSV_ERR_* + the
+    `record` it happened in.  The header reader's error, for the first record, is CsvError."""
 
     def __init__(self, kind: int, record: int):
         super().__init__(f"record {record}: {ERR_NAMES.get(kind, kind)}")
         self.kind, self.record = kind, record
 
 
-class CsvTable:
+class CsvTable(N.Owned):
     """Library-owned result of cph_csv_parse.  `columns` are StrCols (host copies or zero-copy device views
     valid until release())."""
+    _release_fn = "cph_csv_table_release"
 
     def __init__(self, ctx, ptr, out_mem):
-        self.ctx, self.ptr = ctx, ptr
+        super().__init__(ctx, ptr)
         t = ptr.contents
         self.nrecords, self.error_kind, self.error_record = int(t.nrecords), int(t.error_kind), int(t.error_record)
         self.columns = []
@@ -40,31 +42,9 @@ class CsvTable:
                 data = N._ptr_array(sc.data, int(offs[-1]), np.uint8).copy() if int(offs[-1]) else np.empty(0, np.uint8)
                 self.columns.append(StrCol(data, offs, self.nrecords, bits))
             else:
-                self.columns.append(StrCol(_Raw(sc.data), _Raw(sc.offsets), self.nrecords, bits, N.CPH_MEM_DEVICE, fixed_width=0))
-        ctx._children.add(self)
+                self.columns.append(StrCol(N._Raw(sc.data), N._Raw(sc.offsets), self.nrecords, bits, N.CPH_MEM_DEVICE, fixed_width=0))
         if out_mem == N.CPH_MEM_HOST:
             self.release()
-
-    def release(self):
-        if self.ptr:
-            self.ctx.lib.cph_csv_table_release(self.ptr)
-            self.ptr = None
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-
-class _Raw:   # minimal object with data_ptr()
-    def __init__(self, p):
-        self._p = int(p or 0)
-
-    def data_ptr(self):
-        return self._p
 
 
 def csv_parse(ctx: N.Context, data, col_index, *, comma=b",", comment=None, trim_leading_space=False,

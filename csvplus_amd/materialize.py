@@ -17,7 +17,7 @@ from .columns import StrCol
 def gather_rows(ctx: N.Context, col: StrCol, row_ids=None, id_base: int = 0, out_mem: int = N.CPH_MEM_HOST):
     """out[i] = col[row_ids[i] - id_base].  Host columns take numpy uint32/uint64 ids; device columns take
     (device_ptr, bits, count).  Returns a host StrCol (out_mem HOST) or a ColBuf handle (DEVICE)."""
-    sc, keep = col.as_c()
+    sc, keep = N._cols_array([col])
     ptr, bits, n = C.c_void_p(0), 32, 0
     if row_ids is not None:
         if isinstance(row_ids, np.ndarray):
@@ -28,38 +28,31 @@ def gather_rows(ctx: N.Context, col: StrCol, row_ids=None, id_base: int = 0, out
         else:
             ptr, bits, n = C.c_void_p(row_ids[0]), int(row_ids[1]), int(row_ids[2])
     out = C.POINTER(N.cph_colbuf)()
-    ctx._check(ctx.lib.cph_gather_rows(ctx.handle, C.byref(sc), ptr, bits, id_base, n, out_mem, C.byref(out)))
+    ctx._check(ctx.lib.cph_gather_rows(ctx.handle, sc, ptr, bits, id_base, n, out_mem, C.byref(out)))
     del keep
     cb = ColBuf(ctx, out)
-    if out_mem == N.CPH_MEM_HOST:
-        res = cb.to_strcol()
-        cb.release()
-        return res
-    return cb
+    return cb.taken(ColBuf.to_strcol) if out_mem == N.CPH_MEM_HOST else cb
 
 
 def permute_col(ctx: N.Context, index, col: StrCol, out_mem: int = N.CPH_MEM_DEVICE):
     """cph_index_permute: `col` (a column of the table `index` was built over) in index order — out[p] = col[perm[p]] — so
     that the sorted positions a Join reports are row subscripts (csvplus.go:736: the reference keeps its index rows
     sorted).  Returns a ColBuf (DEVICE) or a host StrCol."""
-    sc, keep = col.as_c()
+    sc, keep = N._cols_array([col])
     out = C.POINTER(N.cph_colbuf)()
-    ctx._check(ctx.lib.cph_index_permute(ctx.handle, index.handle, C.byref(sc), out_mem, C.byref(out)))
+    ctx._check(ctx.lib.cph_index_permute(ctx.handle, index.handle, sc, out_mem, C.byref(out)))
     del keep
     cb = ColBuf(ctx, out)
-    if out_mem == N.CPH_MEM_HOST:
-        res = cb.to_strcol()
-        cb.release()
-        return res
-    return cb
+    return cb.taken(ColBuf.to_strcol) if out_mem == N.CPH_MEM_HOST else cb
 
 
-class ColBuf:
+class ColBuf(N.Owned):
+    _release_fn = "cph_colbuf_release"
+
     def __init__(self, ctx, ptr):
-        self.ctx, self.ptr = ctx, ptr
+        super().__init__(ctx, ptr)
         c = ptr.contents
         self.nrows, self.nbytes, self.mem = int(c.col.nrows), int(c.nbytes), int(c.col.mem)
-        ctx._children.add(self)
 
     def to_strcol(self) -> StrCol:
         assert self.mem == N.CPH_MEM_HOST
@@ -72,62 +65,24 @@ class ColBuf:
         """Zero-copy device StrCol view (valid until release)."""
         assert self.mem == N.CPH_MEM_DEVICE
         c = self.ptr.contents.col
-
-        class _Raw:   # minimal object with data_ptr()
-            def __init__(self, p):
-                self._p = int(p or 0)
-
-            def data_ptr(self):
-                return self._p
-
-        return StrCol(_Raw(c.data), _Raw(c.offsets), self.nrows, 64, N.CPH_MEM_DEVICE, fixed_width=0)
-
-    def release(self):
-        if self.ptr:
-            self.ctx.lib.cph_colbuf_release(self.ptr)
-            self.ptr = None
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+        return StrCol(N._Raw(c.data), N._Raw(c.offsets), self.nrows, 64, N.CPH_MEM_DEVICE, fixed_width=0)
 
 
-class DeviceBytes:
+class DeviceBytes(N.Owned):
     """cph_bytes kept in HBM (valid until release())."""
+    _release_fn = "cph_bytes_release"
 
     def __init__(self, ctx, ptr):
-        self.ctx, self.ptr = ctx, ptr
+        super().__init__(ctx, ptr)
         self.size, self.data_ptr = int(ptr.contents.size), int(ptr.contents.data or 0)
-        ctx._children.add(self)
 
     def __len__(self):
         return self.size
 
-    def release(self):
-        if self.ptr:
-            self.ctx.lib.cph_bytes_release(self.ptr)
-            self.ptr = None
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
 
 def _rowsel(cols, row_ids, nrows, keep):
     """cph_strcol array, cph_rowsel array (None without row_ids) and the row count of a writer call (csv_write / json_write)."""
-    arr = (N.cph_strcol * len(cols))()
-    for i, c in enumerate(cols):
-        sc, k = c.as_c()
-        arr[i] = sc
-        keep.append(k)
+    arr = N.cols_array(cols, keep)
     sel = None
     n = cols[0].nrows if nrows is None else int(nrows)
     if row_ids is not None:
@@ -135,19 +90,7 @@ def _rowsel(cols, row_ids, nrows, keep):
         for i, ids in enumerate(row_ids):
             if ids is None:
                 continue
-            if isinstance(ids, tuple) and isinstance(ids[0], np.ndarray):   # (host ids, base)
-                sel[i].base = int(ids[1])
-                ids = ids[0]
-            if isinstance(ids, np.ndarray):
-                if ids.dtype != np.uint64:
-                    ids = ids.astype(np.uint32)
-                ids = np.ascontiguousarray(ids)
-                keep.append(ids)
-                sel[i].ids, sel[i].bits = ids.ctypes.data if len(ids) else None, ids.dtype.itemsize * 8
-                cnt = len(ids)
-            else:
-                sel[i].ids, sel[i].bits, cnt = int(ids[0]) or None, int(ids[1]), int(ids[2])
-                sel[i].base = int(ids[3]) if len(ids) > 3 else 0
+            cnt = N.fill_rowsel(sel[i], ids, keep)
             if nrows is None:
                 n = cnt
     return arr, sel, n
@@ -164,11 +107,10 @@ def _strvals(names, size, keep):
 
 
 def _take_bytes(ctx, out, out_mem):
+    db = DeviceBytes(ctx, out)
     if out_mem == N.CPH_MEM_DEVICE:
-        return DeviceBytes(ctx, out)
-    res = N._ptr_array(out.contents.data, int(out.contents.size), np.uint8).tobytes()
-    ctx.lib.cph_bytes_release(out)
-    return res
+        return db
+    return db.taken(lambda b: N._ptr_array(b.data_ptr, b.size, np.uint8).tobytes())
 
 
 def csv_write(ctx: N.Context, cols, header=None, out_mem: int = N.CPH_MEM_HOST, row_ids=None, nrows=None):
@@ -205,17 +147,17 @@ def json_write(ctx: N.Context, cols, names, out_mem: int = N.CPH_MEM_HOST, row_i
 _MODES = {"where": N.CPH_FILTER_WHERE, "take_while": N.CPH_FILTER_TAKE_WHILE, "drop_while": N.CPH_FILTER_DROP_WHILE}
 
 
-class RowList:
+class RowList(N.Owned):
     """cph_rowlist: an ascending list of row numbers (valid until release()).  A range (the WHILE modes, or an empty
     result) has no array behind it: `ids_ptr` is 0 and the rows are first, first + 1, ..."""
+    _release_fn = "cph_rowlist_release"
 
     def __init__(self, ctx, ptr):
-        self.ctx, self.ptr = ctx, ptr
+        super().__init__(ctx, ptr)
         c = ptr.contents
         self.nrows, self.first, self.bits, self.mem = int(c.nrows), int(c.first), int(c.bits), int(c.mem)
         self.ids_ptr = int(c.ids or 0)
         self.is_range = self.ids_ptr == 0
-        ctx._children.add(self)
 
     def __len__(self):
         return self.nrows
@@ -233,19 +175,6 @@ class RowList:
         assert self.mem == N.CPH_MEM_DEVICE and not self.is_range, "a range has no array: use first / nrows"
         return (self.ids_ptr, self.bits, self.nrows)
 
-    def release(self):
-        if self.ptr:
-            self.ctx.lib.cph_rowlist_release(self.ptr)
-            self.ptr = None
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
 
 def _expr_program(ops, keep):
     """The cph_expr_op array of expr.compile's ops."""
@@ -262,20 +191,23 @@ def _expr_program(ops, keep):
     return prog
 
 
-def _pred_expr(eops, arrs, need, keep):
-    """One cph_pred_expr for an expression term: host arrays are passed as they are, device arrays by pointer; every array
-    has an entry for each of the `need` positions of the selection the call can look at."""
+def _expr_nums(arrs, need, who, keep):
+    """The cph_expr_nums array of an expression's IntArr / FloatArr leaves (expr.arrays): host arrays are passed as they
+    are, device arrays by pointer; every array has at least `need` values."""
     nums = (N.cph_expr_nums * max(len(arrs), 1))()
     for k, a in enumerate(arrs):
-        if a.count < need:
-            raise ValueError(f"filter_rows: {a!r} has {a.count} values for positions 0..{need - 1} of the selection")
-        if a.device:
-            nums[k].ptr, nums[k].mem = a.values or None, N.CPH_MEM_DEVICE
-        else:
-            keep.append(a.values)
-            nums[k].ptr, nums[k].mem = (a.values.ctypes.data if a.count else None), N.CPH_MEM_HOST
-    pe = N.cph_pred_expr(_expr_program(eops, keep), len(eops), len(arrs), nums if arrs else None)
-    keep += [nums, pe]
+        kind = N.CPH_NUM_INT64 if a.dtype is np.int64 else N.CPH_NUM_FLOAT64
+        nums[k].ptr, nums[k].mem = N.number_source(a, kind, need, who, keep)
+    keep.append(nums)
+    return nums if arrs else None
+
+
+def _pred_expr(eops, arrs, need, keep):
+    """One cph_pred_expr for an expression term; its arrays have an entry for each of the `need` positions of the
+    selection the call can look at."""
+    nums = _expr_nums(arrs, need, "filter_rows: {src!r} has {count} values for positions 0..{last} of the selection", keep)
+    pe = N.cph_pred_expr(_expr_program(eops, keep), len(eops), len(arrs), nums)
+    keep.append(pe)
     return pe
 
 
@@ -339,11 +271,7 @@ def filter_rows(ctx: N.Context, cols_by_name, pred, row_ids=None, nrows=None, mo
 
 def _take_rowlist(ctx, out, out_mem, as_handle):
     rl = RowList(ctx, out)
-    if out_mem == N.CPH_MEM_DEVICE or as_handle:
-        return rl
-    res = rl.to_numpy()
-    rl.release()
-    return res
+    return rl if out_mem == N.CPH_MEM_DEVICE or as_handle else rl.taken(RowList.to_numpy)
 
 
 def take_rows(ctx: N.Context, row_ids, rows, out_mem: int = N.CPH_MEM_HOST, as_handle: bool = False):
@@ -354,19 +282,8 @@ def take_rows(ctx: N.Context, row_ids, rows, out_mem: int = N.CPH_MEM_HOST, as_h
     sel, sel_mem = None, N.CPH_MEM_HOST
     if row_ids is not None:
         sel = N.cph_rowsel()
-        if isinstance(row_ids, tuple) and isinstance(row_ids[0], np.ndarray):
-            sel.base = int(row_ids[1])
-            row_ids = row_ids[0]
-        if isinstance(row_ids, np.ndarray):
-            if row_ids.dtype != np.uint64:
-                row_ids = row_ids.astype(np.uint32)
-            row_ids = np.ascontiguousarray(row_ids)
-            keep.append(row_ids)
-            sel.ids, sel.bits = row_ids.ctypes.data if len(row_ids) else None, row_ids.dtype.itemsize * 8
-        else:
-            sel.ids, sel.bits = int(row_ids[0]) or None, int(row_ids[1])
-            sel.base = int(row_ids[3]) if len(row_ids) > 3 else 0
-            sel_mem = N.CPH_MEM_DEVICE
+        N.fill_rowsel(sel, row_ids, keep)
+        sel_mem = N.CPH_MEM_HOST if keep else N.CPH_MEM_DEVICE   # only a host form keeps an array
     if isinstance(rows, RowList):
         lst = rows.ptr
     elif isinstance(rows, Ordered):   # an ordered list is a list of row numbers like any other
@@ -390,42 +307,27 @@ def take_rows(ctx: N.Context, row_ids, rows, out_mem: int = N.CPH_MEM_HOST, as_h
 
 # ---- ValueAsInt / ValueAsFloat64 for a whole column (cph_col_to_number) -------------------------------------------------
 
-class NumCol:
+class NumCol(N.Owned):
     """cph_numcol: a column as int64 / float64 (valid until release()).  `values` and `status` are numpy arrays (copies)
     for a host result and (device_ptr, count) pairs for a device result; status holds CPH_NUM_* per row, and at an error
     row `values` holds what Go returns beside the error.  first_error_row is None when nerrors == 0."""
+    _release_fn = "cph_numcol_release"
 
     def __init__(self, ctx, ptr):
-        self.ctx, self.ptr = ctx, ptr
+        super().__init__(ctx, ptr)
         c = ptr.contents
         self.nrows, self.kind, self.mem = int(c.nrows), int(c.kind), int(c.mem)
         self.nerrors, self.host_rows = int(c.nerrors), int(c.host_rows)
         self.first_error_row = None if int(c.first_error_row) == N.CPH_NO_ROW else int(c.first_error_row)
         self.first_error_kind = int(c.first_error_kind)
         dt = np.float64 if self.kind == N.CPH_NUM_FLOAT64 else np.int64   # INT64 and the two TIME kinds
+        self.values = N.result_array(c.values, self.nrows, dt, self.mem)
+        self.status = N.result_array(c.status, self.nrows, np.uint8, self.mem)
         if self.mem == N.CPH_MEM_HOST:
-            self.values = N._ptr_array(c.values, self.nrows, dt).copy() if self.nrows else np.zeros(0, dt)
-            self.status = N._ptr_array(c.status, self.nrows, np.uint8).copy() if self.nrows else np.zeros(0, np.uint8)
-        else:
-            self.values = (int(c.values or 0), self.nrows)
-            self.status = (int(c.status or 0), self.nrows)
-        ctx._children.add(self)
+            self.release()   # the arrays are copies
 
     def __len__(self):
         return self.nrows
-
-    def release(self):
-        if self.ptr:
-            self.ctx.lib.cph_numcol_release(self.ptr)
-            self.ptr = None
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
 
 def _to_number(ctx, col, row_ids, nrows, kind, out_mem):
@@ -434,10 +336,7 @@ def _to_number(ctx, col, row_ids, nrows, kind, out_mem):
     out = C.POINTER(N.cph_numcol)()
     ctx._check(ctx.lib.cph_col_to_number(ctx.handle, arr, sel, n, kind, out_mem, C.byref(out)))
     del keep
-    res = NumCol(ctx, out)
-    if out_mem == N.CPH_MEM_HOST:
-        res.release()   # the arrays are copies
-    return res
+    return NumCol(ctx, out)
 
 
 def to_int(ctx: N.Context, col: StrCol, row_ids=None, nrows=None, out_mem: int = N.CPH_MEM_HOST):
@@ -498,25 +397,15 @@ def eval_number(ctx: N.Context, cols_by_name, expr, row_ids=None, nrows=None, ou
             n = min(a.count for a in arrs)
         else:
             raise ValueError("eval_number: an expression without columns and arrays needs nrows")
-    nums = (N.cph_expr_nums * max(len(arrs), 1))()
-    for k, a in enumerate(arrs):
-        if a.count < n:
-            raise ValueError(f"eval_number: {a!r} has {a.count} values for {n} rows")
-        if a.device:
-            nums[k].ptr, nums[k].mem = a.values or None, N.CPH_MEM_DEVICE
-        else:
-            keep.append(a.values)
-            nums[k].ptr, nums[k].mem = (a.values.ctypes.data if a.count else None), N.CPH_MEM_HOST
+    nums = _expr_nums(arrs, n, "eval_number: {src!r} has {count} values for {need} rows", keep)
     prog = _expr_program(ops, keep)
     out = C.POINTER(N.cph_numcol)()
     eop = C.c_int32(-1)
-    ctx._check(ctx.lib.cph_num_eval(ctx.handle, arr, sel, len(cols), n, nums if arrs else None, len(arrs), prog, len(ops), out_mem,
+    ctx._check(ctx.lib.cph_num_eval(ctx.handle, arr, sel, len(cols), n, nums, len(arrs), prog, len(ops), out_mem,
                                     C.byref(out), C.byref(eop)))
     del keep
     res = NumCol(ctx, out)
     res.first_error_op = None if eop.value < 0 else int(eop.value)
-    if out_mem == N.CPH_MEM_HOST:
-        res.release()   # the arrays are copies
     return res
 
 
@@ -643,26 +532,20 @@ def _fill_pieces(ctx, cols_by_name, row_ids, pieces, n, keep, computed, pending=
             parr[k].value.data = C.addressof(ops)
             parr[k].value.len = C.sizeof(ops)
         else:
+            src = value
             if value.expr is not None:   # evaluated over the same rows into a device array: cph_num_eval
                 nc = eval_number(ctx, cols_by_name, value.expr, row_ids=row_ids, nrows=n, out_mem=N.CPH_MEM_DEVICE)
                 computed.append(nc)
-                mem, ptr = N.CPH_MEM_DEVICE, nc.values[0] or None
                 if nc.nerrors and pending is None:
                     raise_expr_error(ctx, cols_by_name, value.expr, nc, row_ids)
                 elif nc.nerrors:   # the status bytes on the host; the values travel from there too
                     nc.release()
                     nc = eval_number(ctx, cols_by_name, value.expr, row_ids=row_ids, nrows=n, out_mem=N.CPH_MEM_HOST)
                     pending.append((tag, value.expr, nc))
-                    keep.append(nc.values)
-                    mem, ptr = N.CPH_MEM_HOST, nc.values.ctypes.data if n else None
-            elif value.count < n:
-                raise ValueError(f"map_column: {'an Int' if kind == M.INT64 else 'a Time' if kind == M.TIME else 'a Float'} part has {value.count} values for {n} rows")
-            elif value.device:
-                mem, ptr = N.CPH_MEM_DEVICE, value.values or None
-            else:
-                keep.append(value.values)
-                mem, ptr = N.CPH_MEM_HOST, value.values.ctypes.data if value.count else None
-            parr[k].arg = mem
+                src = nc.values
+            part = "an Int" if kind == M.INT64 else "a Time" if kind == M.TIME else "a Float"
+            ptr, parr[k].arg = N.number_source(src, N.CPH_NUM_INT64 if kind in (M.INT64, M.TIME) else N.CPH_NUM_FLOAT64, n,
+                                               f"map_column: {part} part has {{count}} values for {{need}} rows", keep)
             if kind == M.INT64:
                 parr[k].ints = ptr
             elif kind == M.TIME:
@@ -759,17 +642,17 @@ def validate_rows(ctx: N.Context, cols_by_name, pred, row_ids=None, nrows=None, 
 
 # ---- OrderBy with Drop / Top behind it (cph_order_rows) --------------------------------------------------------------------
 
-class Ordered:
+class Ordered(N.Owned):
     """cph_ordered: the row numbers (positions in the selection, uint32) of order[skip : skip + limit], valid until
     release().  select_used: the Top-N select ran in front of the sort; candidates: rows that entered the sort."""
+    _release_fn = "cph_ordered_release"
 
     def __init__(self, ctx, ptr):
-        self.ctx, self.ptr = ctx, ptr
+        super().__init__(ctx, ptr)
         c = ptr.contents
         self.nrows, self.mem, self.bits = int(c.nrows), int(c.mem), 32
         self.ids_ptr = int(c.ids or 0)
         self.select_used, self.candidates = bool(c.select_used), int(c.candidates)
-        ctx._children.add(self)
 
     def __len__(self):
         return self.nrows
@@ -784,19 +667,6 @@ class Ordered:
         a device column."""
         assert self.mem == N.CPH_MEM_DEVICE, "a host result is a numpy array: use to_numpy()"
         return (self.ids_ptr, 32, self.nrows)
-
-    def release(self):
-        if self.ptr:
-            self.ctx.lib.cph_ordered_release(self.ptr)
-            self.ptr = None
-
-    close = release
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
 
 
 def order_rows(ctx: N.Context, keys, nrows: int, skip: int = 0, limit=None, out_mem: int = N.CPH_MEM_HOST) -> Ordered:
@@ -839,26 +709,8 @@ def order_rows(ctx: N.Context, keys, nrows: int, skip: int = 0, limit=None, out_
                 keep += [v, st]
                 ck.values, ck.status, ck.values_mem = (v.ctypes.data, st.ctypes.data, N.CPH_MEM_HOST) if n else (None, None, N.CPH_MEM_HOST)
             keep.append(src)
-        elif isinstance(src, tuple):   # (device pointer, count)
-            if int(src[1]) < n:
-                raise ValueError(f"{type(key).__name__}: {int(src[1])} values for {n} rows")
-            ck.values, ck.values_mem = int(src[0]) or None, N.CPH_MEM_DEVICE
-        elif hasattr(src, "data_ptr"):   # a device tensor
-            want = "int64" if key.kind == N.CPH_NUM_INT64 else "float64"
-            if not str(getattr(src, "dtype", want)).endswith(want):
-                raise ValueError(f"{type(key).__name__}: the tensor's dtype is {src.dtype}, the kind wants {want}")
-            if not getattr(src, "is_cuda", True):
-                raise ValueError(f"{type(key).__name__}: a tensor source must live on the device (pass .numpy() for host values)")
-            if int(src.numel()) < n:
-                raise ValueError(f"{type(key).__name__}: {int(src.numel())} values for {n} rows")
-            keep.append(src)
-            ck.values, ck.values_mem = int(src.data_ptr()) or None, N.CPH_MEM_DEVICE
         else:
-            v = np.ascontiguousarray(np.asarray(src, dtype=dt).reshape(-1))
-            if len(v) < n:
-                raise ValueError(f"{type(key).__name__}: {len(v)} values for {n} rows")
-            keep.append(v)
-            ck.values, ck.values_mem = v.ctypes.data if len(v) else None, N.CPH_MEM_HOST
+            ck.values, ck.values_mem = N.number_source(src, key.kind, n, f"{type(key).__name__}: {{count}} values for {{need}} rows", keep)
     out = C.POINTER(N.cph_ordered)()
     ctx._check(ctx.lib.cph_order_rows(ctx.handle, arr if keys else None, len(keys), n, int(skip),
                                       N.CPH_NO_LIMIT if limit is None else int(limit), out_mem, C.byref(out)))

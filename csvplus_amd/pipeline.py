@@ -40,10 +40,11 @@ def read_table(ctx: N.Context, text: bytes, select=None, **kw) -> Table:
     """A CSV file as device columns: ingest.read_csv with its keywords (expect_header, assume_header, comma, comment,
     trim_leading_space, num_fields, lazy_quotes).  lazy_quotes=True is Reader.LazyQuotes(): header line and body are read
     by Go's lazy rules (cph_csv_parse_lazy), so a file with `5" nails` or `He said "hi"` in it reaches join_to_csv /
-    filter_to_csv / totals_to_csv like any other table.  A parse error raises ingest.CsvError."""
+    filter_to_csv / totals_to_csv like any other table.  A parse error of the body raises ingest.CsvParseError
+    (one of the header line raises ingest.CsvError, as read_csv does)."""
     t = ingest.read_csv(ctx, text, select=select, out_mem=N.CPH_MEM_DEVICE, **kw)
     if t.error_kind:
-        err = ingest.CsvError(t.error_kind, t.error_record)
+        err = ingest.CsvParseError(t.error_kind, t.error_record)
         t.release()
         raise err
     return Table(t)

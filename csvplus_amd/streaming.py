@@ -70,12 +70,7 @@ class HostEncoder:
 
     def run(self, cols, out: np.ndarray):
         """cols: the index's key columns for the chunk (host StrCols); out: uint32[nrows] (a PinnedArray's .array for overlap)."""
-        arr = (N.cph_strcol * len(cols))()
-        keep = []
-        for i, c in enumerate(cols):
-            sc, k = c.as_c()
-            arr[i] = sc
-            keep.append(k)
+        arr, keep = N._cols_array(cols)
         assert out.dtype == np.uint32 and out.flags.c_contiguous and len(out) >= cols[0].nrows
         self.ctx._check(self.lib.cph_host_encoder_run(self.handle, arr, len(cols), out.ctypes.data))
 
@@ -117,12 +112,7 @@ class StreamJoin:
 
     def submit(self, step_cols, probe_base: int = 0):
         """step_cols: the steps' key columns one after the other (one host StrCol per step in the fused mode).  Raises CphError(CPH_ERR_INVALID) when every slot is in flight."""
-        arr = (N.cph_strcol * len(step_cols))()
-        keep = []
-        for i, c in enumerate(step_cols):
-            sc, k = c.as_c()
-            arr[i] = sc
-            keep.append(k)
+        arr, keep = N._cols_array(step_cols)
         self.ctx._check(self.lib.cph_stream_join_submit(self.handle, arr, probe_base))
         self._keep.append(keep)
 

@@ -584,3 +584,29 @@ def test_fast_path_at_bench_shape(ctx):
     ctx.set_option("csv_fast", 1)
     assert res[0] == res[1]
     assert res[0][0][0] == b"".join(a) and res[0][1][0] == b"".join(b)
+
+
+BAD_BODY = b"id,name\n1,ann\n2,bob\n3,cy,extra\n"   # the header and three records; the third has one field too many
+
+
+def test_bad_body_text_has_a_good_header_and_the_oracle_names_the_record():
+    from csvplus_amd.ingest import first_record
+    assert first_record(BAD_BODY) == [b"id", b"name"]   # the header reader raises nothing
+    _, kind, record = orc.csv_parse(BAD_BODY, [0, 1])
+    assert (kind, record) == (3, 3)
+
+
+@pytest.mark.gpu
+def test_read_table_raises_the_device_parse_error(ctx):
+    """A parse error in the body is the device reader's: its kind is a CPH_CSV_ERR_* code and its record the 0-based index,
+    the header line counted; the header reader's CsvError (a kind in words, a line) is another class."""
+    from csvplus_amd import _native as N
+    from csvplus_amd import ingest, pipeline
+    with pytest.raises(ingest.CsvParseError) as e:
+        pipeline.read_table(ctx, BAD_BODY)
+    assert e.value.record == 3 and e.value.kind == N.CPH_CSV_ERR_FIELD_COUNT
+    assert "wrong number of fields" in str(e.value) and str(e.value) == "record 3: wrong number of fields"
+    assert not isinstance(e.value, ingest.CsvError) and not issubclass(ingest.CsvError, ingest.CsvParseError)
+    good = pipeline.read_table(ctx, BAD_BODY.replace(b",extra", b""))
+    assert good.nrows == 3
+    good.release()

@@ -632,3 +632,21 @@ def test_gpu_join_totals_to_csv(ctx):
     dev.release()
     pt.release()
     ot.release()
+
+
+@pytest.mark.gpu
+def test_gpu_a_device_result_is_a_child_of_its_ctx():
+    """A device-resident JoinTotals is released with its ctx; afterwards release() does not call into the library."""
+    own = N.Context(0)   # closed below: not the session's
+    ix = N.DeviceIndex(own, [StrCol.from_values([b"a", b"b", b"c"])], unique=True)
+    ch = N.join_chain(own, [(ix, [StrCol.from_values([b"b", b"a", b"b", b"c", b"b"])])], out_mem=DEVICE)
+    specs = [A.Sum(np.arange(5, dtype=np.int64), "int")]
+    t = A.join_totals(ch, 0, ix, specs, out_mem=DEVICE)
+    assert t.ngroups == 3 and t.ptr and t in own._children
+    host = A.join_totals(ch, 0, ix, specs)
+    assert host.ptr is None and host.count.tolist() == [1, 3, 1] and host.values[0].tolist() == [1, 6, 3]
+    own.close()
+    assert t.ptr is None and ch.ptr is None and own.handle is None
+    t.lib = None   # a call into the library would fail on this
+    t.release()
+    t.close()

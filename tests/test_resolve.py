@@ -436,3 +436,19 @@ def test_gpu_argument_errors_have_a_status_and_a_message(ctx):
         D.resolve_duplicates_device(ix, lambda lo, hi: lo)
     del keep, keep2
     ix.close()
+
+
+@pytest.mark.gpu
+def test_gpu_a_device_result_is_a_child_of_its_ctx():
+    """A device-resident Resolved is released with its ctx; afterwards release() does not call into the library."""
+    own = N.Context(0)   # closed below: not the session's
+    ix = N.DeviceIndex(own, [StrCol.from_values([b"a", b"b", b"a", b"c", b"b"])])
+    r = D.resolve_duplicates_device(ix, D.First(), keep_last_row=True, out_mem=DEVICE)
+    assert r.positions[1] == 3 and r.ptr and r in own._children
+    host = D.resolve_duplicates_device(ix, D.First(), keep_last_row=True)
+    assert host.ptr is None and host.positions.tolist() == [0, 2, 4]   # sorted a a b b c: the first of each run
+    own.close()
+    assert r.ptr is None and r.index.handle is None and own.handle is None
+    r.lib = None   # a call into the library would fail on this
+    r.release()
+    r.close()

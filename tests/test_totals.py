@@ -618,3 +618,20 @@ def test_gpu_totals_to_csv(ctx):
     with pytest.raises(ValueError, match="names"):
         pipeline.totals_to_csv(ctx, table, by=["cust_id"], specs=specs, names=["n"])
     table.release()
+
+
+@pytest.mark.gpu
+def test_gpu_a_device_result_is_a_child_of_its_ctx():
+    """A device-resident Totals is released with its ctx (the library wants its results released first); afterwards
+    release() does not call into the library."""
+    own = N.Context(0)   # closed below: not the session's
+    ix = N.DeviceIndex(own, [StrCol.from_values([b"a", b"b", b"a", b"c", b"b"])])
+    t = A.totals(ix, [A.Sum(np.arange(5, dtype=np.int64), "int")], out_mem=DEVICE)
+    assert t.ngroups == 3 and t.ptr and t in own._children
+    host = A.totals(ix, [A.Sum(np.arange(5, dtype=np.int64), "int")])
+    assert host.ptr is None and host.count.tolist() == [2, 2, 1] and host.values[0].tolist() == [2, 5, 3]   # released before it came back
+    own.close()
+    assert t.ptr is None and ix.handle is None and own.handle is None
+    t.lib = None   # a call into the library would fail on this
+    t.release()
+    t.close()
